@@ -11,6 +11,11 @@ forward + backward (loss -> every parameter gradient, incl. the embedding all-ga
 bucketed gradient all-reduce of segclip_amd.dist.GradSync); the optimizer step is excluded, as in
 BASELINE.json's metric definition.  --global-batch 2048 switches to SURVEY 8(d)'s strong-scaling form
 (per-GPU batch 2048/N, incl. the single-GPU B=2048 point).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything behind the timed
+region: the exact-f32 parity legs, the single-GPU B=2048 point, the text_trim line, the rocprofv3 roofline children,
+the CPU baseline and the clock / power sampler (each still subject to its --no-* switch).  --dump-outputs DIR writes
+what the last timed step returned to its caller (loss, parameter gradients) as DIR/*.npy.
 """
 import argparse
 import json
@@ -46,6 +51,12 @@ def parse():
     ap.add_argument("--spec", default="vitb16")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--full-loss", action="store_true", help="configs[3]: + superpixel-KL + MAE")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs behind the timed region (parity modes, B=2048 point, text_trim, roofline, CPU "
+                         "baseline, clock sampler); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss and parameter gradients (large ones as a fixed seeded sample) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-roofline", action="store_true")
@@ -67,7 +78,7 @@ def parse():
     ap.add_argument("--text-trim", action="store_true",
                     help="config.text_trim for the TIMED region (opt-in, off by default: the headline times the reference's full "
                          "77-token context): the causal text tower on the positions up to the batch's last EOT only - identical loss "
-                         "and gradients (tests/test_model_gpu.py); the default run reports it as the secondary field `text_trim`")
+                         "and gradients (tests/test_model_gpu.py); a --full run reports it as the secondary field `text_trim`")
     ap.add_argument("--text-after-blocks", type=int, default=-1, help="config.text_after_blocks override (launch order of the towers)")
     ap.add_argument("--wire", default="auto", choices=["auto", "bf16", "fp32"], help="gradient all-reduce wire format (auto = fp32, what the reference DDP exchanges; bf16 is an opt-in)")
     ap.add_argument("--rccl-channels", type=int, default=0,
@@ -336,6 +347,30 @@ def roofline_fallback(a, step, step_frac, work, why):
             "source": "FALLBACK: HIP events around serialised launches (towers on one stream); " + why, "step_frac": step_frac}
 
 
+DUMP_SAMPLE = 65536            # elements kept of one parameter gradient by --dump-outputs
+DUMP_BUDGET = 60 << 20         # bytes of all files of --dump-outputs together (float32 elements)
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what the timed path hands its caller after one step - the loss and every parameter gradient - as
+    out_dir/loss.npy (float64) and out_dir/grad.<parameter name>.npy (float32).  A gradient of more elements than the
+    per-tensor share of DUMP_BUDGET is written as a sorted sample of its flattened elements, drawn from a generator
+    seeded by the parameter's name: the same arguments give the same files, element for element, on any build."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array(float(loss.detach()), dtype=np.float64))
+    grads = [(n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    k = min(DUMP_SAMPLE, DUMP_BUDGET // 4 // max(1, len(grads)))
+    for name, g in grads:
+        g = g.detach()
+        if g.numel() > k:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(g.numel(), (k,), generator=gen).sort().values
+            g = g.reshape(-1)[idx.to(g.device)]
+        np.save(os.path.join(out_dir, f"grad.{name}.npy"), g.float().cpu().numpy())
+
+
 def main():
     a = parse()
     if a.cpu_baseline_worker:
@@ -428,7 +463,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     sampler = None
-    if rank == 0:   # shader clock / socket power during the timed region (a reader thread on the host; no GPU work)
+    if rank == 0 and a.full:   # shader clock / socket power during the timed region (a reader thread on the host; no GPU work)
         try:
             from tools.clock_sampler import ClockSampler, device_bus_id
             sampler = ClockSampler(device_bus_id(local_rank)).start()
@@ -450,12 +485,14 @@ def main():
     loss_val = float(loss.detach())
     ms = elapsed / a.steps * 1e3
     pairs = a.batch * world * a.steps / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, model)
 
     # ---- behind the timed region: the mode that meets north_star's 1e-3 / bit-exact bar, timed, and the
     # agreement of the benchmarked bf16 mode with it on the same inputs and the same injected noise.  Every rank runs the
     # same sequence (the steps contain the collectives); rank 0 reports.
     parity_mode = bf16_vs_f32 = gb2048 = None
-    if not a.no_parity_leg and a.dtype == "bf16" and a.spec == "vitb16":
+    if a.full and not a.no_parity_leg and a.dtype == "bf16" and a.spec == "vitb16":
         noise = synth.synthetic_noise(spec, a.batch, seed=100 + rank, device=dev)
         items = [("gumbel", noise["gumbel_main"])]
         if a.full_loss:
@@ -565,7 +602,7 @@ def main():
                 gb2048 = {"error": f"{type(e).__name__}: {str(e)[:160]}"}
 
     text_trim = None
-    if not a.no_parity_leg and a.dtype == "bf16" and a.spec == "vitb16" and not a.text_trim:
+    if a.full and not a.no_parity_leg and a.dtype == "bf16" and a.spec == "vitb16" and not a.text_trim:
         # opt-in switch, reported beside the headline (never part of it): dead positions of the causal text tower skipped
         segclip_amd.config.text_trim = True
         try:
@@ -593,7 +630,7 @@ def main():
         torch.cuda.synchronize()
 
     roofline = None
-    if not a.no_roofline and a.dtype == "bf16":
+    if a.full and not a.no_roofline and a.dtype == "bf16":
         # EVERY rank runs the op-count pass (one more step: its collectives must be matched on all ranks - ADVICE r3: with
         # rank 0 alone in it, rank 0 hung in the embedding all-gather / bucket all-reduces); only rank 0 starts the
         # rocprofv3 children, which run this rank's per-GPU workload as a single-GPU process (no collectives)
@@ -601,7 +638,7 @@ def main():
         if rank == 0:
             roofline = roofline_block(a, step, pairs / world, world, work, collective_free=world == 1)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline()
     if rank == 0:
         mname = MODEL_NAME.get(a.spec, a.spec)

@@ -178,7 +178,8 @@ def test_bench_script_two_ranks_end_to_end():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
-                         "--spec", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-traffic", "--no-cpu-baseline"],
+                         "--spec", "tiny", "--batch", "4", "--steps", "2", "--warmup", "1", "--full", "--no-traffic",
+                         "--no-cpu-baseline"],
                         cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]

@@ -7,14 +7,14 @@
 TAG=${1:-r03}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 F='^RCCL\|^HIP\|^ROCm\|Hostname\|Librccl\|amdgpu.ids\|socket.cpp\|ProcessGroupNCCL'
-SEGCLIP_BENCH_PROFILE_DIR=$OUT/rl timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
+SEGCLIP_BENCH_PROFILE_DIR=$OUT/rl timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err
 cp $OUT/rl/kernel_stats.txt $OUT/kernel_stats.txt
 cp $OUT/rl/intervals.json $OUT/bench_intervals.json 2>/dev/null
 DB=$(ls $OUT/rl/trace/*.db $OUT/rl/trace/*/*.db 2>/dev/null | head -1)
 python tools/stream_gaps.py $DB 120 > $OUT/stream_gaps.txt 2>&1
 python tools/stream_breakdown.py $DB 6 3 > $OUT/stream_breakdown.txt 2>&1
 rm -rf $OUT/rl/trace $OUT/rl/pmc_*
-b() { local name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "$name: $(grep -o '"ms_per_step": [0-9.]*' $OUT/bench_$name.json) $(grep -o '"value": [0-9.]*' $OUT/bench_$name.json | head -1)"; }
+b() { local name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "$name: $(grep -o '"ms_per_step": [0-9.]*' $OUT/bench_$name.json) $(grep -o '"value": [0-9.]*' $OUT/bench_$name.json | head -1)"; }
 b gb2048 --no-cpu-baseline --no-traffic --no-parity-leg --global-batch 2048 --steps 5 --warmup 2
 b full_loss --no-cpu-baseline --no-traffic --no-parity-leg --full-loss
 b resid_bf16 --no-cpu-baseline --no-roofline --no-parity-leg --resid bf16

@@ -20,7 +20,7 @@ def last_json(path):
 line = last_json(R + "bench_line.json")
 json.dump(line, open(P + "bench_line.json", "w"), indent=1)
 hdr = ("# Kernel table of the rocprofv3 child that bench.py's roofline block is computed from (tools/profile_round.sh %s:\n"
-       "#   SEGCLIP_BENCH_PROFILE_DIR=... python bench.py --steps 20 --warmup 5  ->  profiles/%s_bench_line.json, same run).\n"
+       "#   SEGCLIP_BENCH_PROFILE_DIR=... python bench.py --full --steps 20 --warmup 5  ->  profiles/%s_bench_line.json, same run).\n"
        "# 6 model passes of the child are in the trace; ms/step = total_ms / 6.  at::cuda::spin_kernel = the stream-overlap probe\n"
        "# of segclip_amd/streams.py (once per process, not step work).  Step time of the (unprofiled) parent: %.3f ms.\n"
        "# gemm_bf16_pq_kernel<A_KS,B_KS,MODE>: <0,0,*> forward (0 plain, 2 QuickGELU + one-byte derivative, 5 + fp32 residual),\n"
@@ -56,7 +56,7 @@ for n, desc in (("gb2048", "--global-batch 2048 (SURVEY 8d strong-scaling base o
     if not os.path.exists(R + f"bench_{n}.json"):
         continue
     d = last_json(R + f"bench_{n}.json")
-    cfg[n] = {"command": "python bench.py --no-cpu-baseline " + desc, "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"],
+    cfg[n] = {"command": "python bench.py --full --no-cpu-baseline " + desc, "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"],
               "config": d["config"], "roofline": d.get("roofline"), "clocks": d.get("clocks")}
 json.dump(cfg, open(P + "bench_configs.json", "w"), indent=1)
 txt = ("# rocprofv3 --pmc passes (counters only; one counter group per run) on single GEMM shapes of the shipped 8-phase kernel\n"
