@@ -10,8 +10,6 @@ compute_dtype : torch.float32  -> exact-f32 MFMA kernels (parity gate: 1e-3 on l
 cross_mode    : "t18"      torch-1.8 key-buffer reinterpretation of CrossAttentionBlock (what the
                            published recipe trained with; SURVEY.md finding 0.4)
                 "intended" each sample attends to its own tokens
-overlap_wgrad : weight-gradient GEMMs of a block on a second HIP stream; measured SLOWER (64.4 vs 59.5 ms/step:
-                two 139-KiB-LDS GEMMs cannot share a CU and the interleaving delays the dgrad chain), kept off
 overlap_towers: enqueue the text tower on a second HIP stream (concurrent with the vision tower)
 text_after_blocks : with overlap_towers: the text tower is enqueued after this many vision blocks (host launch order;
                 0 = before the vision tower).  The host needs ~3 ms to enqueue the text tower: queued first, the vision
@@ -45,12 +43,6 @@ aux_u8        : bf16 mode: the towers keep QuickGELU'(u) for the backward as ONE
 fused_head    : training forward: max-token pooling + ln_post + projection on the pooled row only, and the contrastive head
                 (L2-normalise, all-gather, logits, both cross entropies) as ONE autograd node (ops.ClipLossFn) - ~15 instead
                 of ~90 launches between the last forward GEMM and the first backward GEMM; False: the op-by-op path
-reduce_side   : inside ResStackFn's backward the blocks' trailing reductions (split-K combines of the weight gradients, the
-                LayerNorm / bias column sums - HBM-bound, off the data-gradient chain) run on a side stream beside the next
-                block's GEMMs and are joined once per stack (not with GradSync's bucket slots).  MEASURED SLOWER and off: 51.9 vs
-                41.9 ms per step - with two more active streams the runtime maps the text tower's stream onto the main
-                stream's hardware queue and the towers run one after the other (the effect DESIGN.md 6 "hardware queues"
-                describes)
 text_trim     : training fast path of the text tower (CLIP.encode_text_eot): run the causal tower on the first L tokens only,
                 L = the batch's largest EOT position + 1.  The tower is causal and only the EOT row reaches the loss, so the
                 positions behind a caption's EOT influence neither the loss nor any gradient (their rows of every weight
@@ -109,8 +101,8 @@ def tuning_env(name, default):
     return v
 
 
-_DEFAULTS = dict(compute_dtype=torch.float32, f32_split=False, c_exec=tuning_env("SEGCLIP_C_EXEC", "1") != "0", cross_mode="t18", overlap_wgrad=False, overlap_towers=True,
-                 trust_weight_shadows=False, attn_fp8=False, fuse_res_stack=True, bf16_resgrad=True, bf16_resid=False, fused_head=True, reduce_side=False,
+_DEFAULTS = dict(compute_dtype=torch.float32, f32_split=False, c_exec=tuning_env("SEGCLIP_C_EXEC", "1") != "0", cross_mode="t18", overlap_towers=True,
+                 trust_weight_shadows=False, attn_fp8=False, fuse_res_stack=True, bf16_resgrad=True, bf16_resid=False, fused_head=True,
                  aux_u8=tuning_env("SEGCLIP_AUX_U8", "1") != "0",
                  text_after_blocks=3, text_trim=False, text_trim_hint=None, pad_rows=tuning_env("SEGCLIP_PAD_ROWS", "1") != "0", fold_param_grads=tuning_env("SEGCLIP_FOLD_GRADS", "1") != "0",
                  wgrad_group_blocks=int(tuning_env("SEGCLIP_WGRAD_GROUP", "12")), wgrad_group_blocks_dist=int(tuning_env("SEGCLIP_WGRAD_GROUP_DIST", "12")))

@@ -389,16 +389,6 @@ static int choose_splits(const segclip_gemm_desc* d) {
   if (d->bias || d->residual || d->aux || d->act != SEGCLIP_ACT_NONE || d->mul_dact) return 1;
   const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * (d->nb2 > 0 ? d->nb2 : 1);
   const int64_t ksteps = cdiv(d->K, BK);
-  static const int force_tile = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  if (want_dma(d) && force_tile == 128) {
-    // 128x128 tiles, two workgroups per CU: one round = 512 workgroups
-    const int64_t tiles = cdiv(d->M, 128) * cdiv(d->N, 128) * nb;
-    if (tiles >= 320 || ksteps < 32) return 1;
-    int64_t s = 512 / tiles;
-    if (s > ksteps / 8) s = ksteps / 8;
-    if (s > 32) s = 32;
-    return s < 1 ? 1 : (int)s;
-  }
   if (want_dma(d)) {
     // 256-row tiles, long K loops: aim at one full round of the 256 CUs
     const int64_t bn = d->N > 128 ? 256 : 128;
@@ -417,15 +407,9 @@ static int choose_splits(const segclip_gemm_desc* d) {
   return s < 1 ? 1 : (int)s;
 }
 
-size_t segclip_gemm_bf16_pq_tail_ws_bytes(const segclip_gemm_desc* d);
 size_t segclip_gemm_bf16_ws_bytes(const segclip_gemm_desc* d) {
   const int s = choose_splits(d);
-  if (s <= 1) {
-    // no split-K: the tail split of gemm_bf16_pq.hip may want a workspace (bf16 / fp32-residual outputs on full 256-tiles)
-    if (want_dma(d) && d->sak == 1 && (d->c_dtype == SEGCLIP_BF16 || (d->c_dtype == SEGCLIP_F32 && d->residual)))
-      return segclip_gemm_bf16_pq_tail_ws_bytes(d);
-    return 0;
-  }
+  if (s <= 1) return 0;
   const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * (d->nb2 > 0 ? d->nb2 : 1);
   return (size_t)s * nb * d->M * d->N * sizeof(float);
 }
@@ -465,9 +449,8 @@ int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream) {
   if (g.splits > 1) g.splits = (int)cdiv(d->K, g.kper);
   g.slab = (float*)d->ws;
   g.vec_epi = 0;
-  g.touch = 0;
+  g.stagger = 0;
   g.abl = 0;
-  g.colgroups = 1;
   static const int xw_epi = [] { const char* e = segclip_tuning_env("SEGCLIP_EPI_XW"); return e ? atoi(e) : 2; }();
   g.xw_epi = xw_epi;
   static const int slab_staged = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_SLAB_STAGED"); return e ? atoi(e) : 1; }();
@@ -491,12 +474,9 @@ int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream) {
       return SEGCLIP_ERR_UNSUPPORTED;
     }
   } else if (want_dma(d)) {
-    static const int force_tile = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_TILE"); return e ? atoi(e) : 0; }();
-    // 256x256 tiles: the phase-pipelined kernel (gemm_bf16_p8.hip); 256x128 / 128x128 tiles: the one-barrier-per-K-tile
-    // kernel (gemm_bf16_dma.hip)
-    // 256x256 tiles, bf16 output, full tiles, no split-K: the persistent kernel with the overlapped output path
-    // (gemm_bf16_pq.hip); else the phase-pipelined one-tile-per-workgroup kernel (gemm_bf16_p8.hip)
-    if (force_tile == 0 && segclip_gemm_bf16_dma_pick_bn(d, nb * g.splits) == 256) {
+    // 256x256 tiles: the accumulator-register kernel (gemm_bf16_pq.hip) where it takes the problem, else the
+    // phase-pipelined kernel (gemm_bf16_p8.hip); 256x128 / 128x128 tiles: the one-barrier-per-K-tile kernel (gemm_bf16_dma.hip)
+    if (segclip_gemm_bf16_dma_pick_bn(d, nb * g.splits) == 256) {
       launched = segclip_gemm_bf16_pq_try(d, &g, g.splits, nb, stream);
       if (!launched) launched = segclip_gemm_bf16_p8_try(d, &g, g.splits, g.kper, nb, stream);
     }

@@ -15,9 +15,8 @@ struct Args {
   int splits; int64_t kper; float* slab;  // split-K: raw fp32 partial tiles go to slab[s][z][M][N]
   float* colsum_part;  // optional [M/64][N] fp32 partial column sums of the stored output (LDS epilogue only)
   int vec_epi;  // host-checked: every C / aux / residual / bias access of a full tile may be a 16-byte vector
-  int colgroups; // 8-phase kernel: column groups of the tile order (see the kernel); 1 = plain row-major
   int abl;      // 8-phase kernel, timing experiments (SEGCLIP_P8_EPI_ABL): 1 = no epilogue (results garbage)
-  int touch;    // 8-phase kernel: pre-touch the epilogue's side tile (SEGCLIP_P8_TOUCH, default on)
+  int stagger;  // 8-phase kernel: cap in cycles of the first round's stagger unit (SEGCLIP_P8_STAGGER); 0 = off
   int aux_kind; // 0: aux = pre-activation u (stored by EPI_ACT, differentiated by EPI_DACT); 1: aux = act'(u);
                 // 2: aux = act'(u) as one byte per element (staged epilogue only, see EPI_ACT8)
   int slab_staged; // 8-phase kernel: split-K partial tiles through the staged epilogue (SEGCLIP_P8_SLAB_STAGED)
@@ -450,7 +449,7 @@ __device__ __forceinline__ void epilogue_lds2(const Args& g, const f32x16 (&acc0
 #endif
   if (sizeof(CT) == 4 && !EPI_F32_OVERLAP) {
     // fp32 side operands are 64 VGPRs per sub-tile: with the second sub-tile's accumulators still live there is no room
-    // for both, so the sub-tiles run one after the other (their side tile was touched into L2 / MALL at kernel start)
+    // for both, so the sub-tiles run one after the other
     epilogue_lds<CT, MODE, NSPLIT>(g, acc0, t, mw0, nw, lane, coff, roff);
     __builtin_amdgcn_wave_barrier();
     epilogue_lds<CT, MODE, NSPLIT>(g, acc1, t, mw1, nw, lane, coff, roff);

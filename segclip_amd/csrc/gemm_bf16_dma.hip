@@ -87,19 +87,10 @@ __device__ __forceinline__ bf16x8_t frag_ks(const char* lds, int rbase, int kc, 
   return __builtin_bit_cast(bf16x8_t, r);
 }
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
 // <BM, BN, NWV>: <256,256,8> and <256,128,8> own a CU (139 KiB of LDS: operand ring / epilogue patches);
 // <128,128,4> (waves 2x2, 64x64 each) needs 68 KiB, so two workgroups share a CU and one's output phase overlaps
 // the other's MFMA phase.
-template <bool A_KS, bool B_KS, int BM, int BN, int NWV, int STAGES = 2>
+template <bool A_KS, bool B_KS, int BM, int BN, int NWV>
 __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kernel(Args g) {
   constexpr int SZA = BM * BK * 2;
   constexpr int SZB = BN * BK * 2;
@@ -109,7 +100,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
   constexpr int TM = BM / (WM * 32);                   // 32-row MFMA tiles per wave along m
   constexpr int WROWS = TM * 32;                       // rows per wave
   static_assert(TM == 2 || TM == 4, "wave tile must be 64x64 or 128x64");
-  constexpr int LDS_BYTES = STAGES * SZS > NWV * EPI_WAVE_BYTES ? STAGES * SZS : NWV * EPI_WAVE_BYTES;
+  constexpr int LDS_BYTES = 2 * SZS > NWV * EPI_WAVE_BYTES ? 2 * SZS : NWV * EPI_WAVE_BYTES;   // two-stage operand ring
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
   const int nk = (int)((kend - kbeg) / BK);
 
   auto issue = [&](int t) {
-    char* la = smem + (t % STAGES) * SZS;
+    char* la = smem + (t % 2) * SZS;
     char* lb = la + SZA;
     const int64_t k0 = kbeg + (int64_t)t * BK;
     if constexpr (A_KS) issue_ks<BM, NWV>(A, g.lda, m0, g.M, k0, la, wave, lane);
@@ -158,18 +149,12 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
     while (clock64() - t0 < wait) __builtin_amdgcn_s_sleep(32);
   }
   issue(0);
-  if constexpr (STAGES == 3) {
-    if (nk > 1) issue(1);
-  }
-  constexpr int DMA_PER_STAGE = (BM + BN) / (8 * NWV);  // DMA instructions per wave and k-tile
   for (int t = 0; t < nk; ++t) {
-    // this wave's share of tile t has landed (with three stages the DMA of tile t+1 may still be in flight)
-    if (STAGES == 3 && t + 1 < nk) wait_vm<DMA_PER_STAGE>();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                       // ... and everybody else's; buffer (t-1)%STAGES is free
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of tile t has landed
+    __builtin_amdgcn_s_barrier();                       // ... and everybody else's; buffer (t-1)%2 is free
     __builtin_amdgcn_sched_barrier(0);
-    if (t + STAGES - 1 < nk) issue(t + STAGES - 1);
-    const char* la = smem + (t % STAGES) * SZS;
+    if (t + 1 < nk) issue(t + 1);
+    const char* la = smem + (t % 2) * SZS;
     const char* lb = la + SZA;
     // fragments of k16-chunk kc+1 are requested before the MFMAs of chunk kc (register double buffer)
     bf16x8_t fa[2][TM], fb[2][2];
@@ -257,23 +242,13 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
 #ifndef DMA_PART
 #error "compile with -DDMA_PART=0..4 (see build.sh)"
 #endif
-// variant: 0 = 256x128 tile, 1 = 256x256 tile, 2 = 128x128 tile / 4 waves, 3 = 256x128 tile with a 3-stage ring (2, 3:
-// only with -DSEGCLIP_GEMM_EXPERIMENTS)
-#ifdef SEGCLIP_GEMM_EXPERIMENTS
-#define DMA_EXP(AK, BKS)                                                                                        \
-  if (variant == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>), grid, dim3(256), 0, stream, g);      \
-  else if (variant == 3) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8, 3>), grid, dim3(512), 0, stream, g); \
-  else
-#else   // production: the 128x128 / 4-wave tile for problems too small to fill the chip with 256-row tiles (round 4)
-#define DMA_EXP(AK, BKS)                                                                                        \
-  if (variant == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>), grid, dim3(256), 0, stream, g);      \
-  else
-#endif
+// variant: 0 = 256x128 tile, 1 = 256x256 tile, 2 = 128x128 tile / 4 waves (problems too small to fill the chip with
+// 256-row tiles)
 #define DMA_LAUNCHER(NAME, AK, BKS)                                                                             \
   void NAME(int variant, dim3 grid, hipStream_t stream, const void* args) {                                     \
     const Args g = *reinterpret_cast<const Args*>(args);                                                        \
-    DMA_EXP(AK, BKS)                                                                                            \
-    if (variant == 1) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 256, 8>), grid, dim3(512), 0, stream, g); \
+    if (variant == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>), grid, dim3(256), 0, stream, g); \
+    else if (variant == 1) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 256, 8>), grid, dim3(512), 0, stream, g); \
     else hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8>), grid, dim3(512), 0, stream, g);       \
   }
 #if DMA_PART == 0
@@ -324,24 +299,15 @@ bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, in
   // overlaps the MFMA phase of the other.  In isolation (tools/bench_gemm.py, MI355X) this wins 10-25 % on the
   // forward GEMMs with fewer than 4 rounds of 256x256 tiles (N=768 of the vision tower, the whole text tower) and
   // loses 5-15 % on long-K dgrads and every split-K wgrad; inside the training step (text tower concurrent on a
-  // second stream) a shape-based choice measured 58.4 vs 58.2 ms, i.e. no gain, so the 256-wide tiles stay the
-  // default and SEGCLIP_GEMM_TILE=128 selects this variant for experiments.
+  // second stream) a shape-based choice measured 58.4 vs 58.2 ms, i.e. no gain, so the 256-wide tiles stay the default.
   // Round 4: problems whose 256-row tiles cannot fill the 256 CUs (the center stage's q-side linears: M = 8 B = 2048 rows,
   // 48-192 tiles) take the 128x128 tile: four times the workgroups, two per CU, half the K-loop time per tile
   // (SEGCLIP_GEMM_SMALL_TILES=0 switches the rule off; a forward + backward pass of the center stage: see DESIGN 4.4).
   static const int small_rule = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_SMALL_TILES"); return e ? atoi(e) : 1; }();
   const int bn_big = pick_bn(d, nb * splits);
-  const bool auto_small = small_rule && d->M >= 128 && d->N >= 128 && !(d->aux_kind == 2 && d->aux) && !g.colsum_part &&
-                          cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256;
-#ifdef SEGCLIP_GEMM_EXPERIMENTS  // build.sh -DSEGCLIP_GEMM_EXPERIMENTS: the 3-stage-ring instances (+ hipcc time)
-  static const int force_tile = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_TILE"); return e ? atoi(e) : 0; }();
-  const bool small = force_tile == 128 || (force_tile == 0 && auto_small);
-  const bool three = force_tile == 3;  // experiment: 256x128 tiles with a 3-stage ring (96 KiB in flight)
-#else
-  const bool small = auto_small;
-  constexpr bool three = false;
-#endif
-  const int bn = (small || three) ? 128 : bn_big;
+  const bool small = small_rule && d->M >= 128 && d->N >= 128 && !(d->aux_kind == 2 && d->aux) && !g.colsum_part &&
+                     cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256;
+  const int bn = small ? 128 : bn_big;
   const int bm = small ? 128 : 256;
   g.nbx = (int)cdiv(d->N, bn);
   g.nby = (int)cdiv(d->M, bm);
@@ -364,7 +330,7 @@ bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, in
       return false;
   }
   dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
-  const int variant = small ? 2 : three ? 3 : bn == 256 ? 1 : 0;
+  const int variant = small ? 2 : bn == 256 ? 1 : 0;
   if (!a_ks && !b_ks) segclip_dma_launch_ff(variant, grid, stream, &g);
   else if (!a_ks && b_ks) segclip_dma_launch_fk(variant, grid, stream, &g);
   else if (a_ks && b_ks) segclip_dma_launch_kk(variant, grid, stream, &g);

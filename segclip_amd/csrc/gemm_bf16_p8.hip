@@ -141,7 +141,7 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 template <bool A_KS, bool B_KS, int ABL = 0>
 __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   constexpr int LDS_BYTES = RING > NWV * EPI_WAVE_BYTES ? RING : NWV * EPI_WAVE_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + 256];   // + junk slot of the side-tile touches
+  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -153,24 +153,8 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int unit_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   const int wg = unit_id % nt, ksplit = unit_id / nt;
-  // Tile order inside the sequence that is cut into the 8 XCD chunks.  Default: row-major over all nbx column tiles.
-  // Experiment (g.colgroups = G > 1): the sequence walks column group 0 (all rows, its nbx/G columns, row-major), then
-  // group 1, ...: an XCD's chunk lies in one group (or two), its weight working set is 1/G of W; every A slab is read by
-  // G XCDs instead of one.  Hypothesis: row-major makes every XCD sweep the whole weight matrix once per round of its 32
-  // workgroups while the A slabs stream through the same 4-MiB L2 (the weights cost more K-loop time than the
-  // activations, tools/debug/gemm_latency_probe.py).  Measured: no gain (see the dispatcher).
-  int tcol, trow;
-  {
-    const int G = g.colgroups;
-    if (G <= 1) {
-      tcol = wg % g.nbx; trow = wg / g.nbx;
-    } else {
-      const int cq = g.nbx / G, cr = g.nbx % G;      // the first cr groups have cq + 1 columns
-      int rem = wg, c0 = 0, gi = 0, w = cq + (cr > 0 ? 1 : 0);
-      while (gi + 1 < G && rem >= w * g.nby) { rem -= w * g.nby; c0 += w; ++gi; w = cq + (gi < cr ? 1 : 0); }
-      tcol = c0 + rem % w; trow = rem / w;
-    }
-  }
+  // Tile order inside the sequence that is cut into the 8 XCD chunks: row-major over all nbx column tiles.
+  const int tcol = wg % g.nbx, trow = wg / g.nbx;
   const int64_t n0 = (int64_t)tcol * BT, m0 = (int64_t)trow * BT;
   const int64_t z = blockIdx.z, z1 = z / g.nb2, z2 = z % g.nb2;
   const bf16_t* A = reinterpret_cast<const bf16_t*>(g.A) + z1 * g.bsA1 + z2 * g.bsA2;
@@ -210,36 +194,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     else dma16x2(baseB + (int64_t)t * stepB, offB[u - 2][0], offB[u - 2][1], dst);
   };
 
-  // EXPERIMENT, off by default (SEGCLIP_P8_TOUCH=1): side tile of the epilogue (saved activation of the act' dgrad, or
-  // the residual): every 64-byte sector of the tile's 256 rows is touched once now by a 4-byte LDS-DMA into a junk LDS
-  // slot (no VGPR destination), so that the lines travel HBM -> MALL/L2 while the K loop runs.  The touches are the
-  // oldest entries of the in-order VM queue: the first counted wait of the prologue covers them.  Measured on MI355X
-  // (tools/bench_epi.py, M = 50176): SLOWER - out_proj +fp32 residual 89.8 -> 114.1 us, c_proj +residual 253 -> 268,
-  // act' dgrad 326 -> 340: the epilogue is not waiting for the latency of these loads.
-  if ((g.touch & 1) && g.splits == 1 && (g.mul_dact || g.residual) && n0 + BT <= g.N) {
-    const int esz = g.mul_dact ? (g.c_dtype == SEGCLIP_BF16 ? 2 : 4) : (g.r_dtype == SEGCLIP_BF16 ? 2 : 4);
-    const int64_t pitch = (g.mul_dact ? g.ldaux : g.ldr) * esz;
-    const char* sp = g.mul_dact ? reinterpret_cast<const char*>(g.aux) + (coff + m0 * g.ldaux + n0) * esz
-                                : reinterpret_cast<const char*>(g.residual) + (roff + m0 * g.ldr + n0) * esz;
-    const int spr_log = esz == 2 ? 3 : 4;               // 64-byte sectors per tile row: 8 (bf16) / 16 (fp32)
-    const int total = BT << spr_log;
-    const int64_t rmax = g.M - 1 - m0;
-    const uint32_t junk = (uint32_t)(uintptr_t)((lds_void*)smem) + LDS_BYTES;
-    for (int sidx = tid; sidx < total; sidx += NWV * 64) {
-      int64_t row = sidx >> spr_log;
-      row = row < rmax ? row : rmax;
-      const uint32_t off = (uint32_t)(row * pitch + ((sidx & ((1 << spr_log) - 1)) << 6));
-      asm volatile(
-          "s_nop 4\n\t"
-          "s_mov_b32 m0, %2\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dword %0, %1"
-          :
-          : "v"(off), "s"(sp), "s"(junk)
-          : "memory");
-    }
-  }
-
   f32x16 acc[2][2][2];  // [A half][32-row tile][B half]
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -252,9 +206,9 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
 
   // The first round of workgroups (one per CU) starts with a bounded, staggered delay so that the CUs do not all reach
   // their store phase at the same moment in every later round (kept from gemm_bf16_dma.hip, where it measured +5..10 %).
-  if (!(g.touch & 2) && bid < 256 && gridDim.x * gridDim.y * gridDim.z > 256) {
+  if (g.stagger > 0 && bid < 256 && gridDim.x * gridDim.y * gridDim.z > 256) {
     const long long t_tile = (long long)nk * 3000 + 20000;
-    const long long cap = (long long)(g.touch >> 2);          // first-round stagger unit cap in cycles (default 2000)
+    const long long cap = (long long)g.stagger;
     const long long unit = t_tile / 8 < cap ? t_tile / 8 : cap;
     // tiles of one block row share their A rows through the XCD's L2: they get the SAME delay and stay in lockstep
     const long long wait = (trow & 7) * unit;
@@ -538,19 +492,12 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
   // 32-bit DMA offsets: 256 rows (or 64 k-rows) of the leading dimension must stay below 4 GiB
   if ((a_ks ? 64 : 256) * (a_ks ? d->sak : d->sam) * 2 >= (int64_t)1 << 31) return false;
   if ((b_ks ? 64 : 256) * (b_ks ? d->sbk : d->sbn) * 2 >= (int64_t)1 << 31) return false;
-  static const int touch = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_TOUCH"); return e ? atoi(e) : 0; }();   // measured slower (see the kernel)
   static const int stagger = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_STAGGER"); return e ? atoi(e) : 2000; }();   // unit cap in cycles; 0 = off.  In the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
   static const int epi_abl = segclip_ablation_env("SEGCLIP_P8_EPI_ABL");
   g.abl = epi_abl;
-  g.touch = (touch ? 1 : 0) | (stagger > 0 ? 0 : 2) | (stagger << 2);   // bit 0: side-tile touch experiment, bit 1: no first-round stagger
+  g.stagger = stagger;
   g.nbx = (int)cdiv(d->N, BT);
   g.nby = (int)cdiv(d->M, BT);
-  // column groups of the tile order (experiment, SEGCLIP_P8_COLGROUPS = 2..4; default 1 = row-major): measured at
-  // M = 50176 (tools/bench_epi.py): within +-3 % of row-major on every shape (N = 3072: -4 % with 3 groups; N = 768 with
-  // 3 groups loses the A sharing: +18 %) - the weight refetch model in the kernel comment is not what bounds the K loop
-  static const int cg_env = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_COLGROUPS"); return e ? atoi(e) : 0; }();
-  g.colgroups = splits > 1 ? 1 : (cg_env > 0 ? cg_env : 1);
-  if (g.colgroups > g.nbx) g.colgroups = g.nbx;
   g.splits = splits;
   g.kper = kper;
   {

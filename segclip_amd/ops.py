@@ -86,30 +86,15 @@ class ReduceQueue:
         self.keep.append(part)
         self.keep.extend(o for o in outs if o is not None)
 
-    def flush(self, side=None):
-        """side: a HIP stream the reductions are enqueued on instead of the current one (they are HBM-bound and feed nothing
-        in the data-gradient chain: beside the next block's GEMMs they cost almost nothing); the caller joins it before
-        anything reads the reduced gradients."""
+    def flush(self):
         lib = L.load()
         if not self.slabs and not self.rows:
             return
-        main = torch.cuda.current_stream() if side is not None else None
-        if side is not None:
-            side.wait_stream(main)               # the partials were produced on the current stream
-
-        def launch():
-            for kind, ents in ((L.REDUCE_SLABS, self.slabs), (L.REDUCE_ROWS, self.rows)):
-                for i in range(0, len(ents), L.REDUCE_MAX):
-                    chunk = ents[i:i + L.REDUCE_MAX]
-                    arr = (L.ReduceEntry * len(chunk))(*chunk)
-                    L.check(lib.segclip_reduce_multi(arr, len(chunk), kind, L.stream()), "reduce_multi")
-        if side is None:
-            launch()
-        else:
-            with torch.cuda.stream(side):
-                launch()
-            for t in self.keep:                  # workspaces / outputs stay allocated until the side stream has used them
-                t.record_stream(side)
+        for kind, ents in ((L.REDUCE_SLABS, self.slabs), (L.REDUCE_ROWS, self.rows)):
+            for i in range(0, len(ents), L.REDUCE_MAX):
+                chunk = ents[i:i + L.REDUCE_MAX]
+                arr = (L.ReduceEntry * len(chunk))(*chunk)
+                L.check(lib.segclip_reduce_multi(arr, len(chunk), kind, L.stream()), "reduce_multi")
         self.slabs, self.rows, self.keep = [], [], []
 
 
@@ -196,10 +181,6 @@ def _wgrad_group_plan(nblk, tiles_blk, ksteps, gmax):
     return best[nblk][1]
 
 
-_PQ_TAIL_ENV = _tenv("SEGCLIP_PQ_TAIL", "0") not in ("", "0")
-_SHARED_RQ = _tenv("SEGCLIP_SHARED_RQ", "1") != "0"   # A/B: one reduce queue per weight-gradient group (1) or per block (0)
-
-
 def _empty(shape, dtype, like):
     return torch.empty(shape, dtype=dtype, device=like.device)
 
@@ -271,10 +252,10 @@ def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=No
             flags |= L.GEMM_DEFER_COLSUM
             defer.add_rows(csws, M // 64, N, N, (colsum,), N)
     ws = None
-    # a workspace exists only for split-K (no epilogue operands) - or, with the tail-split experiment switched on, for any GEMM:
-    # skip the query call on the ~60 % of launches that can never have one (host time: the step is ~800 launches)
+    # a workspace exists only for split-K (no epilogue operands): skip the query call on the ~60 % of launches that can never
+    # have one (host time: the step is ~800 launches)
     nbytes = (lib.segclip_gemm_ws_bytes(C.byref(d))
-              if (_PQ_TAIL_ENV or (bias is None and residual is None and aux is None and act == ACT_NONE and not mul_dact)) else 0)
+              if (bias is None and residual is None and aux is None and act == ACT_NONE and not mul_dact) else 0)
     if nbytes:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
         d.ws, d.ws_bytes = L.ptr(ws), nbytes
@@ -583,23 +564,6 @@ def p_attn_bwd(d, stats, do, dq, dk, dv, dqs, dks, dvs, dos, dq_off=0, dk_off=0,
         fl = 10.0 * d.B * d.H * d.Tq * d.Tk * d.hd * (0.5 if d.causal else 1.0)
         _OpCount.add("attn_bwd", fl, 2.0 * d.B * d.H * d.hd * (4 * d.Tq + 4 * d.Tk))
     L.check(lib.segclip_attn_bwd(C.byref(d), L.stream()), "attn_bwd")
-
-
-def _wgrad_stream():
-    from . import streams
-    return streams.side_stream("wgrad")
-
-
-def _reduce_stream():
-    """side stream for a tower's trailing reductions (one per tower: keyed by the stream the tower's backward runs on)"""
-    from . import streams
-    return streams.side_stream("reduce:%x" % torch.cuda.current_stream().cuda_stream)
-
-
-# config.overlap_wgrad experiments (read once): SEGCLIP_WGRAD_JOIN=stack joins the weight-gradient stream once per
-# ResStackFn backward instead of once per block (the tensors it reads are kept alive until then); the stream's priority
-# comes from SEGCLIP_WGRAD_PRIO (segclip_amd/streams.py)
-_WGRAD_JOIN_STACK = _tenv("SEGCLIP_WGRAD_JOIN", "block") == "stack"
 
 
 def interp_pos_table(table, h, w):
@@ -1051,8 +1015,7 @@ def _aux_kind(act_dtype, act, M=0, N=0):
     return 0
 
 
-def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, overlap_wgrad=False, keep=None, reduce_side=None,
-                  wgroup=None, rqueue=None):
+def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, wgroup=None, rqueue=None):
     """Hand-scheduled backward of one block.  g: fp32 (M, D) gradient of the block output or None; g16: its bf16 copy or
     None.  need[i]: gradient wanted for forward input i (0 = x, 1..12 = the parameters in forward order).
     chain=False: fp32 residual gradient in and out (plus the bf16 copy the LayerNorm backward emits for free).
@@ -1072,39 +1035,21 @@ def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, overlap
         g16 = g
     res_in = g16 if chain else g
     rdt = act_dtype if chain else torch.float32
-    # The weight gradients do not feed the data-gradient chain: optionally (config.overlap_wgrad) they are enqueued
-    # on a second HIP stream.
-    # (the switch is captured at FORWARD time: backward runs on the autograd thread, after config.scope() has exited)
-    main = torch.cuda.current_stream()
-    side = _wgrad_stream() if overlap_wgrad else None
     sq, so, sf, sp = gslots  # weight gradients land directly in their all-reduce bucket (segclip_amd/dist.py)
     F4 = wfc_c.shape[0]
     s_ln1w, s_ln1b, s_bqkv, s_bo, s_ln2w, s_ln2b, s_bfc, s_bpr = vslots   # ... and so do the 8 vector gradients
 
-    def on_side(fn, *deps):
-        if side is None:
-            return fn()
-        side.wait_stream(main)           # operands produced on the main stream are ready
-        with torch.cuda.stream(side):
-            out = fn()
-        if out is not None:
-            out.record_stream(main)
-        return out
-
     # the block's trailing reductions (split-K combines, LayerNorm / bias column sums) are queued and flushed as two
-    # launches at the end of the block (not when the weight gradients run on the side stream)
+    # launches at the end of the block
     # rqueue (ResStackFn with grouped weight gradients): the caller's queue - the trailing reductions of all blocks of a group
     # are flushed together (2 launches per 16 entries instead of 2 per block)
-    own_rq = rqueue is None or side is not None
-    rq = (ReduceQueue() if side is None else None) if own_rq else rqueue
-    if side is not None:
-        wgroup = None
+    rq = ReduceQueue() if rqueue is None else rqueue
 
     def wgrad(dy_, x_, out_):
         # wgroup (ResStackFn): the weight gradients of several blocks run later, as one grouped launch (WgradGroup)
         if wgroup is not None:
             return wgroup.add(dy_, x_, out_)
-        return on_side(lambda: p_wgrad(dy_, x_, out=out_, defer=rq))
+        return p_wgrad(dy_, x_, out=out_, defer=rq)
     # ---- MLP
     du, dbfc = p_dgrad(g16, wpr_c, act_dtype, aux=u, act=act, want_colsum=True,
                        colsum_out=_slot_out(s_bfc, (F4,)) if need[10] else None,
@@ -1136,25 +1081,20 @@ def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, overlap
     dbqkv = None
     if need[4]:
         bq_out = _slot_out(s_bqkv, (3 * D,))
-        if part is not None and rq is not None and (bq_out is None or bq_out.data_ptr() % 16 == 0):
+        if part is not None and (bq_out is None or bq_out.data_ptr() % 16 == 0):
             # in_proj bias gradient = token sums of dQ|dK|dV, left per sample by the attention backward: its B partial rows
             # join the block's ONE row-reduction launch (was: a column-sum launch + its reduction per block)
             dbqkv = bq_out if bq_out is not None else _empty((3 * D,), torch.float32, x2)
             rq.add_rows(part, B, 3 * D, 3 * D, (dbqkv,), 3 * D)
         else:
-            dbqkv = on_side(lambda: p_colsum(part if part is not None else dqkv, out=bq_out))
+            dbqkv = p_colsum(part if part is not None else dqkv, out=bq_out)
     r = p_ln_bwd(dy1, x2, ln1w, mean1, rstd1, dres=dx1, dx_dtype=rdt, want_bf16=two, want_dres_colsum=True,
                  outs=(_slot_out(s_ln1w, (D,)) if need[1] else None, _slot_out(s_ln1b, (D,)) if need[2] else None,
                        _slot_out(s_bo, (D,)) if need[6] else None), defer=rq)
-    if rq is not None and own_rq:
-        rq.flush(reduce_side)
+    if rqueue is None:
+        rq.flush()
     dln1w, dln1b = r[1], r[2]
     dbo = r[-1] if need[6] else None                             # colsum(dx1), fused into the LN1 backward
-    if side is not None:
-        if keep is not None:   # joined by the caller: until then nothing the side stream reads may be recycled
-            keep.extend(t for t in (g16, h, du, y2, dx1_16, o, dqkv, y1, part) if t is not None)
-        else:
-            main.wait_stream(side)  # every buffer the side stream read may be recycled after this point
     dx32 = None if chain else r[0]
     dx16 = r[0] if chain else (r[3] if two else None)
     return dx32, dx16, (dln1w, dln1b, dwqkv, dbqkv, dwo, dbo, dln2w, dln2b, dwfc, dbfc, dwpr, dbpr)
@@ -1177,8 +1117,6 @@ class ResBlockFn(Function):
         ctx.save_for_backward(*saved)
         ctx.cfg = (B, T, D, n_head, causal, act, act_dtype)
         ctx.klen = klen
-        from . import config as _cfg
-        ctx.overlap_wgrad = bool(_cfg.overlap_wgrad)
         ctx.gslots = tuple(_slot_of(w) for w in (wqkv, wo, wfc, wpr))
         ctx.vslots = tuple(_slot_of(w) for w in (ln1w, ln1b, bqkv, bo, ln2w, ln2b, bfc, bpr))
         _GradFold.other[id(ln1w)] = weakref.ref(ln1w)        # a producer that does not fold: its block's gradients go the engine's way
@@ -1194,7 +1132,7 @@ class ResBlockFn(Function):
         g = g.contiguous().view(M, D)
         g16 = st.view(M, D) if (st is not None and act_dtype == torch.bfloat16) else None
         dx, dx16, grads = _resblock_bwd(ctx.saved_tensors, ctx.cfg, ctx.klen, ctx.gslots, ctx.vslots,
-                                        ctx.needs_input_grad, g, g16, False, ctx.overlap_wgrad)
+                                        ctx.needs_input_grad, g, g16, False)
         dx = dx.view(B, T, D)
         if dx16 is not None:
             dx._segclip_bf16 = dx16.view(B, T, D)
@@ -1308,9 +1246,8 @@ class ResStackFn(Function):
         ctx.cfg = (B, T, D, n_head, causal, act, act_dtype)
         ctx.klen, ctx.nblk = klen, nblk
         ctx.chain = (bool(chain) or resid16) and act_dtype == torch.bfloat16
-        ctx.overlap_wgrad = bool(_cfg.overlap_wgrad)
         ctx.wgrad_group, ctx.wgrad_group_dist = int(_cfg.wgrad_group_blocks), int(_cfg.wgrad_group_blocks_dist)
-        ctx.fold = bool(_cfg.fold_param_grads) and not (ctx.overlap_wgrad or bool(_cfg.reduce_side)) and len(params) > 0
+        ctx.fold = bool(_cfg.fold_param_grads) and len(params) > 0
         if ctx.fold:     # per block (the same blocks may be cut into different stacks by the two passes)
             for b in range(nblk):
                 k = id(params[b * 12])
@@ -1346,17 +1283,11 @@ class ResStackFn(Function):
         saved = ctx.saved_tensors
         need_all = ctx.needs_input_grad
         out = [None] * (nblk * 12)
-        keep = [] if (ctx.overlap_wgrad and _WGRAD_JOIN_STACK) else None
-        # config.reduce_side: the blocks' trailing reductions (split-K combines, LayerNorm / bias column sums) go to a side
-        # stream and are joined once, at the end of the stack - not with GradSync slots (their bucket exchange is ordered
-        # against the stream that PRODUCED a gradient, which must then be this one)
-        from . import config as _cfg
-        rside = _reduce_stream() if (_cfg.reduce_side and not ctx.overlap_wgrad and all(s is None for s in ctx.slots)) else None
         # config.wgrad_group_blocks (captured at forward time): the weight gradients of up to that many consecutive blocks run
         # as one grouped launch (WgradGroup); with GradSync slots the groups stay short so that the bucket exchanges keep
         # overlapping with the backward pass.  A block's gradients are published when its group has been enqueued.
         wg, sizes = None, []
-        if ctx.wgrad_group > 1 and ctx.cfg[-1] == torch.bfloat16 and not ctx.overlap_wgrad and nblk > 1:
+        if ctx.wgrad_group > 1 and ctx.cfg[-1] == torch.bfloat16 and nblk > 1:
             Dm, F4 = ctx.params[2].shape[1], ctx.params[8].shape[0]
             if Dm % 256 == 0 and F4 % 256 == 0 and Mp % 64 == 0:
                 gmax = ctx.wgrad_group if all(s is None for s in ctx.slots) else min(ctx.wgrad_group, ctx.wgrad_group_dist)
@@ -1364,7 +1295,7 @@ class ResStackFn(Function):
                 sizes = wgrad_group_plan(nblk, tiles_blk, Mp // 64, gmax)
                 wg = WgradGroup() if max(sizes) > 1 else None
         left = sizes.pop(0) if wg is not None else 0
-        grq = ReduceQueue() if (wg is not None and rside is None and _SHARED_RQ) else None
+        grq = ReduceQueue() if wg is not None else None
         pending = []
         adds = []
         for b in reversed(range(nblk)):
@@ -1374,7 +1305,7 @@ class ResStackFn(Function):
             gslots = (sl[2], sl[4], sl[8], sl[10])
             vslots = (sl[0], sl[1], sl[3], sl[5], sl[6], sl[7], sl[9], sl[11])
             cur32, cur16, grads = _resblock_bwd(saved[b * N_SAVED:(b + 1) * N_SAVED], ctx.cfg, ctx.klen, gslots, vslots,
-                                                need, cur32, cur16, ctx.chain, ctx.overlap_wgrad, keep, rside, wg, grq)
+                                                need, cur32, cur16, ctx.chain, wg, grq)
             pending.append((b, P, sl, grads))
             if wg is not None:
                 left -= 1
@@ -1400,11 +1331,6 @@ class ResStackFn(Function):
                         out[b_ * 12 + i] = gr
             pending = []
         _GradFold.flush(adds)
-        if keep is not None:
-            torch.cuda.current_stream().wait_stream(_wgrad_stream())
-            keep.clear()
-        if rside is not None:
-            torch.cuda.current_stream().wait_stream(rside)     # the parameter gradients are complete when the node returns
         if Mp != B * T:                      # row-padded stack: back to the token rows
             cur16 = cur16[:B * T] if cur16 is not None else None
             cur32 = cur32[:B * T] if cur32 is not None else None

@@ -7,9 +7,13 @@ import torch
 from segclip_amd import config
 
 
-def test_defaults_the_docs_quote():
+def test_defaults_and_removed_switches():
     # numerics-changing switches are opt-in; fusions that change no arithmetic are on
-    assert config.bf16_resid is False and config.reduce_side is False and config.overlap_wgrad is False
+    assert config.bf16_resid is False
+    for removed in ("reduce_side", "overlap_wgrad"):   # measured slower and removed: no longer switches
+        with pytest.raises(KeyError):
+            with config.scope(**{removed: True}):
+                pass
     assert config.fused_head is True and config.fuse_res_stack is True and config.bf16_resgrad is True
     assert config.cross_mode == "t18" and config.compute_dtype in (torch.float32, torch.bfloat16)
     assert isinstance(config.aux_u8, bool)

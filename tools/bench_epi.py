@@ -1,6 +1,5 @@
 """Fused-epilogue GEMM variants of one residual block at the vision-tower shape against the plain kernel, with a
-numerical check of every variant against a torch fp32 product (random data, HIP events).
-SEGCLIP_P8_TOUCH=0/1 switches the side-tile touch of the 8-phase kernel (read once per process)."""
+numerical check of every variant against a torch fp32 product (random data, HIP events)."""
 import os, sys
 os.environ.setdefault("SEGCLIP_TUNING", "1")   # the library honours its kernel-selection switches only with this set
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -80,6 +79,6 @@ add("c_fc dgrad plain            N=D K=4D", fl_fc, lambda: ops.p_dgrad(h, wfc, B
 add("out_proj dgrad plain        N=D K=D", fl_o, lambda: ops.p_dgrad(g, wo, BF))
 qkvg = torch.randn(M, 3 * D, device=dev).to(BF)
 add("qkv dgrad plain             N=D K=3D", fl_qkv, lambda: ops.p_dgrad(qkvg, wqkv, BF))
-print(f"# M={M} D={D}  SEGCLIP_P8_TOUCH={os.environ.get('SEGCLIP_P8_TOUCH', '1')}")
+print(f"# M={M} D={D}")
 for name, tf, us, err in rows:
     print(f"{name:40s} {tf:8.1f} TF/s {us:9.1f} us   relerr {err:.2e}")
