@@ -7,8 +7,10 @@
 //  * The 128 accumulators live in a[0:127] and are only touched by inline asm (v_mfma ... a[..], v_accvgpr_read): hipcc
 //    sees a kernel with ~100 live registers, compiles it in seconds instead of minutes and spills nothing (the compiler-
 //    managed form of gemm_bf16_p8.hip sits at 256 VGPRs with 31 spilled).  Budget with 2 waves per SIMD: 128 + 128.
-//  * The MFMA operands are SWAPPED (srcA = B fragment, srcB = A fragment): the 32x32 result block is held transposed,
-//    lane = output ROW, 16 registers = 4 groups of 4 CONSECUTIVE columns.  Everything elementwise (bias, QuickGELU and
+//  * The MFMA is v_mfma_f32_16x16x32_bf16 (-DSEGCLIP_PQ_MFMA32=1: v_mfma_f32_32x32x16_bf16, same tile per wave, same LDS
+//    images; in the training step the chip holds ~2.08 instead of ~1.91 GHz on the 16x16x32 form).  Its operands are
+//    SWAPPED (srcA = B fragment, srcB = A fragment): each result block is held transposed, lane = output ROW, register
+//    quads = 4 CONSECUTIVE columns (see pq_row / pq_col for both shapes).  Everything elementwise (bias, QuickGELU and
 //    its saved derivative, act' multiplier) happens in that layout in fp32; bf16 pairs are packed in-lane
 //    (v_cvt_pk_bf16_f32 on adjacent registers, no lane exchange) and a group leaves as ONE ds_write_b64.
 //  * Output = two HALVES (128 rows) of two QUADRANTS (128 x 128) each, parked as bf16 in XOR-swizzled 32-KiB patches
@@ -108,13 +110,28 @@ typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
   "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", \
   "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127"
 
-// accumulator block ACC (16 registers) += srcA x srcB; ZERO: = srcA x srcB (first K chunk of a tile: no zero-fill pass)
+// MFMA shape.  Default v_mfma_f32_16x16x32_bf16: at the same cycles per FLOP the chip holds a higher clock under sustained
+// load on it than on v_mfma_f32_32x32x16_bf16.  -DSEGCLIP_PQ_MFMA32=1 (build.sh flag) builds the 32x32x16 form instead, for
+// same-box A/B runs; everything but the operand / accumulator maps is shared.
+#ifndef SEGCLIP_PQ_MFMA32
+#define SEGCLIP_PQ_MFMA32 0
+#endif
+constexpr bool M16 = !SEGCLIP_PQ_MFMA32;
+constexpr int ACC_REGS = M16 ? 4 : 16;   // accumulator registers of one MFMA block
+
+// accumulator block ACC (ACC_REGS registers) += srcA x srcB; ZERO: = srcA x srcB (first K chunk of a tile: no zero-fill pass)
 template <int ACC, bool ZERO>
 __device__ __forceinline__ void mfma_acc(const bf16x8_t& a, const bf16x8_t& b) {
+#if SEGCLIP_PQ_MFMA32
+#define PQ_MFMA_OP "v_mfma_f32_32x32x16_bf16"
+#else
+#define PQ_MFMA_OP "v_mfma_f32_16x16x32_bf16"
+#endif
   if constexpr (ZERO)
-    asm volatile("v_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, 0" : : "v"(__builtin_bit_cast(u32x4, a)), "v"(__builtin_bit_cast(u32x4, b)), "i"(ACC * 16), "i"(ACC * 16 + 15) : PQ_AGPRS);
+    asm volatile(PQ_MFMA_OP " a[%c2:%c3], %0, %1, 0" : : "v"(__builtin_bit_cast(u32x4, a)), "v"(__builtin_bit_cast(u32x4, b)), "i"(ACC * ACC_REGS), "i"(ACC * ACC_REGS + ACC_REGS - 1) : PQ_AGPRS);
   else
-    asm volatile("v_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" : : "v"(__builtin_bit_cast(u32x4, a)), "v"(__builtin_bit_cast(u32x4, b)), "i"(ACC * 16), "i"(ACC * 16 + 15) : PQ_AGPRS);
+    asm volatile(PQ_MFMA_OP " a[%c2:%c3], %0, %1, a[%c2:%c3]" : : "v"(__builtin_bit_cast(u32x4, a)), "v"(__builtin_bit_cast(u32x4, b)), "i"(ACC * ACC_REGS), "i"(ACC * ACC_REGS + ACC_REGS - 1) : PQ_AGPRS);
+#undef PQ_MFMA_OP
 }
 // 8 accumulator registers a[B .. B+7] -> v[0..7]
 template <int B> __device__ __forceinline__ void acc_read8(float* v) {
@@ -171,15 +188,24 @@ __device__ __forceinline__ uint32_t off_ks(int h, int idx, int lane, int64_t ld)
   const int chunk = (lane & 15) ^ ((krow & 3) << 2);
   return (uint32_t)((krow * ld + h * 128 + chunk * 8) * 2);
 }
+// Operand fragments (lane l, element j = 0..7 of its 16 bytes).  32x32x16: row rbase + (l&31), k = 16 kc + 8 (l>>5) + j.
+// 16x16x32: row rbase + (l&15), k = 32 kc + 8 (l>>4) + j; the XOR (r>>1)&7 repeats every 16 rows, so the 16-row blocks
+// of a base are an immediate 2048 B apart.  ds_read_b128 of either map: conflict-free (each 16-lane group of the
+// instruction covers 8 row pairs x 8 distinct chunks).
 __device__ __forceinline__ uint32_t fragbase_direct(int rbase, int kc, int lane) {
-  const int r = rbase + (lane & 31);
-  const int c = kc * 2 + (lane >> 5);
+  const int r = rbase + (M16 ? (lane & 15) : (lane & 31));
+  const int c = M16 ? kc * 4 + (lane >> 4) : kc * 2 + (lane >> 5);
   return (uint32_t)(r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
 }
+// k-strided operand (LDS image [64 k-rows][256 B], 16-byte chunk c of k-row kr at c ^ ((kr&3)<<2)), read by two
+// ds_read_b64_tr_b16 (k-rows +0..3, +4..7): lane 4q+p of 16-lane group g4 addresses k-row q, columns 4p .. 4p+3 of its
+// group's block.  32x32x16: group g4 = k half g4>>1, 16-column half g4&1; 16x16x32: group g4 = k-rows 8 g4 .., the 16
+// columns rbase ..; the next 16 columns are 32 B on, the next 32 k-rows 8 KiB on.  The 16x16x32 read is 2-way: a 32-lane
+// half takes k-rows kr and kr+8 of the same columns, which the 4-periodic XOR puts on the same banks.
 __device__ __forceinline__ uint32_t fragbase_ks(int rbase, int lane) {
   const int g4 = lane >> 4, q = lane & 15;
-  const int krow = 8 * (g4 >> 1) + (q >> 2);
-  const int col = rbase + 16 * (g4 & 1) + 4 * (q & 3);
+  const int krow = M16 ? 8 * g4 + (q >> 2) : 8 * (g4 >> 1) + (q >> 2);
+  const int col = M16 ? rbase + 4 * (q & 3) : rbase + 16 * (g4 & 1) + 4 * (q & 3);
   return (uint32_t)(krow * 256 + ((((col >> 3) ^ ((krow & 3) << 2))) << 4) + ((col & 7) << 1));
 }
 template <int OFF> __device__ __forceinline__ bf16x8_t frag_direct_at(lds_cchar* base) {
@@ -223,29 +249,38 @@ __device__ __forceinline__ void store16_nt(const void* base_uniform, uint32_t of
   asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(off), "v"(v), "s"(base_uniform) : "memory");
 }
 
-// ---- output path.  Accumulator layout (swapped MFMA): block (I, ri, J) = a[((I*2+ri)*2+J)*16 ..+15]; lane l holds row
-// I*128 + wr*64 + ri*32 + (l&31), register r column J*128 + wc*32 + 8*(r>>2) + 4*(l>>5) + (r&3).
+// ---- output path.  Accumulator layout (swapped MFMA): the 16 registers of block (I, ri, J) = a[((I*2+ri)*2+J)*16 ..+15],
+// register quad gq (registers 4 gq + k, k = 0..3) of lane l holds row I*128 + wr*64 + pq_row(gq, l), columns
+// J*128 + wc*32 + pq_col(gq, l) + k:
+//   32x32x16: row ri*32 + (l&31), columns 8 gq + 4 (l>>5) ..
+//   16x16x32: row ri*32 + (gq>>1)*16 + (l&15), columns 16 (gq&1) + 4 (l>>4) .. (16x16 block rb = 2 ri + (gq>>1), cb = gq&1)
+template <int RI> __device__ __forceinline__ int pq_row(int gq, int lane) {
+  return M16 ? RI * 32 + (gq >> 1) * 16 + (lane & 15) : RI * 32 + (lane & 31);
+}
+__device__ __forceinline__ int pq_col(int gq, int lane) { return M16 ? 16 * (gq & 1) + 4 * (lane >> 4) : 8 * gq + 4 * (lane >> 5); }
 // bf16 patch of a quadrant: [128 rows][256 B]; 16-byte chunk c of row R is stored at chunk c ^ (R&7), and its two 8-byte
-// halves are swapped when (R>>3)&1: the 16 lanes a ds_write_b64 services together (16 consecutive rows, one column group)
-// hit 16 different 8-byte slots of the 128-byte bank window.
+// halves are swapped when (R>>3)&1: the 16 lanes a ds_write_b64 services together hit 16 different 8-byte slots of the
+// 128-byte bank window (32x32x16: 16 consecutive rows, one column group; 16x16x32: 16 consecutive rows, one column group).
 // uint8 patch of a quadrant: [128 rows][128 B]; chunk c at c ^ (R&7) and (patches written by ds_write_b32) dword d of a
-// chunk at d ^ ((R>>3)&3): 32 rows x one dword -> 32 different banks.
+// chunk at d ^ ((R>>3)&3): 32x32x16: 32 rows x one dword -> 32 different banks; 16x16x32: 16 rows x 2 dwords, 2-way (rows
+// R and R+8), which costs a ds_write_b32 nothing.
 template <int MODE, int I, int J, int RI>
-__device__ __forceinline__ void pq_block(const PQArgs& g, lds_char* sm, const f32x4 (&bias)[4], int li, int lk, int wr,
-                                         int wc, int si_off) {
+__device__ __forceinline__ void pq_block(const PQArgs& g, lds_char* sm, const f32x4 (&bias)[4], int lane, int wr, int wc,
+                                         int si_off) {
   float v[16];
   acc_read8<((I * 2 + RI) * 2 + J) * 16>(v);
   acc_read8<((I * 2 + RI) * 2 + J) * 16 + 8>(v + 8);
-  const uint32_t hbase = H_OFF + J * 32768 + (uint32_t)(wr * 64 + RI * 32 + li) * 256 + ((((uint32_t)wc * 4) ^ (li & 4)) << 4) +
-                         ((lk ^ ((li >> 3) & 1)) << 3);
-  const uint32_t row128 = (uint32_t)(wr * 64 + RI * 32 + li) * 128;
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) {
     float w[4];
-    // uint8 patches: byte column wc*32 + 8 gq + 4 lk -> chunk wc*2 + (gq>>1), dword (gq&1)*2 + lk
-    const uint32_t c8 = ((uint32_t)wc * 2 + (gq >> 1)) ^ (li & 7);
+    const uint32_t R = (uint32_t)(wr * 64 + pq_row<RI>(gq, lane)), cw = (uint32_t)pq_col(gq, lane);
+    const uint32_t hadr = H_OFF + J * 32768 + R * 256 + ((((uint32_t)wc * 4 + (cw >> 3)) ^ (R & 7)) << 4) +
+                          ((((cw >> 2) & 1) ^ ((R >> 3) & 1)) << 3);
+    const uint32_t row128 = R * 128;
+    // uint8 patches: byte column wc*32 + cw -> chunk wc*2 + (cw>>4), dword (cw>>2)&3
+    const uint32_t c8 = ((uint32_t)wc * 2 + (cw >> 4)) ^ (R & 7), d8 = (cw >> 2) & 3;
     if constexpr (MODE == PQ_DACT8) {
-      const uint32_t q = *reinterpret_cast<lds_cu32*>(sm + si_off + J * 16384 + row128 + (c8 << 4) + (((gq & 1) * 2 + lk) << 2));
+      const uint32_t q = *reinterpret_cast<lds_cu32*>(sm + si_off + J * 16384 + row128 + (c8 << 4) + (d8 << 2));
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float qf = (float)((q >> (8 * k)) & 0xffu);   // v_cvt_f32_ubyteN
@@ -284,8 +319,7 @@ __device__ __forceinline__ void pq_block(const PQArgs& g, lds_char* sm, const f3
         q = __builtin_amdgcn_cvt_pk_u8_f32(qf[0], 2 * k2, q);
         q = __builtin_amdgcn_cvt_pk_u8_f32(qf[1], 2 * k2 + 1, q);
       }
-      *reinterpret_cast<lds_u32*>(sm + AO_OFF + J * 16384 + row128 + (c8 << 4) +
-                                  ((((gq & 1) * 2 + lk) ^ ((li >> 3) & 3)) << 2)) = q;
+      *reinterpret_cast<lds_u32*>(sm + AO_OFF + J * 16384 + row128 + (c8 << 4) + ((d8 ^ ((R >> 3) & 3)) << 2)) = q;
     }
     if constexpr (MODE == PQ_ACT8) {
       // QuickGELU and its derivative on PAIRS (v_pk_mul / v_pk_add / v_pk_fma_f32: the same IEEE operations as the scalar
@@ -306,13 +340,12 @@ __device__ __forceinline__ void pq_block(const PQArgs& g, lds_char* sm, const f3
         q = __builtin_amdgcn_cvt_pk_u8_f32(qf[0], 2 * k2, q);
         q = __builtin_amdgcn_cvt_pk_u8_f32(qf[1], 2 * k2 + 1, q);
       }
-      *reinterpret_cast<lds_u32*>(sm + AO_OFF + J * 16384 + row128 + (c8 << 4) +
-                                  ((((gq & 1) * 2 + lk) ^ ((li >> 3) & 3)) << 2)) = q;
+      *reinterpret_cast<lds_u32*>(sm + AO_OFF + J * 16384 + row128 + (c8 << 4) + ((d8 ^ ((R >> 3) & 3)) << 2)) = q;
     }
     u32x2 p;
     p[0] = pack2bf(w[0], w[1]);
     p[1] = pack2bf(w[2], w[3]);
-    *reinterpret_cast<lds_u32x2*>(sm + hbase + ((gq ^ (li & 3)) << 4)) = p;
+    *reinterpret_cast<lds_u32x2*>(sm + hadr) = p;
   }
 }
 
@@ -431,16 +464,15 @@ __device__ __forceinline__ void pq_rows_aux(const PQArgs& g, lds_cchar* sm, int 
 // (16 consecutive rows, one column group) hit the 16 different 16-byte slots of a 256-byte bank window, and so do the 16
 // lanes of a ds_read_b128 of the row pass (16 consecutive chunks of one row).  Two quadrants = the whole 128-KiB ring.
 template <int I, int J, int RI>
-__device__ __forceinline__ void pq_block_f32(lds_char* sm, int li, int lk, int wr, int wc) {
+__device__ __forceinline__ void pq_block_f32(lds_char* sm, int lane, int wr, int wc) {
   float v[16];
   acc_read8<((I * 2 + RI) * 2 + J) * 16>(v);
   acc_read8<((I * 2 + RI) * 2 + J) * 16 + 8>(v + 8);
-  const uint32_t row = (uint32_t)(wr * 64 + RI * 32 + li);
-  const uint32_t base = J * 65536 + row * 512;
 #pragma unroll
   for (int gq = 0; gq < 4; ++gq) {
-    const uint32_t chunk = (uint32_t)wc * 8 + 2 * gq + lk;
-    *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(sm + base + ((chunk ^ (row & 15)) << 4)) =
+    const uint32_t row = (uint32_t)(wr * 64 + pq_row<RI>(gq, lane));
+    const uint32_t chunk = (uint32_t)wc * 8 + ((uint32_t)pq_col(gq, lane) >> 2);
+    *reinterpret_cast<__attribute__((address_space(3))) f32x4*>(sm + J * 65536 + row * 512 + ((chunk ^ (row & 15)) << 4)) =
         f32x4{v[gq * 4], v[gq * 4 + 1], v[gq * 4 + 2], v[gq * 4 + 3]};
   }
 }
@@ -576,17 +608,29 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   using std::integral_constant;
   typedef integral_constant<int, 0> I0;
   typedef integral_constant<int, 1> I1;
-  // 8 MFMAs of one C quadrant (A half I, B half J) and one K-tile; srcA = B fragment: the result block is transposed
+  // One C quadrant (A half I, B half J) and one K-tile; srcA = B fragment: the result block is transposed.
+  // 32x32x16: 2 row blocks x 4 k-steps = 8 MFMAs; fa[ri][kc] (rows ri*32 ..), fb[kc].
+  // 16x16x32: 4 row blocks x 2 column blocks x 2 k-steps = 16 MFMAs; fa[ks][rb] (rows rb*16 ..), fb[ks*2 + cb] (columns
+  // cb*16 ..); block (rb, cb) is register quad (rb&1)*2 + cb of the 16 registers the 32x32 block (ri = rb>>1) has.
   auto quadrant = [&](auto ic, auto jc, auto zc, const bf16x8_t (&fb)[4]) {
     constexpr int I = decltype(ic)::value, J = decltype(jc)::value;
     constexpr bool Z = decltype(zc)::value != 0;
     __builtin_amdgcn_s_setprio(1);
-    mfma_acc<(I * 2 + 0) * 2 + J, Z>(fb[0], fa[0][0]);
-    mfma_acc<(I * 2 + 1) * 2 + J, Z>(fb[0], fa[1][0]);
+    if constexpr (M16) {
+#define PQ_MFMA16(KS, RB, CB, ZZ) mfma_acc<(((I * 2 + (RB >> 1)) * 2 + J) * 4 + (RB & 1) * 2 + CB), ZZ>(fb[KS * 2 + CB], fa[KS][RB])
+      PQ_MFMA16(0, 0, 0, Z); PQ_MFMA16(0, 0, 1, Z); PQ_MFMA16(0, 1, 0, Z); PQ_MFMA16(0, 1, 1, Z);
+      PQ_MFMA16(0, 2, 0, Z); PQ_MFMA16(0, 2, 1, Z); PQ_MFMA16(0, 3, 0, Z); PQ_MFMA16(0, 3, 1, Z);
+      PQ_MFMA16(1, 0, 0, false); PQ_MFMA16(1, 0, 1, false); PQ_MFMA16(1, 1, 0, false); PQ_MFMA16(1, 1, 1, false);
+      PQ_MFMA16(1, 2, 0, false); PQ_MFMA16(1, 2, 1, false); PQ_MFMA16(1, 3, 0, false); PQ_MFMA16(1, 3, 1, false);
+#undef PQ_MFMA16
+    } else {
+      mfma_acc<(I * 2 + 0) * 2 + J, Z>(fb[0], fa[0][0]);
+      mfma_acc<(I * 2 + 1) * 2 + J, Z>(fb[0], fa[1][0]);
 #pragma unroll
-    for (int kc = 1; kc < 4; ++kc) {
-      mfma_acc<(I * 2 + 0) * 2 + J, false>(fb[kc], fa[0][kc]);
-      mfma_acc<(I * 2 + 1) * 2 + J, false>(fb[kc], fa[1][kc]);
+      for (int kc = 1; kc < 4; ++kc) {
+        mfma_acc<(I * 2 + 0) * 2 + J, false>(fb[kc], fa[0][kc]);
+        mfma_acc<(I * 2 + 1) * 2 + J, false>(fb[kc], fa[1][kc]);
+      }
     }
     __builtin_amdgcn_s_setprio(0);
   };
@@ -608,8 +652,8 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
           uint32_t oa = fragbase_direct(wr * 64, x, lane);
           uint32_t ob = B_KS ? fragbase_ks(wc * 32, lane) : fragbase_direct(wc * 32, x, lane);
           oa += sl * HSLOT; ob += sl * HSLOT + UNIT;
-          asm volatile("" : "+v"(oa));
-          if ((!B_KS || x < 1)) asm volatile("" : "+v"(ob));
+          if (!M16 || x < 2) asm volatile("" : "+v"(oa));
+          if (B_KS ? x < 1 : (!M16 || x < 2)) asm volatile("" : "+v"(ob));
           abh[sl][x] = sm3 + oa;
           bbh[sl][x] = sm3 + ob;
         }
@@ -621,14 +665,27 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
       };
       auto read_a_h = [&](auto sc) {
         constexpr int SL = decltype(sc)::value;
-        fa[0][0] = frag_direct_at<0>(abh[SL][0]); fa[0][1] = frag_direct_at<0>(abh[SL][1]);
-        fa[0][2] = frag_direct_at<0>(abh[SL][2]); fa[0][3] = frag_direct_at<0>(abh[SL][3]);
-        fa[1][0] = frag_direct_at<4096>(abh[SL][0]); fa[1][1] = frag_direct_at<4096>(abh[SL][1]);
-        fa[1][2] = frag_direct_at<4096>(abh[SL][2]); fa[1][3] = frag_direct_at<4096>(abh[SL][3]);
+        if constexpr (M16) {
+          fa[0][0] = frag_direct_at<0>(abh[SL][0]); fa[0][1] = frag_direct_at<2048>(abh[SL][0]);
+          fa[0][2] = frag_direct_at<4096>(abh[SL][0]); fa[0][3] = frag_direct_at<6144>(abh[SL][0]);
+          fa[1][0] = frag_direct_at<0>(abh[SL][1]); fa[1][1] = frag_direct_at<2048>(abh[SL][1]);
+          fa[1][2] = frag_direct_at<4096>(abh[SL][1]); fa[1][3] = frag_direct_at<6144>(abh[SL][1]);
+        } else {
+          fa[0][0] = frag_direct_at<0>(abh[SL][0]); fa[0][1] = frag_direct_at<0>(abh[SL][1]);
+          fa[0][2] = frag_direct_at<0>(abh[SL][2]); fa[0][3] = frag_direct_at<0>(abh[SL][3]);
+          fa[1][0] = frag_direct_at<4096>(abh[SL][0]); fa[1][1] = frag_direct_at<4096>(abh[SL][1]);
+          fa[1][2] = frag_direct_at<4096>(abh[SL][2]); fa[1][3] = frag_direct_at<4096>(abh[SL][3]);
+        }
       };
       auto read_b_h = [&](auto sc, auto uc, bf16x8_t (&fb)[4]) {
         constexpr int SL = decltype(sc)::value, U = decltype(uc)::value;
-        if constexpr (B_KS) {
+        if constexpr (M16 && B_KS) {
+          fb[0] = frag_ks_at<U>(bbh[SL][0]); fb[1] = frag_ks_at<U + 32>(bbh[SL][0]);
+          fb[2] = frag_ks_at<U + 8192>(bbh[SL][0]); fb[3] = frag_ks_at<U + 8192 + 32>(bbh[SL][0]);
+        } else if constexpr (M16) {
+          fb[0] = frag_direct_at<U>(bbh[SL][0]); fb[1] = frag_direct_at<U + 2048>(bbh[SL][0]);
+          fb[2] = frag_direct_at<U>(bbh[SL][1]); fb[3] = frag_direct_at<U + 2048>(bbh[SL][1]);
+        } else if constexpr (B_KS) {
           fb[0] = frag_ks_at<U + 0 * 4096>(bbh[SL][0]); fb[1] = frag_ks_at<U + 1 * 4096>(bbh[SL][0]);
           fb[2] = frag_ks_at<U + 2 * 4096>(bbh[SL][0]); fb[3] = frag_ks_at<U + 3 * 4096>(bbh[SL][0]);
         } else {
@@ -687,11 +744,12 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
       // k-strided A: one base per 32-row block (x = 0, 1), the k chunk is an immediate; direct A: one base per k chunk
+      // (16x16x32: per k-step, x = 0, 1, the row blocks are immediates)
       uint32_t oa = A_KS ? fragbase_ks(wr * 64 + (x & 1) * 32, lane) : fragbase_direct(wr * 64, x, lane);
       uint32_t ob = B_KS ? fragbase_ks(wc * 32, lane) : fragbase_direct(wc * 32, x, lane);
       oa += bf * BUF; ob += bf * BUF;
-      if (!A_KS || x < 2) asm volatile("" : "+v"(oa));
-      if ((!B_KS || x < 1)) asm volatile("" : "+v"(ob));
+      if ((!A_KS && !M16) || x < 2) asm volatile("" : "+v"(oa));
+      if (B_KS ? x < 1 : (!M16 || x < 2)) asm volatile("" : "+v"(ob));
       abase[bf][x] = sm3 + oa;
       bbase[bf][x] = sm3 + ob;
     }
@@ -704,7 +762,17 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
 
   auto read_a = [&](auto bfc, auto uc) {
     constexpr int BF_ = decltype(bfc)::value, U = decltype(uc)::value;
-    if constexpr (A_KS) {
+    if constexpr (M16 && A_KS) {
+      fa[0][0] = frag_ks_at<U>(abase[BF_][0]); fa[0][1] = frag_ks_at<U + 32>(abase[BF_][0]);
+      fa[0][2] = frag_ks_at<U>(abase[BF_][1]); fa[0][3] = frag_ks_at<U + 32>(abase[BF_][1]);
+      fa[1][0] = frag_ks_at<U + 8192>(abase[BF_][0]); fa[1][1] = frag_ks_at<U + 8192 + 32>(abase[BF_][0]);
+      fa[1][2] = frag_ks_at<U + 8192>(abase[BF_][1]); fa[1][3] = frag_ks_at<U + 8192 + 32>(abase[BF_][1]);
+    } else if constexpr (M16) {
+      fa[0][0] = frag_direct_at<U>(abase[BF_][0]); fa[0][1] = frag_direct_at<U + 2048>(abase[BF_][0]);
+      fa[0][2] = frag_direct_at<U + 4096>(abase[BF_][0]); fa[0][3] = frag_direct_at<U + 6144>(abase[BF_][0]);
+      fa[1][0] = frag_direct_at<U>(abase[BF_][1]); fa[1][1] = frag_direct_at<U + 2048>(abase[BF_][1]);
+      fa[1][2] = frag_direct_at<U + 4096>(abase[BF_][1]); fa[1][3] = frag_direct_at<U + 6144>(abase[BF_][1]);
+    } else if constexpr (A_KS) {
       fa[0][0] = frag_ks_at<U + 0 * 4096>(abase[BF_][0]); fa[0][1] = frag_ks_at<U + 1 * 4096>(abase[BF_][0]);
       fa[0][2] = frag_ks_at<U + 2 * 4096>(abase[BF_][0]); fa[0][3] = frag_ks_at<U + 3 * 4096>(abase[BF_][0]);
       fa[1][0] = frag_ks_at<U + 0 * 4096>(abase[BF_][1]); fa[1][1] = frag_ks_at<U + 1 * 4096>(abase[BF_][1]);
@@ -718,7 +786,13 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   };
   auto read_b = [&](auto bfc, auto uc, bf16x8_t (&fb)[4]) {
     constexpr int BF_ = decltype(bfc)::value, U = decltype(uc)::value;
-    if constexpr (B_KS) {
+    if constexpr (M16 && B_KS) {
+      fb[0] = frag_ks_at<U>(bbase[BF_][0]); fb[1] = frag_ks_at<U + 32>(bbase[BF_][0]);
+      fb[2] = frag_ks_at<U + 8192>(bbase[BF_][0]); fb[3] = frag_ks_at<U + 8192 + 32>(bbase[BF_][0]);
+    } else if constexpr (M16) {
+      fb[0] = frag_direct_at<U>(bbase[BF_][0]); fb[1] = frag_direct_at<U + 2048>(bbase[BF_][0]);
+      fb[2] = frag_direct_at<U>(bbase[BF_][1]); fb[3] = frag_direct_at<U + 2048>(bbase[BF_][1]);
+    } else if constexpr (B_KS) {
       fb[0] = frag_ks_at<U + 0 * 4096>(bbase[BF_][0]); fb[1] = frag_ks_at<U + 1 * 4096>(bbase[BF_][0]);
       fb[2] = frag_ks_at<U + 2 * 4096>(bbase[BF_][0]); fb[3] = frag_ks_at<U + 3 * 4096>(bbase[BF_][0]);
     } else {
@@ -787,7 +861,6 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   if (g.abl & 2) return;
   // ---- output
   asm volatile("" : "+v"(lane));   // lane-dependent epilogue addresses are derived here, not kept live across the K loop
-  const int li = lane & 31, lk = lane >> 5;
   lds_char* const smw = (lds_char*)smem;
   if constexpr (MODE == PQ_SLAB || MODE == PQ_RES32) {
     // fp32 output through fp32 patches: the partial tile of this K range -> its slab (PQ_SLAB), or
@@ -803,10 +876,10 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
     asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
 #define PQ_BLOCKS32(I)                                                   \
     do {                                                                 \
-      pq_block_f32<I, 0, 0>(smw, li, lk, wr, wc);                        \
-      pq_block_f32<I, 0, 1>(smw, li, lk, wr, wc);                        \
-      pq_block_f32<I, 1, 0>(smw, li, lk, wr, wc);                        \
-      pq_block_f32<I, 1, 1>(smw, li, lk, wr, wc);                        \
+      pq_block_f32<I, 0, 0>(smw, lane, wr, wc);                          \
+      pq_block_f32<I, 0, 1>(smw, lane, wr, wc);                          \
+      pq_block_f32<I, 1, 0>(smw, lane, wr, wc);                          \
+      pq_block_f32<I, 1, 1>(smw, lane, wr, wc);                          \
       PQ_BAR_LDS();                                                      \
     } while (0)
     PQ_BLOCKS32(0);
@@ -831,7 +904,7 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      bias[j][q] = has_bias ? *reinterpret_cast<lds_cf32x4*>(sm3 + (half ? BIAS_OFF_H : BIAS_OFF) + wave * 256 + (j * 32 + q * 8 + lk * 4) * 4)
+      bias[j][q] = has_bias ? *reinterpret_cast<lds_cf32x4*>(sm3 + (half ? BIAS_OFF_H : BIAS_OFF) + wave * 256 + (j * 32 + pq_col(q, lane)) * 4)
                             : f32x4{0.f, 0.f, 0.f, 0.f};
   // MFMA results -> v_accvgpr_read: the last MFMA was issued a barrier ago; 16-pass XDL needs 18 wait states
   asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
@@ -847,10 +920,10 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   }
 #define PQ_HALF(I, SI, RESV)                                                   \
   do {                                                                         \
-    pq_block<MODE, I, 0, 0>(g, smw, bias[0], li, lk, wr, wc, SI);              \
-    pq_block<MODE, I, 0, 1>(g, smw, bias[0], li, lk, wr, wc, SI);              \
-    pq_block<MODE, I, 1, 0>(g, smw, bias[1], li, lk, wr, wc, SI);              \
-    pq_block<MODE, I, 1, 1>(g, smw, bias[1], li, lk, wr, wc, SI);              \
+    pq_block<MODE, I, 0, 0>(g, smw, bias[0], lane, wr, wc, SI);                \
+    pq_block<MODE, I, 0, 1>(g, smw, bias[0], lane, wr, wc, SI);                \
+    pq_block<MODE, I, 1, 0>(g, smw, bias[1], lane, wr, wc, SI);                \
+    pq_block<MODE, I, 1, 1>(g, smw, bias[1], lane, wr, wc, SI);                \
     PQ_BAR_LDS();                                                              \
     if constexpr (MODE == PQ_RES) {                                            \
       if (I == 0 && !half) pq_res_issue<1>(g, lane, wave, m0, n0, res1);       \
