@@ -82,7 +82,7 @@ typedef struct segclip_gemm_desc {
   void* ws;         /* optional split-K scratch (bf16 path, plain epilogue only); NULL = no split-K */
   int64_t ws_bytes; /* size of ws; segclip_gemm_ws_bytes(d) is the amount that enables split-K */
   float* colsum;    /* optional [N] fp32: column sums of the stored C (bias gradient fused into the epilogue).
-                       Needs colsum_ws = (M/64)*N floats, M % 256 == 0, N % 256 == 0 and the LDS-DMA bf16 path;
+                       Needs colsum_ws = (M/64)*N floats, M % 128 == 0, N % 256 == 0 and the LDS-DMA bf16 path;
                        otherwise segclip_gemm returns SEGCLIP_ERR_UNSUPPORTED without launching. */
   float* colsum_ws;
   int32_t flags;    /* SEGCLIP_GEMM_DEFER_*: leave the trailing reduction launches to the caller (segclip_reduce_multi):
@@ -560,6 +560,36 @@ int segclip_wgrad_group(const segclip_wgrad_item* items, int n, int64_t R, int s
  * runs on this kernel as q rows of full tiles + N / 256 half-tiles.
  * ------------------------------------------------------------------------------------------ */
 int segclip_gemm_pq_half_tail(int64_t ntiles);
+
+/* ------------------------------------------------------------------------------------------
+ * Test hook: which GEMM kernel instance the last segclip_gemm call on the calling thread launched (one host-side store per
+ * launch; nothing on the GPU).  A call that launched nothing (an error, SEGCLIP_ERR_UNSUPPORTED, M or N = 0) leaves family
+ * SEGCLIP_GEMM_ROUTE_NONE, and segclip_gemm_last_route then returns SEGCLIP_ERR_UNSUPPORTED (out is filled either way).
+ *   a_ks / b_ks : the operand is k-strided (A(m,k) = A[k*sak + m], B(n,k) = B[k*sbk + n]) rather than k-contiguous
+ *   tile_m/_n   : output tile of one workgroup;  splits: K splits (> 1: fp32 slabs in ws and a combine)
+ *   variant     : GENERIC: bit 0 = fp32 A operand, bit 1 = 16-byte aligned (unguarded) operand loads
+ *                 DMA    : 0 = 256 x 128 tiles, 1 = 256 x 256, 2 = 128 x 128
+ *                 P8     : 0
+ *                 PQ     : bits 0-3 the epilogue mode (0 plain, 1 + bf16 residual, 2 QuickGELU + derivative byte, 3 x derivative
+ *                          byte, 4 fp32 partial tiles / weight gradient, 5 + fp32 residual -> fp32, 6 erf-GELU + derivative
+ *                          byte), bits 4-15 the tail tiles run as half-tiles, bits 16-31 the half-tiles of a last row of
+ *                          128 rows (M = 256 q + 128)
+ *                 F32    : 0 = 32 x 128 tiles (M <= 32), 1 = 64 x 64, 2 = 128 x 128
+ * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_GEMM_ROUTE_NONE 0
+#define SEGCLIP_GEMM_ROUTE_GENERIC 1 /* register-staged 128 x 128 bf16 kernel (gemm_bf16.hip) */
+#define SEGCLIP_GEMM_ROUTE_DMA 2     /* LDS-DMA bf16 kernel (gemm_bf16_dma.hip) */
+#define SEGCLIP_GEMM_ROUTE_P8 3      /* phase-pipelined 256 x 256 bf16 kernel (gemm_bf16_p8.hip) */
+#define SEGCLIP_GEMM_ROUTE_PQ 4      /* accumulator-register 256 x 256 bf16 kernel (gemm_bf16_pq.hip) */
+#define SEGCLIP_GEMM_ROUTE_F32 5     /* exact-fp32 kernel (gemm_f32.hip) */
+typedef struct segclip_gemm_route {
+  int32_t family;
+  int32_t a_ks, b_ks;
+  int32_t tile_m, tile_n;
+  int32_t splits;
+  int32_t variant;
+} segclip_gemm_route;
+int segclip_gemm_last_route(segclip_gemm_route* out);
 
 #ifdef __cplusplus
 }

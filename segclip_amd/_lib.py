@@ -32,6 +32,15 @@ class GemmDesc(C.Structure):
                 ("ws", vp), ("ws_bytes", i64), ("colsum", vp), ("colsum_ws", vp), ("flags", i32), ("res_row_mod", i32)]
 
 
+class GemmRoute(C.Structure):
+    _fields_ = [("family", i32), ("a_ks", i32), ("b_ks", i32), ("tile_m", i32), ("tile_n", i32), ("splits", i32),
+                ("variant", i32)]
+
+
+# segclip_gemm_route.family
+GEMM_ROUTE_FAMILIES = {0: None, 1: "generic", 2: "dma", 3: "p8", 4: "pq", 5: "f32"}
+
+
 class ReduceEntry(C.Structure):
     _fields_ = [("src", vp), ("out0", vp), ("out1", vp), ("out2", vp), ("rows", i64), ("width", i64), ("ld", i64), ("seg", i64),
                 ("scale", f32), ("out_dtype", i32)]
@@ -91,6 +100,7 @@ SIGNATURES = {
     "segclip_wgrad_group_splits": (C.c_int, [i64, i64]),
     "segclip_wgrad_group_model_us": (C.c_double, [i64, i64, C.c_int]),
     "segclip_gemm_pq_half_tail": (C.c_int, [i64]),
+    "segclip_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
     "segclip_wgrad_group_ws_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "segclip_wgrad_group": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, C.c_size_t, vp]),
     "segclip_layernorm_fwd_multi": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, vp]),

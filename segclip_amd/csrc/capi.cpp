@@ -31,7 +31,19 @@ extern "C" int segclip_gemm_splits(const segclip_gemm_desc* d) {
   return 1;
 }
 
+static thread_local segclip_gemm_route g_route = {SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
+
+void segclip_gemm_route_note(int family, bool a_ks, bool b_ks, int tile_m, int tile_n, int splits, int variant) {
+  g_route = segclip_gemm_route{family, a_ks, b_ks, tile_m, tile_n, splits, variant};
+}
+
+extern "C" int segclip_gemm_last_route(segclip_gemm_route* out) {
+  if (out) *out = g_route;
+  return g_route.family == SEGCLIP_GEMM_ROUTE_NONE ? SEGCLIP_ERR_UNSUPPORTED : 0;
+}
+
 extern "C" int segclip_gemm(const segclip_gemm_desc* d, void* stream) {
+  g_route = segclip_gemm_route{SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
   SEGCLIP_REQUIRE(d != nullptr, "gemm: null descriptor");
   SEGCLIP_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "gemm: negative size");
   if (d->M == 0 || d->N == 0) return 0;

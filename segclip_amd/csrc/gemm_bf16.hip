@@ -338,6 +338,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
 #define GB_LAUNCHER(NAME, AK, BKS)                                                                              \
   void NAME(bool a_f32, bool fast, dim3 grid, hipStream_t stream, const void* args) {                           \
     const Args g = *reinterpret_cast<const Args*>(args);                                                        \
+    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_GENERIC, AK, BKS, BM, BN, g.splits, (a_f32 ? 1 : 0) | (fast ? 2 : 0)); \
     if (a_f32) {                                                                                                \
       if (fast) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, true, true>), grid, dim3(NT), 0, stream, g);      \
       else hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, true, false>), grid, dim3(NT), 0, stream, g);          \

@@ -305,8 +305,13 @@ bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, in
   // (SEGCLIP_GEMM_SMALL_TILES=0 switches the rule off; a forward + backward pass of the center stage: see DESIGN 4.4).
   static const int small_rule = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_SMALL_TILES"); return e ? atoi(e) : 1; }();
   const int bn_big = pick_bn(d, nb * splits);
-  const bool small = small_rule && d->M >= 128 && d->N >= 128 && !(d->aux_kind == 2 && d->aux) && !g.colsum_part &&
-                     cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256;
+  // fused column sums come from the staged epilogue of FULL tiles only (a partial tile takes the per-element epilogue, which
+  // writes no partial sums): M = 256 q + 128 runs them on the 128-row tiles, where every tile is full (M % 128 == 0 and
+  // N % 256 == 0 are checked by the caller)
+  const bool colsum_rows128 = g.colsum_part && d->M % 256 != 0;
+  const bool small = colsum_rows128 ||
+                     (small_rule && d->M >= 128 && d->N >= 128 && !(d->aux_kind == 2 && d->aux) && !g.colsum_part &&
+                      cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256);
   const int bn = small ? 128 : bn_big;
   const int bm = small ? 128 : 256;
   g.nbx = (int)cdiv(d->N, bn);
@@ -331,6 +336,7 @@ bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, in
   }
   dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
   const int variant = small ? 2 : bn == 256 ? 1 : 0;
+  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_DMA, a_ks, b_ks, bm, bn, splits, variant);
   if (!a_ks && !b_ks) segclip_dma_launch_ff(variant, grid, stream, &g);
   else if (!a_ks && b_ks) segclip_dma_launch_fk(variant, grid, stream, &g);
   else if (a_ks && b_ks) segclip_dma_launch_kk(variant, grid, stream, &g);

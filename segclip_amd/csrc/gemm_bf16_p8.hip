@@ -508,6 +508,9 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
                 d->bsC2 % ce == 0 && (!d->residual || (d->bsR1 % re == 0 && d->bsR2 % re == 0));
     if (d->residual && d->r_dtype != d->c_dtype) g.vec_epi = 0;   // the LDS epilogue holds side operands in the output type
     if (g.colsum_part && !g.vec_epi) return false;
+    // so do the fused column sums (a partial tile's per-element epilogue writes none): M = 256 q + 128 goes to the 128-row
+    // tiles of gemm_bf16_dma.hip
+    if (g.colsum_part && (d->M % BT != 0 || d->N % BT != 0)) return false;
     // the one-byte derivative of the erf-GELU is produced by gemm_bf16_pq.hip only (this epilogue: QuickGELU); decoding is generic
     if (d->aux_kind == 2 && d->aux && !d->mul_dact && d->act != SEGCLIP_ACT_QUICK_GELU) return false;
     // aux_kind 2 (one byte per saved derivative) exists in the staged epilogue of FULL tiles only (8-byte aligned rows)
@@ -516,6 +519,7 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
       return false;
   }
   dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
+  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_P8, a_ks, b_ks, BT, BT, splits, 0);
 #ifdef SEGCLIP_P8_ABLATIONS
   static const int abl = segclip_ablation_env("SEGCLIP_P8_ABL");
   if (!a_ks && !b_ks && abl >= 1 && abl <= 4) {

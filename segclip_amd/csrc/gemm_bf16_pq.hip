@@ -1024,6 +1024,10 @@ static bool pq_tail_setup(PQArgs& g, const segclip_gemm_desc* d, unsigned* nwg) 
   return true;
 }
 
+// segclip_gemm_last_route's variant of this kernel: epilogue mode | tail tiles run as half-tiles << 4 | half-tiles of a last
+// row of 128 rows << 16
+static int pq_route_variant(int mode, const PQArgs& g) { return mode | (g.half_r << 4) | (g.half_x << 16); }
+
 void segclip_pq_launch_f(int, dim3, hipStream_t, const void*);
 void segclip_pq_launch_k(int, dim3, hipStream_t, const void*);
 void segclip_pq_launch_w(int, dim3, hipStream_t, const void*);
@@ -1057,6 +1061,7 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
     else { g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc; g.kper = d->K; g.slab_stride = 0; }
     if (256 * g.ldc * 4 >= (int64_t)1 << 31) return false;
     g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
+    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, true, true, BT, BT, splits, PQ_SLAB);
     segclip_pq_launch_w(PQ_SLAB, dim3((unsigned)(g.ntiles * splits)), stream, &g);
     return true;
   }
@@ -1078,6 +1083,7 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
     g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
     unsigned nwg = 0;
     if (!pq_tail_setup(g, d, &nwg)) return false;
+    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, false, BT, BT, 1, pq_route_variant(PQ_RES32, g));
     segclip_pq_launch_f(PQ_RES32, dim3(nwg), stream, &g);
     return true;
   }
@@ -1118,6 +1124,7 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
   g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
   unsigned nwg = 0;
   if (!pq_tail_setup(g, d, &nwg)) return false;
+  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, b_ks, BT, BT, 1, pq_route_variant(mode, g));
   (b_ks ? segclip_pq_launch_k : segclip_pq_launch_f)(mode, dim3(nwg), stream, &g);
   return true;
 }

@@ -191,6 +191,7 @@ int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream) {
                   (long long)d->M, (long long)nb);
   constexpr size_t lds_small = 2 * 64 * 65 * sizeof(float), lds_big = 2 * 32 * 129 * sizeof(float),
                    lds_skinny = 32 * (33 + 129) * sizeof(float);
+  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_F32, d->sak != 1, d->sbk != 1, (int)bm, (int)bn, 1, skinny ? 0 : small ? 1 : 2);
   if (skinny) hipLaunchKernelGGL((gemm_f32_kernel<1, 32, 1>), grid, dim3(NT), lds_skinny, stream, g);
   else if (small) hipLaunchKernelGGL((gemm_f32_kernel<1, 64, 2>), grid, dim3(NT), lds_small, stream, g);
   else hipLaunchKernelGGL((gemm_f32_kernel<2, 32, 2>), grid, dim3(NT), lds_big, stream, g);

@@ -8,6 +8,7 @@ There is no CPU fallback: tensors must live on the GPU.
 Activation dtype == compute mode: torch.float32 -> exact-f32 MFMA path, torch.bfloat16 -> bf16 MFMA
 path (fp32 residual stream, fp32 parameters / parameter gradients in both modes).
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -287,6 +288,17 @@ def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=No
         return Cc
     L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
     return Cc
+
+
+GemmRoute = collections.namedtuple("GemmRoute", "family a_ks b_ks tile_m tile_n splits variant")
+
+
+def gemm_last_route():
+    """The kernel instance the last segclip_gemm call of this thread launched (include/segclip_hip.h: segclip_gemm_last_route):
+    family 'generic' / 'dma' / 'p8' / 'pq' / 'f32', or None when that call launched nothing."""
+    r = L.GemmRoute()
+    L.load().segclip_gemm_last_route(C.byref(r))
+    return GemmRoute(L.GEMM_ROUTE_FAMILIES[r.family], bool(r.a_ks), bool(r.b_ks), r.tile_m, r.tile_n, r.splits, r.variant)
 
 
 def _split3(t, off, rows, cols, ld, stack, role):

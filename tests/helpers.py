@@ -10,6 +10,24 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FULL_FLAGS = dict(use_seglabel=True, use_vision_mae_recon=True)
 
 
+def _beyond(got, ref, rtol):
+    got, ref = got.double(), ref.double()
+    scale = float(ref.pow(2).mean().sqrt())
+    err = (got - ref).abs()
+    return ~(err <= rtol * (ref.abs() + scale)), err, scale   # (a NaN is beyond any bound)
+
+
+def within(got, ref, rtol):
+    """check()'s bound as a predicate"""
+    return not bool(_beyond(got, ref, rtol)[0].any())
+
+
+def check(got, ref, rtol, what):
+    """|got - ref| <= rtol * (|ref| + the rms of ref): bf16 outputs round to 2^-9 relative, fp32 ones hold the fp32 sum"""
+    bad, err, scale = _beyond(got, ref, rtol)
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())}/{bad.numel()} beyond tolerance, max err {float(err.max()):.3e} (rms {scale:.3e})"
+
+
 def load_golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 

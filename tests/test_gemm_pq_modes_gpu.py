@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from segclip_amd import _lib, ops  # noqa: E402
+from tests.helpers import check  # noqa: E402
 
 DEV = "cuda"
 BF = torch.bfloat16
@@ -20,15 +21,6 @@ AUX_STEP = 1.0 / 204.0                # one-byte derivative: q = rint((act' + 0.
 def rnd(*shape, seed, scale=1.0, dtype=F32):
     g = torch.Generator(device="cpu").manual_seed(seed)
     return (torch.randn(*shape, generator=g) * scale).to(DEV).to(dtype)
-
-
-def check(got, ref, rtol, what):
-    """|got - ref| <= rtol * (|ref| + the rms of ref): bf16 outputs round to 2^-9 relative, fp32 ones hold the fp32 sum"""
-    got, ref = got.double(), ref.double()
-    scale = float(ref.pow(2).mean().sqrt())
-    err = (got - ref).abs()
-    bad = err > rtol * (ref.abs() + scale)
-    assert not bool(bad.any()), f"{what}: {int(bad.sum())}/{bad.numel()} beyond tolerance, max err {float(err.max()):.3e} (rms {scale:.3e})"
 
 
 @pytest.fixture(scope="module")
