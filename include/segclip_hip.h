@@ -209,8 +209,8 @@ typedef struct segclip_attn_desc {
   float scale;
   int32_t causal;
   int32_t dtype;
-  /* SEGCLIP_ATTN_FP8 (bf16 dtype, forward only): Q K^T and P V on the e4m3 MFMA (per-token scales for Q and K, one
-   * scale per 256-key chunk for V, P x 256); the statistics it leaves serve the bf16 backward.  BASELINE configs[4]. */
+  /* SEGCLIP_ATTN_FP8 (bf16 dtype, forward only; BASELINE configs[4]): asked for an e4m3 forward, which was removed
+   * (slower than bf16).  segclip_attn_fwd refuses it with SEGCLIP_ERR_UNSUPPORTED and writes nothing. */
   int32_t flags;
   /* bwd, bf16 only, nullable: fp32 [B][3][H*hd] receives, per sample, the token sums of dQ | dK | dV
    * (= that sample's contribution to the in_proj bias gradient of nn.MultiheadAttention), computed from the

@@ -28,8 +28,8 @@ wgrad_group_blocks_dist : the same limit while GradSync bucket slots are active 
 trust_weight_shadows : False: every training forward re-casts all GEMM weights to bf16 (one multi-tensor launch);
                 True: only weights whose autograd version changed (set per model by train.prep_optimizer when the
                 fused optimizer maintains the bf16 copies itself)
-attn_fp8      : bf16 mode only: the self-attention FORWARD of the residual blocks runs Q K^T and P V on the e4m3 MFMA
-                (BASELINE configs[4]; per-token scales for Q/K, per-chunk scale for V); backward stays bf16
+attn_fp8      : bf16 mode only: asks for an e4m3 self-attention forward (BASELINE configs[4]) that was removed as slower
+                than bf16; the library refuses it (segclip_amd._lib.Unsupported)
 fuse_res_stack: consecutive residual blocks of a tower run as ONE autograd node (ops.ResStackFn) instead of one per block
 bf16_resgrad  : bf16 mode, inside ResStackFn: the residual-stream gradient travels between the LayerNorm backwards as
                 one bf16 tensor (10 instead of 16 bytes per element); False keeps it fp32

@@ -317,7 +317,6 @@ struct BwdArgs {
   float scale; int causal;
   const int* klen;     // nullable: valid keys per sample (fused kernel only)
   float* colsum_part;  // nullable: [B][3][H*hd] token sums of dQ | dK | dV (the in_proj bias gradient, per sample)
-  int abl;             // experiments (SEGCLIP_ATTN_ABL): 0 = the kernel; see attention_sp.inc
   int nitems;          // single-pass kernel: B * H items, walked by a persistent grid
   float* ws;           // attention_dqw.inc, sequences of more than 224 tokens: fp32 dQ accumulators across key chunks
 };
@@ -619,12 +618,6 @@ __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(BwdArgs a) {
 #include "attention_spl.inc"
 #include "attention_dqw.inc"
 #include "attention_stream.inc"
-// e4m3 forward (BASELINE configs[4] as first read): forward-only, non-scaled e4m3 MFMA = the bf16 rate, measured SLOWER than the
-// bf16 kernel in every round (1350 vs 1395 pairs/s at B = 128, profiles/r04_bench_configs.json).  Round 5: out of the default
-// build - configs[4] runs bf16 attention; the kernel stays reachable in `build.sh -DSEGCLIP_EXPERIMENTS` libraries.
-#ifdef SEGCLIP_EXPERIMENTS
-#include "attention_fp8.inc"
-#endif
 
 // ------------------------------- f32 path helpers -------------------------------------------
 // in-place row softmax of S (rows = B*H*Tq, Tk cols), causal mask by query index row % Tq
@@ -675,7 +668,7 @@ bool bf16_ok(const segclip_attn_desc* d) {
 
 
 // persistent forward (attention_pf.inc): launch instance <NT, CAUSAL> on a grid of as many workgroups as the device holds
-template <int NT, bool CAUSAL, int ABL = 0>
+template <int NT, bool CAUSAL>
 int launch_fwd_pf(const FwdArgs& a, int nitems, hipStream_t stream) {
   int dev = 0;
   SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "attn_fwd: cannot query the current device");
@@ -684,7 +677,7 @@ int launch_fwd_pf(const FwdArgs& a, int nitems, hipStream_t stream) {
   static int per_cu_cache[64][33] = {};                    // by (device, key tile rows / 8)
   const size_t lds = fwd_pf_lds_bytes(NT, a.Tq);
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_pf_kernel<NT, CAUSAL, ABL>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_pf_kernel<NT, CAUSAL>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     SEGCLIP_REQUIRE(e == hipSuccess, "attn_fwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
     int ncu = 0;
@@ -695,13 +688,13 @@ int launch_fwd_pf(const FwdArgs& a, int nitems, hipStream_t stream) {
   int& per_cu = per_cu_cache[dev][pf_kv_rows(a.Tq) >> 3];
   if (per_cu == 0) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_pf_kernel<NT, CAUSAL, ABL>, (NT + 1) * 64, lds) != hipSuccess || n < 1) n = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_pf_kernel<NT, CAUSAL>, (NT + 1) * 64, lds) != hipSuccess || n < 1) n = 1;
     static const int grid_env = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_GRID"); return e ? atoi(e) : 0; }();
     per_cu = grid_env > 0 ? grid_env : n;
   }
   const int cap = ncu_dev[dev] * per_cu;
   const int grid = nitems < cap ? nitems : cap;
-  hipLaunchKernelGGL((attn_fwd_pf_kernel<NT, CAUSAL, ABL>), dim3((unsigned)grid), dim3((NT + 1) * 64), lds, stream, a, nitems);
+  hipLaunchKernelGGL((attn_fwd_pf_kernel<NT, CAUSAL>), dim3((unsigned)grid), dim3((NT + 1) * 64), lds, stream, a, nitems);
   SEGCLIP_CHECK_LAUNCH("attn_fwd_pf");
   return 0;
 }
@@ -765,7 +758,7 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
     a.staged = fwd_staged >= 0 ? fwd_staged : (d->Tq > 128 ? 1 : 0);
     static const int fwd_lean = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_LEAN"); return e ? atoi(e) : 1; }();
     a.lean = fwd_lean;
-    SEGCLIP_REQUIRE(!(d->klen && (d->flags & SEGCLIP_ATTN_FP8)), "attn_fwd: klen is not supported by the fp8 kernel");
+    SEGCLIP_REQUIRE(!(d->klen && (d->flags & SEGCLIP_ATTN_FP8)), "attn_fwd: klen is not supported with SEGCLIP_ATTN_FP8");
     if (smallq::covers(d)) {   // at most 8 queries (the learnable-center cross-attention): one wave per (batch, head), VALU
       const int nitems = (int)(d->B * d->H);
       hipLaunchKernelGGL(smallq::attn_smallq_fwd_kernel, dim3((unsigned)cdiv(nitems, smallq::WPB_FWD)), dim3(smallq::WPB_FWD * 64),
@@ -785,31 +778,17 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
         if (tiles == 6) return launch_fwd_pf<6, true>(a, nitems, stream);
         return launch_fwd_pf<7, true>(a, nitems, stream);
       }
-#ifdef SEGCLIP_EXPERIMENTS
-      static const int pf_abl = segclip_ablation_env("SEGCLIP_ATTN_PF_ABL");
-      if (tiles == 7 && pf_abl == 4) return launch_fwd_pf<7, false, 4>(a, nitems, stream);
-      if (tiles == 7 && pf_abl == 5) return launch_fwd_pf<7, false, 5>(a, nitems, stream);
-#endif
       if (tiles == 3) return launch_fwd_pf<3, false>(a, nitems, stream);
       if (tiles == 6) return launch_fwd_pf<6, false>(a, nitems, stream);
       return launch_fwd_pf<7, false>(a, nitems, stream);
     }
     const int nw = tiles < 8 ? tiles : (tiles <= 8 ? 8 : (int)cdiv(tiles, cdiv(tiles, 8)));
     SEGCLIP_REQUIRE(d->B * d->H <= 65535, "attn_fwd: B*H too large");
-#ifndef SEGCLIP_EXPERIMENTS
     if (d->flags & SEGCLIP_ATTN_FP8) {
-      segclip_set_error("attn_fwd: the e4m3 forward is not part of the default build (slower than bf16 at head_dim 64; "
-                        "build.sh -DSEGCLIP_EXPERIMENTS keeps it): configs[4] runs bf16 attention");
+      segclip_set_error("attn_fwd: the e4m3 forward was removed (slower than bf16 at head_dim 64, DESIGN.md section 8): "
+                        "configs[4] runs bf16 attention");
       return SEGCLIP_ERR_UNSUPPORTED;
     }
-#else
-    if (d->flags & SEGCLIP_ATTN_FP8) {
-      hipLaunchKernelGGL(attn_fwd_fp8_kernel, dim3((unsigned)cdiv(tiles, nw), (unsigned)(d->B * d->H)), dim3(nw * 64), 0,
-                         stream, a);
-      SEGCLIP_CHECK_LAUNCH("attn_fwd_fp8");
-      return 0;
-    }
-#endif
     hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3((unsigned)cdiv(tiles, nw), (unsigned)(d->B * d->H)), dim3(nw * 64), 0,
                        stream, a);
     SEGCLIP_CHECK_LAUNCH("attn_fwd_bf16");
@@ -856,8 +835,6 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
     a.scale = d->scale; a.causal = d->causal;
     a.colsum_part = (float*)d->colsum_part;
     a.klen = (const int*)d->klen;
-    static const int abl_env = segclip_ablation_env("SEGCLIP_ATTN_ABL");
-    a.abl = abl_env;
     a.nitems = (int)(d->B * d->H);
     a.ws = (float*)d->ws;
     if (smallq::covers(d)) {

@@ -123,14 +123,6 @@ __device__ __forceinline__ void dqw_wait_vm(uint32_t n) {
   }
 }
 
-// timing experiments (SEGCLIP_ATTN_ABL, results garbage: 1 no memory instructions in the step loop, 2 no compute, 9 s_memtime stamps) exist
-// only in -DSEGCLIP_EXPERIMENTS builds (tools/build_exp_attn.sh): compiled into the production kernel - never taken - they cost registers
-// (2 spilled ones inside the step loop: 261 -> 307 us; a scratch reload is a vector-memory instruction behind which hipcc drains vmcnt)
-#ifdef SEGCLIP_EXPERIMENTS
-#define DQW_ABL a.abl
-#else
-#define DQW_ABL 0
-#endif
 // MULTI (sequences of more than NT * 32 tokens; ViT-L/14@336: 577): the work unit is (item, CHUNK of NT * 32 keys).  The key-owners hold
 // the chunk's K / V fragments and stream ALL NQ = ceil(T / 32) query tiles past them (Q, dO, O are re-streamed once per chunk:
 // NC x the reads, still ~1/10 of a CU's load rate); dK / dV of the chunk are final at the end of the unit and leave as for an
@@ -206,7 +198,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
     // ================================================ dQ wave ================================================
     const int lane = threadIdx.x & 63, lr = lane >> 3, c = lane & 7, li = lane & 31, lh = lane >> 5;
     int lro = lr, co = c, lio = li;                          // re-derived per step from an opaque copy of the lane id (issue_tile: see the key-owners)
-    if (DQW_ABL == 11) __builtin_amdgcn_s_setprio(1);        // (experiments: static priority of the dQ wave)
     // kernel arguments used in the loop come from the lane table `atab` (see below)
 #define adQ DQW_ARGP(bf16_t, dQ)
 #define acs DQW_ARGP(float, colsum_part)
@@ -291,11 +282,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
       return __builtin_bit_cast(bf16x8_t, r);
     };
-    // DQW_ABL == 9 (experiments build): s_memtime stamps, per-wave totals written over the head of dQ:
-    // 0 barrier, 1 dQ product, 2 tile out, 3 token sums + K^T reload
-    uint32_t lph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ltl = DQW_ABL == 9 ? __builtin_amdgcn_s_memtime() : 0;
-#define DQW_LSTAMP(i) do { if (DQW_ABL == 9) { __builtin_amdgcn_sched_barrier(0); const uint64_t t__ = __builtin_amdgcn_s_memtime(); lph[i] += (uint32_t)(t__ - ltl); ltl = t__; __builtin_amdgcn_sched_barrier(0); } } while (0)
     // dQ^T of tile t: one product over all keys; the bf16 tile -> patch -> global as whole 128-byte rows
     auto product = [&](int t, int jt, int cch, int b, int h) {
       f32x16 dq[2];
@@ -310,7 +296,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         dq[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[kw][0][1], st1, dq[0], 0, 0, 0);
         dq[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[kw][1][1], st1, dq[1], 0, 0, 0);
       }
-      DQW_LSTAMP(1);
       if (MULTI) {
         // the tile's fp32 accumulators across the chunks of the item: [workgroup][query tile][8 register quads][64 lanes]
         float* wsp = DQW_ARGP(float, ws) + ((int64_t)blockIdx.x * NQ + jt) * 2048 + lane * 4;
@@ -361,11 +346,10 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         for (int u = 0; u < 4; ++u)
           if (jt * 32 + u * 8 < T) {                         // (wave-uniform: the software vmcnt counts what is really issued)
             const int r = jt * 32 + u * 8 + lr;
-            if (r < T && DQW_ABL != 1) dqw_store16(dQp, (uint32_t)((r * dq_st + c * 8) * 2), v[u]);
+            if (r < T) dqw_store16(dQp, (uint32_t)((r * dq_st + c * 8) * 2), v[u]);
             ++nvmq;
           }
       }
-      DQW_LSTAMP(2);
       if (jt == NQ - 1 && acs) {                             // token sums of dQ | dK | dV of the item
         float* dst = acs + (int64_t)b * 3 * ((int64_t)aH * 64) + (int64_t)h * 64;
         const float vq = (Red[lane] + Red[64 + lane]) * ascale;
@@ -399,38 +383,29 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       }
       for (int j = 0; j < NQ; ++j) {
         __builtin_amdgcn_s_barrier();                        // B_g
-        DQW_LSTAMP(0);
         nvmq = 0;
         {
           int lane_o = lane;
           asm volatile("" : "+v"(lane_o));
           lro = lane_o >> 3; co = lane_o & 7; lio = lane_o & 31;
         }
-        if (RING_DQ && un * NQ + j + DQW_PF < ntiles && DQW_ABL != 1) issue_tile(un * NQ + j + DQW_PF, un);
+        if (RING_DQ && un * NQ + j + DQW_PF < ntiles) issue_tile(un * NQ + j + DQW_PF, un);
         if (j >= 1) {
-          if (DQW_ABL != 2) product(un * NQ + j - 1, j - 1, cch, ib, ih);
+          product(un * NQ + j - 1, j - 1, cch, ib, ih);
         } else if (un > 0) {
           // the previous unit's last tile with the OLD K^T, then this unit's K^T out of KN - under the key-owners' S / dP / softmax of
           // the step; they park the previous unit's dK in those rows behind the barrier K.  (First version: an extra barrier at the end
           // of a unit, this product and the reload behind it while the key-owners waited: ~2300 exposed cycles per unit)
-          if (DQW_ABL != 2) product(un * NQ - 1, NQ - 1, cchP, ibP, ihP);
+          product(un * NQ - 1, NQ - 1, cchP, ibP, ihP);
           load_ktr(MULTI ? cch * TP : 0);
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          DQW_LSTAMP(3);
           __builtin_amdgcn_s_barrier();                      // K
         }
         if (RING_DQ) dqw_wait_vm(nvmq);                      // what this wave issued BEFORE this step has landed / left
       }
     }
     __builtin_amdgcn_s_barrier();                            // F: the last dS^T tiles are parked
-    DQW_LSTAMP(0);
     product(ntiles - 1, NQ - 1, cch, ib, ih);
-    if (DQW_ABL == 9) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (lane < 8) reinterpret_cast<float*>(a.dQ)[((int64_t)blockIdx.x * 8 + wave) * 8 + lane] = (float)lph[lane];
-    }
-#undef DQW_LSTAMP
 #undef adQ
 #undef acs
 #undef dq_sb
@@ -440,7 +415,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 
   // ================================================ key-owner waves ================================================
   // (measured: s_setprio 1 for key-owners 4-6 - the second-dispatched half - leaves the ratio to the round-5 kernel at 0.90)
-  if ((DQW_ABL == 12 && wave >= 4) || DQW_ABL == 13) __builtin_amdgcn_s_setprio(1);   // (experiments: the younger half / all key-owners)
   const int k0 = wave * 32;
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
@@ -609,16 +583,9 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
   load_kv(0);
   dpass_share(0);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  // DQW_ABL == 9: 0 barrier, 1 memory issue (DMA pieces, parked-tile stores), 2 K / V fragments + S / dP of the next tile (issue) + D share,
-  // 3 softmax + park, 4 dV / dK products (issue), 5 end of step (lgkmcnt, vmcnt), 6 end of item
-  uint32_t tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t mph[3] = {0, 0, 0};                               // inside the memory issue: tile pieces, parked-tile stores, own K / V pieces
-  uint64_t tl = DQW_ABL == 9 ? __builtin_amdgcn_s_memtime() : 0;
-#define DQW_STAMP(i) do { if (DQW_ABL == 9) { __builtin_amdgcn_sched_barrier(0); const uint64_t t__ = __builtin_amdgcn_s_memtime(); tph[i] += (uint32_t)(t__ - tl); tl = t__; __builtin_amdgcn_sched_barrier(0); } } while (0)
   int uS = 0, jS = 0;                                        // MULTI: (unit, step) of tile g without a division by NQ
   for (int g = 0; g < ntiles; ++g) {
     __builtin_amdgcn_s_barrier();                            // B_g
-    DQW_STAMP(0);
     const int il = MULTI ? uS : g / NT, j = MULTI ? jS : g - il * NT;   // il: the local UNIT (MULTI: (item, chunk)) of tile g
     nvm = 0;
     {
@@ -635,10 +602,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
     // waves right behind the barrier they queue up behind each other (~470 cycles per instruction and wave: 2000 cycles per step
     // in which no wave computes)
     auto mem_issue = [&]() {
-      uint64_t m0_ = DQW_ABL == 9 ? __builtin_amdgcn_s_memtime() : 0;
-#define DQW_MSTAMP(i) do { if (DQW_ABL == 9) { __builtin_amdgcn_sched_barrier(0); const uint64_t t__ = __builtin_amdgcn_s_memtime(); mph[i] += (uint32_t)(t__ - m0_); m0_ = t__; __builtin_amdgcn_sched_barrier(0); } } while (0)
       if (!RING_DQ && g + DQW_PF < ntiles) issue_tile_share(g + DQW_PF);
-      DQW_MSTAMP(0);
       if (il > 0) {                                          // the previous item's parked gradients: two row groups per step
         // (dV was parked at the end of the unit, dK is parked in the middle of step 0)
         if (j == 0) store_groups(bP, hP, cP, 1, 0, 2);
@@ -646,18 +610,14 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         else if (j == 2) store_groups(bP, hP, cP, 0, 0, 2);
         else if (j == 3) store_groups(bP, hP, cP, 0, 2, 4);
       }
-      DQW_MSTAMP(1);
       if (il + 1 < nunits) {
         // the next item's V / K rows of this wave, behind the stores that read the parked tiles from the same rows
         if (j == 2 || j == 3) issue_own_kv(bN, hN, cN, 1, (j - 2) * 2, (j - 2) * 2 + 2);
         else if (j == 4) issue_own_kv(bN, hN, cN, 0, 0, 4);
       }
-      DQW_MSTAMP(2);
-#undef DQW_MSTAMP
     };
     const int mpos = wave & 3;
-    if (mpos == 0 && DQW_ABL != 1) mem_issue();
-    DQW_STAMP(1);
+    if (mpos == 0) mem_issue();
     // S and dP of THIS tile.  (First version: S / dP of tile g + 1 were issued a step ahead, "so that the matrix pipe has work during
     // the softmax arithmetic".  The 32 registers of the second accumulator pair left hipcc ONE register quad for the eight Q / dO
     // fragments: ds_read_b128 -> s_waitcnt lgkmcnt(0) -> v_mfma, eight times in a row - eight serialised LDS round trips per step.)
@@ -671,7 +631,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
     const char* gsl = qs + 4096;
     bf16x8_t gtf[2][2], qtf[2][2];
     f32x4 l4v[4], d4v[4];
-    if (DQW_ABL != 2) {
+    {
       const float* Lv = reinterpret_cast<const float*>(qs + 3 * 4096 + 256);
       const float* Dv = Lv + 32;
       bf16x8_t qa[4], ga[4];
@@ -702,9 +662,8 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       }
       if (g + 1 < ntiles) dpass_share(g + 1);
     }
-    if (mpos == 1 && DQW_ABL != 1) mem_issue();
-    DQW_STAMP(2);
-    if (DQW_ABL != 2) {
+    if (mpos == 1) mem_issue();
+    {
       float p[16], ds[16];
       asm volatile("" : "+v"(l4v[0]), "+v"(l4v[1]), "+v"(l4v[2]), "+v"(l4v[3]), "+v"(d4v[0]), "+v"(d4v[1]), "+v"(d4v[2]), "+v"(d4v[3]) : : "memory");
 #pragma unroll
@@ -757,8 +716,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         *reinterpret_cast<u32x2*>(scr + woff[2]) = u32x2{w1[0], w1[1]};
         *reinterpret_cast<u32x2*>(scr + woff[3]) = u32x2{w1[2], w1[3]};
       }
-      if (mpos == 2 && DQW_ABL != 1) mem_issue();
-      DQW_STAMP(3);
+      if (mpos == 2) mem_issue();
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
         dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gtf[dt][0], __builtin_bit_cast(bf16x8_t, pb0), dv[dt], 0, 0, 0);
@@ -767,12 +725,10 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       if (j == 0 && il > 0) {
         // K: the dQ wave has finished the previous unit's last tile and taken this unit's K^T out of KN: the previous unit's dK leaves
         // its registers for this wave's (now dead) K rows
-        DQW_STAMP(4);
         __builtin_amdgcn_s_barrier();
         put_tile(KN + k0 * ROWB, dk, ascale);
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; }
-        DQW_STAMP(7);
       }
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
@@ -786,12 +742,9 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
           for (int r = 0; r < 16; ++r) Red[128 + dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = dv[dt][r];
       }
     }
-    if (DQW_ABL == 2 && j == 0 && il > 0) __builtin_amdgcn_s_barrier();   // (experiments: barrier K of the skipped compute)
-    if (mpos == 3 && DQW_ABL != 1) mem_issue();
-    DQW_STAMP(4);
+    if (mpos == 3) mem_issue();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     dqw_wait_vm(nvm);                                        // what this wave issued BEFORE this step has landed / left
-    DQW_STAMP(5);
     if (j == NQ - 1) {
       // end of the unit (no barrier: this wave's own rows only)
       if (il + 1 < nunits) load_kv(cN);                       // the next item's K / V fragments, then this wave's V rows are dead
@@ -800,7 +753,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 #pragma unroll
       for (int r = 0; r < 16; ++r) { dv[0][r] = 0.f; dv[1][r] = 0.f; }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      DQW_STAMP(6);
     }
     if (MULTI) { if (++jS == NQ) { jS = 0; ++uS; } }
   }
@@ -811,14 +763,6 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
   __builtin_amdgcn_wave_barrier();
   store_groups(bC, hC, cC, 0, 0, 4);
   store_groups(bC, hC, cC, 1, 0, 4);
-  if (DQW_ABL == 9) {
-    DQW_STAMP(6);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                            // (the dQ wave's stores of dQ are done)
-    if (lane < 8) reinterpret_cast<float*>(a.dQ)[((int64_t)blockIdx.x * 8 + wave) * 8 + lane] = (float)tph[lane];
-    if (lane < 3) reinterpret_cast<float*>(a.dQ)[65536 + ((int64_t)blockIdx.x * 8 + wave) * 4 + lane] = (float)mph[lane];
-  }
-#undef DQW_STAMP
 #undef aQ
 #undef aG
 #undef aO
@@ -846,4 +790,3 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 #undef DQW_ARG64
 #undef DQW_ARGP
 }
-#undef DQW_ABL

@@ -8,10 +8,10 @@
 //   * ONE LOADER WAVE per workgroup issues every memory instruction: K, V and Q of item i+1 arrive by LDS-DMA
 //     (global_load_lds_dwordx4, 1 KiB per wave instruction; the swizzle of the tiles is applied on the source side) into
 //     the other half of a two-slot ring while item i is computed, and O of item i-1 leaves from LDS as whole 128-byte
-//     rows.  The NT compute waves (one per 32-row query tile) touch LDS and registers only.  Measured on the way here
-//     (s_memtime stamps in an experiments build): with the 12 loads + 5 stores of an item issued by the compute waves
-//     themselves, each wave spent 6-9 thousand of its 18 thousand cycles per item stalled IN THE ISSUE of those
-//     instructions (the CU's vector-memory path is back-pressured by its own outstanding misses), wherever in the item
+//     rows.  The NT compute waves (one per 32-row query tile) touch LDS and registers only.  Measured on the way here:
+//     with the 12 loads + 5 stores of an item issued by the compute waves themselves, each wave spent 6-9 thousand of
+//     its 18 thousand cycles per item stalled IN THE ISSUE of those instructions (the CU's vector-memory path is
+//     back-pressured by its own outstanding misses), wherever in the item
 //     they were placed (one burst behind the barrier: 103 us; spread over the key steps: 122 us);
 //   * one workgroup barrier per item: "item i has landed" (the loader arrives behind its vmcnt(0)) and "every compute
 //     wave is done with item i-1" (its slot and its O tile may be recycled).
@@ -45,9 +45,7 @@ __device__ __forceinline__ float pf_xsum(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// ABL (timing experiments, results garbage; instances only in -DSEGCLIP_EXPERIMENTS builds): 4 no memory traffic after a
-// workgroup's first item (compute only), 5 no compute (memory stream only)
-template <int NT, bool CAUSAL, int ABL = 0>
+template <int NT, bool CAUSAL>
 __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2))) void attn_fwd_pf_kernel(FwdArgs a, int nitems) {
   extern __shared__ __attribute__((aligned(16))) char smem_pf[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -133,9 +131,9 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // item `item` has landed (and the stores of item - 2 grid steps)
       __builtin_amdgcn_s_barrier();                        // B_i
       const int nxt = item + (int)gridDim.x;
-      const bool has_next = nxt < nitems && ABL != 4;
+      const bool has_next = nxt < nitems;
       if (has_next) issue_kv(nxt, slot ^ 1);               // that slot's readers (item i-1) are past the barrier
-      if (prev >= 0 && ABL != 4) flush(prev, slot ^ 1);
+      if (prev >= 0) flush(prev, slot ^ 1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the flush has read QO[slot ^ 1] before Q(i+1) lands in it
       if (has_next) issue_q(nxt, slot ^ 1);
       prev = item;
@@ -168,9 +166,8 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll
         for (int j = 0; j < 2; ++j) voff[dt][j] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * j, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
     }
-    const int sl = ABL == 4 ? 0 : slot;
-    char* const qo = smem_pf + QO_OFF + (sl * NT + wave) * PF_QO_BYTES;
-    float* const lse_w = reinterpret_cast<float*>(smem_pf + LSE_OFF) + (sl * NT + wave) * 32;
+    char* const qo = smem_pf + QO_OFF + (slot * NT + wave) * PF_QO_BYTES;
+    float* const lse_w = reinterpret_cast<float*>(smem_pf + LSE_OFF) + (slot * NT + wave) * 32;
     bf16x8_t qf[4];
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc) {
@@ -180,13 +177,13 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
     int kvalid = T;
     if (klen) { const int b = item / a.H; kvalid = klen[b] < T ? klen[b] : T; }
 
-    const char* Kt = smem_pf + sl * 2 * TILE;
+    const char* Kt = smem_pf + slot * 2 * TILE;
     const char* Vt = Kt + TILE;
     f32x16 o[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
     float m = -INFINITY, l = 0.f;
-    int ntile = ABL == 5 ? 0 : (CAUSAL ? wave + 1 : NT);   // causal: key tiles beyond the wave's own query tile are fully masked
+    int ntile = CAUSAL ? wave + 1 : NT;   // causal: key tiles beyond the wave's own query tile are fully masked
 
     // fragment loads are issued in BATCHES (all K fragments of a step before its first MFMA, all V^T fragments before the
     // softmax arithmetic; the asm statements with a memory clobber pin the issue points)
@@ -319,8 +316,8 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
       if (CAUSAL && wave < nlean) nlean = wave;
       if (ntile > ((kvalid + 31) >> 5)) ntile = (kvalid + 31) >> 5;   // tiles behind the last valid key: P = 0
       int kt = 0;
-      if (nlean >= 2 && ABL != 5) { kload(0, kfa); kload(1, kfb); }
-      for (; kt + 2 <= nlean && ABL != 5; kt += 2) step2(kt, kt + 4 <= nlean);
+      if (nlean >= 2) { kload(0, kfa); kload(1, kfb); }
+      for (; kt + 2 <= nlean; kt += 2) step2(kt, kt + 4 <= nlean);
       for (; kt < ntile; ++kt) step1(kt);
     }
 

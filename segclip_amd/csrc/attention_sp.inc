@@ -63,7 +63,7 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
   // item is issued in one go into registers (one memory round trip; a select right behind a load would make hipcc wait
   // for it, which serialised the first version's prologue: 147 of 420 us) - and for every item but a workgroup's first
   // it is issued BEFORE the previous item's output phase, so the round trip, the store drain and the workgroup launch
-  // that used to sit between two main loops (8.6 + 3.3 us of 29 us per item, `SEGCLIP_ATTN_ABL`) overlap.
+  // that used to sit between two main loops (8.6 + 3.3 us of 29 us per item) overlap.
   // blockDim = 64 n threads and the tiles have 32 n rows of 8 chunks: every thread owns exactly 4 chunks of each tile.
   u32x4 rk[4], rv[4], rks[4], rq[4], rg_[4], ro[4];
   float lse_l = 0.f;
@@ -196,9 +196,6 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
   for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
   float csl = 0.f;
 
-  // a.abl (timing experiments, results are garbage for 1-4): 1 no main loop, 2 no barrier / dQ read-modify-write,
-  // 3 no stores, 4 no main loop and no stores
-  const int nsteps = (a.abl == 1 || a.abl == 4) ? 0 : n;
   auto tile_of = [&](int step) { const int j = wave + step; return j >= n ? j - n : j; };
   auto sdp = [&](int q0, f32x16& s, f32x16& dp) {
 #pragma unroll
@@ -289,44 +286,42 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
     // workgroup barrier per step: the waves of a SIMD may drift apart (one in its MFMA phase, the other in its VALU
     // phase) instead of being re-aligned 7 times.  The LDS executes a wave's operations in order, so a flag value seen
     // here implies the neighbour's accumulator writes are done.  `step` = index of this pair in the wave's walk.
-    if (a.abl != 2) {
-      if (step > 0) {
-        const int nb = wave + 1 == n ? 0 : wave + 1;
-        while (Flag[nb] < step) __builtin_amdgcn_s_sleep(1);
-      }
-      if (!skip) {
-        f32x4* acc = reinterpret_cast<f32x4*>(Acc + jt * SP_ACC_BYTES);
-#pragma unroll
-        for (int g8 = 0; g8 < 8; ++g8) {
-          f32x4 v = acc[g8 * 64 + lane];
-          const int dt = g8 >> 2, rb = (g8 & 3) * 4;
-          v[0] += dq[dt][rb]; v[1] += dq[dt][rb + 1]; v[2] += dq[dt][rb + 2]; v[3] += dq[dt][rb + 3];
-          acc[g8 * 64 + lane] = v;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      if (lane == 0) Flag[wave] = step + 1;
+    if (step > 0) {
+      const int nb = wave + 1 == n ? 0 : wave + 1;
+      while (Flag[nb] < step) __builtin_amdgcn_s_sleep(1);
     }
+    if (!skip) {
+      f32x4* acc = reinterpret_cast<f32x4*>(Acc + jt * SP_ACC_BYTES);
+#pragma unroll
+      for (int g8 = 0; g8 < 8; ++g8) {
+        f32x4 v = acc[g8 * 64 + lane];
+        const int dt = g8 >> 2, rb = (g8 & 3) * 4;
+        v[0] += dq[dt][rb]; v[1] += dq[dt][rb + 1]; v[2] += dq[dt][rb + 2]; v[3] += dq[dt][rb + 3];
+        acc[g8 * 64 + lane] = v;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) Flag[wave] = step + 1;
   };
   if (MASKED) {
-    for (int s_ = 0; s_ < nsteps; ++s_) {
+    for (int s_ = 0; s_ < n; ++s_) {
       const int jt = tile_of(s_);
       const bool skip = a.causal && jt * 32 + 31 < k0;       // every score of the pair is masked (wave-uniform)
       f32x16 s, dp;
       if (!skip) sdp(jt * 32, s, dp);
       finish(s_, s, dp, skip);
     }
-  } else if (nsteps > 0) {
+  } else {
     f32x16 s, dp;
     sdp(tile_of(0) * 32, s, dp);
-    for (int s_ = 0; s_ + 1 < nsteps; ++s_) {
+    for (int s_ = 0; s_ + 1 < n; ++s_) {
       f32x16 sn, dpn;
       sdp(tile_of(s_ + 1) * 32, sn, dpn);      // independent of the step finished below: overlaps its VALU / LDS work
       finish(s_, s, dp, false);
       s = sn; dp = dpn;
     }
-    finish(nsteps - 1, s, dp, false);
+    finish(n - 1, s, dp, false);
   }
   // the next item's loads go out now: they travel while this item's outputs are staged and stored
   // (unconditional, the last item re-reads itself: behind a condition the OLD register values would stay live across the
@@ -373,22 +368,18 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
       if (k0 + r < nrows && c * 8 < a.hd) *reinterpret_cast<u32x4*>(base + (int64_t)(k0 + r) * st + c * 8) = v;
     }
   };
-  if (a.abl < 3) {
-    put_tile(myacc, dk);
-    put_tile(myacc + 4096, dv);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    flush_tile(myacc, a.dK + b * a.dk_sb + hoff, a.dk_st, a.Tk);
-    flush_tile(myacc + 4096, a.dV + b * a.dv_sb + hoff, a.dv_st, a.Tk);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    put_tile(myacc, dq);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    flush_tile(myacc, a.dQ + b * a.dq_sb + hoff, a.dq_st, a.Tq);
-  } else if (dk[0][0] + dv[1][3] + dq[0][2] == 1.2345f) {
-    Cs[key] = dk[0][1];
-  }
+  put_tile(myacc, dk);
+  put_tile(myacc + 4096, dv);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  flush_tile(myacc, a.dK + b * a.dk_sb + hoff, a.dk_st, a.Tk);
+  flush_tile(myacc + 4096, a.dV + b * a.dv_sb + hoff, a.dv_st, a.Tk);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  put_tile(myacc, dq);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  flush_tile(myacc, a.dQ + b * a.dq_sb + hoff, a.dq_st, a.Tq);
   // ---- token sums of dQ | dK | dV (in_proj bias gradient of this sample and head):
   //   sum_q dQ[q][d] = sum_key K[key][d] cs[key]: one more product on the matrix pipe, K^T fragments (registers) x a
   //     B operand whose columns all hold cs (split into two bf16 parts: 16 mantissa bits) - no second read of K;

@@ -3,7 +3,7 @@
 // per 32-key tile, every (query tile, key tile) pair visited once, dQ accumulated in LDS in accumulator format by a skewed
 // walk behind a flag ring); what changes is WHO MOVES THE DATA.  In attention_sp.inc every compute wave issues 25 global
 // loads right behind the main loop (next item's K / V fragments, its share of Q, dO, O, lse) and 12 stores in the output
-// phase; the persistent attention forward of this round measured what that costs (s_memtime stamps): a wave stalls
+// phase; the persistent attention forward of this round measured what that costs: a wave stalls
 // 200-400 cycles IN THE ISSUE of each such instruction while the CU's vector-memory path is backed up by its own misses.
 // The kernel without its main loop took 145 of 297 us: the memory phases were never hidden.  Here
 //   * an extra LOADER WAVE (wave n) owns the memory traffic.  During main loop i it brings item i+1's K tile into a spare
@@ -197,9 +197,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     };
 
     int item = blockIdx.x, cur = 0, prev = -1, parked = 0;
-    uint32_t lph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ltl = a.abl == 9 ? __builtin_amdgcn_s_memtime() : 0;
-#define LD_STAMP(i) do { if (a.abl == 9) { __builtin_amdgcn_sched_barrier(0); const uint64_t t__ = __builtin_amdgcn_s_memtime(); lph[i] += (uint32_t)(t__ - ltl); ltl = t__; __builtin_amdgcn_sched_barrier(0); } } while (0)
     if (item < nitems) {
       prefetch(item, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // K(item) in KN; the K fragments are read between S0 and S1
@@ -211,27 +208,18 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     }
     for (; item < nitems; item += gridDim.x) {
       const int nxt = item + (int)gridDim.x;
-      LD_STAMP(0);                                           // flush_kv (previous item)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      LD_STAMP(1);                                           // wait: Q DMA + stores
       __syncthreads();                                       // S0: Q / dO / K / vectors of `item` are in LDS
-      LD_STAMP(2);                                           // barrier S0
       if (prev >= 0) flush_colsum(prev, cur ^ 1);
       __syncthreads();                                       // S1: the K fragments are in registers, the accumulators are zero
-      LD_STAMP(3);                                           // token sums + barrier S1
       if (nxt < nitems) prefetch(nxt, cur ^ 1);              // during the main loop: K-next, dO-next (registers), D, lse, sums
-      LD_STAMP(4);                                           // prefetch: issue + reduce
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      LD_STAMP(5);                                           // wait: K DMA
       __syncthreads();                                       // S2: the main loop has ended: the Q / dO tiles are dead
-      LD_STAMP(6);                                           // barrier S2 (waiting for the compute waves)
       if (nxt < nitems) fill_tiles(nxt);
-      LD_STAMP(7);                                           // Q DMA issue + dO tile from registers
       // "S3" is one-way (as a barrier it made the compute waves wait ~4000 cycles per item for the loader's Q DMA issue):
       // every compute wave bumps a counter when its dK / dV tiles are parked
       ++parked;
       while (Flag[8] < parked * n) __builtin_amdgcn_s_sleep(2);
-      LD_STAMP(8);                                           // wait: parked counter
       flush_kv(item);
       prev = item;
       cur ^= 1;
@@ -239,8 +227,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                                         // final S0
     if (prev >= 0) flush_colsum(prev, cur ^ 1);
-    if (a.abl == 9 && lane < 10) reinterpret_cast<float*>(a.dQ)[((int64_t)blockIdx.x * 8 + 7) * 8 * 2 + 65536 + lane] = (float)lph[lane];
-#undef LD_STAMP
     return;
   }
 
@@ -263,10 +249,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
   };
   if ((int)blockIdx.x < nitems) issue_v(blockIdx.x, threadIdx.x);
   int cur = 0;
-  // a.abl == 9 (experiments build): s_memtime stamps at the barriers, per-wave totals written over the head of dQ
-  uint32_t tph[6] = {0, 0, 0, 0, 0, 0};
-  uint64_t tl = a.abl == 9 ? __builtin_amdgcn_s_memtime() : 0;
-#define SPL_STAMP(i) do { if (a.abl == 9) { __builtin_amdgcn_sched_barrier(0); const uint64_t t__ = __builtin_amdgcn_s_memtime(); tph[i] += (uint32_t)(t__ - tl); tl = t__; __builtin_amdgcn_sched_barrier(0); } } while (0)
   for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));                            // lane-dependent offsets are not hoisted across items
@@ -278,7 +260,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     const float* Ds = Dsb + cur * tp;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's Q pieces of `item` have landed
     __syncthreads();                                         // S0
-    SPL_STAMP(0);
     bf16x8_t kf[4], vf[4], ktr[2][2];
     {
       const bool rok = key < T;
@@ -314,7 +295,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                         // S1
-    SPL_STAMP(1);
 
     int koff[4], toff[2][2];
 #pragma unroll
@@ -436,7 +416,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       }
       finish(n - 1, s, dp);
     }
-    SPL_STAMP(2);
     // this wave's only loads: the V fragments of the next item (they travel during the output phase)
     issue_v(nxt_item, tid);
 #pragma unroll
@@ -445,7 +424,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     if (lh == 0) Cs[key] = csl * a.scale;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                         // S2: all read-modify-writes are done; Cs is complete
-    SPL_STAMP(3);
     // the next item's Q rows of THIS wave's tile: 4 LDS-DMA pieces (the loader's serial path between S2 and S0 was the
     // bottleneck with all 28 pieces; here they are issued by 7 waves at once and land during the output phase)
     if (item + (int)gridDim.x < nitems) {
@@ -490,7 +468,6 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) __hip_atomic_fetch_add(const_cast<int*>(Flag + 8), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // "S3"
-    SPL_STAMP(4);
     // dQ tile -> global through the wave's 2-KB scratch, one 32-column half at a time ([32 rows][64 B], 16-byte chunk
     // ^ ((row >> 1) & 3)).  (Tried: dK and dV the same way, the loader only loading - 12 stores per compute wave: 305 vs
     // 292 us; the 84 stores of the compute waves and the loader's Q DMA then meet in the same phase of the item.)
@@ -547,10 +524,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    SPL_STAMP(5);
     cur ^= 1;
   }
   __syncthreads();                                           // final S0 (the loader writes the last item's token sums behind it)
-  if (a.abl == 9 && (threadIdx.x & 63) < 6) reinterpret_cast<float*>(a.dQ)[((int64_t)blockIdx.x * 8 + wave) * 8 + (threadIdx.x & 63)] = (float)tph[threadIdx.x & 63];
-#undef SPL_STAMP
 }

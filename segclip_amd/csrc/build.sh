@@ -13,8 +13,8 @@ newest_hdr=$(ls -t *.h *.inc ../../include/*.h | head -1)
 pids=()
 J=${BUILD_JOBS:-$(nproc)}
 throttle() { while [ "$(jobs -rp | wc -l)" -ge "$J" ]; do wait -n || true; done; }
-# the 8-phase GEMM (and likewise gemm_bf16_dma.hip, DMA_PART) is compiled once per operand layout (P8_PART 0..3), its dispatcher as part 4, and - only with
-# -DSEGCLIP_P8_ABLATIONS among the flags - the main-loop ablation instances as part 5: the slow parts build in parallel
+# the 8-phase GEMM (and likewise gemm_bf16_dma.hip, DMA_PART) is compiled once per operand layout (P8_PART 0..3) and its
+# dispatcher as part 4: the slow parts build in parallel
 rm -f build/gemm_bf16.o
 for part in 0 1 2 3 4; do   # the register-staged kernel first: its parts are the longest single jobs
   f=gemm_bf16.hip; o=build/gemm_bf16_part$part.o
@@ -23,9 +23,8 @@ for part in 0 1 2 3 4; do   # the register-staged kernel first: its parts are th
     pids+=($!)
   fi
 done
-parts="0 1 2 3 4"; case "$FLAGS" in *SEGCLIP_P8_ABLATIONS*) parts="$parts 5";; esac
 rm -f build/gemm_bf16_p8.o
-for part in $parts; do
+for part in 0 1 2 3 4; do
   f=gemm_bf16_p8.hip; o=build/gemm_bf16_p8_part$part.o
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$newest_hdr" -nt "$o" ]; then
     throttle; $HIPCC $FLAGS -DP8_PART=$part -c $f -o $o &

@@ -110,8 +110,6 @@ __device__ __forceinline__ float apply_act_grad(int act, float x) {
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Timing ablations that produce GARBAGE results (SEGCLIP_ATTN_ABL, SEGCLIP_P8_EPI_ABL, SEGCLIP_P8_ABL, SEGCLIP_PQ_ABL) exist only in
-// libraries built with `build.sh -DSEGCLIP_EXPERIMENTS`; a production build ignores those environment variables.
 #include <stdlib.h>
 // Kernel-selection / tuning switches of the library (SEGCLIP_GEMM_PQ, SEGCLIP_PQ_HALF, SEGCLIP_ATTN_FWD_PF, ...: A/B tools and
 // profile scripts).  They are honoured only when SEGCLIP_TUNING=1 is set as well: a production process cannot have its kernels
@@ -124,13 +122,4 @@ static inline const char* segclip_tuning_env(const char* name) {
     return nullptr;
   }
   return e;
-}
-static inline int segclip_ablation_env(const char* name) {
-#ifdef SEGCLIP_EXPERIMENTS
-  const char* e = segclip_tuning_env(name);
-  return e ? atoi(e) : 0;
-#else
-  (void)name;
-  return 0;
-#endif
 }

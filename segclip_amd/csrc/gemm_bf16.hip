@@ -451,7 +451,6 @@ int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream) {
   g.slab = (float*)d->ws;
   g.vec_epi = 0;
   g.stagger = 0;
-  g.abl = 0;
   static const int xw_epi = [] { const char* e = segclip_tuning_env("SEGCLIP_EPI_XW"); return e ? atoi(e) : 2; }();
   g.xw_epi = xw_epi;
   static const int slab_staged = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_SLAB_STAGED"); return e ? atoi(e) : 1; }();

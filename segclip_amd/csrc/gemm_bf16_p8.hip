@@ -66,10 +66,10 @@ __device__ __forceinline__ void dma16x2(const char* base_uniform, uint32_t off0,
 
 // Per-lane byte offset (relative to the tile's first element of the operand) of DMA piece `idx` (1 KiB) of half-tile h.
 // k-contiguous operand X(row,k) = X[row*ld + k]: image [128 rows][128 B], piece = 8 rows, 16-B chunk ^ ((row>>1)&7).
-__device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld, int64_t row0, int64_t nrows, int rmask = 0) {
+__device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld, int64_t row0, int64_t nrows) {
   const int u = idx * 8 + (lane >> 3);
   const int chunk = (lane & 7) ^ ((u >> 1) & 7);
-  int64_t r = row0 + h * 128 + (u & ~rmask);   // rmask: experiment (fewer distinct cache lines per DMA instruction)
+  int64_t r = row0 + h * 128 + u;
   r = r < nrows ? r : nrows - 1;
   return (uint32_t)(((r - row0) * ld + chunk * 8) * 2);
 }
@@ -136,9 +136,7 @@ template <int N> __device__ __forceinline__ void wait_vm() {
     __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
 
-// ABL (experiments, SEGCLIP_P8_ABL, k-contiguous layout only): 1 no MFMAs, 2 no DMA, 3 no LDS reads, 4 no stagger
-// between the wave groups - each leaves the rest of the schedule in place, results are garbage.
-template <bool A_KS, bool B_KS, int ABL = 0>
+template <bool A_KS, bool B_KS>
 __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   constexpr int LDS_BYTES = RING > NWV * EPI_WAVE_BYTES ? RING : NWV * EPI_WAVE_BYTES;
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
@@ -167,28 +165,21 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   const int nk = (int)((kend - kbeg) / BK);
 
   // uniform tile bases (bytes) + per-lane 32-bit offsets: the DMA address is SGPR base + VGPR offset
-  // experiments (SEGCLIP_P8_EPI_ABL = 2..5, wrong results): operand rows taken from a small window that stays cache-resident
-  const int64_t m0a = g.abl == 2 || g.abl == 4 ? (m0 & 511) : g.abl == 3 ? (m0 & 4095) : g.abl == 5 ? (m0 & 32767) : m0;
-  const int64_t n0b = g.abl == 4 ? (n0 & 511) : n0;
-  const char* baseA = reinterpret_cast<const char*>(A_KS ? A + kbeg * g.lda + m0a : A + m0a * g.lda + kbeg);
-  const char* baseB = reinterpret_cast<const char*>(B_KS ? B + kbeg * g.ldb + n0b : B + n0b * g.ldb + kbeg);
+  const char* baseA = reinterpret_cast<const char*>(A_KS ? A + kbeg * g.lda + m0 : A + m0 * g.lda + kbeg);
+  const char* baseB = reinterpret_cast<const char*>(B_KS ? B + kbeg * g.ldb + n0 : B + n0 * g.ldb + kbeg);
   const int64_t stepA = A_KS ? (int64_t)BK * g.lda * 2 : BK * 2;   // bytes per K-tile
   const int64_t stepB = B_KS ? (int64_t)BK * g.ldb * 2 : BK * 2;
-  // experiments 6..11: 4 / 2 / 1 distinct rows (cache lines) per DMA instruction, A and B (6-8) or B only (9-11)
-  const int rm_ = g.abl >= 6 && g.abl <= 11 ? (2 << ((g.abl - 6) % 3)) - 1 : 0;
-  const int rmaskA = g.abl >= 9 ? 0 : rm_, rmaskB = rm_;
   uint32_t offA[2][2], offB[2][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      offA[h][i] = A_KS ? off_ks(h, wave * 2 + i, lane, g.lda, m0, g.M) : off_direct(h, wave * 2 + i, lane, g.lda, m0, g.M, rmaskA);
-      offB[h][i] = B_KS ? off_ks(h, wave * 2 + i, lane, g.ldb, n0, g.N) : off_direct(h, wave * 2 + i, lane, g.ldb, n0, g.N, rmaskB);
+      offA[h][i] = A_KS ? off_ks(h, wave * 2 + i, lane, g.lda, m0, g.M) : off_direct(h, wave * 2 + i, lane, g.lda, m0, g.M);
+      offB[h][i] = B_KS ? off_ks(h, wave * 2 + i, lane, g.ldb, n0, g.N) : off_direct(h, wave * 2 + i, lane, g.ldb, n0, g.N);
     }
   // half-tile `u` (0: A0, 1: A1, 2: B0, 3: B1) of K-tile t -> ring buffer t&1
   const uint32_t lds_ring = (uint32_t)(uintptr_t)((lds_void*)smem) + wave * 2048;
   auto stage = [&](int u, int t) {
-    if constexpr (ABL == 2) return;
     const uint32_t dst = lds_ring + (t & 1) * BUF + u * UNIT;
     if (u < 2) dma16x2(baseA + (int64_t)t * stepA, offA[u][0], offA[u][1], dst);
     else dma16x2(baseB + (int64_t)t * stepB, offB[u - 2][0], offB[u - 2][1], dst);
@@ -233,12 +224,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   P8_BAR();
 
   bf16x8_t fa[2][4], fbx[4], fby[4];
-  if constexpr (ABL == 3) {
-#pragma unroll
-    for (int kc = 0; kc < 4; ++kc) {
-      fa[0][kc] = fa[1][kc] = fbx[kc] = fby[kc] = __builtin_bit_cast(bf16x8_t, u32x4{(unsigned)lane, 1u, 2u, 3u});
-    }
-  }
   // lane bases of the fragment reads (see the fragment helpers): [ring buffer][kc] for a k-contiguous operand,
   // [ring buffer][32-row block] for a k-strided one; made opaque so that the compiler keeps them in registers instead
   // of re-deriving them in the K loop
@@ -260,7 +245,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   // U: byte offset of the half-tile unit inside its ring buffer
   auto read_a = [&](auto bfc, auto uc) {
     constexpr int BF_ = decltype(bfc)::value, U = decltype(uc)::value;
-    if constexpr (ABL == 3) return;
 #pragma unroll
     for (int ri = 0; ri < 2; ++ri) {
       if constexpr (A_KS) {
@@ -281,7 +265,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   };
   auto read_b = [&](auto bfc, auto uc, bf16x8_t (&fb)[4]) {
     constexpr int BF_ = decltype(bfc)::value, U = decltype(uc)::value;
-    if constexpr (ABL == 3) return;
     if constexpr (B_KS) {
       fb[0] = frag_ks_at<U + 0 * 4096>(bbase[BF_][0]); fb[1] = frag_ks_at<U + 1 * 4096>(bbase[BF_][0]);
       fb[2] = frag_ks_at<U + 2 * 4096>(bbase[BF_][0]); fb[3] = frag_ks_at<U + 3 * 4096>(bbase[BF_][0]);
@@ -291,14 +274,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     }
   };
   auto quadrant = [&](f32x16 (&c)[2][2], int j, const bf16x8_t (&fb)[4]) {
-    if constexpr (ABL == 1) {  // keep the fragments live without issuing matrix instructions
-#pragma unroll
-      for (int kc = 0; kc < 4; ++kc) {
-        asm volatile("" ::"v"(__builtin_bit_cast(u32x4, fa[0][kc])), "v"(__builtin_bit_cast(u32x4, fa[1][kc])),
-                     "v"(__builtin_bit_cast(u32x4, fb[kc])));
-      }
-      return;
-    }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
@@ -311,7 +286,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   typedef integral_constant<int, 0> I0;
   typedef integral_constant<int, 1> I1;
   read_b(I0{}, integral_constant<int, 2 * UNIT>{}, fbx);   // B0 of K-tile 0 (in the loop this read sits in R4 of the previous tile)
-  if (ABL != 4 && wr == 1) P8_BAR();     // group 1 runs one barrier interval behind group 0
+  if (wr == 1) P8_BAR();     // group 1 runs one barrier interval behind group 0
 
   // one K-tile: fbp holds B0(t) on entry and fbq is free; on exit fbq holds B0(t+1)
   // (bc = t & 1 as a type: the ring-buffer offset of every fragment read is a compile-time constant)
@@ -350,22 +325,9 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     ktile(I1{}, t + 1, fby, fbx);
   }
   if (t < nk) ktile(I0{}, t, fbx, fby);
-  if (ABL != 4 && wr == 0) P8_BAR();  // group 0 catches up: both groups have executed the same number of barriers
+  if (wr == 0) P8_BAR();  // group 0 catches up: both groups have executed the same number of barriers
 
   const int64_t nw = n0 + wc * 32;  // this wave's first column (second strip at +128)
-  if (g.abl == 1) {   // experiment: no epilogue at all (one conditional store keeps the accumulators alive)
-    float sacc = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int ri = 0; ri < 2; ++ri)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc += acc[i][ri][j][r];
-    if (sacc == 1.2345678f) reinterpret_cast<float*>(g.C)[lane] = sacc;
-    return;
-  }
   if (g.splits > 1) {
     const int li = lane & 31, lk = lane >> 5;
     float* slab = g.slab + ((int64_t)ksplit * gridDim.z + z) * g.M * g.N;
@@ -440,14 +402,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
 // carries every epilogue variant and takes over a minute of hipcc time - build in parallel:
 //   P8_PART 0..3 : kernel instance <A_KS = part>>1, B_KS = part&1> and its launcher
 //   P8_PART 4    : the host-side dispatcher below (no device code)
-//   P8_PART 5    : the main-loop ablation instances (only with -DSEGCLIP_P8_ABLATIONS; tools/bench_gemm_abl.py)
 #ifndef P8_PART
-#error "compile with -DP8_PART=0..5 (see build.sh)"
+#error "compile with -DP8_PART=0..4 (see build.sh)"
 #endif
-#define P8_LAUNCHER(NAME, ...)                                                      \
+#define P8_LAUNCHER(NAME, A_KS, B_KS)                                               \
   void NAME(dim3 grid, hipStream_t stream, const void* args) {                      \
     const Args g = *reinterpret_cast<const Args*>(args);                            \
-    hipLaunchKernelGGL((gemm_bf16_p8_kernel<__VA_ARGS__>), grid, dim3(512), 0, stream, g); \
+    hipLaunchKernelGGL((gemm_bf16_p8_kernel<A_KS, B_KS>), grid, dim3(512), 0, stream, g); \
   }
 #if P8_PART == 0
 P8_LAUNCHER(segclip_p8_launch_ff, false, false)
@@ -457,11 +418,6 @@ P8_LAUNCHER(segclip_p8_launch_fk, false, true)
 P8_LAUNCHER(segclip_p8_launch_kf, true, false)
 #elif P8_PART == 3
 P8_LAUNCHER(segclip_p8_launch_kk, true, true)
-#elif P8_PART == 5
-P8_LAUNCHER(segclip_p8_launch_abl1, false, false, 1)
-P8_LAUNCHER(segclip_p8_launch_abl2, false, false, 2)
-P8_LAUNCHER(segclip_p8_launch_abl3, false, false, 3)
-P8_LAUNCHER(segclip_p8_launch_abl4, false, false, 4)
 #endif
 
 #if P8_PART == 4
@@ -469,12 +425,6 @@ void segclip_p8_launch_ff(dim3, hipStream_t, const void*);
 void segclip_p8_launch_fk(dim3, hipStream_t, const void*);
 void segclip_p8_launch_kf(dim3, hipStream_t, const void*);
 void segclip_p8_launch_kk(dim3, hipStream_t, const void*);
-#ifdef SEGCLIP_P8_ABLATIONS
-void segclip_p8_launch_abl1(dim3, hipStream_t, const void*);
-void segclip_p8_launch_abl2(dim3, hipStream_t, const void*);
-void segclip_p8_launch_abl3(dim3, hipStream_t, const void*);
-void segclip_p8_launch_abl4(dim3, hipStream_t, const void*);
-#endif
 
 // Launch the phase-pipelined kernel for problems tiled 256x256.  `args_` is prepared by the caller (gemm_bf16.hip);
 // returns false when the shape does not meet this kernel's preconditions.
@@ -493,8 +443,6 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
   if ((a_ks ? 64 : 256) * (a_ks ? d->sak : d->sam) * 2 >= (int64_t)1 << 31) return false;
   if ((b_ks ? 64 : 256) * (b_ks ? d->sbk : d->sbn) * 2 >= (int64_t)1 << 31) return false;
   static const int stagger = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_STAGGER"); return e ? atoi(e) : 2000; }();   // unit cap in cycles; 0 = off.  In the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
-  static const int epi_abl = segclip_ablation_env("SEGCLIP_P8_EPI_ABL");
-  g.abl = epi_abl;
   g.stagger = stagger;
   g.nbx = (int)cdiv(d->N, BT);
   g.nby = (int)cdiv(d->M, BT);
@@ -520,14 +468,6 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
   }
   dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
   segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_P8, a_ks, b_ks, BT, BT, splits, 0);
-#ifdef SEGCLIP_P8_ABLATIONS
-  static const int abl = segclip_ablation_env("SEGCLIP_P8_ABL");
-  if (!a_ks && !b_ks && abl >= 1 && abl <= 4) {
-    (abl == 1 ? segclip_p8_launch_abl1 : abl == 2 ? segclip_p8_launch_abl2 : abl == 3 ? segclip_p8_launch_abl3
-                                                                             : segclip_p8_launch_abl4)(grid, stream, &g);
-    return true;
-  }
-#endif
   if (!a_ks && !b_ks) segclip_p8_launch_ff(grid, stream, &g);
   else if (!a_ks && b_ks) segclip_p8_launch_fk(grid, stream, &g);
   else if (a_ks && b_ks) segclip_p8_launch_kk(grid, stream, &g);

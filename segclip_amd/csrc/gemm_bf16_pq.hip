@@ -73,7 +73,6 @@ struct PQArgs {
   int nfull, half_r;
   // remainder row: M = 256 q + 128 -> half_x = nbx more half-tile workgroups (the upper halves of tile row q), behind the tail's
   int half_x;
-  int abl;               // timing experiments (SEGCLIP_PQ_ABL, results garbage): 1 = no output stores, 2 = no epilogue at all
 };
 
 // Grouped weight gradients (PQ_SLAB): several C_p = A_p^T B_p problems with the same K (token rows) and the same number of K
@@ -380,7 +379,7 @@ __device__ __forceinline__ void pq_rows_half(const PQArgs& g, lds_cchar* sm, int
           cs[2 * k + 1] += __uint_as_float(d[i4][k] & 0xffff0000u);
         }
       }
-      if (!(g.abl & 1)) store16_nt(cq + (int64_t)it * 8 * ldcb, go, d[i4]);
+      store16_nt(cq + (int64_t)it * 8 * ldcb, go, d[i4]);
     }
   }
   if (MODE == PQ_DACT8 && g.colsum_part != nullptr) {   // column sums of the stored (rounded) values over this wave's 64 rows
@@ -437,7 +436,7 @@ __device__ __forceinline__ void pq_rows_half_res(const PQArgs& g, lds_cchar* sm,
         const float hi = __uint_as_float(d[i4][k] & 0xffff0000u) + __uint_as_float(res[it][k] & 0xffff0000u) + bv[2 * k + 1];
         o[k] = pack2bf(lo, hi);
       }
-      if (!(g.abl & 1)) store16_nt(cq + (int64_t)it * 8 * ldcb, go, o);
+      store16_nt(cq + (int64_t)it * 8 * ldcb, go, o);
     }
   }
 }
@@ -455,7 +454,7 @@ __device__ __forceinline__ void pq_rows_aux(const PQArgs& g, lds_cchar* sm, int 
 #pragma unroll
   for (int it = 0; it < 4; ++it) {   // rows rb + it*8 + rs: (R>>3)&3 = it -> logical dword j sits at j ^ it
     const u32x4 o = u32x4{d[it][0 ^ it], d[it][1 ^ it], d[it][2 ^ it], d[it][3 ^ it]};
-    if (!(g.abl & 1)) store16_nt(aq + (int64_t)it * 8 * g.ldaux, go, o);
+    store16_nt(aq + (int64_t)it * 8 * g.ldaux, go, o);
   }
 }
 
@@ -504,7 +503,7 @@ __device__ __forceinline__ void pq_rows_q_f32(const PQArgs& g, float* out, lds_c
     for (int i4 = 0; i4 < 4; ++i4) {
       const int it = Q * 8 + h4 * 4 + i4;
       if constexpr (RES) d[i4] = (d[i4] + bias4) + res[h4 * 4 + i4];
-      if (!(g.abl & 1)) store16(cq + (int64_t)it * 2 * ldcb, go, __builtin_bit_cast(u32x4, d[i4]));
+      store16(cq + (int64_t)it * 2 * ldcb, go, __builtin_bit_cast(u32x4, d[i4]));
     }
   }
 }
@@ -858,7 +857,6 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   }
   if (wr == 0) PQ_BAR();     // group 0 catches up: every wave is done with the operand ring, the VM queue is empty
 
-  if (g.abl & 2) return;
   // ---- output
   asm volatile("" : "+v"(lane));   // lane-dependent epilogue addresses are derived here, not kept live across the K loop
   lds_char* const smw = (lds_char*)smem;
@@ -936,7 +934,7 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   PQ_HALF(0, (MODE == PQ_DACT8 && half ? SI1_OFF : SI0_OFF), res0);
   if (HALF_OK && half) return;   // half-tile workgroup: 128 rows only
   // second half: its side-in pieces (4 per wave) are older than the first half's 8 output stores of this wave
-  if constexpr (MODE == PQ_DACT8) { if (g.abl & 1) wait_vm<0>(); else wait_vm<8>(); }
+  if constexpr (MODE == PQ_DACT8) wait_vm<8>();
   PQ_BAR_LDS();   // the patches are free again (and every wave's side-in pieces have landed)
   PQ_HALF(1, SI1_OFF, res1);
 #undef PQ_HALF
@@ -1060,7 +1058,6 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
     if (splits > 1) { g.Cf = a.slab; g.ldc = d->N; g.kper = a.kper; g.slab_stride = d->M * d->N; }
     else { g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc; g.kper = d->K; g.slab_stride = 0; }
     if (256 * g.ldc * 4 >= (int64_t)1 << 31) return false;
-    g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
     segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, true, true, BT, BT, splits, PQ_SLAB);
     segclip_pq_launch_w(PQ_SLAB, dim3((unsigned)(g.ntiles * splits)), stream, &g);
     return true;
@@ -1080,7 +1077,6 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
     g.bias = d->bias; g.side = d->residual; g.lds = d->ldr; g.rmod = d->res_row_mod > 0 ? d->res_row_mod : 0;
     g.lda = d->sam; g.ldb = d->sbn; g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc;
     g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
-    g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
     unsigned nwg = 0;
     if (!pq_tail_setup(g, d, &nwg)) return false;
     segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, false, BT, BT, 1, pq_route_variant(PQ_RES32, g));
@@ -1121,7 +1117,6 @@ bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int
   g.colsum_part = a.colsum_part;
   g.lda = lda; g.ldb = ldb; g.ldc = d->ldc; g.lds = mode == PQ_RES ? d->ldr : d->ldaux; g.ldaux = d->ldaux;
   g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
-  g.abl = mode_env == 2 ? segclip_ablation_env("SEGCLIP_PQ_ABL") : 0;
   unsigned nwg = 0;
   if (!pq_tail_setup(g, d, &nwg)) return false;
   segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, b_ks, BT, BT, 1, pq_route_variant(mode, g));
@@ -1195,7 +1190,6 @@ extern "C" int segclip_wgrad_group(const segclip_wgrad_item* it, int n, int64_t 
   }
   PQArgs g = {};
   g.K = (int)R; g.kper = per;
-  g.abl = 0;
   segclip_pq_launch_group(dim3((unsigned)units), stream, &g, &grp);
   SEGCLIP_CHECK_LAUNCH("wgrad_group");
   return 0;

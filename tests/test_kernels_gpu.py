@@ -468,48 +468,31 @@ def test_attention_dqw_backward_is_deterministic_under_memory_contention(B, T, H
 @pytest.mark.parametrize("B,T,H,hd,causal", [(2, 576, 16, 64, False), (2, 196, 12, 64, False), (3, 77, 8, 64, True),
                                              (1, 300, 2, 64, False), (2, 40, 2, 32, False)])
 def test_self_attention_fp8_forward(B, T, H, hd, causal):
-    """e4m3 MFMA forward (BASELINE configs[4]) against the fp32 reference, and against the bf16 kernel on the same
-    inputs: per-token Q/K scales keep the logits to ~2 e4m3 ulps, P is quantised to 8 bits -> looser than bf16."""
+    """SEGCLIP_ATTN_FP8 (BASELINE configs[4] as first read) is refused: the e4m3 forward was removed (slower than bf16,
+    DESIGN §8).  The refusal is SEGCLIP_ERR_UNSUPPORTED with nothing written to O or the statistics, and the bf16 forward
+    on the same inputs - what configs[4] runs - holds the bf16 bounds."""
+    import ctypes
     from segclip_amd import _lib
     D = H * hd
     qkv = rnd(B * T, 3 * D, dtype=BF, seed=71)
     s3 = (T * 3 * D, 3 * D)
-    outs = {}
-    for fp8 in (False, True):
-        o = torch.empty(B * T, D, dtype=BF, device=DEV)
-        d = ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D,
-                           fp8=fp8)
-        try:
-            stats = ops.p_attn_fwd(d, qkv)
-        except _lib.Unsupported as e:      # round 5: the e4m3 forward lives in -DSEGCLIP_EXPERIMENTS builds only (DESIGN 8.4)
-            assert fp8 and "default build" in str(e)
-            pytest.skip("e4m3 attention forward is not in the default build")
-        outs[fp8] = (o.float().view(B, T, D), stats.clone())
+    desc = lambda o, fp8: ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal,
+                                         0, D, 2 * D, fp8=fp8)
+    lib = _lib.load()
+    o8 = torch.full((B * T, D), -3.0, dtype=BF, device=DEV)
+    d = desc(o8, True)
+    stats8 = torch.full((lib.segclip_attn_stats_bytes(ctypes.byref(d)) // 4,), 12345.0, dtype=torch.float32, device=DEV)
+    d.stats = _lib.ptr(stats8)
+    o8_before, stats8_before = o8.clone(), stats8.clone()
+    with pytest.raises(_lib.Unsupported, match="e4m3 forward was removed"):
+        _lib.check(lib.segclip_attn_fwd(ctypes.byref(d), _lib.stream()), "attn_fwd")
+    torch.cuda.synchronize()
+    assert torch.equal(o8.view(torch.int16), o8_before.view(torch.int16)), "the refused fp8 forward wrote O"
+    assert torch.equal(stats8.view(torch.int32), stats8_before.view(torch.int32)), "the refused fp8 forward wrote the statistics"
+    o = torch.empty(B * T, D, dtype=BF, device=DEV)
+    ops.p_attn_fwd(desc(o, False), qkv)
     qr = qkv.float().view(B, T, 3, D)
-    ref = _attn_ref(qr[:, :, 0], qr[:, :, 1], qr[:, :, 2], H, causal)
-    e_bf = float((outs[False][0] - ref).abs().max())
-    e_f8 = float((outs[True][0] - ref).abs().max())
-    rms = float((outs[True][0] - ref).pow(2).mean().sqrt()) / float(ref.pow(2).mean().sqrt())
-    dlse = float((outs[True][1] - outs[False][1]).abs().max())
-    print(f"\n[fp8 attn T={T}] max err bf16 {e_bf:.4f} fp8 {e_f8:.4f} (ref max {float(ref.abs().max()):.2f}); "
-          f"fp8 relative rms {rms:.4f}; max |d lse| vs bf16 kernel {dlse:.4f}")
-    # measured on MI355X: relative rms 0.04-0.05 on these random inputs (3-bit mantissas of P and V; the outputs are
-    # means of ~T random values, so the relative error of the sum equals that of its terms), |d lse| <= 0.07
-    close(outs[True][0], ref, 1e-1, 1e-1, "fp8 attn fwd")
-    assert rms <= 0.075, rms
-    assert dlse <= 0.15, dlse
-    # the statistics feed the bf16 backward: gradients through the fp8 forward stay close to the exact ones
-    o8 = torch.empty(B * T, D, dtype=BF, device=DEV)
-    d = ops._attn_desc(qkv, qkv, qkv, o8, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D,
-                       fp8=True)
-    stats = ops.p_attn_fwd(d, qkv)
-    do = rnd(B * T, D, dtype=BF, seed=72)
-    dqkv = torch.zeros(B * T, 3 * D, dtype=BF, device=DEV)
-    d = ops._attn_desc(qkv, qkv, qkv, o8, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D)
-    ops.p_attn_bwd(d, stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D)
-    qg = qkv.float().view(B, T, 3, D).requires_grad_()
-    _attn_ref(qg[:, :, 0], qg[:, :, 1], qg[:, :, 2], H, causal).backward(do.float().view(B, T, D))
-    close(dqkv.view(B, T, 3, D), qg.grad, 1e-1, 2e-1, "bwd after fp8 fwd")
+    close(o.view(B, T, D), _attn_ref(qr[:, :, 0], qr[:, :, 1], qr[:, :, 2], H, causal), 2e-2, 2e-2, "bf16 attn fwd")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF])

@@ -73,21 +73,11 @@ def test_vitl14_336_f32_matches_oracle_and_bf16_is_bounded():
     # kernel outputs agree to the last bf16 digit almost everywhere, tools/debug/attn_fwd_check.py) - bounds cover both
     assert dl <= 0.06 and dlog <= 0.3 and agree >= 0.97
     assert 0.95 <= float(np.median(rat)) <= 1.05
-    # BASELINE configs[4] as first read: the e4m3 QK^T / PV forward in every self-attention block.  Round 5: slower than bf16 in
-    # every round, so the kernel left the default build (configs[4] runs bf16) - exercised in experiments builds
+    # BASELINE configs[4] as first read: the e4m3 QK^T / PV forward in every self-attention block.  Slower than bf16 in every
+    # round, so the kernel was removed (configs[4] runs bf16): the library refuses the flag
     from segclip_amd import _lib
-    try:
-        e = _run(torch.bfloat16, B, seed, attn_fp8=True)
-    except _lib.Unsupported:
-        print("[vitl14_336] e4m3 attention forward: not in the default build")
-        return
-    dl8, dlog8 = abs(e["loss"] - f["loss"]), float((e["t2v"] - f["t2v"]).abs().max())
-    agree8 = float((e["hard_idx"] == f["hard_idx"]).float().mean())
-    rat8 = [e["gn"][n] / f["gn"][n] for n in f["gn"] if f["gn"][n] > 1e-6]
-    print(f"[vitl14_336 B={B}] bf16 + fp8 attention forward vs f32: d loss {dl8:.2e}, max |dlogit| {dlog8:.4f}, hard_idx "
-          f"agreement {agree8:.4f}, grad-norm ratio median {np.median(rat8):.4f}")
-    assert dl8 <= 0.05 and dlog8 <= 0.5 and agree8 >= 0.9
-    assert 0.9 <= float(np.median(rat8)) <= 1.1
+    with pytest.raises(_lib.Unsupported):
+        _run(torch.bfloat16, B, seed, attn_fp8=True)
 
 
 def test_vitl14_336_b128_the_benchmarked_size_properties():

@@ -13,4 +13,4 @@ def desc():
     return ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), False, 0, D, 2 * D)
 ops.p_attn_fwd(desc(), qkv)
 t = timeit(lambda: ops.p_attn_fwd(desc(), qkv))
-print(f"PF={os.environ.get('SEGCLIP_ATTN_FWD_PF')} ABL={os.environ.get('SEGCLIP_ATTN_PF_ABL')} GRID={os.environ.get('SEGCLIP_ATTN_FWD_GRID')}: fwd {t*1e6:7.1f} us")
+print(f"PF={os.environ.get('SEGCLIP_ATTN_FWD_PF')} GRID={os.environ.get('SEGCLIP_ATTN_FWD_GRID')}: fwd {t*1e6:7.1f} us")

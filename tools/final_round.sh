@@ -17,12 +17,6 @@ timeout 300 python tools/bench_hbm.py 2>&1 | grep -v "$F" > $OUT/hbm_kernels.txt
 timeout 300 python tools/bench_gemm.py 2>&1 | grep -v "$F" > $OUT/gemm_shapes.txt
 timeout 300 python tools/bench_gemm.py 19712 text 2>&1 | grep -v "$F" >> $OUT/gemm_shapes.txt
 timeout 200 python tools/bench_attn.py 2>&1 | grep -v "$F" > $OUT/attn.txt
-# main-loop ablations: only meaningful with a library built with `build.sh -DSEGCLIP_P8_ABLATIONS`
-if nm -D segclip_amd/libsegclip_hip.so | grep -q segclip_p8_launch_abl1; then
-  for a in 0 1 2 3 4; do SEGCLIP_P8_ABL=$a timeout 200 python tools/bench_gemm_abl.py 2>&1 | grep "ABL="; done > $OUT/gemm_ablation.txt
-else
-  echo "library built without -DSEGCLIP_P8_ABLATIONS: ablations skipped" > $OUT/gemm_ablation.txt
-fi
 timeout 300 python tools/bench_train_tail.py 2>&1 | grep -v "$F" > $OUT/train_tail.txt
 timeout 300 python tools/debug/gradsync_cost.py 2>&1 | grep "ms/step" > $OUT/gradsync_cost.txt
 bash tools/pmc_attn.sh $OUT/pmc_attn > $OUT/pmc_attn.log 2>&1
@@ -30,4 +24,4 @@ export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_dist -o bench -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --force-dist > $OUT/bench_dist_prof.json 2> $OUT/bench_dist_prof.err
 python tools/prof_summary.py $(ls $OUT/prof_dist/*.db | head -1) 40 > $OUT/kernel_stats_dist.txt 2>&1
 grep -i "nccl\|rccl\|cast\|AllReduce" $OUT/kernel_stats_dist.txt | cut -c1-150
-cat $OUT/hbm_kernels.txt $OUT/attn.txt $OUT/gemm_ablation.txt $OUT/train_tail.txt $OUT/gradsync_cost.txt
+cat $OUT/hbm_kernels.txt $OUT/attn.txt $OUT/train_tail.txt $OUT/gradsync_cost.txt
