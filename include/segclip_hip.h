@@ -218,8 +218,13 @@ typedef struct segclip_attn_desc {
   void* colsum_part;
   /* nullable: int32 [B] number of valid keys per sample (keys >= klen[b] are masked out).  The key-padding mask of the
    * text-MAE decoder blocks, modules/module_mae.py:213-219: (1 - attention_mask) * -1e6 added to the logits, where
-   * attention_mask is a prefix mask (captions are padded at the end) and exp(-1e6) == 0 in fp32.  Sequences of at most
-   * 256 keys. */
+   * attention_mask is a prefix mask (captions are padded at the end) and exp(-1e6) == 0 in fp32.
+   * The forward accepts klen at any length (but never takes the at-most-8-queries kernel with it); the bf16 backward needs
+   * at most 256 queries and keys and refuses longer ones with SEGCLIP_ERR_INVALID.  1 <= klen[b] (the reference always has
+   * a CLS key; klen[b] == 0 is outside the contract), values above Tk mean Tk.  A masked key is still loaded and enters
+   * the products with a probability of exactly 0, as in the reference (which multiplies it by exp(-1e6) == 0), so K and V
+   * must hold finite values at masked keys; rows at or beyond Tq / Tk are never used.
+   * causal with Tq != Tk is defined on every path: query q sees keys 0 .. min(q, Tk - 1) (indices aligned at 0). */
   const int32_t* klen;
 } segclip_attn_desc;
 
@@ -590,6 +595,38 @@ typedef struct segclip_gemm_route {
   int32_t variant;
 } segclip_gemm_route;
 int segclip_gemm_last_route(segclip_gemm_route* out);
+
+/* ------------------------------------------------------------------------------------------
+ * Test hook: which attention kernel instance the last segclip_attn_fwd / segclip_attn_bwd call on the calling thread launched
+ * (one host-side store per launch; nothing on the GPU).  Every call clears the record first, so after a forward bwd_kernel
+ * is NONE and after a backward fwd_kernel is NONE.  A call that launched nothing (B or Tq = 0, an error, the refused
+ * SEGCLIP_ATTN_FP8 flag) leaves both NONE, and segclip_attn_last_route then returns SEGCLIP_ERR_UNSUPPORTED (out is filled
+ * either way).  The fp32 path records F32 here and its inner products through segclip_gemm_last_route.
+ *   tiles   : 32-row tiles of the longer of Tq, Tk (PF / DQW: the template argument NT; GENERIC: query tiles)
+ *   variant : PF      : bit 0 = the causal instance
+ *             GENERIC : bit 0 = output rows staged through LDS, bits 8-15 = waves (query tiles) per workgroup
+ *             DQW     : bit 0 = MULTI (key chunks of 224, fp32 dQ workspace)
+ *             SP      : bit 0 = the masked instance (causal and / or klen)
+ *             TWOPASS : bits 8-15 = waves per workgroup
+ *             others  : 0
+ * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_ATTN_ROUTE_NONE 0
+#define SEGCLIP_ATTN_ROUTE_SMALLQ 1  /* fwd, bwd: at most 8 queries, one wave per (batch, head) (attention_smallq.inc) */
+#define SEGCLIP_ATTN_ROUTE_PF 2      /* fwd: persistent kernel with a loader wave, 3 / 6 / 7 tiles (attention_pf.inc) */
+#define SEGCLIP_ATTN_ROUTE_GENERIC 3 /* fwd: attn_fwd_bf16_kernel, any Tq, Tk (attention.hip) */
+#define SEGCLIP_ATTN_ROUTE_F32 4     /* fwd, bwd: fp32 GEMMs + row softmax kernels */
+#define SEGCLIP_ATTN_ROUTE_DQW 5     /* bwd: query tiles as a stream with a dQ wave (attention_dqw.inc) */
+#define SEGCLIP_ATTN_ROUTE_STREAM 6  /* bwd: dkv_stream + dq_stream, more than 256 tokens (attention_stream.inc) */
+#define SEGCLIP_ATTN_ROUTE_SPL 7     /* bwd: single pass with a loader wave, 5-7 tiles, head_dim 64 (attention_spl.inc) */
+#define SEGCLIP_ATTN_ROUTE_SP 8      /* bwd: single pass, one wave per key tile (attention_sp.inc) */
+#define SEGCLIP_ATTN_ROUTE_TWOPASS 9 /* bwd: attn_bwd_bf16_kernel, Tq != Tk, both at most 256 (attention.hip) */
+typedef struct segclip_attn_route {
+  int32_t fwd_kernel;
+  int32_t bwd_kernel;
+  int32_t tiles;
+  int32_t variant;
+} segclip_attn_route;
+int segclip_attn_last_route(segclip_attn_route* out);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,15 @@ class GemmRoute(C.Structure):
 GEMM_ROUTE_FAMILIES = {0: None, 1: "generic", 2: "dma", 3: "p8", 4: "pq", 5: "f32"}
 
 
+class AttnRoute(C.Structure):
+    _fields_ = [("fwd_kernel", i32), ("bwd_kernel", i32), ("tiles", i32), ("variant", i32)]
+
+
+# segclip_attn_route.fwd_kernel / bwd_kernel
+ATTN_ROUTE_KERNELS = {0: None, 1: "smallq", 2: "pf", 3: "generic", 4: "f32", 5: "dqw", 6: "stream", 7: "spl", 8: "sp",
+                      9: "twopass"}
+
+
 class ReduceEntry(C.Structure):
     _fields_ = [("src", vp), ("out0", vp), ("out1", vp), ("out2", vp), ("rows", i64), ("width", i64), ("ld", i64), ("seg", i64),
                 ("scale", f32), ("out_dtype", i32)]
@@ -113,6 +122,7 @@ SIGNATURES = {
     "segclip_attn_bwd_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
     "segclip_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
     "segclip_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
+    "segclip_attn_last_route": (C.c_int, [C.POINTER(AttnRoute)]),
     "segclip_resblock_fwd": (C.c_int, [C.POINTER(ResBlockFwdDesc), vp]),
     "segclip_cast": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp]),
     "segclip_split3_bf16": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp]),

@@ -696,6 +696,7 @@ int launch_fwd_pf(const FwdArgs& a, int nitems, hipStream_t stream) {
   const int grid = nitems < cap ? nitems : cap;
   hipLaunchKernelGGL((attn_fwd_pf_kernel<NT, CAUSAL>), dim3((unsigned)grid), dim3((NT + 1) * 64), lds, stream, a, nitems);
   SEGCLIP_CHECK_LAUNCH("attn_fwd_pf");
+  segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_PF, NT, CAUSAL ? 1 : 0);
   return 0;
 }
 
@@ -712,6 +713,7 @@ int launch_bwd_dqw(const BwdArgs& a, int ncu, int dev, hipStream_t stream) {
   const int grid = a.nitems < ncu ? a.nitems : ncu;
   hipLaunchKernelGGL((attn_bwd_dqw_bf16_kernel<NT, MULTI>), dim3((unsigned)grid), dim3((NT + 1) * 64), bwd_dqw_lds_bytes<NT>(), stream, a);
   SEGCLIP_CHECK_LAUNCH("attn_bwd_dqw_bf16");
+  segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_DQW, NT, MULTI ? 1 : 0);
   return 0;
 }
 
@@ -741,6 +743,7 @@ extern "C" size_t segclip_attn_bwd_ws_bytes(const segclip_attn_desc* d) {
 
 extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_NONE, 0, 0);
   SEGCLIP_REQUIRE(d->hd <= 64 && d->hd > 0, "attn: head_dim %lld unsupported (<=64)", (long long)d->hd);
   SEGCLIP_REQUIRE(d->stats != nullptr, "attn_fwd: stats buffer required");
   if (d->B == 0 || d->Tq == 0) return 0;
@@ -764,6 +767,7 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
       hipLaunchKernelGGL(smallq::attn_smallq_fwd_kernel, dim3((unsigned)cdiv(nitems, smallq::WPB_FWD)), dim3(smallq::WPB_FWD * 64),
                          smallq::lds_bytes((int)d->Tk, false), stream, a, nitems);
       SEGCLIP_CHECK_LAUNCH("attn_smallq_fwd");
+      segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0);
       return 0;
     }
     const int tiles = (int)cdiv(d->Tq, 32);
@@ -792,6 +796,7 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
     hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3((unsigned)cdiv(tiles, nw), (unsigned)(d->B * d->H)), dim3(nw * 64), 0,
                        stream, a);
     SEGCLIP_CHECK_LAUNCH("attn_fwd_bf16");
+    segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_GENERIC, tiles, (a.staged ? 1 : 0) | nw << 8);
     return 0;
   }
   // f32: S -> stats, softmax in place, O = P V
@@ -813,11 +818,14 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
   g.sam = d->Tk; g.sak = 1; g.sbn = 1; g.sbk = d->v_st; g.ldc = d->o_st;
   g.bsA1 = d->H * d->Tq * d->Tk; g.bsA2 = d->Tq * d->Tk; g.bsB1 = d->v_sb; g.bsB2 = d->hd;
   g.bsC1 = d->o_sb; g.bsC2 = d->hd;
-  return segclip_gemm_f32_launch(&g, stream);
+  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
+  segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_F32, (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32), 0);
+  return 0;
 }
 
 extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_NONE, 0, 0);
   SEGCLIP_REQUIRE(d->hd <= 64 && d->hd > 0, "attn: head_dim %lld unsupported (<=64)", (long long)d->hd);
   if (d->B == 0 || d->Tq == 0) return 0;
   if (d->dtype == SEGCLIP_BF16) {
@@ -841,6 +849,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
       hipLaunchKernelGGL(smallq::attn_smallq_bwd_kernel, dim3((unsigned)cdiv(a.nitems, smallq::WPB_BWD)), dim3(smallq::WPB_BWD * 64),
                          smallq::lds_bytes((int)d->Tk, true), stream, a, a.nitems);
       SEGCLIP_CHECK_LAUNCH("attn_smallq_bwd");
+      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0);
       return 0;
     }
     if (d->Tq > TMAX || d->Tk > TMAX) {
@@ -874,6 +883,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
       hipLaunchKernelGGL(attn_bwd_dq_stream_kernel, dim3((unsigned)(d->B * d->H), (unsigned)cdiv(qtiles, nwq)),
                          dim3(nwq * 64), lds, stream, a, (const float*)d->ws);
       SEGCLIP_CHECK_LAUNCH("attn_bwd_dq_stream");
+      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_STREAM, qtiles > ktiles ? qtiles : ktiles, 0);
       return 0;
     }
     const int tiles = (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32);
@@ -920,7 +930,10 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
       // vision tower (no mask, 5-7 tiles): the variant whose memory traffic is issued by a loader wave (attention_spl.inc);
       // SEGCLIP_ATTN_BWD_SPL=0 keeps attention_sp.inc
       static const int use_spl = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_SPL"); return e ? atoi(e) : 1; }();
-      if (use_spl && !masked && tiles >= 5 && tiles <= 7 && bwd_spl_lds_bytes((int)d->Tq) <= 160 * 1024) {
+      // head_dim 64 only: its loader wave copies whole 128-byte rows of Q, so with a smaller head the columns beyond it (the next
+      // head, or whatever follows the last one) would enter S = K Q^T against zeroed K columns: 0 x NaN, and a read past the
+      // end of a separately allocated Q.  Smaller heads take attention_sp.inc, which selects by column.
+      if (use_spl && !masked && d->hd == 64 && tiles >= 5 && tiles <= 7 && bwd_spl_lds_bytes((int)d->Tq) <= 160 * 1024) {
         static bool spl_attr_set[64] = {};
         if (!spl_attr_set[dev]) {
           hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_spl_bf16_kernel),
@@ -932,6 +945,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
         if (g2 > a.nitems) g2 = a.nitems;
         hipLaunchKernelGGL(attn_bwd_spl_bf16_kernel, dim3((unsigned)g2), dim3((tiles + 1) * 64), bwd_spl_lds_bytes((int)d->Tq), stream, a);
         SEGCLIP_CHECK_LAUNCH("attn_bwd_spl_bf16");
+        segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SPL, tiles, 0);
         return 0;
       }
       if (masked)
@@ -939,6 +953,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
       else
         hipLaunchKernelGGL(attn_bwd_sp_bf16_kernel<false>, dim3((unsigned)grid), dim3(tiles * 64), lds_sp, stream, a);
       SEGCLIP_CHECK_LAUNCH("attn_bwd_sp_bf16");
+      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SP, tiles, masked ? 1 : 0);
       return 0;
     }
     // 4 waves per workgroup (each wave walks over 1-2 tiles): two such workgroups fit the registers (2 waves per SIMD
@@ -958,6 +973,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
     }
     hipLaunchKernelGGL(attn_bwd_bf16_kernel, dim3((unsigned)(d->B * d->H)), dim3(nw * 64), lds, stream, a);
     SEGCLIP_CHECK_LAUNCH("attn_bwd_bf16");
+    segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_TWOPASS, tiles, nw << 8);
     return 0;
   }
   SEGCLIP_REQUIRE(d->colsum_part == nullptr, "attn_bwd f32: colsum_part is a bf16-path feature");
@@ -994,5 +1010,7 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
   g.A = dP; g.B = d->Q; g.C = d->dK; g.M = d->Tk; g.N = d->hd; g.K = d->Tq;
   g.sam = 1; g.sak = d->Tk; g.sbn = 1; g.sbk = d->q_st; g.ldc = d->dk_st;
   g.bsA1 = pz1; g.bsA2 = pz2; g.bsB1 = d->q_sb; g.bsB2 = d->hd; g.bsC1 = d->dk_sb; g.bsC2 = d->hd;
-  return segclip_gemm_f32_launch(&g, stream);
+  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
+  segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_F32, (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32), 0);
+  return 0;
 }

@@ -42,6 +42,17 @@ extern "C" int segclip_gemm_last_route(segclip_gemm_route* out) {
   return g_route.family == SEGCLIP_GEMM_ROUTE_NONE ? SEGCLIP_ERR_UNSUPPORTED : 0;
 }
 
+static thread_local segclip_attn_route g_attn_route = {SEGCLIP_ATTN_ROUTE_NONE, SEGCLIP_ATTN_ROUTE_NONE, 0, 0};
+
+void segclip_attn_route_note(bool bwd, int kernel, int tiles, int variant) {
+  g_attn_route = segclip_attn_route{bwd ? SEGCLIP_ATTN_ROUTE_NONE : kernel, bwd ? kernel : SEGCLIP_ATTN_ROUTE_NONE, tiles, variant};
+}
+
+extern "C" int segclip_attn_last_route(segclip_attn_route* out) {
+  if (out) *out = g_attn_route;
+  return g_attn_route.fwd_kernel == SEGCLIP_ATTN_ROUTE_NONE && g_attn_route.bwd_kernel == SEGCLIP_ATTN_ROUTE_NONE ? SEGCLIP_ERR_UNSUPPORTED : 0;
+}
+
 extern "C" int segclip_gemm(const segclip_gemm_desc* d, void* stream) {
   g_route = segclip_gemm_route{SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
   SEGCLIP_REQUIRE(d != nullptr, "gemm: null descriptor");

@@ -548,9 +548,22 @@ def _attn_desc(q, k, v, o, B, H, Tq, Tk, hd, qs, ks, vs, os_, scale, causal, q_o
     return d
 
 
-def p_attn_fwd(d, like):
+AttnRoute = collections.namedtuple("AttnRoute", "fwd_kernel bwd_kernel tiles variant")
+
+
+def attn_last_route():
+    """The kernel instance the last segclip_attn_fwd / segclip_attn_bwd call of this thread launched
+    (include/segclip_hip.h: segclip_attn_last_route): kernels by name, None in the direction that did not run."""
+    r = L.AttnRoute()
+    L.load().segclip_attn_last_route(C.byref(r))
+    return AttnRoute(L.ATTN_ROUTE_KERNELS[r.fwd_kernel], L.ATTN_ROUTE_KERNELS[r.bwd_kernel], r.tiles, r.variant)
+
+
+def p_attn_fwd(d, like, stats=None):
+    """stats: optional fp32 buffer of segclip_attn_stats_bytes (the tests hand in one inside a sentinel frame)"""
     lib = L.load()
-    stats = torch.empty(max(lib.segclip_attn_stats_bytes(C.byref(d)) // 4, 1), dtype=torch.float32, device=like.device)
+    if stats is None:
+        stats = torch.empty(max(lib.segclip_attn_stats_bytes(C.byref(d)) // 4, 1), dtype=torch.float32, device=like.device)
     d.stats = L.ptr(stats)
     if _OpCount.enabled:   # QK^T + PV (causal: half), Q K V read + O written
         fl = 4.0 * d.B * d.H * d.Tq * d.Tk * d.hd * (0.5 if d.causal else 1.0)
@@ -559,8 +572,9 @@ def p_attn_fwd(d, like):
     return stats
 
 
-def p_attn_bwd(d, stats, do, dq, dk, dv, dqs, dks, dvs, dos, dq_off=0, dk_off=0, dv_off=0, colsum_part=None):
-    """colsum_part (bf16 path only): fp32 (B, 3*H*hd) buffer that receives the per-sample token sums of dQ|dK|dV."""
+def p_attn_bwd(d, stats, do, dq, dk, dv, dqs, dks, dvs, dos, dq_off=0, dk_off=0, dv_off=0, colsum_part=None, ws=None):
+    """colsum_part (bf16 path only): fp32 (B, 3*H*hd) buffer that receives the per-sample token sums of dQ|dK|dV.
+    ws: optional workspace of at least segclip_attn_bwd_ws_bytes bytes (default: allocated here, uninitialised)."""
     lib = L.load()
     d.stats = L.ptr(stats)
     d.colsum_part = L.ptr(colsum_part)
@@ -570,7 +584,10 @@ def p_attn_bwd(d, stats, do, dq, dk, dv, dqs, dks, dvs, dos, dq_off=0, dk_off=0,
     d.dv_sb, d.dv_st = dvs
     d.do_sb, d.do_st = dos
     nbytes = lib.segclip_attn_bwd_ws_bytes(C.byref(d))
-    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=do.device)
+    if ws is None:
+        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=do.device)
+    elif ws.numel() * ws.element_size() < nbytes:
+        raise ValueError(f"attention backward: workspace of {ws.numel() * ws.element_size()} bytes, {nbytes} needed")
     d.ws = L.ptr(ws)
     if _OpCount.enabled:   # S, dP, dV, dK, dQ = 2.5 x forward; Q K V O dO read + dQ dK dV written
         fl = 10.0 * d.B * d.H * d.Tq * d.Tk * d.hd * (0.5 if d.causal else 1.0)
