@@ -396,6 +396,60 @@ int segclip_reduce_sum(const float* x, float* out, int64_t n, float scale, void*
 int segclip_interp_bicubic(const float* src, float* dst, int64_t n_in, int64_t h, int64_t w, int64_t D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Zero-shot segmentation inference (segment.hip): class prompts + the center stage's soft assignment -> label map.
+ * Forward only; all math fp32.  A "window" is one image handed to the vision tower: the whole image, or one crop of mmseg's
+ * sliding-window grid; all windows of a call have the same size (win_h, win_w) and the same patch grid (grid_h, grid_w).
+ *
+ * segclip_seg_group_table: per window the G x N group-class table of ViTSegInference.encode_decode
+ * (seg_segmentation/evaluation/vit_seg.py:218-254).  One workgroup per window, latency-bound.
+ *   group_tokens : row r of window w at group_tokens + w * group_stride + r * C   (= patch_features[:, 1:, :], :214)
+ *   pooled       : window w at pooled + w * pooled_stride                          (= image_features, :215)
+ *   text         : (N, C), already L2-normalised (evaluation/builder.py:59-66);  logit_scale: device scalar,
+ *                  clamp(exp(.), max=100) applied inside (:232)
+ *   F.normalize of the G + 1 rows (:221-222); logits = cosines * scale (:234, :237); pre = softmax of the group logits
+ *   (:235); softmax of the pooled row and its top-`topk` classes (:238-241; the reference passes min(5, N)) - among EQUAL
+ *   probabilities the LOWEST class index is kept (torch.topk leaves ties unspecified); group logits outside the mask
+ *   -> -inf, softmax (:242-244), times pre (:247).
+ *   table (W, G, N);  table_max (W) = its maximum (the device-side operand of min(bg_thresh, .), :253 without the .item()
+ *   synchronisation);  best_class (W, G) = first maximum over N of each row, best_score (W, G) its value;
+ *   topk_mask (W, N) uint8 or NULL.
+ *   SEGCLIP_ERR_UNSUPPORTED: ((G + 1) * (C + N) + 2 N + 8) * 4 bytes exceed 64 KiB of LDS.  G <= 8.
+ *
+ * segclip_seg_label_map: the fused pixel kernel.  For every output pixel and every window covering it: the G channels of
+ * soft_attn (W, G, grid_h * grid_w) interpolated with F.interpolate(mode="bilinear", align_corners=False) semantics in
+ * ATen's fp32 operation order (vit_seg.py:54 and :191), first maximum over G (:225).  One covering window: label =
+ * best_score < min(bg_thresh, table_max) ? 0 : best_class + 1 with background (:252-254), best_class without.  Several
+ * (mmseg slide_inference): class logits = sum over the windows, in window order, of the window's table row (class 0: its
+ * background indicator) / window count; first maximum.  labels (B, H, W) uint8 (NULL = skip; N + with_bg > 256:
+ * SEGCLIP_ERR_UNSUPPORTED), groups (B, H, W) uint8 (NULL = skip) = the group in the first covering window (what
+ * show_result(vis_mode="final_group") draws, :346-375).  A pixel no window covers gets label 0, group 0.
+ *   windows     : (n_windows, 3) int32 rows (image, y0, x0); the windows of one image are consecutive.  The kernels read y0
+ *                 and x0 only: which image a window belongs to comes from image_first alone, the image column is carried
+ *                 for the caller's bookkeeping and is IGNORED.
+ *   image_first : (B + 1) int32, windows image_first[b] .. image_first[b + 1] - 1 belong to image b
+ *   Limits of the device-side lists, which the host entry cannot inspect - what exceeds them is SILENTLY IGNORED, the caller
+ *   checks them (segclip_amd/segmentation.py does): at most 64 windows per image (later ones are dropped); at most 16
+ *   windows covering one pixel (later ones are dropped); with n_windows <= B every image is taken to have at most one
+ *   window covering a pixel (the block then keeps one slot and no table copy in LDS).  Out-of-range entries cannot make
+ *   the kernels read or write out of bounds.  Bound: HBM writes, 1-2 bytes per pixel.
+ *
+ * segclip_seg_logits: the dense output, logits (B, N + with_bg, H, W) fp32 exactly as encode_decode (:249-256) and
+ * slide_inference define them; same device functions as the label map, which is its first maximum over the classes.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_group_table(const float* group_tokens, int64_t group_stride, const float* pooled, int64_t pooled_stride,
+                            const float* text, const float* logit_scale, float* table, float* table_max,
+                            int32_t* best_class, float* best_score, uint8_t* topk_mask, int64_t n_windows, int64_t G,
+                            int64_t N, int64_t C, int64_t topk, void* stream);
+int segclip_seg_label_map(const float* soft_attn, const float* table, const float* table_max, const int32_t* best_class,
+                          const float* best_score, const int32_t* windows, const int32_t* image_first, int64_t n_windows,
+                          int64_t B, int64_t H, int64_t W, int64_t win_h, int64_t win_w, int64_t grid_h, int64_t grid_w,
+                          int64_t G, int64_t N, int with_bg, float bg_thresh, uint8_t* labels, uint8_t* groups, void* stream);
+int segclip_seg_logits(const float* soft_attn, const float* table, const float* table_max, const int32_t* best_class,
+                       const float* best_score, const int32_t* windows, const int32_t* image_first, int64_t n_windows,
+                       int64_t B, int64_t H, int64_t W, int64_t win_h, int64_t win_w, int64_t grid_h, int64_t grid_w,
+                       int64_t G, int64_t N, int with_bg, float bg_thresh, float* logits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MAE random masking (integer path, bit-exact given the noise).  modules/module_clip_util.py:91-124
  * with keep_cls: noise[:,0] = -1; ids_shuffle = argsort(noise) (stable); ids_restore =
  * argsort(ids_shuffle); mask = 1 except the first len_keep of the shuffle.

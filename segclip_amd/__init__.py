@@ -18,3 +18,12 @@ from . import config  # noqa: F401,E402
 from .config import set_compute_dtype, set_cross_mode, noise_injection  # noqa: F401,E402
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # zero-shot segmentation inference, imported on first use: `import segclip_amd` itself stays free of ops.py
+    if name in ("SegInference", "build_text_embedding", "segmentation"):
+        import importlib
+        mod = importlib.import_module(".segmentation", __name__)
+        return mod if name == "segmentation" else getattr(mod, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

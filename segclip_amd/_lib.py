@@ -160,6 +160,11 @@ SIGNATURES = {
     "segclip_masked_mse_bwd": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, i64, i64, i64, C.c_int, vp]),
     "segclip_mask_sort": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp]),
     "segclip_interp_bicubic": (C.c_int, [vp, vp, i64, i64, i64, i64, vp]),
+    "segclip_seg_group_table": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
+    "segclip_seg_label_map": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                        vp, vp, vp]),
+    "segclip_seg_logits": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                     vp, vp]),
     "segclip_multi_cast_bf16": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_multi_add_f32": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_max_tokens_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),

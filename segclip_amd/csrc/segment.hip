@@ -1,0 +1,383 @@
+// Zero-shot segmentation inference: class prompts + the center stage's soft assignment -> label map
+// (reference seg_segmentation/evaluation/vit_seg.py:202-256 [ViTSegInference.encode_decode], :30-58 [resize_attn_map], and
+// mmseg's slide_inference for overlapping windows).  Forward only, all math fp32: the outputs are arg-maxima.
+//
+// Every pixel's class logits are row g(pixel) of a G x N table per window, so the eager (H, W, G) upsampling, (H, W, G)
+// one-hot, (H, W, N) product and (N + 1, H, W) logit volume never have to exist: segclip_seg_group_table builds the tables
+// (latency-bound: G * N dot products of 512 per window), segclip_seg_label_map interpolates G numbers per pixel, takes the
+// first maximum and looks one row up (bound: 1-2 bytes of HBM writes per pixel).
+#include "common.h"
+
+#define SEG_MAX_G 8          // groups per window (the center stage has 8)
+#define SEG_MAX_COVER 16     // windows covering one pixel
+#define SEG_MAX_IMG_WIN 64   // windows per image
+#define SEG_TAB_FLOATS 8192  // LDS budget of the block's table copies
+
+namespace {
+
+#include "segment_pixel.inc"
+
+__device__ __forceinline__ float seg_clip_scale(const float* ls) { return fminf(expf(*ls), 100.f); }
+
+// lowest index wins among equal values
+__device__ __forceinline__ void wave_argmax_first(float& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+}
+
+// ---------------------------------------------------------------- (a) group-class table, one workgroup per window
+// LDS: rows (G + 1, C) normalised | logits (G + 1, N) | prob (N) | mask (N) | best (SEG_MAX_G)
+__global__ __launch_bounds__(256) void seg_group_table_kernel(const float* __restrict__ group_tokens, int64_t gt_stride,
+                                                              const float* __restrict__ pooled, int64_t pooled_stride,
+                                                              const float* __restrict__ text, const float* __restrict__ logit_scale,
+                                                              float* __restrict__ table, float* __restrict__ table_max,
+                                                              int32_t* __restrict__ best_class, float* __restrict__ best_score,
+                                                              uint8_t* __restrict__ topk_mask, int G, int N, int C, int topk) {
+  extern __shared__ float sm[];
+  float* rows = sm;
+  float* logit = rows + (G + 1) * C;
+  float* prob = logit + (G + 1) * N;
+  int* mask = reinterpret_cast<int*>(prob + N);
+  float* gbest = reinterpret_cast<float*>(mask + N);
+  const int64_t w = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // F.normalize(dim=-1): x / max(|x|, 1e-12)
+  for (int r = wave; r <= G; r += 4) {
+    const float* x = r < G ? group_tokens + w * gt_stride + (int64_t)r * C : pooled + w * pooled_stride;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s = fmaf(x[c], x[c], s);
+    const float nrm = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+    for (int c = lane; c < C; c += 64) rows[r * C + c] = x[c] / nrm;
+  }
+  __syncthreads();
+
+  const float sc = seg_clip_scale(logit_scale);
+  for (int n = wave; n < N; n += 4) {
+    const float* t = text + (int64_t)n * C;
+    float acc[SEG_MAX_G + 1];
+#pragma unroll
+    for (int r = 0; r <= SEG_MAX_G; ++r) acc[r] = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float tv = t[c];
+#pragma unroll
+      for (int r = 0; r <= SEG_MAX_G; ++r)
+        if (r <= G) acc[r] = fmaf(rows[r * C + c], tv, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r <= SEG_MAX_G; ++r)
+      if (r <= G) {
+        const float d = wave_sum(acc[r]);
+        if (lane == 0) logit[r * N + n] = d * sc;
+      }
+  }
+  for (int n = tid; n < N; n += 256) mask[n] = 0;
+  __syncthreads();
+
+  // softmax of the pooled row, then its top-k (ties: lowest class index) - wave 0, the block keeps step at the barriers
+  if (wave == 0) {
+    const float* x = logit + G * N;
+    float m = -INFINITY;
+    for (int n = lane; n < N; n += 64) m = fmaxf(m, x[n]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int n = lane; n < N; n += 64) s += expf(x[n] - m);
+    s = wave_sum(s);
+    for (int n = lane; n < N; n += 64) prob[n] = expf(x[n] - m) / s;
+  }
+  __syncthreads();
+  for (int k = 0; k < topk; ++k) {
+    if (wave == 0) {
+      float v = -INFINITY;
+      int i = 0x7fffffff;
+      for (int n = lane; n < N; n += 64)
+        if (!mask[n] && prob[n] > v) { v = prob[n]; i = n; }
+      wave_argmax_first(v, i);
+      if (lane == 0 && i < N) mask[i] = 1;
+    }
+    __syncthreads();
+  }
+  if (topk_mask)
+    for (int n = tid; n < N; n += 256) topk_mask[w * N + n] = (uint8_t)mask[n];
+
+  // per group: softmax over all classes x softmax over the kept classes
+  for (int g = wave; g < G; g += 4) {
+    const float* x = logit + g * N;
+    float m1 = -INFINITY, m2 = -INFINITY;
+    for (int n = lane; n < N; n += 64) {
+      m1 = fmaxf(m1, x[n]);
+      if (mask[n]) m2 = fmaxf(m2, x[n]);
+    }
+    m1 = wave_max(m1);
+    m2 = wave_max(m2);
+    float s1 = 0.f, s2 = 0.f;
+    for (int n = lane; n < N; n += 64) {
+      s1 += expf(x[n] - m1);
+      if (mask[n]) s2 += expf(x[n] - m2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int n = lane; n < N; n += 64) {
+      const float pre = expf(x[n] - m1) / s1;
+      const float v = mask[n] ? (expf(x[n] - m2) / s2) * pre : 0.f;
+      table[(w * G + g) * N + n] = v;
+      if (v > bv) { bv = v; bi = n; }
+    }
+    wave_argmax_first(bv, bi);
+    if (lane == 0) {
+      if (bi >= N) { bi = 0; bv = 0.f; }
+      best_class[w * G + g] = bi;
+      best_score[w * G + g] = bv;
+      gbest[g] = bv;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float m = gbest[0];
+    for (int g = 1; g < G; ++g) m = fmaxf(m, gbest[g]);
+    table_max[w] = m;
+  }
+}
+
+// ---------------------------------------------------------------- (b), (c) the pixel kernels
+struct SegPixelArgs {
+  const float* soft;         // (n_windows, G, gh * gw)
+  const float* table;        // (n_windows, G, N)
+  const float* table_max;    // (n_windows)
+  const int32_t* best_class; // (n_windows, G)
+  const float* best_score;   // (n_windows, G)
+  const int32_t* windows;    // (n_windows, 3): image, y0, x0; the windows of an image are consecutive
+  const int32_t* image_first;  // (B + 1): windows image_first[b] .. image_first[b + 1] - 1 belong to image b
+  int n_windows, B, H, W, win_h, win_w, gh, gw, G, N, with_bg;
+  int tab_floats, cover_slots;  // dynamic LDS layout (seg_lds)
+  float bg_thresh;
+  uint8_t* labels;  // (B, H, W) or null
+  uint8_t* groups;  // (B, H, W) or null
+  float* logits;    // (B, N + with_bg, H, W)   [LOGITS kernel]
+};
+
+// A lane owns PPL consecutive pixels of one row; the units of an image are numbered row by row, so with W a multiple of 4
+// a wave of the label kernel stores 256 consecutive bytes (one dword per lane), and a wave of the logits kernel (PPL = 1)
+// stores 64 consecutive floats per class.
+template <int PPL, bool LOGITS>
+__global__ __launch_bounds__(256) void seg_pixel_kernel(SegPixelArgs A) {
+  __shared__ int s_wy[SEG_MAX_IMG_WIN], s_wx[SEG_MAX_IMG_WIN], s_wi[SEG_MAX_IMG_WIN], s_row[SEG_MAX_IMG_WIN];
+  __shared__ int s_n;
+  __shared__ uint8_t s_bg[SEG_MAX_IMG_WIN * SEG_MAX_G];
+  __shared__ uint8_t s_lab[SEG_MAX_IMG_WIN * SEG_MAX_G];
+  // dynamic LDS, sized by the host: A.tab_floats floats of table copies, then A.cover_slots * 256 covering-window entries
+  // (one window per image and labels only: no table copy and one slot, so the block's LDS does not limit the occupancy)
+  extern __shared__ float s_dyn[];
+  float* s_tab = s_dyn;
+  uint16_t* s_cov = reinterpret_cast<uint16_t*>(s_dyn + A.tab_floats);
+
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int upr = (A.W + PPL - 1) / PPL;  // units per row
+  const int64_t total = (int64_t)A.H * upr;
+  const int64_t u0 = (int64_t)blockIdx.x * 256;
+  const int y_lo = (int)(u0 / upr);
+  const int64_t u_last = u0 + 255 < total - 1 ? u0 + 255 : total - 1;
+  const int y_hi = (int)(u_last / upr);
+  const int off = A.with_bg ? 1 : 0;
+
+  // the image's windows that touch this block's rows, in window order (at most 64 = one wave: ordered compaction by ballot)
+  if (tid < 64) {
+    int first = A.image_first[b], last = A.image_first[b + 1];
+    first = first < 0 ? 0 : (first > A.n_windows ? A.n_windows : first);
+    last = last < first ? first : (last > A.n_windows ? A.n_windows : last);
+    const int cnt = last - first < SEG_MAX_IMG_WIN ? last - first : SEG_MAX_IMG_WIN;
+    bool p = false;
+    int wy = 0, wx = 0;
+    if (tid < cnt) {
+      wy = A.windows[3 * (first + tid) + 1];
+      wx = A.windows[3 * (first + tid) + 2];
+      p = wy <= y_hi && wy + A.win_h > y_lo;
+    }
+    const unsigned long long m = __ballot(p);
+    if (p) {
+      const int pos = __popcll(m & ((1ull << tid) - 1ull));
+      s_wy[pos] = wy; s_wx[pos] = wx; s_wi[pos] = first + tid;
+    }
+    if (tid == 0) s_n = __popcll(m);
+  }
+  __syncthreads();
+  const int nwin = s_n;
+  // per (window, group): background indicator and the single-window label
+  for (int i = tid; i < nwin * A.G; i += 256) {
+    const int k = i / A.G, g = i % A.G;
+    const int64_t wg = (int64_t)s_wi[k] * A.G + g;
+    const float score = A.best_score[wg];
+    const bool bg = A.with_bg && score < fminf(A.bg_thresh, A.table_max[s_wi[k]]);
+    s_bg[k * SEG_MAX_G + g] = bg ? 1 : 0;
+    // = the first maximum of [bg, row]: bg = 1 beats every table entry (score < table_max <= 1); an all-zero row gives 0
+    s_lab[k * SEG_MAX_G + g] = (uint8_t)(A.with_bg ? ((bg || !(score > 0.f)) ? 0 : A.best_class[wg] + 1) : A.best_class[wg]);
+  }
+  // the tables of these windows in LDS when they fit (overlaps and the dense logits read N entries per pixel from them)
+  const bool want_tab = LOGITS || nwin > 1;
+  const bool staged = want_tab && (int64_t)nwin * A.G * A.N <= A.tab_floats;
+  if (staged) {
+    const int per = A.G * A.N;
+    for (int i = tid; i < nwin * per; i += 256) s_tab[i] = A.table[(int64_t)s_wi[i / per] * per + i % per];
+  }
+  for (int k = tid; k < nwin; k += 256) s_row[k] = staged ? k : s_wi[k];
+  __syncthreads();
+
+  SegBlockWindows bw = {s_wy, s_wx, s_wi, nwin};
+  SegTables tb = {staged ? (const float*)s_tab : A.table, s_row, s_bg, A.G, A.N, off};
+  const float sy = (float)A.gh / (float)A.win_h, sx = (float)A.gw / (float)A.win_w;
+
+  const int64_t unit = u0 + tid;
+  if (unit >= total) return;
+  const int y = (int)(unit / upr);
+  const int xq = (int)(unit % upr) * PPL;
+  uint32_t lab_pack = 0, grp_pack = 0;
+#pragma unroll
+  for (int p = 0; p < PPL; ++p) {
+    const int x = xq + p;
+    if (x >= A.W) break;
+    const int cnt = seg_pixel_cover(bw, A.soft, y, x, A.win_h, A.win_w, A.gh, A.gw, A.G, sy, sx, s_cov, A.cover_slots, tid);
+    if (LOGITS) {
+      const int64_t plane = (int64_t)A.H * A.W;
+      float* o = A.logits + (int64_t)b * (A.N + off) * plane + (int64_t)y * A.W + x;
+      for (int c = 0; c < A.N + off; ++c) o[c * plane] = cnt ? seg_class_logit(tb, c, cnt, s_cov, tid) : 0.f;
+    } else {
+      int lab = 0, grp = 0;
+      if (cnt >= 1) {
+        const int e = s_cov[tid];
+        grp = e & 255;
+        if (cnt == 1) {
+          lab = s_lab[(e >> 8) * SEG_MAX_G + grp];
+        } else if (A.labels) {
+          float best = -INFINITY;
+          for (int c = 0; c < A.N + off; ++c) {
+            const float v = seg_class_logit(tb, c, cnt, s_cov, tid);
+            if (v > best) { best = v; lab = c; }
+          }
+        }
+      }
+      lab_pack |= (uint32_t)(lab & 255) << (8 * p);
+      grp_pack |= (uint32_t)grp << (8 * p);
+    }
+  }
+  if (!LOGITS) {
+    const int64_t o = ((int64_t)b * A.H + y) * A.W + xq;
+    const bool dword = PPL == 4 && (A.W & 3) == 0 && ((reinterpret_cast<uintptr_t>(A.labels) | reinterpret_cast<uintptr_t>(A.groups)) & 3) == 0;
+    if (dword) {  // rows are dword multiples on dword boundaries: one 4-byte store per lane
+      if (A.labels) *reinterpret_cast<uint32_t*>(A.labels + o) = lab_pack;
+      if (A.groups) *reinterpret_cast<uint32_t*>(A.groups + o) = grp_pack;
+    } else {
+      for (int p = 0; p < PPL && xq + p < A.W; ++p) {
+        if (A.labels) A.labels[o + p] = (uint8_t)(lab_pack >> (8 * p));
+        if (A.groups) A.groups[o + p] = (uint8_t)(grp_pack >> (8 * p));
+      }
+    }
+  }
+}
+
+int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, int64_t W, int64_t win_h, int64_t win_w,
+                    int64_t gh, int64_t gw, int64_t G, int64_t N) {
+  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && H >= 1 && W >= 1 && win_h >= 1 && win_w >= 1 && gh >= 1 && gw >= 1 && N >= 1,
+                  "%s: sizes must be positive", what);
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= 65535 && n_windows <= (1 << 24) && H * W < (1ll << 31) && gh * gw * G < (1ll << 31) && N <= (1 << 20),
+                  "%s: size out of range", what);
+  return 0;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int segclip_seg_group_table(const float* group_tokens, int64_t group_stride, const float* pooled, int64_t pooled_stride,
+                                       const float* text, const float* logit_scale, float* table, float* table_max,
+                                       int32_t* best_class, float* best_score, uint8_t* topk_mask, int64_t n_windows, int64_t G,
+                                       int64_t N, int64_t C, int64_t topk, void* stream) {
+  SEGCLIP_REQUIRE(n_windows >= 0 && N >= 1 && C >= 1 && topk >= 1 && topk <= N, "seg_group_table: need N, C >= 1 and 1 <= topk <= N");
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "seg_group_table: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
+  const int64_t lds = ((G + 1) * C + (G + 1) * N + 2 * N + SEG_MAX_G) * 4;
+  if (lds > 64 * 1024) {
+    segclip_set_error("seg_group_table: N=%lld classes x C=%lld need %lld bytes of LDS (64 KiB available)", (long long)N, (long long)C,
+                      (long long)lds);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (n_windows == 0) return 0;
+  hipLaunchKernelGGL(seg_group_table_kernel, dim3((unsigned)n_windows), dim3(256), (size_t)lds, ST, group_tokens, group_stride, pooled,
+                     pooled_stride, text, logit_scale, table, table_max, best_class, best_score, topk_mask, (int)G, (int)N, (int)C,
+                     (int)topk);
+  SEGCLIP_CHECK_LAUNCH("seg_group_table");
+  return 0;
+}
+
+static SegPixelArgs seg_args(const float* soft_attn, const float* table, const float* table_max, const int32_t* best_class,
+                             const float* best_score, const int32_t* windows, const int32_t* image_first, int64_t n_windows, int64_t B,
+                             int64_t H, int64_t W, int64_t win_h, int64_t win_w, int64_t gh, int64_t gw, int64_t G, int64_t N,
+                             int with_bg, float bg_thresh) {
+  SegPixelArgs a;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
+  a.windows = windows; a.image_first = image_first;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.H = (int)H; a.W = (int)W; a.win_h = (int)win_h; a.win_w = (int)win_w;
+  a.gh = (int)gh; a.gw = (int)gw; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
+  a.labels = nullptr; a.groups = nullptr; a.logits = nullptr;
+  return a;
+}
+
+// LDS of a pixel-kernel block.  With one window per image (n_windows <= B) a pixel has one covering window and the label
+// kernel never reads a table row: no table copy, one slot.  Otherwise the tables of up to all windows of an image, capped.
+static size_t seg_lds(SegPixelArgs& a, bool logits) {
+  const bool multi = a.n_windows > a.B;
+  a.cover_slots = multi ? SEG_MAX_COVER : 1;
+  int64_t want = 0;
+  if (logits || multi) {
+    const int64_t per_image = multi ? (a.n_windows + a.B - 1) / a.B : 1;
+    want = (per_image < SEG_MAX_IMG_WIN ? per_image : SEG_MAX_IMG_WIN) * a.G * a.N;
+    if (want > SEG_TAB_FLOATS) want = SEG_TAB_FLOATS;
+  }
+  a.tab_floats = (int)((want + 1) & ~1ll);
+  return (size_t)a.tab_floats * 4 + (size_t)a.cover_slots * 256 * 2;
+}
+
+extern "C" int segclip_seg_label_map(const float* soft_attn, const float* table, const float* table_max, const int32_t* best_class,
+                                     const float* best_score, const int32_t* windows, const int32_t* image_first, int64_t n_windows,
+                                     int64_t B, int64_t H, int64_t W, int64_t win_h, int64_t win_w, int64_t grid_h, int64_t grid_w,
+                                     int64_t G, int64_t N, int with_bg, float bg_thresh, uint8_t* labels, uint8_t* groups,
+                                     void* stream) {
+  if (int rc = seg_pixel_check("seg_label_map", n_windows, B, H, W, win_h, win_w, grid_h, grid_w, G, N)) return rc;
+  SEGCLIP_REQUIRE(labels || groups, "seg_label_map: one of labels, groups is required");
+  if (labels && N + (with_bg ? 1 : 0) > 256) {
+    segclip_set_error("seg_label_map: %lld classes do not fit the uint8 label map (use segclip_seg_logits)",
+                      (long long)(N + (with_bg ? 1 : 0)));
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return 0;
+  SegPixelArgs a = seg_args(soft_attn, table, table_max, best_class, best_score, windows, image_first, n_windows, B, H, W, win_h, win_w,
+                            grid_h, grid_w, G, N, with_bg, bg_thresh);
+  a.labels = labels; a.groups = groups;
+  const int64_t units = H * cdiv(W, 4);
+  const size_t lds = seg_lds(a, false);
+  hipLaunchKernelGGL((seg_pixel_kernel<4, false>), dim3((unsigned)cdiv(units, 256), (unsigned)B), dim3(256), lds, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_label_map");
+  return 0;
+}
+
+extern "C" int segclip_seg_logits(const float* soft_attn, const float* table, const float* table_max, const int32_t* best_class,
+                                  const float* best_score, const int32_t* windows, const int32_t* image_first, int64_t n_windows,
+                                  int64_t B, int64_t H, int64_t W, int64_t win_h, int64_t win_w, int64_t grid_h, int64_t grid_w,
+                                  int64_t G, int64_t N, int with_bg, float bg_thresh, float* logits, void* stream) {
+  if (int rc = seg_pixel_check("seg_logits", n_windows, B, H, W, win_h, win_w, grid_h, grid_w, G, N)) return rc;
+  SEGCLIP_REQUIRE(logits != nullptr, "seg_logits: logits is required");
+  if (B == 0) return 0;
+  SegPixelArgs a = seg_args(soft_attn, table, table_max, best_class, best_score, windows, image_first, n_windows, B, H, W, win_h, win_w,
+                            grid_h, grid_w, G, N, with_bg, bg_thresh);
+  a.logits = logits;
+  const size_t lds = seg_lds(a, true);
+  hipLaunchKernelGGL((seg_pixel_kernel<1, true>), dim3((unsigned)cdiv(H * W, 256), (unsigned)B), dim3(256), lds, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_logits");
+  return 0;
+}

@@ -2298,3 +2298,86 @@ def center_logits(q, k, exact):
     if not exact and G == 8 and D in (768, 1024) and k.shape[1] * 32 <= 60000:
         return CenterLogitsFn.apply(q, k)
     return bmm(q, k, transB=True, out_dtype=torch.float32)
+
+
+# ---------------------------------------------------------------- zero-shot segmentation inference (segment.hip)
+def seg_group_table(group_tokens, pooled, text, logit_scale, topk, want_mask=False):
+    """Per window the G x N group-class table of ViTSegInference.encode_decode (vit_seg.py:218-254).
+    group_tokens (W, G, C) and pooled (W, C) may be strided views of one (W, 1 + G, C) tensor; text (N, C) normalised;
+    logit_scale a device scalar.  -> (table (W, G, N), table_max (W), best_class (W, G) int32, best_score (W, G))
+    [+ topk_mask (W, N) uint8].  No autograd, fp32 only."""
+    L.require_cuda(group_tokens, pooled, text, logit_scale)
+    Wn, G, Cc = group_tokens.shape
+    N = text.shape[0]
+    for t in (group_tokens, pooled, text, logit_scale):
+        if t.dtype != torch.float32:
+            raise TypeError("seg_group_table: fp32 inputs only")
+    text = text.contiguous()
+    if group_tokens.stride(2) != 1 or group_tokens.stride(1) != Cc or (Wn > 1 and group_tokens.stride(0) < G * Cc):
+        group_tokens = group_tokens.contiguous()
+    if pooled.stride(1) != 1:
+        pooled = pooled.contiguous()
+    if pooled.shape != (Wn, Cc) or text.shape[1] != Cc:
+        raise ValueError("seg_group_table: shapes do not agree")
+    dev = text.device
+    table = torch.empty(Wn, G, N, dtype=torch.float32, device=dev)
+    tmax = torch.empty(Wn, dtype=torch.float32, device=dev)
+    bcls = torch.empty(Wn, G, dtype=torch.int32, device=dev)
+    bsc = torch.empty(Wn, G, dtype=torch.float32, device=dev)
+    mask = torch.empty(Wn, N, dtype=torch.uint8, device=dev) if want_mask else None
+    L.check(L.load().segclip_seg_group_table(L.ptr(group_tokens), group_tokens.stride(0), L.ptr(pooled), pooled.stride(0),
+                                             L.ptr(text), L.ptr(logit_scale.detach()), L.ptr(table), L.ptr(tmax), L.ptr(bcls),
+                                             L.ptr(bsc), L.ptr(mask), Wn, G, N, Cc, int(topk), L.stream()), "seg_group_table")
+    out = (table, tmax, bcls, bsc)
+    return out + (mask,) if want_mask else out
+
+
+def _seg_pixel_args(soft_attn, tables, windows, image_first, out_size, win_size, grid):
+    table, tmax, bcls, bsc = tables
+    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, image_first)
+    nW, G, N = table.shape
+    B, H, W = out_size
+    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
+            or image_first.dtype != torch.int32 or bcls.dtype != torch.int32:
+        raise TypeError("seg pixel kernels: fp32 soft_attn / tables, int32 window list")
+    if soft_attn.numel() != nW * G * grid[0] * grid[1] or tuple(windows.shape) != (nW, 3) or image_first.numel() != B + 1 \
+            or tmax.numel() != nW or bcls.numel() != nW * G or bsc.numel() != nW * G:
+        raise ValueError("seg pixel kernels: shapes do not agree")
+    keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, image_first))
+    return keep, (nW, B, H, W, win_size[0], win_size[1], grid[0], grid[1], G, N)
+
+
+def seg_label_map(soft_attn, tables, windows, image_first, out_size, win_size, grid, with_bg, bg_thresh, labels=True,
+                  groups=False):
+    """The fused pixel kernel (segclip_seg_label_map): soft_attn (nW, G, gh * gw) + the outputs of seg_group_table + the
+    window list -> labels (B, H, W) uint8 and / or groups (B, H, W) uint8.  `labels` / `groups`: True (allocate), False
+    (skip) or a contiguous uint8 tensor of B * H * W elements to write into."""
+    keep, dims = _seg_pixel_args(soft_attn, tables, windows, image_first, out_size, win_size, grid)
+
+    def out(o):
+        if o is False or o is None:
+            return None
+        if o is True:
+            return torch.empty(out_size, dtype=torch.uint8, device=soft_attn.device)
+        if o.dtype != torch.uint8 or not o.is_contiguous() or o.numel() != out_size[0] * out_size[1] * out_size[2]:
+            raise ValueError("seg_label_map: outputs are contiguous uint8 tensors of B * H * W elements")
+        return o
+
+    lab, grp = out(labels), out(groups)
+    L.check(L.load().segclip_seg_label_map(*(L.ptr(t) for t in keep), *dims, int(bool(with_bg)), float(bg_thresh), L.ptr(lab),
+                                           L.ptr(grp), L.stream()), "seg_label_map")
+    return lab, grp
+
+
+def seg_logits(soft_attn, tables, windows, image_first, out_size, win_size, grid, with_bg, bg_thresh, out=None):
+    """The dense output (segclip_seg_logits): (B, N + with_bg, H, W) fp32 as encode_decode / slide_inference define it."""
+    keep, dims = _seg_pixel_args(soft_attn, tables, windows, image_first, out_size, win_size, grid)
+    N = tables[0].shape[2]
+    shape = (out_size[0], N + int(bool(with_bg)), out_size[1], out_size[2])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=soft_attn.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != shape[0] * shape[1] * shape[2] * shape[3]:
+        raise ValueError("seg_logits: out is a contiguous fp32 tensor of B * (N + with_bg) * H * W elements")
+    L.check(L.load().segclip_seg_logits(*(L.ptr(t) for t in keep), *dims, int(bool(with_bg)), float(bg_thresh), L.ptr(out),
+                                        L.stream()), "seg_logits")
+    return out
