@@ -450,6 +450,47 @@ int segclip_seg_logits(const float* soft_attn, const float* table, const float* 
                        int64_t G, int64_t N, int with_bg, float bg_thresh, float* logits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Zero-shot segmentation evaluation (segment_eval.inc): label maps at the ground truth's size for images of mixed sizes in
+ * ONE launch, and the per-class areas of the mIoU (mmseg: resize(logits, size=ori_shape) -> arg-max -> intersect_and_union).
+ *
+ * The rescaled label map.  Output pixel (y, x) of an image with network size (H, W) and output size (oh, ow): taps and weights
+ * of upsample_bilinear2d(align_corners=False, no scale factors) on the (H, W) grid, scales (float)H / oh and (float)W / ow;
+ * at each tap the class logits exactly as the dense-logits entry above defines them (same device functions); per class the
+ * blend h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) in fp32; first maximum over the classes; one byte.  A tap of
+ * weight 0 is not evaluated, so (oh, ow) = (H, W) reproduces the label-map entry above bit for bit.  Where the four taps have
+ * the same covering windows and groups, hence one logit vector v, the label is v's first maximum without the blend (the blend
+ * is monotone in v; two classes can change places only where it rounds two different logits to one value).  No
+ * (C, oh, ow) or (C, H, W) array exists.
+ *   soft_attn : flat fp32 of soft_floats elements; the windows of one image are consecutive (G, grid_h * grid_w) planes
+ *   images    : (B, 16) int64 rows on the device:
+ *               0 first window  1 window count  2 H  3 W  4 oh  5 ow  6 offset of the image's oh * ow labels in `labels`
+ *               7 offset of its ground truth in `gt`, or -1  8 its first workgroup = the sum of ceil(oh * ow / 1024) over the
+ *               images before it  9 win_h  10 win_w  11 grid_h  12 grid_w  13 offset of its first window in soft_attn  14, 15 0
+ *               Windows, tables and the window list (image, y0, x0) are as above, but the window size and grid are per image.
+ *   n_blocks  : the sum of ceil(oh * ow / 1024) over all images;  max_image_windows: the largest window count of an image
+ *               (sizes the LDS; 1 = no image has overlapping windows)
+ *   labels    : flat uint8 of labels_bytes, or NULL; a label offset that is a multiple of 4 gives dword stores
+ *   gt, areas : flat uint8 of gt_bytes and (3, N + with_bg) int64, or both NULL.  areas is ADDED to: [0] intersection,
+ *               [1] prediction area, [2] label area per class.  Ground-truth rule of both entries: the value ignore_index
+ *               contributes nothing; with reduce_zero_label 0 contributes nothing as well and every other value counts as
+ *               g - 1; a value >= the class count adds to the prediction area only (torch.histc drops it from the others).
+ *               Per-workgroup integer counters in LDS, one global add per touched counter: the sums do not depend on order.
+ *   Every entry of `images` is range-checked on the device; an image whose row is inconsistent with soft_floats,
+ *   labels_bytes or gt_bytes is skipped.  SEGCLIP_ERR_UNSUPPORTED: N + with_bg > 256, max_image_windows > 64.  At most 16
+ *   windows covering one pixel, G <= 8.  H, W, oh, ow < 2^30 and oh * ow < 2^31.
+ *
+ * The areas alone: the same accumulation for n pixels of label maps the caller already has.  SEGCLIP_ERR_UNSUPPORTED: C > 256.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                   const int32_t* best_class, const float* best_score, const int32_t* windows,
+                                   const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
+                                   int64_t max_image_windows, int64_t G, int64_t N, int with_bg, float bg_thresh,
+                                   uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes,
+                                   int ignore_index, int reduce_zero_label, int64_t* areas, void* stream);
+int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index, int reduce_zero_label,
+                      int64_t* areas, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MAE random masking (integer path, bit-exact given the noise).  modules/module_clip_util.py:91-124
  * with keep_cls: noise[:,0] = -1; ids_shuffle = argsort(noise) (stable); ids_restore =
  * argsort(ids_shuffle); mask = 1 except the first len_keep of the shuffle.

@@ -22,7 +22,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # zero-shot segmentation inference, imported on first use: `import segclip_amd` itself stays free of ops.py
-    if name in ("SegInference", "build_text_embedding", "segmentation"):
+    if name in ("SegInference", "SegEvaluator", "build_text_embedding", "segmentation"):
         import importlib
         mod = importlib.import_module(".segmentation", __name__)
         return mod if name == "segmentation" else getattr(mod, name)

@@ -165,6 +165,9 @@ SIGNATURES = {
                                         vp, vp, vp]),
     "segclip_seg_logits": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                      vp, vp]),
+    "segclip_seg_label_map_rescaled": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                                 vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_areas": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_multi_cast_bf16": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_multi_add_f32": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_max_tokens_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),

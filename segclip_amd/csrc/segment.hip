@@ -291,6 +291,8 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
   return 0;
 }
 
+#include "segment_eval.inc"
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -379,5 +381,64 @@ extern "C" int segclip_seg_logits(const float* soft_attn, const float* table, co
   const size_t lds = seg_lds(a, true);
   hipLaunchKernelGGL((seg_pixel_kernel<1, true>), dim3((unsigned)cdiv(H * W, 256), (unsigned)B), dim3(256), lds, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_logits");
+  return 0;
+}
+
+extern "C" int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                              const int32_t* best_class, const float* best_score, const int32_t* windows,
+                                              const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
+                                              int64_t max_image_windows, int64_t G, int64_t N, int with_bg, float bg_thresh,
+                                              uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes,
+                                              int ignore_index, int reduce_zero_label, int64_t* areas, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_bytes >= 0 && gt_bytes >= 0,
+                  "seg_label_map_rescaled: sizes must not be negative, N >= 1");
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "seg_label_map_rescaled: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "seg_label_map_rescaled: size out of range");
+  SEGCLIP_REQUIRE(labels || gt, "seg_label_map_rescaled: one of labels, gt is required");
+  SEGCLIP_REQUIRE(!gt || areas, "seg_label_map_rescaled: a ground truth needs the areas to add to");
+  const int64_t C = N + (with_bg ? 1 : 0);
+  if (C > SEG_MAX_CLASSES) {
+    segclip_set_error("seg_label_map_rescaled: %lld classes, at most %d (uint8 labels, per-class counters in LDS)", (long long)C,
+                      SEG_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_image_windows > SEG_MAX_IMG_WIN) {
+    segclip_set_error("seg_label_map_rescaled: %lld windows per image, at most %d", (long long)max_image_windows, SEG_MAX_IMG_WIN);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0 || n_blocks == 0) return 0;
+  SegEvalArgs a;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
+  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_bytes; a.gt_bytes = gt_bytes;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
+  a.labels = labels; a.gt = gt; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  // LDS: the tables of the windows that touch a tile's source rows (a tile of 1024 output pixels spans few rows, so these are
+  // one or two rows of the window grid; more than the budget: the kernel reads the global table), and the covering-window
+  // lists of the four taps (one slot when no image has more than one window)
+  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
+  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
+  int64_t want = per_image * G * N;
+  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
+  a.tab_floats = (int)((want + 1) & ~1ll);
+  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
+  hipLaunchKernelGGL(seg_rescaled_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_label_map_rescaled");
+  return 0;
+}
+
+extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index, int reduce_zero_label,
+                                 int64_t* areas, void* stream) {
+  SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "seg_areas: need 0 <= n <= 2^40 and C >= 1");
+  SEGCLIP_REQUIRE(n == 0 || (pred && gt && areas), "seg_areas: pred, gt and areas are required");
+  if (C > SEG_MAX_CLASSES) {
+    segclip_set_error("seg_areas: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return 0;
+  const int64_t blocks = cdiv(n, SEG_EVAL_TILE) < 1024 ? cdiv(n, SEG_EVAL_TILE) : 1024;
+  hipLaunchKernelGGL(seg_areas_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
+                     reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(areas));
+  SEGCLIP_CHECK_LAUNCH("seg_areas");
   return 0;
 }

@@ -2381,3 +2381,71 @@ def seg_logits(soft_attn, tables, windows, image_first, out_size, win_size, grid
     L.check(L.load().segclip_seg_logits(*(L.ptr(t) for t in keep), *dims, int(bool(with_bg)), float(bg_thresh), L.ptr(out),
                                         L.stream()), "seg_logits")
     return out
+
+
+SEG_IMAGE_COLS = 16   # int64 columns of one row of the image table of segclip_seg_label_map_rescaled
+SEG_EVAL_TILE = 1024  # output pixels of one of its workgroups
+
+
+def seg_image_table(rows, device):
+    """The device descriptor table of seg_label_map_rescaled from per-image dicts(first, count, net=(H, W), out=(oh, ow),
+    win=(win_h, win_w), grid=(gh, gw), soft_off[, gt_off]).  Label offsets are assigned here, each a multiple of 4.
+    -> (table (B, 16) int64, label offsets, labels_bytes, n_blocks, max windows of an image)."""
+    tab, offs, lab, blk, most = [], [], 0, 0, 0
+    for r in rows:
+        (H, W), (oh, ow), (wh, ww), (gh, gw) = r["net"], r["out"], r["win"], r["grid"]
+        if min(H, W, oh, ow, wh, ww, gh, gw) < 1 or r["count"] < 1:
+            raise ValueError(f"seg_image_table: sizes must be positive, got {r}")
+        tab.append([r["first"], r["count"], H, W, oh, ow, lab, r.get("gt_off", -1), blk, wh, ww, gh, gw, r["soft_off"], 0, 0])
+        offs.append(lab)
+        lab += (oh * ow + 3) // 4 * 4
+        blk += (oh * ow + SEG_EVAL_TILE - 1) // SEG_EVAL_TILE
+        most = max(most, r["count"])
+    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_IMAGE_COLS), offs, lab, blk, most
+
+
+def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_image_windows, with_bg, bg_thresh, labels=None,
+                           gt=None, areas=None, ignore_index=255, reduce_zero_label=False):
+    """The fused evaluation kernel (segclip_seg_label_map_rescaled): flat soft_attn + the outputs of seg_group_table + the
+    window list + the image table -> `labels` (flat uint8, or None) at every image's output size and, with `gt` (flat uint8),
+    the (3, C) int64 `areas` added to in place."""
+    table, tmax, bcls, bsc = tables
+    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images, labels, gt, areas)
+    nW, G, N = table.shape
+    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
+            or images.dtype != torch.int64 or bcls.dtype != torch.int32:
+        raise TypeError("seg_label_map_rescaled: fp32 soft_attn / tables, int32 window list, int64 image table")
+    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
+            or bcls.numel() != nW * G or bsc.numel() != nW * G:
+        raise ValueError("seg_label_map_rescaled: shapes do not agree")
+    for name, t in (("labels", labels), ("gt", gt)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"seg_label_map_rescaled: {name} is a contiguous uint8 tensor")
+    if (gt is None) != (areas is None):
+        raise ValueError("seg_label_map_rescaled: gt and areas go together")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous()
+                              or tuple(areas.shape) != (3, N + int(bool(with_bg)))):
+        raise ValueError("seg_label_map_rescaled: areas is a contiguous (3, N + with_bg) int64 tensor")
+    keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, images))
+    L.check(L.load().segclip_seg_label_map_rescaled(
+        L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
+        G, N, int(bool(with_bg)), float(bg_thresh), L.ptr(labels), labels.numel() if labels is not None else 0, L.ptr(gt),
+        gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(areas), L.stream()),
+        "seg_label_map_rescaled")
+    return labels
+
+
+def seg_areas(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, areas=None):
+    """mmseg's intersect_and_union of uint8 label maps (segclip_seg_areas): -> (3, C) int64 = intersection, prediction area,
+    label area per class; added to `areas` when given."""
+    L.require_cuda(pred, gt, areas)
+    if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.numel() != gt.numel():
+        raise ValueError("seg_areas: pred and gt are uint8 tensors of the same size")
+    if areas is None:
+        areas = torch.zeros(3, num_classes, dtype=torch.int64, device=pred.device)
+    elif areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (3, num_classes):
+        raise ValueError("seg_areas: areas is a contiguous (3, C) int64 tensor")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    L.check(L.load().segclip_seg_areas(L.ptr(pred), L.ptr(gt), pred.numel(), int(num_classes), int(ignore_index),
+                                       int(bool(reduce_zero_label)), L.ptr(areas), L.stream()), "seg_areas")
+    return areas

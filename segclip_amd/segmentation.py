@@ -2,11 +2,19 @@
 
 Replaces seg_segmentation/evaluation of the reference without mmseg / mmcv: build_text_embedding is the text step of
 build_seg_inference (evaluation/builder.py:55-66), SegInference is ViTSegInference (evaluation/vit_seg.py:118-256) plus
-mmseg's whole / slide inference.  The dataset, the tokenizer, rescaling to the original image size and mIoU stay with the
-caller.  The post-processing runs in three HIP kernels (csrc/segment.hip): the label map is written as one byte per pixel
-without the reference's (H, W, G) / (H, W, N) intermediates, and the vision tower sees every window once, all windows of
-all images of a call in one batch.
+mmseg's whole / slide inference.  The post-processing runs in three HIP kernels (csrc/segment.hip): the label map is written
+as one byte per pixel without the reference's (H, W, G) / (H, W, N) intermediates, and the vision tower sees every window
+once, all windows of all images of a call in one batch.
+
+The evaluation (main_seg_zeroshot.py:122-167 and mmseg's single_gpu_test / eval_metrics): SegInference.predict_list takes
+images of mixed sizes and writes their label maps at the ground truth's size in one launch (csrc/segment_eval.inc), and
+SegEvaluator accumulates mmseg's per-class areas in the same launch and turns them into mIoU / aAcc / mAcc.  The dataset, the
+image decoding, the tokenizer and the resize of an image to its test size (test_size gives the size) stay with the caller.
+mmseg takes a softmax between the resize and the arg-max; here the arg-max is taken of the logits, which can differ only
+where fp32 exp rounds two different logits to one value.
 """
+import math
+
 import torch
 
 from . import config, ops
@@ -25,6 +33,16 @@ def slide_windows(H, W, crop, stride):
             y1, x1 = min(i * sh + ch, H), min(j * sw + cw, W)
             out.append((max(y1 - ch, 0), max(x1 - cw, 0)))
     return out
+
+
+def test_size(h, w, img_scale=(2048, 224)):
+    """mmcv's keep-ratio rescale of an (h, w) image to the test pipeline's img_scale -> (H, W): the largest scale that keeps
+    the long side within max(img_scale) and the short side within min(img_scale), sizes rounded half up."""
+    s = min(max(img_scale) / max(h, w), min(img_scale) / min(h, w))
+    return int(h * s + 0.5), int(w * s + 0.5)
+
+
+test_size.__test__ = False   # a product function, not a test
 
 
 def _require_eval_gpu(model, t):
@@ -150,3 +168,137 @@ class SegInference:
         """(B, 3, H, W) -> (B, N + with_bg, H, W) fp32 logits (vit_seg.py:202-256; any batch size)."""
         soft, tables, dwin, dfirst, size, win, grid = self._windows_forward(img)
         return ops.seg_logits(soft, tables, dwin, dfirst, size, win, grid, self.with_bg, self.bg_thresh)
+
+    # ------------------------------------------------------------------------------------------ images of mixed sizes
+    def _list_plan(self, sizes):
+        """Windows of a list of image sizes -> (batches [(win size, [(image, y0, x0)])] in tower order, per-image
+        (first window, window count, win size)).  Slide mode: one batch of all windows; whole mode: one batch per size."""
+        per_image = [None] * len(sizes)
+        if self.mode == "slide":
+            wins = []
+            for i, (H, W) in enumerate(sizes):
+                per = slide_windows(H, W, self.crop_size, self.stride)
+                if len(per) > 64:
+                    raise ValueError(f"slide mode: {len(per)} windows per image, at most 64 supported")
+                per_image[i] = (len(wins), len(per), self.crop_size)
+                wins += [(i, y, x) for (y, x) in per]
+            return [(self.crop_size, wins)], per_image
+        by_size = {}
+        for i, hw in enumerate(sizes):
+            by_size.setdefault(hw, []).append(i)
+        batches, n = [], 0
+        for hw, members in by_size.items():
+            for k, i in enumerate(members):
+                per_image[i] = (n + k, 1, hw)
+            batches.append((hw, [(i, 0, 0) for i in members]))
+            n += len(members)
+        return batches, per_image
+
+    def _list_forward(self, imgs, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True):
+        if len(imgs) == 0:
+            raise ValueError("empty image list")
+        for t in imgs:
+            _require_eval_gpu(self.model, t)
+            if t.dim() != 3 or t.shape[0] != 3:
+                raise ValueError(f"predict_list takes (3, H, W) images, got {tuple(t.shape)}")
+        sizes = [(int(t.shape[1]), int(t.shape[2])) for t in imgs]
+        if out_shapes is None:
+            out_shapes = sizes
+        if len(out_shapes) != len(imgs):
+            raise ValueError(f"{len(imgs)} images but {len(out_shapes)} output shapes")
+        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
+        if self.num_classes > 256:
+            raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
+        p = self.model.clip.visual.patch_size
+        batches, per_image = self._list_plan(sizes)
+        N = self.text_embedding.shape[0]
+        dev = imgs[0].device
+        parts, wins_all, win_off, floats = [], [], [], 0   # win_off: a window's offset in the flat soft_attn
+        for (wh, ww), wins in batches:
+            if wh % p or ww % p:
+                raise ValueError(f"window {wh}x{ww} is not a multiple of the patch size {p}")
+            for s in range(0, len(wins), self.max_windows):
+                chunk = wins[s:s + self.max_windows]
+                x = torch.stack([imgs[i][:, y:y + wh, x0:x0 + ww] for (i, y, x0) in chunk])
+                with config.scope(cross_mode="intended"):   # see _windows_forward
+                    feat, hidden, mid = self.model.clip.encode_image(x, return_hidden=True)
+                if not mid["attns"]:
+                    raise ValueError(f"window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x or 4x the "
+                                     "training token count (modules/module_seg_vit.py:423)")
+                soft = mid["attns"][-1]["soft_attn"]
+                del mid, x
+                tables = ops.seg_group_table(hidden[:, 1:, :], feat, self.text_embedding, self.model.clip.logit_scale, min(5, N))
+                win_off += range(floats, floats + soft.numel(), soft.numel() // soft.shape[0])
+                floats += soft.numel()
+                parts.append((soft.reshape(-1),) + tables)
+            wins_all += wins
+        if len(parts) == 1:
+            soft, tables = parts[0][0], parts[0][1:]
+        else:
+            cat = [torch.cat([q[i] for q in parts]) for i in range(5)]
+            soft, tables = cat[0], tuple(cat[1:])
+        rows, gt_off = [], 0
+        for i, (first, count, (wh, ww)) in enumerate(per_image):
+            rows.append(dict(first=first, count=count, net=sizes[i], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
+                             soft_off=win_off[first], gt_off=gt_off if gts is not None else -1))
+            gt_off += out_shapes[i][0] * out_shapes[i][1]
+        images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, dev)
+        dwin = torch.tensor(wins_all, dtype=torch.int32, device=dev).view(-1, 3)
+        labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
+        gt = None
+        if gts is not None:
+            gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
+        ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels, gt=gt,
+                                   areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+        if not want_labels:
+            return None
+        return [labels[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
+    @torch.no_grad()
+    def predict_list(self, imgs, out_shapes=None):
+        """[(3, H_i, W_i)] of any mix of sizes -> [(oh_i, ow_i) uint8 labels], views of one flat buffer; out_shapes defaults
+        to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
+        maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
+        Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size."""
+        return self._list_forward(imgs, out_shapes)
+
+
+class SegEvaluator:
+    """mmseg's mIoU evaluation on the device.  update() adds every image's per-class intersection, prediction area and label
+    area (intersect_and_union with ignore_index / reduce_zero_label) to `areas`, a (3, C) int64 device tensor, inside the
+    label-map launch and without a host synchronisation; compute() copies it to the host once.  Several ranks: all_reduce
+    `areas` (sum) before compute()."""
+
+    def __init__(self, seg, ignore_index=255, reduce_zero_label=False):
+        self.seg, self.ignore_index, self.reduce_zero_label = seg, int(ignore_index), bool(reduce_zero_label)
+        self.areas = torch.zeros(3, seg.num_classes, dtype=torch.int64, device=seg.text_embedding.device)
+
+    def reset(self):
+        self.areas.zero_()
+
+    @torch.no_grad()
+    def update(self, imgs, gts, return_labels=False):
+        """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size."""
+        if len(imgs) != len(gts):
+            raise ValueError(f"{len(imgs)} images but {len(gts)} ground truths")
+        for g in gts:
+            if not g.is_cuda:
+                raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {g.device} tensor")
+            if g.dtype != torch.uint8 or g.dim() != 2:
+                raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
+        return self.seg._list_forward(imgs, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
+                                      ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
+                                      want_labels=return_labels)
+
+    @staticmethod
+    def metrics_from_areas(areas):
+        """(3, C) integer CPU tensor -> dict(mIoU, aAcc, mAcc, IoU, Acc) as mmseg's eval_metrics: IoU = I / (P + L - I),
+        Acc = I / L, aAcc = sum(I) / sum(L); a class absent from prediction and label is NaN and left out of the means."""
+        a = areas.to(torch.float64)
+        inter, pred, label = a[0], a[1], a[2]
+        iou, acc = inter / (pred + label - inter), inter / label
+        return dict(mIoU=float(torch.nanmean(iou)), aAcc=float(inter.sum() / label.sum()), mAcc=float(torch.nanmean(acc)),
+                    IoU=iou, Acc=acc)
+
+    def compute(self):
+        return self.metrics_from_areas(self.areas.cpu())

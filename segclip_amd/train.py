@@ -4,6 +4,7 @@ the hot path, with the per-iteration host round-trips removed.
   freeze_parameters(args, model)                   main_task_align.py:388-441
   prep_optimizer(args, model, t_total, ...)        main_task_align.py:175-256   (8 name-routed param groups)
   train_epoch(epoch, args, model, loader, ...)     main_task_align.py:292-359
+  eval_epoch(args, model, device, n_gpu, ...)      main_task_align.py:361-370, main_seg_zeroshot.py:122-167 (mIoU * 100)
   TrainTail                                        :326-347 fused: clip_grad_norm_ -> AdaptAdamW.step (skipped on the
                                                    device when the loss is NaN) -> zero_grad -> clamp(logit_scale)
 
@@ -264,3 +265,25 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
         model.drain()   # GradSync: read the cross-rank agreements posted in the last passes (tail.read() below waits for the device anyway)
     total = tail.read()["loss_sum"] - start_sum + (float(partial) if partial is not None else 0.0)
     return total / max(n_batches, 1), global_step
+
+
+def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_cfg=None):
+    """The zero-shot segmentation score of a checkpoint (main_task_align.py:361-370 -> main_seg_zeroshot.py:122-167):
+    mIoU * 100 over `batches`, an iterable of (imgs, gts) with imgs a list of (3, H, W) images already resized to their test
+    size (segmentation.test_size) and gts the (oh, ow) uint8 ground truths.  text_tokens (N, T, L): the class prompts;
+    test_cfg: keyword arguments of SegInference (mode, crop_size, stride, bg_thresh, max_windows) and optionally
+    ignore_index / reduce_zero_label.  The areas stay on the device until the end.  With several ranks every rank scores its
+    own share; all_reduce SegEvaluator.areas instead of calling this when one figure over all ranks is wanted."""
+    from .segmentation import SegEvaluator, SegInference, build_text_embedding
+    cfg = dict(test_cfg or {})
+    ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
+    model = _unwrap(model)
+    model.eval()
+    emb = build_text_embedding(model, text_tokens.to(device))
+    evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label)
+    for imgs, gts in batches:
+        evaluator.update([t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts])
+    miou = evaluator.compute()["mIoU"] * 100.0
+    if getattr(args, "local_rank", 0) == 0:
+        logger.info("Zero-shot segmentation mIoU: %.2f", miou)
+    return miou

@@ -8,7 +8,11 @@
 Every figure: 3 warm-up calls, then `reps` timed repeats of `inner` calls each, device-synchronised; median and min-max of
 the repeats.  The shader clock the box held during the timed region is sampled (tools/clock_sampler.py).
 The lines are printed and written to `out`.
-usage: python tools/bench_seg.py [reps=7] [out=profiles/seg_infer.txt]"""
+With --eval instead: the mIoU evaluation of 64 images of mixed VOC-like sizes (21 classes, slide 224 / 224):
+  (iv)  images/s of SegEvaluator.update (one call for the list), the time of segclip_seg_label_map_rescaled alone, the time of
+        the Python-side window extraction (torch.stack of slices) alone, peak allocation, and the same evaluation done the
+        obvious way on the same GPU: encode_decode per image -> F.interpolate -> argmax -> three histc, batch 1.
+usage: python tools/bench_seg.py [--eval] [reps=7] [out=profiles/seg_infer.txt | profiles/seg_eval.txt]"""
 import os
 import statistics
 import sys
@@ -23,8 +27,11 @@ from segclip_amd import config, ops, synth
 from segclip_amd.segmentation import SegInference
 from tools.clock_sampler import ClockSampler
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-OUT = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "seg_infer.txt")
+EVAL = "--eval" in sys.argv[1:]
+ARGV = [a for a in sys.argv[1:] if a != "--eval"]
+REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
+OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                 "seg_eval.txt" if EVAL else "seg_infer.txt")
 lines = []
 
 
@@ -117,6 +124,88 @@ def case(name, model, text, B, H, W, inner, **kw):
     say(f"{name}: post-processing share of predict: kernels {k_med / med:.4f}, eager would be {e_med / (med - k_med + e_med):.4f}")
 
 
+# original sizes of the evaluation leg (VOC-like), cycled; the network sizes are their test_size at img_scale (2048, 224)
+EVAL_SIZES = [(375, 500), (500, 375), (281, 500), (333, 500), (500, 334), (366, 500), (500, 500), (442, 500)]
+
+
+def peak_of(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    with torch.no_grad():
+        fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def eval_case(model, text, n_images=64):
+    from segclip_amd.segmentation import SegEvaluator, slide_windows, test_size
+    name = f"(iv) eval   {n_images} mixed sizes"
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    C = seg.num_classes
+    g = torch.Generator().manual_seed(1)
+    outs = [EVAL_SIZES[i % len(EVAL_SIZES)] for i in range(n_images)]
+    imgs = [torch.randn(3, *test_size(*o), generator=g).cuda() for o in outs]
+    gts = [torch.randint(0, C, o, generator=g).to(torch.uint8).cuda() for o in outs]
+    ev = SegEvaluator(seg)
+    sampler = ClockSampler().start()
+    med, lo, hi = timed(lambda: ev.update(imgs, gts), 2)
+    clk = sampler.stop()
+    wins = [(i, y, x) for i, t in enumerate(imgs) for (y, x) in slide_windows(t.shape[1], t.shape[2], (224, 224), (224, 224))]
+    say(f"{name}: SegEvaluator.update {med * 1e3:8.2f} ms (min {lo * 1e3:.2f}, max {hi * 1e3:.2f}; {REPS} x 2 calls)  "
+        f"{n_images / med:8.1f} images/s   {len(wins)} windows   clock {clk}")
+    # the fused kernel alone, on the arguments of one update
+    captured = {}
+    real = ops.seg_label_map_rescaled
+
+    def capture(*a, **k):
+        captured["call"] = (a, k)
+        return real(*a, **k)
+
+    ops.seg_label_map_rescaled = capture
+    try:
+        with torch.no_grad():
+            ev.update(imgs, gts)
+    finally:
+        ops.seg_label_map_rescaled = real
+    a, k = captured["call"]
+    sampler = ClockSampler().start()
+    k_med, k_lo, k_hi = timed(lambda: real(*a, **k), 40)
+    k_clk = sampler.stop()
+    pixels = sum(o[0] * o[1] for o in outs)
+    say(f"{name}: segclip_seg_label_map_rescaled + areas alone {k_med * 1e6:9.1f} us (min {k_lo * 1e6:.1f}, max {k_hi * 1e6:.1f}) for "
+        f"{pixels} output pixels = {pixels / k_med / 1e9:.2f} Gpixel/s   clock {k_clk}   share of update {k_med / med:.4f}")
+    s_med, s_lo, s_hi = timed(lambda: torch.stack([imgs[i][:, y:y + 224, x:x + 224] for (i, y, x) in wins]), 2)
+    say(f"{name}: window extraction (torch.stack of {len(wins)} slices) alone {s_med * 1e3:8.2f} ms (min {s_lo * 1e3:.2f}, "
+        f"max {s_hi * 1e3:.2f})   share of update {s_med / med:.4f}")
+
+    def obvious():
+        areas = torch.zeros(3, C, device="cuda")
+        for img, gt in zip(imgs, gts):
+            logits = seg.encode_decode(img[None])
+            pred = F.interpolate(logits, size=tuple(gt.shape), mode="bilinear", align_corners=False).argmax(dim=1)[0]
+            keep = gt != 255
+            p, t = pred[keep].float(), gt[keep].float()
+            areas[0] += torch.histc(p[p == t], bins=C, min=0, max=C - 1)
+            areas[1] += torch.histc(p, bins=C, min=0, max=C - 1)
+            areas[2] += torch.histc(t, bins=C, min=0, max=C - 1)
+        return areas
+
+    ev.reset()
+    with torch.no_grad():
+        ev.update(imgs, gts)
+        ref = obvious()
+    same = float((ev.areas.double() - ref.double()).abs().sum() / ref.double().sum())
+    sampler = ClockSampler().start()
+    o_med, o_lo, o_hi = timed(obvious, 1)
+    o_clk = sampler.stop()
+    say(f"{name}: the obvious way (encode_decode per image -> F.interpolate -> argmax -> 3 histc, batch 1) {o_med * 1e3:8.2f} ms "
+        f"(min {o_lo * 1e3:.2f}, max {o_hi * 1e3:.2f})  {n_images / o_med:8.1f} images/s   ratio {o_med / med:6.2f}x   clock {o_clk}   "
+        f"areas differ by {same:.2e} of their sum")
+    say(f"{name}: peak allocation of one call: update {peak_of(lambda: ev.update(imgs, gts)) / 2**20:8.1f} MiB, the obvious way "
+        f"{peak_of(obvious) / 2**20:8.1f} MiB")
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -125,8 +214,11 @@ if __name__ == "__main__":
     text = torch.randn(20, 512, generator=g)
     text = (text / text.norm(dim=-1, keepdim=True)).cuda()
     say(f"# tools/bench_seg.py  ViT-B/16 synthetic weights, bf16 towers, 20 classes + background, {torch.cuda.get_device_name(0)}")
-    case("(i)  whole  B=64 224x224", model, text, 64, 224, 224, 3)
-    case("(ii) slide  B=16 448x672", model, text, 16, 448, 672, 2, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    if EVAL:
+        eval_case(model, text)
+    else:
+        case("(i)  whole  B=64 224x224", model, text, 64, 224, 224, 3)
+        case("(ii) slide  B=16 448x672", model, text, 16, 448, 672, 2, mode="slide", crop_size=(224, 224), stride=(224, 224))
     if OUT:
         with open(OUT, "w") as f:
             f.write("\n".join(lines) + "\n")
