@@ -335,7 +335,8 @@ int segclip_scatter_rows(const void* dout, const int64_t* idx, void* dsrc, int64
  *   training: y = softmax((logits + gumbel)/tau, dim=G);  eval (gumbel NULL): y = softmax(logits)
  *   idx[b,t] = argmax_g y (first max wins, like torch.max);  hard = onehot(idx)
  *   soft = softmax(logits, dim=G)   (consumed by the segmentation evaluation only)
- *   counts[b,g] = max(sum_t hard, 1)
+ *   counts[b,g] = sum_t hard[b,g,t]   (the token count, NOT clamped: an empty center has 0; the segment mean clamps)
+ * Limits: G <= 255 (idx is uint8); any B, T.  y_soft, soft, hard: (B,G,T) fp32; idx (B,T); counts (B,G), zeroed by the call.
  * bwd (straight-through): dlogits = dy_soft-path gradient of y given dhard (B,G,T):
  *   dlogits[b,:,t] = (y * (dhard - sum_g dhard*y)) / tau
  * ------------------------------------------------------------------------------------------ */
@@ -547,7 +548,8 @@ typedef struct segclip_adamw_tensor {
  *   out_o(m, g*64 + n) = sum_i sum_k in_i(m, g*64 + k) * w[i*n_out + o][g*64 + n][k],   bf16 in / out, fp32 accumulation.
  * (n_in, n_out) = (1, 1), (1, 2): one or two convolutions of the same input in one pass; (2, 1): sum of two - their data
  * gradient when w holds the per-group TRANSPOSED weights.  in/out/w and the pitches are HOST arrays; w[.]: (groups*64, 64)
- * bf16 row-major; all pointers 16-byte aligned, pitches multiples of 8 elements. */
+ * bf16 row-major; all pointers 16-byte aligned, pitches multiples of 8 elements and at least groups*64 (columns of a row beyond
+ * groups*64 are neither read nor written); any M >= 0 and groups >= 1.  A violation is an ERROR (-1), nothing is launched. */
 int segclip_group_linear64(const void* const* in, const int64_t* ld_in, int n_in, void* const* out, const int64_t* ld_out,
                            int n_out, const void* const* w, int64_t M, int groups, void* stream);
 
@@ -575,22 +577,29 @@ int segclip_clip_ce_bwd(const float* cos, const float* lse, const float* logit_s
  *   out[b][g][:] = (sum_t [idx[b][t] == g] v[b][t][:]) / max(counts[b][g], 1)       (hard assignment = one-hot of idx)
  * and its backward: dv[b][t][:] = dN[b][idx[b][t]][:], dhard[b][g][t] = dN[b][g] . v[b][t] + dc[b][g] with dN = dout / max(count, 1),
  * dc = -[count >= 1] (dout[b][g] . out[b][g]) / max(count, 1).  idx (B,T) uint8, counts (B,G) fp32 as segclip_assign_fwd leaves
- * them; v / dv (B,T,D) fp32 or bf16; out, dout (B,G,D) and dhard (B,G,T) fp32.  G <= 8, D a multiple of 4 (backward: D <= 1024). */
+ * them; v / dv (B,T,D) fp32 or bf16; out, dout (B,G,D) and dhard (B,G,T) fp32.
+ * Limits.  Forward: G <= 8, D a multiple of 4, T >= 1; any T.  Backward: the same and D <= 1024 and (T + 1) * 32 <= 60000 bytes
+ * of LDS, i.e. T <= 1874.  Either reports a violation as an ERROR (-1), not as SEGCLIP_ERR_UNSUPPORTED, and launches nothing:
+ * the caller must choose another path before the forward whenever the backward will be needed. */
 int segclip_segmean_fwd(const uint8_t* idx, const void* v, int v_dtype, const float* counts, float* out, int64_t B, int64_t G,
                         int64_t T, int64_t D, void* stream);
 int segclip_segmean_bwd(const float* dout, const float* out, const uint8_t* idx, const void* v, int v_dtype, const float* counts,
                         void* dv, float* dhard, int64_t B, int64_t G, int64_t T, int64_t D, void* stream);
 
 /* Token rows from the centers (MAE branch, reference modules/module_seg_vit.py:338-342): out (B,M,D) = a (B,M,G) @ x (B,G,D), fp32,
- * and the backward da (B,M,G) = dout x^T, dx (B,G,D) = a^T dout.  Covers G = 8, D a multiple of 4 up to 4096; other shapes return
- * SEGCLIP_ERR_UNSUPPORTED (use segclip_gemm). */
+ * and the backward da (B,M,G) = dout x^T, dx (B,G,D) = a^T dout.
+ * Limits, the same both ways: G = 8, D a multiple of 4, 4 <= D <= 4096 (the backward runs one lane per 4 columns in one
+ * workgroup of at most 1024 threads); any M.  Other shapes return SEGCLIP_ERR_UNSUPPORTED (use segclip_gemm). */
 int segclip_recon_mix_fwd(const float* a, const float* x, float* out, int64_t B, int64_t M, int64_t G, int64_t D, void* stream);
 int segclip_recon_mix_bwd(const float* a, const float* x, const float* dout, float* da, float* dx, int64_t B, int64_t M, int64_t G,
                           int64_t D, void* stream);
 
 /* Assignment logits of the center stage: attn[b][g][t] = q[b][g][:] . k[b][t][:] (fp32, un-scaled; reference
- * modules/module_seg_vit.py:304) and the backward dq = dl k, dk = dl^T q.  Covers G = 8, D = 768 | 1024; other shapes return
- * SEGCLIP_ERR_UNSUPPORTED (use segclip_gemm).  Not the summation order of the exact-fp32 GEMM. */
+ * modules/module_seg_vit.py:304) and the backward dq = dl k, dk = dl^T q.  Not the summation order of the exact-fp32 GEMM.
+ * Limits.  Both: G = 8, D = 768 | 1024.  Forward: T * 32 <= 60000 bytes of LDS, i.e. T <= 1875.  Backward: (8 T + 8 D) * 4 <=
+ * 64000 bytes of LDS, i.e. T <= 1232 at D = 768 and T <= 976 at D = 1024 - LOWER than the forward's: a caller that will need the
+ * backward must test the backward's limit before it takes this forward (ops.center_logits_covers).  Other shapes return
+ * SEGCLIP_ERR_UNSUPPORTED (use segclip_gemm) and launch nothing. */
 int segclip_center_logits_fwd(const float* q, const float* k, float* attn, int64_t B, int64_t G, int64_t T, int64_t D, void* stream);
 int segclip_center_logits_bwd(const float* dl, const float* q, const float* k, float* dq, float* dk, int64_t B, int64_t G,
                               int64_t T, int64_t D, void* stream);

@@ -132,6 +132,8 @@ class GroupLinearFn(torch.autograd.Function):
     def forward(ctx, x, w, groups):
         M, D = x.shape
         hd = D // groups
+        if x.stride(1) != 1 or x.stride(0) != D:      # the launches below (and the backward's) address dense rows
+            x = x.contiguous()
         wc = ops.wcast(w.reshape(D, hd), x.dtype)
         y = torch.empty_like(x)
         ops.p_gemm(x, wc, y, M, hd, hd, (D, 1), (hd, 1), D, nb1=groups, bsA=(hd, 0), bsB=(hd * hd, 0), bsC=(hd, 0))
@@ -201,7 +203,7 @@ class GroupLinearPairFn(torch.autograd.Function):
         for need, dy, name in ((ctx.needs_input_grad[1], dk, "k"), (ctx.needs_input_grad[2], dv, "v")):
             if need:
                 dw = torch.empty((D, hd), dtype=torch.float32, device=x.device)
-                ops.p_gemm(dy, x, dw, hd, hd, M, (1, D), (1, D), hd, nb1=G, bsA=(hd, 0), bsB=(hd, 0), bsC=(hd * hd, 0))
+                ops.p_gemm(dy, x, dw, hd, hd, M, (1, D), (1, x.stride(0)), hd, nb1=G, bsA=(hd, 0), bsB=(hd, 0), bsC=(hd * hd, 0))
                 if name == "k":
                     dwk = dw.view(ctx.wshape)
                 else:
@@ -219,6 +221,26 @@ def _group_linear_pair(n2d, wk, wv, groups):
             and n2d.data_ptr() % 16 == 0):
         return GroupLinearPairFn.apply(n2d, wk, wv, groups)
     return _group_linear(n2d, wk, groups), _group_linear(n2d, wv, groups)
+
+
+def _segmean_covers(G, T, D, backward):
+    """Whether segclip_segmean_fwd / _bwd (csrc/center.hip) take the shape: G <= 8 and D a multiple of 4 both ways; the
+    backward also D <= 1024 and `(T + 1) * CG * sizeof(float) <= 60000` of LDS (T <= 1874), which it reports as an error."""
+    if G > 8 or D % 4 != 0 or D > 1024:
+        return False
+    return not backward or (T + 1) * 8 * 4 <= 60000
+
+
+def _segment_mean(hard_attn, idx, counts, v):
+    """outputs (B,G,D) fp32 = (hard @ v) / clamp_min(hard.sum(-1), 1) (modules/module_seg_vit.py:308-309): the segment mean by
+    center index, one launch each way, where the kernels cover the shape - the backward's limits count whenever a gradient
+    will be asked for - and the batched GEMM otherwise."""
+    B, G, T = hard_attn.shape
+    needs_grad = torch.is_grad_enabled() and (hard_attn.requires_grad or v.requires_grad)
+    if _segmean_covers(G, T, v.shape[2], backward=needs_grad):
+        return ops.SegMeanFn.apply(hard_attn, idx, counts, v)
+    cnt = torch.clamp_min(hard_attn.sum(dim=-1, keepdim=True), 1.0)
+    return ops.bmm(hard_attn.to(v.dtype), v, transB=False, out_dtype=torch.float32) / cnt
 
 
 class SemanticLearnerModule(nn.Module):
@@ -275,12 +297,8 @@ class SemanticLearnerModule(nn.Module):
         attn = ops.center_logits(q, k, exact=ad != torch.bfloat16)
         g = config.gumbel((B, G, T), inputs.device) if self.training else None
         hard_attn, soft_attn, idx, counts = ops.AssignFn.apply(attn, g, 0.9)
-        if G <= 8 and D <= 1024:      # segment mean by center index: one launch each way (csrc/center.hip)
-            outputs = ops.SegMeanFn.apply(hard_attn, idx, counts, v)
-        else:
-            cnt = torch.clamp_min(hard_attn.sum(dim=-1, keepdim=True), 1.0)
-            outputs = ops.bmm(hard_attn.to(ad), v, transB=False, out_dtype=torch.float32) / cnt
-        z = ops.layer_norm(q + outputs, self.proj_o.ln.weight, self.proj_o.ln.bias, self.proj_o.ln.eps, ad)
+        outputs = _segment_mean(hard_attn, idx, counts, v)
+        z =ops.layer_norm(q + outputs, self.proj_o.ln.weight, self.proj_o.ln.bias, self.proj_o.ln.eps, ad)
         outputs = self.proj_o.mlp(z, final_act=ops.ACT_QUICK_GELU, out_dtype=torch.float32)
         self.last_hard_idx = idx
         return outputs, hard_attn, soft_attn, q

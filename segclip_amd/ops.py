@@ -2292,10 +2292,27 @@ class CenterLogitsFn(Function):
         return dq, dk
 
 
+def center_logits_covers(G, T, D, backward):
+    """Whether the token-loop kernels of csrc/center.hip take the shape.  Each limit restates ONE condition of that file:
+      forward:  segclip_center_logits_fwd, `(size_t)T * CG * sizeof(float) > 60000` -> unsupported         (T <= 1875)
+      backward: segclip_center_logits_bwd, `lds = (T * CG + CG * D) * sizeof(float)`, `lds > 64000` -> unsupported
+                                                                          (T <= 1232 at D = 768, T <= 976 at D = 1024)
+    A change of either line there is a change of the matching line here (tests/test_center_stage_gpu.py runs both sides of
+    both limits through center_logits)."""
+    if G != 8 or D not in (768, 1024):
+        return False
+    if T * 8 * 4 > 60000:
+        return False
+    return not backward or (T * 8 + 8 * D) * 4 <= 64000
+
+
 def center_logits(q, k, exact):
-    """(B,G,T) fp32 assignment logits; exact=True (the exact-f32 mode) or uncovered shapes: the exact-fp32 batched GEMM"""
+    """(B,G,T) fp32 assignment logits; exact=True (the exact-f32 mode) or uncovered shapes: the exact-fp32 batched GEMM.
+    Where a gradient will be asked for, the token-loop forward is chosen only if the token-loop backward covers the shape too
+    (its LDS limit is the lower one); a forward-only call keeps the token loop up to the forward's own limit."""
     B, G, D = q.shape
-    if not exact and G == 8 and D in (768, 1024) and k.shape[1] * 32 <= 60000:
+    needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad)
+    if not exact and center_logits_covers(G, k.shape[1], D, backward=needs_grad):
         return CenterLogitsFn.apply(q, k)
     return bmm(q, k, transB=True, out_dtype=torch.float32)
 
