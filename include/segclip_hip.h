@@ -492,6 +492,33 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
                       int64_t* areas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Front end of the zero-shot evaluation (segment_frontend.inc): decoded uint8 images -> the vision tower's input windows in ONE
+ * launch.  Replaces the test pipeline's Resize(keep_ratio=True) + Normalize(mean, std, to_rgb=True)
+ * (seg_segmentation/configs/_base_/datasets/pascal_voc12.py:19-34, mmcv / cv2 there) and the window slicing of mmseg's
+ * slide_inference; the resized image is never materialised.
+ *   images  : (B, 6) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
+ *             3 row stride in bytes (>= 3 w)  4 H  5 W, the network size the image is resized to
+ *   windows : (n_windows, 3) int32 rows (image, y0, x0) as above; here the image column IS read
+ *   mean, inv_std : 3 host floats each, copied into the launch
+ *   out     : (n_windows, 3, win_h, win_w) fp32, the layout segclip_im2col reads
+ * out[k, c, y, x] = (r - mean[c]) * inv_std[c] with r the source channel c (2 - c with reverse_channels: BGR sources) of image
+ * i resized to (H, W) at (Y, X) = (y0 + y, x0 + x).  Geometry of cv2 INTER_LINEAR = F.interpolate(mode="bilinear",
+ * align_corners=False, antialias=False), the scale taken from the two sizes: along an axis of n source and m destination pixels
+ * the coordinate of destination d is the rational ((2 d + 1) n - m) / (2 m), split in integers into s0 = its floor and
+ * f = (float)remainder / (float)(2 m); s0 < 0 -> s0 = 0, f = 0; s0 >= n - 1 -> s0 = n - 1, f = 0; s1 = min(s0 + 1, n - 1).
+ * In fp32: top = a (1 - fx) + b fx, bot = c (1 - fx) + d fx, r = top (1 - fy) + bot fy, each sum one fused multiply-add.  r is
+ * NOT rounded back to uint8 as cv2's 8-bit fixed-point resize does (about one grey level, 0.015 normalised; unmeasured).
+ *   Every table row is range-checked on the device.  A window is ZERO-FILLED when its image index is outside [0, B), when it
+ *   does not lie inside (H, W), or when its image row has a null address, a stride below 3 w, or one of h, w, H, W outside
+ *   [1, 2^15).  Nothing is read outside the (h, w, stride) a row states and nothing written outside `out`.
+ *   16-byte stores when win_w % 4 == 0 and out is 16-byte aligned, scalar stores otherwise (any win_w).  Bound: HBM writes,
+ *   12 bytes per window pixel.  SEGCLIP_ERR_UNSUPPORTED: win_h * win_w >= 2^31.  n_windows, B <= 2^24.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
+                                int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
+                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MAE random masking (integer path, bit-exact given the noise).  modules/module_clip_util.py:91-124
  * with keep_cls: noise[:,0] = -1; ids_shuffle = argsort(noise) (stable); ids_restore =
  * argsort(ids_shuffle); mask = 1 except the first len_keep of the shuffle.

@@ -168,6 +168,7 @@ SIGNATURES = {
     "segclip_seg_label_map_rescaled": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                                  vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_seg_areas": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
     "segclip_multi_cast_bf16": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_multi_add_f32": (C.c_int, [vp, vp, vp, i64, vp]),
     "segclip_max_tokens_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),

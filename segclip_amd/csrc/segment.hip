@@ -292,6 +292,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 }
 
 #include "segment_eval.inc"
+#include "segment_frontend.inc"
 
 }  // namespace
 
@@ -440,5 +441,32 @@ extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t
   hipLaunchKernelGGL(seg_areas_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
                      reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(areas));
   SEGCLIP_CHECK_LAUNCH("seg_areas");
+  return 0;
+}
+
+extern "C" int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
+                                           int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
+                                           void* stream) {
+  const int64_t lim = 1ll << 31;
+  SEGCLIP_REQUIRE(n_windows >= 0 && n_windows <= (1 << 24) && B >= 0 && B <= (1 << 24) && win_h >= 1 && win_w >= 1, "seg_windows_from_u8: sizes out of range");
+  SEGCLIP_REQUIRE(mean && inv_std, "seg_windows_from_u8: mean and inv_std are required");
+  if (win_h >= lim || win_w >= lim || win_h * win_w >= lim) {
+    segclip_set_error("seg_windows_from_u8: a window of %lld x %lld pixels, fewer than 2^31 supported", (long long)win_h, (long long)win_w);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (n_windows == 0) return 0;
+  SEGCLIP_REQUIRE(windows && out && (images || B == 0), "seg_windows_from_u8: images, windows and out are required");
+  SegFrontArgs a;
+  a.images = images; a.windows = windows; a.out = out;
+  a.B = (int)B; a.win_h = (int)win_h; a.win_w = (int)win_w; a.upr = (int)cdiv(win_w, SEG_FE_PPL);
+  const int64_t per_window = cdiv(win_h * a.upr, 256);
+  SEGCLIP_REQUIRE(n_windows * per_window < lim, "seg_windows_from_u8: %lld windows of %lld x %lld pixels exceed one launch",
+                  (long long)n_windows, (long long)win_h, (long long)win_w);
+  a.blocks_per_window = (int)per_window;
+  a.reverse = reverse_channels ? 1 : 0;
+  a.vec = (win_w % SEG_FE_PPL == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.inv_std[c] = inv_std[c]; }
+  hipLaunchKernelGGL(seg_front_kernel, dim3((unsigned)(n_windows * per_window)), dim3(256), 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_windows_from_u8");
   return 0;
 }

@@ -2466,3 +2466,62 @@ def seg_areas(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, 
     L.check(L.load().segclip_seg_areas(L.ptr(pred), L.ptr(gt), pred.numel(), int(num_classes), int(ignore_index),
                                        int(bool(reduce_zero_label)), L.ptr(areas), L.stream()), "seg_areas")
     return areas
+
+
+SEG_SOURCE_COLS = 6         # int64 columns of one row of the source table of segclip_seg_windows_from_u8
+SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
+
+
+def seg_source_table(raws, net_sizes):
+    """The device source table of seg_windows_from_u8: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows
+    possibly strided], net_sizes [(H, W)] -> (B, 6) int64.  It holds the tensors' addresses: keep `raws` alive while it is
+    in use."""
+    if len(raws) == 0 or len(raws) != len(net_sizes):
+        raise ValueError(f"seg_source_table: {len(raws)} images but {len(net_sizes)} network sizes")
+    L.require_cuda(*raws)
+    tab = []
+    for t, (H, W) in zip(raws, net_sizes):
+        if t.dtype != torch.uint8:
+            raise TypeError(f"seg_windows_from_u8: a source image is uint8, got {t.dtype}")
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"seg_windows_from_u8: a source image is (h, w, 3), got {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if t.device != raws[0].device:
+            raise ValueError("seg_windows_from_u8: the source images are on different devices")
+        if min(h, w, int(H), int(W)) < 1 or max(h, w, int(H), int(W)) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_windows_from_u8: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w} -> {H}x{W}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
+            raise ValueError(f"seg_windows_from_u8: a source image has interleaved channels and contiguous pixels (strides "
+                             f"(>= 3 w, 3, 1)), got {tuple(t.stride())}")
+        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(H), int(W)])
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_SOURCE_COLS)
+
+
+def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
+    """The fused front end (segclip_seg_windows_from_u8): decoded uint8 images -> (n_windows, 3, win_h, win_w) fp32, every
+    window pixel resized bilinearly (cv2 INTER_LINEAR geometry) from its image to the image's network size and normalised as
+    (r - mean[c]) * inv_std[c].  windows: (n_windows, 3) int32 device rows (image, y0, x0), or a list of them; a window outside
+    its image's network size or with an image index outside the list is zero-filled.  table: seg_source_table(raws,
+    net_sizes) when the caller launches several times on the same images."""
+    if table is None:
+        table = seg_source_table(raws, net_sizes)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (len(raws), SEG_SOURCE_COLS) or not table.is_contiguous():
+        raise ValueError("seg_windows_from_u8: table is the (B, 6) int64 tensor of seg_source_table")
+    if not torch.is_tensor(windows):
+        windows = torch.tensor(windows, dtype=torch.int32, device=table.device).view(-1, 3)
+    L.require_cuda(table, windows, out)
+    if windows.dtype != torch.int32 or windows.dim() != 2 or windows.shape[1] != 3:
+        raise ValueError("seg_windows_from_u8: windows is an (n_windows, 3) int32 tensor")
+    windows = windows.contiguous()
+    wh, ww = int(win_size[0]), int(win_size[1])
+    if wh < 1 or ww < 1 or len(mean) != 3 or len(inv_std) != 3:
+        raise ValueError("seg_windows_from_u8: a window has win_h, win_w >= 1; mean and inv_std have 3 entries")
+    n = windows.shape[0]
+    if out is None:
+        out = torch.empty(n, 3, wh, ww, dtype=torch.float32, device=table.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * 3 * wh * ww:
+        raise ValueError("seg_windows_from_u8: out is a contiguous fp32 tensor of n_windows * 3 * win_h * win_w elements")
+    f3 = L.f32 * 3
+    L.check(L.load().segclip_seg_windows_from_u8(L.ptr(table), L.ptr(windows), n, table.shape[0], wh, ww, f3(*mean), f3(*inv_std),
+                                                 int(bool(reverse_channels)), L.ptr(out), L.stream()), "seg_windows_from_u8")
+    return out

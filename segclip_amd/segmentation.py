@@ -8,10 +8,18 @@ once, all windows of all images of a call in one batch.
 
 The evaluation (main_seg_zeroshot.py:122-167 and mmseg's single_gpu_test / eval_metrics): SegInference.predict_list takes
 images of mixed sizes and writes their label maps at the ground truth's size in one launch (csrc/segment_eval.inc), and
-SegEvaluator accumulates mmseg's per-class areas in the same launch and turns them into mIoU / aAcc / mAcc.  The dataset, the
-image decoding, the tokenizer and the resize of an image to its test size (test_size gives the size) stay with the caller.
-mmseg takes a softmax between the resize and the arg-max; here the arg-max is taken of the logits, which can differ only
-where fp32 exp rounds two different logits to one value.
+SegEvaluator accumulates mmseg's per-class areas in the same launch and turns them into mIoU / aAcc / mAcc.
+
+The front end (the test pipeline of configs/_base_/datasets/pascal_voc12.py:19-34, mmcv's Resize(keep_ratio=True) and
+Normalize there): ImageTransform states it, and predict_raw / update_raw / preprocess take decoded (h, w, 3) uint8 images.
+One HIP kernel (csrc/segment_frontend.inc) writes the tower's input windows from the raw bytes, resized bilinearly and
+normalised on the way, so the resized image does not exist: decoded image in, mIoU out.  The dataset, the image decoding and
+the tokenizer stay with the caller.
+
+Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; here the arg-max is taken of the
+logits, which can differ only where fp32 exp rounds two different logits to one value.  A ground-truth value of 255 stays
+ignored whatever reduce_zero_label says.  The resized pixel is kept in fp32 and not rounded back to uint8 as cv2's 8-bit
+fixed-point resize does: about one grey level, 0.015 in normalised units (unmeasured: cv2 is not a dependency).
 """
 import math
 
@@ -43,6 +51,100 @@ def test_size(h, w, img_scale=(2048, 224)):
 
 
 test_size.__test__ = False   # a product function, not a test
+
+
+class ImageTransform:
+    """The test pipeline's Resize(keep_ratio=True) at img_scale + Normalize(mean, std) (pascal_voc12.py:19-34).  mean and std
+    are per channel in RGB order, in grey levels (the defaults are the VOC config's); channel_order is the order of the
+    decoded source's channels: "bgr" sources (cv2.imread) are reversed on the way, as to_rgb=True does."""
+
+    def __init__(self, img_scale=(2048, 224), mean=(122.7709383, 116.7460125, 104.09373615),
+                 std=(68.5005327, 66.6321579, 70.32316305), channel_order="rgb"):
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("mean and std have one entry per channel")
+        self.img_scale, self.channel_order = tuple(img_scale), channel_order
+        self.mean, self.std = tuple(float(m) for m in mean), tuple(float(v) for v in std)
+        # 1 / std in fp64, rounded to fp32 once: the kernel multiplies by exactly this number
+        self.inv_std = tuple(torch.tensor([1.0 / v for v in self.std], dtype=torch.float64).float().tolist())
+
+    def net_size(self, h, w):
+        """The (H, W) an (h, w) image is resized to."""
+        return test_size(h, w, self.img_scale)
+
+
+def _raw_sizes(raws, transform, net_sizes):
+    """Checks of a list of decoded images -> their network sizes [(H, W)]."""
+    if len(raws) == 0:
+        raise ValueError("empty image list")
+    if not isinstance(transform, ImageTransform):
+        raise TypeError("transform is an ImageTransform")
+    for t in raws:
+        if not t.is_cuda:
+            raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {t.device} tensor")
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    if net_sizes is None:
+        return [transform.net_size(int(t.shape[0]), int(t.shape[1])) for t in raws]
+    if len(net_sizes) != len(raws):
+        raise ValueError(f"{len(raws)} images but {len(net_sizes)} network sizes")
+    return [(int(a), int(b)) for (a, b) in net_sizes]
+
+
+def _raw_windows(raws, transform, sizes, table, dwin, wh, ww):
+    return ops.seg_windows_from_u8(raws, sizes, dwin, (wh, ww), transform.mean, transform.inv_std,
+                                   reverse_channels=transform.channel_order == "bgr", table=table)
+
+
+@torch.no_grad()
+def preprocess(raws, transform, net_sizes=None):
+    """[(h_i, w_i, 3) uint8] -> [(3, H_i, W_i) fp32]: every image resized to its network size (transform.net_size, or
+    net_sizes) and normalised, by the kernel of predict_raw with one whole-image window per image, one launch per distinct
+    size.  predict_list on the result equals predict_raw on the raw images bit for bit; predict_raw does not form it."""
+    sizes = _raw_sizes(raws, transform, net_sizes)
+    table = ops.seg_source_table(raws, sizes)
+    by_size = {}
+    for i, hw in enumerate(sizes):
+        by_size.setdefault(hw, []).append(i)
+    out = [None] * len(raws)
+    for (H, W), members in by_size.items():
+        x = _raw_windows(raws, transform, sizes, table, [(i, 0, 0) for i in members], H, W)
+        for k, i in enumerate(members):
+            out[i] = x[k]
+    return out
+
+
+class _SlicedImages:
+    """The tower input of _list_forward from images already resized and normalised: one slice per window."""
+
+    def __init__(self, model, imgs):
+        if len(imgs) == 0:
+            raise ValueError("empty image list")
+        for t in imgs:
+            _require_eval_gpu(model, t)
+            if t.dim() != 3 or t.shape[0] != 3:
+                raise ValueError(f"predict_list takes (3, H, W) images, got {tuple(t.shape)}")
+        self.imgs, self.device = imgs, imgs[0].device
+        self.sizes = [(int(t.shape[1]), int(t.shape[2])) for t in imgs]
+        self.default_out = self.sizes
+
+    def windows(self, chunk, dwin, wh, ww):
+        return torch.stack([self.imgs[i][:, y:y + wh, x0:x0 + ww] for (i, y, x0) in chunk])
+
+
+class _RawImages:
+    """The tower input of _list_forward from decoded uint8 images: the front-end kernel writes a chunk's windows."""
+
+    def __init__(self, model, raws, transform, net_sizes):
+        self.sizes = _raw_sizes(raws, transform, net_sizes)
+        _require_eval_gpu(model, raws[0])
+        self.raws, self.transform, self.device = raws, transform, raws[0].device
+        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
+        self.table = ops.seg_source_table(raws, self.sizes)
+
+    def windows(self, chunk, dwin, wh, ww):
+        return _raw_windows(self.raws, self.transform, self.sizes, self.table, dwin, wh, ww)
 
 
 def _require_eval_gpu(model, t):
@@ -194,32 +296,30 @@ class SegInference:
             n += len(members)
         return batches, per_image
 
-    def _list_forward(self, imgs, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True):
-        if len(imgs) == 0:
-            raise ValueError("empty image list")
-        for t in imgs:
-            _require_eval_gpu(self.model, t)
-            if t.dim() != 3 or t.shape[0] != 3:
-                raise ValueError(f"predict_list takes (3, H, W) images, got {tuple(t.shape)}")
-        sizes = [(int(t.shape[1]), int(t.shape[2])) for t in imgs]
+    def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True):
+        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows."""
+        sizes, n_img = src.sizes, len(src.sizes)
         if out_shapes is None:
-            out_shapes = sizes
-        if len(out_shapes) != len(imgs):
-            raise ValueError(f"{len(imgs)} images but {len(out_shapes)} output shapes")
+            out_shapes = src.default_out
+        if len(out_shapes) != n_img:
+            raise ValueError(f"{n_img} images but {len(out_shapes)} output shapes")
         out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
         if self.num_classes > 256:
             raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
         p = self.model.clip.visual.patch_size
         batches, per_image = self._list_plan(sizes)
         N = self.text_embedding.shape[0]
-        dev = imgs[0].device
-        parts, wins_all, win_off, floats = [], [], [], 0   # win_off: a window's offset in the flat soft_attn
-        for (wh, ww), wins in batches:
+        dev = src.device
+        for (wh, ww), _ in batches:
             if wh % p or ww % p:
                 raise ValueError(f"window {wh}x{ww} is not a multiple of the patch size {p}")
+        wins_all = [w for _, wins in batches for w in wins]
+        dwin = torch.tensor(wins_all, dtype=torch.int32, device=dev).view(-1, 3)
+        parts, done, win_off, floats = [], 0, [], 0   # win_off: a window's offset in the flat soft_attn
+        for (wh, ww), wins in batches:
             for s in range(0, len(wins), self.max_windows):
                 chunk = wins[s:s + self.max_windows]
-                x = torch.stack([imgs[i][:, y:y + wh, x0:x0 + ww] for (i, y, x0) in chunk])
+                x = src.windows(chunk, dwin[done + s:done + s + len(chunk)], wh, ww)
                 with config.scope(cross_mode="intended"):   # see _windows_forward
                     feat, hidden, mid = self.model.clip.encode_image(x, return_hidden=True)
                 if not mid["attns"]:
@@ -231,7 +331,7 @@ class SegInference:
                 win_off += range(floats, floats + soft.numel(), soft.numel() // soft.shape[0])
                 floats += soft.numel()
                 parts.append((soft.reshape(-1),) + tables)
-            wins_all += wins
+            done += len(wins)
         if len(parts) == 1:
             soft, tables = parts[0][0], parts[0][1:]
         else:
@@ -243,7 +343,6 @@ class SegInference:
                              soft_off=win_off[first], gt_off=gt_off if gts is not None else -1))
             gt_off += out_shapes[i][0] * out_shapes[i][1]
         images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, dev)
-        dwin = torch.tensor(wins_all, dtype=torch.int32, device=dev).view(-1, 3)
         labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
         gt = None
         if gts is not None:
@@ -260,7 +359,15 @@ class SegInference:
         to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
         Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size."""
-        return self._list_forward(imgs, out_shapes)
+        return self._list_forward(_SlicedImages(self.model, imgs), out_shapes)
+
+    @torch.no_grad()
+    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None):
+        """[(h_i, w_i, 3) uint8 decoded images] -> [(oh_i, ow_i) uint8 labels] as predict_list(preprocess(raws, transform,
+        net_sizes), out_shapes), bit for bit, without the resized images: the windows of a tower call are written from the
+        raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
+        ori_shape); net_sizes overrides transform.net_size (whole mode needs multiples of the patch size)."""
+        return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes)
 
 
 class SegEvaluator:
@@ -279,6 +386,17 @@ class SegEvaluator:
     @torch.no_grad()
     def update(self, imgs, gts, return_labels=False):
         """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size."""
+        self._check_gts(imgs, gts)
+        return self._forward(_SlicedImages(self.seg.model, imgs), gts, return_labels)
+
+    @torch.no_grad()
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None):
+        """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw."""
+        self._check_gts(raws, gts)
+        return self._forward(_RawImages(self.seg.model, raws, transform, net_sizes), gts, return_labels)
+
+    @staticmethod
+    def _check_gts(imgs, gts):
         if len(imgs) != len(gts):
             raise ValueError(f"{len(imgs)} images but {len(gts)} ground truths")
         for g in gts:
@@ -286,7 +404,9 @@ class SegEvaluator:
                 raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {g.device} tensor")
             if g.dtype != torch.uint8 or g.dim() != 2:
                 raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
-        return self.seg._list_forward(imgs, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
+
+    def _forward(self, src, gts, return_labels):
+        return self.seg._list_forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
                                       ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
                                       want_labels=return_labels)
 

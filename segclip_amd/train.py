@@ -267,13 +267,15 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
     return total / max(n_batches, 1), global_step
 
 
-def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_cfg=None):
+def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_cfg=None, transform=None):
     """The zero-shot segmentation score of a checkpoint (main_task_align.py:361-370 -> main_seg_zeroshot.py:122-167):
     mIoU * 100 over `batches`, an iterable of (imgs, gts) with imgs a list of (3, H, W) images already resized to their test
     size (segmentation.test_size) and gts the (oh, ow) uint8 ground truths.  text_tokens (N, T, L): the class prompts;
     test_cfg: keyword arguments of SegInference (mode, crop_size, stride, bg_thresh, max_windows) and optionally
-    ignore_index / reduce_zero_label.  The areas stay on the device until the end.  With several ranks every rank scores its
-    own share; all_reduce SegEvaluator.areas instead of calling this when one figure over all ranks is wanted."""
+    ignore_index / reduce_zero_label.  With transform (a segmentation.ImageTransform) imgs are the decoded (h, w, 3) uint8
+    images instead, resized and normalised on the device (SegEvaluator.update_raw).  The areas stay on the device until the
+    end.  With several ranks every rank scores its own share; all_reduce SegEvaluator.areas instead of calling this when one
+    figure over all ranks is wanted."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
@@ -282,7 +284,11 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     emb = build_text_embedding(model, text_tokens.to(device))
     evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label)
     for imgs, gts in batches:
-        evaluator.update([t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts])
+        imgs, gts = [t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts]
+        if transform is None:
+            evaluator.update(imgs, gts)
+        else:
+            evaluator.update_raw(imgs, gts, transform)
     miou = evaluator.compute()["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)

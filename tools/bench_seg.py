@@ -12,7 +12,13 @@ With --eval instead: the mIoU evaluation of 64 images of mixed VOC-like sizes (2
   (iv)  images/s of SegEvaluator.update (one call for the list), the time of segclip_seg_label_map_rescaled alone, the time of
         the Python-side window extraction (torch.stack of slices) alone, peak allocation, and the same evaluation done the
         obvious way on the same GPU: encode_decode per image -> F.interpolate -> argmax -> three histc, batch 1.
-usage: python tools/bench_seg.py [--eval] [reps=7] [out=profiles/seg_infer.txt | profiles/seg_eval.txt]"""
+With --raw instead: the same 64 images as decoded uint8 (h, w, 3) tensors, in ONE command and alternating within every repeat:
+  (v)   images/s of SegEvaluator.update_raw (the fused front-end kernel), of segmentation.preprocess + update (the same kernel
+        writing the resized images, then torch.stack of slices), and of an eager-torch front end + update (per image a float
+        copy, F.interpolate, normalise; then the slices); the front-end kernel's own time from a separate
+        `rocprofv3 --kernel-trace --stats` child (--raw-child: five update_raw calls and nothing else) and its bytes per second
+        against the HBM peak.
+usage: python tools/bench_seg.py [--eval | --raw] [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt]"""
 import os
 import statistics
 import sys
@@ -27,11 +33,12 @@ from segclip_amd import config, ops, synth
 from segclip_amd.segmentation import SegInference
 from tools.clock_sampler import ClockSampler
 
-EVAL = "--eval" in sys.argv[1:]
-ARGV = [a for a in sys.argv[1:] if a != "--eval"]
+EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("--raw-child" in sys.argv[1:])
+ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_eval.txt" if EVAL else "seg_infer.txt")
+                                                 "seg_frontend.txt" if RAW else "seg_eval.txt" if EVAL else "seg_infer.txt")
+HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
 
 
@@ -206,6 +213,107 @@ def eval_case(model, text, n_images=64):
         f"{peak_of(obvious) / 2**20:8.1f} MiB")
 
 
+def raw_inputs(seg, n_images=64):
+    g = torch.Generator().manual_seed(1)
+    outs = [EVAL_SIZES[i % len(EVAL_SIZES)] for i in range(n_images)]
+    raws = [torch.randint(0, 256, (*o, 3), generator=g, dtype=torch.uint8).cuda() for o in outs]
+    gts = [torch.randint(0, seg.num_classes, o, generator=g).to(torch.uint8).cuda() for o in outs]
+    return raws, gts
+
+
+def raw_case(model, text, n_images=64):
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator, preprocess
+    from tools import rocprof_roofline as rr
+    name = f"(v)  raw    {n_images} mixed sizes"
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    tf = ImageTransform()
+    raws, gts = raw_inputs(seg, n_images)
+    ev = SegEvaluator(seg)
+    mean = torch.tensor(tf.mean, device="cuda")[:, None, None]
+    std = torch.tensor(tf.std, device="cuda")[:, None, None]
+
+    def eager_front():
+        return [(F.interpolate(r.permute(2, 0, 1)[None].float(), size=tf.net_size(r.shape[0], r.shape[1]), mode="bilinear",
+                               align_corners=False)[0] - mean) / std for r in raws]
+
+    ways = [("update_raw", lambda: ev.update_raw(raws, gts, tf)),
+            ("preprocess + update", lambda: ev.update(preprocess(raws, tf), gts)),
+            ("eager front end + update", lambda: ev.update(eager_front(), gts))]
+    with torch.no_grad():
+        areas = []
+        for _, fn in ways:   # warm-up, and the three ways' areas
+            ev.reset()
+            fn()
+            areas.append(ev.areas.clone())
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):   # alternating: every repeat times the three ways one after the other
+            for k, (_, fn) in enumerate(ways):
+                t0 = time.perf_counter()
+                fn()
+                fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / 2)
+        clk = sampler.stop()
+    meds = [statistics.median(t) for t in ts]
+    for (what, _), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:26s} {med * 1e3:8.2f} ms (min {min(t) * 1e3:.2f}, max {max(t) * 1e3:.2f}; {REPS} x 2 calls)  "
+            f"{n_images / med:8.1f} images/s")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts[:2])
+    say(f"{name}: update_raw / (preprocess + update) {meds[0] / meds[1]:.4f}, update_raw / (eager front end + update) "
+        f"{meds[0] / meds[2]:.4f}; run-to-run spread of the first two {spread:.4f} of the median; clock {clk}")
+    same = float((areas[0] - areas[2]).abs().sum()) / float(areas[2].sum())
+    say(f"{name}: areas of update_raw and preprocess + update equal: {bool(torch.equal(areas[0], areas[1]))}; against the eager "
+        f"front end (ATen's fp32 coordinates) they differ by {same:.2e} of their sum")
+    # the kernel's bytes, from the arguments of one update_raw
+    captured = {}
+    real = ops.seg_windows_from_u8
+
+    def capture(*a, **k):
+        out = real(*a, **k)
+        captured["written"] = captured.get("written", 0) + out.numel() * 4
+        return out
+
+    ops.seg_windows_from_u8 = capture
+    try:
+        with torch.no_grad():
+            ev.update_raw(raws, gts, tf)
+    finally:
+        ops.seg_windows_from_u8 = real
+    written, source = captured["written"], sum(r.numel() for r in raws)
+    # its own time: a child of this tool that only calls update_raw, under rocprofv3 --kernel-trace --stats
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--raw-child"], tmp)
+            db = rr.find_db(tmp)
+            rows = [r for r in rr.kernel_table(db) if "seg_front_kernel" in r[0]] if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, rows = -1, repr(e), []
+    if rows:
+        _, calls, total_us, avg_us = rows[0]
+        say(f"{name}: segclip_seg_windows_from_u8 alone (rocprofv3 --kernel-trace --stats, {calls} launches) {avg_us:8.1f} us per launch: "
+            f"{written} bytes written, {source} source bytes = {written / avg_us / 1e6:.3f} TB/s written "
+            f"({written / avg_us * 1e6 / HBM_PEAK:.3f} of the {HBM_PEAK / 1e12:.1f} TB/s HBM peak), {(written + source) / avg_us / 1e6:.3f} TB/s "
+            f"with the source read once; share of update_raw {avg_us * 1e-6 / meds[0]:.5f}")
+    else:
+        say(f"{name}: segclip_seg_windows_from_u8 alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+
+
+def raw_child(model, text):
+    """Five update_raw calls and nothing else: what the rocprofv3 child of raw_case traces."""
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    raws, gts = raw_inputs(seg)
+    ev = SegEvaluator(seg)
+    with torch.no_grad():
+        for _ in range(5):
+            ev.update_raw(raws, gts, ImageTransform())
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -214,7 +322,12 @@ if __name__ == "__main__":
     text = torch.randn(20, 512, generator=g)
     text = (text / text.norm(dim=-1, keepdim=True)).cuda()
     say(f"# tools/bench_seg.py  ViT-B/16 synthetic weights, bf16 towers, 20 classes + background, {torch.cuda.get_device_name(0)}")
-    if EVAL:
+    if RAW_CHILD:
+        raw_child(model, text)
+        sys.exit(0)
+    if RAW:
+        raw_case(model, text)
+    elif EVAL:
         eval_case(model, text)
     else:
         case("(i)  whole  B=64 224x224", model, text, 64, 224, 224, 3)
