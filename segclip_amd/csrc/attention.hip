@@ -14,6 +14,8 @@
 // f32 path (exact parity mode): S = scale*Q K^T, row softmax, O = P V as three launches of the f32 MFMA
 //   GEMM + a softmax kernel; P is kept for backward (5 GEMMs + one elementwise kernel).
 #include <stdlib.h>
+#include <algorithm>
+#include <atomic>
 
 #include "common.h"
 
@@ -653,12 +655,8 @@ __global__ void softmax_bwd_rows_kernel(const float* __restrict__ P, float* __re
   for (int c = lane; c < Tk; c += 64) d[c] = p[c] * (d[c] - dot) * scale;
 }
 
-void base_gemm(segclip_gemm_desc& g, const segclip_attn_desc* d) {
-  g = segclip_gemm_desc{};
-  g.nb1 = d->B; g.nb2 = d->H;
-  g.a_dtype = g.b_dtype = g.c_dtype = g.r_dtype = SEGCLIP_F32;
-  g.alpha = 1.f;
-}
+// ------------------------------- host side -------------------------------------------
+// segclip_attn_fwd / segclip_attn_bwd: validate, fill the kernel arguments, plan (which kernel), launch, note the route.
 
 bool bf16_ok(const segclip_attn_desc* d) {
   const int64_t s[] = {d->q_sb, d->q_st, d->k_sb, d->k_st, d->v_sb, d->v_st, d->o_sb, d->o_st};
@@ -666,62 +664,259 @@ bool bf16_ok(const segclip_attn_desc* d) {
   return d->hd % 8 == 0 && d->hd <= 64;
 }
 
+// the tuning switches of the dispatcher (common.h), read once; each is explained where it is asked
+struct Tuning {
+  int smallq = segclip_tuning_int("SEGCLIP_ATTN_SMALLQ", 1);
+  int fwd_staged = segclip_tuning_int("SEGCLIP_ATTN_FWD_STAGED", -1), fwd_lean = segclip_tuning_int("SEGCLIP_ATTN_FWD_LEAN", 1);
+  int fwd_pf = segclip_tuning_int("SEGCLIP_ATTN_FWD_PF", 1), fwd_grid = segclip_tuning_int("SEGCLIP_ATTN_FWD_GRID", 0);
+  int bwd_dqw_long = segclip_tuning_int("SEGCLIP_ATTN_BWD_DQW_LONG", 1), bwd_dqw = segclip_tuning_int("SEGCLIP_ATTN_BWD_DQW", 1);
+  int bwd_sp = segclip_tuning_int("SEGCLIP_ATTN_BWD_SP", 1), bwd_spl = segclip_tuning_int("SEGCLIP_ATTN_BWD_SPL", 1);
+  int bwd_grid = segclip_tuning_int("SEGCLIP_ATTN_BWD_GRID", -1), bwd_waves = segclip_tuning_int("SEGCLIP_ATTN_BWD_WAVES", 0);
+};
+const Tuning& tuning() { static const Tuning t; return t; }
 
-// persistent forward (attention_pf.inc): launch instance <NT, CAUSAL> on a grid of as many workgroups as the device holds
+// ---- the planner: pure functions of the descriptor and the switches, no HIP call ----
+struct Plan {
+  int route, tiles, variant;   // what segclip_attn_route_note records after the launch
+  int waves;                   // per workgroup, a loader / dQ wave included (0: the streaming pair sizes its own)
+  size_t lds;                  // dynamic LDS bytes
+  int staged;                  // forward: FwdArgs::staged
+};
+int tiles_of(const segclip_attn_desc* d) { return (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32); }
+bool long_seq(const segclip_attn_desc* d) { return d->Tq > TMAX || d->Tk > TMAX; }
+
+Plan plan_fwd(const segclip_attn_desc* d) {
+  const Tuning& t = tuning();
+  if (d->dtype != SEGCLIP_BF16) return {SEGCLIP_ATTN_ROUTE_F32, tiles_of(d)};
+  // LDS-staged output rows: 117 -> 112 us at T = 196 (B = 256, H = 12), 27.8 -> 29.3 us at T = 77: on for the long sequences
+  // (SEGCLIP_ATTN_FWD_STAGED = 0 / 1 forces them off / on)
+  const int staged = t.fwd_staged >= 0 ? t.fwd_staged : (d->Tq > 128 ? 1 : 0);
+  // at most 8 queries (the learnable-center cross-attention): one wave per (batch, head), VALU.  SEGCLIP_ATTN_SMALLQ=0: off
+  if (t.smallq && smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_FWD, smallq::lds_bytes((int)d->Tk, false), staged};
+  const int tiles = (int)cdiv(d->Tq, 32);
+  const size_t pf_lds = fwd_pf_lds_bytes(tiles, (int)d->Tq);
+  // self-attention of 65..96 / 161..200 tokens: the persistent kernel with a loader wave (attention_pf.inc);
+  // SEGCLIP_ATTN_FWD_PF=0 falls back to one workgroup per (batch, head)
+  if (t.fwd_pf && d->Tq == d->Tk && !(d->flags & SEGCLIP_ATTN_FP8) && (tiles == 3 || tiles == 6 || tiles == 7) && pf_lds <= 160 * 1024)
+    return {SEGCLIP_ATTN_ROUTE_PF, tiles, d->causal ? 1 : 0, tiles + 1, pf_lds, staged};
+  // one wave per query tile, at most 8 per workgroup, spread evenly over the workgroups of a (batch, head)
+  const int nw = tiles < 8 ? tiles : (tiles <= 8 ? 8 : (int)cdiv(tiles, cdiv(tiles, 8)));
+  return {SEGCLIP_ATTN_ROUTE_GENERIC, tiles, (staged ? 1 : 0) | nw << 8, nw, 0, staged};
+}
+
+Plan plan_bwd(const segclip_attn_desc* d) {
+  const Tuning& t = tuning();
+  const int tiles = tiles_of(d);
+  if (d->dtype != SEGCLIP_BF16) return {SEGCLIP_ATTN_ROUTE_F32, tiles};
+  if (t.smallq && smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_BWD, smallq::lds_bytes((int)d->Tk, true)};
+  if (long_seq(d)) {
+    // unmasked self-attention, head_dim 64: the dQ-wave kernel over chunks of 224 keys (attention_dqw.inc, MULTI).
+    // SEGCLIP_ATTN_BWD_DQW_LONG=0 (tuning) keeps the two streaming launches
+    // (its token sums ride on a padded key in the last chunk and on two padded rows of the last query tile)
+    if (t.bwd_dqw_long && d->Tq == d->Tk && !d->causal && d->hd == 64 && d->Tq % 32 <= 30 && d->Tq % 224 != 0)
+      return {SEGCLIP_ATTN_ROUTE_DQW, 7, 1, 8, bwd_dqw_lds_bytes<7>()};
+    return {SEGCLIP_ATTN_ROUTE_STREAM, tiles, 0, 0, bwd_stream_lds_bytes()};   // two streaming launches (dK,dV | dQ)
+  }
+  const bool masked = d->causal || d->klen;
+  // self-attention: the single-pass kernels, one wave per key tile.  SEGCLIP_ATTN_BWD_SP=0 falls back to the two-pass kernel
+  // (benchmarking); cross-attention (Tq != Tk) always takes the two-pass kernel.
+  if (t.bwd_sp && d->Tq == d->Tk) {
+    // vision tower (no mask, head_dim 64, 7 tiles, padded rows in the last tile): the query tiles as a stream with a dQ wave
+    // (attention_dqw.inc, round 6); SEGCLIP_ATTN_BWD_DQW=0 keeps the kernels below
+    if (t.bwd_dqw && !masked && d->hd == 64 && tiles == 7 && d->Tq % 32 >= 1 && d->Tq % 32 <= 30)
+      return {SEGCLIP_ATTN_ROUTE_DQW, 7, 0, 8, bwd_dqw_lds_bytes<7>()};
+    // vision tower (no mask, 5-7 tiles): the variant whose memory traffic is issued by a loader wave (attention_spl.inc);
+    // SEGCLIP_ATTN_BWD_SPL=0 keeps attention_sp.inc
+    // head_dim 64 only: its loader wave copies whole 128-byte rows of Q, so with a smaller head the columns beyond it (the next
+    // head, or whatever follows the last one) would enter S = K Q^T against zeroed K columns: 0 x NaN, and a read past the
+    // end of a separately allocated Q.  Smaller heads take attention_sp.inc, which selects by column.
+    const size_t spl_lds = bwd_spl_lds_bytes((int)d->Tq);
+    if (t.bwd_spl && !masked && d->hd == 64 && tiles >= 5 && tiles <= 7 && spl_lds <= 160 * 1024)
+      return {SEGCLIP_ATTN_ROUTE_SPL, tiles, 0, tiles + 1, spl_lds};
+    return {SEGCLIP_ATTN_ROUTE_SP, tiles, masked ? 1 : 0, tiles, bwd_sp_lds_bytes(tiles * 32)};   // variant: instance <MASKED>
+  }
+  // 4 waves per workgroup (each wave walks over 1-2 tiles): two such workgroups fit the registers (2 waves per SIMD
+  // at ~215 VGPRs) and the LDS of a CU, so their load / MFMA / store phases interleave.  SEGCLIP_ATTN_BWD_WAVES
+  // overrides (benchmarking).
+  int nw = tiles < 4 ? tiles : 4;
+  if (t.bwd_waves >= 1 && t.bwd_waves <= 8) nw = tiles < t.bwd_waves ? tiles : t.bwd_waves;
+  return {SEGCLIP_ATTN_ROUTE_TWOPASS, tiles, nw << 8, nw, bwd_lds_bytes(tiles * 32)};
+}
+
+// ---- per-device state (function attributes and the CU count belong to the device a launch goes to), in atomics: two host
+// threads may enter at once (config.scope() is per thread); both fill an empty entry alike ----
+constexpr int MAX_DEVICES = 64;
+struct Device { int index, ncu; };
+std::atomic<int> device_ncu[MAX_DEVICES];
+std::atomic<int> pf_per_cu[MAX_DEVICES][2][8][33];   // attention_pf.inc: workgroups per CU by (causal, tiles, key tile rows / 8)
+
+// the current device and its CU count (256 where the runtime does not tell), for the workspace query and every launcher
+// alike, so that the grid of a launch and the workspace sized for it agree
+bool current_device(Device& dv) {
+  if (hipGetDevice(&dv.index) != hipSuccess || dv.index < 0 || dv.index >= MAX_DEVICES) return false;
+  if ((dv.ncu = device_ncu[dv.index]) == 0) {
+    if (hipDeviceGetAttribute(&dv.ncu, hipDeviceAttributeMultiprocessorCount, dv.index) != hipSuccess || dv.ncu <= 0) dv.ncu = 256;
+    device_ncu[dv.index] = dv.ncu;
+  }
+  return true;
+}
+
+// raises the dynamic-LDS limit of KERNEL once per (kernel, device): 0, or the refusal of `who` (attn_fwd / attn_bwd)
+template <auto KERNEL>
+int raise_lds_limit(const char* who, const Device& dv, size_t bytes) {
+  static std::atomic<bool> done[MAX_DEVICES];
+  if (done[dv.index]) return 0;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  SEGCLIP_REQUIRE(e == hipSuccess, "%s bf16: cannot raise the dynamic LDS limit: %s", who, hipGetErrorString(e));
+  done[dv.index] = true;
+  return 0;
+}
+
+// KERNEL on `grid` workgroups of `waves` waves with the planned dynamic LDS
+template <auto KERNEL, typename... Args>
+int launch(const char* name, dim3 grid, int waves, const Plan& p, hipStream_t stream, const Args&... args) {
+  hipLaunchKernelGGL(KERNEL, grid, dim3(waves * 64), p.lds, stream, args...);
+  SEGCLIP_CHECK_LAUNCH(name);
+  return 0;
+}
+
+// ---- forward launchers (smallq: launch<>) ----
+// persistent forward (attention_pf.inc), instance <NT, CAUSAL>: as many workgroups as the device holds
 template <int NT, bool CAUSAL>
-int launch_fwd_pf(const FwdArgs& a, int nitems, hipStream_t stream) {
-  int dev = 0;
-  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "attn_fwd: cannot query the current device");
-  static bool attr_set[64] = {};
-  static int ncu_dev[64] = {};
-  static int per_cu_cache[64][33] = {};                    // by (device, key tile rows / 8)
-  const size_t lds = fwd_pf_lds_bytes(NT, a.Tq);
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_pf_kernel<NT, CAUSAL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    SEGCLIP_REQUIRE(e == hipSuccess, "attn_fwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    ncu_dev[dev] = ncu;
-    attr_set[dev] = true;
+int launch_fwd_pf_as(const FwdArgs& a, const Plan& p, int nitems, hipStream_t stream) {
+  Device dv;
+  SEGCLIP_REQUIRE(current_device(dv), "attn_fwd: cannot query the current device");
+  if (int rc = raise_lds_limit<attn_fwd_pf_kernel<NT, CAUSAL>>("attn_fwd", dv, 160 * 1024)) return rc;
+  std::atomic<int>& cached = pf_per_cu[dv.index][CAUSAL][NT][pf_kv_rows(a.Tq) >> 3];
+  int per_cu = cached;
+  if (per_cu == 0) {   // SEGCLIP_ATTN_FWD_GRID overrides what the occupancy query says
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_fwd_pf_kernel<NT, CAUSAL>, p.waves * 64, p.lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (tuning().fwd_grid > 0) per_cu = tuning().fwd_grid;
+    cached = per_cu;
   }
-  int& per_cu = per_cu_cache[dev][pf_kv_rows(a.Tq) >> 3];
-  if (per_cu == 0) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_pf_kernel<NT, CAUSAL>, (NT + 1) * 64, lds) != hipSuccess || n < 1) n = 1;
-    static const int grid_env = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_GRID"); return e ? atoi(e) : 0; }();
-    per_cu = grid_env > 0 ? grid_env : n;
+  return launch<attn_fwd_pf_kernel<NT, CAUSAL>>("attn_fwd_pf", dim3(std::min(nitems, dv.ncu * per_cu)), p.waves, p, stream, a, nitems);
+}
+int launch_fwd_pf(const FwdArgs& a, const Plan& p, int nitems, hipStream_t stream) {
+  switch (p.tiles * 2 + p.variant) {   // variant: causal.  plan_fwd picks 3, 6 or 7 tiles
+    case 3 * 2: return launch_fwd_pf_as<3, false>(a, p, nitems, stream);
+    case 3 * 2 + 1: return launch_fwd_pf_as<3, true>(a, p, nitems, stream);
+    case 6 * 2: return launch_fwd_pf_as<6, false>(a, p, nitems, stream);
+    case 6 * 2 + 1: return launch_fwd_pf_as<6, true>(a, p, nitems, stream);
+    case 7 * 2: return launch_fwd_pf_as<7, false>(a, p, nitems, stream);
+    default: return launch_fwd_pf_as<7, true>(a, p, nitems, stream);
   }
-  const int cap = ncu_dev[dev] * per_cu;
-  const int grid = nitems < cap ? nitems : cap;
-  hipLaunchKernelGGL((attn_fwd_pf_kernel<NT, CAUSAL>), dim3((unsigned)grid), dim3((NT + 1) * 64), lds, stream, a, nitems);
-  SEGCLIP_CHECK_LAUNCH("attn_fwd_pf");
-  segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_PF, NT, CAUSAL ? 1 : 0);
-  return 0;
 }
 
-// streaming backward with a dQ wave (attention_dqw.inc): one workgroup of NT + 1 waves per CU walks its share of the items
-template <int NT, bool MULTI>
-int launch_bwd_dqw(const BwdArgs& a, int ncu, int dev, hipStream_t stream) {
-  static bool attr_set[64] = {};
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dqw_bf16_kernel<NT, MULTI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    SEGCLIP_REQUIRE(e == hipSuccess, "attn_bwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    attr_set[dev] = true;
+int launch_fwd_generic(const segclip_attn_desc* d, const FwdArgs& a, const Plan& p, hipStream_t stream) {
+  SEGCLIP_REQUIRE(d->B * d->H <= 65535, "attn_fwd: B*H too large");
+  if (d->flags & SEGCLIP_ATTN_FP8) {
+    segclip_set_error("attn_fwd: the e4m3 forward was removed (slower than bf16 at head_dim 64, DESIGN.md section 8): "
+                      "configs[4] runs bf16 attention");
+    return SEGCLIP_ERR_UNSUPPORTED;
   }
-  const int grid = a.nitems < ncu ? a.nitems : ncu;
-  hipLaunchKernelGGL((attn_bwd_dqw_bf16_kernel<NT, MULTI>), dim3((unsigned)grid), dim3((NT + 1) * 64), bwd_dqw_lds_bytes<NT>(), stream, a);
-  SEGCLIP_CHECK_LAUNCH("attn_bwd_dqw_bf16");
-  segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_DQW, NT, MULTI ? 1 : 0);
-  return 0;
+  return launch<attn_fwd_bf16_kernel>("attn_fwd_bf16", dim3((unsigned)cdiv(p.tiles, p.waves), (unsigned)(d->B * d->H)), p.waves, p, stream, a);
 }
 
-// workgroups of the key-chunked dqw launch: the CUs of the current device
-int dqw_multi_max_grid() {
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  return n;
+// f32 path: one batched GEMM C(m,n) = alpha * sum_k A(m,k) B(n,k) over the B * H (sample, head) pairs.  An operand is
+// {pointer, stride of its first index, stride of k (for C: 1), stride per sample, stride per head}
+struct Mat { const void* p; int64_t s0, sk, sb, sh; };
+int gemm_f32(const segclip_attn_desc* d, hipStream_t stream, int64_t M, int64_t N, int64_t K, Mat A, Mat B, Mat C, float alpha = 1.f) {
+  segclip_gemm_desc g{};
+  g.nb1 = d->B; g.nb2 = d->H;
+  g.a_dtype = g.b_dtype = g.c_dtype = g.r_dtype = SEGCLIP_F32;
+  g.alpha = alpha;
+  g.A = A.p; g.B = B.p; g.C = const_cast<void*>(C.p); g.M = M; g.N = N; g.K = K;
+  g.sam = A.s0; g.sak = A.sk; g.sbn = B.s0; g.sbk = B.sk; g.ldc = C.s0;
+  g.bsA1 = A.sb; g.bsA2 = A.sh; g.bsB1 = B.sb; g.bsB2 = B.sh; g.bsC1 = C.sb; g.bsC2 = C.sh;
+  return segclip_gemm_f32_launch(&g, stream);
+}
+Mat scores(const segclip_attn_desc* d, const void* p, bool transposed) {   // P, dP: [B][H][Tq][Tk], as (q, key) or as (key, q)
+  return transposed ? Mat{p, 1, d->Tk, d->H * d->Tq * d->Tk, d->Tq * d->Tk} : Mat{p, d->Tk, 1, d->H * d->Tq * d->Tk, d->Tq * d->Tk};
+}
+
+// f32: S -> stats, softmax in place, O = P V
+int launch_fwd_f32(const segclip_attn_desc* d, hipStream_t stream) {
+  float* P = (float*)d->stats;
+  if (int rc = gemm_f32(d, stream, d->Tq, d->Tk, d->hd, {d->Q, d->q_st, 1, d->q_sb, d->hd}, {d->K, d->k_st, 1, d->k_sb, d->hd}, scores(d, P, false), d->scale)) return rc;
+  const int64_t rows = d->B * d->H * d->Tq;
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, P, rows, (int)d->Tq,
+                     (int)d->Tk, d->causal, (const int*)d->klen, (int)d->H);
+  SEGCLIP_CHECK_LAUNCH("attn_softmax_rows");
+  return gemm_f32(d, stream, d->Tq, d->hd, d->Tk, scores(d, P, false), {d->V, 1, d->v_st, d->v_sb, d->hd}, {d->O, d->o_st, 1, d->o_sb, d->hd});
+}
+
+// ---- backward launchers (smallq: launch<>) ----
+// streaming backward with a dQ wave (attention_dqw.inc): one workgroup of 7 + 1 waves per CU walks its share of the items
+template <bool MULTI>
+int launch_bwd_dqw(const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
+  if (int rc = raise_lds_limit<attn_bwd_dqw_bf16_kernel<7, MULTI>>("attn_bwd", dv, 160 * 1024)) return rc;
+  return launch<attn_bwd_dqw_bf16_kernel<7, MULTI>>("attn_bwd_dqw_bf16", dim3(std::min(a.nitems, dv.ncu)), p.waves, p, stream, a);
+}
+
+// long sequences: two streaming launches (dK,dV | dQ), 8 owned tiles per workgroup
+int launch_bwd_stream(const segclip_attn_desc* d, const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
+  if (raise_lds_limit<attn_bwd_dkv_stream_kernel>("attn_bwd", dv, p.lds) || raise_lds_limit<attn_bwd_dq_stream_kernel>("attn_bwd", dv, p.lds))
+    SEGCLIP_REQUIRE(false, "attn_bwd bf16: cannot raise the dynamic LDS limit");   // names no cause
+  const int ktiles = (int)cdiv(d->Tk, 32), qtiles = (int)cdiv(d->Tq, 32);
+  const int nwk = ktiles < 8 ? ktiles : 8, nwq = qtiles < 8 ? qtiles : 8;
+  if (int rc = launch<attn_bwd_dkv_stream_kernel>("attn_bwd_dkv_stream", dim3(a.nitems, (unsigned)cdiv(ktiles, nwk)), nwk, p, stream, a, a.ws)) return rc;
+  return launch<attn_bwd_dq_stream_kernel>("attn_bwd_dq_stream", dim3(a.nitems, (unsigned)cdiv(qtiles, nwq)), nwq, p, stream, a, (const float*)a.ws);
+}
+
+// persistent grid of the single-pass kernels: as many workgroups as the chip holds at once (LDS / registers: 1 per CU at
+// T = 197, more for the short text sequences); SEGCLIP_ATTN_BWD_GRID overrides the number per CU (0 = one workgroup per item)
+dim3 bwd_persistent_grid(int nitems, const Device& dv, int per_cu) {
+  const int env = tuning().bwd_grid;
+  return dim3((unsigned)(env == 0 ? nitems : std::min<int64_t>(nitems, (int64_t)dv.ncu * (env > 0 ? env : per_cu))));
+}
+// with a loader wave (attention_spl.inc): one workgroup per CU
+int launch_bwd_spl(const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
+  if (int rc = raise_lds_limit<attn_bwd_spl_bf16_kernel>("attn_bwd", dv, 160 * 1024)) return rc;
+  return launch<attn_bwd_spl_bf16_kernel>("attn_bwd_spl_bf16", bwd_persistent_grid(a.nitems, dv, 1), p.waves, p, stream, a);
+}
+// attention_sp.inc, instance <MASKED>: as many workgroups per CU as the occupancy query allows
+template <bool MASKED>
+int launch_bwd_sp(const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
+  if (int rc = raise_lds_limit<attn_bwd_sp_bf16_kernel<MASKED>>("attn_bwd", dv, bwd_sp_lds_bytes(TMAX))) return rc;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_bwd_sp_bf16_kernel<MASKED>, p.waves * 64, p.lds) != hipSuccess || per_cu < 1) per_cu = 1;
+  return launch<attn_bwd_sp_bf16_kernel<MASKED>>("attn_bwd_sp_bf16", bwd_persistent_grid(a.nitems, dv, per_cu), p.waves, p, stream, a);
+}
+
+// two-pass kernel (cross-attention): one workgroup per (batch, head)
+int launch_bwd_twopass(const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
+  if (int rc = raise_lds_limit<attn_bwd_bf16_kernel>("attn_bwd", dv, bwd_lds_bytes(TMAX))) return rc;
+  return launch<attn_bwd_bf16_kernel>("attn_bwd_bf16", dim3(a.nitems), p.waves, p, stream, a);
+}
+
+int launch_bwd_f32(const segclip_attn_desc* d, hipStream_t stream) {
+  SEGCLIP_REQUIRE(d->colsum_part == nullptr, "attn_bwd f32: colsum_part is a bf16-path feature");
+  SEGCLIP_REQUIRE(d->ws != nullptr, "attn_bwd f32: workspace required");
+  const float* P = (const float*)d->stats;
+  float* dP = (float*)d->ws;
+  const Mat dO = {d->dO, d->do_st, 1, d->do_sb, d->hd}, dO_T = {d->dO, 1, d->do_st, d->do_sb, d->hd};
+  int rc;
+  // dV(key,d) = sum_q P[q][key] dO[q][d]
+  if ((rc = gemm_f32(d, stream, d->Tk, d->hd, d->Tq, scores(d, P, true), dO_T, {d->dV, d->dv_st, 1, d->dv_sb, d->hd}))) return rc;
+  // dP[q][key] = sum_d dO[q][d] V[key][d]
+  if ((rc = gemm_f32(d, stream, d->Tq, d->Tk, d->hd, dO, {d->V, d->v_st, 1, d->v_sb, d->hd}, scores(d, dP, false)))) return rc;
+  const int64_t rows = d->B * d->H * d->Tq;
+  hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, P, dP, rows, (int)d->Tk, d->scale);
+  SEGCLIP_CHECK_LAUNCH("attn_softmax_bwd_rows");
+  // dQ[q][d] = sum_key dS[q][key] K[key][d]
+  if ((rc = gemm_f32(d, stream, d->Tq, d->hd, d->Tk, scores(d, dP, false), {d->K, 1, d->k_st, d->k_sb, d->hd}, {d->dQ, d->dq_st, 1, d->dq_sb, d->hd}))) return rc;
+  // dK[key][d] = sum_q dS[q][key] Q[q][d]
+  return gemm_f32(d, stream, d->Tk, d->hd, d->Tq, scores(d, dP, true), {d->Q, 1, d->q_st, d->q_sb, d->hd}, {d->dK, d->dk_st, 1, d->dk_sb, d->hd});
+}
+
+// what the bf16 forward and backward kernels read alike
+template <typename Args>
+void fill_common(Args& a, const segclip_attn_desc* d) {
+  a.Q = (const bf16_t*)d->Q; a.K = (const bf16_t*)d->K; a.V = (const bf16_t*)d->V;
+  a.H = (int)d->H; a.Tq = (int)d->Tq; a.Tk = (int)d->Tk; a.hd = (int)d->hd;
+  a.q_sb = d->q_sb; a.q_st = d->q_st; a.k_sb = d->k_sb; a.k_st = d->k_st; a.v_sb = d->v_sb; a.v_st = d->v_st;
+  a.o_sb = d->o_sb; a.o_st = d->o_st; a.scale = d->scale; a.causal = d->causal;
+  a.klen = (const int*)d->klen;
 }
 
 }  // namespace
@@ -731,14 +926,14 @@ extern "C" size_t segclip_attn_stats_bytes(const segclip_attn_desc* d) {
   return (size_t)d->B * d->H * d->Tq * d->Tk * sizeof(float);
 }
 extern "C" size_t segclip_attn_bwd_ws_bytes(const segclip_attn_desc* d) {
-  if (d->dtype == SEGCLIP_BF16) {
-    if (d->Tq <= TMAX && d->Tk <= TMAX) return 0;
-    const size_t stream_ws = (size_t)d->B * d->H * (d->Tq + d->Tk) * sizeof(float);  // streaming kernels: cs[key] and D[q]
-    // attention_dqw.inc, key-chunked: 8 KB of fp32 dQ accumulators per query tile and workgroup (one workgroup per CU)
-    const size_t dqw_ws = (size_t)dqw_multi_max_grid() * (size_t)(d->Tq / 32 + 1) * 8192;
-    return stream_ws > dqw_ws ? stream_ws : dqw_ws;
-  }
-  return (size_t)d->B * d->H * d->Tq * d->Tk * sizeof(float);
+  if (d->dtype != SEGCLIP_BF16) return (size_t)d->B * d->H * d->Tq * d->Tk * sizeof(float);
+  if (!long_seq(d)) return 0;
+  Device dv;   // enough for either long-sequence route
+  if (!current_device(dv)) dv.ncu = 256;
+  const size_t stream_ws = (size_t)d->B * d->H * (d->Tq + d->Tk) * sizeof(float);  // streaming kernels: cs[key] and D[q]
+  // attention_dqw.inc, key-chunked: 8 KB of fp32 dQ accumulators per query tile and workgroup (one workgroup per CU)
+  const size_t dqw_ws = (size_t)dv.ncu * (size_t)(d->Tq / 32 + 1) * 8192;
+  return stream_ws > dqw_ws ? stream_ws : dqw_ws;
 }
 
 extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
@@ -747,80 +942,26 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
   SEGCLIP_REQUIRE(d->hd <= 64 && d->hd > 0, "attn: head_dim %lld unsupported (<=64)", (long long)d->hd);
   SEGCLIP_REQUIRE(d->stats != nullptr, "attn_fwd: stats buffer required");
   if (d->B == 0 || d->Tq == 0) return 0;
+  FwdArgs a{};
   if (d->dtype == SEGCLIP_BF16) {
     SEGCLIP_REQUIRE(bf16_ok(d), "attn_fwd bf16: head_dim and all strides must be multiples of 8");
-    FwdArgs a;
-    a.Q = (const bf16_t*)d->Q; a.K = (const bf16_t*)d->K; a.V = (const bf16_t*)d->V; a.O = (bf16_t*)d->O;
-    a.lse = (float*)d->stats;
-    a.H = (int)d->H; a.Tq = (int)d->Tq; a.Tk = (int)d->Tk; a.hd = (int)d->hd;
-    a.q_sb = d->q_sb; a.q_st = d->q_st; a.k_sb = d->k_sb; a.k_st = d->k_st; a.v_sb = d->v_sb; a.v_st = d->v_st;
-    a.o_sb = d->o_sb; a.o_st = d->o_st; a.scale = d->scale; a.causal = d->causal;
-    a.klen = (const int*)d->klen;
-    // LDS-staged output rows: 117 -> 112 us at T = 196 (B = 256, H = 12), 27.8 -> 29.3 us at T = 77: on for the long sequences
-    static const int fwd_staged = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_STAGED"); return e ? atoi(e) : -1; }();
-    a.staged = fwd_staged >= 0 ? fwd_staged : (d->Tq > 128 ? 1 : 0);
-    static const int fwd_lean = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_LEAN"); return e ? atoi(e) : 1; }();
-    a.lean = fwd_lean;
     SEGCLIP_REQUIRE(!(d->klen && (d->flags & SEGCLIP_ATTN_FP8)), "attn_fwd: klen is not supported with SEGCLIP_ATTN_FP8");
-    if (smallq::covers(d)) {   // at most 8 queries (the learnable-center cross-attention): one wave per (batch, head), VALU
-      const int nitems = (int)(d->B * d->H);
-      hipLaunchKernelGGL(smallq::attn_smallq_fwd_kernel, dim3((unsigned)cdiv(nitems, smallq::WPB_FWD)), dim3(smallq::WPB_FWD * 64),
-                         smallq::lds_bytes((int)d->Tk, false), stream, a, nitems);
-      SEGCLIP_CHECK_LAUNCH("attn_smallq_fwd");
-      segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0);
-      return 0;
-    }
-    const int tiles = (int)cdiv(d->Tq, 32);
-    // self-attention of 65..96 / 161..200 tokens: the persistent kernel with a loader wave (attention_pf.inc);
-    // SEGCLIP_ATTN_FWD_PF=0 falls back to one workgroup per (batch, head)
-    static const int use_pf = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_FWD_PF"); return e ? atoi(e) : 1; }();
-    if (use_pf && d->Tq == d->Tk && !(d->flags & SEGCLIP_ATTN_FP8) && (tiles == 3 || tiles == 6 || tiles == 7) &&
-        fwd_pf_lds_bytes(tiles, (int)d->Tq) <= 160 * 1024) {
-      const int nitems = (int)(d->B * d->H);
-      if (d->causal) {
-        if (tiles == 3) return launch_fwd_pf<3, true>(a, nitems, stream);
-        if (tiles == 6) return launch_fwd_pf<6, true>(a, nitems, stream);
-        return launch_fwd_pf<7, true>(a, nitems, stream);
-      }
-      if (tiles == 3) return launch_fwd_pf<3, false>(a, nitems, stream);
-      if (tiles == 6) return launch_fwd_pf<6, false>(a, nitems, stream);
-      return launch_fwd_pf<7, false>(a, nitems, stream);
-    }
-    const int nw = tiles < 8 ? tiles : (tiles <= 8 ? 8 : (int)cdiv(tiles, cdiv(tiles, 8)));
-    SEGCLIP_REQUIRE(d->B * d->H <= 65535, "attn_fwd: B*H too large");
-    if (d->flags & SEGCLIP_ATTN_FP8) {
-      segclip_set_error("attn_fwd: the e4m3 forward was removed (slower than bf16 at head_dim 64, DESIGN.md section 8): "
-                        "configs[4] runs bf16 attention");
-      return SEGCLIP_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3((unsigned)cdiv(tiles, nw), (unsigned)(d->B * d->H)), dim3(nw * 64), 0,
-                       stream, a);
-    SEGCLIP_CHECK_LAUNCH("attn_fwd_bf16");
-    segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_GENERIC, tiles, (a.staged ? 1 : 0) | nw << 8);
-    return 0;
+    fill_common(a, d);
+    a.O = (bf16_t*)d->O; a.lse = (float*)d->stats;
+    a.lean = tuning().fwd_lean;   // SEGCLIP_ATTN_FWD_LEAN=0: no lean softmax step on unmasked key tiles
   }
-  // f32: S -> stats, softmax in place, O = P V
-  float* P = (float*)d->stats;
-  segclip_gemm_desc g;
-  base_gemm(g, d);
-  g.A = d->Q; g.B = d->K; g.C = P; g.M = d->Tq; g.N = d->Tk; g.K = d->hd;
-  g.sam = d->q_st; g.sak = 1; g.sbn = d->k_st; g.sbk = 1; g.ldc = d->Tk;
-  g.bsA1 = d->q_sb; g.bsA2 = d->hd; g.bsB1 = d->k_sb; g.bsB2 = d->hd;
-  g.bsC1 = d->H * d->Tq * d->Tk; g.bsC2 = d->Tq * d->Tk; g.alpha = d->scale;
-  int rc = segclip_gemm_f32_launch(&g, stream);
-  if (rc) return rc;
-  const int64_t rows = d->B * d->H * d->Tq;
-  hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, P, rows, (int)d->Tq,
-                     (int)d->Tk, d->causal, (const int*)d->klen, (int)d->H);
-  SEGCLIP_CHECK_LAUNCH("attn_softmax_rows");
-  base_gemm(g, d);
-  g.A = P; g.B = d->V; g.C = d->O; g.M = d->Tq; g.N = d->hd; g.K = d->Tk;
-  g.sam = d->Tk; g.sak = 1; g.sbn = 1; g.sbk = d->v_st; g.ldc = d->o_st;
-  g.bsA1 = d->H * d->Tq * d->Tk; g.bsA2 = d->Tq * d->Tk; g.bsB1 = d->v_sb; g.bsB2 = d->hd;
-  g.bsC1 = d->o_sb; g.bsC2 = d->hd;
-  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
-  segclip_attn_route_note(false, SEGCLIP_ATTN_ROUTE_F32, (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32), 0);
-  return 0;
+  const Plan p = plan_fwd(d);
+  a.staged = p.staged;
+  const int nitems = (int)(d->B * d->H);
+  int rc;
+  switch (p.route) {
+    case SEGCLIP_ATTN_ROUTE_SMALLQ: rc = launch<smallq::attn_smallq_fwd_kernel>("attn_smallq_fwd", dim3((unsigned)cdiv(nitems, p.waves)), p.waves, p, stream, a, nitems); break;
+    case SEGCLIP_ATTN_ROUTE_PF: rc = launch_fwd_pf(a, p, nitems, stream); break;
+    case SEGCLIP_ATTN_ROUTE_GENERIC: rc = launch_fwd_generic(d, a, p, stream); break;
+    default: rc = launch_fwd_f32(d, stream); break;
+  }
+  if (rc == 0) segclip_attn_route_note(false, p.route, p.tiles, p.variant);
+  return rc;
 }
 
 extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
@@ -828,189 +969,38 @@ extern "C" int segclip_attn_bwd(const segclip_attn_desc* d, void* stream_) {
   segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_NONE, 0, 0);
   SEGCLIP_REQUIRE(d->hd <= 64 && d->hd > 0, "attn: head_dim %lld unsupported (<=64)", (long long)d->hd);
   if (d->B == 0 || d->Tq == 0) return 0;
+  BwdArgs a{};
   if (d->dtype == SEGCLIP_BF16) {
     SEGCLIP_REQUIRE(bf16_ok(d), "attn_bwd bf16: head_dim and all strides must be multiples of 8");
     const int64_t s[] = {d->dq_sb, d->dq_st, d->dk_sb, d->dk_st, d->dv_sb, d->dv_st, d->do_sb, d->do_st};
     for (int64_t v : s) SEGCLIP_REQUIRE(v % 8 == 0, "attn_bwd bf16: gradient strides must be multiples of 8");
-    BwdArgs a;
-    a.Q = (const bf16_t*)d->Q; a.K = (const bf16_t*)d->K; a.V = (const bf16_t*)d->V; a.O = (const bf16_t*)d->O;
-    a.dO = (const bf16_t*)d->dO; a.lse = (const float*)d->stats;
+    fill_common(a, d);
+    a.O = (const bf16_t*)d->O; a.dO = (const bf16_t*)d->dO; a.lse = (const float*)d->stats;
     a.dQ = (bf16_t*)d->dQ; a.dK = (bf16_t*)d->dK; a.dV = (bf16_t*)d->dV;
-    a.H = (int)d->H; a.Tq = (int)d->Tq; a.Tk = (int)d->Tk; a.hd = (int)d->hd;
-    a.q_sb = d->q_sb; a.q_st = d->q_st; a.k_sb = d->k_sb; a.k_st = d->k_st; a.v_sb = d->v_sb; a.v_st = d->v_st;
-    a.o_sb = d->o_sb; a.o_st = d->o_st; a.do_sb = d->do_sb; a.do_st = d->do_st;
+    a.do_sb = d->do_sb; a.do_st = d->do_st;
     a.dq_sb = d->dq_sb; a.dq_st = d->dq_st; a.dk_sb = d->dk_sb; a.dk_st = d->dk_st; a.dv_sb = d->dv_sb; a.dv_st = d->dv_st;
-    a.scale = d->scale; a.causal = d->causal;
     a.colsum_part = (float*)d->colsum_part;
-    a.klen = (const int*)d->klen;
     a.nitems = (int)(d->B * d->H);
     a.ws = (float*)d->ws;
-    if (smallq::covers(d)) {
-      hipLaunchKernelGGL(smallq::attn_smallq_bwd_kernel, dim3((unsigned)cdiv(a.nitems, smallq::WPB_BWD)), dim3(smallq::WPB_BWD * 64),
-                         smallq::lds_bytes((int)d->Tk, true), stream, a, a.nitems);
-      SEGCLIP_CHECK_LAUNCH("attn_smallq_bwd");
-      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0);
-      return 0;
-    }
-    if (d->Tq > TMAX || d->Tk > TMAX) {
-      SEGCLIP_REQUIRE(d->klen == nullptr, "attn_bwd bf16: klen needs sequences of at most %d tokens", TMAX);
-      // long sequences: two streaming launches (dK,dV | dQ), 8 owned tiles per workgroup
-      SEGCLIP_REQUIRE(d->ws != nullptr, "attn_bwd bf16: workspace required for sequences longer than %d", TMAX);
-      // unmasked self-attention, head_dim 64: the dQ-wave kernel over chunks of 224 keys (attention_dqw.inc, MULTI).
-      // SEGCLIP_ATTN_BWD_DQW_LONG=0 (tuning) keeps the two streaming launches
-      static const int use_dqw_long = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_DQW_LONG"); return e ? atoi(e) : 1; }();
-      // (its token sums ride on a padded key in the last chunk and on two padded rows of the last query tile)
-      if (use_dqw_long && d->Tq == d->Tk && !d->causal && d->hd == 64 && d->Tq % 32 <= 30 && d->Tq % 224 != 0) {
-        int dev = 0;
-        SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "attn_bwd: cannot query the current device");
-        return launch_bwd_dqw<7, true>(a, dqw_multi_max_grid(), dev, stream);
-      }
-      const size_t lds = bwd_stream_lds_bytes();
-      static bool attr_set = false;
-      if (!attr_set) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_stream_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_stream_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        SEGCLIP_REQUIRE(e1 == hipSuccess && e2 == hipSuccess, "attn_bwd bf16: cannot raise the dynamic LDS limit");
-        attr_set = true;
-      }
-      const int ktiles = (int)cdiv(d->Tk, 32), qtiles = (int)cdiv(d->Tq, 32);
-      const int nwk = ktiles < 8 ? ktiles : 8, nwq = qtiles < 8 ? qtiles : 8;
-      hipLaunchKernelGGL(attn_bwd_dkv_stream_kernel, dim3((unsigned)(d->B * d->H), (unsigned)cdiv(ktiles, nwk)),
-                         dim3(nwk * 64), lds, stream, a, (float*)d->ws);
-      SEGCLIP_CHECK_LAUNCH("attn_bwd_dkv_stream");
-      hipLaunchKernelGGL(attn_bwd_dq_stream_kernel, dim3((unsigned)(d->B * d->H), (unsigned)cdiv(qtiles, nwq)),
-                         dim3(nwq * 64), lds, stream, a, (const float*)d->ws);
-      SEGCLIP_CHECK_LAUNCH("attn_bwd_dq_stream");
-      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_STREAM, qtiles > ktiles ? qtiles : ktiles, 0);
-      return 0;
-    }
-    const int tiles = (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32);
-    // self-attention: the single-pass kernel (attention_sp.inc), one wave per key tile.  SEGCLIP_ATTN_BWD_SP=0 falls back
-    // to the two-pass kernel (benchmarking); cross-attention (Tq != Tk) always takes the two-pass kernel.
-    static const int use_sp = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_SP"); return e ? atoi(e) : 1; }();
-    if (use_sp && d->Tq == d->Tk) {
-      const size_t lds_sp = bwd_sp_lds_bytes(tiles * 32);
-      // per DEVICE (function attributes and the CU count belong to the device the launch goes to, not to the process)
-      int dev = 0;
-      SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "attn_bwd: cannot query the current device");
-      static bool sp_attr_set[64] = {};
-      static int ncu_dev[64] = {};
-      if (!sp_attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_sp_bf16_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_sp_lds_bytes(TMAX));
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_sp_bf16_kernel<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_sp_lds_bytes(TMAX));
-        SEGCLIP_REQUIRE(e == hipSuccess && e2 == hipSuccess, "attn_bwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-        sp_attr_set[dev] = true;
-      }
-      // persistent grid: as many workgroups as the chip holds at once (LDS / registers: 1 per CU at T = 197, more for the
-      // short text sequences); SEGCLIP_ATTN_BWD_GRID overrides the number per CU (0 = one workgroup per item)
-      const bool masked = d->causal || d->klen;
-      if (ncu_dev[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        ncu_dev[dev] = n;
-      }
-      const int ncu = ncu_dev[dev];
-      static const int grid_env = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_GRID"); return e ? atoi(e) : -1; }();
-      int per_cu = 0;
-      hipError_t eo = masked ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_bwd_sp_bf16_kernel<true>, tiles * 64, lds_sp)
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_bwd_sp_bf16_kernel<false>, tiles * 64, lds_sp);
-      if (eo != hipSuccess || per_cu < 1) per_cu = 1;
-      if (grid_env > 0) per_cu = grid_env;
-      int64_t grid = grid_env == 0 ? a.nitems : (int64_t)ncu * per_cu;
-      if (grid > a.nitems) grid = a.nitems;
-      // vision tower (no mask, head_dim 64, 7 tiles, padded rows in the last tile): the query tiles as a stream with a dQ wave
-      // (attention_dqw.inc, round 6); SEGCLIP_ATTN_BWD_DQW=0 keeps the kernels below
-      static const int use_dqw = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_DQW"); return e ? atoi(e) : 1; }();
-      if (use_dqw && !masked && d->hd == 64 && tiles == 7 && d->Tq % 32 >= 1 && d->Tq % 32 <= 30)
-        return launch_bwd_dqw<7, false>(a, ncu, dev, stream);
-      // vision tower (no mask, 5-7 tiles): the variant whose memory traffic is issued by a loader wave (attention_spl.inc);
-      // SEGCLIP_ATTN_BWD_SPL=0 keeps attention_sp.inc
-      static const int use_spl = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_SPL"); return e ? atoi(e) : 1; }();
-      // head_dim 64 only: its loader wave copies whole 128-byte rows of Q, so with a smaller head the columns beyond it (the next
-      // head, or whatever follows the last one) would enter S = K Q^T against zeroed K columns: 0 x NaN, and a read past the
-      // end of a separately allocated Q.  Smaller heads take attention_sp.inc, which selects by column.
-      if (use_spl && !masked && d->hd == 64 && tiles >= 5 && tiles <= 7 && bwd_spl_lds_bytes((int)d->Tq) <= 160 * 1024) {
-        static bool spl_attr_set[64] = {};
-        if (!spl_attr_set[dev]) {
-          hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_spl_bf16_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          SEGCLIP_REQUIRE(e3 == hipSuccess, "attn_bwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e3));
-          spl_attr_set[dev] = true;
-        }
-        int64_t g2 = grid_env == 0 ? a.nitems : (int64_t)ncu * (grid_env > 0 ? grid_env : 1);
-        if (g2 > a.nitems) g2 = a.nitems;
-        hipLaunchKernelGGL(attn_bwd_spl_bf16_kernel, dim3((unsigned)g2), dim3((tiles + 1) * 64), bwd_spl_lds_bytes((int)d->Tq), stream, a);
-        SEGCLIP_CHECK_LAUNCH("attn_bwd_spl_bf16");
-        segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SPL, tiles, 0);
-        return 0;
-      }
-      if (masked)
-        hipLaunchKernelGGL(attn_bwd_sp_bf16_kernel<true>, dim3((unsigned)grid), dim3(tiles * 64), lds_sp, stream, a);
-      else
-        hipLaunchKernelGGL(attn_bwd_sp_bf16_kernel<false>, dim3((unsigned)grid), dim3(tiles * 64), lds_sp, stream, a);
-      SEGCLIP_CHECK_LAUNCH("attn_bwd_sp_bf16");
-      segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_SP, tiles, masked ? 1 : 0);
-      return 0;
-    }
-    // 4 waves per workgroup (each wave walks over 1-2 tiles): two such workgroups fit the registers (2 waves per SIMD
-    // at ~215 VGPRs) and the LDS of a CU, so their load / MFMA / store phases interleave.  SEGCLIP_ATTN_BWD_WAVES
-    // overrides (benchmarking).
-    static const int force_waves = [] { const char* e = segclip_tuning_env("SEGCLIP_ATTN_BWD_WAVES"); return e ? atoi(e) : 0; }();
-    int nw = tiles < 4 ? tiles : 4;
-    if (force_waves >= 1 && force_waves <= 8) nw = tiles < force_waves ? tiles : force_waves;
-    const int tp = (int)(cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32) * 32);
-    const size_t lds = bwd_lds_bytes(tp);
-    static bool lds_attr_set = false;
-    if (!lds_attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_bf16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bwd_lds_bytes(TMAX));
-      SEGCLIP_REQUIRE(e == hipSuccess, "attn_bwd bf16: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-      lds_attr_set = true;
-    }
-    hipLaunchKernelGGL(attn_bwd_bf16_kernel, dim3((unsigned)(d->B * d->H)), dim3(nw * 64), lds, stream, a);
-    SEGCLIP_CHECK_LAUNCH("attn_bwd_bf16");
-    segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_TWOPASS, tiles, nw << 8);
-    return 0;
   }
-  SEGCLIP_REQUIRE(d->colsum_part == nullptr, "attn_bwd f32: colsum_part is a bf16-path feature");
-  SEGCLIP_REQUIRE(d->ws != nullptr, "attn_bwd f32: workspace required");
-  const float* P = (const float*)d->stats;
-  float* dP = (float*)d->ws;
-  const int64_t pz1 = d->H * d->Tq * d->Tk, pz2 = d->Tq * d->Tk;
-  segclip_gemm_desc g;
+  const Plan p = plan_bwd(d);
+  if (p.route == SEGCLIP_ATTN_ROUTE_STREAM || (p.route == SEGCLIP_ATTN_ROUTE_DQW && p.variant)) {   // the long-sequence routes
+    SEGCLIP_REQUIRE(d->klen == nullptr, "attn_bwd bf16: klen needs sequences of at most %d tokens", TMAX);
+    SEGCLIP_REQUIRE(d->ws != nullptr, "attn_bwd bf16: workspace required for sequences longer than %d", TMAX);
+  }
+  Device dv{};   // the bf16 routes but smallq keep per-device state
+  if (p.route != SEGCLIP_ATTN_ROUTE_SMALLQ && p.route != SEGCLIP_ATTN_ROUTE_F32)
+    SEGCLIP_REQUIRE(current_device(dv), "attn_bwd: cannot query the current device");
   int rc;
-  // dV(key,d) = sum_q P[q][key] dO[q][d]
-  base_gemm(g, d);
-  g.A = P; g.B = d->dO; g.C = d->dV; g.M = d->Tk; g.N = d->hd; g.K = d->Tq;
-  g.sam = 1; g.sak = d->Tk; g.sbn = 1; g.sbk = d->do_st; g.ldc = d->dv_st;
-  g.bsA1 = pz1; g.bsA2 = pz2; g.bsB1 = d->do_sb; g.bsB2 = d->hd; g.bsC1 = d->dv_sb; g.bsC2 = d->hd;
-  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
-  // dP[q][key] = sum_d dO[q][d] V[key][d]
-  base_gemm(g, d);
-  g.A = d->dO; g.B = d->V; g.C = dP; g.M = d->Tq; g.N = d->Tk; g.K = d->hd;
-  g.sam = d->do_st; g.sak = 1; g.sbn = d->v_st; g.sbk = 1; g.ldc = d->Tk;
-  g.bsA1 = d->do_sb; g.bsA2 = d->hd; g.bsB1 = d->v_sb; g.bsB2 = d->hd; g.bsC1 = pz1; g.bsC2 = pz2;
-  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
-  const int64_t rows = d->B * d->H * d->Tq;
-  hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, stream, P, dP, rows,
-                     (int)d->Tk, d->scale);
-  SEGCLIP_CHECK_LAUNCH("attn_softmax_bwd_rows");
-  // dQ[q][d] = sum_key dS[q][key] K[key][d]
-  base_gemm(g, d);
-  g.A = dP; g.B = d->K; g.C = d->dQ; g.M = d->Tq; g.N = d->hd; g.K = d->Tk;
-  g.sam = d->Tk; g.sak = 1; g.sbn = 1; g.sbk = d->k_st; g.ldc = d->dq_st;
-  g.bsA1 = pz1; g.bsA2 = pz2; g.bsB1 = d->k_sb; g.bsB2 = d->hd; g.bsC1 = d->dq_sb; g.bsC2 = d->hd;
-  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
-  // dK[key][d] = sum_q dS[q][key] Q[q][d]
-  base_gemm(g, d);
-  g.A = dP; g.B = d->Q; g.C = d->dK; g.M = d->Tk; g.N = d->hd; g.K = d->Tq;
-  g.sam = 1; g.sak = d->Tk; g.sbn = 1; g.sbk = d->q_st; g.ldc = d->dk_st;
-  g.bsA1 = pz1; g.bsA2 = pz2; g.bsB1 = d->q_sb; g.bsB2 = d->hd; g.bsC1 = d->dk_sb; g.bsC2 = d->hd;
-  if ((rc = segclip_gemm_f32_launch(&g, stream))) return rc;
-  segclip_attn_route_note(true, SEGCLIP_ATTN_ROUTE_F32, (int)cdiv(d->Tq > d->Tk ? d->Tq : d->Tk, 32), 0);
-  return 0;
+  switch (p.route) {
+    case SEGCLIP_ATTN_ROUTE_SMALLQ: rc = launch<smallq::attn_smallq_bwd_kernel>("attn_smallq_bwd", dim3((unsigned)cdiv(a.nitems, p.waves)), p.waves, p, stream, a, a.nitems); break;
+    case SEGCLIP_ATTN_ROUTE_DQW: rc = p.variant ? launch_bwd_dqw<true>(a, p, dv, stream) : launch_bwd_dqw<false>(a, p, dv, stream); break;
+    case SEGCLIP_ATTN_ROUTE_STREAM: rc = launch_bwd_stream(d, a, p, dv, stream); break;
+    case SEGCLIP_ATTN_ROUTE_SPL: rc = launch_bwd_spl(a, p, dv, stream); break;
+    case SEGCLIP_ATTN_ROUTE_SP: rc = p.variant ? launch_bwd_sp<true>(a, p, dv, stream) : launch_bwd_sp<false>(a, p, dv, stream); break;
+    case SEGCLIP_ATTN_ROUTE_TWOPASS: rc = launch_bwd_twopass(a, p, dv, stream); break;
+    default: rc = launch_bwd_f32(d, stream); break;
+  }
+  if (rc == 0) segclip_attn_route_note(true, p.route, p.tiles, p.variant);
+  return rc;
 }

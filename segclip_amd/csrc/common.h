@@ -125,3 +125,9 @@ static inline const char* segclip_tuning_env(const char* name) {
   }
   return e;
 }
+// the integer value of a tuning switch, or dflt where it is unset (or not honoured).  Reads the environment at every call:
+// a launch site keeps the value in a `static const int`, so that it is read once per process.
+static inline int segclip_tuning_int(const char* name, int dflt) {
+  const char* e = segclip_tuning_env(name);
+  return e ? atoi(e) : dflt;
+}

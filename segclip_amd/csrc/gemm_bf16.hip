@@ -451,9 +451,9 @@ int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream) {
   g.slab = (float*)d->ws;
   g.vec_epi = 0;
   g.stagger = 0;
-  static const int xw_epi = [] { const char* e = segclip_tuning_env("SEGCLIP_EPI_XW"); return e ? atoi(e) : 2; }();
+  static const int xw_epi = segclip_tuning_int("SEGCLIP_EPI_XW", 2);
   g.xw_epi = xw_epi;
-  static const int slab_staged = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_SLAB_STAGED"); return e ? atoi(e) : 1; }();
+  static const int slab_staged = segclip_tuning_int("SEGCLIP_P8_SLAB_STAGED", 1);
   g.slab_staged = slab_staged;
   g.colsum_part = nullptr;
   dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)g.splits, (unsigned)nb);

@@ -303,7 +303,7 @@ bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, in
   // Round 4: problems whose 256-row tiles cannot fill the 256 CUs (the center stage's q-side linears: M = 8 B = 2048 rows,
   // 48-192 tiles) take the 128x128 tile: four times the workgroups, two per CU, half the K-loop time per tile
   // (SEGCLIP_GEMM_SMALL_TILES=0 switches the rule off; a forward + backward pass of the center stage: see DESIGN 4.4).
-  static const int small_rule = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_SMALL_TILES"); return e ? atoi(e) : 1; }();
+  static const int small_rule = segclip_tuning_int("SEGCLIP_GEMM_SMALL_TILES", 1);
   const int bn_big = pick_bn(d, nb * splits);
   // fused column sums come from the staged epilogue of FULL tiles only (a partial tile takes the per-element epilogue, which
   // writes no partial sums): M = 256 q + 128 runs them on the 128-row tiles, where every tile is full (M % 128 == 0 and

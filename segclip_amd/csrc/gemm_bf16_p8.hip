@@ -430,7 +430,7 @@ void segclip_p8_launch_kk(dim3, hipStream_t, const void*);
 // returns false when the shape does not meet this kernel's preconditions.
 bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int splits, int64_t kper, int64_t nb,
                               hipStream_t stream) {
-  static const int disabled = [] { const char* e = segclip_tuning_env("SEGCLIP_GEMM_P8"); return e ? atoi(e) == 0 : 0; }();
+  static const bool disabled = segclip_tuning_int("SEGCLIP_GEMM_P8", 1) == 0;
   if (disabled) return false;
   Args g = *reinterpret_cast<const Args*>(args_);
   const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
@@ -442,7 +442,7 @@ bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int
   // 32-bit DMA offsets: 256 rows (or 64 k-rows) of the leading dimension must stay below 4 GiB
   if ((a_ks ? 64 : 256) * (a_ks ? d->sak : d->sam) * 2 >= (int64_t)1 << 31) return false;
   if ((b_ks ? 64 : 256) * (b_ks ? d->sbk : d->sbn) * 2 >= (int64_t)1 << 31) return false;
-  static const int stagger = [] { const char* e = segclip_tuning_env("SEGCLIP_P8_STAGGER"); return e ? atoi(e) : 2000; }();   // unit cap in cycles; 0 = off.  In the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
+  static const int stagger = segclip_tuning_int("SEGCLIP_P8_STAGGER", 2000);   // unit cap in cycles; 0 = off.  In the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
   g.stagger = stagger;
   g.nbx = (int)cdiv(d->N, BT);
   g.nby = (int)cdiv(d->M, BT);

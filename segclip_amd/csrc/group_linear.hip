@@ -14,6 +14,7 @@
 // bf16 packing in-lane, and the 32 x 64 output block through a wave-private 4-KiB LDS patch so that it leaves as whole
 // 128-byte lines.  The next group's row fragments are in flight while the current group is multiplied.
 #include <stdlib.h>
+#include <algorithm>
 
 #include "common.h"
 
@@ -139,7 +140,7 @@ extern "C" int segclip_group_linear64(const void* const* in, const int64_t* ld_i
       a.W[i][o] = (const bf16_t*)p;
     }
   a.M = M; a.groups = groups;
-  static const int gsplit_env = [] { const char* e = segclip_tuning_env("SEGCLIP_GL64_GSPLIT"); const int v = e ? atoi(e) : 6; return v < 1 ? 1 : v; }();
+  static const int gsplit_env = std::max(1, segclip_tuning_int("SEGCLIP_GL64_GSPLIT", 6));
   const int gsplit = gsplit_env < groups ? gsplit_env : groups;
   const dim3 grid((unsigned)cdiv(M, GL_WAVES * GL_ROWS), (unsigned)gsplit), block(GL_WAVES * 64);
   if (n_in == 1 && n_out == 1) hipLaunchKernelGGL((group_linear_kernel<1, 1>), grid, block, 0, (hipStream_t)stream, a);

@@ -548,6 +548,16 @@ def _attn_desc(q, k, v, o, B, H, Tq, Tk, hd, qs, ks, vs, os_, scale, causal, q_o
     return d
 
 
+def attn_desc_packed(qkv, o, B, H, T, causal, klen=None, fp8=False):
+    """Self-attention over a packed projection: qkv holds rows of 3 * D columns (Q | K | V of one token, tokens of a sample
+    in consecutive rows), o rows of D columns; the head dimension is D / H."""
+    D = qkv.shape[-1] // 3
+    hd = D // H
+    s3 = (T * 3 * D, 3 * D)
+    return _attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1.0 / math.sqrt(hd), causal, 0, D, 2 * D,
+                      fp8=fp8, klen=klen)
+
+
 AttnRoute = collections.namedtuple("AttnRoute", "fwd_kernel bwd_kernel tiles variant")
 
 
@@ -1011,9 +1021,7 @@ def _resblock_fwd(x2, P, B, T, n_head, causal, act, eps, act_dtype, klen):
     if M > B * T:                 # row-padded stack (ResStackFn): the attention kernel writes the B * T token rows only
         o[B * T:].zero_()
     from . import config as _cfg
-    ad = _attn_desc(qkv, qkv, qkv, o, B, n_head, T, T, hd, (T * 3 * D, 3 * D), (T * 3 * D, 3 * D),
-                    (T * 3 * D, 3 * D), (T * D, D), 1.0 / math.sqrt(hd), causal, 0, D, 2 * D,
-                    fp8=bool(_cfg.attn_fp8) and act_dtype == torch.bfloat16, klen=klen)
+    ad = attn_desc_packed(qkv, o, B, n_head, T, causal, klen=klen, fp8=bool(_cfg.attn_fp8) and act_dtype == torch.bfloat16)
     stats = p_attn_fwd(ad, x2)
     x1, _ = p_linear(o, wo_c, bo, residual=x2, out_dtype=x2.dtype)
     y2, mean2, rstd2 = p_ln_fwd(x1, ln2w, ln2b, eps, act_dtype)
@@ -1101,8 +1109,7 @@ def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, wgroup=
     if M > B * T:
         dqkv[B * T:].zero_()      # the attention backward writes the token rows; a pad row must contribute exact zeros downstream
     s3 = (T * 3 * D, 3 * D)
-    ad = _attn_desc(qkv, qkv, qkv, o, B, n_head, T, T, hd, s3, s3, s3, (T * D, D), 1.0 / math.sqrt(hd), causal,
-                    0, D, 2 * D, klen=klen)
+    ad = attn_desc_packed(qkv, o, B, n_head, T, causal, klen=klen)
     part = _empty((B, 3 * D), torch.float32, x2) if (bf and need[4]) else None  # in_proj bias gradient per sample
     p_attn_bwd(ad, stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D, colsum_part=part)
     dy1 = p_dgrad(dqkv, wqkv_c, act_dtype)

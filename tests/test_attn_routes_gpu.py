@@ -551,6 +551,19 @@ def test_attn_route_and_value(case):
     run_case(case, kernel_fwd, kernel_bwd, DEV)
 
 
+def test_second_device_raises_its_own_lds_limit():
+    """the streaming pair and the two-pass backward need more dynamic LDS than the default limit, and that limit is raised
+    per (kernel, device): in one process, first on device 0, then on device 1, with the checks of the table's rows"""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    rows = [c for c in CASES if c.name in ("s319", "x33_256_causal")]
+    assert [c.bwd[0] for c in rows] == ["stream", "twopass"]
+    for i in (0, 1):
+        with torch.cuda.device(i):
+            for case in rows:
+                run_case(case, kernel_fwd, kernel_bwd, f"cuda:{i}")
+
+
 def test_call_that_launches_nothing_records_no_route():
     case = S("probe", 64, gen(2, 2, 0), sp(2))
     s = make_slots(case, DEV)

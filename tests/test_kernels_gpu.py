@@ -400,7 +400,7 @@ def test_self_attention_block_packed_qkv(dtype, B, T, H, hd, causal):
     qkv = rnd(B * T, 3 * D, dtype=dtype, seed=41)
     o = torch.empty(B * T, D, dtype=dtype, device=DEV)
     s3 = (T * 3 * D, 3 * D)
-    d = ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D)
+    d = ops.attn_desc_packed(qkv, o, B, H, T, causal)
     stats = ops.p_attn_fwd(d, qkv)
     qr = qkv.float().view(B, T, 3, D).requires_grad_()
     ref = _attn_ref(qr[:, :, 0], qr[:, :, 1], qr[:, :, 2], H, causal)
@@ -408,7 +408,7 @@ def test_self_attention_block_packed_qkv(dtype, B, T, H, hd, causal):
     close(o.view(B, T, D), ref, rt, at, "attn fwd")
     do = rnd(B * T, D, dtype=dtype, seed=42)
     dqkv = torch.zeros(B * T, 3 * D, dtype=dtype, device=DEV)
-    d = ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D)
+    d = ops.attn_desc_packed(qkv, o, B, H, T, causal)
     part = torch.full((B, 3 * D), float("nan"), device=DEV) if dtype == BF else None
     ops.p_attn_bwd(d, stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D, colsum_part=part)
     ref.backward(do.float().view(B, T, D))
@@ -432,7 +432,7 @@ def test_attention_dqw_backward_is_deterministic_under_memory_contention(B, T, H
     do = rnd(B * T, D, dtype=BF, seed=92)
     o = torch.empty(B * T, D, dtype=BF, device=DEV)
     s3 = (T * 3 * D, 3 * D)
-    desc = lambda: ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), False, 0, D, 2 * D)
+    desc = lambda: ops.attn_desc_packed(qkv, o, B, H, T, False)
     stats = ops.p_attn_fwd(desc(), qkv)
     side = torch.cuda.Stream()
     junk = torch.empty(128 << 20, dtype=torch.uint8, device=DEV)
@@ -464,9 +464,7 @@ def test_self_attention_fp8_forward(B, T, H, hd, causal):
     from segclip_amd import _lib
     D = H * hd
     qkv = rnd(B * T, 3 * D, dtype=BF, seed=71)
-    s3 = (T * 3 * D, 3 * D)
-    desc = lambda o, fp8: ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal,
-                                         0, D, 2 * D, fp8=fp8)
+    desc = lambda o, fp8: ops.attn_desc_packed(qkv, o, B, H, T, causal, fp8=fp8)
     lib = _lib.load()
     o8 = torch.full((B * T, D), -3.0, dtype=BF, device=DEV)
     d = desc(o8, True)

@@ -1,4 +1,4 @@
-import sys, os, math
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from segclip_amd import ops
@@ -30,7 +30,7 @@ for (B, T, H, causal) in SHAPES:
     dqkv = torch.empty_like(qkv)
     s3 = (T * 3 * D, 3 * D)
     def desc():
-        return ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D)
+        return ops.attn_desc_packed(qkv, o, B, H, T, causal)
     stats = ops.p_attn_fwd(desc(), qkv)
     tf = timeit(lambda: ops.p_attn_fwd(desc(), qkv))
     tb = timeit(lambda: ops.p_attn_bwd(desc(), stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D))

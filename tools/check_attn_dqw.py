@@ -25,7 +25,7 @@ def run(path):
         do = torch.randn(B * T, D, device="cuda", generator=g).to(torch.bfloat16)
         o = torch.empty(B * T, D, dtype=torch.bfloat16, device="cuda")
         s3 = (T * 3 * D, 3 * D)
-        desc = lambda: ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), False, 0, D, 2 * D)
+        desc = lambda: ops.attn_desc_packed(qkv, o, B, H, T, False)
         stats = ops.p_attn_fwd(desc(), qkv)
         dqkv = torch.full_like(qkv, float("nan"))
         cs = torch.full((B, 3 * D), float("nan"), dtype=torch.float32, device="cuda")

@@ -1,6 +1,6 @@
 """Bit-equality of the persistent forward (attention_pf.inc) with the one-workgroup-per-item forward on the same inputs:
 runs itself twice (SEGCLIP_ATTN_FWD_PF=0 / 1: the switch is read once per process) and compares the saved outputs."""
-import math, os, subprocess, sys, tempfile
+import os, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CASES = [(256, 196, 12, 64, False, False), (64, 77, 8, 64, True, False), (5, 197, 8, 48, False, False),
          (7, 170, 3, 64, True, False), (9, 77, 8, 64, False, True), (3, 224, 2, 64, False, False), (300, 196, 12, 64, False, False)]
@@ -15,9 +15,8 @@ def run(path):
         g = torch.Generator(device="cuda").manual_seed(100 + i)
         qkv = torch.randn(B * T, 3 * D, device="cuda", generator=g).to(torch.bfloat16)
         o = torch.full((B * T, D), float("nan"), dtype=torch.bfloat16, device="cuda")
-        s3 = (T * 3 * D, 3 * D)
         klen = (torch.arange(B, device="cuda", dtype=torch.int32) * 7 % T + 1).contiguous() if use_klen else None
-        d = ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), causal, 0, D, 2 * D, klen=klen)
+        d = ops.attn_desc_packed(qkv, o, B, H, T, causal, klen=klen)
         stats = ops.p_attn_fwd(d, qkv)
         torch.cuda.synchronize()
         out[f"o{i}"] = o.float().cpu(); out[f"s{i}"] = stats.cpu()

@@ -1,6 +1,6 @@
 """A few launches of the attention forward + backward kernels at one shape (for rocprofv3 --pmc runs).
 usage: python tools/one_attn.py [B T H causal]"""
-import sys, os, math
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from segclip_amd import ops
@@ -12,7 +12,7 @@ o = torch.empty(B * T, D, dtype=BF, device=dev)
 do = torch.randn(B * T, D, device=dev).to(BF)
 dqkv = torch.empty_like(qkv)
 s3 = (T * 3 * D, 3 * D)
-desc = lambda: ops._attn_desc(qkv, qkv, qkv, o, B, H, T, T, hd, s3, s3, s3, (T * D, D), 1 / math.sqrt(hd), bool(causal), 0, D, 2 * D)
+desc = lambda: ops.attn_desc_packed(qkv, o, B, H, T, bool(causal))
 for _ in range(3):
     stats = ops.p_attn_fwd(desc(), qkv)
     ops.p_attn_bwd(desc(), stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D)
