@@ -519,6 +519,62 @@ int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, i
                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rendering of segmentation results (segment_render.inc): what the reference's demo draws, for images of mixed sizes in ONE
+ * launch per entry.
+ *
+ * segclip_seg_groups_rescaled: the group map at each image's output size.  Replaces get_attn_maps
+ * (seg_segmentation/evaluation/vit_seg.py:144-200: resize_attn_map to the network size, :180) and the group branch of
+ * show_result (:359-362: F.interpolate to the picture's size, arg-max over the groups).  An output pixel of an image with
+ * network size (H, W), grid (grid_h, grid_w) and output size (oh, ow): taps and weights on the (H, W) grid as in
+ * segclip_seg_label_map_rescaled; at each tap, per group, the value of soft_attn resized to (H, W) as segclip_seg_label_map
+ * forms it (four grid values); per group the blend h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) in fp32; first
+ * maximum over the groups; one byte.  A tap of weight 0 is not evaluated, and where one network pixel remains the group is
+ * formed by the label-map entry's own device function: (oh, ow) = (H, W) reproduces its `groups` bit for bit.  Neither the
+ * (G, H, W) nor the (G, oh, ow) array exists.
+ *   soft_attn : flat fp32 of soft_floats elements
+ *   images    : the (B, 16) int64 table of segclip_seg_label_map_rescaled, with column 6 = offset of the image's oh * ow
+ *               group bytes in `groups` (a multiple of 4 gives dword stores), column 8 = its first workgroup = the sum of
+ *               ceil(oh * ow / 1024) over the images before it, column 13 = offset of its window in soft_attn; 0 and 7 unused
+ *   n_blocks  : the sum of ceil(oh * ow / 1024) over all images;  groups: flat uint8 of groups_bytes
+ *   Group maps are defined for exactly ONE window per image, the image itself.  Every row is range-checked on the device: an
+ *   image whose window count (column 1) is not 1, whose window size (9, 10) is not (H, W), whose sizes are outside
+ *   [1, 2^30) or oh * ow >= 2^31, or whose offsets are inconsistent with soft_floats or groups_bytes is SKIPPED (its bytes
+ *   stay as they were).  The grid rows a workgroup's 1024 pixels reach are staged in LDS when G * rows * grid_w <= 6400
+ *   floats (a whole 8 x 28 x 28 window fits), read from global memory otherwise.
+ *   SEGCLIP_ERR_UNSUPPORTED: G > 8.  Bound: HBM writes, 1 byte per output pixel.
+ *
+ * segclip_seg_blend: the overlay of blend_result (vit_seg.py:258-284) on the decoded images and, with `sums`, the sums that
+ * seg2coord (:100-115) averages into the label anchors of vis_mode="input_pred_label" (:299-320), in the same pass.
+ *   images  : (B, 8) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
+ *             3 row stride in bytes (>= 3 w)  4 offset of the image's h * w indices in `maps`  5 offset of its 3 * h * w
+ *             output bytes in `out`  6 its first workgroup = the sum of ceil(h * w / 1024) over the images before it  7 0
+ *   n_blocks: the sum of ceil(h * w / 1024) over all images
+ *   maps    : flat uint8 of maps_bytes: per pixel the palette index (a label or a group)
+ *   palette : (P, 3) uint8, RGB, 1 <= P <= 256 (checked on the host).  reverse_channels: the source is BGR, palette channel c
+ *             meets image channel 2 - c (:272)
+ *   a, b    : 1.0 - opacity and opacity as fp64, computed by the caller as numpy computes them; 0 <= a < 1, 0 < b <= 1
+ *   out     : flat uint8 of out_bytes, (h, w, 3) per image in the source's channel order; must not overlap a source
+ *   out = (uint8) trunc(fl(fl(p * a) + fl(c * b))) in fp64 with p the source byte and c the palette byte: two rounded
+ *   products and one rounded sum, NOT a fused multiply-add (:276-279; fp32 or a fused sum give other bytes).  An index >= P
+ *   has colour (0, 0, 0) (color_seg stays zero, :268-270).  With skip_zero a pixel of index 0 is copied (fg_mask, :274-276).
+ *   sums    : (B, P, 3) int64 or NULL, ADDED to: per image and index the pixel count, the sum of y and the sum of x.  Index 0
+ *             is counted whatever skip_zero says; an index >= P is not counted.  Per-workgroup int32 counters in LDS, one
+ *             64-bit global add per touched counter: the sums do not depend on order.  A workgroup's tile is 1024 pixels;
+ *             with h, w < 2^15 its sums stay below 2^25 (the scheme's limit is a tile of 2^16 pixels: 2^16 * 2^15 = 2^31).
+ *   Every row is range-checked on the device.  An image whose row has a null address, a stride below 3 w, h or w outside
+ *   [1, 2^15), or offsets inconsistent with maps_bytes or out_bytes is SKIPPED: nothing of it is read, written or counted.
+ *   A lane owns 4 consecutive pixels of the flat (h, w) image: dword accesses where the unit is whole and its map, source
+ *   and output addresses are multiples of 4 (offsets that are multiples of 4 and a contiguous dword-aligned source give
+ *   that at every unit; with a padded row stride the source decides per unit), byte accesses otherwise - any w, any stride.
+ *   Bound: HBM traffic, 3 + 1 bytes read and 3 written per pixel.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_groups_rescaled(const float* soft_attn, int64_t soft_floats, const int64_t* images, int64_t B, int64_t n_blocks,
+                                int64_t G, uint8_t* groups, int64_t groups_bytes, void* stream);
+int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const uint8_t* maps, int64_t maps_bytes,
+                      const uint8_t* palette, int64_t P, int reverse_channels, double a, double b, int skip_zero, uint8_t* out,
+                      int64_t out_bytes, int64_t* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MAE random masking (integer path, bit-exact given the noise).  modules/module_clip_util.py:91-124
  * with keep_cls: noise[:,0] = -1; ids_shuffle = argsort(noise) (stable); ids_restore =
  * argsort(ids_shuffle); mask = 1 except the first len_keep of the shuffle.

@@ -293,6 +293,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 
 #include "segment_eval.inc"
 #include "segment_frontend.inc"
+#include "segment_render.inc"
 
 }  // namespace
 
@@ -468,5 +469,42 @@ extern "C" int segclip_seg_windows_from_u8(const int64_t* images, const int32_t*
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.inv_std[c] = inv_std[c]; }
   hipLaunchKernelGGL(seg_front_kernel, dim3((unsigned)(n_windows * per_window)), dim3(256), 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_windows_from_u8");
+  return 0;
+}
+
+extern "C" int segclip_seg_groups_rescaled(const float* soft_attn, int64_t soft_floats, const int64_t* images, int64_t B,
+                                           int64_t n_blocks, int64_t G, uint8_t* groups, int64_t groups_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && soft_floats >= 0 && groups_bytes >= 0, "seg_groups_rescaled: sizes must not be negative");
+  SEGCLIP_REQUIRE(G >= 1, "seg_groups_rescaled: G >= 1");
+  if (G > SEG_MAX_G) {
+    segclip_set_error("seg_groups_rescaled: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31), "seg_groups_rescaled: size out of range");
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(soft_attn && images && groups, "seg_groups_rescaled: soft_attn, images and groups are required");
+  SegGroupsArgs a;
+  a.soft = soft_attn; a.images = images; a.soft_floats = soft_floats; a.groups_bytes = groups_bytes;
+  a.B = (int)B; a.G = (int)G; a.groups = groups;
+  hipLaunchKernelGGL(seg_groups_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_groups_rescaled");
+  return 0;
+}
+
+extern "C" int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const uint8_t* maps, int64_t maps_bytes,
+                                 const uint8_t* palette, int64_t P, int reverse_channels, double a, double b, int skip_zero,
+                                 uint8_t* out, int64_t out_bytes, int64_t* sums, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && maps_bytes >= 0 && out_bytes >= 0, "seg_blend: sizes must not be negative");
+  SEGCLIP_REQUIRE(P >= 1 && P <= SEG_MAX_PALETTE, "seg_blend: a palette has 1..%d colours, got %lld", SEG_MAX_PALETTE, (long long)P);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31), "seg_blend: size out of range");
+  SEGCLIP_REQUIRE(a >= 0.0 && a < 1.0 && b > 0.0 && b <= 1.0, "seg_blend: a = 1 - opacity in [0, 1), b = opacity in (0, 1]");
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(images && maps && palette && out, "seg_blend: images, maps, palette and out are required");
+  SegBlendArgs k;
+  k.images = images; k.maps = maps; k.palette = palette; k.maps_bytes = maps_bytes; k.out_bytes = out_bytes;
+  k.B = (int)B; k.P = (int)P; k.reverse = reverse_channels ? 1 : 0; k.skip_zero = skip_zero ? 1 : 0; k.a = a; k.b = b;
+  k.out = out; k.sums = reinterpret_cast<unsigned long long*>(sums);
+  hipLaunchKernelGGL(seg_blend_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ST, k);
+  SEGCLIP_CHECK_LAUNCH("seg_blend");
   return 0;
 }

@@ -2532,3 +2532,77 @@ def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, rever
     L.check(L.load().segclip_seg_windows_from_u8(L.ptr(table), L.ptr(windows), n, table.shape[0], wh, ww, f3(*mean), f3(*inv_std),
                                                  int(bool(reverse_channels)), L.ptr(out), L.stream()), "seg_windows_from_u8")
     return out
+
+
+# ---------------------------------------------------------------- rendering of segmentation results (segment_render.inc)
+SEG_RENDER_TILE = 1024   # pixels of one workgroup of segclip_seg_groups_rescaled and segclip_seg_blend
+SEG_BLEND_COLS = 8       # int64 columns of one row of the image table of segclip_seg_blend
+SEG_MAX_GROUPS = 8
+
+
+def seg_groups_rescaled(soft_attn, images, n_blocks, G, groups):
+    """The group-map kernel (segclip_seg_groups_rescaled): flat soft_attn + the image table of seg_image_table (one window
+    per image; its label offsets are the group offsets) -> `groups`, a flat uint8 tensor written at every image's output
+    size.  An image whose row the device refuses keeps its bytes."""
+    L.require_cuda(soft_attn, images, groups)
+    if soft_attn.dtype != torch.float32 or images.dtype != torch.int64:
+        raise TypeError("seg_groups_rescaled: fp32 soft_attn, int64 image table")
+    if images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS:
+        raise ValueError("seg_groups_rescaled: images is the (B, 16) table of seg_image_table")
+    if groups.dtype != torch.uint8 or not groups.is_contiguous():
+        raise ValueError("seg_groups_rescaled: groups is a contiguous uint8 tensor")
+    soft_attn, images = soft_attn.contiguous(), images.contiguous()
+    L.check(L.load().segclip_seg_groups_rescaled(L.ptr(soft_attn), soft_attn.numel(), L.ptr(images), images.shape[0], int(n_blocks),
+                                                 int(G), L.ptr(groups), groups.numel(), L.stream()), "seg_groups_rescaled")
+    return groups
+
+
+def seg_blend_table(raws, map_offsets):
+    """The device image table of seg_blend: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows possibly strided],
+    map_offsets [offset of each image's (h, w) indices in the flat map buffer].  Output offsets are assigned here, each a
+    multiple of 4.  It holds the tensors' addresses: keep `raws` alive while it is in use.
+    -> (table (B, 8) int64, output offsets, out_bytes, n_blocks)."""
+    if len(raws) == 0 or len(raws) != len(map_offsets):
+        raise ValueError(f"seg_blend: {len(raws)} images but {len(map_offsets)} index maps")
+    L.require_cuda(*raws)
+    tab, offs, out, blk = [], [], 0, 0
+    for t, mo in zip(raws, map_offsets):
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"seg_blend: a source image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if t.device != raws[0].device:
+            raise ValueError("seg_blend: the source images are on different devices")
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_blend: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
+            raise ValueError(f"seg_blend: a source image has interleaved channels and contiguous pixels (strides (>= 3 w, 3, 1)), "
+                             f"got {tuple(t.stride())}")
+        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(mo), out, blk, 0])
+        offs.append(out)
+        out += (3 * h * w + 3) // 4 * 4
+        blk += (h * w + SEG_RENDER_TILE - 1) // SEG_RENDER_TILE
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_BLEND_COLS), offs, out, blk
+
+
+def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, reverse_channels=False, sums=None):
+    """The overlay kernel (segclip_seg_blend): the table of seg_blend_table + the flat uint8 index maps + a (P, 3) uint8 RGB
+    palette -> `out`, flat uint8, (h, w, 3) per image at the table's output offsets; `sums` (B, P, 3) int64 is added to."""
+    L.require_cuda(table, maps, palette, out, sums)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_BLEND_COLS or not table.is_contiguous():
+        raise ValueError("seg_blend: table is the (B, 8) int64 tensor of seg_blend_table")
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256:
+        raise ValueError(f"seg_blend: a palette is a (P <= 256, 3) uint8 tensor, got {palette.dtype} {tuple(palette.shape)}")
+    opacity = float(opacity)
+    if not 0.0 < opacity <= 1.0:
+        raise ValueError(f"seg_blend: opacity lies in (0, 1], got {opacity}")
+    for name, t in (("maps", maps), ("out", out)):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"seg_blend: {name} is a contiguous uint8 tensor")
+    P = palette.shape[0]
+    if sums is not None and (sums.dtype != torch.int64 or not sums.is_contiguous() or tuple(sums.shape) != (table.shape[0], P, 3)):
+        raise ValueError("seg_blend: sums is a contiguous (B, P, 3) int64 tensor")
+    palette = palette.contiguous()
+    L.check(L.load().segclip_seg_blend(L.ptr(table), table.shape[0], int(n_blocks), L.ptr(maps), maps.numel(), L.ptr(palette), P,
+                                       int(bool(reverse_channels)), 1.0 - opacity, opacity, int(bool(skip_zero)), L.ptr(out),
+                                       out.numel(), L.ptr(sums), L.stream()), "seg_blend")
+    return out

@@ -16,11 +16,20 @@ One HIP kernel (csrc/segment_frontend.inc) writes the tower's input windows from
 normalised on the way, so the resized image does not exist: decoded image in, mIoU out.  The dataset, the image decoding and
 the tokenizer stay with the caller.
 
+The demo (main_seg_vis.py; ViTSegInference.show_result / blend_result / seg2coord, vit_seg.py:100-115, 258-377): blend draws
+an index map over decoded images in numpy's fp64 arithmetic and sums the label anchors in the same launch, groups_list /
+groups_raw write the group map at each picture's size, and render_raw serves the reference's --vis modes from one pass of the
+vision tower (csrc/segment_render.inc).  Encoding the pictures, the palette-mode PNG of vis_mode="pred" and the label text
+stay with the caller.
+
 Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; here the arg-max is taken of the
 logits, which can differ only where fp32 exp rounds two different logits to one value.  A ground-truth value of 255 stays
 ignored whatever reduce_zero_label says.  The resized pixel is kept in fp32 and not rounded back to uint8 as cv2's 8-bit
-fixed-point resize does: about one grey level, 0.015 in normalised units (unmeasured: cv2 is not a dependency).
+fixed-point resize does: about one grey level, 0.015 in normalised units (unmeasured: cv2 is not a dependency).  The overlay
+is drawn on the decoded image itself, where the reference draws on a de-normalised copy of the network input resized back
+to the picture's size.  Text is not drawn: input_pred_label returns the anchor positions beside the overlay.
 """
+import colorsys
 import math
 
 import torch
@@ -296,18 +305,27 @@ class SegInference:
             n += len(members)
         return batches, per_image
 
-    def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True):
-        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows."""
+    def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
+                      groups=None):
+        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows.
+        groups: None, "also" (-> (labels, group maps, G), both at out_shapes, from the same pass of the tower) or "only"
+        (-> (None, group maps, G): no class tables, no label map)."""
         sizes, n_img = src.sizes, len(src.sizes)
         if out_shapes is None:
             out_shapes = src.default_out
         if len(out_shapes) != n_img:
             raise ValueError(f"{n_img} images but {len(out_shapes)} output shapes")
         out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
-        if self.num_classes > 256:
+        classes = groups != "only"
+        if classes and self.num_classes > 256:
             raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
         p = self.model.clip.visual.patch_size
         batches, per_image = self._list_plan(sizes)
+        if groups is not None:
+            for i, (_, count, _) in enumerate(per_image):
+                if count != 1:
+                    raise ValueError(f"group maps are defined for one window per image: image {i} ({sizes[i][0]}x{sizes[i][1]}) "
+                                     f"has {count} windows in slide mode")
         N = self.text_embedding.shape[0]
         dev = src.device
         for (wh, ww), _ in batches:
@@ -327,15 +345,18 @@ class SegInference:
                                      "training token count (modules/module_seg_vit.py:423)")
                 soft = mid["attns"][-1]["soft_attn"]
                 del mid, x
-                tables = ops.seg_group_table(hidden[:, 1:, :], feat, self.text_embedding, self.model.clip.logit_scale, min(5, N))
+                tables = ()
+                if classes:
+                    tables = ops.seg_group_table(hidden[:, 1:, :], feat, self.text_embedding, self.model.clip.logit_scale, min(5, N))
                 win_off += range(floats, floats + soft.numel(), soft.numel() // soft.shape[0])
                 floats += soft.numel()
+                n_groups = int(soft.shape[1])
                 parts.append((soft.reshape(-1),) + tables)
             done += len(wins)
         if len(parts) == 1:
             soft, tables = parts[0][0], parts[0][1:]
         else:
-            cat = [torch.cat([q[i] for q in parts]) for i in range(5)]
+            cat = [torch.cat([q[i] for q in parts]) for i in range(len(parts[0]))]
             soft, tables = cat[0], tuple(cat[1:])
         rows, gt_off = [], 0
         for i, (first, count, (wh, ww)) in enumerate(per_image):
@@ -343,15 +364,24 @@ class SegInference:
                              soft_off=win_off[first], gt_off=gt_off if gts is not None else -1))
             gt_off += out_shapes[i][0] * out_shapes[i][1]
         images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, dev)
-        labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
-        gt = None
-        if gts is not None:
-            gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
-        ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels, gt=gt,
-                                   areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
-        if not want_labels:
-            return None
-        return [labels[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
+        def views(flat):
+            return [flat[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
+        labels = None
+        if classes:
+            labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
+            gt = None
+            if gts is not None:
+                gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
+            ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels,
+                                       gt=gt, areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+            labels = views(labels) if want_labels else None
+        if groups is None:
+            return labels
+        # the table's label offsets and workgroup numbers serve the group maps as they are: same sizes, same tile
+        gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=dev))
+        return labels, views(gmaps), n_groups
 
     @torch.no_grad()
     def predict_list(self, imgs, out_shapes=None):
@@ -368,6 +398,167 @@ class SegInference:
         raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
         ori_shape); net_sizes overrides transform.net_size (whole mode needs multiples of the patch size)."""
         return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes)
+
+    # ------------------------------------------------------------------------------------------ the demo's outputs
+    @torch.no_grad()
+    def groups_list(self, imgs, out_shapes=None):
+        """[(3, H_i, W_i)] -> [(oh_i, ow_i) uint8 group maps], views of one flat buffer: the soft assignment resized to the
+        network size and again to the output size, first maximum over the groups (get_attn_maps + show_result's group
+        branch, vit_seg.py:144-200, :359-362), one launch for the list.  out_shapes defaults to the images' own sizes, where
+        the result equals group_map's.  Every image is one window: a slide-mode image with more raises ValueError."""
+        return self._list_forward(_SlicedImages(self.model, imgs), out_shapes, groups="only")[1]
+
+    @torch.no_grad()
+    def groups_raw(self, raws, transform, out_shapes=None, net_sizes=None):
+        """groups_list from decoded (h_i, w_i, 3) uint8 images, as predict_raw; out_shapes defaults to the raw sizes."""
+        return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes, groups="only")[1]
+
+    @torch.no_grad()
+    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None):
+        """The reference's --vis modes (show_result, vit_seg.py:286-377) for decoded images, at their own sizes -> dict
+        mode -> result:
+          input              the raws
+          pred               [(h_i, w_i) uint8 label maps] (predict_raw's)
+          input_pred         [(h_i, w_i, 3) uint8]: blend at opacity 0.8, background kept as it is when with_bg (:298)
+          input_pred_label   (blend at opacity 0.6, anchors [[(label, y, x)]] without the background when with_bg) (:299-320)
+          final_group, first_group   [(h_i, w_i, 3) uint8]: the group map blended at 0.6 with group_palette[:G] (:346-375)
+          all_groups         the same as a one-element list per image: this model has one grouping stage
+        palette: (P, 3) uint8 RGB class colours (index 0 = background when with_bg); group_palette defaults to
+        default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
+        call whatever the modes: labels and group maps come from the same encode_image pass."""
+        modes = list(vis_modes)
+        for m in modes:
+            if m not in VIS_MODES:
+                raise ValueError(f"unknown vis mode {m!r}; known: {', '.join(VIS_MODES)}")
+        want_labels = any(m in ("pred", "input_pred", "input_pred_label") for m in modes)
+        want_groups = any(m in _GROUP_MODES for m in modes)
+        src = _RawImages(self.model, raws, transform, net_sizes)
+        palette = _check_palette(palette, src.device)
+        labels = gmaps = None
+        if want_groups:
+            labels, gmaps, G = self._list_forward(src, None, want_labels=want_labels, groups="also" if want_labels else "only")
+        elif want_labels:
+            labels = self._list_forward(src, None)
+        order = transform.channel_order
+        out = {}
+        for m in modes:
+            if m in out:
+                continue
+            if m == "input":
+                out[m] = list(raws)
+            elif m == "pred":
+                out[m] = labels
+            elif m == "input_pred":
+                out[m] = blend(raws, labels, palette, 0.8, skip_zero=self.with_bg, channel_order=order)
+            elif m == "input_pred_label":
+                imgs, sums = blend(raws, labels, palette, 0.6, skip_zero=self.with_bg, channel_order=order, anchors=True)
+                marks = anchors_from_sums(sums.cpu())
+                if self.with_bg:
+                    marks = [[a for a in per if a[0] != 0] for per in marks]
+                out[m] = (imgs, marks)
+            else:
+                if "_groups" not in out:
+                    gp = default_group_palette(G) if group_palette is None else group_palette
+                    gp = _check_palette(gp, src.device)
+                    if gp.shape[0] < G:
+                        raise ValueError(f"the group palette has {gp.shape[0]} colours for {G} groups")
+                    out["_groups"] = blend(raws, gmaps, gp[:G], 0.6, channel_order=order)
+                out[m] = [[t] for t in out["_groups"]] if m == "all_groups" else out["_groups"]
+        out.pop("_groups", None)
+        return out
+
+
+VIS_MODES = ("input", "pred", "input_pred", "all_groups", "first_group", "final_group", "input_pred_label")
+_GROUP_MODES = ("all_groups", "first_group", "final_group")
+
+
+def default_group_palette(G):
+    """(G, 3) uint8 RGB colours for group maps: evenly spaced hues at full saturation, two brightness levels in turn so
+    that neighbouring hues stay apart.  (The reference's group_palette.txt is its data: a caller who wants it passes it.)"""
+    G = int(G)
+    if not 1 <= G <= 256:
+        raise ValueError(f"a palette has 1 .. 256 colours, got {G}")
+    rows = [[int(c * 255.0 + 0.5) for c in colorsys.hsv_to_rgb(i / G, 1.0, 1.0 if i % 2 == 0 else 0.65)] for i in range(G)]
+    return torch.tensor(rows, dtype=torch.uint8)
+
+
+def _check_palette(palette, device):
+    """-> (P, 3) uint8 on `device`; a palette is a small host-side setting like the normalisation constants and may come from
+    anywhere."""
+    palette = torch.as_tensor(palette)
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256:
+        raise ValueError(f"a palette is a (P <= 256, 3) uint8 tensor, got {palette.dtype} {tuple(palette.shape)}")
+    return palette.to(device).contiguous()
+
+
+def _flat_maps(maps):
+    """Index maps -> (flat uint8 buffer, offset of every map).  Views of one buffer (what predict_raw and groups_raw return)
+    are used where they lie; anything else is copied into a new buffer at offsets that are multiples of 4."""
+    store = maps[0].untyped_storage().data_ptr()
+    if all(m.is_contiguous() and m.untyped_storage().data_ptr() == store for m in maps):
+        lo = min(m.storage_offset() for m in maps)
+        hi = max(m.storage_offset() + m.numel() for m in maps)
+        return torch.as_strided(maps[0], (hi - lo,), (1,), lo), [m.storage_offset() - lo for m in maps]
+    offs, n = [], 0
+    for m in maps:
+        offs.append(n)
+        n += (m.numel() + 3) // 4 * 4
+    flat = torch.zeros(n, dtype=torch.uint8, device=maps[0].device)
+    for m, o in zip(maps, offs):
+        flat[o:o + m.numel()].view(m.shape).copy_(m)
+    return flat, offs
+
+
+@torch.no_grad()
+def blend(raws, maps, palette, opacity=0.5, skip_zero=False, channel_order="rgb", anchors=False):
+    """blend_result (vit_seg.py:258-284) for a list of pictures of mixed sizes in one launch: raws [(h_i, w_i, 3) uint8
+    decoded images, rows possibly strided], maps [(h_i, w_i) uint8 palette indices: labels or groups], palette (P <= 256, 3)
+    uint8 RGB -> [(h_i, w_i, 3) uint8] in the raws' channel order, views of one flat buffer.  Every byte is numpy's
+    (img * (1 - opacity) + color * opacity).astype(uint8), computed in fp64 as numpy does; an index >= P is black; with
+    skip_zero the pixels of index 0 stay as they are (the reference's with_bg).  anchors=True: also the (B, P, 3) int64
+    device tensor of per-index pixel counts, sums of y and sums of x (anchors_from_sums turns it into positions)."""
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+    opacity = float(opacity)
+    if not 0.0 < opacity <= 1.0:
+        raise ValueError(f"opacity lies in (0, 1], got {opacity}")
+    if len(raws) == 0:
+        raise ValueError("empty image list")
+    if len(raws) != len(maps):
+        raise ValueError(f"{len(raws)} images but {len(maps)} index maps")
+    for t in list(raws) + list(maps):
+        if not t.is_cuda:
+            raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {t.device} tensor")
+    for t, m in zip(raws, maps):
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        if m.dtype != torch.uint8 or m.dim() != 2 or tuple(m.shape) != tuple(t.shape[:2]):
+            raise ValueError(f"an index map is an (h, w) uint8 tensor of its image's size {tuple(t.shape[:2])}, got {m.dtype} "
+                             f"{tuple(m.shape)}")
+    dev = raws[0].device
+    palette = _check_palette(palette, dev)
+    flat, map_offs = _flat_maps(list(maps))
+    table, offs, nbytes, n_blocks = ops.seg_blend_table(list(raws), map_offs)
+    out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sums = torch.zeros(len(raws), palette.shape[0], 3, dtype=torch.int64, device=dev) if anchors else None
+    ops.seg_blend(table, n_blocks, flat, palette, opacity, out, skip_zero=skip_zero, reverse_channels=channel_order == "bgr",
+                  sums=sums)
+    imgs = [out[o:o + 3 * t.shape[0] * t.shape[1]].view(t.shape[0], t.shape[1], 3) for o, t in zip(offs, raws)]
+    return (imgs, sums) if anchors else imgs
+
+
+def anchors_from_sums(sums):
+    """The (B, P, 3) sums of blend(anchors=True), copied to the host -> per image [(index, y, x)] for the indices present:
+    y = int(sum_y / count), x = int(sum_x / count) in fp64 = seg2coord(...)[index].astype(np.int32) (vit_seg.py:100-115,
+    :320), where the label text is anchored."""
+    if sums.is_cuda:
+        raise ValueError("anchors_from_sums takes a CPU copy of the sums (sums.cpu())")
+    if sums.dim() != 3 or sums.shape[2] != 3 or sums.dtype != torch.int64:
+        raise ValueError(f"sums is a (B, P, 3) int64 tensor, got {sums.dtype} {tuple(sums.shape)}")
+    out = []
+    for per in sums.tolist():
+        out.append([(i, int(sy / n), int(sx / n)) for i, (n, sy, sx) in enumerate(per) if n > 0])
+    return out
 
 
 class SegEvaluator:
