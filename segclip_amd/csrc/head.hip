@@ -65,6 +65,13 @@ __global__ void max_tokens_bwd_kernel(const float* __restrict__ dout, const int3
 
 // ---------------------------------------------------------------- contrastive head
 __device__ __forceinline__ float clip_scale(const float* ls) { return fminf(expf(*ls), 100.f); }
+// the logit as ONE fp32 number, never contracted into the subtraction that follows: the row maximum is then one of the logits,
+// z_label - max is exact, and a row of one column has loss 0 and gradient 0 exactly (an fma would leave the product's rounding
+// residual there)
+__device__ __forceinline__ float clip_logit(float sc, float c) {
+#pragma clang fp contract(off)
+  return sc * c;
+}
 
 // both (B, 2, C): [b][0] = v[b] / |v[b]|, [b][1] = t[b] / |t[b]| (the stacked message of the embedding all-gather);
 // norms (2B): [2b + which].  One wave per (b, which) row.
@@ -98,7 +105,9 @@ __global__ void l2norm_pair_bwd_kernel(const float* __restrict__ dboth, const fl
   for (int c = lane; c < C; c += 64) d[c] = ((g[c] + (g2 ? g2[c] : 0.f)) - y[c] * s) * inv;
 }
 // cos (2, B, N): [0] = t . v_all^T, [1] = v . t_all^T (raw cosines); logits = clamp(exp(logit_scale), 100) * cos.
-// Row r of matrix z has label r + label_offset.  lse, loss_rows: (2B).  One wave per row.
+// Row r of matrix z has label r + label_offset.  lse, loss_rows: (2B).  One wave per row.  The row loss is formed as
+// log(s) - (z_label - max) and the backward's softmax as exp(z - lse) / sum exp(z - lse), as ce_fwd / ce_bwd of misc.hip do
+// and for the same reason: at a scale of 100 the rounding of max + log(s) is the size of a trained row's loss.
 __global__ void clip_ce_fwd_kernel(const float* __restrict__ cosm, const float* __restrict__ logit_scale, float* __restrict__ lse,
                                    float* __restrict__ loss_rows, int64_t B, int64_t N, int64_t label_offset) {
   const int lane = threadIdx.x & 63;
@@ -107,13 +116,13 @@ __global__ void clip_ce_fwd_kernel(const float* __restrict__ cosm, const float* 
   const float sc = clip_scale(logit_scale);
   const float* p = cosm + r * N;
   float mx = -INFINITY;
-  for (int64_t c = lane; c < N; c += 64) mx = fmaxf(mx, sc * p[c]);
+  for (int64_t c = lane; c < N; c += 64) mx = fmaxf(mx, clip_logit(sc, p[c]));
   mx = wave_max(mx);
   float s = 0.f;
-  for (int64_t c = lane; c < N; c += 64) s += expf(sc * p[c] - mx);
+  for (int64_t c = lane; c < N; c += 64) s += expf(clip_logit(sc, p[c]) - mx);
   s = wave_sum(s);
-  const float l = mx + logf(s);
-  if (lane == 0) { lse[r] = l; loss_rows[r] = l - sc * p[(r % B) + label_offset]; }
+  const float ls = logf(s);
+  if (lane == 0) { lse[r] = mx + ls; loss_rows[r] = ls - (clip_logit(sc, p[(r % B) + label_offset]) - mx); }
 }
 // dcos = coef * sc * (softmax - onehot), coef = g / (2B); ds_rows[r] = coef * sum_j (softmax - onehot)_j cos_j
 __global__ void clip_ce_bwd_kernel(const float* __restrict__ cosm, const float* __restrict__ lse, const float* __restrict__ logit_scale,
@@ -127,9 +136,12 @@ __global__ void clip_ce_bwd_kernel(const float* __restrict__ cosm, const float* 
   const float* p = cosm + r * N;
   const float l = lse[r];
   const int64_t label = (r % B) + label_offset;
+  float s = 0.f;
+  for (int64_t c = lane; c < N; c += 64) s += expf(clip_logit(sc, p[c]) - l);
+  const float inv = 1.f / wave_sum(s);
   float ds = 0.f;
   for (int64_t c = lane; c < N; c += 64) {
-    const float d = coef * (expf(sc * p[c] - l) - (c == label ? 1.f : 0.f));
+    const float d = coef * (expf(clip_logit(sc, p[c]) - l) * inv - (c == label ? 1.f : 0.f));
     dcos[r * N + c] = d * sc;
     ds += d * p[c];
   }

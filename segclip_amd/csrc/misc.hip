@@ -473,7 +473,9 @@ __global__ void l2norm_bwd_kernel(const float* __restrict__ dy, const float* __r
   const float inv = 1.f / norm[row];
   for (int c = lane; c < cols; c += 64) dx[row * cols + c] = (dy[row * cols + c] - y[row * cols + c] * s) * inv;
 }
-// one wave per row: lse and -log softmax[label]
+// one wave per row: lse and -log softmax[label].  The row loss is formed as log(s) - (z_label - max), the log_softmax order:
+// max + log(s) - z_label rounds the sum to an ulp of |max| first (4e-6 at logits of 85) and then cancels against z_label, which
+// is the whole loss of a trained row (3e-3).  lse keeps its meaning, max + log(s).
 __global__ void ce_fwd_kernel(const float* __restrict__ logits, float* __restrict__ lse, float* __restrict__ loss_rows,
                               int64_t rows, int64_t cols, int64_t label_offset) {
   const int lane = threadIdx.x & 63;
@@ -486,18 +488,28 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, float* __restric
   float s = 0.f;
   for (int64_t c = lane; c < cols; c += 64) s += expf(p[c] - mx);
   s = wave_sum(s);
-  const float l = mx + logf(s);
-  if (lane == 0) { lse[row] = l; loss_rows[row] = l - p[row + label_offset]; }
+  const float ls = logf(s);
+  if (lane == 0) { lse[row] = mx + ls; loss_rows[row] = ls - (p[row + label_offset] - mx); }
+}
+// one wave per row.  softmax_c = exp(z_c - lse) / sum_j exp(z_j - lse): lse serves as the shift only (z - lse <= 0, the sum is
+// 1 up to the rounding of lse), so that rounding - an ulp of |max|, relative 4e-6 in every probability at logits of 85 and
+// 1e-3 of (softmax - 1) on the label of a trained row - cancels between numerator and sum instead of entering the gradient.
+__device__ __forceinline__ float softmax_row_inv(const float* __restrict__ p, int64_t cols, float l, int lane) {
+  float s = 0.f;
+  for (int64_t c = lane; c < cols; c += 64) s += expf(p[c] - l);
+  return 1.f / wave_sum(s);
 }
 __global__ void ce_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ lse, const float* gscale_ptr,
                               float gscale, float* __restrict__ dlogits, int64_t rows, int64_t cols, int64_t label_offset) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
   const float gs = (gscale_ptr ? *gscale_ptr : 1.f) * gscale / (float)rows;
-  const int64_t total = rows * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t row = i / cols, c = i % cols;
-    const float p = expf(logits[i] - lse[row]);
-    dlogits[i] = gs * (p - (c == row + label_offset ? 1.f : 0.f));
-  }
+  const float* p = logits + row * cols;
+  const float l = lse[row];
+  const float inv = softmax_row_inv(p, cols, l, lane);
+  const int64_t label = row + label_offset;
+  for (int64_t c = lane; c < cols; c += 64) dlogits[row * cols + c] = gs * (expf(p[c] - l) * inv - (c == label ? 1.f : 0.f));
 }
 
 // cross entropy with explicit labels and an ignore index; one wave per row (the vocabulary: 49408 columns)
@@ -514,12 +526,12 @@ __global__ void ce_labels_fwd_kernel(const float* __restrict__ logits, const int
   float s = 0.f;
   for (int64_t c = lane; c < cols; c += 64) s += expf(p[c] - mx);
   s = wave_sum(s);
-  const float l = mx + logf(s);
+  const float ls = logf(s);
   if (lane == 0) {
     const int64_t lab = labels[row];
     const bool ok = lab != ignore && lab >= 0 && lab < cols;
-    lse[row] = l;
-    loss_rows[row] = ok ? l - p[lab] : 0.f;
+    lse[row] = mx + ls;
+    loss_rows[row] = ok ? ls - (p[lab] - mx) : 0.f;
     valid[row] = ok ? 1.f : 0.f;
   }
 }
@@ -527,14 +539,20 @@ __global__ void ce_labels_bwd_kernel(const float* __restrict__ logits, const flo
                                      const int64_t* __restrict__ labels, int64_t ignore, const float* __restrict__ gscale,
                                      const float* __restrict__ inv_count, float* __restrict__ dlogits, int64_t rows,
                                      int64_t cols) {
-  const float gs = gscale[0] * inv_count[0];
-  const int64_t total = rows * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t row = i / cols, c = i % cols;
-    const int64_t lab = labels[row];
-    const bool ok = lab != ignore && lab >= 0 && lab < cols;
-    dlogits[i] = ok ? gs * (expf(logits[i] - lse[row]) - (c == lab ? 1.f : 0.f)) : 0.f;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t lab = labels[row];
+  float* d = dlogits + row * cols;
+  if (!(lab != ignore && lab >= 0 && lab < cols)) {      // a row without a label: zeros, its logits are not read
+    for (int64_t c = lane; c < cols; c += 64) d[c] = 0.f;
+    return;
   }
+  const float gs = gscale[0] * inv_count[0];
+  const float* p = logits + row * cols;
+  const float l = lse[row];
+  const float inv = softmax_row_inv(p, cols, l, lane);
+  for (int64_t c = lane; c < cols; c += 64) d[c] = gs * (expf(p[c] - l) * inv - (c == lab ? 1.f : 0.f));
 }
 
 // superpixel-KL: one block per image.  hard (B,G,T) one-hot, seg (B,T) int64.  Emits loss_rows[b] (already
@@ -907,7 +925,7 @@ extern "C" int segclip_ce_fwd(const float* logits, float* lse, float* loss_rows,
 extern "C" int segclip_ce_bwd(const float* logits, const float* lse, const float* gscale_ptr, float gscale, float* dlogits,
                               int64_t rows, int64_t cols, int64_t label_offset, void* stream) {
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(ce_bwd_kernel, dim3(grid1d(rows * cols)), dim3(TPB), 0, ST, logits, lse, gscale_ptr, gscale, dlogits,
+  hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, ST, logits, lse, gscale_ptr, gscale, dlogits,
                      rows, cols, label_offset);
   SEGCLIP_CHECK_LAUNCH("ce_bwd");
   return 0;
@@ -924,7 +942,7 @@ extern "C" int segclip_ce_labels_bwd(const float* logits, const float* lse, cons
                                      const float* gscale, const float* inv_count, float* dlogits, int64_t rows,
                                      int64_t cols, void* stream) {
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(ce_labels_bwd_kernel, dim3(grid1d(rows * cols)), dim3(TPB), 0, ST, logits, lse, labels, ignore_index,
+  hipLaunchKernelGGL(ce_labels_bwd_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, ST, logits, lse, labels, ignore_index,
                      gscale, inv_count, dlogits, rows, cols);
   SEGCLIP_CHECK_LAUNCH("ce_labels_bwd");
   return 0;

@@ -69,7 +69,6 @@ Fixes that came with this file:
     test_group_linear_pair_end_to_end.
 """
 import dataclasses
-import math
 
 import pytest
 import torch
@@ -79,22 +78,10 @@ pytestmark = pytest.mark.gpu
 from segclip_amd import _lib as L  # noqa: E402
 from segclip_amd import ops  # noqa: E402
 from segclip_amd.modules import module_seg_vit as msv  # noqa: E402
-from tests.helpers import _beyond, check, within  # noqa: E402
+from tests.kernel_frames import BF, DEV, F32, F64, Bounds, Frame, draw, lib_call, put, run_twice, seeded  # noqa: E402
 
-DEV = "cuda"
-BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
-GUARD = 64
-IDX_FILL = 0xAB
 TAU = 0.9
 TAU32 = float(torch.tensor(TAU, dtype=F32))     # the value the kernel receives through its `float tau`
-
-def round_up_1(x):
-    """x rounded up to one significant digit"""
-    if x <= 0:
-        return 0.0
-    e = math.floor(math.log10(x))
-    return math.ceil(x / 10 ** e - 1e-9) * 10 ** e
-
 
 RT_BF = 2.0 ** -8
 # floors measured by floors() (torch float32 against fp64 on this file's rows, maximum over the rows of the kernel) ...
@@ -106,103 +93,11 @@ FLOORS = {
     "gl.dw": 3.189e-7,
 }
 
-# ... and the bounds: 4 x floor rounded up to one digit
-RT = {k: round_up_1(4 * f) for k, f in FLOORS.items()}
-
-STATS = None     # a dict here (floors() sets it) switches the rows from asserting the values to recording floors and errors
-
-
-def units(got, ref):
-    """the largest error in check() units, |err| / (|ref| + rms(ref))"""
-    _, err, rms = _beyond(got, ref, 0.0)
-    return float((err / (ref.double().abs() + rms)).max())
-
-
-def judge(key, what, got, ref, ref32=None, rtol=None):
-    """the value check of a row; under floors() it records the floor and the kernel's error instead"""
-    if STATS is None:
-        check(got, ref, RT[key] if rtol is None else rtol, what)
-        return
-    s = STATS.setdefault(key, {"floor": 0.0, "kernel": 0.0, "floor_row": "", "kernel_row": ""})
-    if ref32 is not None:
-        f = units(ref32, ref)
-        if f > s["floor"]:
-            s["floor"], s["floor_row"] = f, what
-    e = units(got, ref)
-    if e > s["kernel"]:
-        s["kernel"], s["kernel_row"] = e, what
-
-
-def rejects(key, what, got, wrong, rtol=None):
-    assert within(got, wrong, RT[key] if rtol is None else rtol) is False, f"{what}: the bound accepts the defect"
-
-
-# ---- frames ---------------------------------------------------------------------------------------------------------------
-class Frame:
-    """a view of `shape` (rows of shape[-1] elements, `pitch` apart) inside a flat buffer filled with NaN (0xAB for uint8):
-    GUARD words before, two guard rows and GUARD words after"""
-
-    def __init__(self, shape, dtype, pitch=None):
-        shape = tuple(shape)
-        W = shape[-1]
-        pitch = pitch or W
-        rows = math.prod(shape[:-1])
-        self.fill = float("nan") if dtype.is_floating_point else IDX_FILL
-        self.buf = torch.full((GUARD + (rows + 2) * pitch + GUARD,), self.fill, dtype=dtype, device=DEV)
-        st = [1] if len(shape) == 1 else [pitch, 1]
-        for d in reversed(shape[1:-1]):
-            st.insert(0, st[0] * d)
-        self.v = self.buf.as_strided(shape, st, GUARD)
-        self.inside = torch.zeros_like(self.buf, dtype=torch.bool)
-        self.inside.as_strided(shape, st, GUARD).fill_(True)
-
-    def intact(self):
-        out = self.buf[~self.inside]
-        return bool(out.isnan().all()) if self.buf.dtype.is_floating_point else bool((out == self.fill).all())
-
-    def finite(self):
-        return bool(self.v.isfinite().all()) if self.buf.dtype.is_floating_point else bool((self.v != self.fill).all())
-
-    def bits(self):
-        return self.buf.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[self.buf.element_size()]).clone()
-
-    @property
-    def p(self):
-        return L.ptr(self.v)
-
-
-def put(t, pitch=None):
-    """the input t inside a frame of its own"""
-    f = Frame(t.shape, t.dtype, pitch)
-    f.v.copy_(t)
-    return f
-
-
-def draw(gen, *shape, dtype=F32, scale=1.0):
-    return (torch.randn(*shape, generator=gen, dtype=F64) * scale).to(dtype).to(DEV)
-
-
-def seeded(name):
-    return torch.Generator().manual_seed(sum((i + 1) * ord(c) for i, c in enumerate(name)))
-
-
-def run_twice(name, call, outs):
-    """the call, its frames checked, and the same call again: bit-identical, frames included"""
-    for f in outs:
-        f.buf.fill_(f.fill)
-    call()
-    torch.cuda.synchronize()
-    snap = [f.bits() for f in outs]
-    call()
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, f.bits()) for a, f in zip(snap, outs)), f"{name}: the second call differs"
-    for i, f in enumerate(outs):
-        assert f.intact(), f"{name}: output {i} written outside its view"
-        assert f.finite(), f"{name}: output {i} not written everywhere / not finite"
-
-
-def lib_call(fn_name, *args):
-    L.check(getattr(L.load(), fn_name)(*args, L.stream()), fn_name)
+# ... and the bounds: 4 x floor rounded up to one digit (tests/kernel_frames.Bounds); BOUNDS.stats is None while the rows assert,
+# floors() sets a dict there and the rows record floors and errors instead
+BOUNDS = Bounds(FLOORS)
+RT = BOUNDS.rt
+judge, rejects = BOUNDS.judge, BOUNDS.rejects
 
 
 # ---- grouped 64-channel linear ---------------------------------------------------------------------------------------------
@@ -392,7 +287,7 @@ def test_segment_mean(c):
     v, dout = draw(gen, c.B, c.T, c.D, dtype=c.dtype), draw(gen, c.B, c.G, c.D)
     out, dv, dhard = sm_run(c.name, idx, v, dout, c.G)
     ref = sm_expr(idx, v, dout, c.G, F64)
-    r32 = sm_expr(idx, v, dout, c.G, F32) if STATS is not None else {}
+    r32 = sm_expr(idx, v, dout, c.G, F32) if BOUNDS.stats is not None else {}
     bf = c.dtype == BF
     judge("segmean.out", f"{c.name}: out", out, ref["out"], r32.get("out"))
     if bf:
@@ -474,7 +369,7 @@ def test_center_logits(c):
               [fdq, fdk])
     assert all(f.intact() for f in (fq, fk, fdl))
     ref = cl_expr(q, k, dl, F64)
-    r32 = cl_expr(q, k, dl, F32) if STATS is not None else {}
+    r32 = cl_expr(q, k, dl, F32) if BOUNDS.stats is not None else {}
     got = {"attn": fa.v, "dq": fdq.v, "dk": fdk.v}
     for n in got:
         judge(f"logits.{n}", f"{c.name}: {n}", got[n], ref[n], r32.get(n))
@@ -499,7 +394,7 @@ def test_center_logits_forward_at_its_largest_lds():
     for j in range(16):
         s = slice(8 * j, 8 * j + 8)
         ref = cl_expr(q[s], kb, None, F64)["attn"] * 2.0 ** (j - 8)
-        r32 = cl_expr(q[s], kb * 2.0 ** (j - 8), None, F32)["attn"] if STATS is not None else None
+        r32 = cl_expr(q[s], kb * 2.0 ** (j - 8), None, F32)["attn"] if BOUNDS.stats is not None else None
         judge("logits.attn", f"{c.name}: samples {8 * j}..{8 * j + 7}", fa.v[s], ref, r32)
         rejects("logits.attn", f"{c.name}: copy {j}, the last token replaced by its neighbour", fa.v[s],
                 cl_expr(q[s], kb2, None, F64)["attn"] * 2.0 ** (j - 8))
@@ -546,7 +441,7 @@ def test_recon_mix(B, M, D):
     run_twice(name + " bwd", lambda: lib_call("segclip_recon_mix_bwd", fa.p, fx.p, fd.p, fda.p, fdx.p, B, M, 8, D), [fda, fdx])
     assert all(f.intact() for f in (fa, fx, fd))
     ref = rm_expr(a, x, dout, F64)
-    r32 = rm_expr(a, x, dout, F32) if STATS is not None else {}
+    r32 = rm_expr(a, x, dout, F32) if BOUNDS.stats is not None else {}
     got = {"out": fo.v, "da": fda.v, "dx": fdx.v}
     for n in got:
         judge(f"recon.{n}", f"{name}: {n}", got[n], ref[n], r32.get(n))
@@ -611,7 +506,7 @@ def test_assign(B, G, T, train):
     run_twice(name + " bwd", lambda: lib_call("segclip_assign_bwd", fdh.p, fy.p, tau, fdl.p, B, G, T), [fdl])
     assert fl.intact() and fdh.intact() and fy.intact() and (fg is None or fg.intact())
     ref = as_expr(l, g, tau, dhard, F64)
-    r32 = as_expr(l, g, tau, dhard, F32) if STATS is not None else {}
+    r32 = as_expr(l, g, tau, dhard, F32) if BOUNDS.stats is not None else {}
     idx = first_max(ref["z"])
     if not train:
         assert int(idx[0, 0]) == 0 and int(idx[1, 0]) == 0, "the ties are meant to be won by the lowest index"
@@ -765,9 +660,8 @@ def test_rows_reach_every_instance():
 
 # ---- the measurement behind FLOORS -----------------------------------------------------------------------------------------------
 def floors():
-    """every row once with STATS set: {key: floor of torch float32 against fp64, the kernel's error, the rows they come from}"""
-    global STATS
-    STATS = {}
+    """every row once with BOUNDS.stats set: {key: floor of torch float32 against fp64, the kernel's error, the rows they come from}"""
+    BOUNDS.stats = {}
     try:
         for c in SM_CASES:
             test_segment_mean(c)
@@ -780,6 +674,6 @@ def floors():
         for r in AS_CASES:
             test_assign(*r)
         test_group_linear_pair_end_to_end()
-        return STATS
+        return BOUNDS.stats
     finally:
-        STATS = None
+        BOUNDS.stats = None
