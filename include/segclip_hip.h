@@ -575,6 +575,48 @@ int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const 
                       int64_t out_bytes, int64_t* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Front end of training (train_frontend.inc): decoded uint8 images and int32 segment maps -> the model's `image` and
+ * `image_seg`, each in ONE launch for a batch of mixed sizes.  Both entries are integer algorithms and reproduce the
+ * reference's CPU pipeline to the last bit.
+ *
+ * segclip_train_images_from_u8: RawImageExtractor's transforms (dataloaders/rawimage_util.py:40-52: RandomResizedCropCoord
+ * with Image.BICUBIC :45, :347-361, or Resize + CenterCrop :47; ToTensor and Normalize :49) = Pillow's 8-bit BICUBIC resize of
+ * a crop, a window of the result, a value table.
+ *   images : (B, 13) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
+ *            3 row stride in bytes (>= 3 w)  4 x0  5 y0  6 bw  7 bh, the crop box inside the source - the filter sees the box
+ *            as the whole image (crop() then resize(), NOT resize(box=...))  8 RW  9 RH, the size the box is resized to
+ *            10 ox  11 oy, the offset of the (out_h, out_w) output window inside (RH, RW)  12 flags: bit 0 = horizontal,
+ *            bit 1 = vertical flip of the window
+ *   lut    : (256, 3) fp32 on the device; out[b, c, y, x] = lut[byte][c]: no floating-point arithmetic touches a pixel
+ *   out    : (B, 3, out_h, out_w) fp32, contiguous
+ * Per axis with in = crop side and out = RW or RH, in fp64 without contraction (Pillow's precompute_coeffs):
+ * scale = in / out, fs = max(scale, 1), support = 2 fs, center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ * xmax = min((int)(center + support + 0.5), in), weights bicubic((x + xmin - center + 0.5) * (1 / fs)) with a = -0.5, summed in
+ * index order, each divided by the sum, each rounded to (int)(w * 2^22 +- 0.5) with the sign of w.  A pass is
+ * clamp((2^21 + sum byte * k) >> 22, 0, 255) in int32; the horizontal pass runs first and is rounded to bytes.
+ *   Every row is range-checked on the device.  An image is ZERO-FILLED when its row has a null address, a stride below 3 w,
+ *   one of h, w, RW, RH outside [1, 2^15), a box not inside (h, w), a window not inside (RH, RW), bw > 8 RW or bh > 8 RH
+ *   (at most 33 taps), or flags outside 0..3; the other images are unaffected.  Nothing is read outside the box.
+ *   16-byte stores when out_w % 4 == 0 and out is 16-byte aligned, scalar stores otherwise.  Design bound: the crop bytes
+ *   read once + 12 bytes written per output pixel.  SEGCLIP_ERR_UNSUPPORTED: out_w > 256.  out_h < 2^15, B <= 2^24.
+ *
+ * segclip_train_patch_labels: get_felzenszwalb_from_cache (dataloaders/rawimage_util.py:100-144) given the integer box of
+ * :119-120, which the host computes.
+ *   maps   : (B, 9) int64 rows on the device: 0 address of the map (int32, (h, w), 4-byte aligned)  1 h  2 w  3 row stride in
+ *            bytes (>= 4 w, a multiple of 4)  4 x0  5 y0  6 x1  7 y1, the box; x1 - x0 < 2 or y1 - y0 < 2 takes the whole
+ *            map (:122)  8 flags: bit 0 = horizontal, bit 1 = vertical flip of the cropped map (:127-128)
+ *   out    : (B, 1, size / patch, size / patch) int64
+ * The crop is resampled to size x size with ATen's nearest index min((int64) floorf(d * ((float) in / size)), in - 1), product
+ * and quotient in fp32 (:132); every patch x patch tile gives sum >> log2(patch^2), or a 64-bit division where patch^2 is no
+ * power of two, the sum taken in 64 bits (:136-139, np.mean(...).astype(long) for labels in [0, 2^31)).
+ *   A row with a null or unaligned address, a stride below 4 w, h or w outside [1, 2^15), a box outside the map, flags outside
+ *   0..3, or a NEGATIVE label among the pixels read gives -1 in all its entries; the other rows are unaffected.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_train_images_from_u8(const int64_t* images, int64_t B, int64_t out_h, int64_t out_w, const float* lut, float* out,
+                                 void* stream);
+int segclip_train_patch_labels(const int64_t* maps, int64_t B, int64_t size, int64_t patch, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MAE random masking (integer path, bit-exact given the noise).  modules/module_clip_util.py:91-124
  * with keep_cls: noise[:,0] = -1; ids_shuffle = argsort(noise) (stable); ids_restore =
  * argsort(ids_shuffle); mask = 1 except the first len_keep of the shuffle.

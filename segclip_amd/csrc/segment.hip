@@ -8,6 +8,8 @@
 // first maximum and looks one row up (bound: 1-2 bytes of HBM writes per pixel).
 #include "common.h"
 
+#include <atomic>
+
 #define SEG_MAX_G 8          // groups per window (the center stage has 8)
 #define SEG_MAX_COVER 16     // windows covering one pixel
 #define SEG_MAX_IMG_WIN 64   // windows per image
@@ -294,6 +296,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_eval.inc"
 #include "segment_frontend.inc"
 #include "segment_render.inc"
+#include "train_frontend.inc"
 
 }  // namespace
 
@@ -506,5 +509,48 @@ extern "C" int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blo
   k.out = out; k.sums = reinterpret_cast<unsigned long long*>(sums);
   hipLaunchKernelGGL(seg_blend_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ST, k);
   SEGCLIP_CHECK_LAUNCH("seg_blend");
+  return 0;
+}
+
+extern "C" int segclip_train_images_from_u8(const int64_t* images, int64_t B, int64_t out_h, int64_t out_w, const float* lut, float* out,
+                                            void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && B <= (1 << 24) && out_h >= 1 && out_w >= 1 && out_h < TF_LIMIT, "train_images_from_u8: sizes out of range");
+  if (out_w > TF_MAX_OUT_W) {
+    segclip_set_error("train_images_from_u8: an output of %lld columns, at most %d (coefficients and 33 rows of bytes in LDS)",
+                      (long long)out_w, TF_MAX_OUT_W);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0) return 0;
+  SEGCLIP_REQUIRE(images && lut && out, "train_images_from_u8: images, lut and out are required");
+  const int64_t bands = cdiv(out_h, TF_BAND);
+  SEGCLIP_REQUIRE(B * bands < (1ll << 31), "train_images_from_u8: %lld images of %lld rows exceed one launch", (long long)B, (long long)out_h);
+  static std::atomic<bool> raised[64];
+  int dev = 0;
+  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "train_images_from_u8: cannot query the current device");
+  if (!raised[dev]) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(train_front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             TF_LDS_BYTES);
+    SEGCLIP_REQUIRE(e == hipSuccess, "train_images_from_u8: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+    raised[dev] = true;
+  }
+  TrainFrontArgs a;
+  a.images = images; a.lut = lut; a.out = out; a.out_h = (int)out_h; a.out_w = (int)out_w; a.bands = (int)bands;
+  a.vec = (out_w % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(train_front_kernel, dim3((unsigned)(B * bands)), dim3(256), TF_LDS_BYTES, ST, a);
+  SEGCLIP_CHECK_LAUNCH("train_images_from_u8");
+  return 0;
+}
+
+extern "C" int segclip_train_patch_labels(const int64_t* maps, int64_t B, int64_t size, int64_t patch, int64_t* out, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && B <= (1 << 24) && size >= 1 && size < TF_LIMIT && patch >= 1 && patch <= size && size % patch == 0,
+                  "train_patch_labels: need 1 <= patch <= size < 2^15 and size a multiple of patch");
+  if (B == 0) return 0;
+  SEGCLIP_REQUIRE(maps && out, "train_patch_labels: maps and out are required");
+  const int64_t pp = patch * patch;
+  int shift = -1;  // log2(patch^2), or the division path
+  if ((pp & (pp - 1)) == 0)
+    for (shift = 0; (1ll << shift) < pp; ++shift) {}
+  hipLaunchKernelGGL(train_labels_kernel, dim3((unsigned)B), dim3(256), 0, ST, maps, out, (int)size, (int)patch, shift);
+  SEGCLIP_CHECK_LAUNCH("train_patch_labels");
   return 0;
 }

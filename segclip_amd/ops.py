@@ -2606,3 +2606,122 @@ def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, rev
                                        int(bool(reverse_channels)), 1.0 - opacity, opacity, int(bool(skip_zero)), L.ptr(out),
                                        out.numel(), L.ptr(sums), L.stream()), "seg_blend")
     return out
+
+
+# ---------------------------------------------------------------- front end of training (train_frontend.inc)
+TRAIN_SOURCE_COLS = 13    # int64 columns of one row of the source table of segclip_train_images_from_u8
+TRAIN_MAP_COLS = 9        # int64 columns of one row of the map table of segclip_train_patch_labels
+TRAIN_MAX_SCALE = 8       # crop side / resized side, per axis (33 filter taps)
+TRAIN_MAX_OUT_W = 256
+
+
+def train_source_table(raws, geometry, out_size):
+    """The device source table of train_images_from_u8: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows possibly
+    strided], geometry [(x0, y0, bw, bh, RW, RH, ox, oy, flags)] per image - the crop box, the size it is resized to, the
+    offset of the out_size = (out_h, out_w) window in the resized image, flags bit 0 / 1 = horizontal / vertical flip of the
+    window -> (B, 13) int64.  Everything the device would refuse raises here.  It holds the tensors' addresses: keep `raws`
+    alive while it is in use."""
+    if len(raws) == 0 or len(raws) != len(geometry):
+        raise ValueError(f"train_source_table: {len(raws)} images but {len(geometry)} geometry rows")
+    L.require_cuda(*raws)
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if oh < 1 or ow < 1 or oh >= SEG_SOURCE_LIMIT or ow > TRAIN_MAX_OUT_W:
+        raise ValueError(f"train_images_from_u8: an output of 1 .. {SEG_SOURCE_LIMIT - 1} rows and 1 .. {TRAIN_MAX_OUT_W} columns, "
+                         f"got {oh}x{ow}")
+    tab = []
+    for t, g in zip(raws, geometry):
+        if t.dtype != torch.uint8:
+            raise TypeError(f"train_images_from_u8: a source image is uint8, got {t.dtype}")
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"train_images_from_u8: a source image is (h, w, 3), got {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if t.device != raws[0].device:
+            raise ValueError("train_images_from_u8: the source images are on different devices")
+        if len(g) != 9:
+            raise ValueError("train_images_from_u8: a geometry row is (x0, y0, bw, bh, RW, RH, ox, oy, flags)")
+        x0, y0, bw, bh, RW, RH, ox, oy, flags = (int(v) for v in g)
+        if min(h, w, RW, RH) < 1 or max(h, w, RW, RH) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"train_images_from_u8: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w} -> {RH}x{RW}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
+            raise ValueError(f"train_images_from_u8: a source image has interleaved channels and contiguous pixels (strides "
+                             f"(>= 3 w, 3, 1)), got {tuple(t.stride())}")
+        if x0 < 0 or y0 < 0 or bw < 1 or bh < 1 or x0 + bw > w or y0 + bh > h:
+            raise ValueError(f"train_images_from_u8: the box (x0, y0, bw, bh) = {(x0, y0, bw, bh)} is not inside the {h}x{w} image")
+        if ox < 0 or oy < 0 or ox + ow > RW or oy + oh > RH:
+            raise ValueError(f"train_images_from_u8: the {oh}x{ow} window at (ox, oy) = {(ox, oy)} is not inside the resized "
+                             f"{RH}x{RW} image")
+        if bw > TRAIN_MAX_SCALE * RW or bh > TRAIN_MAX_SCALE * RH:
+            raise ValueError(f"train_images_from_u8: a crop of {bh}x{bw} to {RH}x{RW} shrinks more than {TRAIN_MAX_SCALE} times")
+        if not 0 <= flags <= 3:
+            raise ValueError(f"train_images_from_u8: flags are 0 .. 3, got {flags}")
+        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), x0, y0, bw, bh, RW, RH, ox, oy, flags])
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, TRAIN_SOURCE_COLS)
+
+
+def train_images_from_u8(raws, geometry, out_size, lut, out=None, table=None):
+    """The training front end (segclip_train_images_from_u8): decoded uint8 images -> (B, 3, out_h, out_w) fp32, each the
+    out_size window of Pillow's BICUBIC resize of its crop, looked up in `lut` (256, 3) fp32 - bit for bit
+    Image.crop(box).resize((RW, RH), Image.BICUBIC), ToTensor and Normalize.  One launch.  table: train_source_table(raws,
+    geometry, out_size) when the caller built it already; the device zero-fills an image whose row it refuses.  Crops more
+    than 8 times the resized side are not supported and raise."""
+    if table is None:
+        table = train_source_table(raws, geometry, out_size)
+    elif table.dtype != torch.int64 or tuple(table.shape) != (len(raws), TRAIN_SOURCE_COLS) or not table.is_contiguous():
+        raise ValueError("train_images_from_u8: table is the (B, 13) int64 tensor of train_source_table")
+    L.require_cuda(table, lut, out)
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous():
+        raise ValueError("train_images_from_u8: lut is a contiguous (256, 3) fp32 tensor")
+    B = table.shape[0]
+    if out is None:
+        out = torch.empty(B, 3, oh, ow, dtype=torch.float32, device=table.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * 3 * oh * ow:
+        raise ValueError("train_images_from_u8: out is a contiguous fp32 tensor of B * 3 * out_h * out_w elements")
+    L.check(L.load().segclip_train_images_from_u8(L.ptr(table), B, oh, ow, L.ptr(lut), L.ptr(out), L.stream()),
+            "train_images_from_u8")
+    return out
+
+
+def train_patch_labels(seg_maps, boxes, size, patch, out=None, table=None):
+    """The patch labels of a batch (segclip_train_patch_labels): seg_maps [(h, w) int32 device tensors, rows possibly strided],
+    boxes [(x0, y0, x1, y1, flags)] per map - a box thinner than 2 takes the whole map, flags bit 0 / 1 = horizontal /
+    vertical flip of the crop -> (B, 1, size / patch, size / patch) int64, bit for bit get_felzenszwalb_from_cache.  One
+    launch.  A map with a negative label among the pixels read gives a row of -1."""
+    size, patch = int(size), int(patch)
+    if size < 1 or size >= SEG_SOURCE_LIMIT or patch < 1 or size % patch != 0:
+        raise ValueError(f"train_patch_labels: size 1 .. {SEG_SOURCE_LIMIT - 1}, a multiple of patch; got {size} / {patch}")
+    if table is None:
+        if len(seg_maps) == 0 or len(seg_maps) != len(boxes):
+            raise ValueError(f"train_patch_labels: {len(seg_maps)} maps but {len(boxes)} boxes")
+        L.require_cuda(*seg_maps)
+        tab = []
+        for t, bx in zip(seg_maps, boxes):
+            if t.dtype != torch.int32:
+                raise TypeError(f"train_patch_labels: a segment map is int32, got {t.dtype}")
+            if t.dim() != 2:
+                raise ValueError(f"train_patch_labels: a segment map is (h, w), got {tuple(t.shape)}")
+            h, w = int(t.shape[0]), int(t.shape[1])
+            if t.device != seg_maps[0].device:
+                raise ValueError("train_patch_labels: the segment maps are on different devices")
+            if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+                raise ValueError(f"train_patch_labels: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+            if t.stride(1) != 1 or (h > 1 and t.stride(0) < w):
+                raise ValueError(f"train_patch_labels: a segment map has contiguous rows (strides (>= w, 1)), got {tuple(t.stride())}")
+            x0, y0, x1, y1, flags = (int(v) for v in bx)
+            whole = x1 - x0 < 2 or y1 - y0 < 2
+            if not whole and (x0 < 0 or y0 < 0 or x1 > w or y1 > h):
+                raise ValueError(f"train_patch_labels: the box {(x0, y0, x1, y1)} is not inside the {h}x{w} map")
+            if not 0 <= flags <= 3:
+                raise ValueError(f"train_patch_labels: flags are 0 .. 3, got {flags}")
+            tab.append([t.data_ptr(), h, w, 4 * max(int(t.stride(0)), w), x0, y0, x1, y1, flags])
+        table = torch.tensor(tab, dtype=torch.int64, device=seg_maps[0].device).view(-1, TRAIN_MAP_COLS)
+    elif table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != TRAIN_MAP_COLS or not table.is_contiguous():
+        raise ValueError("train_patch_labels: table is a (B, 9) int64 tensor")
+    L.require_cuda(table, out)
+    B, P = table.shape[0], size // patch
+    if out is None:
+        out = torch.empty(B, 1, P, P, dtype=torch.int64, device=table.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B * P * P:
+        raise ValueError("train_patch_labels: out is a contiguous int64 tensor of B * (size / patch)^2 elements")
+    L.check(L.load().segclip_train_patch_labels(L.ptr(table), B, size, patch, L.ptr(out), L.stream()), "train_patch_labels")
+    return out

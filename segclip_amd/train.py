@@ -215,9 +215,12 @@ class TrainTail:
 
 
 def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, scheduler, global_step, scaler=None,
-                local_rank=0, tail=None):
+                local_rank=0, tail=None, transform=None):
     """Signature and return value of the reference's train_epoch.  `tail` may be passed to keep one TrainTail (and
-    its NaN-skip counter) across epochs."""
+    its NaN-skip counter) across epochs.  With transform (a transforms.RawImageTransform) a batch's `image` is a list of
+    decoded (h, w, 3) uint8 images and its sixth element, when present, a list of (h, w) int32 segment maps: they go to the
+    device as they are, and the transform's two kernels produce the `image` and `image_seg` the model is fed (the batch's
+    coord slot is not read: the transform draws the crops)."""
     model.train()
     log_step = getattr(args, "n_display", 100)
     acc = max(int(getattr(args, "gradient_accumulation_steps", 1)), 1)
@@ -234,12 +237,20 @@ def train_epoch(epoch, args, model, train_dataloader, device, n_gpu, optimizer, 
     n_batches = 0
     for step, batch in enumerate(train_dataloader):
         n_batches += 1
-        batch = tuple(t.to(device=device, non_blocking=True) for t in batch)
         image_seg = None
-        if len(batch) == 6:
-            input_ids, input_mask, segment_ids, image, coord, image_seg = batch
+        if transform is None:
+            batch = tuple(t.to(device=device, non_blocking=True) for t in batch)
+            if len(batch) == 6:
+                input_ids, input_mask, segment_ids, image, coord, image_seg = batch
+            else:
+                input_ids, input_mask, segment_ids, image, coord = batch
         else:
-            input_ids, input_mask, segment_ids, image, coord = batch
+            input_ids, input_mask, segment_ids = (t.to(device=device, non_blocking=True) for t in batch[:3])
+            raws = [t.to(device=device, non_blocking=True) for t in batch[3]]
+            image, coord = transform(raws)
+            image = image.unsqueeze(1)   # (B, 1, 3, size, size): the loader's pair axis
+            if len(batch) == 6:
+                image_seg = transform.patch_labels([m.to(device=device, non_blocking=True) for m in batch[5]], coord)
         loss = model(input_ids, segment_ids, input_mask, image, image_seg=image_seg)
         if n_gpu > 1:
             loss = loss.mean()
