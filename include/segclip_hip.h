@@ -466,7 +466,8 @@ int segclip_seg_logits(const float* soft_attn, const float* table, const float* 
  *   images    : (B, 16) int64 rows on the device:
  *               0 first window  1 window count  2 H  3 W  4 oh  5 ow  6 offset of the image's oh * ow labels in `labels`
  *               7 offset of its ground truth in `gt`, or -1  8 its first workgroup = the sum of ceil(oh * ow / 1024) over the
- *               images before it  9 win_h  10 win_w  11 grid_h  12 grid_w  13 offset of its first window in soft_attn  14, 15 0
+ *               images before it  9 win_h  10 win_w  11 grid_h  12 grid_w  13 offset of its first window in soft_attn  14 flag word
+ *               of a view (read by segclip_seg_label_map_views alone; 0 here)  15 0
  *               Windows, tables and the window list (image, y0, x0) are as above, but the window size and grid are per image.
  *   n_blocks  : the sum of ceil(oh * ow / 1024) over all images;  max_image_windows: the largest window count of an image
  *               (sizes the LDS; 1 = no image has overlapping windows)
@@ -490,6 +491,55 @@ int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t soft_floats, 
                                    int ignore_index, int reduce_zero_label, int64_t* areas, void* stream);
 int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index, int reduce_zero_label,
                       int64_t* areas, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Flip and multi-scale test-time augmentation (segment_aug.inc): mmseg's MultiScaleFlipAug + EncoderDecoder.aug_test, the
+ * wrapper of every test configuration of the reference (seg_segmentation/configs/_base_/datasets/pascal_voc12.py:24-26,
+ * evaluation/builder.py:121-123): every view is segmented, its logits are resized to the original size and passed through a
+ * soft-max, flipped back, the probabilities are averaged over the views and the arg-max is taken.  ONE launch for a list of
+ * images of mixed sizes; no (C, oh, ow), (C, H, W) or per-view probability array exists.
+ *
+ * segclip_seg_label_map_views: the arguments of segclip_seg_label_map_rescaled, except that `images` holds one row PER VIEW
+ * (the view's own network size, windows, window size, grid and soft_attn offset; column 14 = flag word, bit 0 horizontal flip,
+ * bit 1 vertical flip) and `views` groups them:
+ *   views   : (B, 2) int64 rows on the device: 0 the image's first row of `images` (its views are consecutive rows)  1 V
+ *   images  : (n_rows, 16); columns 4-8 (oh, ow, label offset, ground-truth offset, first workgroup) are the IMAGE's and are
+ *             read from its first view's row; every view row must state the same (oh, ow)
+ *   Output pixel (y, x) of an image with output size (oh, ow):
+ *   1. per view v in list order the source position (y', x') = (y, x) mirrored in (oh, ow) along each flagged axis (mmseg flips
+ *      the probability map back at the original size, after the resize and the soft-max);
+ *   2. at (y', x') the view's class logits exactly as segclip_seg_label_map_rescaled defines them: same device functions, the
+ *      four-tap fp32 blend h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) at every pixel, a tap of weight 0 not evaluated;
+ *   3. p_v = soft-max over the N + with_bg classes in fp32: maximum subtracted, expf, divided by the sum (class order);
+ *   4. the sum over the views in view order divided by (float)V; its first maximum is the label, one byte.
+ *   labels / gt / areas / ignore_index / reduce_zero_label: as in segclip_seg_label_map_rescaled (dword stores at label offsets
+ *   that are multiples of 4; per-workgroup counters in LDS).  best_class is not needed: the entry takes best_score only.
+ *   Limits.  SEGCLIP_ERR_UNSUPPORTED: N + with_bg > 256; max_views > 16; max_image_windows > 64, where
+ *   max_image_windows = the largest number of windows of one image over ALL its views, max_view_windows = the largest of one
+ *   view (1 = no view has overlapping windows: one list slot per tap), max_views = the largest V.  The device-side lists are
+ *   not inspected by the host entry: a view's windows beyond 64, an image's windows beyond 64 over its views and covering windows
+ *   beyond 16 are SILENTLY IGNORED - the caller checks (segclip_amd/ops.py seg_view_tables, segmentation.py).  Every row of
+ *   both tables is range-checked on the device: an image whose view row is outside `images`, whose V is outside 1..16 or
+ *   above the stated max_views (the (maximum, sum) slots in LDS are sized by it), or one of whose views is inconsistent (sizes, another (oh, ow), soft_floats, labels_bytes, gt_bytes) is SKIPPED.
+ *   LDS: up to 96 KiB dynamic - the covering-window lists, a table copy, and per-lane accumulators acc[class][lane]; when the
+ *   classes do not fit (C KiB) they are walked in chunks and every view's (maximum, sum) is kept from the first walk.
+ *   Bound: ALU - about 3 V C logit evaluations (1-4 LDS reads each) and V C expf per output pixel; design figure, unmeasured.
+ *
+ * segclip_seg_view_probs: the dense twin for ONE image (views has one row): probs (N + with_bg, oh, ow) fp32 = the mean of step
+ * 4, by the same kernel body, so the label above is its first maximum over the classes by construction.  An inconsistent
+ * table or probs_floats < C * oh * ow: nothing is written.  Bound: HBM writes, 4 C bytes per pixel, beside the same ALU work.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_label_map_views(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
+                                const int64_t* views, int64_t n_windows, int64_t B, int64_t n_blocks, int64_t max_image_windows,
+                                int64_t max_view_windows, int64_t max_views, int64_t G, int64_t N, int with_bg, float bg_thresh,
+                                uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes, int ignore_index,
+                                int reduce_zero_label, int64_t* areas, void* stream);
+int segclip_seg_view_probs(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                           const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
+                           const int64_t* views, int64_t n_windows, int64_t n_blocks, int64_t max_image_windows,
+                           int64_t max_view_windows, int64_t max_views, int64_t G, int64_t N, int with_bg, float bg_thresh,
+                           float* probs, int64_t probs_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Front end of the zero-shot evaluation (segment_frontend.inc): decoded uint8 images -> the vision tower's input windows in ONE
@@ -517,6 +567,15 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
 int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
                                 int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
                                 void* stream);
+
+/* The front end for flipped views (MultiScaleFlipAug's RandomFlip after its Resize): segclip_seg_windows_from_u8 with (B, 7)
+ * rows - the six columns above and 6 = flag word.  With bit 0 window pixel (Y, X) reads the resized image at (Y, W - 1 - X),
+ * with bit 1 at (H - 1 - Y, X); the resize geometry is the unflipped image's.  A multi-scale view needs nothing here: it is the
+ * same source address with another (H, W).  Same kernel body (the coordinates are exact integers however they are reached):
+ * flags 0 give the entry above bit for bit.  One row per view: an image with V views has V rows.  Same checks, limits and bound. */
+int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
+                                     int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Rendering of segmentation results (segment_render.inc): what the reference's demo draws, for images of mixed sizes in ONE

@@ -167,8 +167,13 @@ SIGNATURES = {
                                      vp, vp]),
     "segclip_seg_label_map_rescaled": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                                  vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_label_map_views": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                              vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_view_probs": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                         vp, i64, vp]),
     "segclip_seg_areas": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_seg_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
+    "segclip_seg_view_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
     "segclip_seg_groups_rescaled": (C.c_int, [vp, i64, vp, i64, i64, i64, vp, i64, vp]),
     "segclip_seg_blend": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, C.c_int, C.c_double, C.c_double, C.c_int, vp, i64, vp, vp]),
     "segclip_train_images_from_u8": (C.c_int, [vp, i64, i64, i64, vp, vp, vp]),

@@ -294,6 +294,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 }
 
 #include "segment_eval.inc"
+#include "segment_aug.inc"
 #include "segment_frontend.inc"
 #include "segment_render.inc"
 #include "train_frontend.inc"
@@ -432,6 +433,121 @@ extern "C" int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t so
   return 0;
 }
 
+// The launch of both view entries.  LDS: the covering-window lists of the four taps first, then the accumulators - every class
+// when they fit beside the table copy, otherwise chunks of classes with every view's (maximum, sum) kept beside them.  (The
+// kernel reads the global table when its windows' rows do not fit the copy.)
+static int seg_views_launch(const char* what, bool dense, SegViewsArgs& v, int64_t max_image_windows, int64_t max_view_windows,
+                            int64_t max_views, int64_t n_blocks, void* stream) {
+  SegEvalArgs& a = v.e;
+  const int64_t C = a.N + a.with_bg;
+  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
+  a.cover_slots = max_view_windows > 1 ? SEG_MAX_COVER : 1;  // no view has two windows: no pixel has two covering windows
+  const int64_t cov_bytes = (int64_t)4 * a.cover_slots * 256 * 2;
+  int64_t want = per_image * a.G * a.N;
+  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
+  want = (want + 1) & ~1ll;
+  int64_t left = SEG_AUG_LDS_BYTES - cov_bytes;
+  v.acc_classes = (int)C; v.ms_views = 0; v.max_views = (int)max_views;
+  if (C * 1024 + want * 4 > left) {
+    v.ms_views = (int)max_views;
+    left -= max_views * 2 * 1024;
+    const int64_t ch = (left - want * 4) / 1024;  // >= 16: 96 KiB less 32 of lists, 32 of (maximum, sum), 16 of tables
+    v.acc_classes = (int)(ch < C ? ch : C);
+  }
+  a.tab_floats = (int)want;
+  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)v.acc_classes * 1024 + (size_t)v.ms_views * 2048 + (size_t)cov_bytes;
+  SEGCLIP_REQUIRE(v.acc_classes >= 1 && lds <= SEG_AUG_LDS_BYTES, "%s: internal LDS plan of %lld bytes", what, (long long)lds);
+  static std::atomic<bool> raised[2][64];
+  int dev = 0;
+  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: cannot query the current device", what);
+  const void* fn = dense ? reinterpret_cast<const void*>(seg_views_kernel<true>) : reinterpret_cast<const void*>(seg_views_kernel<false>);
+  if (!raised[dense][dev]) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SEG_AUG_LDS_BYTES);
+    SEGCLIP_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
+    raised[dense][dev] = true;
+  }
+  if (dense) hipLaunchKernelGGL(seg_views_kernel<true>, dim3((unsigned)n_blocks), dim3(256), lds, ST, v);
+  else hipLaunchKernelGGL(seg_views_kernel<false>, dim3((unsigned)n_blocks), dim3(256), lds, ST, v);
+  SEGCLIP_CHECK_LAUNCH(what);
+  return 0;
+}
+
+static int seg_views_check(const char* what, int64_t soft_floats, int64_t n_rows, int64_t n_windows, int64_t B, int64_t n_blocks,
+                           int64_t max_image_windows, int64_t max_view_windows, int64_t max_views, int64_t G, int64_t N, int with_bg) {
+  SEGCLIP_REQUIRE(B >= 0 && n_rows >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0,
+                  "%s: sizes must not be negative, N >= 1", what);
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_rows <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
+  if (N + (with_bg ? 1 : 0) > SEG_MAX_CLASSES) {
+    segclip_set_error("%s: %lld classes, at most %d", what, (long long)(N + (with_bg ? 1 : 0)), SEG_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_views < 1 || max_views > SEG_MAX_VIEWS) {
+    segclip_set_error("%s: %lld views of an image, 1..%d supported", what, (long long)max_views, SEG_MAX_VIEWS);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_image_windows > SEG_MAX_IMG_WIN) {
+    segclip_set_error("%s: %lld windows over all views of an image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  SEGCLIP_REQUIRE(max_view_windows <= max_image_windows, "%s: %lld windows in one view but %lld over all views of an image", what,
+                  (long long)max_view_windows, (long long)max_image_windows);
+  return 0;
+}
+
+static SegViewsArgs seg_views_args(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                   const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
+                                   const int64_t* views, int64_t n_windows, int64_t B, int64_t G, int64_t N, int with_bg, float bg_thresh) {
+  SegViewsArgs v;
+  SegEvalArgs& a = v.e;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = nullptr; a.best_score = best_score;
+  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = 0; a.gt_bytes = 0;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
+  a.labels = nullptr; a.gt = nullptr; a.ignore_index = 255; a.reduce_zero = 0; a.areas = nullptr;
+  v.views = views; v.n_rows = (int)n_rows; v.probs = nullptr; v.probs_floats = 0;
+  return v;
+}
+
+extern "C" int segclip_seg_label_map_views(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                           const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
+                                           const int64_t* views, int64_t n_windows, int64_t B, int64_t n_blocks,
+                                           int64_t max_image_windows, int64_t max_view_windows, int64_t max_views, int64_t G,
+                                           int64_t N, int with_bg, float bg_thresh, uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes,
+                                           int ignore_index, int reduce_zero_label, int64_t* areas, void* stream) {
+  const char* what = "seg_label_map_views";
+  if (int rc = seg_views_check(what, soft_floats, n_rows, n_windows, B, n_blocks, max_image_windows, max_view_windows, max_views, G, N,
+                               with_bg))
+    return rc;
+  SEGCLIP_REQUIRE(labels_bytes >= 0 && gt_bytes >= 0, "%s: sizes must not be negative", what);
+  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
+  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
+  if (B == 0 || n_blocks == 0 || n_rows == 0) return 0;
+  SEGCLIP_REQUIRE(soft_attn && table && table_max && best_score && windows && images && views, "%s: the tables are required", what);
+  SegViewsArgs v = seg_views_args(soft_attn, soft_floats, table, table_max, best_score, windows, images, n_rows, views, n_windows, B, G, N,
+                                  with_bg, bg_thresh);
+  v.e.labels = labels; v.e.labels_bytes = labels_bytes; v.e.gt = gt; v.e.gt_bytes = gt_bytes; v.e.ignore_index = ignore_index;
+  v.e.reduce_zero = reduce_zero_label ? 1 : 0; v.e.areas = reinterpret_cast<unsigned long long*>(areas);
+  return seg_views_launch(what, false, v, max_image_windows, max_view_windows, max_views, n_blocks, stream);
+}
+
+extern "C" int segclip_seg_view_probs(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                      const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
+                                      const int64_t* views, int64_t n_windows, int64_t n_blocks, int64_t max_image_windows,
+                                      int64_t max_view_windows, int64_t max_views, int64_t G, int64_t N, int with_bg, float bg_thresh, float* probs,
+                                      int64_t probs_floats, void* stream) {
+  const char* what = "seg_view_probs";
+  if (int rc = seg_views_check(what, soft_floats, n_rows, n_windows, 1, n_blocks, max_image_windows, max_view_windows, max_views, G, N,
+                               with_bg))
+    return rc;
+  SEGCLIP_REQUIRE(probs && probs_floats >= 0, "%s: probs is required", what);
+  if (n_blocks == 0 || n_rows == 0) return 0;
+  SEGCLIP_REQUIRE(soft_attn && table && table_max && best_score && windows && images && views, "%s: the tables are required", what);
+  SegViewsArgs v = seg_views_args(soft_attn, soft_floats, table, table_max, best_score, windows, images, n_rows, views, n_windows, 1, G, N,
+                                  with_bg, bg_thresh);
+  v.probs = probs; v.probs_floats = probs_floats;
+  return seg_views_launch(what, true, v, max_image_windows, max_view_windows, max_views, n_blocks, stream);
+}
+
 extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index, int reduce_zero_label,
                                  int64_t* areas, void* stream) {
   SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "seg_areas: need 0 <= n <= 2^40 and C >= 1");
@@ -448,31 +564,44 @@ extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t
   return 0;
 }
 
-extern "C" int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
-                                           int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
-                                           void* stream) {
+// views: the (B, 7) table with a flag word per row and the kernel that mirrors (segment_frontend.inc)
+static int seg_front_launch(const char* what, bool views, const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
+                            int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out, void* stream) {
   const int64_t lim = 1ll << 31;
-  SEGCLIP_REQUIRE(n_windows >= 0 && n_windows <= (1 << 24) && B >= 0 && B <= (1 << 24) && win_h >= 1 && win_w >= 1, "seg_windows_from_u8: sizes out of range");
-  SEGCLIP_REQUIRE(mean && inv_std, "seg_windows_from_u8: mean and inv_std are required");
+  SEGCLIP_REQUIRE(n_windows >= 0 && n_windows <= (1 << 24) && B >= 0 && B <= (1 << 24) && win_h >= 1 && win_w >= 1, "%s: sizes out of range", what);
+  SEGCLIP_REQUIRE(mean && inv_std, "%s: mean and inv_std are required", what);
   if (win_h >= lim || win_w >= lim || win_h * win_w >= lim) {
-    segclip_set_error("seg_windows_from_u8: a window of %lld x %lld pixels, fewer than 2^31 supported", (long long)win_h, (long long)win_w);
+    segclip_set_error("%s: a window of %lld x %lld pixels, fewer than 2^31 supported", what, (long long)win_h, (long long)win_w);
     return SEGCLIP_ERR_UNSUPPORTED;
   }
   if (n_windows == 0) return 0;
-  SEGCLIP_REQUIRE(windows && out && (images || B == 0), "seg_windows_from_u8: images, windows and out are required");
+  SEGCLIP_REQUIRE(windows && out && (images || B == 0), "%s: images, windows and out are required", what);
   SegFrontArgs a;
   a.images = images; a.windows = windows; a.out = out;
   a.B = (int)B; a.win_h = (int)win_h; a.win_w = (int)win_w; a.upr = (int)cdiv(win_w, SEG_FE_PPL);
   const int64_t per_window = cdiv(win_h * a.upr, 256);
-  SEGCLIP_REQUIRE(n_windows * per_window < lim, "seg_windows_from_u8: %lld windows of %lld x %lld pixels exceed one launch",
+  SEGCLIP_REQUIRE(n_windows * per_window < lim, "%s: %lld windows of %lld x %lld pixels exceed one launch", what,
                   (long long)n_windows, (long long)win_h, (long long)win_w);
   a.blocks_per_window = (int)per_window;
   a.reverse = reverse_channels ? 1 : 0;
   a.vec = (win_w % SEG_FE_PPL == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.inv_std[c] = inv_std[c]; }
-  hipLaunchKernelGGL(seg_front_kernel, dim3((unsigned)(n_windows * per_window)), dim3(256), 0, ST, a);
-  SEGCLIP_CHECK_LAUNCH("seg_windows_from_u8");
+  if (views) hipLaunchKernelGGL(seg_front_kernel<true>, dim3((unsigned)(n_windows * per_window)), dim3(256), 0, ST, a);
+  else hipLaunchKernelGGL(seg_front_kernel<false>, dim3((unsigned)(n_windows * per_window)), dim3(256), 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH(what);
   return 0;
+}
+
+extern "C" int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
+                                           int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
+                                           void* stream) {
+  return seg_front_launch("seg_windows_from_u8", false, images, windows, n_windows, B, win_h, win_w, mean, inv_std, reverse_channels, out, stream);
+}
+
+extern "C" int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B,
+                                                int64_t win_h, int64_t win_w, const float* mean, const float* inv_std,
+                                                int reverse_channels, float* out, void* stream) {
+  return seg_front_launch("seg_view_windows_from_u8", true, images, windows, n_windows, B, win_h, win_w, mean, inv_std, reverse_channels, out, stream);
 }
 
 extern "C" int segclip_seg_groups_rescaled(const float* soft_attn, int64_t soft_floats, const int64_t* images, int64_t B,

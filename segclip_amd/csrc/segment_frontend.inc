@@ -12,12 +12,13 @@
 // of an evaluation call, so the simple form stays (DESIGN.md section 8 names the next step).
 
 #define SEG_FE_COLS 6    // int64 columns of one image row of the source table (segclip_hip.h)
+#define SEG_FE_VIEW_COLS 7  // ... of the view entry's table: the same row and a flag word (bit 0 horizontal, bit 1 vertical flip)
 #define SEG_FE_PPL 4     // consecutive window pixels of a lane: one 16-byte store per channel
 #define SEG_FE_LIMIT (1 << 15)
-enum { FE_SRC, FE_H, FE_W, FE_STRIDE, FE_NET_H, FE_NET_W };
+enum { FE_SRC, FE_H, FE_W, FE_STRIDE, FE_NET_H, FE_NET_W, FE_FLAGS };
 
 struct SegFrontArgs {
-  const int64_t* images;   // (B, SEG_FE_COLS)
+  const int64_t* images;   // (B, SEG_FE_COLS), or (B, SEG_FE_VIEW_COLS) for the view kernel
   const int32_t* windows;  // (n_windows, 3): image, y0, x0
   float* out;              // (n_windows, 3, win_h, win_w)
   int B, win_h, win_w, upr, blocks_per_window, reverse, vec;
@@ -53,6 +54,10 @@ __device__ __forceinline__ float seg_fe_blend(float a, float b, float c, float d
 // A lane owns SEG_FE_PPL consecutive pixels of one window row, a workgroup 256 consecutive such units of one window; a wave
 // stores 1 KiB of consecutive floats per channel.  Every table entry is range-checked here (the host entry cannot inspect
 // device memory): a window that fails is zero-filled, and a source byte is read only inside the (h, w) the row states.
+// VIEWS: the rows carry a flag word, and window pixel (Y, X) of a flipped view reads the resized image at (Y, W - 1 - X) and /
+// or (H - 1 - Y, X): mmseg flips after the resize, so the geometry is the unflipped image's.  The coordinates are exact
+// integers whichever way they are reached: flags 0 give the bytes of the plain kernel.
+template <bool VIEWS>
 __global__ __launch_bounds__(256) void seg_front_kernel(SegFrontArgs A) {
   const int tid = threadIdx.x;
   const int64_t k = blockIdx.x / A.blocks_per_window;
@@ -65,9 +70,10 @@ __global__ __launch_bounds__(256) void seg_front_kernel(SegFrontArgs A) {
   bool ok = img >= 0 && img < A.B;
   const uint8_t* src = nullptr;
   int64_t stride = 0;
-  int h = 1, w = 1, H = 1, W = 1;
+  int h = 1, w = 1, H = 1, W = 1, flags = 0;
   if (ok) {
-    const int64_t* D = A.images + (int64_t)img * SEG_FE_COLS;
+    const int64_t* D = A.images + (int64_t)img * (VIEWS ? SEG_FE_VIEW_COLS : SEG_FE_COLS);
+    if (VIEWS) flags = (int)(D[FE_FLAGS] & 3);
     const int64_t h64 = D[FE_H], w64 = D[FE_W], H64 = D[FE_NET_H], W64 = D[FE_NET_W];
     src = reinterpret_cast<const uint8_t*>(D[FE_SRC]);
     stride = D[FE_STRIDE];
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(256) void seg_front_kernel(SegFrontArgs A) {
   if (ok) {  // block-uniform
     int qy, ry, ya, yb, qx, rx;
     float fy;
-    seg_fe_coord(y0 + y, h, H, qy, ry);
+    seg_fe_coord((flags & 2) ? H - 1 - (y0 + y) : y0 + y, h, H, qy, ry);
     seg_fe_taps(qy, ry, h, H, ya, yb, fy);
     const uint8_t* ra = src + (int64_t)ya * stride;
     const uint8_t* rb = src + (int64_t)yb * stride;
@@ -96,6 +102,7 @@ __global__ __launch_bounds__(256) void seg_front_kernel(SegFrontArgs A) {
       if (xq + p < A.win_w) {
         int xa, xb;
         float fx;
+        if (flags & 1) seg_fe_coord(W - 1 - (x0 + xq + p), w, W, qx, rx);
         seg_fe_taps(qx, rx, w, W, xa, xb, fx);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {

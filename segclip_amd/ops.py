@@ -2459,6 +2459,106 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     return labels
 
 
+SEG_MAX_VIEWS = 16         # views of one image in segclip_seg_label_map_views
+SEG_MAX_IMAGE_WINDOWS = 64  # windows of one image, over all its views
+SEG_FLIP_H, SEG_FLIP_V = 1, 2
+
+
+def seg_view_tables(rows, view_counts, device):
+    """The device tables of seg_label_map_views / seg_view_probs.  rows: one dict per view as seg_image_table takes them, plus
+    flags (SEG_FLIP_H | SEG_FLIP_V), the views of an image consecutive; view_counts: the number of views of every image.
+    Every view row carries its image's output size, label offset (a multiple of 4), ground-truth offset and first workgroup.
+    -> (image table (R, 16) int64, view table (B, 2) int64, label offsets per image, labels_bytes, n_blocks,
+        most windows of an image over its views, most windows of a view, most views)."""
+    if sum(view_counts) != len(rows):
+        raise ValueError(f"seg_view_tables: {len(rows)} view rows but the view counts sum to {sum(view_counts)}")
+    tab, vtab, offs, lab, blk, r0 = [], [], [], 0, 0, 0
+    most_img = most_view = 0
+    for i, V in enumerate(view_counts):
+        if not 1 <= V <= SEG_MAX_VIEWS:
+            raise ValueError(f"image {i}: {V} views, 1 .. {SEG_MAX_VIEWS} supported")
+        mine = rows[r0:r0 + V]
+        oh, ow = mine[0]["out"]
+        for v, r in enumerate(mine):
+            (H, W), (wh, ww), (gh, gw) = r["net"], r["win"], r["grid"]
+            if min(H, W, oh, ow, wh, ww, gh, gw) < 1 or r["count"] < 1:
+                raise ValueError(f"seg_view_tables: sizes must be positive, got {r}")
+            if tuple(r["out"]) != (oh, ow):
+                raise ValueError(f"image {i} view {v}: output size {tuple(r['out'])}, its first view has {(oh, ow)}")
+            flags = int(r.get("flags", 0))
+            if flags not in (0, 1, 2, 3):
+                raise ValueError(f"image {i} view {v}: flags {flags}, bit 0 = horizontal flip and bit 1 = vertical flip")
+            tab.append([r["first"], r["count"], H, W, oh, ow, lab, mine[0].get("gt_off", -1), blk, wh, ww, gh, gw, r["soft_off"], flags, 0])
+            most_view = max(most_view, r["count"])
+        n_win = sum(r["count"] for r in mine)
+        if n_win > SEG_MAX_IMAGE_WINDOWS:
+            raise ValueError(f"image {i}: {n_win} windows over its {V} views, at most {SEG_MAX_IMAGE_WINDOWS} supported")
+        most_img = max(most_img, n_win)
+        vtab.append([r0, V])
+        offs.append(lab)
+        lab += (oh * ow + 3) // 4 * 4
+        blk += (oh * ow + SEG_EVAL_TILE - 1) // SEG_EVAL_TILE
+        r0 += V
+    return (torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_IMAGE_COLS),
+            torch.tensor(vtab, dtype=torch.int64, device=device).view(-1, 2), offs, lab, blk, most_img, most_view, max(view_counts))
+
+
+def _seg_views_args(what, soft_attn, tables, windows, images, views):
+    table, tmax, _, bsc = tables
+    L.require_cuda(soft_attn, table, tmax, bsc, windows, images, views)
+    nW, G, N = table.shape
+    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
+            or images.dtype != torch.int64 or views.dtype != torch.int64:
+        raise TypeError(f"{what}: fp32 soft_attn / tables, int32 window list, int64 image and view tables")
+    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or views.dim() != 2 \
+            or views.shape[1] != 2 or tmax.numel() != nW or bsc.numel() != nW * G:
+        raise ValueError(f"{what}: shapes do not agree")
+    return tuple(t.contiguous() for t in (soft_attn, table, tmax, bsc, windows, images, views)), (nW, G, N)
+
+
+def seg_label_map_views(soft_attn, tables, windows, images, views, n_blocks, max_image_windows, max_view_windows, max_views, with_bg,
+                        bg_thresh, labels=None, gt=None, areas=None, ignore_index=255, reduce_zero_label=False):
+    """The fused multi-view kernel (segclip_seg_label_map_views): as seg_label_map_rescaled with the tables of
+    seg_view_tables - per view the rescaled class logits at the mirrored position, their soft-max, the mean over an image's
+    views, its first maximum -> `labels` (flat uint8, or None) and, with `gt`, the (3, C) int64 `areas` added to in place."""
+    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_views_args("seg_label_map_views", soft_attn, tables, windows, images, views)
+    L.require_cuda(labels, gt, areas)
+    for name, t in (("labels", labels), ("gt", gt)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"seg_label_map_views: {name} is a contiguous uint8 tensor")
+    if (gt is None) != (areas is None):
+        raise ValueError("seg_label_map_views: gt and areas go together")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous()
+                              or tuple(areas.shape) != (3, N + int(bool(with_bg)))):
+        raise ValueError("seg_label_map_views: areas is a contiguous (3, N + with_bg) int64 tensor")
+    L.check(L.load().segclip_seg_label_map_views(
+        L.ptr(soft), soft.numel(), L.ptr(table), L.ptr(tmax), L.ptr(bsc), L.ptr(win), L.ptr(img), img.shape[0], L.ptr(vws), nW,
+        vws.shape[0], int(n_blocks), int(max_image_windows), int(max_view_windows), int(max_views), G, N, int(bool(with_bg)),
+        float(bg_thresh), L.ptr(labels), labels.numel() if labels is not None else 0, L.ptr(gt), gt.numel() if gt is not None else 0,
+        int(ignore_index), int(bool(reduce_zero_label)), L.ptr(areas), L.stream()), "seg_label_map_views")
+    return labels
+
+
+def seg_view_probs(soft_attn, tables, windows, images, views, n_blocks, max_image_windows, max_view_windows, max_views, with_bg,
+                   bg_thresh, out_size, out=None):
+    """The dense twin (segclip_seg_view_probs) for ONE image: (N + with_bg, oh, ow) fp32, the mean over its views of the
+    soft-max of the rescaled class logits, by the device functions of seg_label_map_views (whose label is its first maximum)."""
+    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_views_args("seg_view_probs", soft_attn, tables, windows, images, views)
+    if vws.shape[0] != 1:
+        raise ValueError(f"seg_view_probs: one image per call, got a view table of {vws.shape[0]}")
+    shape = (N + int(bool(with_bg)), int(out_size[0]), int(out_size[1]))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=soft.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != shape[0] * shape[1] * shape[2]:
+        raise ValueError("seg_view_probs: out is a contiguous fp32 tensor of (N + with_bg) * oh * ow elements")
+    L.require_cuda(out)
+    L.check(L.load().segclip_seg_view_probs(
+        L.ptr(soft), soft.numel(), L.ptr(table), L.ptr(tmax), L.ptr(bsc), L.ptr(win), L.ptr(img), img.shape[0], L.ptr(vws), nW,
+        int(n_blocks), int(max_image_windows), int(max_view_windows), int(max_views), G, N, int(bool(with_bg)), float(bg_thresh),
+        L.ptr(out), out.numel(), L.stream()), "seg_view_probs")
+    return out
+
+
 def seg_areas(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, areas=None):
     """mmseg's intersect_and_union of uint8 label maps (segclip_seg_areas): -> (3, C) int64 = intersection, prediction area,
     label area per class; added to `areas` when given."""
@@ -2504,6 +2604,25 @@ def seg_source_table(raws, net_sizes):
     return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_SOURCE_COLS)
 
 
+def seg_view_source_table(raws, net_sizes, flags):
+    """The source table of seg_view_windows_from_u8: seg_source_table's rows and a flag word per row (SEG_FLIP_H | SEG_FLIP_V)
+    -> (B, 7) int64.  One row per view: an image with several views appears once per view in `raws`."""
+    if len(flags) != len(raws) or any(int(f) not in (0, 1, 2, 3) for f in flags):
+        raise ValueError("seg_view_windows_from_u8: one flag word of 0 .. 3 per source row")
+    base = seg_source_table(raws, net_sizes)
+    return torch.cat([base, torch.tensor([int(f) for f in flags], dtype=torch.int64, device=base.device)[:, None]], dim=1).contiguous()
+
+
+def seg_view_windows_from_u8(raws, net_sizes, flags, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
+    """seg_windows_from_u8 for flipped views (segclip_seg_view_windows_from_u8): window pixel (Y, X) of a row with the
+    horizontal flag reads the resized image at (Y, W - 1 - X), with the vertical flag at (H - 1 - Y, X) - mmseg's flip after
+    the resize.  Flags 0 give seg_windows_from_u8's output bit for bit.  table: seg_view_source_table(raws, net_sizes, flags)."""
+    if table is None:
+        table = seg_view_source_table(raws, net_sizes, flags)
+    return _seg_windows_launch("segclip_seg_view_windows_from_u8", SEG_SOURCE_COLS + 1, len(raws), table, windows, win_size, mean,
+                               inv_std, reverse_channels, out)
+
+
 def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
     """The fused front end (segclip_seg_windows_from_u8): decoded uint8 images -> (n_windows, 3, win_h, win_w) fp32, every
     window pixel resized bilinearly (cv2 INTER_LINEAR geometry) from its image to the image's network size and normalised as
@@ -2512,8 +2631,13 @@ def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, rever
     net_sizes) when the caller launches several times on the same images."""
     if table is None:
         table = seg_source_table(raws, net_sizes)
-    elif table.dtype != torch.int64 or tuple(table.shape) != (len(raws), SEG_SOURCE_COLS) or not table.is_contiguous():
-        raise ValueError("seg_windows_from_u8: table is the (B, 6) int64 tensor of seg_source_table")
+    return _seg_windows_launch("segclip_seg_windows_from_u8", SEG_SOURCE_COLS, len(raws), table, windows, win_size, mean, inv_std,
+                               reverse_channels, out)
+
+
+def _seg_windows_launch(entry, cols, n_rows, table, windows, win_size, mean, inv_std, reverse_channels, out):
+    if table.dtype != torch.int64 or tuple(table.shape) != (n_rows, cols) or not table.is_contiguous():
+        raise ValueError(f"seg_windows_from_u8: table is the (B, {cols}) int64 tensor of seg_source_table")
     if not torch.is_tensor(windows):
         windows = torch.tensor(windows, dtype=torch.int32, device=table.device).view(-1, 3)
     L.require_cuda(table, windows, out)
@@ -2529,8 +2653,8 @@ def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, rever
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * 3 * wh * ww:
         raise ValueError("seg_windows_from_u8: out is a contiguous fp32 tensor of n_windows * 3 * win_h * win_w elements")
     f3 = L.f32 * 3
-    L.check(L.load().segclip_seg_windows_from_u8(L.ptr(table), L.ptr(windows), n, table.shape[0], wh, ww, f3(*mean), f3(*inv_std),
-                                                 int(bool(reverse_channels)), L.ptr(out), L.stream()), "seg_windows_from_u8")
+    L.check(getattr(L.load(), entry)(L.ptr(table), L.ptr(windows), n, table.shape[0], wh, ww, f3(*mean), f3(*inv_std),
+                                     int(bool(reverse_channels)), L.ptr(out), L.stream()), "seg_windows_from_u8")
     return out
 
 

@@ -22,8 +22,15 @@ groups_raw write the group map at each picture's size, and render_raw serves the
 vision tower (csrc/segment_render.inc).  Encoding the pictures, the palette-mode PNG of vis_mode="pred" and the label text
 stay with the caller.
 
-Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; here the arg-max is taken of the
-logits, which can differ only where fp32 exp rounds two different logits to one value.  A ground-truth value of 255 stays
+Test-time augmentation (mmseg's MultiScaleFlipAug + aug_test, the wrapper of every test configuration of the reference):
+TestAug lists an image's views, predict_raw / update_raw / eval_epoch take aug=, predict_views / update_views take tensors
+that are already pre-processed and flipped, and predict_proba_* return the mean probabilities.  Every (image, view) pair is
+an entry of the list plan, so the windows of all views share the tower calls, and one kernel (csrc/segment_aug.inc) rescales
+every view's logits, takes their soft-max, mirrors, averages and takes the first maximum per output pixel.
+
+Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; without augmentation the arg-max
+is taken of the logits here, which can differ only where fp32 exp rounds two different logits to one value (the augmented
+path takes the soft-max mmseg takes: the mean over views needs it).  A ground-truth value of 255 stays
 ignored whatever reduce_zero_label says.  The resized pixel is kept in fp32 and not rounded back to uint8 as cv2's 8-bit
 fixed-point resize does: about one grey level, 0.015 in normalised units (unmeasured: cv2 is not a dependency).  The overlay
 is drawn on the decoded image itself, where the reference draws on a de-normalised copy of the network input resized back
@@ -154,6 +161,99 @@ class _RawImages:
 
     def windows(self, chunk, dwin, wh, ww):
         return _raw_windows(self.raws, self.transform, self.sizes, self.table, dwin, wh, ww)
+
+
+class TestAug:
+    """mmseg's MultiScaleFlipAug(img_ratios, flip, flip_direction): the views of one image, in mmseg's order."""
+
+    __test__ = False   # a product class, not a test
+
+    def __init__(self, img_ratios=(1.0,), flip=False, flip_direction="horizontal"):
+        ratios = [float(r) for r in ([img_ratios] if isinstance(img_ratios, (int, float)) else img_ratios)]
+        if len(ratios) == 0:
+            raise ValueError("TestAug: empty ratio list")
+        if any(not r > 0.0 for r in ratios):
+            raise ValueError(f"TestAug: ratios are positive, got {ratios}")
+        if flip_direction not in ("horizontal", "vertical"):   # one direction: a list of them is not taken
+            raise ValueError(f"TestAug: flip_direction is 'horizontal' or 'vertical', got {flip_direction!r}")
+        self.img_ratios, self.flip, self.flip_direction = tuple(ratios), bool(flip), flip_direction
+
+    def views(self, h, w, transform):
+        """[(H, W, flags)] of an (h, w) image: for each ratio the unflipped view, then with flip the flipped one.  (H, W) is
+        the keep-ratio test size at (int(s0 * r), int(s1 * r)) of the transform's img_scale; flags: ops.SEG_FLIP_H / _V."""
+        out = []
+        for r in self.img_ratios:
+            H, W = test_size(h, w, (int(transform.img_scale[0] * r), int(transform.img_scale[1] * r)))
+            out.append((H, W, 0))
+            if self.flip:
+                out.append((H, W, ops.SEG_FLIP_H if self.flip_direction == "horizontal" else ops.SEG_FLIP_V))
+        return out
+
+
+class _Views:
+    """Bookkeeping of the (image, view) entries of a list plan: entry e = view e - first[i] of image i."""
+
+    def _set_views(self, counts):
+        self.view_counts = counts
+        self.owner = [(i, v) for i, n in enumerate(counts) for v in range(n)]
+
+    def name(self, e):
+        return "image %d view %d" % self.owner[e]
+
+
+class _SlicedViews(_Views):
+    """The tower input from views already resized, normalised and flipped (what mmseg hands to aug_test)."""
+
+    def __init__(self, model, views):
+        if len(views) == 0:
+            raise ValueError("empty image list")
+        self.imgs, self.flags = [], []
+        for i, per in enumerate(views):
+            if len(per) == 0:
+                raise ValueError(f"image {i}: no views")
+            for v, (t, flags) in enumerate(per):
+                _require_eval_gpu(model, t)
+                if t.dim() != 3 or t.shape[0] != 3:
+                    raise ValueError(f"image {i} view {v}: a view is a (3, H, W) tensor, got {tuple(t.shape)}")
+                if int(flags) not in (0, 1, 2, 3):
+                    raise ValueError(f"image {i} view {v}: flags {flags}, bit 0 = horizontal flip and bit 1 = vertical flip")
+                self.imgs.append(t)
+                self.flags.append(int(flags))
+        self._set_views([len(per) for per in views])
+        self.device = self.imgs[0].device
+        self.sizes = [(int(t.shape[1]), int(t.shape[2])) for t in self.imgs]
+        self.default_out = None
+
+    def windows(self, chunk, dwin, wh, ww):
+        return torch.stack([self.imgs[e][:, y:y + wh, x0:x0 + ww] for (e, y, x0) in chunk])
+
+
+class _RawViews(_Views):
+    """The tower input from decoded uint8 images and an augmentation: the view kernel of the front end resizes, normalises
+    and mirrors a chunk's windows; neither a resized nor a flipped image exists."""
+
+    def __init__(self, model, raws, transform, aug, net_sizes):
+        if not isinstance(aug, TestAug):
+            raise TypeError("aug is a TestAug")
+        _raw_sizes(raws, transform, None)
+        _require_eval_gpu(model, raws[0])
+        lists = [aug.views(int(t.shape[0]), int(t.shape[1]), transform) for t in raws]
+        if net_sizes is not None:   # per image one (H, W) per view, in the order of aug.views
+            if len(net_sizes) != len(raws) or any(len(a) != len(b) for a, b in zip(net_sizes, lists)):
+                raise ValueError("with aug, net_sizes holds one (H, W) per view of every image")
+            lists = [[(int(H), int(W), f) for (H, W), (_, _, f) in zip(a, b)] for a, b in zip(net_sizes, lists)]
+        self._set_views([len(per) for per in lists])
+        self.sizes = [(H, W) for per in lists for (H, W, _) in per]
+        self.flags = [f for per in lists for (_, _, f) in per]
+        self.raws = [raws[i] for i, _ in self.owner]
+        self.transform, self.device = transform, raws[0].device
+        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
+        self.table = ops.seg_view_source_table(self.raws, self.sizes, self.flags)
+
+    def windows(self, chunk, dwin, wh, ww):
+        t = self.transform
+        return ops.seg_view_windows_from_u8(self.raws, self.sizes, self.flags, dwin, (wh, ww), t.mean, t.inv_std,
+                                            reverse_channels=t.channel_order == "bgr", table=self.table)
 
 
 def _require_eval_gpu(model, t):
@@ -305,32 +405,18 @@ class SegInference:
             n += len(members)
         return batches, per_image
 
-    def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
-                      groups=None):
-        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows.
-        groups: None, "also" (-> (labels, group maps, G), both at out_shapes, from the same pass of the tower) or "only"
-        (-> (None, group maps, G): no class tables, no label map)."""
-        sizes, n_img = src.sizes, len(src.sizes)
-        if out_shapes is None:
-            out_shapes = src.default_out
-        if len(out_shapes) != n_img:
-            raise ValueError(f"{n_img} images but {len(out_shapes)} output shapes")
-        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
-        classes = groups != "only"
-        if classes and self.num_classes > 256:
-            raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
+    def _list_towers(self, src, classes=True, plan=None):
+        """The tower part of a list call: every window of the plan (_list_plan(src.sizes) unless the caller has it) through
+        encode_image (max_windows at a time) and, with `classes`, segclip_seg_group_table.  -> (flat soft_attn, tables, device
+        window list, per-entry (first window, window count, win size), a window's offset in soft_attn, group count)."""
+        name = getattr(src, "name", None)
         p = self.model.clip.visual.patch_size
-        batches, per_image = self._list_plan(sizes)
-        if groups is not None:
-            for i, (_, count, _) in enumerate(per_image):
-                if count != 1:
-                    raise ValueError(f"group maps are defined for one window per image: image {i} ({sizes[i][0]}x{sizes[i][1]}) "
-                                     f"has {count} windows in slide mode")
+        batches, per_image = self._list_plan(src.sizes) if plan is None else plan
         N = self.text_embedding.shape[0]
         dev = src.device
-        for (wh, ww), _ in batches:
+        for (wh, ww), wins in batches:
             if wh % p or ww % p:
-                raise ValueError(f"window {wh}x{ww} is not a multiple of the patch size {p}")
+                raise ValueError((f"{name(wins[0][0])}: " if name else "") + f"window {wh}x{ww} is not a multiple of the patch size {p}")
         wins_all = [w for _, wins in batches for w in wins]
         dwin = torch.tensor(wins_all, dtype=torch.int32, device=dev).view(-1, 3)
         parts, done, win_off, floats = [], 0, [], 0   # win_off: a window's offset in the flat soft_attn
@@ -341,7 +427,8 @@ class SegInference:
                 with config.scope(cross_mode="intended"):   # see _windows_forward
                     feat, hidden, mid = self.model.clip.encode_image(x, return_hidden=True)
                 if not mid["attns"]:
-                    raise ValueError(f"window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x or 4x the "
+                    raise ValueError((f"{name(chunk[0][0])}: " if name else "") +
+                                     f"window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x or 4x the "
                                      "training token count (modules/module_seg_vit.py:423)")
                 soft = mid["attns"][-1]["soft_attn"]
                 del mid, x
@@ -358,6 +445,31 @@ class SegInference:
         else:
             cat = [torch.cat([q[i] for q in parts]) for i in range(len(parts[0]))]
             soft, tables = cat[0], tuple(cat[1:])
+        return soft, tables, dwin, per_image, win_off, n_groups
+
+    def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
+                      groups=None):
+        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows.
+        groups: None, "also" (-> (labels, group maps, G), both at out_shapes, from the same pass of the tower) or "only"
+        (-> (None, group maps, G): no class tables, no label map)."""
+        sizes, n_img = src.sizes, len(src.sizes)
+        if out_shapes is None:
+            out_shapes = src.default_out
+        if len(out_shapes) != n_img:
+            raise ValueError(f"{n_img} images but {len(out_shapes)} output shapes")
+        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
+        classes = groups != "only"
+        if classes and self.num_classes > 256:
+            raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
+        p = self.model.clip.visual.patch_size
+        plan = self._list_plan(sizes)
+        if groups is not None:
+            for i, (_, count, _) in enumerate(plan[1]):
+                if count != 1:
+                    raise ValueError(f"group maps are defined for one window per image: image {i} ({sizes[i][0]}x{sizes[i][1]}) "
+                                     f"has {count} windows in slide mode")
+        dev = src.device
+        soft, tables, dwin, per_image, win_off, n_groups = self._list_towers(src, classes, plan)
         rows, gt_off = [], 0
         for i, (first, count, (wh, ww)) in enumerate(per_image):
             rows.append(dict(first=first, count=count, net=sizes[i], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
@@ -383,6 +495,68 @@ class SegInference:
         gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=dev))
         return labels, views(gmaps), n_groups
 
+    def _views_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
+                       dense=False):
+        """The augmented list call.  src: _SlicedViews or _RawViews - one plan entry per (image, view) pair, so the windows of
+        all views share the tower calls of _list_towers; segclip_seg_label_map_views takes the place of the rescaled kernel.
+        dense: -> the (C, oh, ow) fp32 mean probabilities of the single image instead of labels."""
+        counts, n_img = src.view_counts, len(src.view_counts)
+        if out_shapes is None:
+            out_shapes = src.default_out
+        if out_shapes is None or len(out_shapes) != n_img:
+            raise ValueError(f"{n_img} images but {0 if out_shapes is None else len(out_shapes)} output shapes")
+        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
+        if self.num_classes > 256:
+            raise ops.L.Unsupported(f"{self.num_classes} classes: the multi-view kernel holds at most 256")
+        if dense and n_img != 1:
+            raise ValueError(f"the dense probabilities are formed for one image per call, got {n_img}")
+        p = self.model.clip.visual.patch_size
+        base = self.model.clip.visual.transformer.patch_len ** 2   # tokens of the training resolution
+        # what a single view already requires, and the limits of the kernel's device-side lists (what exceeds them would be
+        # silently ignored), before anything runs
+        e0 = 0
+        for i, V in enumerate(counts):
+            if V > ops.SEG_MAX_VIEWS:
+                raise ValueError(f"image {i}: {V} views, at most {ops.SEG_MAX_VIEWS} supported")
+            n_win = 0
+            for e in range(e0, e0 + V):
+                try:
+                    _, count, (wh, ww) = self._list_plan([src.sizes[e]])[1][0]
+                except ValueError as err:
+                    raise ValueError(f"{src.name(e)}: {err}") from None
+                if wh % p or ww % p:
+                    raise ValueError(f"{src.name(e)}: window {wh}x{ww} is not a multiple of the patch size {p}")
+                if (wh // p) * (ww // p) not in (base, 4 * base):
+                    raise ValueError(f"{src.name(e)}: window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x "
+                                     f"or 4x the training token count ({base}; modules/module_seg_vit.py:423)")
+                n_win += count
+            if n_win > ops.SEG_MAX_IMAGE_WINDOWS:
+                raise ValueError(f"image {i}: {n_win} windows over its {V} views, at most {ops.SEG_MAX_IMAGE_WINDOWS} supported")
+            e0 += V
+        dev = src.device
+        soft, tables, dwin, per_entry, win_off, _ = self._list_towers(src)
+        rows, gt_off, e = [], 0, 0
+        for i, V in enumerate(counts):
+            for _ in range(V):
+                first, count, (wh, ww) = per_entry[e]
+                rows.append(dict(first=first, count=count, net=src.sizes[e], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
+                                 soft_off=win_off[first], gt_off=gt_off if gts is not None else -1, flags=src.flags[e]))
+                e += 1
+            gt_off += out_shapes[i][0] * out_shapes[i][1]
+        images, vtab, offs, nbytes, n_blocks, most_img, most_view, most_v = ops.seg_view_tables(rows, counts, dev)
+        if dense:
+            return ops.seg_view_probs(soft, tables, dwin, images, vtab, n_blocks, most_img, most_view, most_v, self.with_bg,
+                                      self.bg_thresh, out_shapes[0])
+        labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
+        gt = None
+        if gts is not None:
+            gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
+        ops.seg_label_map_views(soft, tables, dwin, images, vtab, n_blocks, most_img, most_view, most_v, self.with_bg, self.bg_thresh,
+                                labels=labels, gt=gt, areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+        if not want_labels:
+            return None
+        return [labels[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
     @torch.no_grad()
     def predict_list(self, imgs, out_shapes=None):
         """[(3, H_i, W_i)] of any mix of sizes -> [(oh_i, ow_i) uint8 labels], views of one flat buffer; out_shapes defaults
@@ -392,12 +566,37 @@ class SegInference:
         return self._list_forward(_SlicedImages(self.model, imgs), out_shapes)
 
     @torch.no_grad()
-    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None):
+    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None):
         """[(h_i, w_i, 3) uint8 decoded images] -> [(oh_i, ow_i) uint8 labels] as predict_list(preprocess(raws, transform,
         net_sizes), out_shapes), bit for bit, without the resized images: the windows of a tower call are written from the
         raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
-        ori_shape); net_sizes overrides transform.net_size (whole mode needs multiples of the patch size)."""
+        ori_shape); net_sizes overrides transform.net_size (whole mode needs multiples of the patch size).
+        aug (a TestAug): mmseg's aug_test over the views of aug.views - every view segmented, its logits rescaled to the output
+        size and passed through a soft-max, flipped back, the probabilities averaged over the views, first maximum.  net_sizes
+        then holds one (H, W) per view of every image."""
+        if aug is not None:
+            return self._views_forward(_RawViews(self.model, raws, transform, aug, net_sizes), out_shapes)
         return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes)
+
+    @torch.no_grad()
+    def predict_views(self, views, out_shapes):
+        """views[i] = [((3, H, W) tensor, flags)]: the views of image i, pre-processed and ALREADY FLIPPED as mmseg hands imgs
+        and img_metas to aug_test (flags: ops.SEG_FLIP_H | ops.SEG_FLIP_V, what img_metas' flip / flip_direction say)
+        -> [(oh_i, ow_i) uint8 labels] of the mean probabilities, as predict_raw(aug=)."""
+        return self._views_forward(_SlicedViews(self.model, views), out_shapes)
+
+    @torch.no_grad()
+    def predict_proba_views(self, views, out_shape):
+        """The views [((3, H, W) tensor, flags)] of ONE image -> (N + with_bg, oh, ow) fp32: the mean over the views of the
+        soft-max of the rescaled logits, what aug_test takes the arg-max of (predict_views' label is its first maximum)."""
+        return self._views_forward(_SlicedViews(self.model, [views]), [out_shape], dense=True)
+
+    @torch.no_grad()
+    def predict_proba_raw(self, raw, transform, aug=None, out_shape=None, net_sizes=None):
+        """predict_proba_views from ONE decoded (h, w, 3) uint8 image; aug defaults to the single unflipped view, out_shape to
+        the image's own size."""
+        src = _RawViews(self.model, [raw], transform, TestAug() if aug is None else aug, None if net_sizes is None else [net_sizes])
+        return self._views_forward(src, None if out_shape is None else [out_shape], dense=True)
 
     # ------------------------------------------------------------------------------------------ the demo's outputs
     @torch.no_grad()
@@ -581,10 +780,18 @@ class SegEvaluator:
         return self._forward(_SlicedImages(self.seg.model, imgs), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None):
-        """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw."""
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None):
+        """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included)."""
         self._check_gts(raws, gts)
+        if aug is not None:
+            return self._forward(_RawViews(self.seg.model, raws, transform, aug, net_sizes), gts, return_labels, views=True)
         return self._forward(_RawImages(self.seg.model, raws, transform, net_sizes), gts, return_labels)
+
+    @torch.no_grad()
+    def update_views(self, views, gts, return_labels=False):
+        """views[i] = [((3, H, W) tensor, flags)] as SegInference.predict_views, scored at each ground truth's size."""
+        self._check_gts(views, gts)
+        return self._forward(_SlicedViews(self.seg.model, views), gts, return_labels, views=True)
 
     @staticmethod
     def _check_gts(imgs, gts):
@@ -596,10 +803,10 @@ class SegEvaluator:
             if g.dtype != torch.uint8 or g.dim() != 2:
                 raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
 
-    def _forward(self, src, gts, return_labels):
-        return self.seg._list_forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
-                                      ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
-                                      want_labels=return_labels)
+    def _forward(self, src, gts, return_labels, views=False):
+        forward = self.seg._views_forward if views else self.seg._list_forward
+        return forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas, ignore_index=self.ignore_index,
+                       reduce_zero_label=self.reduce_zero_label, want_labels=return_labels)
 
     @staticmethod
     def metrics_from_areas(areas):

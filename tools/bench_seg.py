@@ -18,7 +18,16 @@ With --raw instead: the same 64 images as decoded uint8 (h, w, 3) tensors, in ON
         copy, F.interpolate, normalise; then the slices); the front-end kernel's own time from a separate
         `rocprofv3 --kernel-trace --stats` child (--raw-child: five update_raw calls and nothing else) and its bytes per second
         against the HBM peak.
-usage: python tools/bench_seg.py [--eval | --raw] [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt]"""
+With --aug instead: the same 64 decoded images under test-time augmentation, TestAug(img_ratios=(1.0, 1.5), flip=True) = four
+views per image, in ONE command and alternating within every repeat:
+  (vi)  images/s of SegEvaluator.update_raw(aug=) (every window of every view through shared tower calls, then one
+        segclip_seg_label_map_views launch) and of the eager composition from this library's public pieces (preprocess per view;
+        per image and view a flip, encode_decode at batch 1, F.interpolate to the ground truth's size, soft-max, flip back, sum;
+        arg-max of the mean; three histc), the areas of the two, peak allocation, and the multi-view kernel's and the view front
+        end's own time from a separate `rocprofv3 --kernel-trace --stats` child (--aug-child: five update_raw(aug=) calls and
+        nothing else).
+usage: python tools/bench_seg.py [--eval | --raw | --aug] [reps=7]
+                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt]"""
 import os
 import statistics
 import sys
@@ -34,10 +43,12 @@ from segclip_amd.segmentation import SegInference
 from tools.clock_sampler import ClockSampler
 
 EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("--raw-child" in sys.argv[1:])
-ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child")]
+AUG, AUG_CHILD = ("--aug" in sys.argv[1:]), ("--aug-child" in sys.argv[1:])
+ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_frontend.txt" if RAW else "seg_eval.txt" if EVAL else "seg_infer.txt")
+                                                 "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
 
@@ -314,6 +325,116 @@ def raw_child(model, text):
     torch.cuda.synchronize()
 
 
+AUG_RATIOS = (1.0, 1.5)   # 375 x 500 -> views of 224 x 299 (2 windows) and 336 x 448 (4 windows), each unflipped and flipped
+
+
+def aug_case(model, text, n_images=64):
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator, TestAug, preprocess, slide_windows
+    from tools import rocprof_roofline as rr
+    name = f"(vi) aug    {n_images} mixed sizes"
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    C = seg.num_classes
+    tf, aug = ImageTransform(), TestAug(img_ratios=AUG_RATIOS, flip=True)
+    raws, gts = raw_inputs(seg, n_images)
+    ev = SegEvaluator(seg)
+    views = [aug.views(int(r.shape[0]), int(r.shape[1]), tf) for r in raws]
+    V = len(views[0])
+    n_win = sum(len(slide_windows(H, W, (224, 224), (224, 224))) for per in views for (H, W, _) in per)
+    pixels = sum(int(g.numel()) for g in gts)
+
+    def eager():
+        """What a user writes today: mmseg's aug_test from preprocess, encode_decode and eager torch."""
+        areas = torch.zeros(3, C, device="cuda")
+        nets = [preprocess(raws, tf, net_sizes=[per[v][:2] for per in views]) for v in range(V)]
+        for i, gt in enumerate(gts):
+            total = None
+            for v in range(V):
+                flags = views[i][v][2]
+                dims = [d for d, bit in ((2, ops.SEG_FLIP_H), (1, ops.SEG_FLIP_V)) if flags & bit]   # of a (3, H, W) image
+                x = nets[v][i].flip(dims) if dims else nets[v][i]
+                logits = seg.encode_decode(x[None])
+                p = F.softmax(F.interpolate(logits, size=tuple(gt.shape), mode="bilinear", align_corners=False), dim=1)
+                if dims:
+                    p = p.flip([d + 1 for d in dims])
+                total = p if total is None else total + p
+            pred = (total / V).argmax(dim=1)[0]
+            keep = gt != 255
+            q, t = pred[keep].float(), gt[keep].float()
+            areas[0] += torch.histc(q[q == t], bins=C, min=0, max=C - 1)
+            areas[1] += torch.histc(q, bins=C, min=0, max=C - 1)
+            areas[2] += torch.histc(t, bins=C, min=0, max=C - 1)
+        return areas
+
+    def fused():
+        ev.update_raw(raws, gts, tf, aug=aug)
+
+    ways = [("update_raw(aug=)", fused, 2), ("eager composition", eager, 1)]   # (what, call, calls per timed repeat)
+    with torch.no_grad():
+        ev.reset()
+        fused()
+        a_fused = ev.areas.clone()
+        a_eager = eager()
+        fused()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):   # alternating: every repeat times the two ways one after the other
+            for k, (_, fn, inner) in enumerate(ways):
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: {V} views per image (ratios {AUG_RATIOS} x flip), {n_win} windows, {pixels} output pixels, {C} classes")
+    meds = [statistics.median(t) for t in ts]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:18s} {med * 1e3:9.2f} ms (min {min(t) * 1e3:.2f}, max {max(t) * 1e3:.2f}; {REPS} x {inner} calls)  "
+            f"{n_images / med:8.1f} images/s")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts)
+    say(f"{name}: update_raw(aug=) / eager composition {meds[0] / meds[1]:.4f}; largest run-to-run spread {spread:.4f} of the median; "
+        f"clock {clk}")
+    same = float((a_fused.double() - a_eager.double()).abs().sum() / a_eager.double().sum())
+    say(f"{name}: areas of the two differ by {same:.2e} of their sum (fp32 accumulation order and ATen's fp32 coordinates)")
+    say(f"{name}: peak allocation of one call: update_raw(aug=) {peak_of(fused) / 2**20:8.1f} MiB, the eager composition "
+        f"{peak_of(eager) / 2**20:8.1f} MiB")
+    # the kernels' own time: a child of this tool that only calls update_raw(aug=), under rocprofv3 --kernel-trace --stats
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--aug-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    total_us = sum(r[2] for r in table)
+    for what, pat in (("segclip_seg_label_map_views", "seg_views_kernel"), ("segclip_seg_view_windows_from_u8", "seg_front_kernel")):
+        rows = [r for r in table if pat in r[0]]
+        if not rows:
+            say(f"{name}: {what} alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+            continue
+        calls, us = sum(r[1] for r in rows), sum(r[2] for r in rows)
+        line = (f"{name}: {what} alone (rocprofv3 --kernel-trace --stats, {calls} launches) {us / calls:9.1f} us per launch, "
+                f"{us / total_us:.4f} of the child's kernel time")
+        if pat == "seg_views_kernel":
+            avg = us / calls
+            line += (f"; {avg * 1e-6 / meds[0]:.4f} of update_raw(aug=); {pixels / avg / 1e3:.3f} Gpixel/s = {avg * 1e3 / (pixels * V * C):.3f} ns "
+                     f"per (pixel, view, class)")
+        say(line)
+
+
+def aug_child(model, text):
+    """Five update_raw(aug=) calls and nothing else: what the rocprofv3 child of aug_case traces."""
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator, TestAug
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    raws, gts = raw_inputs(seg)
+    ev = SegEvaluator(seg)
+    with torch.no_grad():
+        for _ in range(5):
+            ev.update_raw(raws, gts, ImageTransform(), aug=TestAug(img_ratios=AUG_RATIOS, flip=True))
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -325,7 +446,12 @@ if __name__ == "__main__":
     if RAW_CHILD:
         raw_child(model, text)
         sys.exit(0)
-    if RAW:
+    if AUG_CHILD:
+        aug_child(model, text)
+        sys.exit(0)
+    if AUG:
+        aug_case(model, text)
+    elif RAW:
         raw_case(model, text)
     elif EVAL:
         eval_case(model, text)
