@@ -2411,21 +2411,40 @@ SEG_IMAGE_COLS = 16   # int64 columns of one row of the image table of segclip_s
 SEG_EVAL_TILE = 1024  # output pixels of one of its workgroups
 
 
+def _seg_image_row(what, r, out, label_off, gt_off, first_block, flags=0):
+    """One row of the 16-column image table: of an image (seg_image_table) or of one of its views (seg_view_tables), which
+    carries its image's output size, label offset, ground-truth offset and first workgroup."""
+    (H, W), (oh, ow), (wh, ww), (gh, gw) = r["net"], out, r["win"], r["grid"]
+    if min(H, W, oh, ow, wh, ww, gh, gw) < 1 or r["count"] < 1:
+        raise ValueError(f"{what}: sizes must be positive, got {r}")
+    return [r["first"], r["count"], H, W, oh, ow, label_off, gt_off, first_block, wh, ww, gh, gw, r["soft_off"], flags, 0]
+
+
 def seg_image_table(rows, device):
     """The device descriptor table of seg_label_map_rescaled from per-image dicts(first, count, net=(H, W), out=(oh, ow),
     win=(win_h, win_w), grid=(gh, gw), soft_off[, gt_off]).  Label offsets are assigned here, each a multiple of 4.
     -> (table (B, 16) int64, label offsets, labels_bytes, n_blocks, max windows of an image)."""
     tab, offs, lab, blk, most = [], [], 0, 0, 0
     for r in rows:
-        (H, W), (oh, ow), (wh, ww), (gh, gw) = r["net"], r["out"], r["win"], r["grid"]
-        if min(H, W, oh, ow, wh, ww, gh, gw) < 1 or r["count"] < 1:
-            raise ValueError(f"seg_image_table: sizes must be positive, got {r}")
-        tab.append([r["first"], r["count"], H, W, oh, ow, lab, r.get("gt_off", -1), blk, wh, ww, gh, gw, r["soft_off"], 0, 0])
+        oh, ow = r["out"]
+        tab.append(_seg_image_row("seg_image_table", r, (oh, ow), lab, r.get("gt_off", -1), blk))
         offs.append(lab)
         lab += (oh * ow + 3) // 4 * 4
         blk += (oh * ow + SEG_EVAL_TILE - 1) // SEG_EVAL_TILE
         most = max(most, r["count"])
     return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_IMAGE_COLS), offs, lab, blk, most
+
+
+def _seg_check_outputs(what, labels, gt, areas, n_classes):
+    """`labels` / `gt` / `areas` of the two fused label-map kernels."""
+    L.require_cuda(labels, gt, areas)
+    for name, t in (("labels", labels), ("gt", gt)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} is a contiguous uint8 tensor")
+    if (gt is None) != (areas is None):
+        raise ValueError(f"{what}: gt and areas go together")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (3, n_classes)):
+        raise ValueError(f"{what}: areas is a contiguous (3, N + with_bg) int64 tensor")
 
 
 def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_image_windows, with_bg, bg_thresh, labels=None,
@@ -2434,7 +2453,7 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     window list + the image table -> `labels` (flat uint8, or None) at every image's output size and, with `gt` (flat uint8),
     the (3, C) int64 `areas` added to in place."""
     table, tmax, bcls, bsc = tables
-    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images, labels, gt, areas)
+    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images)
     nW, G, N = table.shape
     if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
             or images.dtype != torch.int64 or bcls.dtype != torch.int32:
@@ -2442,14 +2461,7 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
             or bcls.numel() != nW * G or bsc.numel() != nW * G:
         raise ValueError("seg_label_map_rescaled: shapes do not agree")
-    for name, t in (("labels", labels), ("gt", gt)):
-        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
-            raise ValueError(f"seg_label_map_rescaled: {name} is a contiguous uint8 tensor")
-    if (gt is None) != (areas is None):
-        raise ValueError("seg_label_map_rescaled: gt and areas go together")
-    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous()
-                              or tuple(areas.shape) != (3, N + int(bool(with_bg)))):
-        raise ValueError("seg_label_map_rescaled: areas is a contiguous (3, N + with_bg) int64 tensor")
+    _seg_check_outputs("seg_label_map_rescaled", labels, gt, areas, N + int(bool(with_bg)))
     keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, images))
     L.check(L.load().segclip_seg_label_map_rescaled(
         L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
@@ -2480,15 +2492,12 @@ def seg_view_tables(rows, view_counts, device):
         mine = rows[r0:r0 + V]
         oh, ow = mine[0]["out"]
         for v, r in enumerate(mine):
-            (H, W), (wh, ww), (gh, gw) = r["net"], r["win"], r["grid"]
-            if min(H, W, oh, ow, wh, ww, gh, gw) < 1 or r["count"] < 1:
-                raise ValueError(f"seg_view_tables: sizes must be positive, got {r}")
             if tuple(r["out"]) != (oh, ow):
                 raise ValueError(f"image {i} view {v}: output size {tuple(r['out'])}, its first view has {(oh, ow)}")
             flags = int(r.get("flags", 0))
             if flags not in (0, 1, 2, 3):
                 raise ValueError(f"image {i} view {v}: flags {flags}, bit 0 = horizontal flip and bit 1 = vertical flip")
-            tab.append([r["first"], r["count"], H, W, oh, ow, lab, mine[0].get("gt_off", -1), blk, wh, ww, gh, gw, r["soft_off"], flags, 0])
+            tab.append(_seg_image_row("seg_view_tables", r, (oh, ow), lab, mine[0].get("gt_off", -1), blk, flags))
             most_view = max(most_view, r["count"])
         n_win = sum(r["count"] for r in mine)
         if n_win > SEG_MAX_IMAGE_WINDOWS:
@@ -2522,15 +2531,7 @@ def seg_label_map_views(soft_attn, tables, windows, images, views, n_blocks, max
     seg_view_tables - per view the rescaled class logits at the mirrored position, their soft-max, the mean over an image's
     views, its first maximum -> `labels` (flat uint8, or None) and, with `gt`, the (3, C) int64 `areas` added to in place."""
     (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_views_args("seg_label_map_views", soft_attn, tables, windows, images, views)
-    L.require_cuda(labels, gt, areas)
-    for name, t in (("labels", labels), ("gt", gt)):
-        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
-            raise ValueError(f"seg_label_map_views: {name} is a contiguous uint8 tensor")
-    if (gt is None) != (areas is None):
-        raise ValueError("seg_label_map_views: gt and areas go together")
-    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous()
-                              or tuple(areas.shape) != (3, N + int(bool(with_bg)))):
-        raise ValueError("seg_label_map_views: areas is a contiguous (3, N + with_bg) int64 tensor")
+    _seg_check_outputs("seg_label_map_views", labels, gt, areas, N + int(bool(with_bg)))
     L.check(L.load().segclip_seg_label_map_views(
         L.ptr(soft), soft.numel(), L.ptr(table), L.ptr(tmax), L.ptr(bsc), L.ptr(win), L.ptr(img), img.shape[0], L.ptr(vws), nW,
         vws.shape[0], int(n_blocks), int(max_image_windows), int(max_view_windows), int(max_views), G, N, int(bool(with_bg)),
@@ -2579,15 +2580,16 @@ SEG_SOURCE_COLS = 6         # int64 columns of one row of the source table of se
 SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 
 
-def seg_source_table(raws, net_sizes):
-    """The device source table of seg_windows_from_u8: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows
-    possibly strided], net_sizes [(H, W)] -> (B, 6) int64.  It holds the tensors' addresses: keep `raws` alive while it is
-    in use."""
+def _seg_source_table(raws, net_sizes, flags=None):
+    """The source table of both front-end kernels: a row per source image, with a seventh column of flag words for the view
+    kernel."""
     if len(raws) == 0 or len(raws) != len(net_sizes):
         raise ValueError(f"seg_source_table: {len(raws)} images but {len(net_sizes)} network sizes")
+    if flags is not None and (len(flags) != len(raws) or any(int(f) not in (0, 1, 2, 3) for f in flags)):
+        raise ValueError("seg_view_windows_from_u8: one flag word of 0 .. 3 per source row")
     L.require_cuda(*raws)
     tab = []
-    for t, (H, W) in zip(raws, net_sizes):
+    for k, (t, (H, W)) in enumerate(zip(raws, net_sizes)):
         if t.dtype != torch.uint8:
             raise TypeError(f"seg_windows_from_u8: a source image is uint8, got {t.dtype}")
         if t.dim() != 3 or t.shape[2] != 3:
@@ -2600,27 +2602,28 @@ def seg_source_table(raws, net_sizes):
         if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
             raise ValueError(f"seg_windows_from_u8: a source image has interleaved channels and contiguous pixels (strides "
                              f"(>= 3 w, 3, 1)), got {tuple(t.stride())}")
-        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(H), int(W)])
-    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_SOURCE_COLS)
+        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(H), int(W)] + ([] if flags is None else [int(flags[k])]))
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(len(tab), -1)
+
+
+def seg_source_table(raws, net_sizes):
+    """The device source table of seg_windows_from_u8: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows
+    possibly strided], net_sizes [(H, W)] -> (B, 6) int64.  It holds the tensors' addresses: keep `raws` alive while it is
+    in use."""
+    return _seg_source_table(raws, net_sizes)
 
 
 def seg_view_source_table(raws, net_sizes, flags):
     """The source table of seg_view_windows_from_u8: seg_source_table's rows and a flag word per row (SEG_FLIP_H | SEG_FLIP_V)
     -> (B, 7) int64.  One row per view: an image with several views appears once per view in `raws`."""
-    if len(flags) != len(raws) or any(int(f) not in (0, 1, 2, 3) for f in flags):
-        raise ValueError("seg_view_windows_from_u8: one flag word of 0 .. 3 per source row")
-    base = seg_source_table(raws, net_sizes)
-    return torch.cat([base, torch.tensor([int(f) for f in flags], dtype=torch.int64, device=base.device)[:, None]], dim=1).contiguous()
+    return _seg_source_table(raws, net_sizes, flags)
 
 
 def seg_view_windows_from_u8(raws, net_sizes, flags, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
     """seg_windows_from_u8 for flipped views (segclip_seg_view_windows_from_u8): window pixel (Y, X) of a row with the
     horizontal flag reads the resized image at (Y, W - 1 - X), with the vertical flag at (H - 1 - Y, X) - mmseg's flip after
     the resize.  Flags 0 give seg_windows_from_u8's output bit for bit.  table: seg_view_source_table(raws, net_sizes, flags)."""
-    if table is None:
-        table = seg_view_source_table(raws, net_sizes, flags)
-    return _seg_windows_launch("segclip_seg_view_windows_from_u8", SEG_SOURCE_COLS + 1, len(raws), table, windows, win_size, mean,
-                               inv_std, reverse_channels, out)
+    return _seg_windows_launch(raws, net_sizes, flags, table, windows, win_size, mean, inv_std, reverse_channels, out)
 
 
 def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
@@ -2629,14 +2632,16 @@ def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, rever
     (r - mean[c]) * inv_std[c].  windows: (n_windows, 3) int32 device rows (image, y0, x0), or a list of them; a window outside
     its image's network size or with an image index outside the list is zero-filled.  table: seg_source_table(raws,
     net_sizes) when the caller launches several times on the same images."""
+    return _seg_windows_launch(raws, net_sizes, None, table, windows, win_size, mean, inv_std, reverse_channels, out)
+
+
+def _seg_windows_launch(raws, net_sizes, flags, table, windows, win_size, mean, inv_std, reverse_channels, out):
+    """flags None: the plain kernel on the (B, 6) table; a flag word per row: the view kernel on the (B, 7) one."""
+    entry, cols = ("segclip_seg_windows_from_u8", SEG_SOURCE_COLS) if flags is None else \
+        ("segclip_seg_view_windows_from_u8", SEG_SOURCE_COLS + 1)
     if table is None:
-        table = seg_source_table(raws, net_sizes)
-    return _seg_windows_launch("segclip_seg_windows_from_u8", SEG_SOURCE_COLS, len(raws), table, windows, win_size, mean, inv_std,
-                               reverse_channels, out)
-
-
-def _seg_windows_launch(entry, cols, n_rows, table, windows, win_size, mean, inv_std, reverse_channels, out):
-    if table.dtype != torch.int64 or tuple(table.shape) != (n_rows, cols) or not table.is_contiguous():
+        table = _seg_source_table(raws, net_sizes, flags)
+    if table.dtype != torch.int64 or tuple(table.shape) != (len(raws), cols) or not table.is_contiguous():
         raise ValueError(f"seg_windows_from_u8: table is the (B, {cols}) int64 tensor of seg_source_table")
     if not torch.is_tensor(windows):
         windows = torch.tensor(windows, dtype=torch.int32, device=table.device).view(-1, 3)

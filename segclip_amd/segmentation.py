@@ -25,8 +25,14 @@ stay with the caller.
 Test-time augmentation (mmseg's MultiScaleFlipAug + aug_test, the wrapper of every test configuration of the reference):
 TestAug lists an image's views, predict_raw / update_raw / eval_epoch take aug=, predict_views / update_views take tensors
 that are already pre-processed and flipped, and predict_proba_* return the mean probabilities.  Every (image, view) pair is
-an entry of the list plan, so the windows of all views share the tower calls, and one kernel (csrc/segment_aug.inc) rescales
+an entry of the plan, so the windows of all views share the tower calls, and one kernel (csrc/segment_aug.inc) rescales
 every view's logits, takes their soft-max, mirrors, averages and takes the first maximum per output pixel.
+
+The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
+no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
+SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
+image without augmentation is one view with flags 0.  _list_forward (arg-max of the logits, group maps) and _views_forward
+(soft-max mean, dense twin) are the two kernel calls over the same steps.
 
 Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; without augmentation the arg-max
 is taken of the logits here, which can differ only where fp32 exp rounds two different logits to one value (the augmented
@@ -36,8 +42,8 @@ fixed-point resize does: about one grey level, 0.015 in normalised units (unmeas
 is drawn on the decoded image itself, where the reference draws on a de-normalised copy of the network input resized back
 to the picture's size.  Text is not drawn: input_pred_label returns the anchor positions beside the overlay.
 """
+import collections
 import colorsys
-import math
 
 import torch
 
@@ -90,27 +96,175 @@ class ImageTransform:
         return test_size(h, w, self.img_scale)
 
 
-def _raw_sizes(raws, transform, net_sizes):
-    """Checks of a list of decoded images -> their network sizes [(H, W)]."""
-    if len(raws) == 0:
-        raise ValueError("empty image list")
-    if not isinstance(transform, ImageTransform):
-        raise TypeError("transform is an ImageTransform")
-    for t in raws:
-        if not t.is_cuda:
-            raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {t.device} tensor")
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-    if net_sizes is None:
-        return [transform.net_size(int(t.shape[0]), int(t.shape[1])) for t in raws]
-    if len(net_sizes) != len(raws):
-        raise ValueError(f"{len(raws)} images but {len(net_sizes)} network sizes")
-    return [(int(a), int(b)) for (a, b) in net_sizes]
+_Plan = collections.namedtuple("_Plan", "batches entries image_windows")
 
 
-def _raw_windows(raws, transform, sizes, table, dwin, wh, ww):
-    return ops.seg_windows_from_u8(raws, sizes, dwin, (wh, ww), transform.mean, transform.inv_std,
-                                   reverse_channels=transform.channel_order == "bgr", table=table)
+def _entry_name(view_counts, e):
+    """Entry e of a plan, for a message: the views of an image are consecutive entries."""
+    for i, n in enumerate(view_counts):
+        if e < n:
+            return f"image {i} view {e}"
+        e -= n
+
+
+def _plan_windows(mode, crop_size, stride, sizes, view_counts=None):
+    """The windows of a call, from sizes alone.  sizes[e] = (H, W) of entry e; image i owns view_counts[i] consecutive
+    entries, its views (one each unless given).  -> _Plan(batches [(win size, [(entry, y0, x0)])] in tower order, entries
+    [(first window, window count, win size)], image_windows [windows of an image over its views]).  Slide mode: one batch of
+    all windows; whole mode: one batch per distinct size, sizes and their entries in first-seen order.  What exceeds the
+    limits of the kernels' device-side lists would be silently ignored there, so it raises here, image and view named."""
+    counts = [1] * len(sizes) if view_counts is None else list(view_counts)
+    if sum(counts) != len(sizes):
+        raise ValueError(f"{len(sizes)} entries but the view counts sum to {sum(counts)}")
+    entries = [None] * len(sizes)
+    if mode == "slide":
+        crop, wins = tuple(crop_size), []
+        for e, (H, W) in enumerate(sizes):
+            try:
+                per = slide_windows(H, W, crop, stride)
+            except ValueError as err:
+                raise ValueError(f"{_entry_name(counts, e)}: {err}") from None
+            if len(per) > ops.SEG_MAX_IMAGE_WINDOWS:
+                raise ValueError(f"{_entry_name(counts, e)}: slide mode: {len(per)} windows, at most "
+                                 f"{ops.SEG_MAX_IMAGE_WINDOWS} supported")
+            entries[e] = (len(wins), len(per), crop)
+            wins += [(e, y, x) for (y, x) in per]
+        batches = [(crop, wins)]
+    else:
+        by_size = {}
+        for e, hw in enumerate(sizes):
+            by_size.setdefault(tuple(hw), []).append(e)
+        batches, n = [], 0
+        for hw, members in by_size.items():
+            for k, e in enumerate(members):
+                entries[e] = (n + k, 1, hw)
+            batches.append((hw, [(e, 0, 0) for e in members]))
+            n += len(members)
+    image_windows, e0 = [], 0
+    for i, V in enumerate(counts):
+        if V > ops.SEG_MAX_VIEWS:
+            raise ValueError(f"image {i}: {V} views, at most {ops.SEG_MAX_VIEWS} supported")
+        image_windows.append(sum(count for _, count, _ in entries[e0:e0 + V]))
+        if image_windows[i] > ops.SEG_MAX_IMAGE_WINDOWS:
+            raise ValueError(f"image {i}: {image_windows[i]} windows over its {V} views, at most {ops.SEG_MAX_IMAGE_WINDOWS} "
+                             "supported")
+        e0 += V
+    return _Plan(batches, entries, image_windows)
+
+
+def _check_tower_windows(plan, name, patch, base):
+    """What the vision tower requires of a plan's window sizes, before anything runs.  name(e): entry e for the message;
+    base: the tokens of the training resolution."""
+    for (wh, ww), wins in plan.batches:
+        if wh % patch or ww % patch:
+            raise ValueError(f"{name(wins[0][0])}: window {wh}x{ww} is not a multiple of the patch size {patch}")
+        if (wh // patch) * (ww // patch) not in (base, 4 * base):
+            raise ValueError(f"{name(wins[0][0])}: window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x "
+                             f"or 4x the training token count ({base}; modules/module_seg_vit.py:423)")
+
+
+class _Source:
+    """The tower input of a call, always view-shaped: image i has view_counts[i] consecutive entries, its views; sizes[e] is
+    the network size of entry e and flags[e] its flip word.  default_out: the output sizes when the caller names
+    none; augmented: the call takes mmseg's aug_test (_views_forward) - an image without augmentation is one view, flags 0.
+    windows(chunk, dwin, wh, ww): the (n, 3, wh, ww) tower input of a chunk of the plan's windows, dwin its device rows."""
+
+    augmented = False
+
+    def name(self, e):
+        return _entry_name(self.view_counts, e)
+
+
+class _BatchImages(_Source):
+    """A (B, 3, H, W) batch (predict, group_map, encode_decode).  Whole mode: a chunk is a run of images, so its input is a
+    view of the batch; slide mode: one slice per window."""
+
+    def __init__(self, img, whole):
+        ops.L.require_cuda(img)
+        B, _, H, W = img.shape
+        if B == 0:
+            raise ValueError("empty image batch")
+        self.img, self.whole, self.device = img, whole, img.device
+        self.sizes, self.flags, self.view_counts = [(int(H), int(W))] * B, [0] * B, [1] * B
+
+    def windows(self, chunk, dwin, wh, ww):
+        if self.whole:
+            return self.img[chunk[0][0]:chunk[-1][0] + 1]
+        return torch.stack([self.img[b, :, y:y + wh, x0:x0 + ww] for (b, y, x0) in chunk])
+
+
+class _SlicedImages(_Source):
+    """views[i] = [((3, H, W) tensor, flags)]: images already resized and normalised (predict_list: one view each, flags 0) or
+    views that are also flipped already (what mmseg hands to aug_test).  One slice per window."""
+
+    def __init__(self, views, augmented=False):
+        if len(views) == 0:
+            raise ValueError("empty image list")
+        self.imgs, self.flags = [], []
+        for i, per in enumerate(views):
+            if len(per) == 0:
+                raise ValueError(f"image {i}: no views")
+            for v, (t, flags) in enumerate(per):
+                ops.L.require_cuda(t)
+                if t.dim() != 3 or t.shape[0] != 3:
+                    raise ValueError(f"image {i} view {v}: a view is a (3, H, W) tensor, got {tuple(t.shape)}")
+                if int(flags) not in (0, 1, 2, 3):
+                    raise ValueError(f"image {i} view {v}: flags {flags}, bit 0 = horizontal flip and bit 1 = vertical flip")
+                self.imgs.append(t)
+                self.flags.append(int(flags))
+        self.view_counts = [len(per) for per in views]
+        self.augmented, self.device = augmented, self.imgs[0].device
+        self.sizes = [(int(t.shape[1]), int(t.shape[2])) for t in self.imgs]
+        self.default_out = None if augmented else self.sizes
+
+    def windows(self, chunk, dwin, wh, ww):
+        return torch.stack([self.imgs[e][:, y:y + wh, x0:x0 + ww] for (e, y, x0) in chunk])
+
+
+class _RawImages(_Source):
+    """Decoded (h, w, 3) uint8 images, one unflipped view each or with aug (a TestAug) its views: the front-end kernel resizes,
+    normalises and mirrors a chunk's windows; neither a resized nor a flipped image exists.  net_sizes overrides the network
+    sizes: one (H, W) per image, with aug one per view of every image in the order of aug.views."""
+
+    def __init__(self, raws, transform, net_sizes=None, aug=None):
+        if len(raws) == 0:
+            raise ValueError("empty image list")
+        if not isinstance(transform, ImageTransform):
+            raise TypeError("transform is an ImageTransform")
+        if aug is not None and not isinstance(aug, TestAug):
+            raise TypeError("aug is a TestAug")
+        ops.L.require_cuda(*raws)
+        for t in raws:
+            if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+                raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
+        if aug is None:
+            if net_sizes is not None and len(net_sizes) != len(raws):
+                raise ValueError(f"{len(raws)} images but {len(net_sizes)} network sizes")
+            lists = [[tuple(transform.net_size(h, w) if net_sizes is None else net_sizes[i]) + (0,)]
+                     for i, (h, w) in enumerate(self.default_out)]
+        else:
+            lists = [aug.views(h, w, transform) for (h, w) in self.default_out]
+            if net_sizes is not None:
+                if len(net_sizes) != len(raws) or any(len(a) != len(b) for a, b in zip(net_sizes, lists)):
+                    raise ValueError("with aug, net_sizes holds one (H, W) per view of every image")
+                lists = [[(H, W, f) for (H, W), (_, _, f) in zip(a, b)] for a, b in zip(net_sizes, lists)]
+        self.view_counts = [len(per) for per in lists]
+        self.sizes = [(int(H), int(W)) for per in lists for (H, W, _) in per]
+        self.flags = [f for per in lists for (_, _, f) in per]
+        self.raws = [t for t, per in zip(raws, lists) for _ in per]
+        self.transform, self.augmented, self.device = transform, aug is not None, raws[0].device
+        # no flipped view: the plain kernel and its table (the view kernel at flags 0 writes the same bits)
+        self.flipped = any(self.flags)
+        self.table = ops.seg_view_source_table(self.raws, self.sizes, self.flags) if self.flipped else \
+            ops.seg_source_table(self.raws, self.sizes)
+
+    def windows(self, chunk, dwin, wh, ww):
+        t = self.transform
+        kw = dict(reverse_channels=t.channel_order == "bgr", table=self.table)
+        if self.flipped:
+            return ops.seg_view_windows_from_u8(self.raws, self.sizes, self.flags, dwin, (wh, ww), t.mean, t.inv_std, **kw)
+        return ops.seg_windows_from_u8(self.raws, self.sizes, dwin, (wh, ww), t.mean, t.inv_std, **kw)
 
 
 @torch.no_grad()
@@ -118,49 +272,13 @@ def preprocess(raws, transform, net_sizes=None):
     """[(h_i, w_i, 3) uint8] -> [(3, H_i, W_i) fp32]: every image resized to its network size (transform.net_size, or
     net_sizes) and normalised, by the kernel of predict_raw with one whole-image window per image, one launch per distinct
     size.  predict_list on the result equals predict_raw on the raw images bit for bit; predict_raw does not form it."""
-    sizes = _raw_sizes(raws, transform, net_sizes)
-    table = ops.seg_source_table(raws, sizes)
-    by_size = {}
-    for i, hw in enumerate(sizes):
-        by_size.setdefault(hw, []).append(i)
+    src = _RawImages(raws, transform, net_sizes)
     out = [None] * len(raws)
-    for (H, W), members in by_size.items():
-        x = _raw_windows(raws, transform, sizes, table, [(i, 0, 0) for i in members], H, W)
-        for k, i in enumerate(members):
+    for (H, W), wins in _plan_windows("whole", None, None, src.sizes).batches:
+        x = src.windows(wins, wins, H, W)   # the window list as it is: the wrapper copies it to the device
+        for k, (i, _, _) in enumerate(wins):
             out[i] = x[k]
     return out
-
-
-class _SlicedImages:
-    """The tower input of _list_forward from images already resized and normalised: one slice per window."""
-
-    def __init__(self, model, imgs):
-        if len(imgs) == 0:
-            raise ValueError("empty image list")
-        for t in imgs:
-            _require_eval_gpu(model, t)
-            if t.dim() != 3 or t.shape[0] != 3:
-                raise ValueError(f"predict_list takes (3, H, W) images, got {tuple(t.shape)}")
-        self.imgs, self.device = imgs, imgs[0].device
-        self.sizes = [(int(t.shape[1]), int(t.shape[2])) for t in imgs]
-        self.default_out = self.sizes
-
-    def windows(self, chunk, dwin, wh, ww):
-        return torch.stack([self.imgs[i][:, y:y + wh, x0:x0 + ww] for (i, y, x0) in chunk])
-
-
-class _RawImages:
-    """The tower input of _list_forward from decoded uint8 images: the front-end kernel writes a chunk's windows."""
-
-    def __init__(self, model, raws, transform, net_sizes):
-        self.sizes = _raw_sizes(raws, transform, net_sizes)
-        _require_eval_gpu(model, raws[0])
-        self.raws, self.transform, self.device = raws, transform, raws[0].device
-        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
-        self.table = ops.seg_source_table(raws, self.sizes)
-
-    def windows(self, chunk, dwin, wh, ww):
-        return _raw_windows(self.raws, self.transform, self.sizes, self.table, dwin, wh, ww)
 
 
 class TestAug:
@@ -190,75 +308,28 @@ class TestAug:
         return out
 
 
-class _Views:
-    """Bookkeeping of the (image, view) entries of a list plan: entry e = view e - first[i] of image i."""
-
-    def _set_views(self, counts):
-        self.view_counts = counts
-        self.owner = [(i, v) for i, n in enumerate(counts) for v in range(n)]
-
-    def name(self, e):
-        return "image %d view %d" % self.owner[e]
-
-
-class _SlicedViews(_Views):
-    """The tower input from views already resized, normalised and flipped (what mmseg hands to aug_test)."""
-
-    def __init__(self, model, views):
-        if len(views) == 0:
-            raise ValueError("empty image list")
-        self.imgs, self.flags = [], []
-        for i, per in enumerate(views):
-            if len(per) == 0:
-                raise ValueError(f"image {i}: no views")
-            for v, (t, flags) in enumerate(per):
-                _require_eval_gpu(model, t)
-                if t.dim() != 3 or t.shape[0] != 3:
-                    raise ValueError(f"image {i} view {v}: a view is a (3, H, W) tensor, got {tuple(t.shape)}")
-                if int(flags) not in (0, 1, 2, 3):
-                    raise ValueError(f"image {i} view {v}: flags {flags}, bit 0 = horizontal flip and bit 1 = vertical flip")
-                self.imgs.append(t)
-                self.flags.append(int(flags))
-        self._set_views([len(per) for per in views])
-        self.device = self.imgs[0].device
-        self.sizes = [(int(t.shape[1]), int(t.shape[2])) for t in self.imgs]
-        self.default_out = None
-
-    def windows(self, chunk, dwin, wh, ww):
-        return torch.stack([self.imgs[e][:, y:y + wh, x0:x0 + ww] for (e, y, x0) in chunk])
+def _out_shapes(src, out_shapes):
+    """The output sizes of a list call, one per image: the caller's, or the source's default."""
+    n_img = len(src.view_counts)
+    if out_shapes is None:
+        out_shapes = src.default_out
+    if out_shapes is None or len(out_shapes) != n_img:
+        raise ValueError(f"{n_img} images but {0 if out_shapes is None else len(out_shapes)} output shapes")
+    return [(int(a), int(b)) for (a, b) in out_shapes]
 
 
-class _RawViews(_Views):
-    """The tower input from decoded uint8 images and an augmentation: the view kernel of the front end resizes, normalises
-    and mirrors a chunk's windows; neither a resized nor a flipped image exists."""
-
-    def __init__(self, model, raws, transform, aug, net_sizes):
-        if not isinstance(aug, TestAug):
-            raise TypeError("aug is a TestAug")
-        _raw_sizes(raws, transform, None)
-        _require_eval_gpu(model, raws[0])
-        lists = [aug.views(int(t.shape[0]), int(t.shape[1]), transform) for t in raws]
-        if net_sizes is not None:   # per image one (H, W) per view, in the order of aug.views
-            if len(net_sizes) != len(raws) or any(len(a) != len(b) for a, b in zip(net_sizes, lists)):
-                raise ValueError("with aug, net_sizes holds one (H, W) per view of every image")
-            lists = [[(int(H), int(W), f) for (H, W), (_, _, f) in zip(a, b)] for a, b in zip(net_sizes, lists)]
-        self._set_views([len(per) for per in lists])
-        self.sizes = [(H, W) for per in lists for (H, W, _) in per]
-        self.flags = [f for per in lists for (_, _, f) in per]
-        self.raws = [raws[i] for i, _ in self.owner]
-        self.transform, self.device = transform, raws[0].device
-        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
-        self.table = ops.seg_view_source_table(self.raws, self.sizes, self.flags)
-
-    def windows(self, chunk, dwin, wh, ww):
-        t = self.transform
-        return ops.seg_view_windows_from_u8(self.raws, self.sizes, self.flags, dwin, (wh, ww), t.mean, t.inv_std,
-                                            reverse_channels=t.channel_order == "bgr", table=self.table)
+def _flat_gts(gts):
+    if gts is None:
+        return None
+    return gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
 
 
-def _require_eval_gpu(model, t):
-    if not t.is_cuda:
-        raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {t.device} tensor")
+def _split_maps(flat, offs, out_shapes):
+    """The per-image (oh, ow) views of a flat buffer of maps."""
+    return None if flat is None else [flat[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
+
+def _require_eval(model):
     if model.training:
         raise RuntimeError("segclip_amd.segmentation: call model.eval() first (training mode draws Gumbel noise)")
 
@@ -266,7 +337,8 @@ def _require_eval_gpu(model, t):
 def build_text_embedding(model, text_tokens, chunk=1024):
     """(N, T, L) int64 prompt ids (N classes x T templates) -> (N, C): encode_text, mean over the templates, L2 norm
     (evaluation/builder.py:59-66).  The N * T captions go through the text tower `chunk` rows at a time."""
-    _require_eval_gpu(model, text_tokens)
+    ops.L.require_cuda(text_tokens)
+    _require_eval(model)
     N, T, Lc = text_tokens.shape
     flat = text_tokens.reshape(N * T, Lc)
     with torch.no_grad():
@@ -286,150 +358,54 @@ class SegInference:
                  max_windows=256):
         if mode not in ("whole", "slide"):
             raise ValueError(f"mode must be 'whole' or 'slide', got {mode!r}")
-        if not text_embedding.is_cuda:
-            raise RuntimeError("segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a "
-                               f"{text_embedding.device} text embedding")
+        ops.L.require_cuda(text_embedding)
         self.model = model
         self.text_embedding = text_embedding.detach().float().contiguous()
         self.with_bg, self.bg_thresh, self.mode = bool(with_bg), float(bg_thresh), mode
         self.crop_size, self.stride, self.max_windows = tuple(crop_size), tuple(stride), int(max_windows)
         self.num_classes = self.text_embedding.shape[0] + int(self.with_bg)
-        self._lists = {}
+        self._memo = {}
 
     def window_list(self, B, H, W):
         """(windows [(image, y0, x0)], (win_h, win_w)) of a (B, 3, H, W) batch."""
-        if self.mode == "whole":
-            return [(b, 0, 0) for b in range(B)], (H, W)
-        per = slide_windows(H, W, self.crop_size, self.stride)
-        return [(b, y, x) for b in range(B) for (y, x) in per], self.crop_size
+        plan = _plan_windows(self.mode, self.crop_size, self.stride, [(H, W)] * B)
+        return [w for _, wins in plan.batches for w in wins], ((H, W) if self.mode == "whole" else self.crop_size)
 
-    def _device_lists(self, B, H, W, device):
-        """The window list on the device; the last (B, H, W) is kept (a dataset of varying sizes does not accumulate lists)."""
-        key = (B, H, W, str(device))
-        if self._lists.get("key") != key:
-            wins, size = self.window_list(B, H, W)
-            per = len(wins) // B
-            if per > 64:
-                raise ValueError(f"slide mode: {per} windows per image, at most 64 supported")
-            self._lists = dict(key=key, value=(wins, size, torch.tensor(wins, dtype=torch.int32, device=device).view(-1, 3),
-                                               torch.arange(0, len(wins) + 1, per, dtype=torch.int32, device=device)))
-        return self._lists["value"]
+    def _device_plan(self, src, image_first=False):
+        """(_plan_windows of a source, checked against the tower; its windows as (nW, 3) int32 device rows; with image_first
+        the (images + 1) int32 device list of every image's first window, for sources of one view per image).  The last
+        call shape - sizes, view counts, device - is remembered (a dataset of varying sizes does not accumulate plans)."""
+        key = (tuple(src.sizes), tuple(src.view_counts), str(src.device))
+        memo = self._memo
+        if memo.get("key") != key:
+            plan = _plan_windows(self.mode, self.crop_size, self.stride, src.sizes, src.view_counts)
+            visual = self.model.clip.visual
+            _check_tower_windows(plan, src.name, visual.patch_size, visual.transformer.patch_len ** 2)
+            wins = [w for _, ws in plan.batches for w in ws]
+            memo = self._memo = dict(key=key, plan=plan, dfirst=None,
+                                     dwin=torch.tensor(wins, dtype=torch.int32, device=src.device).view(-1, 3))
+        if image_first and memo["dfirst"] is None:
+            firsts = [first for first, _, _ in memo["plan"].entries] + [memo["dwin"].shape[0]]
+            memo["dfirst"] = torch.tensor(firsts, dtype=torch.int32, device=src.device)
+        return memo["plan"], memo["dwin"], memo["dfirst"]
 
-    def _windows_forward(self, img, with_tables=True):
-        """Vision tower + group tables of every window -> the pixel kernels' arguments.  with_tables=False (group_map: the
-        groups do not depend on the classes): zero tables of one class instead of segclip_seg_group_table."""
-        _require_eval_gpu(self.model, img)
-        B, _, H, W = img.shape
-        if B == 0:
-            raise ValueError("empty image batch")
-        p = self.model.clip.visual.patch_size
-        wins, (wh, ww), dwin, dfirst = self._device_lists(B, H, W, img.device)
-        if wh % p or ww % p:
-            raise ValueError(f"window {wh}x{ww} is not a multiple of the patch size {p}")
-        grid = (wh // p, ww // p)
+    def _list_towers(self, src, plan, dwin, classes=True):
+        """The tower part of every call: every window of the plan through encode_image (max_windows at a time) and, with
+        `classes`, segclip_seg_group_table.  -> (flat soft_attn, tables, a window's offset in soft_attn, group count)."""
+        _require_eval(self.model)
         N = self.text_embedding.shape[0]
-        topk = min(5, N)
-        nW = len(wins)
-        parts = []
-        for s in range(0, nW, self.max_windows):
-            e = min(s + self.max_windows, nW)
-            if self.mode == "whole":
-                x = img[s:e]
-            else:
-                x = torch.stack([img[b, :, y:y + wh, x0:x0 + ww] for (b, y, x0) in wins[s:e]])
-            # the reference segments one image per call, where the two key layouts of the cross-attention block coincide;
-            # in a batch only "intended" keeps every window attending to its own tokens (config.py, SURVEY finding 0.4)
-            with config.scope(cross_mode="intended"):
-                feat, hidden, mid = self.model.clip.encode_image(x, return_hidden=True)
-            if not mid["attns"]:
-                raise ValueError(f"window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x or 4x the "
-                                 "training token count (modules/module_seg_vit.py:423)")
-            soft = mid["attns"][-1]["soft_attn"]
-            del mid, x
-            if with_tables:
-                tables = ops.seg_group_table(hidden[:, 1:, :], feat, self.text_embedding, self.model.clip.logit_scale, topk)
-            else:
-                n, G = soft.shape[0], soft.shape[1]
-                tables = (soft.new_zeros(n, G, 1), soft.new_zeros(n), soft.new_zeros(n, G, dtype=torch.int32), soft.new_zeros(n, G))
-            parts.append((soft,) + tables)
-        if len(parts) == 1:
-            soft, tables = parts[0][0], parts[0][1:]
-        else:
-            cat = [torch.cat([q[i] for q in parts]) for i in range(5)]
-            soft, tables = cat[0], tuple(cat[1:])
-        return soft, tables, dwin, dfirst, (B, H, W), (wh, ww), grid
-
-    @torch.no_grad()
-    def predict(self, img):
-        """(B, 3, H, W) -> (B, H, W) uint8 labels (class 0 = background when with_bg)."""
-        if self.num_classes > 256:
-            raise ops.L.Unsupported(f"predict: {self.num_classes} classes do not fit a uint8 label map; use encode_decode")
-        soft, tables, dwin, dfirst, size, win, grid = self._windows_forward(img)
-        return ops.seg_label_map(soft, tables, dwin, dfirst, size, win, grid, self.with_bg, self.bg_thresh)[0]
-
-    @torch.no_grad()
-    def group_map(self, img):
-        """(B, 3, H, W) -> (B, H, W) uint8: the group of every pixel (in its first covering window)."""
-        soft, tables, dwin, dfirst, size, win, grid = self._windows_forward(img, with_tables=False)
-        return ops.seg_label_map(soft, tables, dwin, dfirst, size, win, grid, self.with_bg, self.bg_thresh, labels=False,
-                                 groups=True)[1]
-
-    @torch.no_grad()
-    def encode_decode(self, img):
-        """(B, 3, H, W) -> (B, N + with_bg, H, W) fp32 logits (vit_seg.py:202-256; any batch size)."""
-        soft, tables, dwin, dfirst, size, win, grid = self._windows_forward(img)
-        return ops.seg_logits(soft, tables, dwin, dfirst, size, win, grid, self.with_bg, self.bg_thresh)
-
-    # ------------------------------------------------------------------------------------------ images of mixed sizes
-    def _list_plan(self, sizes):
-        """Windows of a list of image sizes -> (batches [(win size, [(image, y0, x0)])] in tower order, per-image
-        (first window, window count, win size)).  Slide mode: one batch of all windows; whole mode: one batch per size."""
-        per_image = [None] * len(sizes)
-        if self.mode == "slide":
-            wins = []
-            for i, (H, W) in enumerate(sizes):
-                per = slide_windows(H, W, self.crop_size, self.stride)
-                if len(per) > 64:
-                    raise ValueError(f"slide mode: {len(per)} windows per image, at most 64 supported")
-                per_image[i] = (len(wins), len(per), self.crop_size)
-                wins += [(i, y, x) for (y, x) in per]
-            return [(self.crop_size, wins)], per_image
-        by_size = {}
-        for i, hw in enumerate(sizes):
-            by_size.setdefault(hw, []).append(i)
-        batches, n = [], 0
-        for hw, members in by_size.items():
-            for k, i in enumerate(members):
-                per_image[i] = (n + k, 1, hw)
-            batches.append((hw, [(i, 0, 0) for i in members]))
-            n += len(members)
-        return batches, per_image
-
-    def _list_towers(self, src, classes=True, plan=None):
-        """The tower part of a list call: every window of the plan (_list_plan(src.sizes) unless the caller has it) through
-        encode_image (max_windows at a time) and, with `classes`, segclip_seg_group_table.  -> (flat soft_attn, tables, device
-        window list, per-entry (first window, window count, win size), a window's offset in soft_attn, group count)."""
-        name = getattr(src, "name", None)
-        p = self.model.clip.visual.patch_size
-        batches, per_image = self._list_plan(src.sizes) if plan is None else plan
-        N = self.text_embedding.shape[0]
-        dev = src.device
-        for (wh, ww), wins in batches:
-            if wh % p or ww % p:
-                raise ValueError((f"{name(wins[0][0])}: " if name else "") + f"window {wh}x{ww} is not a multiple of the patch size {p}")
-        wins_all = [w for _, wins in batches for w in wins]
-        dwin = torch.tensor(wins_all, dtype=torch.int32, device=dev).view(-1, 3)
-        parts, done, win_off, floats = [], 0, [], 0   # win_off: a window's offset in the flat soft_attn
-        for (wh, ww), wins in batches:
+        parts, done, win_off, floats = [], 0, [], 0
+        for (wh, ww), wins in plan.batches:
             for s in range(0, len(wins), self.max_windows):
                 chunk = wins[s:s + self.max_windows]
                 x = src.windows(chunk, dwin[done + s:done + s + len(chunk)], wh, ww)
-                with config.scope(cross_mode="intended"):   # see _windows_forward
+                # the reference segments one image per call, where the two key layouts of the cross-attention block coincide;
+                # in a batch only "intended" keeps every window attending to its own tokens (config.py, SURVEY finding 0.4)
+                with config.scope(cross_mode="intended"):
                     feat, hidden, mid = self.model.clip.encode_image(x, return_hidden=True)
                 if not mid["attns"]:
-                    raise ValueError((f"{name(chunk[0][0])}: " if name else "") +
-                                     f"window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x or 4x the "
-                                     "training token count (modules/module_seg_vit.py:423)")
+                    raise ValueError(f"{src.name(chunk[0][0])}: window {wh}x{ww}: the vision tower takes its segmentation "
+                                     "branch only at 1x or 4x the training token count (modules/module_seg_vit.py:423)")
                 soft = mid["attns"][-1]["soft_attn"]
                 del mid, x
                 tables = ()
@@ -445,117 +421,106 @@ class SegInference:
         else:
             cat = [torch.cat([q[i] for q in parts]) for i in range(len(parts[0]))]
             soft, tables = cat[0], tuple(cat[1:])
-        return soft, tables, dwin, per_image, win_off, n_groups
+        return soft, tables, win_off, n_groups
+
+    def _check_classes(self):
+        if self.num_classes > 256:
+            raise ops.L.Unsupported(f"{self.num_classes} classes: the label-map kernels hold at most 256; use encode_decode")
+
+    def _batch_forward(self, img, classes=True):
+        """Vision tower + group tables of every window of a (B, 3, H, W) batch -> the pixel kernels' arguments.
+        classes=False (group_map: the groups do not depend on the classes): zero tables of one class."""
+        src = _BatchImages(img, self.mode == "whole")
+        plan, dwin, dfirst = self._device_plan(src, image_first=True)
+        soft, tables, _, G = self._list_towers(src, plan, dwin, classes)
+        if not classes:
+            n = dwin.shape[0]
+            tables = (soft.new_zeros(n, G, 1), soft.new_zeros(n), soft.new_zeros(n, G, dtype=torch.int32), soft.new_zeros(n, G))
+        (B, _, H, W), (wh, ww), p = img.shape, plan.entries[0][2], self.model.clip.visual.patch_size
+        return soft, tables, dwin, dfirst, (B, H, W), (wh, ww), (wh // p, ww // p)
+
+    @torch.no_grad()
+    def predict(self, img):
+        """(B, 3, H, W) -> (B, H, W) uint8 labels (class 0 = background when with_bg)."""
+        self._check_classes()
+        return ops.seg_label_map(*self._batch_forward(img), self.with_bg, self.bg_thresh)[0]
+
+    @torch.no_grad()
+    def group_map(self, img):
+        """(B, 3, H, W) -> (B, H, W) uint8: the group of every pixel (in its first covering window)."""
+        return ops.seg_label_map(*self._batch_forward(img, classes=False), self.with_bg, self.bg_thresh, labels=False, groups=True)[1]
+
+    @torch.no_grad()
+    def encode_decode(self, img):
+        """(B, 3, H, W) -> (B, N + with_bg, H, W) fp32 logits (vit_seg.py:202-256; any batch size)."""
+        return ops.seg_logits(*self._batch_forward(img), self.with_bg, self.bg_thresh)
+
+    # ------------------------------------------------------------------------------------------ images of mixed sizes
+    def _image_rows(self, src, plan, win_off, out_shapes, with_gt):
+        """The rows of ops.seg_image_table / seg_view_tables: one per entry, with its image's output size and ground-truth
+        offset (the ground truths lie flat one after the other)."""
+        p = self.model.clip.visual.patch_size
+        rows, gt_off = [], 0
+        for i, V in enumerate(src.view_counts):
+            for e in range(len(rows), len(rows) + V):
+                first, count, (wh, ww) = plan.entries[e]
+                rows.append(dict(first=first, count=count, net=src.sizes[e], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
+                                 soft_off=win_off[first], gt_off=gt_off if with_gt else -1, flags=src.flags[e]))
+            gt_off += out_shapes[i][0] * out_shapes[i][1]
+        return rows
 
     def _list_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
                       groups=None):
-        """src: _SlicedImages or _RawImages - the network sizes of the images and the tower input of a chunk of windows.
+        """The list call without augmentation: the arg-max of the rescaled logits (segclip_seg_label_map_rescaled).
         groups: None, "also" (-> (labels, group maps, G), both at out_shapes, from the same pass of the tower) or "only"
         (-> (None, group maps, G): no class tables, no label map)."""
-        sizes, n_img = src.sizes, len(src.sizes)
-        if out_shapes is None:
-            out_shapes = src.default_out
-        if len(out_shapes) != n_img:
-            raise ValueError(f"{n_img} images but {len(out_shapes)} output shapes")
-        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
+        out_shapes = _out_shapes(src, out_shapes)
         classes = groups != "only"
-        if classes and self.num_classes > 256:
-            raise ops.L.Unsupported(f"{self.num_classes} classes do not fit a uint8 label map; use encode_decode")
-        p = self.model.clip.visual.patch_size
-        plan = self._list_plan(sizes)
+        if classes:
+            self._check_classes()
+        plan, dwin, _ = self._device_plan(src)
         if groups is not None:
-            for i, (_, count, _) in enumerate(plan[1]):
+            for i, count in enumerate(plan.image_windows):
                 if count != 1:
-                    raise ValueError(f"group maps are defined for one window per image: image {i} ({sizes[i][0]}x{sizes[i][1]}) "
-                                     f"has {count} windows in slide mode")
-        dev = src.device
-        soft, tables, dwin, per_image, win_off, n_groups = self._list_towers(src, classes, plan)
-        rows, gt_off = [], 0
-        for i, (first, count, (wh, ww)) in enumerate(per_image):
-            rows.append(dict(first=first, count=count, net=sizes[i], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
-                             soft_off=win_off[first], gt_off=gt_off if gts is not None else -1))
-            gt_off += out_shapes[i][0] * out_shapes[i][1]
-        images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, dev)
-
-        def views(flat):
-            return [flat[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
-
+                    raise ValueError(f"group maps are defined for one window per image: image {i} ({src.sizes[i][0]}x"
+                                     f"{src.sizes[i][1]}) has {count} windows in slide mode")
+        soft, tables, win_off, n_groups = self._list_towers(src, plan, dwin, classes)
+        rows = self._image_rows(src, plan, win_off, out_shapes, gts is not None)
+        images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, src.device)
         labels = None
         if classes:
-            labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
-            gt = None
-            if gts is not None:
-                gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
+            labels = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
             ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels,
-                                       gt=gt, areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
-            labels = views(labels) if want_labels else None
+                                       gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+            labels = _split_maps(labels, offs, out_shapes)
         if groups is None:
             return labels
         # the table's label offsets and workgroup numbers serve the group maps as they are: same sizes, same tile
-        gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=dev))
-        return labels, views(gmaps), n_groups
+        gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=src.device))
+        return labels, _split_maps(gmaps, offs, out_shapes), n_groups
 
     def _views_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
                        dense=False):
-        """The augmented list call.  src: _SlicedViews or _RawViews - one plan entry per (image, view) pair, so the windows of
-        all views share the tower calls of _list_towers; segclip_seg_label_map_views takes the place of the rescaled kernel.
-        dense: -> the (C, oh, ow) fp32 mean probabilities of the single image instead of labels."""
-        counts, n_img = src.view_counts, len(src.view_counts)
-        if out_shapes is None:
-            out_shapes = src.default_out
-        if out_shapes is None or len(out_shapes) != n_img:
-            raise ValueError(f"{n_img} images but {0 if out_shapes is None else len(out_shapes)} output shapes")
-        out_shapes = [(int(a), int(b)) for (a, b) in out_shapes]
-        if self.num_classes > 256:
-            raise ops.L.Unsupported(f"{self.num_classes} classes: the multi-view kernel holds at most 256")
-        if dense and n_img != 1:
-            raise ValueError(f"the dense probabilities are formed for one image per call, got {n_img}")
-        p = self.model.clip.visual.patch_size
-        base = self.model.clip.visual.transformer.patch_len ** 2   # tokens of the training resolution
-        # what a single view already requires, and the limits of the kernel's device-side lists (what exceeds them would be
-        # silently ignored), before anything runs
-        e0 = 0
-        for i, V in enumerate(counts):
-            if V > ops.SEG_MAX_VIEWS:
-                raise ValueError(f"image {i}: {V} views, at most {ops.SEG_MAX_VIEWS} supported")
-            n_win = 0
-            for e in range(e0, e0 + V):
-                try:
-                    _, count, (wh, ww) = self._list_plan([src.sizes[e]])[1][0]
-                except ValueError as err:
-                    raise ValueError(f"{src.name(e)}: {err}") from None
-                if wh % p or ww % p:
-                    raise ValueError(f"{src.name(e)}: window {wh}x{ww} is not a multiple of the patch size {p}")
-                if (wh // p) * (ww // p) not in (base, 4 * base):
-                    raise ValueError(f"{src.name(e)}: window {wh}x{ww}: the vision tower takes its segmentation branch only at 1x "
-                                     f"or 4x the training token count ({base}; modules/module_seg_vit.py:423)")
-                n_win += count
-            if n_win > ops.SEG_MAX_IMAGE_WINDOWS:
-                raise ValueError(f"image {i}: {n_win} windows over its {V} views, at most {ops.SEG_MAX_IMAGE_WINDOWS} supported")
-            e0 += V
-        dev = src.device
-        soft, tables, dwin, per_entry, win_off, _ = self._list_towers(src)
-        rows, gt_off, e = [], 0, 0
-        for i, V in enumerate(counts):
-            for _ in range(V):
-                first, count, (wh, ww) = per_entry[e]
-                rows.append(dict(first=first, count=count, net=src.sizes[e], out=out_shapes[i], win=(wh, ww), grid=(wh // p, ww // p),
-                                 soft_off=win_off[first], gt_off=gt_off if gts is not None else -1, flags=src.flags[e]))
-                e += 1
-            gt_off += out_shapes[i][0] * out_shapes[i][1]
-        images, vtab, offs, nbytes, n_blocks, most_img, most_view, most_v = ops.seg_view_tables(rows, counts, dev)
+        """The augmented list call: the mean over an image's views of the soft-max of the rescaled logits, its first maximum
+        (segclip_seg_label_map_views).  dense: -> the (C, oh, ow) fp32 mean probabilities of the single image instead."""
+        out_shapes = _out_shapes(src, out_shapes)
+        self._check_classes()
+        if dense and len(out_shapes) != 1:
+            raise ValueError(f"the dense probabilities are formed for one image per call, got {len(out_shapes)}")
+        plan, dwin, _ = self._device_plan(src)
+        soft, tables, win_off, _ = self._list_towers(src, plan, dwin)
+        rows = self._image_rows(src, plan, win_off, out_shapes, gts is not None)
+        images, vtab, offs, nbytes, *limits = ops.seg_view_tables(rows, src.view_counts, src.device)
+        args = (soft, tables, dwin, images, vtab, *limits, self.with_bg, self.bg_thresh)
         if dense:
-            return ops.seg_view_probs(soft, tables, dwin, images, vtab, n_blocks, most_img, most_view, most_v, self.with_bg,
-                                      self.bg_thresh, out_shapes[0])
-        labels = torch.empty(nbytes, dtype=torch.uint8, device=dev) if want_labels else None
-        gt = None
-        if gts is not None:
-            gt = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
-        ops.seg_label_map_views(soft, tables, dwin, images, vtab, n_blocks, most_img, most_view, most_v, self.with_bg, self.bg_thresh,
-                                labels=labels, gt=gt, areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
-        if not want_labels:
-            return None
-        return [labels[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+            return ops.seg_view_probs(*args, out_shapes[0])
+        labels = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
+        ops.seg_label_map_views(*args, labels=labels, gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index,
+                                reduce_zero_label=reduce_zero_label)
+        return _split_maps(labels, offs, out_shapes)
+
+    def _forward(self, src, out_shapes, **kw):
+        return (self._views_forward if src.augmented else self._list_forward)(src, out_shapes, **kw)
 
     @torch.no_grad()
     def predict_list(self, imgs, out_shapes=None):
@@ -563,7 +528,7 @@ class SegInference:
         to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
         Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size."""
-        return self._list_forward(_SlicedImages(self.model, imgs), out_shapes)
+        return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes)
 
     @torch.no_grad()
     def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None):
@@ -574,28 +539,26 @@ class SegInference:
         aug (a TestAug): mmseg's aug_test over the views of aug.views - every view segmented, its logits rescaled to the output
         size and passed through a soft-max, flipped back, the probabilities averaged over the views, first maximum.  net_sizes
         then holds one (H, W) per view of every image."""
-        if aug is not None:
-            return self._views_forward(_RawViews(self.model, raws, transform, aug, net_sizes), out_shapes)
-        return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes)
+        return self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
 
     @torch.no_grad()
     def predict_views(self, views, out_shapes):
         """views[i] = [((3, H, W) tensor, flags)]: the views of image i, pre-processed and ALREADY FLIPPED as mmseg hands imgs
         and img_metas to aug_test (flags: ops.SEG_FLIP_H | ops.SEG_FLIP_V, what img_metas' flip / flip_direction say)
         -> [(oh_i, ow_i) uint8 labels] of the mean probabilities, as predict_raw(aug=)."""
-        return self._views_forward(_SlicedViews(self.model, views), out_shapes)
+        return self._views_forward(_SlicedImages(views, augmented=True), out_shapes)
 
     @torch.no_grad()
     def predict_proba_views(self, views, out_shape):
         """The views [((3, H, W) tensor, flags)] of ONE image -> (N + with_bg, oh, ow) fp32: the mean over the views of the
         soft-max of the rescaled logits, what aug_test takes the arg-max of (predict_views' label is its first maximum)."""
-        return self._views_forward(_SlicedViews(self.model, [views]), [out_shape], dense=True)
+        return self._views_forward(_SlicedImages([views], augmented=True), [out_shape], dense=True)
 
     @torch.no_grad()
     def predict_proba_raw(self, raw, transform, aug=None, out_shape=None, net_sizes=None):
         """predict_proba_views from ONE decoded (h, w, 3) uint8 image; aug defaults to the single unflipped view, out_shape to
         the image's own size."""
-        src = _RawViews(self.model, [raw], transform, TestAug() if aug is None else aug, None if net_sizes is None else [net_sizes])
+        src = _RawImages([raw], transform, None if net_sizes is None else [net_sizes], TestAug() if aug is None else aug)
         return self._views_forward(src, None if out_shape is None else [out_shape], dense=True)
 
     # ------------------------------------------------------------------------------------------ the demo's outputs
@@ -605,12 +568,12 @@ class SegInference:
         network size and again to the output size, first maximum over the groups (get_attn_maps + show_result's group
         branch, vit_seg.py:144-200, :359-362), one launch for the list.  out_shapes defaults to the images' own sizes, where
         the result equals group_map's.  Every image is one window: a slide-mode image with more raises ValueError."""
-        return self._list_forward(_SlicedImages(self.model, imgs), out_shapes, groups="only")[1]
+        return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes, groups="only")[1]
 
     @torch.no_grad()
     def groups_raw(self, raws, transform, out_shapes=None, net_sizes=None):
         """groups_list from decoded (h_i, w_i, 3) uint8 images, as predict_raw; out_shapes defaults to the raw sizes."""
-        return self._list_forward(_RawImages(self.model, raws, transform, net_sizes), out_shapes, groups="only")[1]
+        return self._list_forward(_RawImages(raws, transform, net_sizes), out_shapes, groups="only")[1]
 
     @torch.no_grad()
     def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None):
@@ -631,7 +594,7 @@ class SegInference:
                 raise ValueError(f"unknown vis mode {m!r}; known: {', '.join(VIS_MODES)}")
         want_labels = any(m in ("pred", "input_pred", "input_pred_label") for m in modes)
         want_groups = any(m in _GROUP_MODES for m in modes)
-        src = _RawImages(self.model, raws, transform, net_sizes)
+        src = _RawImages(raws, transform, net_sizes)
         palette = _check_palette(palette, src.device)
         labels = gmaps = None
         if want_groups:
@@ -725,9 +688,7 @@ def blend(raws, maps, palette, opacity=0.5, skip_zero=False, channel_order="rgb"
         raise ValueError("empty image list")
     if len(raws) != len(maps):
         raise ValueError(f"{len(raws)} images but {len(maps)} index maps")
-    for t in list(raws) + list(maps):
-        if not t.is_cuda:
-            raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {t.device} tensor")
+    ops.L.require_cuda(*raws, *maps)
     for t, m in zip(raws, maps):
         if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
             raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
@@ -777,36 +738,32 @@ class SegEvaluator:
     def update(self, imgs, gts, return_labels=False):
         """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size."""
         self._check_gts(imgs, gts)
-        return self._forward(_SlicedImages(self.seg.model, imgs), gts, return_labels)
+        return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
     def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None):
         """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included)."""
         self._check_gts(raws, gts)
-        if aug is not None:
-            return self._forward(_RawViews(self.seg.model, raws, transform, aug, net_sizes), gts, return_labels, views=True)
-        return self._forward(_RawImages(self.seg.model, raws, transform, net_sizes), gts, return_labels)
+        return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
 
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):
         """views[i] = [((3, H, W) tensor, flags)] as SegInference.predict_views, scored at each ground truth's size."""
         self._check_gts(views, gts)
-        return self._forward(_SlicedViews(self.seg.model, views), gts, return_labels, views=True)
+        return self._forward(_SlicedImages(views, augmented=True), gts, return_labels)
 
     @staticmethod
     def _check_gts(imgs, gts):
         if len(imgs) != len(gts):
             raise ValueError(f"{len(imgs)} images but {len(gts)} ground truths")
+        ops.L.require_cuda(*gts)
         for g in gts:
-            if not g.is_cuda:
-                raise RuntimeError(f"segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a {g.device} tensor")
             if g.dtype != torch.uint8 or g.dim() != 2:
                 raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
 
-    def _forward(self, src, gts, return_labels, views=False):
-        forward = self.seg._views_forward if views else self.seg._list_forward
-        return forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas, ignore_index=self.ignore_index,
-                       reduce_zero_label=self.reduce_zero_label, want_labels=return_labels)
+    def _forward(self, src, gts, return_labels):
+        return self.seg._forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas, ignore_index=self.ignore_index,
+                                 reduce_zero_label=self.reduce_zero_label, want_labels=return_labels)
 
     @staticmethod
     def metrics_from_areas(areas):

@@ -516,7 +516,7 @@ def test_interface_errors():
         with pytest.raises(ValueError, match="output shapes"):
             seg.predict_views([[(img, 0)], [(img, 1)]], [(50, 50)])
         with pytest.raises(ValueError, match="one image per call"):
-            seg._views_forward(segclip_amd.segmentation._SlicedViews(model, [[(img, 0)], [(img, 0)]]), [(50, 50)] * 2, dense=True)
+            seg._views_forward(segclip_amd.segmentation._SlicedImages([[(img, 0)], [(img, 0)]], augmented=True), [(50, 50)] * 2, dense=True)
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             seg.predict_views([[(img.cpu(), 0)]], [(50, 50)])
         with pytest.raises(ValueError, match="image 0 view 1.*1x or 4x"):   # whole mode: a view the tower has no segmentation branch for

@@ -333,6 +333,38 @@ def test_batching_and_chunking_invariance(mode):
         segclip_amd.set_compute_dtype(torch.float32)
 
 
+@pytest.mark.parametrize("mode", ["whole", "slide"])
+def test_remembered_plan_serves_only_its_own_call_shape(mode):
+    """SegInference remembers the plan and the device window list of its last call shape.  predict(a), predict(b), predict(a)
+    with a and b of different shapes: the first and the third result are equal bit for bit and b's equals a fresh object's;
+    predict_list of a's images straight after (the same sizes: the remembered plan serves it) equals a fresh object's."""
+    g = load_golden("seg_tiny.npz")
+    try:
+        model = _tiny_model()
+        emb = torch.from_numpy(g["text_embedding"]).to(DEV)
+        gen = torch.Generator().manual_seed(11)
+        kw = dict(mode="slide", crop_size=(64, 64), stride=(48, 40)) if mode == "slide" else {}
+        shape_a, shape_b = ((2, 3, 100, 150), (1, 3, 64, 64)) if mode == "slide" else ((2, 3, 128, 128), (1, 3, 256, 64))
+        a, b = torch.randn(shape_a, generator=gen).to(DEV), torch.randn(shape_b, generator=gen).to(DEV)
+
+        def fresh():
+            return SegInference(model, emb, True, bg_thresh=0.03, **kw)
+
+        seg = fresh()
+        first, other, third = seg.predict(a), seg.predict(b), seg.predict(a)
+        assert tuple(first.shape) == (2,) + shape_a[2:] and tuple(other.shape) == (1,) + shape_b[2:]
+        assert torch.equal(first, third)
+        assert torch.equal(other, fresh().predict(b))
+        assert torch.equal(first, fresh().predict(a))
+        listed, want = seg.predict_list(list(a)), fresh().predict_list(list(a))
+        assert len(listed) == len(want) == 2
+        for x, y in zip(listed, want):
+            assert tuple(x.shape) == shape_a[2:] and torch.equal(x, y)
+        assert torch.equal(seg.predict(b), other)
+    finally:
+        segclip_amd.set_compute_dtype(torch.float32)
+
+
 # ------------------------------------------------------------------------------------------------ 5. interface
 def test_interface_errors_and_wide_class_lists():
     g = load_golden("seg_tiny.npz")

@@ -39,7 +39,7 @@ import torch.nn.functional as F
 
 import segclip_amd
 from segclip_amd import config, ops, synth
-from segclip_amd.segmentation import SegInference
+from segclip_amd.segmentation import SegInference, _BatchImages
 from tools.clock_sampler import ClockSampler
 
 EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("--raw-child" in sys.argv[1:])
@@ -117,7 +117,7 @@ def case(name, model, text, B, H, W, inner, **kw):
         x = img if seg.mode == "whole" else torch.stack([img[b, :, y:y + win[0], x0:x0 + win[1]] for (b, y, x0) in wins])
         feat, hidden, mid = model.clip.encode_image(x, return_hidden=True)
     soft = mid["attns"][-1]["soft_attn"]
-    _, _, dwin, dfirst = seg._device_lists(B, H, W, img.device)
+    _, dwin, dfirst = seg._device_plan(_BatchImages(img, seg.mode == "whole"), image_first=True)
     grid = (win[0] // 16, win[1] // 16)
     ls = model.clip.logit_scale.detach()
 
