@@ -634,6 +634,42 @@ int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const 
                       int64_t out_bytes, int64_t* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
+ * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
+ * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the
+ * multi-caption layout (sentences_dict, cut_off_points, sentence_num, image_num, multi_sentence_per_image;
+ * dataloaders/dataloader_coco_retrieval.py:85-104); it ships no evaluator, so the definition is this project's:
+ *   V (Ni, E), T (Nt, E) fp32, contiguous, 16-byte aligned;  g (Nt) int32, the image of every caption (any number of
+ *   captions per image, zero included);  sim[t, j] = <T[t], V[j]> (the logit scale is a positive factor and left out)
+ *   rank_t2i[t] = #{ j != g[t] : sim[t, j] > sim[t, g[t]] }                      (0-based; a tie favours the ground truth)
+ *   rank_i2t[j] = #{ t : g[t] != j and sim[t, j] > best[j] },  best[j] = max{ sim[t, j] : g[t] == j };  -1 without captions
+ *
+ * segclip_retrieval_thresholds (modules/modeling.py:338-372 restricted to the ground-truth pairs): thr_t[t] = sim[t, g[t]] as
+ *   the k-ordered fp32 fused-multiply-add chain the matrix cores form; n_cap[j] = the captions of image j; best[j] = the
+ *   maximum of thr_t over them, an integer atomic maximum on an order-preserving key (no float atomics), +inf where
+ *   n_cap[j] = 0.  A g[t] outside [0, Ni) is found on the device: bit 0 of *status is set (status is OR-ed into, never
+ *   cleared here), thr_t[t] = +inf, and the caption counts for no image.  thr_t (Nt), best (Ni) fp32, n_cap (Ni) int32 are
+ *   written whole.
+ * segclip_retrieval_count (modules/modeling.py:356-357, the logits product, and the ranking a consumer of
+ *   dataloaders/dataloader_coco_retrieval.py:85-104 forms from it): tiles of 128 captions x 128 images on
+ *   v_mfma_f32_32x32x2_f32 (fp32 operands and accumulation), K in slices of 32 through LDS.  No similarity is stored: a lane
+ *   compares its accumulators with its rows' thr_t and its columns' best, skipping j == g[t]; a tile sums the hits per row
+ *   and column in registers and LDS and ADDS them to rank_t2i (Nt) and rank_i2t (Ni), int32, with one integer atomic per row
+ *   and column that has hits.  The caller zeroes both before the call.  Integer sums: independent of scheduling.
+ * segclip_retrieval_hist (the rank layout of dataloaders/dataloader_coco_retrieval.py:85-104 turned into the metrics' input):
+ *   ADDS every rank_t2i to hist_t2i (Ni) and every rank_i2t of an image with captions to hist_i2t (Nt + 1), int64; sets
+ *   rank_i2t[j] = -1 where n_cap[j] = 0.  R@K, median and mean rank follow from the histograms exactly.
+ * SEGCLIP_ERR_UNSUPPORTED, naming the argument: E not a multiple of 32 or above 1024; Ni or Nt >= 2^24.
+ * Bound of the count pass: 2 Nt Ni E flop at the f32-MFMA rate (256 flop / clock / CU).
+ * ------------------------------------------------------------------------------------------ */
+int segclip_retrieval_thresholds(const float* V, const float* T, const int32_t* g, int64_t Ni, int64_t Nt, int64_t E, float* thr_t,
+                                 float* best, int32_t* n_cap, int32_t* status, void* stream);
+int segclip_retrieval_count(const float* V, const float* T, const int32_t* g, const float* thr_t, const float* best, int64_t Ni,
+                            int64_t Nt, int64_t E, int32_t* rank_t2i, int32_t* rank_i2t, void* stream);
+int segclip_retrieval_hist(const int32_t* rank_t2i, int32_t* rank_i2t, const int32_t* n_cap, int64_t Ni, int64_t Nt,
+                           int64_t* hist_t2i, int64_t* hist_i2t, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Front end of training (train_frontend.inc): decoded uint8 images and int32 segment maps -> the model's `image` and
  * `image_seg`, each in ONE launch for a batch of mixed sizes.  Both entries are integer algorithms and reproduce the
  * reference's CPU pipeline to the last bit.

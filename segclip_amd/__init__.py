@@ -26,4 +26,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".segmentation", __name__)
         return mod if name == "segmentation" else getattr(mod, name)
+    if name in ("RetrievalEvaluator", "retrieval"):   # image-text retrieval evaluation, likewise
+        import importlib
+        mod = importlib.import_module(".retrieval", __name__)
+        return mod if name == "retrieval" else getattr(mod, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -2737,6 +2737,69 @@ def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, rev
     return out
 
 
+# ---------------------------------------------------------------- image-text retrieval evaluation (retrieval.hip)
+RETRIEVAL_BAD_INDEX = 1   # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
+
+
+def _retrieval_inputs(what, visual, sequence, image_index):
+    L.require_cuda(visual, sequence, image_index)
+    if visual.dtype != torch.float32 or sequence.dtype != torch.float32 or image_index.dtype != torch.int32:
+        raise TypeError(f"{what}: fp32 visual and sequence embeddings, int32 image_index")
+    if visual.dim() != 2 or sequence.dim() != 2 or visual.shape[1] != sequence.shape[1] \
+            or tuple(image_index.shape) != (sequence.shape[0],):
+        raise ValueError(f"{what}: visual (Ni, E), sequence (Nt, E), image_index (Nt,); got {tuple(visual.shape)}, "
+                         f"{tuple(sequence.shape)}, {tuple(image_index.shape)}")
+    return visual.contiguous(), sequence.contiguous(), image_index.contiguous()
+
+
+def retrieval_thresholds(visual, sequence, image_index, status):
+    """segclip_retrieval_thresholds: -> (thr_t (Nt,) fp32 = <sequence[t], visual[image_index[t]]>, best (Ni,) fp32 = the
+    maximum of thr_t over an image's captions, n_cap (Ni,) int32 = its captions).  status: (1,) int32, OR-ed into on the
+    device (RETRIEVAL_BAD_INDEX)."""
+    V, T, g = _retrieval_inputs("retrieval_thresholds", visual, sequence, image_index)
+    L.require_cuda(status)
+    if status.dtype != torch.int32 or status.numel() != 1:
+        raise ValueError("retrieval_thresholds: status is a (1,) int32 tensor")
+    (Ni, E), Nt = V.shape, T.shape[0]
+    thr, best, n_cap = _empty((Nt,), torch.float32, V), _empty((Ni,), torch.float32, V), _empty((Ni,), torch.int32, V)
+    L.check(L.load().segclip_retrieval_thresholds(L.ptr(V), L.ptr(T), L.ptr(g), Ni, Nt, E, L.ptr(thr), L.ptr(best), L.ptr(n_cap),
+                                                  L.ptr(status), L.stream()), "retrieval_thresholds")
+    return thr, best, n_cap
+
+
+def retrieval_count(visual, sequence, image_index, thr_t, best):
+    """segclip_retrieval_count: the tiled compare-and-count pass -> (rank_t2i (Nt,), rank_i2t (Ni,)) int32.  No (Nt, Ni)
+    array exists; an image without captions has rank 0 here and -1 after retrieval_hist."""
+    V, T, g = _retrieval_inputs("retrieval_count", visual, sequence, image_index)
+    L.require_cuda(thr_t, best)
+    (Ni, E), Nt = V.shape, T.shape[0]
+    if thr_t.dtype != torch.float32 or best.dtype != torch.float32 or not thr_t.is_contiguous() or not best.is_contiguous() \
+            or tuple(thr_t.shape) != (Nt,) or tuple(best.shape) != (Ni,):
+        raise ValueError("retrieval_count: thr_t (Nt,) and best (Ni,) are the contiguous fp32 outputs of retrieval_thresholds")
+    rank_t2i = torch.zeros(Nt, dtype=torch.int32, device=V.device)
+    rank_i2t = torch.zeros(Ni, dtype=torch.int32, device=V.device)
+    L.check(L.load().segclip_retrieval_count(L.ptr(V), L.ptr(T), L.ptr(g), L.ptr(thr_t), L.ptr(best), Ni, Nt, E, L.ptr(rank_t2i),
+                                             L.ptr(rank_i2t), L.stream()), "retrieval_count")
+    return rank_t2i, rank_i2t
+
+
+def retrieval_hist(rank_t2i, rank_i2t, n_cap):
+    """segclip_retrieval_hist: -> (hist_t2i (Ni,), hist_i2t (Nt + 1,)) int64, the number of captions / of images with captions
+    at every rank; rank_i2t becomes -1 in place where n_cap is 0."""
+    L.require_cuda(rank_t2i, rank_i2t, n_cap)
+    for name, t in (("rank_t2i", rank_t2i), ("rank_i2t", rank_i2t), ("n_cap", n_cap)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"retrieval_hist: {name} is a contiguous one-dimensional int32 tensor")
+    Nt, Ni = rank_t2i.shape[0], rank_i2t.shape[0]
+    if n_cap.shape[0] != Ni:
+        raise ValueError(f"retrieval_hist: n_cap has {n_cap.shape[0]} entries for {Ni} images")
+    hist_t2i = torch.zeros(Ni, dtype=torch.int64, device=rank_t2i.device)
+    hist_i2t = torch.zeros(Nt + 1, dtype=torch.int64, device=rank_t2i.device)
+    L.check(L.load().segclip_retrieval_hist(L.ptr(rank_t2i), L.ptr(rank_i2t), L.ptr(n_cap), Ni, Nt, L.ptr(hist_t2i),
+                                            L.ptr(hist_i2t), L.stream()), "retrieval_hist")
+    return hist_t2i, hist_i2t
+
+
 # ---------------------------------------------------------------- front end of training (train_frontend.inc)
 TRAIN_SOURCE_COLS = 13    # int64 columns of one row of the source table of segclip_train_images_from_u8
 TRAIN_MAP_COLS = 9        # int64 columns of one row of the map table of segclip_train_patch_labels

@@ -308,3 +308,30 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)
     return miou
+
+
+def eval_retrieval_epoch(args, model, device, image_batches, text_batches, chunk=256):
+    """The retrieval score of a checkpoint on a multi-caption set (the layout of dataloaders/dataloader_coco_retrieval.py:85-104;
+    the similarity is modules/modeling.py:338-372 without the logit scale): {"t2i": {R1, R5, R10, MedianR, MeanR}, "i2t": {...}}.
+    image_batches: an iterable of (B, 1, 3, H, W) or (B, 3, H, W) images; text_batches: an iterable of (input_ids, segment_ids,
+    input_mask, image_index) with image_index[b] the number of the caption's image in the order image_batches gives them
+    (retrieval.image_index_from_cut_off_points turns the loader's cut_off_points into it).  The embeddings, ranks and
+    histograms stay on the device until the end.  With several ranks gather the embeddings and use
+    RetrievalEvaluator.add_embeddings instead."""
+    from .retrieval import RetrievalEvaluator
+    model = _unwrap(model)
+    model.eval()
+    evaluator = RetrievalEvaluator(model, chunk=chunk)
+    for image in image_batches:
+        evaluator.add_images(image.to(device, non_blocking=True))
+    for input_ids, segment_ids, input_mask, image_index in text_batches:
+        input_ids, segment_ids, input_mask, image_index = (t.to(device, non_blocking=True)
+                                                           for t in (input_ids, segment_ids, input_mask, image_index))
+        evaluator.add_texts(input_ids, segment_ids, input_mask, image_index)
+    out = evaluator.compute()
+    if getattr(args, "local_rank", 0) == 0:
+        for name, key in (("Text-to-Image", "t2i"), ("Image-to-Text", "i2t")):
+            m = out[key]
+            logger.info("%s: R@1: %.1f - R@5: %.1f - R@10: %.1f - Median R: %.1f - Mean R: %.1f", name, m["R1"], m["R5"],
+                        m["R10"], m["MedianR"], m["MeanR"])
+    return out
