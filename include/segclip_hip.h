@@ -670,6 +670,40 @@ int segclip_retrieval_hist(const int32_t* rank_t2i, int32_t* rank_i2t, const int
                            int64_t* hist_t2i, int64_t* hist_i2t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Top-K image-text search (retrieval_topk.inc): what was retrieved, again without the similarity matrix.  Both entries
+ * consume the similarity of modules/modeling.py:338-372 (get_similarity_logits / _loose_similarity, the logit scale left out).
+ * The definition is this project's (tests/retrieval_topk_reference.py restates it in fp64):
+ *   Q (Nq, E) queries, X (Nx, E) gallery, fp32, contiguous, 16-byte aligned;  s[q, j] = <Q[q], X[j]>
+ *   Row q of idx (Nq, k) int32 holds the first min(k, Nx) gallery indices under the total order "higher score first, equal
+ *   scores: lower index first"; val (Nq, k) fp32 holds their scores.  Positions from min(k, Nx) on hold idx = -1, val = -inf.
+ *   The order is total, so the result is a function of the inputs alone: never of scheduling, tile order or the number of
+ *   partial lists.  val[q, p] is bit for bit the k-ordered fp32 fused-multiply-add chain from 0 that
+ *   segclip_retrieval_thresholds and the matrix cores of segclip_retrieval_count form for that pair: the search and the ranks
+ *   agree exactly.  "Equal scores" means equal fp32 bits, compared through the order-preserving integer key of the segment
+ *   maximum (sign-magnitude bits mapped onto unsigned integers): -0 sorts below +0, and a NaN sorts where its bits put it,
+ *   above +inf with the sign bit clear and below -inf with it set.
+ * segclip_retrieval_topk (modules/modeling.py:338-372, the logits product, and the selection a consumer forms from it): the
+ *   128 x 128 x 32 product of segclip_retrieval_count on v_mfma_f32_32x32x2_f32 with a selecting epilogue.  A workgroup keeps
+ *   128 queries and, per query, a sorted list of 64-bit keys (score key << 32 | 0xFFFFFFFF - index) in LDS; the k-th key is
+ *   the row's admission threshold.  After a tile the scores pass through LDS, a wave takes a row at a time with one candidate
+ *   per lane, one ballot against the threshold skips the row, and otherwise a bitonic sort and merge in lane exchanges
+ *   updates the list.  The gallery tiles are dealt to `splits` partial lists per query (0 = auto: enough to fill the CUs when
+ *   the queries alone do not, at most 64, never more than there are tiles); with more than one, the lists go through the
+ *   workspace, (Nq rounded up to 128) * splits * k * 8 bytes, and a second kernel merges them.  splits is part of the ABI so
+ *   that a test can hold every partition count to one result; nothing else passes a non-zero value.
+ * segclip_retrieval_topk_ws_bytes (modules/modeling.py:338-372, sized for the same consumer): the workspace of that call, 0
+ *   with one partial list; a negative error code where segclip_retrieval_topk would refuse the same arguments.
+ * Nq = 0 or Nx = 0 is a successful call; the second fills idx and val with the padding.  idx and val are written whole.
+ * SEGCLIP_ERR_UNSUPPORTED, naming the value: k outside [1, 64]; E not a multiple of 32 or above 1024; Nq or Nx >= 2^24; Q or X
+ * not 16-byte aligned.  SEGCLIP_ERR_INVALID: a workspace smaller than segclip_retrieval_topk_ws_bytes says (nothing is launched).
+ * Bound: 2 Nq Nx E flop at the f32-MFMA rate, as the count pass; the selection adds, per row and tile, two LDS reads and a
+ * ballot where nothing is admitted and ~30 lane-exchange stages where something is.
+ * ------------------------------------------------------------------------------------------ */
+int64_t segclip_retrieval_topk_ws_bytes(int64_t Nq, int64_t Nx, int64_t k, int64_t splits);
+int segclip_retrieval_topk(const float* Q, const float* X, int64_t Nq, int64_t Nx, int64_t E, int64_t k, int64_t splits, int32_t* idx,
+                           float* val, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Front end of training (train_frontend.inc): decoded uint8 images and int32 segment maps -> the model's `image` and
  * `image_seg`, each in ONE launch for a batch of mixed sizes.  Both entries are integer algorithms and reproduce the
  * reference's CPU pipeline to the last bit.

@@ -26,7 +26,7 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".segmentation", __name__)
         return mod if name == "segmentation" else getattr(mod, name)
-    if name in ("RetrievalEvaluator", "retrieval"):   # image-text retrieval evaluation, likewise
+    if name in ("RetrievalEvaluator", "ZeroShotClassifier", "retrieval"):   # retrieval evaluation and search, likewise
         import importlib
         mod = importlib.import_module(".retrieval", __name__)
         return mod if name == "retrieval" else getattr(mod, name)

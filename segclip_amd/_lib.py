@@ -179,6 +179,8 @@ SIGNATURES = {
     "segclip_retrieval_thresholds": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "segclip_retrieval_count": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
     "segclip_retrieval_hist": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp]),
+    "segclip_retrieval_topk_ws_bytes": (i64, [i64, i64, i64, i64]),
+    "segclip_retrieval_topk": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
     "segclip_train_images_from_u8":(C.c_int, [vp, i64, i64, i64, vp, vp, vp]),
     "segclip_train_patch_labels": (C.c_int, [vp, i64, i64, i64, vp, vp]),
     "segclip_multi_cast_bf16": (C.c_int, [vp, vp, vp, i64, vp]),

@@ -921,6 +921,14 @@ void fill_common(Args& a, const segclip_attn_desc* d) {
 
 }  // namespace
 
+// the per-device state above for the other translation units (common.h)
+bool segclip_current_device(int* index, int* ncu) {
+  Device dv;
+  if (!current_device(dv)) return false;
+  *index = dv.index; *ncu = dv.ncu;
+  return true;
+}
+
 extern "C" size_t segclip_attn_stats_bytes(const segclip_attn_desc* d) {
   if (d->dtype == SEGCLIP_BF16) return (size_t)d->B * d->H * d->Tq * sizeof(float);
   return (size_t)d->B * d->H * d->Tq * d->Tk * sizeof(float);

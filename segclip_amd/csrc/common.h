@@ -23,6 +23,8 @@ void segclip_set_error(const char* fmt, ...);
 void segclip_gemm_route_note(int family, bool a_ks, bool b_ks, int tile_m, int tile_n, int splits, int variant);
 // host: the same for the attention entries (segclip_attn_last_route; capi.cpp).  Clears the other direction's field.
 void segclip_attn_route_note(bool bwd, int kernel, int tiles, int variant);
+// host: the current device (below 64) and its CU count, read once per device (attention.hip); false where there is none
+bool segclip_current_device(int* index, int* ncu);
 
 #define SEGCLIP_CHECK_LAUNCH(name)                                              \
   do {                                                                          \

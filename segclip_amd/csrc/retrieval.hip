@@ -85,6 +85,48 @@ __device__ __forceinline__ void slice_store(float* lds, int tid, const float4 (&
   }
 }
 
+// acc = the [BT x BT] tile  A[m0.., :] B[n0.., :]^T  of two row-major (rows, E) matrices: gemm_f32.hip's 128 x 128 x 32 schedule
+// (the next slice travels in registers while this one is multiplied).  Every entry is the k-ordered fmaf chain from 0.  C/D map
+// of a 32 x 32 MFMA tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5); acc[i][j] is the tile at rows
+// wm * 64 + i * 32, columns wn * 64 + j * 32.  Ends behind a barrier: As and Bs are free again.
+__device__ __forceinline__ void tile_product(const float* __restrict__ A, int m0, int M, const float* __restrict__ B, int n0,
+                                             int N, int E, float* As, float* Bs, f32x16 (&acc)[2][2]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lk = lane >> 5;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  float4 ra[NCH], rb[NCH];
+  slice_load(A, m0, M, 0, E, tid, ra);
+  slice_load(B, n0, N, 0, E, tid, rb);
+  for (int k0 = 0; k0 < E; k0 += BK) {
+    slice_store(As, tid, ra);
+    slice_store(Bs, tid, rb);
+    __syncthreads();
+    if (k0 + BK < E) {
+      slice_load(A, m0, M, k0 + BK, E, tid, ra);
+      slice_load(B, n0, N, k0 + BK, E, tid, rb);
+    }
+#pragma unroll 4
+    for (int kk = 0; kk < BK; kk += 2) {
+      float x[2], y[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) x[i] = As[(kk + lk) * PITCH + wm * 64 + i * 32 + li];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) y[j] = Bs[(kk + lk) * PITCH + wn * 64 + j * 32 + li];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[i], y[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+}
+
 struct CountArgs {
   const float* V; const float* T; const int32_t* g; const float* thr; const float* best;
   int32_t* rank_t2i; int32_t* rank_i2t;
@@ -92,8 +134,7 @@ struct CountArgs {
 };
 
 // blockIdx.x: a tile of 128 captions, kept for the workgroup's life; blockIdx.y strides over the tiles of 128 images.
-// The product is gemm_f32.hip's 128 x 128 x 32 schedule (the next slice travels in registers while this one is multiplied).
-// Epilogue, C/D map of a 32 x 32 tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  A lane owns two columns:
+// Epilogue on tile_product's accumulators.  A lane owns two columns:
 // its column hits are summed in registers.  The hits of a row lie in the 32 lanes of one half-wave: a ballot counts them.
 // Both go to per-tile counters in LDS, and every row and column with hits gets ONE global integer add.
 __global__ __launch_bounds__(NT) void retrieval_count_kernel(CountArgs a) {
@@ -119,38 +160,8 @@ __global__ __launch_bounds__(NT) void retrieval_count_kernel(CountArgs a) {
       s_col[c] = 0;
     }
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    float4 ra[NCH], rb[NCH];
-    slice_load(a.T, m0, a.Nt, 0, a.E, tid, ra);
-    slice_load(a.V, n0, a.Ni, 0, a.E, tid, rb);
-    for (int k0 = 0; k0 < a.E; k0 += BK) {
-      slice_store(As, tid, ra);
-      slice_store(Bs, tid, rb);
-      __syncthreads();   // (the first one also publishes s_thr, s_g, s_best and the zeroed counters)
-      if (k0 + BK < a.E) {
-        slice_load(a.T, m0, a.Nt, k0 + BK, a.E, tid, ra);
-        slice_load(a.V, n0, a.Ni, k0 + BK, a.E, tid, rb);
-      }
-#pragma unroll 4
-      for (int kk = 0; kk < BK; kk += 2) {
-        float x[2], y[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) x[i] = As[(kk + lk) * PITCH + wm * 64 + i * 32 + li];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) y[j] = Bs[(kk + lk) * PITCH + wn * 64 + j * 32 + li];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[i], y[j], acc[i][j], 0, 0, 0);
-      }
-      __syncthreads();
-    }
+    // (the product's first barrier also publishes s_thr, s_g, s_best and the zeroed counters)
+    tile_product(a.T, m0, a.Nt, a.V, n0, a.Ni, a.E, As, Bs, acc);
 
     int col_hits[2] = {0, 0};
     float bst[2];
@@ -297,3 +308,5 @@ extern "C" int segclip_retrieval_hist(const int32_t* rank_t2i, int32_t* rank_i2t
   SEGCLIP_CHECK_LAUNCH("retrieval_hist");
   return 0;
 }
+
+#include "retrieval_topk.inc"   // segclip_retrieval_topk: the same product with a selecting epilogue

@@ -2800,6 +2800,31 @@ def retrieval_hist(rank_t2i, rank_i2t, n_cap):
     return hist_t2i, hist_i2t
 
 
+def retrieval_topk(queries, gallery, k, splits=0):
+    """segclip_retrieval_topk: queries (Nq, E), gallery (Nx, E), contiguous fp32 -> (idx (Nq, k) int32, val (Nq, k) fp32): per
+    query the first min(k, Nx) gallery rows under "higher <q, x> first, equal scores: lower index first" with their scores,
+    then idx = -1, val = -inf.  No (Nq, Nx) array exists and nothing synchronises.  splits = 0 lets the library choose the
+    number of partial lists; a test passes another value to hold every partition to one result, nothing else should."""
+    L.require_cuda(queries, gallery)
+    if queries.dtype != torch.float32 or gallery.dtype != torch.float32:
+        raise TypeError(f"retrieval_topk: fp32 queries and gallery, got {queries.dtype} and {gallery.dtype}")
+    if queries.dim() != 2 or gallery.dim() != 2 or queries.shape[1] != gallery.shape[1]:
+        raise ValueError(f"retrieval_topk: queries (Nq, E) and gallery (Nx, E) of equal E; got {tuple(queries.shape)}, "
+                         f"{tuple(gallery.shape)}")
+    if not queries.is_contiguous() or not gallery.is_contiguous():
+        raise ValueError("retrieval_topk: queries and gallery are contiguous")
+    (Nq, E), Nx, k, splits = queries.shape, gallery.shape[0], int(k), int(splits)
+    lib = L.load()
+    ws_bytes = lib.segclip_retrieval_topk_ws_bytes(Nq, Nx, k, splits)
+    if ws_bytes < 0:
+        L.check(ws_bytes, "retrieval_topk")
+    idx, val = _empty((Nq, k), torch.int32, queries), _empty((Nq, k), torch.float32, queries)
+    ws = _empty((ws_bytes // 8,), torch.int64, queries) if ws_bytes else None
+    L.check(lib.segclip_retrieval_topk(L.ptr(queries), L.ptr(gallery), Nq, Nx, E, k, splits, L.ptr(idx), L.ptr(val), L.ptr(ws),
+                                       ws_bytes, L.stream()), "retrieval_topk")
+    return idx, val
+
+
 # ---------------------------------------------------------------- front end of training (train_frontend.inc)
 TRAIN_SOURCE_COLS = 13    # int64 columns of one row of the source table of segclip_train_images_from_u8
 TRAIN_MAP_COLS = 9        # int64 columns of one row of the map table of segclip_train_patch_labels

@@ -310,14 +310,15 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     return miou
 
 
-def eval_retrieval_epoch(args, model, device, image_batches, text_batches, chunk=256):
+def eval_retrieval_epoch(args, model, device, image_batches, text_batches, chunk=256, topk=None):
     """The retrieval score of a checkpoint on a multi-caption set (the layout of dataloaders/dataloader_coco_retrieval.py:85-104;
     the similarity is modules/modeling.py:338-372 without the logit scale): {"t2i": {R1, R5, R10, MedianR, MeanR}, "i2t": {...}}.
     image_batches: an iterable of (B, 1, 3, H, W) or (B, 3, H, W) images; text_batches: an iterable of (input_ids, segment_ids,
     input_mask, image_index) with image_index[b] the number of the caption's image in the order image_batches gives them
     (retrieval.image_index_from_cut_off_points turns the loader's cut_off_points into it).  The embeddings, ranks and
     histograms stay on the device until the end.  With several ranks gather the embeddings and use
-    RetrievalEvaluator.add_embeddings instead."""
+    RetrievalEvaluator.add_embeddings instead.  topk=K adds a "topk" entry, RetrievalEvaluator.topk(K) as CPU copies:
+    {"t2i": (idx (Nt, K), val (Nt, K)), "i2t": (idx (Ni, K), val (Ni, K))}, what was retrieved for every caption and image."""
     from .retrieval import RetrievalEvaluator
     model = _unwrap(model)
     model.eval()
@@ -334,4 +335,6 @@ def eval_retrieval_epoch(args, model, device, image_batches, text_batches, chunk
             m = out[key]
             logger.info("%s: R@1: %.1f - R@5: %.1f - R@10: %.1f - Median R: %.1f - Mean R: %.1f", name, m["R1"], m["R5"],
                         m["R10"], m["MedianR"], m["MeanR"])
+    if topk is not None:
+        out["topk"] = {key: tuple(t.cpu() for t in pair) for key, pair in evaluator.topk(topk).items()}
     return out
