@@ -141,6 +141,7 @@ int segclip_reduce_multi(const segclip_reduce_entry* entries, int n, int kind, v
  * ws: segclip_layernorm_bwd_ws_bytes(rows, cols) bytes of scratch.
  * dgamma == NULL: the final reduction is left to the caller - ws then holds segclip_layernorm_bwd_ws_bytes / (3*cols*4)
  *      partial rows of [dgamma | dbeta | dres column sums] (3*cols floats each), see segclip_reduce_multi.
+ * rows == 0: dgamma, dbeta and dres_colsum (where passed) are zeroed; dgamma == NULL: the one partial row of ws is.
  * ------------------------------------------------------------------------------------------ */
 int segclip_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                           float* rstd, int64_t rows, int64_t cols, float eps, int x_dtype, int y_dtype,

@@ -428,7 +428,15 @@ static int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const 
   SEGCLIP_REQUIRE(cols % 4 == 0 && cols <= MAXV * 256, "layernorm: cols=%lld must be a multiple of 4 and <= %d",
                   (long long)cols, MAXV * 256);
   SEGCLIP_REQUIRE(ws != nullptr, "layernorm_bwd: workspace required");
-  if (rows == 0) return 0;
+  if (rows == 0) {   // no row: the sums over the rows are 0 (dgamma == NULL: the one partial row the caller combines)
+    float* const outs[4] = {dgamma, dgamma ? dbeta : nullptr, dgamma ? dres_colsum : nullptr, dgamma ? nullptr : (float*)ws};
+    for (int k = 0; k < 4; ++k) {
+      if (outs[k] == nullptr || cols == 0) continue;
+      const hipError_t e = hipMemsetAsync(outs[k], 0, (size_t)(k == 3 ? 3 : 1) * cols * sizeof(float), (hipStream_t)stream);
+      SEGCLIP_REQUIRE(e == hipSuccess, "layernorm_bwd: memset failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+  }
   const int nb = ln_blocks(rows);
   const bool has_res = dres != nullptr, has_dx2 = dx_bf16 != nullptr;
   SEGCLIP_REQUIRE(x_dtype == SEGCLIP_F32 || x_dtype == SEGCLIP_BF16, "layernorm_bwd: bad x dtype");
