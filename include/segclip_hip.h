@@ -494,6 +494,38 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
                       int64_t* areas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Background-threshold sweep (segment_sweep.inc): segclip_seg_label_map_rescaled for T values of bg_thresh in ONE launch, for
+ * tuning the one hyperparameter of the zero-shot evaluation (the reference's configurations use 0.80, 0.25 and 0.65:
+ * the dataset files of seg_segmentation/configs/_base_/datasets, test_cfg) without repeating towers, front end and group tables per value.
+ * The arguments, descriptor tables, tile, range checks and limits are those of segclip_seg_label_map_rescaled; the background
+ * class is implied (no with_bg argument, N + 1 classes).
+ *   thresholds : HOST pointer to T finite, strictly increasing floats, 1 <= T <= 16; they travel in the kernel arguments
+ *   labels     : NULL, or T planes of labels_bytes each; plane t is, byte for byte, what segclip_seg_label_map_rescaled writes
+ *                with bg_thresh = thresholds[t] (the label offsets of `images` are offsets in a plane; dword stores where
+ *                plane base + offset is a multiple of 4, byte stores otherwise)
+ *   gt, areas  : flat uint8 of gt_bytes and (T, 3, N + 1) int64, or both NULL.  areas is ADDED to; slice t equals, integer for
+ *                integer, what segclip_seg_label_map_rescaled adds with bg_thresh = thresholds[t].
+ * How.  The threshold decides only the background indicator best_score < min(bg_thresh, table_max[window]) of a (window, group)
+ * pair, which over ascending thresholds can only switch on; the class-0 logit is a monotone fp32 function of the indicators and
+ * the other classes do not see the threshold.  So a pixel has one foreground label f (first maximum over the classes >= 1)
+ * and one switch index s: its label is f for t < s and 0 for t >= s.  Covers, taps and the foreground scan run once per pixel
+ * (the device functions of the single-threshold entry); the class-0 logit is evaluated per threshold until it is not below the
+ * foreground maximum (class 0 comes first and wins ties, as the strict > scan decides).  Areas: LDS buckets by (s, class),
+ * turned into the T slices by a prefix sum at flush time, one integer global add per touched counter.
+ *   LDS: tables and cover lists as the single-threshold entry, plus (2 (T + 1) + 1) (N + 1) counters: at most 83 KiB dynamic
+ *   (the limit is raised once per device when a launch needs more than 56 KiB).
+ *   Bound: as the single-threshold entry (covers and class scan) plus T bytes of label stores per pixel; design figure.
+ * SEGCLIP_ERR_INVALID (no launch): T < 1, thresholds NULL, a non-finite or non-increasing threshold.
+ * SEGCLIP_ERR_UNSUPPORTED (no launch): T > 16, N + 1 > 256, max_image_windows > 64.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                         const int32_t* best_class, const float* best_score, const int32_t* windows,
+                                         const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
+                                         int64_t max_image_windows, int64_t G, int64_t N, const float* thresholds, int64_t T,
+                                         uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes,
+                                         int ignore_index, int reduce_zero_label, int64_t* areas, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Flip and multi-scale test-time augmentation (segment_aug.inc): mmseg's MultiScaleFlipAug + EncoderDecoder.aug_test, the
  * wrapper of every test configuration of the reference (seg_segmentation/configs/_base_/datasets/pascal_voc12.py:24-26,
  * evaluation/builder.py:121-123): every view is segmented, its logits are resized to the original size and passed through a

@@ -167,6 +167,8 @@ SIGNATURES = {
                                      vp, vp]),
     "segclip_seg_label_map_rescaled": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                                  vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_label_map_rescaled_sweep": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, i64,
+                                                       vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_seg_label_map_views": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                               vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_seg_view_probs": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,

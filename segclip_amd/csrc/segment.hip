@@ -6,6 +6,9 @@
 // one-hot, (H, W, N) product and (N + 1, H, W) logit volume never have to exist: segclip_seg_group_table builds the tables
 // (latency-bound: G * N dot products of 512 per window), segclip_seg_label_map interpolates G numbers per pixel, takes the
 // first maximum and looks one row up (bound: 1-2 bytes of HBM writes per pixel).
+// The .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
+// the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
+// uint8 front end (segment_frontend.inc), rendering (segment_render.inc) and the training front end (train_frontend.inc).
 #include "common.h"
 
 #include <atomic>
@@ -294,6 +297,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 }
 
 #include "segment_eval.inc"
+#include "segment_sweep.inc"
 #include "segment_aug.inc"
 #include "segment_frontend.inc"
 #include "segment_render.inc"
@@ -430,6 +434,72 @@ extern "C" int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t so
   const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
   hipLaunchKernelGGL(seg_rescaled_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_label_map_rescaled");
+  return 0;
+}
+
+extern "C" int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_floats, const float* table,
+                                                    const float* table_max, const int32_t* best_class, const float* best_score,
+                                                    const int32_t* windows, const int64_t* images, int64_t n_windows, int64_t B,
+                                                    int64_t n_blocks, int64_t max_image_windows, int64_t G, int64_t N,
+                                                    const float* thresholds, int64_t T, uint8_t* labels, int64_t labels_bytes,
+                                                    const uint8_t* gt, int64_t gt_bytes, int ignore_index, int reduce_zero_label,
+                                                    int64_t* areas, void* stream) {
+  const char* what = "seg_label_map_rescaled_sweep";
+  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_bytes >= 0 && gt_bytes >= 0,
+                  "%s: sizes must not be negative, N >= 1", what);
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
+  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
+  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
+  SEGCLIP_REQUIRE(thresholds && T >= 1, "%s: thresholds is a host array of T >= 1 floats", what);
+  if (T > SEG_SWEEP_MAX_T) {
+    segclip_set_error("%s: %lld thresholds, at most %d (they travel in the kernel arguments)", what, (long long)T, SEG_SWEEP_MAX_T);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  for (int64_t t = 0; t < T; ++t)
+    SEGCLIP_REQUIRE(std::isfinite(thresholds[t]) && (t == 0 || thresholds[t] > thresholds[t - 1]),
+                    "%s: thresholds must be finite and strictly increasing (entry %lld)", what, (long long)t);
+  const int64_t C = N + 1;
+  if (C > SEG_MAX_CLASSES) {
+    segclip_set_error("%s: %lld classes, at most %d (uint8 labels, per-class counters in LDS)", what, (long long)C, SEG_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_image_windows > SEG_MAX_IMG_WIN) {
+    segclip_set_error("%s: %lld windows per image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0 || n_blocks == 0) return 0;
+  SegSweepArgs s;
+  SegEvalArgs& a = s.e;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
+  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_bytes; a.gt_bytes = gt_bytes;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = 1; a.bg_thresh = 0.f;
+  a.labels = labels; a.gt = gt; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  s.T = (int)T;
+  for (int t = 0; t < SEG_SWEEP_MAX_T; ++t) s.thr[t] = t < T ? thresholds[t] : 0.f;
+  // LDS: tables and cover lists as in segclip_seg_label_map_rescaled, then the (T + 1, C) prediction and intersection buckets
+  // and the C label counters
+  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
+  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
+  int64_t want = per_image * G * N;
+  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
+  a.tab_floats = (int)((want + 1) & ~1ll);
+  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2 + (size_t)(2 * (T + 1) + 1) * C * 4;
+  SEGCLIP_REQUIRE(lds <= SEG_SWEEP_LDS_BYTES, "%s: internal LDS plan of %lld bytes", what, (long long)lds);
+  if (lds > 56 * 1024) {  // beside 3 KiB of static LDS: past the 64 KiB a kernel gets without asking
+    static std::atomic<bool> raised[64];
+    int dev = 0;
+    SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: cannot query the current device", what);
+    if (!raised[dev]) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seg_sweep_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, SEG_SWEEP_LDS_BYTES);
+      SEGCLIP_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
+      raised[dev] = true;
+    }
+  }
+  hipLaunchKernelGGL(seg_sweep_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, s);
+  SEGCLIP_CHECK_LAUNCH(what);
   return 0;
 }
 

@@ -2471,6 +2471,46 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     return labels
 
 
+SEG_MAX_THRESHOLDS = 16    # background thresholds of one segclip_seg_label_map_rescaled_sweep launch
+
+
+def seg_label_map_sweep(soft_attn, tables, windows, images, n_blocks, max_image_windows, thresholds, labels=None, gt=None,
+                        areas=None, ignore_index=255, reduce_zero_label=False):
+    """The threshold sweep (segclip_seg_label_map_rescaled_sweep): seg_label_map_rescaled with the background class for every
+    bg_thresh of `thresholds` (T host floats, finite and strictly increasing, T <= 16) in one launch -> `labels` ((T, labels_bytes)
+    uint8: plane t is the single call's output at thresholds[t], or None) and, with `gt`, the (T, 3, N + 1) int64 `areas` added
+    to in place, slice t as the single call adds it.  The library checks the thresholds: a bad list is a RuntimeError, more than
+    16 an L.Unsupported."""
+    table, tmax, bcls, bsc = tables
+    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images, labels, gt, areas)
+    nW, G, N = table.shape
+    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
+            or images.dtype != torch.int64 or bcls.dtype != torch.int32:
+        raise TypeError("seg_label_map_sweep: fp32 soft_attn / tables, int32 window list, int64 image table")
+    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
+            or bcls.numel() != nW * G or bsc.numel() != nW * G:
+        raise ValueError("seg_label_map_sweep: shapes do not agree")
+    thr = [float(v) for v in thresholds]
+    T = len(thr)
+    for name, t in (("labels", labels), ("gt", gt)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"seg_label_map_sweep: {name} is a contiguous uint8 tensor")
+    if labels is not None and (labels.dim() != 2 or labels.shape[0] != T):
+        raise ValueError("seg_label_map_sweep: labels is a (T, labels_bytes) uint8 tensor, one plane per threshold")
+    if (gt is None) != (areas is None):
+        raise ValueError("seg_label_map_sweep: gt and areas go together")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (T, 3, N + 1)):
+        raise ValueError("seg_label_map_sweep: areas is a contiguous (T, 3, N + 1) int64 tensor")
+    host = (L.C.c_float * max(T, 1))(*thr)
+    keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, images))
+    L.check(L.load().segclip_seg_label_map_rescaled_sweep(
+        L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
+        G, N, L.C.cast(host, L.C.c_void_p), T, L.ptr(labels), labels.shape[1] if labels is not None else 0, L.ptr(gt),
+        gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(areas), L.stream()),
+        "seg_label_map_sweep")
+    return labels
+
+
 SEG_MAX_VIEWS = 16         # views of one image in segclip_seg_label_map_views
 SEG_MAX_IMAGE_WINDOWS = 64  # windows of one image, over all its views
 SEG_FLIP_H, SEG_FLIP_V = 1, 2

@@ -28,11 +28,17 @@ that are already pre-processed and flipped, and predict_proba_* return the mean 
 an entry of the plan, so the windows of all views share the tower calls, and one kernel (csrc/segment_aug.inc) rescales
 every view's logits, takes their soft-max, mirrors, averages and takes the first maximum per output pixel.
 
+The threshold sweep (bg_thresh is the one hyperparameter of the evaluation that is tuned per dataset and checkpoint: the
+reference's configurations use 0.80, 0.25 and 0.65): SegSweepEvaluator scores up to 16 ascending thresholds in one pass - the
+towers, the front end and the group tables run once, and one kernel (csrc/segment_sweep.inc) writes every threshold's label
+map and areas, bit for bit those of one SegEvaluator per threshold.  Not swept: the augmented path, the dense logits, the
+top-5 mask.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
-image without augmentation is one view with flags 0.  _list_forward (arg-max of the logits, group maps) and _views_forward
-(soft-max mean, dense twin) are the two kernel calls over the same steps.
+image without augmentation is one view with flags 0.  _list_forward (arg-max of the logits, group maps), _sweep_forward
+(the same for a list of thresholds) and _views_forward (soft-max mean, dense twin) are the kernel calls over the same steps.
 
 Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; without augmentation the arg-max
 is taken of the logits here, which can differ only where fp32 exp rounds two different logits to one value (the augmented
@@ -44,6 +50,7 @@ to the picture's size.  Text is not drawn: input_pred_label returns the anchor p
 """
 import collections
 import colorsys
+import math
 
 import torch
 
@@ -499,6 +506,23 @@ class SegInference:
         gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=src.device))
         return labels, _split_maps(gmaps, offs, out_shapes), n_groups
 
+    def _sweep_forward(self, src, out_shapes, thresholds, gts=None, areas=None, ignore_index=255, reduce_zero_label=False,
+                       want_labels=True):
+        """_list_forward for every background threshold of a list at once (segclip_seg_label_map_rescaled_sweep): one pass of
+        the towers, -> [(T, oh_i, ow_i) uint8 labels], views of one (T, bytes) buffer, or None."""
+        out_shapes = _out_shapes(src, out_shapes)
+        self._check_classes()
+        plan, dwin, _ = self._device_plan(src)
+        soft, tables, win_off, _ = self._list_towers(src, plan, dwin)
+        rows = self._image_rows(src, plan, win_off, out_shapes, gts is not None)
+        images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, src.device)
+        labels = torch.empty(len(thresholds), nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
+        ops.seg_label_map_sweep(soft, tables, dwin, images, n_blocks, most, thresholds, labels=labels, gt=_flat_gts(gts), areas=areas,
+                                ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+        if labels is None:
+            return None
+        return [labels[:, o:o + oh * ow].view(-1, oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
+
     def _views_forward(self, src, out_shapes, gts=None, areas=None, ignore_index=255, reduce_zero_label=False, want_labels=True,
                        dense=False):
         """The augmented list call: the mean over an image's views of the soft-max of the rescaled logits, its first maximum
@@ -777,3 +801,85 @@ class SegEvaluator:
 
     def compute(self):
         return self.metrics_from_areas(self.areas.cpu())
+
+
+def check_thresholds(thresholds):
+    """The background thresholds of a sweep -> a list of floats: 1 .. ops.SEG_MAX_THRESHOLDS finite values, strictly increasing
+    (the kernel's switch index needs the order; a duplicate would only repeat a slice)."""
+    try:
+        thr = [float(v) for v in thresholds]
+    except TypeError:
+        raise ValueError(f"thresholds is a sequence of numbers, got {thresholds!r}") from None
+    if len(thr) < 1:
+        raise ValueError("thresholds is empty")
+    if len(thr) > ops.SEG_MAX_THRESHOLDS:
+        raise ValueError(f"thresholds has {len(thr)} values, at most {ops.SEG_MAX_THRESHOLDS} per sweep (split the list)")
+    # what the kernel compares is the fp32 value: two numbers that round to one float are duplicates
+    thr = torch.tensor(thr, dtype=torch.float64).float().tolist()
+    if any(not math.isfinite(v) for v in thr):
+        raise ValueError(f"thresholds must be finite, got {thr}")
+    for a, b in zip(thr, thr[1:]):
+        if b == a:
+            raise ValueError(f"thresholds holds the duplicate {a} (as fp32)")
+        if b < a:
+            raise ValueError(f"thresholds must be sorted in ascending order, got {b} after {a}")
+    return thr
+
+
+class SegSweepEvaluator:
+    """SegEvaluator for a list of background thresholds in ONE pass: towers, front end and group tables run once per update,
+    and the fused kernel (csrc/segment_sweep.inc) adds every image's areas to `areas`, a (T, 3, C) int64 device tensor whose
+    slice t is, integer for integer, the `areas` of SegEvaluator(SegInference(..., bg_thresh=thresholds[t])).  For tuning
+    bg_thresh on a new dataset or checkpoint (the reference's configurations use 0.80, 0.25 and 0.65).
+
+    seg.bg_thresh is IGNORED here: the thresholds of the list take its place.  seg must have with_bg=True (without a background
+    class there is no threshold).  Not covered: test-time augmentation (aug= raises: the augmented path takes a soft-max that
+    includes the background logit, so it would need accumulators per threshold), the dense logits, more than 16 thresholds per
+    sweep (split the list over two evaluators) and a sweep of the top-5 mask."""
+
+    def __init__(self, seg, thresholds, ignore_index=255, reduce_zero_label=False):
+        if not seg.with_bg:
+            raise ValueError("SegSweepEvaluator: seg must have with_bg=True (the threshold decides the background class)")
+        self.thresholds = check_thresholds(thresholds)
+        self.seg, self.ignore_index, self.reduce_zero_label = seg, int(ignore_index), bool(reduce_zero_label)
+        self.areas = torch.zeros(len(self.thresholds), 3, seg.num_classes, dtype=torch.int64, device=seg.text_embedding.device)
+
+    def reset(self):
+        self.areas.zero_()
+
+    @torch.no_grad()
+    def update(self, imgs, gts, return_labels=False):
+        """As SegEvaluator.update; with return_labels one (T, oh_i, ow_i) uint8 tensor per image."""
+        SegEvaluator._check_gts(imgs, gts)
+        return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
+
+    @torch.no_grad()
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None):
+        """As SegEvaluator.update_raw, without aug."""
+        if aug is not None:
+            raise ValueError("SegSweepEvaluator: aug is not supported (the augmented path needs accumulators per threshold); "
+                             "use one SegEvaluator per threshold")
+        SegEvaluator._check_gts(raws, gts)
+        return self._forward(_RawImages(raws, transform, net_sizes), gts, return_labels)
+
+    def _forward(self, src, gts, return_labels):
+        return self.seg._sweep_forward(src, [tuple(g.shape) for g in gts], self.thresholds, gts=list(gts), areas=self.areas,
+                                       ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
+                                       want_labels=return_labels)
+
+    @staticmethod
+    def sweep_from_areas(areas, thresholds):
+        """(T, 3, C) integer CPU tensor -> dict(thresholds, metrics [SegEvaluator.metrics_from_areas per threshold],
+        best=(index, threshold, mIoU)): the highest mIoU, the lowest threshold among equal ones (a NaN mIoU never wins)."""
+        thr = [float(v) for v in thresholds]
+        if areas.dim() != 3 or areas.shape[0] != len(thr) or areas.shape[1] != 3:
+            raise ValueError(f"areas is a (T, 3, C) tensor for {len(thr)} thresholds, got {tuple(areas.shape)}")
+        metrics = [SegEvaluator.metrics_from_areas(a) for a in areas]
+        best = 0
+        for t, m in enumerate(metrics):
+            if m["mIoU"] > metrics[best]["mIoU"] or (math.isnan(metrics[best]["mIoU"]) and not math.isnan(m["mIoU"])):
+                best = t
+        return dict(thresholds=thr, metrics=metrics, best=(best, thr[best], metrics[best]["mIoU"]))
+
+    def compute(self):
+        return self.sweep_from_areas(self.areas.cpu(), self.thresholds)

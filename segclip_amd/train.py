@@ -5,6 +5,7 @@ the hot path, with the per-iteration host round-trips removed.
   prep_optimizer(args, model, t_total, ...)        main_task_align.py:175-256   (8 name-routed param groups)
   train_epoch(epoch, args, model, loader, ...)     main_task_align.py:292-359
   eval_epoch(args, model, device, n_gpu, ...)      main_task_align.py:361-370, main_seg_zeroshot.py:122-167 (mIoU * 100)
+  sweep_bg_thresh(args, model, device, n_gpu, ...) eval_epoch for a list of bg_thresh values in one pass (test_cfg's one knob)
   TrainTail                                        :326-347 fused: clip_grad_norm_ -> AdaptAdamW.step (skipped on the
                                                    device when the loss is NaN) -> zero_grad -> clamp(logit_scale)
 
@@ -308,6 +309,35 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)
     return miou
+
+
+def sweep_bg_thresh(args, model, device, n_gpu, batches, text_tokens, thresholds, test_cfg=None, transform=None):
+    """eval_epoch for a list of background thresholds in one pass over `batches` (segmentation.SegSweepEvaluator: towers and
+    group tables run once, the fused kernel scores every threshold): -> the evaluator's compute() dict (thresholds, metrics
+    per threshold, best = (index, threshold, mIoU), the lowest threshold among equal mIoU).  batches, text_tokens, test_cfg
+    and transform as in eval_epoch; the background class is implied, test_cfg's bg_thresh is ignored and test_cfg['aug'] is
+    refused (the augmented path is not swept)."""
+    from .segmentation import SegInference, SegSweepEvaluator, build_text_embedding
+    cfg = dict(test_cfg or {})
+    ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
+    if cfg.pop("aug", None) is not None:
+        raise ValueError("sweep_bg_thresh: test_cfg['aug'] is not supported: the threshold sweep has no augmented path")
+    model = _unwrap(model)
+    model.eval()
+    emb = build_text_embedding(model, text_tokens.to(device))
+    evaluator = SegSweepEvaluator(SegInference(model, emb, True, **cfg), thresholds, ignore_index, reduce_zero_label)
+    for imgs, gts in batches:
+        imgs, gts = [t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts]
+        if transform is None:
+            evaluator.update(imgs, gts)
+        else:
+            evaluator.update_raw(imgs, gts, transform)
+    out = evaluator.compute()
+    if getattr(args, "local_rank", 0) == 0:
+        for thr, m in zip(out["thresholds"], out["metrics"]):
+            logger.info("bg_thresh %.4f: mIoU %.2f, aAcc %.2f, mAcc %.2f", thr, m["mIoU"] * 100.0, m["aAcc"] * 100.0, m["mAcc"] * 100.0)
+        logger.info("best bg_thresh %.4f (mIoU %.2f)", out["best"][1], out["best"][2] * 100.0)
+    return out
 
 
 def eval_retrieval_epoch(args, model, device, image_batches, text_batches, chunk=256, topk=None):

@@ -26,8 +26,17 @@ views per image, in ONE command and alternating within every repeat:
         arg-max of the mean; three histc), the areas of the two, peak allocation, and the multi-view kernel's and the view front
         end's own time from a separate `rocprofv3 --kernel-trace --stats` child (--aug-child: five update_raw(aug=) calls and
         nothing else).
-usage: python tools/bench_seg.py [--eval | --raw | --aug] [reps=7]
-                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt]"""
+With --sweep instead: the same 64 decoded images and a list of 8 background thresholds, in ONE command and alternating within
+every repeat:
+  (vii) one SegEvaluator.update_raw (the yardstick: the single evaluation, unchanged by the sweep), one
+        SegSweepEvaluator.update_raw with the 8 thresholds, and 8 single update_raw calls (one evaluator per threshold): medians,
+        spread, the ratios sweep / single and (8 singles) / sweep, peak allocation, the clock held, whether the 8 area slices equal
+        the 8 single runs, and the sweep kernel's own time from a separate `rocprofv3 --kernel-trace --stats` child
+        (--sweep-child: five sweep and five single update_raw calls and nothing else), beside the single entry's own time.  The
+        thresholds are quantiles of the inputs' own best_score: synthetic weights score far below the reference's 0.25-0.80, where
+        every threshold is clamped by table_max and all slices are one.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep] [reps=7]
+                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt]"""
 import os
 import statistics
 import sys
@@ -44,10 +53,11 @@ from tools.clock_sampler import ClockSampler
 
 EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("--raw-child" in sys.argv[1:])
 AUG, AUG_CHILD = ("--aug" in sys.argv[1:]), ("--aug-child" in sys.argv[1:])
-ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child")]
+SWEEP, SWEEP_CHILD = ("--sweep" in sys.argv[1:]), ("--sweep-child" in sys.argv[1:])
+ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -435,6 +445,117 @@ def aug_child(model, text):
     torch.cuda.synchronize()
 
 
+def sweep_thresholds(seg, raws, gts, tf, T=8):
+    """T thresholds that decide something on synthetic weights, whose group scores lie far below the reference's 0.25-0.80 (every
+    threshold of that range is clamped by table_max, and all T slices are one): the k / (T + 1) quantiles of the best_score of
+    one pass over the inputs, rounded to fp32, duplicates dropped."""
+    from segclip_amd.segmentation import SegEvaluator, check_thresholds
+    captured = {}
+    real = ops.seg_label_map_rescaled
+
+    def capture(soft, tables, *a, **k):
+        captured["score"] = tables[3].reshape(-1).clone()
+        return real(soft, tables, *a, **k)
+
+    ops.seg_label_map_rescaled = capture
+    try:
+        with torch.no_grad():
+            SegEvaluator(seg).update_raw(raws, gts, tf)
+    finally:
+        ops.seg_label_map_rescaled = real
+    q = torch.quantile(captured["score"].double().cpu(), torch.arange(1, T + 1, dtype=torch.float64) / (T + 1))
+    return check_thresholds(sorted(set(q.float().tolist())))
+
+
+def sweep_case(model, text, n_images=64):
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator, SegSweepEvaluator
+    from tools import rocprof_roofline as rr
+    name = f"(vii) sweep {n_images} mixed sizes"
+    kw = dict(mode="slide", crop_size=(224, 224), stride=(224, 224))
+    seg = SegInference(model, text, True, bg_thresh=0.80, **kw)
+    tf = ImageTransform()
+    raws, gts = raw_inputs(seg, n_images)
+    SWEEP_THR = sweep_thresholds(seg, raws, gts, tf)
+    T = len(SWEEP_THR)
+    pixels = sum(int(g.numel()) for g in gts)
+    single = SegEvaluator(seg)
+    sweep = SegSweepEvaluator(seg, SWEEP_THR)
+    singles = [SegEvaluator(SegInference(model, text, True, bg_thresh=t, **kw)) for t in SWEEP_THR]
+
+    def all_singles():
+        for ev in singles:
+            ev.update_raw(raws, gts, tf)
+
+    ways = [("single update_raw", lambda: single.update_raw(raws, gts, tf), 2),
+            (f"sweep update_raw, {T} thresholds", lambda: sweep.update_raw(raws, gts, tf), 2),
+            (f"{T} single update_raw calls", all_singles, 1)]
+    with torch.no_grad():
+        for _, fn, _ in ways:   # warm-up, and the areas of the sweep and of the singles after the same number of calls
+            fn()
+        equal = all(bool(torch.equal(sweep.areas[t], ev.areas)) for t, ev in enumerate(singles))
+        distinct = 1 + sum(int(not torch.equal(sweep.areas[t], sweep.areas[t - 1])) for t in range(1, T))
+        for _, fn, _ in ways:
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):   # alternating: every repeat times the three ways one after the other
+            for k, (_, fn, inner) in enumerate(ways):
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: thresholds {[float(f'{t:.4g}') for t in SWEEP_THR]} (quantiles of the inputs' best_score), {pixels} output pixels, "
+        f"{seg.num_classes} classes")
+    meds = [statistics.median(t) for t in ts]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:32s} {med * 1e3:9.2f} ms (min {min(t) * 1e3:.2f}, max {max(t) * 1e3:.2f}; {REPS} x {inner} calls)  "
+            f"{n_images / med:8.1f} images/s")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts)
+    say(f"{name}: sweep / single {meds[1] / meds[0]:.4f}; ({T} singles) / sweep {meds[2] / meds[1]:.4f}; largest run-to-run spread "
+        f"{spread:.4f} of the median; clock {clk}")
+    say(f"{name}: the {T} area slices equal the {T} single runs: {equal}; {distinct} distinct slices")
+    say(f"{name}: peak allocation of one call: single {peak_of(ways[0][1]) / 2**20:8.1f} MiB, sweep {peak_of(ways[1][1]) / 2**20:8.1f} MiB, "
+        f"sweep with the {T} label planes {peak_of(lambda: sweep.update_raw(raws, gts, tf, return_labels=True)) / 2**20:8.1f} MiB")
+    # the kernel's own time: a child of this tool that only calls the sweep's update_raw, under rocprofv3 --kernel-trace --stats
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--sweep-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    for what, pat, med in (("segclip_seg_label_map_rescaled_sweep", "seg_sweep_kernel", meds[1]),
+                           ("segclip_seg_label_map_rescaled (the single entry, middle threshold)", "seg_rescaled_kernel", meds[0])):
+        rows = [r for r in table if pat in r[0]]
+        if not rows:
+            say(f"{name}: {what} alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+            continue
+        calls, us = sum(r[1] for r in rows), sum(r[2] for r in rows)
+        avg = us / calls
+        say(f"{name}: {what} alone (rocprofv3 --kernel-trace --stats, {calls} launches) {avg:9.1f} us per launch = {avg * 1e-6 / med:.4f} "
+            f"of its update_raw; {pixels / avg / 1e3:.3f} Gpixel/s")
+
+
+def sweep_child(model, text):
+    """Five sweep update_raw calls and five single ones, nothing else: what the rocprofv3 child of sweep_case traces."""
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator, SegSweepEvaluator
+    kw = dict(mode="slide", crop_size=(224, 224), stride=(224, 224))
+    seg = SegInference(model, text, True, bg_thresh=0.80, **kw)
+    raws, gts = raw_inputs(seg)
+    tf = ImageTransform()
+    thr = sweep_thresholds(seg, raws, gts, tf)
+    ev, one = SegSweepEvaluator(seg, thr), SegEvaluator(SegInference(model, text, True, bg_thresh=thr[len(thr) // 2], **kw))
+    with torch.no_grad():
+        for _ in range(5):
+            ev.update_raw(raws, gts, tf)
+            one.update_raw(raws, gts, tf)
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -449,7 +570,12 @@ if __name__ == "__main__":
     if AUG_CHILD:
         aug_child(model, text)
         sys.exit(0)
-    if AUG:
+    if SWEEP_CHILD:
+        sweep_child(model, text)
+        sys.exit(0)
+    if SWEEP:
+        sweep_case(model, text)
+    elif AUG:
         aug_case(model, text)
     elif RAW:
         raw_case(model, text)
