@@ -667,6 +667,61 @@ int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const 
                       int64_t out_bytes, int64_t* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pixel-adaptive refinement of label maps (segment_refine.inc): PAMR (Araslanov & Roth, CVPR 2020), the post-processing step
+ * with which the zero-shot segmentation systems after SegCLIP report their numbers.  THE REFERENCE HAS NO SUCH OP: the
+ * definition is this project's, stated here and restated in fp64 by tests/pamr_reference.py.
+ *
+ * Per image: picture R (h, w, 3) uint8, label map L (h, w) uint8, C <= 256 classes, the transform's mean[3] and 1 / std[3]
+ * (RGB order; with reverse_channels the picture is BGR and its channel s meets entry 2 - s, as in
+ * segclip_seg_windows_from_u8), dilations d_1 < ... < d_D, T iterations.
+ *   x_c(p)   = (R_c(p) - mean_c) / std_c
+ *   q_n(p)   = clamp(p + d o), the 8 D neighbours of p, dilation-major, o over (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1),
+ *              (1,0), (1,1) in (row, column) order; coordinates clamped to the picture (replicate padding)
+ *   sigma_c(p) = the unbiased standard deviation (divisor 9 D - 1) over the 8 D values x_c(q_n(p)) and D copies of x_c(p)
+ *   a(p, n)  = -(1/3) sum_c |x_c(p) - x_c(q_n(p))| / (1e-8 + 0.1 sigma_c(p));   w(p, .) = softmax_n a(p, n)
+ *   m0_k(p)  = [L(p) = k] for k < C;   m(t+1)_k(p) = sum_n w(p, n) mt_k(q_n(p))
+ *   L'(p)    = the smallest k that attains max_k mT_k(p)
+ *   T = 0 gives L' = L.  A byte >= C belongs to no plane.  A pixel whose planes are all zero keeps its input byte.
+ * x enters through differences to the centre only, so the mean cancels (it is taken for the definition's sake), and sigma is
+ * formed from the integer byte differences d to the centre, exactly: var = (9 D sum d^2 - (sum d)^2) / (9 D (9 D - 1)) / std^2
+ * with D zeros for the centre copies - never E[x^2] - E[x]^2 of the normalised values.  All other math is fp32; a pixel's sum
+ * over n runs in the order of n with fused multiply-adds and there are no float atomics: two calls give the same bits.
+ *
+ *   images   : (B, 8) int64 rows on the device: 0 address of the picture (uint8, HWC, 3 interleaved channels)  1 h  2 w
+ *              3 row stride in bytes (>= 3 w)  4 offset of the image's h * w bytes in `labels` AND `out` (and its pixel index
+ *              in the workspace)  5 offset of its h * w bytes in `gt`, or -1  6 its first workgroup = the sum of
+ *              ceil(h * w / 256) over the images before it  7 0
+ *   n_blocks : the sum of ceil(h * w / 256) over all images;  max_side: the caller's bound on every h and w
+ *   labels   : flat uint8 of labels_bytes, read only;  out: flat uint8 of out_bytes = labels_bytes, must not overlap labels
+ *   gt/areas : optional flat uint8 ground truth and the (3, C) int64 areas of segclip_seg_areas, ADDED to for the refined
+ *              labels by the last kernel (integer adds: no order dependence)
+ *   probs    : optional, B = 1 only: (C, h, w) fp32, the final planes mT (cleared, then written; for tests and inspection)
+ *   ws       : segclip_seg_refine_ws_bytes(labels_bytes, B, D) bytes, 16-byte aligned; not needed for T = 0.  It does NOT
+ *              depend on C: the planes of different classes never meet before the arg-max, so they pass through the
+ *              iterations in chunks of 8, in one fp32 buffer pair of 8 planes (two float4 per pixel), with a running (best value, best
+ *              label) pair per pixel.  Only labels present in an image carry a non-zero plane: a 256-bit presence map per
+ *              image is built on the device, the present labels get compact ids in ascending order, and the workgroups of a
+ *              chunk beyond an image's label count exit at once.
+ *   The entry enqueues the whole sequence without a host synchronisation: two clears, the weights kernel (once), and
+ *   ceil(C / 8) * T step kernels; the first step reads the label bytes (no one-hot pass), the last one of an image's last
+ *   chunk writes the label and counts the areas.
+ *   Every table row is range-checked on the device: an image with a null address, h or w outside [1, min(max_side, 2^15 - 1)],
+ *   a stride below 3 w or offsets inconsistent with labels_bytes is SKIPPED (nothing of it read, written or counted); with gt
+ *   offsets inconsistent with gt_bytes it is refined but not counted.
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: D outside 1..6, a dilation outside 1..32 or not increasing,
+ *   T outside 0..32, C outside 1..256, max_side outside [1, 2^15), a workspace smaller than ws_bytes.  SEGCLIP_ERR_INVALID:
+ *   out overlapping labels, out_bytes != labels_bytes, probs with B != 1, gt without areas, missing pointers.
+ *   Traffic per pixel, iteration and chunk of 8 planes: 32 D bytes of weights + 32 bytes of planes written from / to memory,
+ *   and 8 D taps of 32 bytes served by the caches (dilations up to 32: an LDS halo tile does not pay).
+ * ------------------------------------------------------------------------------------------ */
+int64_t segclip_seg_refine_ws_bytes(int64_t labels_bytes, int64_t B, int64_t D);
+int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                       int64_t labels_bytes, int64_t C, const int32_t* dilations, int64_t D, int64_t T, const float* mean,
+                       const float* inv_std, int reverse_channels, uint8_t* out, int64_t out_bytes, const uint8_t* gt,
+                       int64_t gt_bytes, int ignore_index, int reduce_zero_label, int64_t* areas, float* probs,
+                       int64_t probs_floats, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
  * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
  * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the

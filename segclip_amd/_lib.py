@@ -178,6 +178,9 @@ SIGNATURES = {
     "segclip_seg_view_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
     "segclip_seg_groups_rescaled": (C.c_int, [vp, i64, vp, i64, i64, i64, vp, i64, vp]),
     "segclip_seg_blend": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, C.c_int, C.c_double, C.c_double, C.c_int, vp, i64, vp, vp]),
+    "segclip_seg_refine_ws_bytes": (i64, [i64, i64, i64]),
+    "segclip_seg_refine": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp, C.c_int, vp, i64, vp, i64, C.c_int,
+                                     C.c_int, vp, vp, i64, vp, i64, vp]),
     "segclip_retrieval_thresholds": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "segclip_retrieval_count": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
     "segclip_retrieval_hist": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp]),

@@ -8,7 +8,8 @@
 // first maximum and looks one row up (bound: 1-2 bytes of HBM writes per pixel).
 // The .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
-// uint8 front end (segment_frontend.inc), rendering (segment_render.inc) and the training front end (train_frontend.inc).
+// uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
+// (segment_refine.inc) and the training front end (train_frontend.inc).
 #include "common.h"
 
 #include <atomic>
@@ -301,6 +302,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_aug.inc"
 #include "segment_frontend.inc"
 #include "segment_render.inc"
+#include "segment_refine.inc"
 #include "train_frontend.inc"
 
 }  // namespace
@@ -708,6 +710,129 @@ extern "C" int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blo
   k.out = out; k.sums = reinterpret_cast<unsigned long long*>(sums);
   hipLaunchKernelGGL(seg_blend_kernel, dim3((unsigned)n_blocks), dim3(256), 0, ST, k);
   SEGCLIP_CHECK_LAUNCH("seg_blend");
+  return 0;
+}
+
+// ---------------------------------------------------------------- pixel-adaptive refinement (segment_refine.inc)
+struct SegRefineWs { int64_t pres, wts, plane0, plane1, bestv, bestl, total; };
+static SegRefineWs seg_refine_ws(int64_t n, int64_t B, int64_t D) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegRefineWs w;
+  w.pres = 0;
+  w.wts = up(B * 8 * 4);
+  w.plane0 = w.wts + up(8 * D * n * 4);
+  w.plane1 = w.plane0 + up(n * SEG_REFINE_PLANES * 4);
+  w.bestv = w.plane1 + up(n * SEG_REFINE_PLANES * 4);
+  w.bestl = w.bestv + up(n * 4);
+  w.total = w.bestl + up(n);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_refine_ws_bytes(int64_t labels_bytes, int64_t B, int64_t D) {
+  if (labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || D < 1 || D > SEG_REFINE_MAX_D) {
+    segclip_set_error("seg_refine_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 1 <= D <= %d", SEG_REFINE_MAX_D);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  return seg_refine_ws(labels_bytes, B, D).total;
+}
+
+template <bool FIRST, bool LAST>
+static void seg_refine_step(const SegRefineArgs& a, int64_t n_blocks, int chunk, int parity, void* stream) {
+  hipLaunchKernelGGL((seg_refine_step_kernel<FIRST, LAST>), dim3((unsigned)n_blocks), dim3(256), 0, ST, a, chunk, parity);
+}
+
+extern "C" int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                                  int64_t labels_bytes, int64_t C, const int32_t* dilations, int64_t D, int64_t T, const float* mean,
+                                  const float* inv_std, int reverse_channels, uint8_t* out, int64_t out_bytes, const uint8_t* gt,
+                                  int64_t gt_bytes, int ignore_index, int reduce_zero_label, int64_t* areas, float* probs,
+                                  int64_t probs_floats, void* ws, int64_t ws_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_bytes >= 0 && out_bytes >= 0 && gt_bytes >= 0 && probs_floats >= 0 && ws_bytes >= 0,
+                  "seg_refine: sizes must not be negative");
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "seg_refine: size out of range");
+  SEGCLIP_REQUIRE(dilations && mean && inv_std, "seg_refine: dilations, mean and inv_std are required");
+  SEGCLIP_REQUIRE(!gt || areas, "seg_refine: a ground truth needs the areas to add to");
+  SEGCLIP_REQUIRE(!probs || B == 1, "seg_refine: probs holds the planes of one image, got %lld images", (long long)B);
+  for (int c = 0; c < 3; ++c)
+    SEGCLIP_REQUIRE(inv_std[c] > 0.f && inv_std[c] < INFINITY && mean[c] == mean[c], "seg_refine: inv_std is positive and finite");
+#define SEG_REFINE_REFUSE(cond, ...)     \
+  do {                                   \
+    if (cond) {                          \
+      segclip_set_error(__VA_ARGS__);    \
+      return SEGCLIP_ERR_UNSUPPORTED;    \
+    }                                    \
+  } while (0)
+  SEG_REFINE_REFUSE(D < 1 || D > SEG_REFINE_MAX_D, "seg_refine: %lld dilations, 1..%d supported", (long long)D, SEG_REFINE_MAX_D);
+  for (int64_t i = 0; i < D; ++i)
+    SEG_REFINE_REFUSE(dilations[i] < 1 || dilations[i] > SEG_REFINE_MAX_DIL || (i > 0 && dilations[i] <= dilations[i - 1]),
+                      "seg_refine: dilations are increasing values in 1..%d, got %d at position %lld", SEG_REFINE_MAX_DIL, dilations[i],
+                      (long long)i);
+  SEG_REFINE_REFUSE(T < 0 || T > SEG_REFINE_MAX_T, "seg_refine: %lld iterations, 0..%d supported", (long long)T, SEG_REFINE_MAX_T);
+  SEG_REFINE_REFUSE(C < 1 || C > SEG_MAX_CLASSES, "seg_refine: %lld classes, 1..%d supported (uint8 labels)", (long long)C, SEG_MAX_CLASSES);
+  SEG_REFINE_REFUSE(max_side < 1 || max_side >= SEG_REFINE_LIMIT, "seg_refine: sides of 1..%d pixels supported, got a bound of %lld",
+                    SEG_REFINE_LIMIT - 1, (long long)max_side);
+  const SegRefineWs w = seg_refine_ws(labels_bytes, B, D);
+  SEG_REFINE_REFUSE(T > 0 && ws_bytes < w.total, "seg_refine: the workspace has %lld bytes, segclip_seg_refine_ws_bytes asks for %lld",
+                    (long long)ws_bytes, (long long)w.total);
+#undef SEG_REFINE_REFUSE
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(images && labels && out, "seg_refine: images, labels and out are required");
+  SEGCLIP_REQUIRE(out_bytes == labels_bytes, "seg_refine: out has the layout of labels: %lld bytes, got %lld", (long long)labels_bytes,
+                  (long long)out_bytes);
+  SEGCLIP_REQUIRE(out + out_bytes <= labels || labels + labels_bytes <= out, "seg_refine: out overlaps labels (the refinement is out of place)");
+  SEGCLIP_REQUIRE(T == 0 || (ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0), "seg_refine: the workspace is required, 16-byte aligned");
+
+  SegRefineArgs a;
+  a.images = images; a.labels = labels; a.out = out; a.gt = gt; a.areas = reinterpret_cast<unsigned long long*>(areas);
+  a.probs = probs; a.labels_bytes = labels_bytes; a.gt_bytes = gt_bytes; a.probs_floats = probs_floats;
+  a.B = (int)B; a.C = (int)C; a.D = (int)D; a.max_side = (int)max_side; a.ignore_index = ignore_index;
+  a.reduce_zero = reduce_zero_label ? 1 : 0;
+  for (int i = 0; i < SEG_REFINE_MAX_D; ++i) a.dil[i] = i < D ? dilations[i] : 0;
+  // the picture's channel s is the transform's channel 2 - s when the picture is BGR (segclip_seg_windows_from_u8)
+  for (int s = 0; s < 3; ++s) a.isd[s] = inv_std[reverse_channels ? 2 - s : s];
+  char* base = static_cast<char*>(ws);
+  a.pres = reinterpret_cast<uint32_t*>(base + w.pres);
+  a.wts = reinterpret_cast<float*>(base + w.wts);
+  a.plane[0] = reinterpret_cast<float*>(base + w.plane0);
+  a.plane[1] = reinterpret_cast<float*>(base + w.plane1);
+  a.bestv = reinterpret_cast<float*>(base + w.bestv);
+  a.bestl = reinterpret_cast<uint8_t*>(base + w.bestl);
+  if (T == 0) { a.pres = nullptr; a.wts = a.plane[0] = a.plane[1] = a.bestv = nullptr; a.bestl = nullptr; }
+
+  if (probs && probs_floats > 0) {  // the planes of the labels that do not occur
+    const hipError_t e = hipMemsetAsync(probs, 0, (size_t)probs_floats * sizeof(float), ST);
+    SEGCLIP_REQUIRE(e == hipSuccess, "seg_refine: clearing probs failed: %s", hipGetErrorString(e));
+  }
+  const dim3 grid((unsigned)n_blocks), block(256);
+  if (T == 0) {
+    hipLaunchKernelGGL(seg_refine_copy_kernel, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_refine");
+    return 0;
+  }
+  {
+    const hipError_t e = hipMemsetAsync(a.pres, 0, (size_t)B * 8 * sizeof(uint32_t), ST);
+    SEGCLIP_REQUIRE(e == hipSuccess, "seg_refine: clearing the label presence maps failed: %s", hipGetErrorString(e));
+  }
+  switch (D) {
+    case 1: hipLaunchKernelGGL(seg_refine_weights_kernel<1>, grid, block, 0, ST, a); break;
+    case 2: hipLaunchKernelGGL(seg_refine_weights_kernel<2>, grid, block, 0, ST, a); break;
+    case 3: hipLaunchKernelGGL(seg_refine_weights_kernel<3>, grid, block, 0, ST, a); break;
+    case 4: hipLaunchKernelGGL(seg_refine_weights_kernel<4>, grid, block, 0, ST, a); break;
+    case 5: hipLaunchKernelGGL(seg_refine_weights_kernel<5>, grid, block, 0, ST, a); break;
+    default: hipLaunchKernelGGL(seg_refine_weights_kernel<6>, grid, block, 0, ST, a); break;
+  }
+  SEGCLIP_CHECK_LAUNCH("seg_refine (weights)");
+  // a chunk's T steps follow each other on the stream, and the chunks share the plane pair; a chunk beyond an image's label
+  // count costs that image T launches of workgroups that exit at once
+  const int chunks = (int)cdiv(C, SEG_REFINE_PLANES);
+  for (int chunk = 0; chunk < chunks; ++chunk)
+    for (int t = 0; t < (int)T; ++t) {
+      const bool first = t == 0, last = t == (int)T - 1;
+      if (first && last) seg_refine_step<true, true>(a, n_blocks, chunk, t & 1, stream);
+      else if (first) seg_refine_step<true, false>(a, n_blocks, chunk, t & 1, stream);
+      else if (last) seg_refine_step<false, true>(a, n_blocks, chunk, t & 1, stream);
+      else seg_refine_step<false, false>(a, n_blocks, chunk, t & 1, stream);
+      SEGCLIP_CHECK_LAUNCH("seg_refine (step)");
+    }
   return 0;
 }
 

@@ -2777,8 +2777,81 @@ def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, rev
     return out
 
 
+# ---------------------------------------------------------------- pixel-adaptive refinement of label maps (segment_refine.inc)
+SEG_REFINE_TILE = 256        # pixels of one workgroup of segclip_seg_refine
+SEG_REFINE_COLS = 8          # int64 columns of one row of its image table
+SEG_REFINE_MAX_DILATIONS = 6
+SEG_REFINE_MAX_DILATION = 32
+SEG_REFINE_MAX_ITERS = 32
+
+
+def seg_refine_table(raws, label_offsets):
+    """The device image table of seg_refine: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows possibly strided],
+    label_offsets [offset of each image's (h, w) labels in the flat label buffer; the refined labels take the same offsets].
+    The ground truths of a call lie flat one after the other, so their offsets are the running sum of h * w.  It holds the
+    tensors' addresses: keep `raws` alive while it is in use.  -> (table (B, 8) int64, n_blocks, largest side)."""
+    if len(raws) == 0 or len(raws) != len(label_offsets):
+        raise ValueError(f"seg_refine: {len(raws)} images but {len(label_offsets)} label maps")
+    L.require_cuda(*raws)
+    tab, gt, blk, side = [], 0, 0, 0
+    for t, lo in zip(raws, label_offsets):
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"seg_refine: a picture is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if t.device != raws[0].device:
+            raise ValueError("seg_refine: the pictures are on different devices")
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_refine: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
+            raise ValueError(f"seg_refine: a picture has interleaved channels and contiguous pixels (strides (>= 3 w, 3, 1)), "
+                             f"got {tuple(t.stride())}")
+        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(lo), gt, blk, 0])
+        gt += h * w
+        blk += (h * w + SEG_REFINE_TILE - 1) // SEG_REFINE_TILE
+        side = max(side, h, w)
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_REFINE_COLS), blk, side
+
+
+def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv_std, reverse_channels=False, out=None, gt=None,
+               areas=None, ignore_index=255, reduce_zero_label=False, probs=None, max_side=None):
+    """Pixel-adaptive refinement (segclip_seg_refine; the definition stands in include/segclip_hip.h): the table of
+    seg_refine_table + the flat uint8 `labels` -> `out`, flat uint8 with the same offsets (a new tensor unless given; it may not
+    overlap `labels`).  dilations: 1 .. 6 increasing values in 1 .. 32; iters: 0 .. 32.  With `gt` (flat uint8) the (3, C) int64
+    `areas` of seg_areas are added to for the refined labels, by the last kernel.  probs: a flat fp32 buffer for ONE image's
+    (C, h, w) final planes, for tests and inspection.  max_side: the largest h or w of the table (seg_refine_table's third
+    result; defaults to the limit).  No host synchronisation; the workspace does not depend on num_classes."""
+    L.require_cuda(table, labels, out, gt, areas, probs)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_REFINE_COLS or not table.is_contiguous():
+        raise ValueError("seg_refine: table is the (B, 8) int64 tensor of seg_refine_table")
+    if out is None:
+        out = torch.empty_like(labels)
+    _seg_check_outputs("seg_refine", labels, gt, areas, int(num_classes))
+    if out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError("seg_refine: out is a contiguous uint8 tensor")
+    if probs is not None and (probs.dtype != torch.float32 or not probs.is_contiguous()):
+        raise ValueError("seg_refine: probs is a contiguous fp32 tensor")
+    if len(mean) != 3 or len(inv_std) != 3:
+        raise ValueError("seg_refine: mean and inv_std have 3 entries")
+    dil = [int(d) for d in dilations]
+    B, D = table.shape[0], len(dil)
+    lib = L.load()
+    ws_bytes, ws = 0, None
+    if int(iters) != 0:
+        ws_bytes = lib.segclip_seg_refine_ws_bytes(labels.numel(), B, D)
+        if ws_bytes < 0:
+            L.check(ws_bytes, "seg_refine")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=labels.device)
+    f3 = L.f32 * 3
+    L.check(lib.segclip_seg_refine(
+        L.ptr(table), B, int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(labels), labels.numel(),
+        int(num_classes), (C.c_int32 * max(D, 1))(*dil), D, int(iters), f3(*mean), f3(*inv_std), int(bool(reverse_channels)),
+        L.ptr(out), out.numel(), L.ptr(gt), gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)),
+        L.ptr(areas), L.ptr(probs), probs.numel() if probs is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_refine")
+    return out
+
+
 # ---------------------------------------------------------------- image-text retrieval evaluation (retrieval.hip)
-RETRIEVAL_BAD_INDEX = 1   # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
+RETRIEVAL_BAD_INDEX = 1  # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
 
 
 def _retrieval_inputs(what, visual, sequence, image_index):

@@ -34,6 +34,13 @@ towers, the front end and the group tables run once, and one kernel (csrc/segmen
 map and areas, bit for bit those of one SegEvaluator per threshold.  Not swept: the augmented path, the dense logits, the
 top-5 mask.
 
+Refinement (not in the reference; the zero-shot systems after SegCLIP report their numbers with it): PAMR states the
+pixel-adaptive mask refinement of Araslanov & Roth (CVPR 2020), refine_labels applies it to label maps against the decoded
+pictures, and predict_raw / update_raw / eval_epoch take refine=.  The label map is the arg-max of a 14 x 14 assignment blown
+up twice, so its borders follow the patch grid; the refinement moves them onto the picture's edges.  It runs on the device
+(csrc/segment_refine.inc) without a (C, h, w) tensor and without a host synchronisation, and with a ground truth its last
+kernel adds the mIoU areas.  Not covered: the threshold sweep, render_raw, and the entry points without a raw picture.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -315,6 +322,77 @@ class TestAug:
         return out
 
 
+class PAMR:
+    """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a post-processing step of the label maps: `iters`
+    iterations of an affinity-weighted average over the 8 neighbours at each of `dilations` (csrc/segment_refine.inc; the
+    definition stands in include/segclip_hip.h).  The defaults are the paper's.  The reference has no refinement."""
+
+    def __init__(self, iters=10, dilations=(8, 16)):
+        if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= ops.SEG_REFINE_MAX_ITERS:
+            raise ValueError(f"PAMR: iters is an integer in 0 .. {ops.SEG_REFINE_MAX_ITERS}, got {iters!r}")
+        try:
+            dil = tuple(dilations)
+        except TypeError:
+            raise ValueError(f"PAMR: dilations is a sequence of integers, got {dilations!r}") from None
+        if not 1 <= len(dil) <= ops.SEG_REFINE_MAX_DILATIONS:
+            raise ValueError(f"PAMR: dilations holds 1 .. {ops.SEG_REFINE_MAX_DILATIONS} values, got {len(dil)}")
+        if any(isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= ops.SEG_REFINE_MAX_DILATION for d in dil):
+            raise ValueError(f"PAMR: dilations are integers in 1 .. {ops.SEG_REFINE_MAX_DILATION}, got {dil}")
+        if any(b <= a for a, b in zip(dil, dil[1:])):
+            raise ValueError(f"PAMR: dilations must be strictly increasing, got {dil}")
+        self.iters, self.dilations = iters, dil
+
+
+def _refine_maps(raws, maps, num_classes, transform, pamr, gts=None, areas=None, ignore_index=255, reduce_zero_label=False):
+    """The refinement of a list call: maps [(h_i, w_i) uint8] of the pictures' own sizes -> the refined maps, views of one new
+    buffer; with gts the areas of the refined maps are added to `areas` by the refinement's last kernel."""
+    if not isinstance(pamr, PAMR):
+        raise TypeError("refine is a PAMR")
+    if not isinstance(transform, ImageTransform):
+        raise TypeError("transform is an ImageTransform")
+    if len(raws) == 0:
+        raise ValueError("empty image list")
+    if len(raws) != len(maps):
+        raise ValueError(f"{len(raws)} images but {len(maps)} label maps")
+    ops.L.require_cuda(*raws, *maps)
+    for t, m in zip(raws, maps):
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        if m.dtype != torch.uint8 or m.dim() != 2 or tuple(m.shape) != tuple(t.shape[:2]):
+            raise ValueError(f"a label map is an (h, w) uint8 tensor of its image's size {tuple(t.shape[:2])}, got {m.dtype} "
+                             f"{tuple(m.shape)}")
+    if gts is not None:
+        for g, m in zip(gts, maps):
+            if tuple(g.shape) != tuple(m.shape):
+                raise ValueError(f"refine: a ground truth has its picture's size {tuple(m.shape)}, got {tuple(g.shape)}")
+    flat, offs = _flat_maps(list(maps))
+    table, n_blocks, side = ops.seg_refine_table(list(raws), offs)
+    out = ops.seg_refine(table, n_blocks, flat, num_classes, pamr.dilations, pamr.iters, transform.mean, transform.inv_std,
+                         reverse_channels=transform.channel_order == "bgr", gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index,
+                         reduce_zero_label=reduce_zero_label, max_side=side)
+    return _split_maps(out, offs, [tuple(m.shape) for m in maps])
+
+
+@torch.no_grad()
+def refine_labels(raws, labels, num_classes, transform, pamr):
+    """raws [(h_i, w_i, 3) uint8 decoded images, rows possibly strided], labels [(h_i, w_i) uint8 label maps at the pictures'
+    own sizes] -> [(h_i, w_i) uint8 refined maps], views of one buffer: `pamr` (a PAMR) applied to every map, all images in one
+    call and without a host synchronisation.  transform supplies the normalisation and the pictures' channel order.  The
+    inputs stay as they are."""
+    return _refine_maps(raws, labels, num_classes, transform, pamr)
+
+
+def _check_refine(refine, raws, out_shapes):
+    """refine= of predict_raw / update_raw: a PAMR, and label maps at the pictures' own sizes."""
+    if not isinstance(refine, PAMR):
+        raise TypeError("refine is a PAMR")
+    if out_shapes is not None:
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
+        if [(int(a), int(b)) for (a, b) in out_shapes] != sizes:
+            raise ValueError(f"refine: out_shapes must be the raw images' own sizes {sizes} (the refinement reads the picture under "
+                             f"every label), got {list(out_shapes)}")
+
+
 def _out_shapes(src, out_shapes):
     """The output sizes of a list call, one per image: the caller's, or the source's default."""
     n_img = len(src.view_counts)
@@ -547,23 +625,33 @@ class SegInference:
         return (self._views_forward if src.augmented else self._list_forward)(src, out_shapes, **kw)
 
     @torch.no_grad()
-    def predict_list(self, imgs, out_shapes=None):
+    def predict_list(self, imgs, out_shapes=None, refine=None):
         """[(3, H_i, W_i)] of any mix of sizes -> [(oh_i, ow_i) uint8 labels], views of one flat buffer; out_shapes defaults
         to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
-        Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size."""
+        Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size.
+        refine is refused: there is no raw picture here (predict_raw has it)."""
+        if refine is not None:
+            raise ValueError("predict_list: refine needs the decoded pictures: use predict_raw(refine=) or refine_labels")
         return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes)
 
     @torch.no_grad()
-    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None):
+    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None, refine=None):
         """[(h_i, w_i, 3) uint8 decoded images] -> [(oh_i, ow_i) uint8 labels] as predict_list(preprocess(raws, transform,
         net_sizes), out_shapes), bit for bit, without the resized images: the windows of a tower call are written from the
         raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
         ori_shape); net_sizes overrides transform.net_size (whole mode needs multiples of the patch size).
         aug (a TestAug): mmseg's aug_test over the views of aug.views - every view segmented, its logits rescaled to the output
         size and passed through a soft-max, flipped back, the probabilities averaged over the views, first maximum.  net_sizes
-        then holds one (H, W) per view of every image."""
-        return self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
+        then holds one (H, W) per view of every image.
+        refine (a PAMR): the label maps pass through the pixel-adaptive refinement against the raw pictures before they are
+        returned, = refine_labels(raws, predict_raw(raws, ...), num_classes, transform, refine) bit for bit.  out_shapes must
+        then be the raw sizes (the default).  It composes with aug: the refinement sees only labels."""
+        if refine is None:
+            return self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
+        _check_refine(refine, raws, out_shapes)
+        labels = self._forward(_RawImages(raws, transform, net_sizes, aug), None)
+        return _refine_maps(raws, labels, self.num_classes, transform, refine)
 
     @torch.no_grad()
     def predict_views(self, views, out_shapes):
@@ -600,7 +688,7 @@ class SegInference:
         return self._list_forward(_RawImages(raws, transform, net_sizes), out_shapes, groups="only")[1]
 
     @torch.no_grad()
-    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None):
+    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None, refine=None):
         """The reference's --vis modes (show_result, vit_seg.py:286-377) for decoded images, at their own sizes -> dict
         mode -> result:
           input              the raws
@@ -611,7 +699,10 @@ class SegInference:
           all_groups         the same as a one-element list per image: this model has one grouping stage
         palette: (P, 3) uint8 RGB class colours (index 0 = background when with_bg); group_palette defaults to
         default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
-        call whatever the modes: labels and group maps come from the same encode_image pass."""
+        call whatever the modes: labels and group maps come from the same encode_image pass.  refine is refused: draw refined
+        maps with blend(raws, predict_raw(raws, transform, refine=...), palette)."""
+        if refine is not None:
+            raise ValueError("render_raw: refine is not supported; blend the maps of predict_raw(refine=) instead")
         modes = list(vis_modes)
         for m in modes:
             if m not in VIS_MODES:
@@ -759,16 +850,27 @@ class SegEvaluator:
         self.areas.zero_()
 
     @torch.no_grad()
-    def update(self, imgs, gts, return_labels=False):
-        """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size."""
+    def update(self, imgs, gts, return_labels=False, refine=None):
+        """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size.  refine is
+        refused: there is no raw picture here (update_raw has it)."""
+        if refine is not None:
+            raise ValueError("SegEvaluator.update: refine needs the decoded pictures: use update_raw(refine=)")
         self._check_gts(imgs, gts)
         return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None):
-        """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included)."""
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None):
+        """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included).
+        refine (a PAMR): the areas are those of the refined label maps, added by the refinement's last kernel; the label
+        kernel then only writes the maps and counts nothing.  The ground truths must have the pictures' sizes."""
         self._check_gts(raws, gts)
-        return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
+        if refine is None:
+            return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
+        _check_refine(refine, raws, [tuple(g.shape) for g in gts])
+        labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), None)
+        refined = _refine_maps(raws, labels, self.seg.num_classes, transform, refine, gts=list(gts), areas=self.areas,
+                               ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
+        return refined if return_labels else None
 
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):
@@ -854,8 +956,11 @@ class SegSweepEvaluator:
         return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None):
-        """As SegEvaluator.update_raw, without aug."""
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None):
+        """As SegEvaluator.update_raw, without aug and without refine."""
+        if refine is not None:
+            raise ValueError("SegSweepEvaluator: refine is not supported (every threshold's map would need its own refinement); "
+                             "use one SegEvaluator per threshold")
         if aug is not None:
             raise ValueError("SegSweepEvaluator: aug is not supported (the augmented path needs accumulators per threshold); "
                              "use one SegEvaluator per threshold")

@@ -35,8 +35,17 @@ every repeat:
         (--sweep-child: five sweep and five single update_raw calls and nothing else), beside the single entry's own time.  The
         thresholds are quantiles of the inputs' own best_score: synthetic weights score far below the reference's 0.25-0.80, where
         every threshold is clamped by table_max and all slices are one.
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep] [reps=7]
-                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt]"""
+With --refine instead: the same 64 decoded images with pixel-adaptive refinement of the label maps, PAMR() = 10 iterations at
+dilations (8, 16), in ONE command and alternating within every repeat:
+  (viii) one SegEvaluator.update_raw (the yardstick: unchanged by the refinement), one update_raw(refine=PAMR()), and update_raw's
+        label maps refined by an eager fp32 transcription of the definition (replicate pad + F.unfold on the (C, h, w) one-hot,
+        per image) and scored by segclip_seg_areas: medians, spread, the refinement's cost over the yardstick both ways and their
+        ratio, the share of pixels on which the two agree, peak allocation, the clock held, and the refinement kernels' own time
+        from a separate `rocprofv3 --kernel-trace --stats` child (--refine-child: five update_raw(refine=) calls and nothing
+        else) with the step kernel's bytes per second against its design traffic.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine] [reps=7]
+                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
+                                  seg_refine.txt]"""
 import os
 import statistics
 import sys
@@ -54,10 +63,12 @@ from tools.clock_sampler import ClockSampler
 EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("--raw-child" in sys.argv[1:])
 AUG, AUG_CHILD = ("--aug" in sys.argv[1:]), ("--aug-child" in sys.argv[1:])
 SWEEP, SWEEP_CHILD = ("--sweep" in sys.argv[1:]), ("--sweep-child" in sys.argv[1:])
-ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child")]
+REFINE, REFINE_CHILD = ("--refine" in sys.argv[1:]), ("--refine-child" in sys.argv[1:])
+ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
+                                             "--refine", "--refine-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -556,6 +567,121 @@ def sweep_child(model, text):
     torch.cuda.synchronize()
 
 
+def eager_pamr(raw, lab, C, mean, std, dilations, iters):
+    """The definition of segclip_seg_refine transcribed to eager torch in fp32 for one image: (h, w, 3) uint8 picture and (h, w)
+    uint8 labels -> refined (h, w) uint8 labels.  The (C, h, w) one-hot and its (C, 8 D, h, w) unfolding exist here."""
+    h, w = lab.shape
+    D = len(dilations)
+
+    def taps(t):   # (1, K, h, w) -> (1, K, 8 D, h, w)
+        out = []
+        for d in dilations:
+            u = F.unfold(F.pad(t, (d, d, d, d), mode="replicate"), 3, dilation=d).view(1, t.shape[1], 9, h, w)
+            out.append(torch.cat([u[:, :, :4], u[:, :, 5:]], dim=2))
+        return torch.cat(out, dim=2)
+
+    x = ((raw.float() - mean) / std).permute(2, 0, 1)[None]
+    nx = taps(x)
+    sigma = torch.cat([nx, x[:, :, None].expand(-1, -1, D, -1, -1)], dim=2).std(dim=2, keepdim=True)
+    wts = torch.softmax(-((x[:, :, None] - nx).abs() / (1e-8 + 0.1 * sigma)).mean(dim=1, keepdim=True), dim=2)
+    m = (lab.long()[None] == torch.arange(C, device=lab.device)[:, None, None]).float()[None]
+    for _ in range(iters):
+        m = (taps(m) * wts).sum(dim=2)
+    top, arg = m[0].max(dim=0)
+    return torch.where(top > 0, arg.to(torch.uint8), lab)
+
+
+def refine_case(model, text, n_images=64):
+    from segclip_amd.segmentation import PAMR, ImageTransform, SegEvaluator
+    from tools import rocprof_roofline as rr
+    name = f"(viii) refine {n_images} mixed sizes"
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    tf, pamr = ImageTransform(), PAMR()
+    raws, gts = raw_inputs(seg, n_images)
+    C, D, T = seg.num_classes, len(pamr.dilations), pamr.iters
+    pixels = sum(int(g.numel()) for g in gts)
+    mean, std = torch.tensor(tf.mean, device="cuda"), torch.tensor(tf.std, device="cuda")
+    plain, fused, eager = SegEvaluator(seg), SegEvaluator(seg), SegEvaluator(seg)
+
+    def eager_way(keep=None):
+        maps = eager.update_raw(raws, gts, tf, return_labels=True)
+        eager.areas.zero_()   # the areas of the refined maps only
+        for r, l, g in zip(raws, maps, gts):
+            out = eager_pamr(r, l, C, mean, std, pamr.dilations, T)
+            ops.seg_areas(out, g, C, areas=eager.areas)
+            if keep is not None:
+                keep.append(out)
+
+    ways = [("update_raw", lambda: plain.update_raw(raws, gts, tf), 2),
+            (f"update_raw(refine=PAMR({T}, {pamr.dilations}))", lambda: fused.update_raw(raws, gts, tf, refine=pamr), 2),
+            ("update_raw + eager unfold PAMR + seg_areas", eager_way, 1)]
+    with torch.no_grad():
+        maps = plain.update_raw(raws, gts, tf, return_labels=True)
+        chunks = [max(1, (int(m.unique().numel()) + 7) // 8) for m in maps]   # chunks of 8 planes an image keeps busy
+        got, want = fused.update_raw(raws, gts, tf, return_labels=True, refine=pamr), []
+        eager_way(want)
+        agree = sum(int((a == b).sum()) for a, b in zip(got, want)) / pixels
+        moved = sum(int((a != b).sum()) for a, b in zip(got, maps)) / pixels
+        for _, fn, _ in ways:
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):   # alternating: every repeat times the three ways one after the other
+            for k, (_, fn, inner) in enumerate(ways):
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: {pixels} pixels, {C} classes, {T} iterations at dilations {pamr.dilations}; the refinement changes {moved:.4%} of the "
+        f"labels; kernel and eager transcription agree on {agree:.4%} of the pixels")
+    meds = [statistics.median(t) for t in ts]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:44s} {med * 1e3:9.2f} ms (min {min(t) * 1e3:.2f}, max {max(t) * 1e3:.2f}; {REPS} x {inner} calls)  "
+            f"{n_images / med:8.1f} images/s")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts)
+    say(f"{name}: the refinement costs {(meds[1] - meds[0]) * 1e3:.2f} ms fused and {(meds[2] - meds[0]) * 1e3:.2f} ms eager over the "
+        f"yardstick: eager / fused {(meds[2] - meds[0]) / max(meds[1] - meds[0], 1e-9):.2f}; refined / plain update_raw "
+        f"{meds[1] / meds[0]:.4f}; largest run-to-run spread {spread:.4f} of the median; clock {clk}")
+    say(f"{name}: peak allocation of one call: plain {peak_of(ways[0][1]) / 2**20:8.1f} MiB, refined {peak_of(ways[1][1]) / 2**20:8.1f} MiB, "
+        f"eager {peak_of(eager_way) / 2**20:8.1f} MiB")
+    # the kernels' own time: a child of this tool that only calls update_raw(refine=), under rocprofv3 --kernel-trace --stats
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--refine-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    design = sum(int(g.numel()) * c for g, c in zip(gts, chunks)) * T * (32 * D + 64)   # bytes of the step kernels of one call
+    for what, pat in (("seg_refine_weights_kernel", "seg_refine_weights_kernel"), ("seg_refine_step_kernel", "seg_refine_step_kernel")):
+        rows = [r for r in table if pat in r[0]]
+        if not rows:
+            say(f"{name}: {what} alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+            continue
+        calls, us = sum(r[1] for r in rows), sum(r[2] for r in rows)
+        line = f"{name}: {what} alone (rocprofv3 --kernel-trace --stats, {calls} launches in 5 calls) {us / 5:9.1f} us per update_raw"
+        if pat == "seg_refine_step_kernel":
+            line += (f"; design traffic {design / 1e6:.1f} MB per call ({32 * D + 64} B per pixel, iteration and busy chunk of 8 planes) "
+                     f"= {design / (us / 5 * 1e-6) / 1e12:.3f} TB/s, {design / (us / 5 * 1e-6) / HBM_PEAK:.3f} of the HBM peak")
+        say(line)
+
+
+def refine_child(model, text):
+    """Five update_raw(refine=PAMR()) calls and nothing else: what the rocprofv3 child of refine_case traces."""
+    from segclip_amd.segmentation import PAMR, ImageTransform, SegEvaluator
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    raws, gts = raw_inputs(seg)
+    ev, tf, pamr = SegEvaluator(seg), ImageTransform(), PAMR()
+    with torch.no_grad():
+        for _ in range(5):
+            ev.update_raw(raws, gts, tf, refine=pamr)
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -573,7 +699,12 @@ if __name__ == "__main__":
     if SWEEP_CHILD:
         sweep_child(model, text)
         sys.exit(0)
-    if SWEEP:
+    if REFINE_CHILD:
+        refine_child(model, text)
+        sys.exit(0)
+    if REFINE:
+        refine_case(model, text)
+    elif SWEEP:
         sweep_case(model, text)
     elif AUG:
         aug_case(model, text)
