@@ -722,6 +722,53 @@ int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64
                        int64_t probs_floats, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of label maps (segment_objects.inc): component ids, areas, a compact list of objects with their boxes
+ * and coordinate sums, and despeckled maps, for images of mixed sizes in one call.  THE REFERENCE HAS NO SUCH OP: the
+ * definition is this project's, stated here and restated with a plain union-find by tests/cc_reference.py.
+ *
+ * Per image: label map L (h, w) uint8, connectivity 4 or 8, skip_label in 0..255 or -1 for none.
+ *   A component is a maximal set of pixels with the same byte that is connected under the connectivity (4: left / right /
+ *   up / down; 8: the diagonals too).  Pixels whose byte is skip_label belong to no component.
+ *   The id of a component is the smallest flat in-image index y * w + x of its pixels: its first pixel in raster order.
+ *   Ids, areas, boxes and sums are integers and the ids depend on no scheduling: two calls give the same bits.
+ *   ids[p]     = the id of p's component, or -1 for a skipped pixel
+ *   area_px[p] = the pixel count of p's component, or 0 for a skipped pixel
+ *   records    : one row of 10 int64 per component, rows in ascending (image, id) order:
+ *                image, id, label, area, y0, x0, y1, x1, sum of y, sum of x over its pixels; y1 and x1 are EXCLUSIVE (the box
+ *                is rows y0..y1-1, columns x0..x1-1, as scipy.ndimage.find_objects gives slices)
+ *   count[0]   = the number of components of all images, also when it exceeds K; then exactly the first K rows in that order
+ *                are written and nothing beyond records + 10 K
+ *   cleaned[p] = fill where p is not skipped and area_px[p] < min_area, otherwise L[p].  ONE PASS: pixels that become `fill`
+ *                are not merged again with neighbours that carry `fill` already, and nothing is labelled twice.
+ *
+ *   images   : (B, 8) int64 rows on the device: 0 h  1 w  2 offset of the image's h * w entries in `labels`, `ids`, `area_px`
+ *              AND `cleaned`  3 its first workgroup = the sum of ceil(h / 16) * ceil(w / 64) over the images before it  4-7 0
+ *   n_blocks : that sum over all images (the tile is 16 rows x 64 columns);  max_side: the caller's bound on every h and w
+ *   labels   : flat uint8 of labels_bytes, read only
+ *   ids, area_px : optional flat int32 of px_count = labels_bytes entries
+ *   records  : optional (K, 10) int64; needs count.  count: optional, one int64
+ *   cleaned  : optional flat uint8 of cleaned_bytes = labels_bytes, must not overlap labels; min_area >= 0, fill in 0..255
+ *   ws       : segclip_seg_components_ws_bytes(labels_bytes, B, n_blocks) bytes (16 per pixel + about 130 per workgroup), 16-byte
+ *              aligned
+ *   Every output is optional; the entry enqueues its kernels without a host synchronisation: the tiles' union-find in LDS,
+ *   the merge across the tiles' rims (atomicMin on a flat int32 parent array; parents only ever decrease, every retry
+ *   continues from a strictly smaller index, and no workgroup waits for another), with count a root count per row segment,
+ *   one scan and the ranks, then areas / boxes / sums reduced in LDS and added with one set of integer atomics per (tile,
+ *   tile-local component), and the pass that writes area_px and cleaned.
+ *   Every table row is range-checked on the device: an image with h or w outside [1, min(max_side, 2^15 - 1)], offsets
+ *   inconsistent with labels_bytes or workgroups beyond n_blocks is SKIPPED (nothing of it read, written or counted).
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: connectivity other than 4 or 8, skip_label outside
+ *   -1..255, fill outside 0..255, min_area < 0, max_side outside [1, 2^15), a workspace smaller than ws_bytes.
+ *   SEGCLIP_ERR_INVALID: records without count, cleaned overlapping labels, cleaned_bytes != labels_bytes,
+ *   px_count != labels_bytes with ids or area_px, missing pointers.
+ * ------------------------------------------------------------------------------------------ */
+int64_t segclip_seg_components_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks);
+int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                           int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                           int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                           uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
  * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
  * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the

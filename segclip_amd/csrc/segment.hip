@@ -9,7 +9,7 @@
 // The .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
-// (segment_refine.inc) and the training front end (train_frontend.inc).
+// (segment_refine.inc), their connected components (segment_objects.inc) and the training front end (train_frontend.inc).
 #include "common.h"
 
 #include <atomic>
@@ -303,6 +303,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_frontend.inc"
 #include "segment_render.inc"
 #include "segment_refine.inc"
+#include "segment_objects.inc"
 #include "train_frontend.inc"
 
 }  // namespace
@@ -833,6 +834,117 @@ extern "C" int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_bl
       else seg_refine_step<false, false>(a, n_blocks, chunk, t & 1, stream);
       SEGCLIP_CHECK_LAUNCH("seg_refine (step)");
     }
+  return 0;
+}
+
+// ---------------------------------------------------------------- connected components (segment_objects.inc)
+struct SegCCWs { int64_t parent, root, area, rank, seg, part, total; };
+static SegCCWs seg_cc_ws(int64_t n, int64_t n_blocks) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegCCWs w;
+  w.seg = 0;  // first: the one part that is cleared
+  w.part = up(n_blocks * SEG_CC_TH * 8);
+  w.parent = w.part + up(cdiv(n_blocks * SEG_CC_TH, SEG_CC_SCAN_CHUNK) * 8);
+  w.root = w.parent + up(n * 4);
+  w.area = w.root + up(n * 4);
+  w.rank = w.area + up(n * 4);
+  w.total = w.rank + up(n * 4);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_components_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks) {
+  if (labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31)) {
+    segclip_set_error("seg_components_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  return seg_cc_ws(labels_bytes, n_blocks).total;
+}
+
+extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                                      int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                                      int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                                      uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_bytes >= 0 && px_count >= 0 && K >= 0 && cleaned_bytes >= 0 && ws_bytes >= 0,
+                  "seg_components: sizes must not be negative");
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "seg_components: size out of range");
+  SEGCLIP_REQUIRE(!records || count, "seg_components: records need count, the number of rows that exist");
+  SEGCLIP_REQUIRE(!(ids || area_px) || px_count == labels_bytes,
+                  "seg_components: ids and area_px have one entry per label byte: %lld, got %lld", (long long)labels_bytes,
+                  (long long)px_count);
+  SEGCLIP_REQUIRE(!cleaned || cleaned_bytes == labels_bytes, "seg_components: cleaned has the layout of labels: %lld bytes, got %lld",
+                  (long long)labels_bytes, (long long)cleaned_bytes);
+  SEGCLIP_REQUIRE(!cleaned || !labels || cleaned + cleaned_bytes <= labels || labels + labels_bytes <= cleaned,
+                  "seg_components: cleaned overlaps labels (the despeckling is out of place)");
+#define SEG_CC_REFUSE(cond, ...)         \
+  do {                                   \
+    if (cond) {                          \
+      segclip_set_error(__VA_ARGS__);    \
+      return SEGCLIP_ERR_UNSUPPORTED;    \
+    }                                    \
+  } while (0)
+  SEG_CC_REFUSE(connectivity != 4 && connectivity != 8, "seg_components: connectivity is 4 or 8, got %d", connectivity);
+  SEG_CC_REFUSE(skip_label < -1 || skip_label > 255, "seg_components: skip_label is a byte or -1, got %d", skip_label);
+  SEG_CC_REFUSE(fill < 0 || fill > 255, "seg_components: fill is a byte, got %d", fill);
+  SEG_CC_REFUSE(min_area < 0, "seg_components: min_area must not be negative, got %lld", (long long)min_area);
+  SEG_CC_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_components: sides of 1..%d pixels supported, got a bound of %lld",
+                SEG_CC_LIMIT - 1, (long long)max_side);
+  const SegCCWs w = seg_cc_ws(labels_bytes, n_blocks);
+  SEG_CC_REFUSE(ws_bytes < w.total, "seg_components: the workspace has %lld bytes, segclip_seg_components_ws_bytes asks for %lld",
+                (long long)ws_bytes, (long long)w.total);
+#undef SEG_CC_REFUSE
+  if (B == 0 || n_blocks == 0) {
+    if (count) {
+      const hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), ST);
+      SEGCLIP_REQUIRE(e == hipSuccess, "seg_components: clearing count failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+  }
+  SEGCLIP_REQUIRE(images && labels, "seg_components: images and labels are required");
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_components: the workspace is required, 16-byte aligned");
+  if (!ids && !area_px && !count && !cleaned) return 0;  // nothing asked for
+
+  SegCCArgs a;
+  a.images = images; a.labels = labels; a.labels_bytes = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
+  a.B = (int)B; a.max_side = (int)max_side; a.conn8 = connectivity == 8; a.skip = skip_label;
+  char* base = static_cast<char*>(ws);
+  a.seg = reinterpret_cast<int64_t*>(base + w.seg);
+  a.parent = reinterpret_cast<int32_t*>(base + w.parent);
+  a.root = ids ? ids : reinterpret_cast<int32_t*>(base + w.root);
+  a.area = reinterpret_cast<int32_t*>(base + w.area);
+  a.rank = reinterpret_cast<int32_t*>(base + w.rank);
+  a.area_px = area_px; a.records = records; a.K = records ? K : 0; a.min_area = min_area; a.fill = fill; a.cleaned = cleaned;
+
+  const dim3 grid((unsigned)n_blocks), block(256);
+  hipLaunchKernelGGL(seg_cc_local_kernel, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_components (local)");
+  hipLaunchKernelGGL(seg_cc_merge_kernel, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_components (merge)");
+  if (count) {
+    // the entries of a table row that the device skips, and those past an image's last row, count nothing
+    const hipError_t e = hipMemsetAsync(a.seg, 0, (size_t)a.n_seg * sizeof(int64_t), ST);
+    SEGCLIP_REQUIRE(e == hipSuccess, "seg_components: clearing the segment counts failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(seg_cc_roots_kernel<false>, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_components (count)");
+    int64_t* part = reinterpret_cast<int64_t*>(base + w.part);
+    const int64_t chunks = cdiv(a.n_seg, SEG_CC_SCAN_CHUNK);
+    hipLaunchKernelGGL(seg_cc_chunk_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, ST, a.seg, a.n_seg, part);
+    SEGCLIP_CHECK_LAUNCH("seg_components (chunk totals)");
+    hipLaunchKernelGGL(seg_cc_scan_kernel, dim3(1), dim3(1024), 0, ST, part, chunks, count);
+    SEGCLIP_CHECK_LAUNCH("seg_components (scan)");
+    hipLaunchKernelGGL(seg_cc_chunk_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, ST, a.seg, a.n_seg, part);
+    SEGCLIP_CHECK_LAUNCH("seg_components (chunk scans)");
+    if (records && K > 0) {
+      hipLaunchKernelGGL(seg_cc_roots_kernel<true>, grid, block, 0, ST, a);
+      SEGCLIP_CHECK_LAUNCH("seg_components (rank)");
+    }
+  }
+  if (records && K > 0) hipLaunchKernelGGL(seg_cc_stats_kernel<true>, grid, block, 0, ST, a);
+  else hipLaunchKernelGGL(seg_cc_stats_kernel<false>, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_components (stats)");
+  if (area_px || cleaned) {
+    hipLaunchKernelGGL(seg_cc_final_kernel, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_components (final)");
+  }
   return 0;
 }
 

@@ -2850,6 +2850,66 @@ def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv
     return out
 
 
+# ---------------------------------------------------------------- connected components of label maps (segment_objects.inc)
+SEG_CC_TILE = (16, 64)       # (TH, TW): rows x columns of one workgroup's tile of segclip_seg_components
+SEG_CC_COLS = 8              # int64 columns of one row of its image table
+SEG_CC_RECORD = 10           # int64 columns of a record: image, id, label, area, y0, x0, y1, x1, sum of y, sum of x
+
+
+def seg_components_table(sizes, offsets, device):
+    """The device image table of seg_components: sizes [(h, w)], offsets [offset of each image's h * w entries in the flat
+    label buffer; ids, area_px and cleaned take the same offsets] -> (table (B, 8) int64, n_blocks, largest side)."""
+    if len(sizes) == 0 or len(sizes) != len(offsets):
+        raise ValueError(f"seg_components: {len(sizes)} sizes but {len(offsets)} offsets")
+    th, tw = SEG_CC_TILE
+    tab, blk, side = [], 0, 0
+    for (h, w), off in zip(sizes, offsets):
+        h, w = int(h), int(w)
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_components: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+        tab.append([h, w, int(off), blk, 0, 0, 0, 0])
+        blk += ((h + th - 1) // th) * ((w + tw - 1) // tw)
+        side = max(side, h, w)
+    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_CC_COLS), blk, side
+
+
+def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids=None, area_px=None, records=None, count=None,
+                   min_area=0, fill=0, cleaned=None, max_side=None):
+    """Connected components of the flat uint8 `labels` under the table of seg_components_table (segclip_seg_components; the
+    definition stands in include/segclip_hip.h).  Every output is optional and written where given: ids / area_px flat int32
+    with one entry per label byte, records (K, 10) int64 with count (1,) int64 (count alone is allowed), cleaned flat uint8 of
+    the labels' size (it may not overlap them): fill where a component has fewer than min_area pixels.  skip_label: a byte whose
+    pixels belong to no component.  max_side: the largest h or w of the table (defaults to the limit).  No host
+    synchronisation.  -> None."""
+    L.require_cuda(table, labels, ids, area_px, records, count, cleaned)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_CC_COLS or not table.is_contiguous():
+        raise ValueError("seg_components: table is the (B, 8) int64 tensor of seg_components_table")
+    if labels.dtype != torch.uint8 or not labels.is_contiguous():
+        raise ValueError("seg_components: labels is a contiguous uint8 tensor")
+    for name, t, dt in (("ids", ids, torch.int32), ("area_px", area_px, torch.int32), ("records", records, torch.int64),
+                        ("count", count, torch.int64), ("cleaned", cleaned, torch.uint8)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"seg_components: {name} is a contiguous {dt} tensor")
+    if records is not None and (records.dim() != 2 or records.shape[1] != SEG_CC_RECORD):
+        raise ValueError(f"seg_components: records is a (K, {SEG_CC_RECORD}) int64 tensor, got {tuple(records.shape)}")
+    if count is not None and count.numel() != 1:
+        raise ValueError("seg_components: count holds one int64")
+    px = [t.numel() for t in (ids, area_px) if t is not None]
+    if len(set(px)) > 1:
+        raise ValueError("seg_components: ids and area_px have the same number of entries")
+    B = table.shape[0]
+    lib = L.load()
+    ws_bytes = lib.segclip_seg_components_ws_bytes(labels.numel(), B, int(n_blocks))
+    if ws_bytes < 0:
+        L.check(ws_bytes, "seg_components")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=labels.device)
+    L.check(lib.segclip_seg_components(
+        L.ptr(table), B, int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(labels), labels.numel(),
+        int(connectivity), -1 if skip_label is None else int(skip_label), L.ptr(ids), L.ptr(area_px), px[0] if px else 0,
+        L.ptr(records), records.shape[0] if records is not None else 0, L.ptr(count), int(min_area), int(fill), L.ptr(cleaned),
+        cleaned.numel() if cleaned is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_components")
+
+
 # ---------------------------------------------------------------- image-text retrieval evaluation (retrieval.hip)
 RETRIEVAL_BAD_INDEX = 1  # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
 

@@ -41,6 +41,12 @@ up twice, so its borders follow the patch grid; the refinement moves them onto t
 (csrc/segment_refine.inc) without a (C, h, w) tensor and without a host synchronisation, and with a ground truth its last
 kernel adds the mIoU areas.  Not covered: the threshold sweep, render_raw, and the entry points without a raw picture.
 
+Objects (not in the reference): components labels the connected components of label maps on the device
+(csrc/segment_objects.inc) - ids whose value is the component's first pixel in raster order, so they depend on no scheduling -
+and returns them with a compact list of boxes, areas and coordinate sums; despeckle / Despeckle replace components below a
+minimum area by a fill label, and predict_raw / update_raw / eval_epoch take clean=, applied after refine=.  Not covered: the
+threshold sweep, render_raw, predict_list and update (apply despeckle to their maps).
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -393,6 +399,109 @@ def _check_refine(refine, raws, out_shapes):
                              f"every label), got {list(out_shapes)}")
 
 
+class Despeckle:
+    """Despeckling as a post-processing step of the label maps: every connected component (`connectivity` 4 or 8) with fewer
+    than `min_area` pixels becomes `fill`; the pixels of `skip_label` belong to no component and stay.  One pass: what became
+    `fill` is not merged again (csrc/segment_objects.inc; the definition stands in include/segclip_hip.h).  The reference has
+    no such step."""
+
+    def __init__(self, min_area, fill=0, connectivity=8, skip_label=None):
+        if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 0:
+            raise ValueError(f"Despeckle: min_area is a non-negative integer, got {min_area!r}")
+        if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+            raise ValueError(f"Despeckle: fill is an integer in 0 .. 255, got {fill!r}")
+        if isinstance(connectivity, bool) or connectivity not in (4, 8):
+            raise ValueError(f"Despeckle: connectivity is 4 or 8, got {connectivity!r}")
+        if skip_label is not None and (isinstance(skip_label, bool) or not isinstance(skip_label, int) or not 0 <= skip_label <= 255):
+            raise ValueError(f"Despeckle: skip_label is None or an integer in 0 .. 255, got {skip_label!r}")
+        self.min_area, self.fill, self.connectivity, self.skip_label = min_area, fill, connectivity, skip_label
+
+
+def _check_label_maps(maps):
+    if len(maps) == 0:
+        raise ValueError("empty list of label maps")
+    ops.L.require_cuda(*maps)
+    for m in maps:
+        if m.dtype != torch.uint8 or m.dim() != 2 or m.numel() == 0:
+            raise ValueError(f"a label map is a non-empty (h, w) uint8 tensor, got {m.dtype} {tuple(m.shape)}")
+        if m.device != maps[0].device:
+            raise ValueError("the label maps are on different devices")
+
+
+class Objects:
+    """The connected components of a list of label maps (components): ids [(h_i, w_i) int32 maps, views of one buffer: the id
+    of a pixel's component = the flat index y * w + x of the component's first pixel in raster order, -1 where the label is
+    skipped], records ((n, 10) int64 device tensor, one row per component in ascending (image, id) order: image, id, label,
+    area, y0, x0, y1, x1, sum of y, sum of x; y1 and x1 exclusive) and count = n."""
+
+    def __init__(self, ids, records, count):
+        self.ids, self.records, self.count = ids, records, count
+
+    def boxes(self):
+        """(n, 6) int64: image, label, y0, x0, y1, x1 (y1 and x1 exclusive)"""
+        return self.records[:, [0, 2, 4, 5, 6, 7]]
+
+    def centroids(self):
+        """(n, 2) fp64: (sum of y / area, sum of x / area)"""
+        return self.records[:, 8:10].double() / self.records[:, 3:4].double()
+
+
+@torch.no_grad()
+def components(maps, connectivity=8, skip_label=None, max_objects=None):
+    """maps [(h_i, w_i) uint8 label maps of any mix of sizes] -> Objects: the connected components of every map, labelled on the
+    device in one call.  max_objects bounds the record list (default: one row per 16 pixels, at least 4096 rows).  Reading the
+    count is the ONE host synchronisation of this function; more components than max_objects raise a ValueError that names
+    both numbers (ask again with a larger max_objects)."""
+    maps = list(maps)
+    _check_label_maps(maps)
+    flat, offs = _flat_maps(maps)
+    sizes = [tuple(m.shape) for m in maps]
+    dev = flat.device
+    if max_objects is None:
+        max_objects = max(4096, sum(h * w for h, w in sizes) // 16)
+    if isinstance(max_objects, bool) or not isinstance(max_objects, int) or max_objects < 1:
+        raise ValueError(f"components: max_objects is a positive integer, got {max_objects!r}")
+    table, n_blocks, side = ops.seg_components_table(sizes, offs, dev)
+    ids = torch.empty(flat.numel(), dtype=torch.int32, device=dev)
+    records = torch.empty(max_objects, ops.SEG_CC_RECORD, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ops.seg_components(table, n_blocks, flat, connectivity=connectivity, skip_label=skip_label, ids=ids, records=records,
+                       count=count, max_side=side)
+    n = int(count.item())
+    if n > max_objects:
+        raise ValueError(f"components: the maps hold {n} components but max_objects is {max_objects}")
+    return Objects(_split_maps(ids, offs, sizes), records[:n], n)
+
+
+def _check_clean(clean):
+    if not isinstance(clean, Despeckle):
+        raise TypeError("clean is a Despeckle")
+
+
+def _despeckle_maps(maps, clean):
+    """-> (the cleaned maps, views of one new buffer; that buffer; the maps' offsets in it)"""
+    _check_clean(clean)
+    maps = list(maps)
+    _check_label_maps(maps)
+    flat, offs = _flat_maps(maps)
+    sizes = [tuple(m.shape) for m in maps]
+    table, n_blocks, side = ops.seg_components_table(sizes, offs, flat.device)
+    out = torch.empty_like(flat)
+    if out.numel() != sum(h * w for h, w in sizes):
+        out.zero_()  # the bytes between the maps
+    ops.seg_components(table, n_blocks, flat, connectivity=clean.connectivity, skip_label=clean.skip_label, min_area=clean.min_area,
+                       fill=clean.fill, cleaned=out, max_side=side)
+    return _split_maps(out, offs, sizes), out, offs
+
+
+@torch.no_grad()
+def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None):
+    """maps [(h_i, w_i) uint8 label maps] -> [(h_i, w_i) uint8], views of one new buffer: every connected component with fewer
+    than min_area pixels replaced by `fill` (see Despeckle), all maps in one call and without a host synchronisation.  The
+    inputs stay as they are."""
+    return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label))[0]
+
+
 def _out_shapes(src, out_shapes):
     """The output sizes of a list call, one per image: the caller's, or the source's default."""
     n_img = len(src.view_counts)
@@ -625,18 +734,20 @@ class SegInference:
         return (self._views_forward if src.augmented else self._list_forward)(src, out_shapes, **kw)
 
     @torch.no_grad()
-    def predict_list(self, imgs, out_shapes=None, refine=None):
+    def predict_list(self, imgs, out_shapes=None, refine=None, clean=None):
         """[(3, H_i, W_i)] of any mix of sizes -> [(oh_i, ow_i) uint8 labels], views of one flat buffer; out_shapes defaults
         to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
         Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size.
-        refine is refused: there is no raw picture here (predict_raw has it)."""
+        refine is refused: there is no raw picture here (predict_raw has it); clean too: despeckle the maps."""
         if refine is not None:
             raise ValueError("predict_list: refine needs the decoded pictures: use predict_raw(refine=) or refine_labels")
+        if clean is not None:
+            raise ValueError("predict_list: clean is not supported; apply despeckle to the maps it returns")
         return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes)
 
     @torch.no_grad()
-    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None, refine=None):
+    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None, refine=None, clean=None):
         """[(h_i, w_i, 3) uint8 decoded images] -> [(oh_i, ow_i) uint8 labels] as predict_list(preprocess(raws, transform,
         net_sizes), out_shapes), bit for bit, without the resized images: the windows of a tower call are written from the
         raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
@@ -646,12 +757,18 @@ class SegInference:
         then holds one (H, W) per view of every image.
         refine (a PAMR): the label maps pass through the pixel-adaptive refinement against the raw pictures before they are
         returned, = refine_labels(raws, predict_raw(raws, ...), num_classes, transform, refine) bit for bit.  out_shapes must
-        then be the raw sizes (the default).  It composes with aug: the refinement sees only labels."""
+        then be the raw sizes (the default).  It composes with aug: the refinement sees only labels.
+        clean (a Despeckle): the maps, after the refinement if there is one, are despeckled before they are returned,
+        = despeckle(predict_raw(raws, ...), ...) bit for bit."""
+        if clean is not None:
+            _check_clean(clean)
         if refine is None:
-            return self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
-        _check_refine(refine, raws, out_shapes)
-        labels = self._forward(_RawImages(raws, transform, net_sizes, aug), None)
-        return _refine_maps(raws, labels, self.num_classes, transform, refine)
+            labels = self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
+        else:
+            _check_refine(refine, raws, out_shapes)
+            labels = self._forward(_RawImages(raws, transform, net_sizes, aug), None)
+            labels = _refine_maps(raws, labels, self.num_classes, transform, refine)
+        return labels if clean is None else _despeckle_maps(labels, clean)[0]
 
     @torch.no_grad()
     def predict_views(self, views, out_shapes):
@@ -688,7 +805,7 @@ class SegInference:
         return self._list_forward(_RawImages(raws, transform, net_sizes), out_shapes, groups="only")[1]
 
     @torch.no_grad()
-    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None, refine=None):
+    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None, refine=None, clean=None):
         """The reference's --vis modes (show_result, vit_seg.py:286-377) for decoded images, at their own sizes -> dict
         mode -> result:
           input              the raws
@@ -700,9 +817,11 @@ class SegInference:
         palette: (P, 3) uint8 RGB class colours (index 0 = background when with_bg); group_palette defaults to
         default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
         call whatever the modes: labels and group maps come from the same encode_image pass.  refine is refused: draw refined
-        maps with blend(raws, predict_raw(raws, transform, refine=...), palette)."""
+        maps with blend(raws, predict_raw(raws, transform, refine=...), palette).  clean is refused in the same way."""
         if refine is not None:
             raise ValueError("render_raw: refine is not supported; blend the maps of predict_raw(refine=) instead")
+        if clean is not None:
+            raise ValueError("render_raw: clean is not supported; blend the maps of despeckle(predict_raw(...)) instead")
         modes = list(vis_modes)
         for m in modes:
             if m not in VIS_MODES:
@@ -850,20 +969,40 @@ class SegEvaluator:
         self.areas.zero_()
 
     @torch.no_grad()
-    def update(self, imgs, gts, return_labels=False, refine=None):
+    def update(self, imgs, gts, return_labels=False, refine=None, clean=None):
         """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size.  refine is
-        refused: there is no raw picture here (update_raw has it)."""
+        refused: there is no raw picture here (update_raw has it); clean is refused too (update_raw has it)."""
         if refine is not None:
             raise ValueError("SegEvaluator.update: refine needs the decoded pictures: use update_raw(refine=)")
+        if clean is not None:
+            raise ValueError("SegEvaluator.update: clean is not supported; use update_raw(clean=), or despeckle the maps and "
+                             "score them with ops.seg_areas")
         self._check_gts(imgs, gts)
         return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None):
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
         """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included).
         refine (a PAMR): the areas are those of the refined label maps, added by the refinement's last kernel; the label
-        kernel then only writes the maps and counts nothing.  The ground truths must have the pictures' sizes."""
+        kernel then only writes the maps and counts nothing.  The ground truths must have the pictures' sizes.
+        clean (a Despeckle): the labels are formed (and refined) without counting, despeckled, and ops.seg_areas of the cleaned
+        maps against the ground truths is added: the areas are those of the cleaned maps."""
         self._check_gts(raws, gts)
+        if clean is not None:
+            _check_clean(clean)
+            shapes = [tuple(g.shape) for g in gts]
+            if refine is None:
+                labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), shapes)
+            else:
+                _check_refine(refine, raws, shapes)
+                labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), None)
+                labels = _refine_maps(raws, labels, self.seg.num_classes, transform, refine)
+            cleaned, flat, offs = _despeckle_maps(labels, clean)
+            if flat.numel() != sum(g.numel() for g in gts):  # bytes between the maps: score a gapless copy
+                flat = torch.cat([c.reshape(-1) for c in cleaned])
+            ops.seg_areas(flat, _flat_gts(list(gts)), self.seg.num_classes, ignore_index=self.ignore_index,
+                          reduce_zero_label=self.reduce_zero_label, areas=self.areas)
+            return cleaned if return_labels else None
         if refine is None:
             return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
         _check_refine(refine, raws, [tuple(g.shape) for g in gts])
@@ -956,8 +1095,11 @@ class SegSweepEvaluator:
         return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None):
-        """As SegEvaluator.update_raw, without aug and without refine."""
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
+        """As SegEvaluator.update_raw, without aug, without refine and without clean."""
+        if clean is not None:
+            raise ValueError("SegSweepEvaluator: clean is not supported (every threshold's map would need its own pass); despeckle "
+                             "the maps of one SegEvaluator per threshold (update_raw(clean=))")
         if refine is not None:
             raise ValueError("SegSweepEvaluator: refine is not supported (every threshold's map would need its own refinement); "
                              "use one SegEvaluator per threshold")

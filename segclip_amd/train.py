@@ -289,7 +289,10 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     end.  With several ranks every rank scores its own share; all_reduce SegEvaluator.areas instead of calling this when one
     figure over all ranks is wanted.  test_cfg["aug"] (a segmentation.TestAug; needs transform): mmseg's flip / multi-scale
     test-time augmentation, SegEvaluator.update_raw(aug=).  test_cfg["refine"] (a segmentation.PAMR; needs transform): the
-    label maps are refined against the decoded pictures before they are scored, SegEvaluator.update_raw(refine=)."""
+    label maps are refined against the decoded pictures before they are scored, SegEvaluator.update_raw(refine=).
+    test_cfg["clean"] (a segmentation.Despeckle; needs transform): connected components of the label maps below its minimum
+    area are replaced by its fill label before the maps are scored, after the refinement if both are given,
+    SegEvaluator.update_raw(clean=)."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
@@ -299,6 +302,9 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     refine = cfg.pop("refine", None)
     if refine is not None and transform is None:
         raise ValueError("eval_epoch: test_cfg['refine'] refines against the decoded images: pass a transform")
+    clean = cfg.pop("clean", None)
+    if clean is not None and transform is None:
+        raise ValueError("eval_epoch: test_cfg['clean'] is applied by SegEvaluator.update_raw: pass a transform")
     model = _unwrap(model)
     model.eval()
     emb = build_text_embedding(model, text_tokens.to(device))
@@ -308,7 +314,7 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
         if transform is None:
             evaluator.update(imgs, gts)
         else:
-            evaluator.update_raw(imgs, gts, transform, aug=aug, refine=refine)
+            evaluator.update_raw(imgs, gts, transform, aug=aug, refine=refine, clean=clean)
     miou = evaluator.compute()["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)

@@ -1,0 +1,490 @@
+"""GPU: the connected components of label maps (csrc/segment_objects.inc, segclip_seg_components) against the CPU restatement
+tests/cc_reference.py.  Everything is an integer, so every comparison is torch.equal: ids, area_px, records[:count], count and
+cleaned, for connectivity 4 and 8.  Every output lies in a frame (tests/kernel_frames.py), the input labels too: nothing outside
+the outputs is written and the inputs stay as they are.  The maps come from cc_reference.cases(*ops.SEG_CC_TILE): their
+features sit on the borders of whatever tile the kernel uses."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import segclip_amd
+from segclip_amd import _lib as L
+from segclip_amd import ops
+from segclip_amd.segmentation import (PAMR, Despeckle, ImageTransform, Objects, SegEvaluator, SegInference, SegSweepEvaluator,
+                                      components, despeckle, refine_labels)
+from segclip_amd.train import eval_epoch
+from tests import cc_reference as cc
+from tests import kernel_frames as kf
+from tests.helpers import load_golden
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+TH, TW = ops.SEG_CC_TILE
+CASES = cc.cases(TH, TW)
+ERR_INVALID, ERR_UNSUPPORTED = -1, -2
+BOTH = pytest.mark.parametrize("connectivity", [4, 8])
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, connectivity, skip=None, min_area=0, fill=0):
+    """the restatement of a case, computed once: (flat ids, flat area_px, records, flat cleaned) as CPU tensors"""
+    ids, area, records, cleaned = cc.components(CASES[name], connectivity, skip, min_area, fill)
+    cat = lambda xs: torch.from_numpy(np.concatenate([x.reshape(-1) for x in xs]))
+    return cat(ids), cat(area), torch.from_numpy(records), cat(cleaned)
+
+
+class Run:
+    """One call of ops.seg_components on framed buffers.  The maps lie one after the other (offsets that are no multiples of 4
+    where the sizes are not), `gap` unused bytes between them."""
+
+    def __init__(self, maps, connectivity, skip=None, K=0, min_area=0, fill=0, gap=0, outputs=("ids", "area_px", "records", "cleaned")):
+        self.sizes = [tuple(m.shape) for m in maps]
+        self.offs, n = [], 0
+        for (h, w) in self.sizes:
+            self.offs.append(n)
+            n += h * w + gap
+        n -= gap
+        self.n = n
+        self.used = torch.zeros(n, dtype=torch.bool)
+        self.fin = kf.Frame((n,), torch.uint8)
+        self.fin.v.fill_(0xEE)
+        for m, o in zip(maps, self.offs):
+            self.fin.v[o:o + m.size] = torch.from_numpy(np.ascontiguousarray(m)).reshape(-1).to(DEV)
+            self.used[o:o + m.size] = True
+        self.in_bits = self.fin.bits()
+        self.fids = kf.Frame((n,), torch.int32) if "ids" in outputs else None
+        self.farea = kf.Frame((n,), torch.int32) if "area_px" in outputs else None
+        self.frec = kf.Frame((K, ops.SEG_CC_RECORD), torch.int64) if "records" in outputs and K > 0 else None
+        self.fcount = kf.Frame((1,), torch.int64) if "records" in outputs or "count" in outputs else None
+        self.fclean = kf.Frame((n,), torch.uint8) if "cleaned" in outputs else None
+        self.K = K
+        self.table, self.n_blocks, self.side = ops.seg_components_table(self.sizes, self.offs, DEV)
+        v = lambda f: None if f is None else f.v
+        self.call = lambda table=self.table: ops.seg_components(
+            table, self.n_blocks, self.fin.v, connectivity=connectivity, skip_label=skip, ids=v(self.fids), area_px=v(self.farea),
+            records=v(self.frec), count=v(self.fcount), min_area=min_area, fill=fill, cleaned=v(self.fclean), max_side=self.side)
+
+    def frames(self):
+        return [f for f in (self.fids, self.farea, self.frec, self.fcount, self.fclean) if f is not None]
+
+    def run(self, **kw):
+        self.call(**kw)
+        torch.cuda.synchronize()
+        self.check_frames()
+        return self
+
+    def check_frames(self):
+        assert all(f.intact() for f in self.frames()), "wrote outside an output"
+        assert torch.equal(self.in_bits, self.fin.bits()), "the input labels changed"
+        for f in (self.fids, self.farea, self.fclean):   # the bytes between two maps stay
+            if f is not None:
+                assert bool((f.v.cpu()[~self.used] == f.fill).all()), "wrote between the maps"
+
+    def check(self, ids, area, records, cleaned, images=None):
+        """torch.equal against the restatement; images: the maps that the table really describes (default: all)"""
+        used = self.used
+        if images is not None:
+            used = torch.zeros_like(self.used)
+            for k in images:
+                used[self.offs[k]:self.offs[k] + self.sizes[k][0] * self.sizes[k][1]] = True
+        for f, want, what in ((self.fids, ids, "ids"), (self.farea, area, "area_px"), (self.fclean, cleaned, "cleaned")):
+            if f is not None:
+                got = f.v.cpu()
+                assert torch.equal(got[used], want.to(got.dtype)), f"{what} differs from the restatement"
+                assert bool((got[~used] == f.fill).all()), f"{what}: written outside the images of the table"
+        if self.fcount is not None:
+            n = int(self.fcount.v.cpu()[0])
+            assert n == records.shape[0], f"count {n}, the restatement has {records.shape[0]} components"
+            if self.frec is not None:
+                got, k = self.frec.v.cpu(), min(n, self.K)
+                assert torch.equal(got[:k], records[:k]), "records differ from the restatement"
+                assert bool((got[k:] == self.frec.fill).all()), "rows beyond the count were written"
+
+
+# ------------------------------------------------------------------------------------------------ 1. every map, every output
+@BOTH
+@pytest.mark.parametrize("name", list(CASES))
+def test_against_the_restatement(name, connectivity):
+    ids, area, records, cleaned = reference(name, connectivity, None, 3, 200)
+    r = Run(CASES[name], connectivity, K=records.shape[0] + 3, min_area=3, fill=200).run()
+    r.check(ids, area, records, cleaned)
+
+
+def test_what_the_cases_are_there_for():
+    """the counts that make the cases what the issue describes: diagonal pairs join under 8 only, chains are one component, the
+    4-connected checkerboard has one component per pixel"""
+    for name in cc.diagonals(TH, TW):
+        assert (reference(name, 4)[2].shape[0], reference(name, 8)[2].shape[0]) == (3, 2), name
+    for name in ("serpentine", "spiral"):
+        assert reference(name, 4)[2].shape[0] == reference(name, 8)[2].shape[0] == 2
+    h, w = CASES["checkerboard"][0].shape
+    assert reference("checkerboard", 4)[2].shape[0] == h * w and reference("checkerboard", 8)[2].shape[0] == 2
+    for name in ("long_row", "long_column", "whole_image"):
+        assert reference(name, 4)[2].tolist() == reference(name, 8)[2].tolist() and reference(name, 4)[2].shape[0] == 1
+    assert [o % 4 for o in Run(CASES["mixed_batch"], 8, outputs=("ids",)).offs] == [0, 3, 2, 1]
+
+
+@BOTH
+def test_mixed_batch_with_a_gap_between_the_maps(connectivity):
+    ids, area, records, cleaned = reference("mixed_batch", connectivity, None, 3, 200)
+    r = Run(CASES["mixed_batch"], connectivity, K=records.shape[0], min_area=3, fill=200, gap=5).run()
+    assert [o % 4 for o in r.offs] == [0, 0, 0, 0] and r.offs[1] == 40
+    r.check(ids, area, records, cleaned)
+
+
+def test_more_row_segments_than_one_pass_of_the_scan():
+    """2^20 + 5 images of one pixel = as many tiles: 16 row-segment entries each, so the chunk totals (one per 2048 entries) are
+    more than the 8192 that the scanning workgroup takes in one pass.  Every image is one component of one pixel; the restatement
+    says so for the first of them."""
+    B = (1 << 20) + 5
+    labels = (torch.arange(B, device=DEV) % 3).to(torch.uint8)
+    idx = torch.arange(B, device=DEV)
+    table = torch.zeros(B, ops.SEG_CC_COLS, dtype=torch.int64, device=DEV)
+    table[:, 0], table[:, 1], table[:, 2], table[:, 3] = 1, 1, idx, idx
+    small = ops.seg_components_table([(1, 1)] * 4, list(range(4)), DEV)
+    assert torch.equal(table[:4], small[0]) and small[1] == 4
+    fids, farea, frec, fcount = kf.Frame((B,), torch.int32), kf.Frame((B,), torch.int32), kf.Frame((B, 10), torch.int64), kf.Frame((1,), torch.int64)
+    ops.seg_components(table, B, labels, connectivity=4, ids=fids.v, area_px=farea.v, records=frec.v, count=fcount.v, max_side=1)
+    torch.cuda.synchronize()
+    assert all(f.intact() for f in (fids, farea, frec, fcount))
+    want = torch.zeros(B, 10, dtype=torch.int64, device=DEV)
+    want[:, 0], want[:, 2], want[:, 3], want[:, 6], want[:, 7] = idx, labels.long(), 1, 1, 1
+    ref = cc.components([np.full((1, 1), k % 3, dtype=np.uint8) for k in range(50)], 4)
+    assert torch.equal(want[:50].cpu(), torch.from_numpy(ref[2]))
+    assert int(fcount.v[0]) == B and torch.equal(frec.v, want)
+    assert bool((fids.v == 0).all()) and bool((farea.v == 1).all())
+
+
+# ------------------------------------------------------------------------------------------------ 2. the skip label
+@BOTH
+@pytest.mark.parametrize("name,skip", [("noise_3_labels", 0), ("bytes_0_7_255", 255), ("whole_image", 1)])
+def test_skip_label(name, skip, connectivity):
+    ids, area, records, cleaned = reference(name, connectivity, skip, 3, 9)
+    r = Run(CASES[name], connectivity, skip=skip, K=records.shape[0] + 1, min_area=3, fill=9).run()
+    r.check(ids, area, records, cleaned)
+    skipped = torch.from_numpy(np.concatenate([m.reshape(-1) for m in CASES[name]])) == skip
+    assert int(skipped.sum()) > 0
+    assert bool((r.fids.v.cpu()[skipped] == -1).all()) and bool((r.farea.v.cpu()[skipped] == 0).all())
+    assert bool((r.fclean.v.cpu()[skipped] == skip).all()) and not bool((records[:, 2] == skip).any())
+
+
+# ------------------------------------------------------------------------------------------------ 3. the record capacity
+@BOTH
+@pytest.mark.parametrize("name", ["noise_3_labels", "mixed_batch"])
+def test_record_capacity(name, connectivity):
+    ids, area, records, cleaned = reference(name, connectivity)
+    n = records.shape[0]
+    assert n > 3
+    for K in (n - 1, 1, n):
+        r = Run(CASES[name], connectivity, K=K).run()
+        r.check(ids, area, records, cleaned)          # the true count, exactly the first K rows, the frame behind them intact
+    # no records: the count alone, and ids without either
+    r = Run(CASES[name], connectivity, outputs=("ids", "count")).run()
+    r.check(ids, area, records, cleaned)
+    r = Run(CASES[name], connectivity, outputs=("ids",)).run()
+    assert r.fcount is None and r.frec is None
+    r.check(ids, area, records, cleaned)
+    for only in ("area_px", "cleaned", "count"):
+        Run(CASES[name], connectivity, outputs=(only,)).run().check(ids, area, records, cleaned)
+
+
+# ------------------------------------------------------------------------------------------------ 4. despeckling
+@BOTH
+@pytest.mark.parametrize("fill", [0, 255])
+def test_despeckle_thresholds(fill, connectivity):
+    name = "blocks_21_labels"
+    sizes = sorted(set(reference(name, connectivity)[2][:, 3].tolist()))
+    assert len(sizes) >= 2
+    between = (sizes[0] + sizes[1] + 1) // 2
+    assert sizes[0] < between <= sizes[1]
+    h, w = CASES[name][0].shape
+    labels = torch.from_numpy(CASES[name][0].reshape(-1))
+    seen = set()
+    for min_area in (0, 1, 2, between, h * w + 1):
+        ids, area, records, cleaned = reference(name, connectivity, None, min_area, fill)
+        r = Run(CASES[name], connectivity, min_area=min_area, fill=fill, outputs=("cleaned",)).run()
+        r.check(ids, area, records, cleaned)
+        got = r.fclean.v.cpu()
+        if min_area <= 1:
+            assert torch.equal(got, labels), "min_area 0 and 1 return the input"
+        if min_area == h * w + 1:
+            assert bool((got == fill).all())
+        seen.add(int((got != labels).sum()))
+    assert len(seen) >= 3, "the thresholds of the case do not tell its components apart"
+
+
+def test_despeckle_is_one_pass():
+    """a speck inside a region of the fill label becomes fill and is NOT merged: the region's own area_px stays what it was"""
+    m = np.zeros((TH + 4, TW + 4), dtype=np.uint8)
+    m[TH - 1:TH + 1, TW - 1:TW + 1] = 4
+    r = Run([m], 8, min_area=5, fill=0).run()
+    assert bool((r.fclean.v == 0).all())
+    assert sorted(set(r.farea.v.cpu().tolist())) == [4, m.size - 4]
+
+
+# ------------------------------------------------------------------------------------------------ 5. table rows
+@BOTH
+def test_a_bad_table_row_is_skipped(connectivity):
+    ids, area, records, cleaned = cc.components(CASES["mixed_batch"], connectivity, None, 3, 200)
+    for row, col, value in ((1, 0, 0), (1, 1, 1 << 15), (2, 2, None), (0, 2, -1), (1, 0, None)):
+        r = Run(CASES["mixed_batch"], connectivity, K=records.shape[0], min_area=3, fill=200)
+        bad = r.table.clone()
+        if value is None and col == 2:
+            value = r.n - 10                      # the offset runs past the buffer
+        if value is None:
+            value = r.side + 1                    # beyond the caller's max_side
+        bad[row, col] = value
+        r.run(table=bad)
+        keep = [k for k in range(4) if k != row]
+        rows = records[records[:, 0] != row]
+        cat = lambda xs: torch.from_numpy(np.concatenate([xs[k].reshape(-1) for k in keep]))
+        r.check(cat(ids), cat(area), torch.from_numpy(rows), cat(cleaned), images=keep)
+
+
+# ------------------------------------------------------------------------------------------------ 6. two calls, the same bits
+@BOTH
+@pytest.mark.parametrize("name", ["noise_3_labels", "mixed_batch"])
+def test_two_calls_give_identical_bits(name, connectivity):
+    n = reference(name, connectivity)[2].shape[0]
+    r = Run(CASES[name], connectivity, K=n, min_area=2, fill=7).run()
+    snap = [f.bits() for f in r.frames()]
+    for f in r.frames():
+        f.buf.fill_(f.fill)
+    r.run()
+    assert all(torch.equal(a, f.bits()) for a, f in zip(snap, r.frames())), f"{name}: the second call differs"
+
+
+def test_the_call_does_not_synchronise():
+    n = reference("mixed_batch", 8)[2].shape[0]
+    r = Run(CASES["mixed_batch"], 8, K=n, min_area=2, fill=7).run()     # the library is loaded
+    want = [f.bits() for f in r.frames()]
+    for f in r.frames():
+        f.buf.fill_(f.fill)
+    maps = [torch.from_numpy(m).to(DEV) for m in CASES["mixed_batch"]]
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        r.call()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    cleaned = despeckle(maps, 2, fill=7)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, f.bits()) for a, f in zip(want, r.frames()))
+    assert torch.equal(torch.cat([c.reshape(-1) for c in cleaned]), r.fclean.v)
+
+
+# ------------------------------------------------------------------------------------------------ 7. return codes
+def test_refusals_leave_the_outputs_untouched():
+    lib = L.load()
+    ids, area, records, cleaned = reference("mixed_batch", 8, None, 3, 200)
+    r = Run(CASES["mixed_batch"], 8, K=records.shape[0], min_area=3, fill=200)
+    n, B = r.n, len(r.sizes)
+    ws_bytes = lib.segclip_seg_components_ws_bytes(n, B, r.n_blocks)
+    assert ws_bytes >= 16 * n
+    ws = kf.Frame((ws_bytes,), torch.uint8)
+    P = lambda f: None if f is None else f.p
+
+    def call(conn=8, skip=-1, fill=200, min_area=3, side=r.side, ws_n=ws_bytes, ws_p=ws.p, px=n, records=r.frec, count=r.fcount,
+             cleaned=r.fclean.p, cleaned_n=n, labels=r.fin.p, images=L.ptr(r.table), K=r.K):
+        rc = lib.segclip_seg_components(images, B, r.n_blocks, side, labels, n, conn, skip, r.fids.p, r.farea.p, px, P(records), K,
+                                        P(count), min_area, fill, cleaned, cleaned_n, ws_p, ws_n, L.stream())
+        torch.cuda.synchronize()
+        return rc
+
+    def untouched():
+        return all(f.untouched() for f in r.frames()) and ws.untouched()
+
+    for kw in (dict(conn=6), dict(conn=0), dict(skip=-2), dict(skip=256), dict(fill=-1), dict(fill=256), dict(min_area=-1),
+               dict(side=0), dict(side=1 << 15), dict(ws_n=ws_bytes - 1), dict(ws_n=0)):
+        assert call(**kw) == ERR_UNSUPPORTED, kw
+        assert lib.segclip_last_error_string().decode().startswith("seg_components"), kw
+        assert untouched(), kw
+    for kw in (dict(count=None), dict(cleaned=r.fin.p), dict(cleaned=r.fin.v.data_ptr() + 8), dict(cleaned_n=n - 4), dict(px=n - 1),
+               dict(labels=None), dict(images=None), dict(ws_p=None), dict(K=-1)):
+        assert call(**kw) == ERR_INVALID, kw
+        assert lib.segclip_last_error_string().decode().startswith("seg_components"), kw
+        assert untouched(), kw
+    assert torch.equal(r.in_bits, r.fin.bits())
+    assert lib.segclip_seg_components_ws_bytes(-1, 1, 1) == ERR_UNSUPPORTED and lib.segclip_seg_components_ws_bytes(n, 1, 1 << 31) == ERR_UNSUPPORTED
+    # the wrapper
+    with pytest.raises(L.Unsupported, match="connectivity"):
+        ops.seg_components(r.table, r.n_blocks, r.fin.v, connectivity=5, ids=r.fids.v)
+    with pytest.raises(RuntimeError, match="overlaps"):
+        ops.seg_components(r.table, r.n_blocks, r.fin.v, cleaned=r.fin.v)
+    with pytest.raises(RuntimeError, match="records need count"):
+        ops.seg_components(r.table, r.n_blocks, r.fin.v, records=r.frec.v)
+    with pytest.raises(ValueError, match="records is a"):
+        ops.seg_components(r.table, r.n_blocks, r.fin.v, records=r.frec.v[:, :9].contiguous(), count=r.fcount.v)
+    with pytest.raises(ValueError, match="ids is a contiguous"):
+        ops.seg_components(r.table, r.n_blocks, r.fin.v, ids=r.fids.v.long())
+    assert untouched()
+    # and the accepted call on the same frames, with a workspace of exactly ws_bytes
+    assert call() == 0
+    r.check_frames()
+    assert ws.intact()
+    r.check(ids, area, records, cleaned)
+
+
+# ------------------------------------------------------------------------------------------------ 8. the Python layer
+@BOTH
+def test_components_and_despeckle(connectivity):
+    name = "mixed_batch"
+    ids, area, records, cleaned = reference(name, connectivity, 0, 4, 9)
+    maps = [torch.from_numpy(m).to(DEV) for m in CASES[name]]
+    keep = [m.clone() for m in maps]
+    obj = components(maps, connectivity=connectivity, skip_label=0)
+    assert isinstance(obj, Objects) and obj.count == records.shape[0] and obj.records.is_cuda
+    assert torch.equal(obj.records.cpu(), records)
+    assert [tuple(t.shape) for t in obj.ids] == [tuple(m.shape) for m in maps] and all(t.dtype == torch.int32 for t in obj.ids)
+    assert len({t.untyped_storage().data_ptr() for t in obj.ids}) == 1
+    assert torch.equal(torch.cat([t.reshape(-1) for t in obj.ids]).cpu(), ids)
+    assert torch.equal(obj.boxes().cpu(), records[:, [0, 2, 4, 5, 6, 7]])
+    cen = obj.centroids().cpu()
+    assert cen.dtype == torch.float64 and torch.equal(cen, records[:, 8:10].double() / records[:, 3:4].double())
+    with pytest.raises(ValueError, match=f"{records.shape[0]} components.*max_objects is {records.shape[0] - 1}"):
+        components(maps, connectivity=connectivity, skip_label=0, max_objects=records.shape[0] - 1)
+    assert components(maps, connectivity=connectivity, skip_label=0, max_objects=records.shape[0]).count == records.shape[0]
+    got = despeckle(maps, 4, fill=9, connectivity=connectivity, skip_label=0)
+    assert torch.equal(torch.cat([t.reshape(-1) for t in got]).cpu(), cleaned)
+    assert all(torch.equal(a, b) for a, b in zip(maps, keep)), "the inputs changed"
+    # views of one buffer (what predict_raw returns) are used where they lie
+    flat = torch.cat([m.reshape(-1) for m in maps])
+    views, o = [], 0
+    for m in maps:
+        views.append(flat[o:o + m.numel()].view(m.shape))
+        o += m.numel()
+    again = despeckle(views, 4, fill=9, connectivity=connectivity, skip_label=0)
+    assert torch.equal(torch.cat([t.reshape(-1) for t in again]).cpu(), cleaned)
+    with pytest.raises(ValueError, match="label map"):
+        despeckle([maps[0].int()], 2)
+    with pytest.raises(ValueError, match="min_area"):
+        despeckle(maps, -1)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        components([maps[0].cpu()])
+
+
+# ------------------------------------------------------------------------------------------------ 9. end to end
+TF = ImageTransform()
+SLIDE = dict(mode="slide", crop_size=(128, 128), stride=(96, 96))
+RAW_SIZES = [(90, 120), (130, 101), (75, 75)]
+
+
+def _tiny_model():
+    from segclip_amd import synth
+    segclip_amd.set_compute_dtype(torch.float32)
+    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
+    return model.eval()
+
+
+def _raws(seed):
+    g = torch.Generator().manual_seed(seed)
+    raws = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
+    gts = [torch.randint(0, 14, (h, w), generator=g).to(torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
+    for t in gts:
+        t[5:9] = 255
+    return raws, gts
+
+
+def _areas(maps, gts, C):
+    areas = torch.zeros(3, C, dtype=torch.int64, device=DEV)
+    for m, t in zip(maps, gts):
+        ops.seg_areas(m, t, C, reduce_zero_label=True, areas=areas)
+    return areas
+
+
+def _eq(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_end_to_end():
+    g = load_golden("seg_tiny.npz")
+    try:
+        model = _tiny_model()
+        emb = torch.from_numpy(g["text_embedding"]).to(DEV)
+        raws, gts = _raws(11)
+        seg = SegInference(model, emb, True, bg_thresh=0.02, **SLIDE)
+        C = seg.num_classes
+        plain = seg.predict_raw(raws, TF)
+        keep = [p.clone() for p in plain]
+        sizes = sorted(set(components(plain).records[:, 3].tolist()))
+        d = Despeckle(max(2, sizes[len(sizes) // 2]), fill=0, connectivity=4)
+        want = despeckle(plain, d.min_area, d.fill, d.connectivity, d.skip_label)
+        assert _eq(plain, keep), "despeckle changed its input"
+        assert not _eq(want, plain), "the case has nothing to despeckle"
+        # the restatement on this build's own label maps
+        ref = cc.components([p.cpu().numpy() for p in plain], 4, None, d.min_area, d.fill)[3]
+        assert _eq([w.cpu() for w in want], [torch.from_numpy(r) for r in ref])
+        # clean=None is the existing path
+        assert _eq(seg.predict_raw(raws, TF, clean=None), plain)
+        got = seg.predict_raw(raws, TF, clean=d)
+        assert [tuple(t.shape) for t in got] == RAW_SIZES and all(t.dtype == torch.uint8 for t in got)
+        assert _eq(got, want), "predict_raw(clean=) differs from despeckle(predict_raw())"
+        # the evaluator: the areas of the cleaned maps, once; without clean= what it gave before
+        ev0 = SegEvaluator(seg, reduce_zero_label=True)
+        assert _eq(ev0.update_raw(raws, gts, TF, return_labels=True, clean=None), plain)
+        assert torch.equal(ev0.areas, _areas(plain, gts, C))
+        ev = SegEvaluator(seg, reduce_zero_label=True)
+        maps = ev.update_raw(raws, gts, TF, return_labels=True, clean=d)
+        assert _eq(maps, want)
+        areas = _areas(want, gts, C)
+        assert torch.equal(ev.areas, areas) and int(areas.sum()) > 0 and not torch.equal(areas, ev0.areas)
+        assert ev.update_raw(raws, gts, TF, clean=d) is None
+        assert torch.equal(ev.areas, 2 * areas)
+        # refine= and clean= together: the two functions in that order
+        pamr = PAMR(iters=2, dilations=(1, 2))
+        both = despeckle(refine_labels(raws, plain, C, TF, pamr), d.min_area, d.fill, d.connectivity, d.skip_label)
+        assert _eq(seg.predict_raw(raws, TF, refine=pamr, clean=d), both)
+        ev = SegEvaluator(seg, reduce_zero_label=True)
+        assert _eq(ev.update_raw(raws, gts, TF, return_labels=True, refine=pamr, clean=d), both)
+        assert torch.equal(ev.areas, _areas(both, gts, C))
+    finally:
+        segclip_amd.set_compute_dtype(torch.float32)
+
+
+def test_eval_epoch_and_interface_errors():
+    g = load_golden("seg_tiny.npz")
+    try:
+        model = _tiny_model()
+        tokens = torch.from_numpy(g["prompt_ids"])
+        emb = torch.from_numpy(g["text_embedding"]).to(DEV)
+        d = Despeckle(6, fill=0)
+        batches = []
+        for k in range(2):
+            raws, gts = _raws(40 + k)
+            batches.append(([t.cpu() for t in raws[:2 + k]], [t.cpu() for t in gts[:2 + k]]))
+        cfg = dict(bg_thresh=0.02, reduce_zero_label=True, **SLIDE)
+        got = eval_epoch(None, model, DEV, 1, batches, tokens, True, dict(clean=d, **cfg), transform=TF)
+        seg = SegInference(model, emb, True, bg_thresh=0.02, **SLIDE)
+        ev = SegEvaluator(seg, reduce_zero_label=True)
+        areas = torch.zeros_like(ev.areas)
+        for raws, gts in batches:
+            raws, gts = [t.to(DEV) for t in raws], [t.to(DEV) for t in gts]
+            ev.update_raw(raws, gts, TF, clean=d)
+            areas += _areas(despeckle(seg.predict_raw(raws, TF), 6), gts, seg.num_classes)
+        assert torch.equal(ev.areas, areas)
+        assert got == ev.compute()["mIoU"] * 100.0 and 0.0 <= got <= 100.0
+        plain = eval_epoch(None, model, DEV, 1, batches, tokens, True, dict(cfg), transform=TF)
+        assert plain == eval_epoch(None, model, DEV, 1, batches, tokens, True, dict(clean=None, **cfg), transform=TF)
+        with pytest.raises(ValueError, match="clean.*transform"):
+            eval_epoch(None, model, DEV, 1, batches, tokens, True, dict(clean=d, **cfg))
+
+        raws, gts = _raws(50)
+        ev = SegEvaluator(seg)
+        with pytest.raises(TypeError, match="Despeckle"):
+            seg.predict_raw(raws, TF, clean=6)
+        with pytest.raises(TypeError, match="Despeckle"):
+            ev.update_raw(raws, gts, TF, clean=(6, 0))
+        pre = [torch.zeros(3, 128, 128, device=DEV)]
+        with pytest.raises(ValueError, match="predict_list.*clean.*despeckle"):
+            seg.predict_list(pre, clean=d)
+        with pytest.raises(ValueError, match="update.*clean.*despeckle"):
+            ev.update(pre, [gts[0]], clean=d)
+        with pytest.raises(ValueError, match="render_raw.*clean.*despeckle"):
+            seg.render_raw(raws, TF, ["pred"], torch.zeros(14, 3, dtype=torch.uint8), clean=d)
+        with pytest.raises(ValueError, match="SegSweepEvaluator.*clean"):
+            SegSweepEvaluator(seg, [0.1, 0.5]).update_raw(raws, gts, TF, clean=d)
+        assert int(ev.areas.sum()) == 0
+    finally:
+        segclip_amd.set_compute_dtype(torch.float32)

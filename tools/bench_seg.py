@@ -43,9 +43,18 @@ dilations (8, 16), in ONE command and alternating within every repeat:
         ratio, the share of pixels on which the two agree, peak allocation, the clock held, and the refinement kernels' own time
         from a separate `rocprofv3 --kernel-trace --stats` child (--refine-child: five update_raw(refine=) calls and nothing
         else) with the step kernel's bytes per second against its design traffic.
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine] [reps=7]
+With --objects instead: the label maps that update_raw forms for the same 64 decoded images, and their connected components
+(segmentation.components / despeckle, csrc/segment_objects.inc), in ONE command and alternating within every repeat:
+  (ix)  segclip_seg_components with every output (ids, area_px, records, count, cleaned) without a host copy, components() with
+        its one host synchronisation, despeckle alone, one SegEvaluator.update_raw (the yardstick: unchanged by the feature), one
+        update_raw(clean=Despeckle(16)), and the host route on the same maps: .cpu(), then scipy.ndimage.label per present class
+        (without scipy: the numpy restatement of the tests on 4 maps, scaled to 64); then one 500 x 500 map that is one component,
+        one 4-connected checkerboard (250 000 components) and one of 3-label noise, every output each: whether the atomics on one
+        root or the chains of the merge dominate; and the kernels' own times from a separate `rocprofv3 --kernel-trace --stats`
+        child (--objects-child: five calls with every output on the 64 maps and nothing else).
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects] [reps=7]
                                  [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt]"""
+                                  seg_refine.txt | seg_objects.txt]"""
 import os
 import statistics
 import sys
@@ -64,11 +73,12 @@ EVAL, RAW, RAW_CHILD = ("--eval" in sys.argv[1:]), ("--raw" in sys.argv[1:]), ("
 AUG, AUG_CHILD = ("--aug" in sys.argv[1:]), ("--aug-child" in sys.argv[1:])
 SWEEP, SWEEP_CHILD = ("--sweep" in sys.argv[1:]), ("--sweep-child" in sys.argv[1:])
 REFINE, REFINE_CHILD = ("--refine" in sys.argv[1:]), ("--refine-child" in sys.argv[1:])
+OBJECTS, OBJECTS_CHILD = ("--objects" in sys.argv[1:]), ("--objects-child" in sys.argv[1:])
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
-                                             "--refine", "--refine-child")]
+                                             "--refine", "--refine-child", "--objects", "--objects-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -682,6 +692,132 @@ def refine_child(model, text):
     torch.cuda.synchronize()
 
 
+class _AllOutputs:
+    """segclip_seg_components with every output on a list of label maps: buffers and table made once, call() enqueues only."""
+
+    def __init__(self, maps, connectivity=8, min_area=16):
+        from segclip_amd.segmentation import _flat_maps
+        self.flat, offs = _flat_maps(list(maps))
+        n = self.flat.numel()
+        self.table, self.n_blocks, self.side = ops.seg_components_table([tuple(m.shape) for m in maps], offs, "cuda")
+        self.ids, self.area = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
+        self.records = torch.empty(n, ops.SEG_CC_RECORD, dtype=torch.int64, device="cuda")   # room for one component per pixel
+        self.count = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.cleaned = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        self.kw = dict(connectivity=connectivity, min_area=min_area, max_side=self.side)
+
+    def call(self):
+        ops.seg_components(self.table, self.n_blocks, self.flat, ids=self.ids, area_px=self.area, records=self.records,
+                           count=self.count, cleaned=self.cleaned, **self.kw)
+
+
+def objects_maps(model, text, n_images=64):
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    raws, gts = raw_inputs(seg, n_images)
+    tf = ImageTransform()
+    with torch.no_grad():
+        maps = SegEvaluator(seg).update_raw(raws, gts, tf, return_labels=True)
+    return seg, tf, raws, gts, maps
+
+
+def objects_case(model, text, n_images=64):
+    from segclip_amd.segmentation import Despeckle, SegEvaluator, components, despeckle
+    from tools import rocprof_roofline as rr
+    name = f"(ix) objects {n_images} mixed sizes"
+    seg, tf, raws, gts, maps = objects_maps(model, text, n_images)
+    pixels = sum(int(m.numel()) for m in maps)
+    d = Despeckle(16)
+    full = _AllOutputs(maps)
+    plain, cleaned_ev = SegEvaluator(seg), SegEvaluator(seg)
+    try:
+        from scipy import ndimage
+        host_maps, scale, host_what = maps, 1.0, ".cpu() + scipy.ndimage.label per present class (8-structure)"
+        ones = [[1, 1, 1]] * 3
+
+        def host_one(a):
+            return sum(ndimage.label(a == v, structure=ones)[1] for v in set(a.reshape(-1).tolist()))
+    except ImportError:
+        from tests import cc_reference
+        host_maps, scale = maps[:4], n_images / 4
+        host_what = f".cpu() + the numpy restatement of the tests on 4 maps, scaled by {scale:g} (no scipy here)"
+
+        def host_one(a):
+            return len(cc_reference.components([a], 8)[2])
+
+    def host_way():
+        return sum(host_one(m.cpu().numpy()) for m in host_maps)
+
+    ways = [("seg_components, every output, no host copy", full.call, 4),
+            ("components() (ids + records, one host sync)", lambda: components(maps, max_objects=pixels), 4),
+            (f"despeckle(min_area={d.min_area})", lambda: despeckle(maps, d.min_area), 4),
+            ("update_raw", lambda: plain.update_raw(raws, gts, tf), 2),
+            (f"update_raw(clean=Despeckle({d.min_area}))", lambda: cleaned_ev.update_raw(raws, gts, tf, clean=d), 2),
+            (host_what, host_way, 1)]
+    with torch.no_grad():
+        n_obj = components(maps, max_objects=pixels).count
+        assert scale != 1.0 or n_obj == host_way(), "the host route counts other components"
+        changed = sum(int((a != b).sum()) for a, b in zip(despeckle(maps, d.min_area), maps)) / pixels
+        for _, fn, _ in ways[:-1]:
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for rep in range(REPS):
+            for k, (_, fn, inner) in enumerate(ways):
+                if k == len(ways) - 1 and rep >= 3:
+                    continue   # the host route: three repeats
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: {pixels} pixels in the label maps of update_raw, {n_obj} components under 8-connectivity; despeckling below "
+        f"{d.min_area} pixels changes {changed:.4%} of the labels")
+    meds = [statistics.median(t) * (scale if k == len(ways) - 1 else 1.0) for k, t in enumerate(ts)]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:60s} {med * 1e3:9.3f} ms (min {min(t) * 1e3:.3f}, max {max(t) * 1e3:.3f}; {len(t)} x {inner} calls)")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts[:-1])
+    say(f"{name}: clean= adds {(meds[4] - meds[3]) * 1e3:.3f} ms to update_raw ({meds[4] / meds[3]:.4f} x); host route / components() "
+        f"{meds[5] / meds[1]:.1f}; host route / every output {meds[5] / meds[0]:.1f}; every output: {pixels / meds[0] / 1e9:.2f} Gpixel/s; "
+        f"largest run-to-run spread {spread:.4f} of the median; clock {clk}")
+    # atomic contention: one root for every tile, one root per pixel, and noise
+    side = 500
+    g = torch.Generator().manual_seed(2)
+    yy, xx = torch.meshgrid(torch.arange(side), torch.arange(side), indexing="ij")
+    for what, m, conn in (("one component", torch.ones(side, side, dtype=torch.uint8), 8),
+                          ("checkerboard, 4-connectivity", ((yy + xx) % 2).to(torch.uint8), 4),
+                          ("3-label noise", torch.randint(0, 3, (side, side), generator=g).to(torch.uint8), 8)):
+        one = _AllOutputs([m.cuda()], connectivity=conn)
+        med, lo, hi = timed(one.call, 20)
+        say(f"{name}: {side} x {side} {what:30s} {int(one.count.item()):7d} components, every output {med * 1e6:9.1f} us "
+            f"(min {lo * 1e6:.1f}, max {hi * 1e6:.1f}; {REPS} x 20 calls)")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--objects-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    rows = [r for r in table if "seg_cc_" in r[0]]
+    if not rows:
+        say(f"{name}: the kernels alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+    for r in rows:
+        say(f"{name}: {r[0][r[0].find('seg_cc_'):][:36]:36s} alone (rocprofv3 --kernel-trace --stats, {r[1]} launches in 5 calls) {r[2] / 5:9.1f} us per call")
+    if rows:
+        say(f"{name}: all seg_cc kernels {sum(r[2] for r in rows) / 5:9.1f} us per call with every output")
+
+
+def objects_child(model, text):
+    """Five calls of segclip_seg_components with every output on the 64 label maps: what the rocprofv3 child of objects_case traces."""
+    full = _AllOutputs(objects_maps(model, text)[4])
+    for _ in range(5):
+        full.call()
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -702,7 +838,12 @@ if __name__ == "__main__":
     if REFINE_CHILD:
         refine_child(model, text)
         sys.exit(0)
-    if REFINE:
+    if OBJECTS_CHILD:
+        objects_child(model, text)
+        sys.exit(0)
+    if OBJECTS:
+        objects_case(model, text)
+    elif REFINE:
         refine_case(model, text)
     elif SWEEP:
         sweep_case(model, text)
