@@ -769,6 +769,60 @@ int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, i
                            uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Boundary metrics of label maps (segment_boundary.inc): the boundary bands of a prediction and a ground truth, and the
+ * per-class areas of Boundary IoU (Cheng et al., CVPR 2021) and of the trimap mIoU of the DeepLab papers, for maps of mixed
+ * sizes in one call.  THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated with the
+ * brute-force window by tests/boundary_reference.py.
+ *
+ * Per map M (h, w) uint8 and radius d >= 1, the BAND BYTE of the pixel p = (y, x):
+ *   bit 0: some pixel p' = (y', x') OF THE MAP with |y - y'| <= d and |x - x'| <= d has M[p'] != M[p]
+ *   bit 1: the (2d+1)^2 window around p leaves the map: y < d, x < d, y >= h - d or x >= w - d
+ *   band != 0 is, for every class k at once, the official mask_to_boundary(M == k, d) of Boundary IoU (one ring of zeros
+ *   around the mask, d erosions with a 3 x 3 kernel, the mask minus its erosion): that result equals (M == k) & (band != 0).
+ *   The radius of a map is the caller's; Boundary IoU takes d = max(1, round(0.02 * sqrt(h * h + w * w))).
+ * Areas: a (2, 3, C) int64 tensor that is ADDED to.  q = the prediction's byte, g = the ground truth's, bp and bg their band
+ *   bytes.  The bands are formed on the raw bytes: an ignored region is a region like any other.  The ground-truth rule is
+ *   segclip_seg_areas': a pixel with g == ignore_index contributes nothing; with reduce_zero_label a pixel with g == 0
+ *   contributes nothing either and every other g counts as g' = g - 1 (otherwise g' = g); a value >= C adds to the other
+ *   side's areas only.
+ *   areas[0] Boundary IoU: I[k] += [q = k, g' = k, bp != 0, bg != 0]   P[k] += [q = k, bp != 0]   L[k] += [g' = k, bg != 0]
+ *   areas[1] trimap      : the I / P / L of segclip_seg_areas over the pixels with bg & 1, those within d of a change of the
+ *                          ground truth's byte (the picture frame is no change)
+ *   With d >= max(h, w) every band byte is non-zero and areas[0] is segclip_seg_areas'; a ground truth of one single byte
+ *   leaves areas[1] as it was.
+ *
+ *   images   : (B, 8) int64 rows on the device: 0 h  1 w  2 offset of the map's h * w bytes in `pred` AND `pred_band`
+ *              3 its offset in `gt` AND `gt_band`, or -1 for a map without a ground truth (not looked at when gt is null)
+ *              4 its radius d  5 its first workgroup = the sum of ceil(ceil(h / 32) * ceil(w / 64) / 4) over the maps
+ *              before it  6-7 0
+ *   n_blocks : that sum over all maps (a wave owns a strip of 32 rows x 64 columns, a workgroup four consecutive strips of
+ *              a map);  max_side: the caller's bound on every h and w
+ *   pred, gt : flat uint8 of pred_bytes / gt_bytes, read only; gt optional.  They have offsets of their own because an
+ *              evaluator's label buffer has gaps between its maps and its ground truths lie gapless.
+ *   pred_band, gt_band : optional flat uint8 with the layout of pred / gt; gt_band needs gt
+ *   areas    : optional (2, 3, C) int64; needs gt.  1 <= C <= 256
+ *   ws       : segclip_seg_boundary_ws_bytes(pred_bytes, gt_bytes) bytes (2 per byte of pred and of gt), 16-byte aligned
+ *   The entry enqueues two kernels without a host synchronisation.  The first counts, per row, the changes of byte from its
+ *   left end to every pixel (uint16 in ws): the part [x - d, x + d] of a row is constant exactly when the counts at its two
+ *   ends agree.  The second walks down the columns: the window of p is constant exactly when every row of it has a constant
+ *   row part and the byte of p's column does not change over it; a lane remembers the last row of either kind, d rows ahead
+ *   of the pixel it emits.  Work per pixel is (32 + 2 d) / 32 row visits, never d^2.  The areas are counted in LDS and added
+ *   with one integer atomic per touched counter and workgroup: the sums depend on no schedule.
+ *   Every table row is range-checked on the device: a map with h or w outside [1, min(max_side, 2^15 - 1)], a radius outside
+ *   [1, 128], offsets inconsistent with pred_bytes / gt_bytes or workgroups beyond n_blocks is SKIPPED (nothing of it read,
+ *   written or counted).
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: C > 256, max_side outside [1, 2^15), a workspace smaller
+ *   than ws_bytes.
+ *   SEGCLIP_ERR_INVALID: areas or gt_band without gt, a band output overlapping an input or the other band, C < 1, missing
+ *   pointers.
+ * ------------------------------------------------------------------------------------------ */
+int64_t segclip_seg_boundary_ws_bytes(int64_t pred_bytes, int64_t gt_bytes);
+int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* pred,
+                         int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
+                         int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws, int64_t ws_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
  * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
  * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the

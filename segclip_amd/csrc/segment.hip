@@ -304,6 +304,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_render.inc"
 #include "segment_refine.inc"
 #include "segment_objects.inc"
+#include "segment_boundary.inc"
 #include "train_frontend.inc"
 
 }  // namespace
@@ -945,6 +946,77 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
     hipLaunchKernelGGL(seg_cc_final_kernel, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_components (final)");
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
+struct SegBdWs { int64_t pred_s, gt_s, total; };
+static SegBdWs seg_bd_ws(int64_t pred_bytes, int64_t gt_bytes) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegBdWs w;
+  w.pred_s = 0;
+  w.gt_s = up(pred_bytes * 2);
+  w.total = w.gt_s + up(gt_bytes * 2);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_boundary_ws_bytes(int64_t pred_bytes, int64_t gt_bytes) {
+  if (pred_bytes < 0 || pred_bytes > (1ll << 40) || gt_bytes < 0 || gt_bytes > (1ll << 40)) {
+    segclip_set_error("seg_boundary_ws_bytes: need 0 <= pred_bytes, gt_bytes <= 2^40");
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  return seg_bd_ws(pred_bytes, gt_bytes).total;
+}
+
+static bool seg_bd_overlap(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb) {
+  return a && b && na > 0 && nb > 0 && a < b + nb && b < a + na;
+}
+
+extern "C" int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* pred,
+                                    int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
+                                    int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && pred_bytes >= 0 && gt_bytes >= 0 && ws_bytes >= 0 && C >= 1,
+                  "seg_boundary: sizes must not be negative, and C >= 1");
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && pred_bytes <= (1ll << 40) && gt_bytes <= (1ll << 40),
+                  "seg_boundary: size out of range");
+  SEGCLIP_REQUIRE(!areas || gt, "seg_boundary: areas need gt");
+  SEGCLIP_REQUIRE(!gt_band || gt, "seg_boundary: gt_band needs gt");
+  SEGCLIP_REQUIRE(!seg_bd_overlap(pred_band, pred_bytes, pred, pred_bytes) && !seg_bd_overlap(pred_band, pred_bytes, gt, gt_bytes) &&
+                      !seg_bd_overlap(gt_band, gt_bytes, pred, pred_bytes) && !seg_bd_overlap(gt_band, gt_bytes, gt, gt_bytes) &&
+                      !seg_bd_overlap(pred_band, pred_bytes, gt_band, gt_bytes),
+                  "seg_boundary: a band output overlaps an input or the other band");
+  if (C > SEG_MAX_CLASSES) {
+    segclip_set_error("seg_boundary: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_side < 1 || max_side >= SEG_BD_LIMIT) {
+    segclip_set_error("seg_boundary: sides of 1..%d pixels supported, got a bound of %lld", SEG_BD_LIMIT - 1, (long long)max_side);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  const SegBdWs w = seg_bd_ws(pred_bytes, gt_bytes);
+  if (ws_bytes < w.total) {
+    segclip_set_error("seg_boundary: the workspace has %lld bytes, segclip_seg_boundary_ws_bytes asks for %lld", (long long)ws_bytes,
+                      (long long)w.total);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(images && pred, "seg_boundary: images and pred are required");
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_boundary: the workspace is required, 16-byte aligned");
+  if (!pred_band && !gt_band && !areas) return 0;  // nothing asked for
+
+  SegBdArgs a;
+  a.images = images; a.pred = pred; a.gt = gt; a.pred_bytes = pred_bytes; a.gt_bytes = gt ? gt_bytes : 0; a.n_blocks = n_blocks;
+  a.B = (int)B; a.max_side = (int)max_side; a.C = (int)C; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.pred_band = pred_band; a.gt_band = gt_band; a.areas = reinterpret_cast<unsigned long long*>(areas);
+  char* base = static_cast<char*>(ws);
+  a.pred_s = reinterpret_cast<uint16_t*>(base + w.pred_s);
+  a.gt_s = reinterpret_cast<uint16_t*>(base + w.gt_s);
+  const dim3 grid((unsigned)n_blocks), block(256);
+  hipLaunchKernelGGL(seg_bd_rows_kernel, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_boundary (rows)");
+  hipLaunchKernelGGL(seg_bd_band_kernel, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_boundary (bands)");
   return 0;
 }
 

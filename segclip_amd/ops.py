@@ -2910,6 +2910,81 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
         cleaned.numel() if cleaned is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_components")
 
 
+# ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
+SEG_BOUNDARY_TILE = (32, 64)     # (rows, columns) of one wave's strip of segclip_seg_boundary; 64 is also its rows pass's chunk
+SEG_BOUNDARY_WAVES = 4           # consecutive strips of a map that share a workgroup
+SEG_BOUNDARY_COLS = 8            # int64 columns of one row of its image table
+SEG_BOUNDARY_MAX_RADIUS = 128
+
+
+def seg_boundary_table(sizes, pred_offsets, gt_offsets, radii, device):
+    """The device image table of seg_boundary: sizes [(h, w)], pred_offsets [offset of each map's h * w bytes in the flat
+    prediction buffer and in pred_band], gt_offsets [the same for the ground truths and gt_band; None: no map has one, a single
+    None or -1: that map has none], radii [d of each map] -> (table (B, 8) int64, n_blocks, largest side)."""
+    n = len(sizes)
+    if n == 0:
+        raise ValueError("seg_boundary: sizes is empty")
+    if gt_offsets is None:
+        gt_offsets = [-1] * n
+    for name, v in (("pred_offsets", pred_offsets), ("gt_offsets", gt_offsets), ("radii", radii)):
+        if len(v) != n:
+            raise ValueError(f"seg_boundary: {n} sizes but {name} has {len(v)} entries")
+    sh, tw = SEG_BOUNDARY_TILE
+    tab, blk, side = [], 0, 0
+    for i, ((h, w), po, go, d) in enumerate(zip(sizes, pred_offsets, gt_offsets, radii)):
+        h, w, d = int(h), int(w), int(d)
+        go = -1 if go is None else int(go)
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_boundary: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, map {i} is {h}x{w}")
+        if not 1 <= d <= SEG_BOUNDARY_MAX_RADIUS:
+            raise ValueError(f"seg_boundary: radii 1 .. {SEG_BOUNDARY_MAX_RADIUS} supported, map {i} ({h}x{w}) has radius {d}")
+        if int(po) < 0:
+            raise ValueError(f"seg_boundary: pred_offsets are not negative, map {i} has {po}")
+        if go < -1:
+            raise ValueError(f"seg_boundary: gt_offsets are not negative (-1 or None: no ground truth), map {i} has {go}")
+        tab.append([h, w, int(po), go, d, blk, 0, 0])
+        strips = ((h + sh - 1) // sh) * ((w + tw - 1) // tw)
+        blk += (strips + SEG_BOUNDARY_WAVES - 1) // SEG_BOUNDARY_WAVES
+        side = max(side, h, w)
+    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_BOUNDARY_COLS), blk, side
+
+
+def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255, reduce_zero_label=False, pred_band=None,
+                 gt_band=None, areas=None, max_side=None):
+    """Boundary bands and boundary areas of the flat uint8 `pred` (and `gt`) under the table of seg_boundary_table
+    (segclip_seg_boundary; the definition stands in include/segclip_hip.h).  Every output is optional and written where given:
+    pred_band / gt_band flat uint8 of pred's / gt's size (bit 0: a label change within the radius, bit 1: the window leaves the
+    map), areas (2, 3, C) int64 that is ADDED to (slot 0 Boundary IoU, slot 1 trimap; needs gt).  max_side: the largest h or w
+    of the table (defaults to the limit).  No host synchronisation.  -> None."""
+    L.require_cuda(table, pred, gt, pred_band, gt_band, areas)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_BOUNDARY_COLS or not table.is_contiguous():
+        raise ValueError("seg_boundary: table is the (B, 8) int64 tensor of seg_boundary_table")
+    for name, t in (("pred", pred), ("gt", gt), ("pred_band", pred_band), ("gt_band", gt_band)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+            raise ValueError(f"seg_boundary: {name} is a contiguous uint8 tensor")
+    if pred_band is not None and pred_band.numel() != pred.numel():
+        raise ValueError(f"seg_boundary: pred_band has the layout of pred: {pred.numel()} bytes, got {pred_band.numel()}")
+    if gt is None and (gt_band is not None or areas is not None):
+        raise ValueError("seg_boundary: gt_band and areas need gt")
+    if gt_band is not None and gt_band.numel() != gt.numel():
+        raise ValueError(f"seg_boundary: gt_band has the layout of gt: {gt.numel()} bytes, got {gt_band.numel()}")
+    num_classes = int(num_classes)
+    if num_classes < 1:
+        raise ValueError(f"seg_boundary: num_classes is positive, got {num_classes}")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (2, 3, num_classes)):
+        raise ValueError(f"seg_boundary: areas is a contiguous (2, 3, {num_classes}) int64 tensor")
+    lib = L.load()
+    gt_bytes = gt.numel() if gt is not None else 0
+    ws_bytes = lib.segclip_seg_boundary_ws_bytes(pred.numel(), gt_bytes)
+    if ws_bytes < 0:
+        L.check(ws_bytes, "seg_boundary")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=pred.device)
+    L.check(lib.segclip_seg_boundary(
+        L.ptr(table), table.shape[0], int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(pred),
+        pred.numel(), L.ptr(gt), gt_bytes, num_classes, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(pred_band),
+        L.ptr(gt_band), L.ptr(areas), L.ptr(ws), ws_bytes, L.stream()), "seg_boundary")
+
+
 # ---------------------------------------------------------------- image-text retrieval evaluation (retrieval.hip)
 RETRIEVAL_BAD_INDEX = 1  # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
 

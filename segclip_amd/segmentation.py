@@ -47,6 +47,13 @@ and returns them with a compact list of boxes, areas and coordinate sums; despec
 minimum area by a fill label, and predict_raw / update_raw / eval_epoch take clean=, applied after refine=.  Not covered: the
 threshold sweep, render_raw, predict_list and update (apply despeckle to their maps).
 
+Boundary metrics (not in the reference): mIoU counts every pixel alike and hardly sees the borders that refine= and clean=
+exist to improve.  Boundary states the band radius of Boundary IoU (Cheng et al., CVPR 2021), boundary_bands returns the
+band bytes of label maps, boundary_areas the (2, 3, C) areas of Boundary IoU and of the trimap mIoU of the DeepLab papers,
+and SegEvaluator(boundary=) scores the labels of every update path against the ground truths with one more call
+(csrc/segment_boundary.inc), without a host synchronisation; compute() adds bIoU, mbIoU, trimap_IoU, trimap_mIoU and
+trimap_aAcc.  Not covered: SegSweepEvaluator and render_raw.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -500,6 +507,93 @@ def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None):
     than min_area pixels replaced by `fill` (see Despeckle), all maps in one call and without a host synchronisation.  The
     inputs stay as they are."""
     return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label))[0]
+
+
+class Boundary:
+    """The band of the boundary metrics: the pixels of a map within `radius` pixels (Chebyshev distance) of a pixel with another
+    label or of the picture frame.  ratio: the radius as a share of the map's diagonal, d = max(1, round(ratio * sqrt(h^2 +
+    w^2))) - 0.02 is the default of Boundary IoU (Cheng et al., CVPR 2021); radius: a fixed radius in pixels that overrides
+    the ratio (the trimap widths of the DeepLab papers).  csrc/segment_boundary.inc; the definition stands in
+    include/segclip_hip.h.  The reference has no such measure."""
+
+    def __init__(self, ratio=0.02, radius=None):
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not math.isfinite(ratio) or not ratio > 0:
+            raise ValueError(f"Boundary: ratio is a positive number, got {ratio!r}")
+        if radius is not None and (isinstance(radius, bool) or not isinstance(radius, int) or
+                                   not 1 <= radius <= ops.SEG_BOUNDARY_MAX_RADIUS):
+            raise ValueError(f"Boundary: radius is None or an integer in 1 .. {ops.SEG_BOUNDARY_MAX_RADIUS}, got {radius!r}")
+        self.ratio, self.radius = float(ratio), radius
+
+    def radius_of(self, h, w, image=None):
+        """The radius of an (h, w) map; one above the kernel's limit raises, naming the image."""
+        if self.radius is not None:
+            return self.radius
+        d = max(1, int(round(self.ratio * math.sqrt(h * h + w * w))))
+        if d > ops.SEG_BOUNDARY_MAX_RADIUS:
+            name = "a map" if image is None else f"image {image}"
+            raise ValueError(f"Boundary: {name} of {h}x{w} has the radius {d} at ratio {self.ratio}, at most "
+                             f"{ops.SEG_BOUNDARY_MAX_RADIUS} supported (pass a fixed radius)")
+        return d
+
+
+def _check_boundary(boundary):
+    if not isinstance(boundary, Boundary):
+        raise TypeError("boundary is a Boundary")
+
+
+def _boundary_call(maps, boundary, gts=None, flat=None, **kw):
+    """ops.seg_boundary over a list of maps (flat: their (buffer, offsets) where _flat_maps has laid them out already) and
+    their ground truths, which lie gapless one after the other as _flat_gts lays them."""
+    flat, offs = _flat_maps(maps) if flat is None else flat
+    sizes = [tuple(m.shape) for m in maps]
+    radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(sizes)]
+    gt_offs = None
+    if gts is not None:
+        gt_offs, n = [], 0
+        for g, hw in zip(gts, sizes):
+            if tuple(g.shape) != hw:
+                raise ValueError(f"boundary: a ground truth has its label map's size {hw}, got {tuple(g.shape)}")
+            gt_offs.append(n)
+            n += g.numel()
+    table, n_blocks, side = ops.seg_boundary_table(sizes, offs, gt_offs, radii, flat.device)
+    ops.seg_boundary(table, n_blocks, flat, gt=_flat_gts(gts), max_side=side, **kw)
+
+
+@torch.no_grad()
+def boundary_bands(maps, boundary):
+    """maps [(h_i, w_i) uint8 label maps of any mix of sizes] -> [(h_i, w_i) uint8 band maps], views of one new buffer: bit 0
+    where a pixel within the radius (boundary.radius_of(h_i, w_i), Chebyshev distance, inside the map) carries another byte,
+    bit 1 where the (2d+1)^2 window leaves the map.  (map == k) & (band != 0) is Boundary IoU's mask_to_boundary of class k.
+    All maps in one call and without a host synchronisation; the inputs stay as they are."""
+    _check_boundary(boundary)
+    maps = list(maps)
+    _check_label_maps(maps)
+    flat, offs = _flat_maps(maps)
+    band = torch.empty_like(flat)
+    if band.numel() != sum(m.numel() for m in maps):
+        band.zero_()  # the bytes between the maps
+    _boundary_call(maps, boundary, flat=(flat, offs), pred_band=band)
+    return _split_maps(band, offs, [tuple(m.shape) for m in maps])
+
+
+@torch.no_grad()
+def boundary_areas(preds, gts, num_classes, boundary, ignore_index=255, reduce_zero_label=False, areas=None):
+    """preds, gts [(h_i, w_i) uint8] -> (2, 3, C) int64 on the device, added to `areas` when given: slot 0 the intersection,
+    prediction area and label area of Boundary IoU (each side restricted to its own band), slot 1 those of the trimap (the
+    pixels within the radius of a change of the ground truth's byte).  The ground-truth rule (ignore_index,
+    reduce_zero_label, values >= C) is ops.seg_areas'.  SegEvaluator.boundary_metrics_from_areas turns a host copy into
+    figures.  One call, no host synchronisation."""
+    _check_boundary(boundary)
+    preds, gts = list(preds), list(gts)
+    _check_label_maps(preds)
+    if len(preds) != len(gts):
+        raise ValueError(f"{len(preds)} predictions but {len(gts)} ground truths")
+    SegEvaluator._check_gts(preds, gts)
+    if areas is None:
+        areas = torch.zeros(2, 3, int(num_classes), dtype=torch.int64, device=preds[0].device)
+    _boundary_call(preds, boundary, gts=gts, num_classes=num_classes, ignore_index=ignore_index,
+                   reduce_zero_label=reduce_zero_label, areas=areas)
+    return areas
 
 
 def _out_shapes(src, out_shapes):
@@ -959,14 +1053,31 @@ class SegEvaluator:
     """mmseg's mIoU evaluation on the device.  update() adds every image's per-class intersection, prediction area and label
     area (intersect_and_union with ignore_index / reduce_zero_label) to `areas`, a (3, C) int64 device tensor, inside the
     label-map launch and without a host synchronisation; compute() copies it to the host once.  Several ranks: all_reduce
-    `areas` (sum) before compute()."""
+    `areas` (sum) before compute().
+    boundary (a Boundary): every update path also scores the labels whose areas it counts - the refined or cleaned ones -
+    against the ground truths with one more call (segclip_seg_boundary) that adds to `boundary_areas`, a (2, 3, C) int64
+    device tensor (slot 0 Boundary IoU, slot 1 trimap); the labels are then formed even when return_labels is False, and
+    compute() adds bIoU, mbIoU, trimap_IoU, trimap_mIoU and trimap_aAcc from the same host copy.  Several ranks: all_reduce
+    `boundary_areas` like `areas`.  Without it nothing changes."""
 
-    def __init__(self, seg, ignore_index=255, reduce_zero_label=False):
+    def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None):
+        if boundary is not None:
+            _check_boundary(boundary)
         self.seg, self.ignore_index, self.reduce_zero_label = seg, int(ignore_index), bool(reduce_zero_label)
         self.areas = torch.zeros(3, seg.num_classes, dtype=torch.int64, device=seg.text_embedding.device)
+        self.boundary, self.boundary_areas = boundary, None
+        if boundary is not None:
+            self.boundary_areas = torch.zeros(2, 3, seg.num_classes, dtype=torch.int64, device=self.areas.device)
 
     def reset(self):
         self.areas.zero_()
+        if self.boundary_areas is not None:
+            self.boundary_areas.zero_()
+
+    def _score_boundary(self, labels, gts):
+        if self.boundary is not None:
+            _boundary_call(list(labels), self.boundary, gts=list(gts), num_classes=self.seg.num_classes,
+                           ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label, areas=self.boundary_areas)
 
     @torch.no_grad()
     def update(self, imgs, gts, return_labels=False, refine=None, clean=None):
@@ -1002,6 +1113,7 @@ class SegEvaluator:
                 flat = torch.cat([c.reshape(-1) for c in cleaned])
             ops.seg_areas(flat, _flat_gts(list(gts)), self.seg.num_classes, ignore_index=self.ignore_index,
                           reduce_zero_label=self.reduce_zero_label, areas=self.areas)
+            self._score_boundary(cleaned, gts)
             return cleaned if return_labels else None
         if refine is None:
             return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
@@ -1009,6 +1121,7 @@ class SegEvaluator:
         labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), None)
         refined = _refine_maps(raws, labels, self.seg.num_classes, transform, refine, gts=list(gts), areas=self.areas,
                                ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
+        self._score_boundary(refined, gts)
         return refined if return_labels else None
 
     @torch.no_grad()
@@ -1027,8 +1140,24 @@ class SegEvaluator:
                 raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
 
     def _forward(self, src, gts, return_labels):
-        return self.seg._forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas, ignore_index=self.ignore_index,
-                                 reduce_zero_label=self.reduce_zero_label, want_labels=return_labels)
+        labels = self.seg._forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
+                                   ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
+                                   want_labels=return_labels or self.boundary is not None)
+        self._score_boundary(labels, gts)
+        return labels if return_labels else None
+
+    @staticmethod
+    def boundary_metrics_from_areas(areas):
+        """(2, 3, C) integer CPU tensor (boundary_areas) -> dict(bIoU, mbIoU, trimap_IoU, trimap_mIoU, trimap_aAcc), each slot
+        as metrics_from_areas treats `areas`: IoU = I / (P + L - I) per class, a class absent from both sides of a slot is NaN
+        and left out of its mean, trimap_aAcc = sum(I) / sum(L) of the trimap."""
+        if areas.dim() != 3 or tuple(areas.shape[:2]) != (2, 3):
+            raise ValueError(f"areas is a (2, 3, C) tensor, got {tuple(areas.shape)}")
+        a = areas.to(torch.float64)
+        biou = a[0, 0] / (a[0, 1] + a[0, 2] - a[0, 0])
+        tiou = a[1, 0] / (a[1, 1] + a[1, 2] - a[1, 0])
+        return dict(bIoU=biou, mbIoU=float(torch.nanmean(biou)), trimap_IoU=tiou, trimap_mIoU=float(torch.nanmean(tiou)),
+                    trimap_aAcc=float(a[1, 0].sum() / a[1, 2].sum()))
 
     @staticmethod
     def metrics_from_areas(areas):
@@ -1041,7 +1170,12 @@ class SegEvaluator:
                     IoU=iou, Acc=acc)
 
     def compute(self):
-        return self.metrics_from_areas(self.areas.cpu())
+        if self.boundary is None:
+            return self.metrics_from_areas(self.areas.cpu())
+        both = torch.cat([self.areas.unsqueeze(0), self.boundary_areas]).cpu()  # the one host copy
+        out = self.metrics_from_areas(both[0])
+        out.update(self.boundary_metrics_from_areas(both[1:]))
+        return out
 
 
 def check_thresholds(thresholds):

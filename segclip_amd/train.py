@@ -292,7 +292,10 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     label maps are refined against the decoded pictures before they are scored, SegEvaluator.update_raw(refine=).
     test_cfg["clean"] (a segmentation.Despeckle; needs transform): connected components of the label maps below its minimum
     area are replaced by its fill label before the maps are scored, after the refinement if both are given,
-    SegEvaluator.update_raw(clean=)."""
+    SegEvaluator.update_raw(clean=).  test_cfg["boundary"] (a segmentation.Boundary): the labels are also scored on their
+    boundary bands, SegEvaluator(boundary=), and the function returns a dict instead of the number: mIoU, mbIoU, trimap_mIoU
+    and trimap_aAcc in percent and the per-class bIoU and trimap_IoU tensors in percent; boundary_areas stays this rank's like
+    areas."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
@@ -305,20 +308,29 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     clean = cfg.pop("clean", None)
     if clean is not None and transform is None:
         raise ValueError("eval_epoch: test_cfg['clean'] is applied by SegEvaluator.update_raw: pass a transform")
+    boundary = cfg.pop("boundary", None)
     model = _unwrap(model)
     model.eval()
     emb = build_text_embedding(model, text_tokens.to(device))
-    evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label)
+    evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label, boundary=boundary)
     for imgs, gts in batches:
         imgs, gts = [t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts]
         if transform is None:
             evaluator.update(imgs, gts)
         else:
             evaluator.update_raw(imgs, gts, transform, aug=aug, refine=refine, clean=clean)
-    miou = evaluator.compute()["mIoU"] * 100.0
+    metrics = evaluator.compute()
+    miou = metrics["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)
-    return miou
+    if boundary is None:
+        return miou
+    out = {"mIoU": miou}
+    for key in ("bIoU", "mbIoU", "trimap_IoU", "trimap_mIoU", "trimap_aAcc"):
+        out[key] = metrics[key] * 100.0
+    if getattr(args, "local_rank", 0) == 0:
+        logger.info("Boundary IoU: %.2f, trimap mIoU: %.2f, trimap aAcc: %.2f", out["mbIoU"], out["trimap_mIoU"], out["trimap_aAcc"])
+    return out
 
 
 def sweep_bg_thresh(args, model, device, n_gpu, batches, text_tokens, thresholds, test_cfg=None, transform=None):

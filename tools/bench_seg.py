@@ -52,9 +52,17 @@ With --objects instead: the label maps that update_raw forms for the same 64 dec
         one 4-connected checkerboard (250 000 components) and one of 3-label noise, every output each: whether the atomics on one
         root or the chains of the merge dominate; and the kernels' own times from a separate `rocprofv3 --kernel-trace --stats`
         child (--objects-child: five calls with every output on the 64 maps and nothing else).
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects] [reps=7]
+With --boundary instead: the boundary metrics (SegEvaluator(boundary=), csrc/segment_boundary.inc) on the inputs of --raw, in
+ONE command and alternating within every repeat:
+  (x)   one SegEvaluator.update_raw (the yardstick: the code path without the feature), one update_raw of an evaluator with
+        boundary=Boundary(), segclip_seg_boundary alone on update_raw's label maps (areas only, and with both bands written),
+        and the host route on the same maps: .cpu(), then scipy.ndimage.binary_erosion per present class of prediction and
+        ground truth, then counting (without scipy: unmeasured); peak allocation, the clock held, the run-to-run spread, and the
+        kernels' own times from a separate `rocprofv3 --kernel-trace --stats` child (--boundary-child: five calls with every
+        output on the 64 maps and nothing else).
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary] [reps=7]
                                  [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt | seg_objects.txt]"""
+                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt]"""
 import os
 import statistics
 import sys
@@ -74,11 +82,13 @@ AUG, AUG_CHILD = ("--aug" in sys.argv[1:]), ("--aug-child" in sys.argv[1:])
 SWEEP, SWEEP_CHILD = ("--sweep" in sys.argv[1:]), ("--sweep-child" in sys.argv[1:])
 REFINE, REFINE_CHILD = ("--refine" in sys.argv[1:]), ("--refine-child" in sys.argv[1:])
 OBJECTS, OBJECTS_CHILD = ("--objects" in sys.argv[1:]), ("--objects-child" in sys.argv[1:])
+BOUNDARY, BOUNDARY_CHILD = ("--boundary" in sys.argv[1:]), ("--boundary-child" in sys.argv[1:])
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
-                                             "--refine", "--refine-child", "--objects", "--objects-child")]
+                                             "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
+                                             "--boundary-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -818,6 +828,129 @@ def objects_child(model, text):
     torch.cuda.synchronize()
 
 
+class _BoundaryCall:
+    """segclip_seg_boundary on a list of label maps and ground truths, the outputs allocated once."""
+
+    def __init__(self, maps, gts, C, boundary, bands):
+        from segclip_amd.segmentation import _flat_gts, _flat_maps
+        self.flat, offs = _flat_maps(list(maps))
+        self.gt = _flat_gts(list(gts))
+        sizes = [tuple(m.shape) for m in maps]
+        gt_offs, n = [], 0
+        for g in gts:
+            gt_offs.append(n)
+            n += g.numel()
+        self.radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(sizes)]
+        self.table, self.n_blocks, self.side = ops.seg_boundary_table(sizes, offs, gt_offs, self.radii, "cuda")
+        self.areas = torch.zeros(2, 3, C, dtype=torch.int64, device="cuda")
+        self.pred_band = torch.zeros_like(self.flat) if bands else None
+        self.gt_band = torch.zeros_like(self.gt) if bands else None
+        self.C = C
+
+    def call(self):
+        ops.seg_boundary(self.table, self.n_blocks, self.flat, gt=self.gt, num_classes=self.C, pred_band=self.pred_band,
+                         gt_band=self.gt_band, areas=self.areas, max_side=self.side)
+
+
+def boundary_case(model, text, n_images=64):
+    from segclip_amd.segmentation import Boundary, SegEvaluator
+    from tools import rocprof_roofline as rr
+    name = f"(x) boundary {n_images} mixed sizes"
+    seg, tf, raws, gts, maps = objects_maps(model, text, n_images)
+    pixels = sum(int(m.numel()) for m in maps)
+    C, b = seg.num_classes, Boundary()
+    plain, with_b = SegEvaluator(seg), SegEvaluator(seg, boundary=b)
+    alone, banded = _BoundaryCall(maps, gts, C, b, False), _BoundaryCall(maps, gts, C, b, True)
+    HOST = min(8, n_images)   # the host route takes seconds per map: the first 8 maps, scaled to all
+    try:
+        from scipy import ndimage
+        ones = [[True] * 3] * 3
+
+        def host_one(p, g, d):
+            out = torch.zeros(2, 3, C, dtype=torch.int64)
+            bp, bg = torch.zeros(p.shape, dtype=torch.bool), torch.zeros(p.shape, dtype=torch.bool)
+            for m, band in ((p, bp), (g, bg)):
+                for v in set(m.reshape(-1).tolist()):
+                    mask = m == v
+                    band |= torch.from_numpy(mask & ~ndimage.binary_erosion(mask, ones, iterations=d, border_value=0))
+            keep = torch.from_numpy(g != 255)
+            p, g = torch.from_numpy(p).long(), torch.from_numpy(g).long()
+            # slot 0 alone: the trimap would need the frame taken off the eroded band
+            out[0, 0] = torch.bincount(p[keep & bp & bg & (p == g)], minlength=256)[:C]
+            out[0, 1] = torch.bincount(p[keep & bp], minlength=256)[:C]
+            out[0, 2] = torch.bincount(g[keep & bg & (g < C)], minlength=256)[:C]
+            return out
+
+        def host_way():
+            return sum(host_one(m.cpu().numpy(), g.cpu().numpy(), d) for m, g, d in zip(maps[:HOST], gts[:HOST], alone.radii))
+    except ImportError:
+        host_way = None
+
+    ways = [("update_raw", lambda: plain.update_raw(raws, gts, tf), 2),
+            ("update_raw of SegEvaluator(boundary=Boundary())", lambda: with_b.update_raw(raws, gts, tf), 2),
+            ("seg_boundary alone, areas only", alone.call, 4),
+            ("seg_boundary alone, areas and both bands", banded.call, 4)]
+    if host_way is not None:
+        ways.append((f".cpu() + scipy binary_erosion per present class + counting (slot 0), {HOST} maps scaled to {n_images}", host_way, 1))
+    with torch.no_grad():
+        if host_way is not None:
+            first = _BoundaryCall(maps[:HOST], gts[:HOST], C, b, False)
+            first.call()
+            assert torch.equal(first.areas[0].cpu(), host_way()[0]), "the host route counts other areas"
+        for _, fn, _ in ways[:4]:
+            fn()
+        torch.cuda.synchronize()
+        peaks = [peak_of(fn) for _, fn, _ in ways[:2]]
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for rep in range(REPS):
+            for k, (_, fn, inner) in enumerate(ways):
+                if k == 4 and rep >= 2:
+                    continue   # the host route: two repeats
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: {pixels} pixels in the label maps of update_raw, radii {min(alone.radii)} .. {max(alone.radii)} at ratio {b.ratio}; "
+        f"ground truths of per-pixel noise: every pixel lies in the band")
+    meds = [statistics.median(t) * (n_images / HOST if k == 4 else 1.0) for k, t in enumerate(ts)]
+    for k, ((what, _, inner), t, med) in enumerate(zip(ways, ts, meds)):
+        f = n_images / HOST if k == 4 else 1.0
+        say(f"{name}: {what:96s} {med * 1e3:9.3f} ms (min {min(t) * f * 1e3:.3f}, max {max(t) * f * 1e3:.3f}; {len(t)} x {inner} calls)")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts[:4])
+    host = f"host route / seg_boundary alone {meds[4] / meds[2]:.1f}" if host_way is not None else "host route: **Unmeasured** (no scipy here)"
+    say(f"{name}: boundary= adds {(meds[1] - meds[0]) * 1e3:.3f} ms to update_raw ({meds[1] / meds[0]:.4f} x); {host}; areas only: "
+        f"{pixels / meds[2] / 1e9:.2f} Gpixel/s; peak allocation {peaks[0] / 2**20:.1f} MiB without, {peaks[1] / 2**20:.1f} MiB with boundary=; "
+        f"largest run-to-run spread {spread:.4f} of the median; clock {clk}")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--boundary-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    rows = [r for r in table if "seg_bd_" in r[0]]
+    if not rows:
+        say(f"{name}: the kernels alone: **Unmeasured** (rocprofv3 child rc={rc}: {err[-200:]})")
+    for r in rows:
+        say(f"{name}: {r[0][r[0].find('seg_bd_'):][:36]:36s} alone (rocprofv3 --kernel-trace --stats, {r[1]} launches in 5 calls) {r[2] / 5:9.1f} us per call")
+    if rows:
+        say(f"{name}: all seg_bd kernels {sum(r[2] for r in rows) / 5:9.1f} us per call with every output")
+
+
+def boundary_child(model, text):
+    """Five calls of segclip_seg_boundary with every output on the 64 label maps: what the rocprofv3 child of boundary_case traces."""
+    from segclip_amd.segmentation import Boundary
+    seg, _, _, gts, maps = objects_maps(model, text)
+    full = _BoundaryCall(maps, gts, seg.num_classes, Boundary(), True)
+    for _ in range(5):
+        full.call()
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -841,7 +974,12 @@ if __name__ == "__main__":
     if OBJECTS_CHILD:
         objects_child(model, text)
         sys.exit(0)
-    if OBJECTS:
+    if BOUNDARY_CHILD:
+        boundary_child(model, text)
+        sys.exit(0)
+    if BOUNDARY:
+        boundary_case(model, text)
+    elif OBJECTS:
         objects_case(model, text)
     elif REFINE:
         refine_case(model, text)
