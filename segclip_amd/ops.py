@@ -2435,16 +2435,38 @@ def seg_image_table(rows, device):
     return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_IMAGE_COLS), offs, lab, blk, most
 
 
-def _seg_check_outputs(what, labels, gt, areas, n_classes):
-    """`labels` / `gt` / `areas` of the two fused label-map kernels."""
+def _seg_fused_args(what, soft_attn, tables, windows, images, views=None):
+    """The common inputs of the fused label-map kernels: flat soft_attn, the outputs of seg_group_table, the window list, the
+    image table and, for the view kernels, the view table (they do not read best_class).
+    -> (the tensors, contiguous, in the kernels' argument order; (nW, G, N))."""
+    table, tmax, bcls, bsc = tables
+    ints, tabs = ((bcls,), (images,)) if views is None else ((), (images, views))
+    L.require_cuda(soft_attn, table, tmax, *ints, bsc, windows, *tabs)
+    nW, G, N = table.shape
+    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
+            or any(t.dtype != torch.int32 for t in ints) or any(t.dtype != torch.int64 for t in tabs):
+        raise TypeError(f"{what}: fp32 soft_attn / tables, int32 window list, int64 image "
+                        f"{'table' if views is None else 'and view tables'}")
+    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
+            or any(t.numel() != nW * G for t in ints + (bsc,)) or (views is not None and (views.dim() != 2 or views.shape[1] != 2)):
+        raise ValueError(f"{what}: shapes do not agree")
+    return tuple(t.contiguous() for t in (soft_attn, table, tmax, *ints, bsc, windows, *tabs)), (nW, G, N)
+
+
+def _seg_check_outputs(what, labels, gt, areas, n_classes, T=None):
+    """`labels` / `gt` / `areas` of the fused label-map kernels and of seg_refine; T: the sweep's leading dimension of
+    `labels` and `areas`, one plane per threshold."""
     L.require_cuda(labels, gt, areas)
     for name, t in (("labels", labels), ("gt", gt)):
         if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
             raise ValueError(f"{what}: {name} is a contiguous uint8 tensor")
+    if T is not None and labels is not None and (labels.dim() != 2 or labels.shape[0] != T):
+        raise ValueError(f"{what}: labels is a (T, labels_bytes) uint8 tensor, one plane per threshold")
     if (gt is None) != (areas is None):
         raise ValueError(f"{what}: gt and areas go together")
-    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (3, n_classes)):
-        raise ValueError(f"{what}: areas is a contiguous (3, N + with_bg) int64 tensor")
+    lead, shape = ((), "(3, N + with_bg)") if T is None else ((T,), "(T, 3, N + 1)")
+    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != lead + (3, n_classes)):
+        raise ValueError(f"{what}: areas is a contiguous {shape} int64 tensor")
 
 
 def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_image_windows, with_bg, bg_thresh, labels=None,
@@ -2452,17 +2474,8 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     """The fused evaluation kernel (segclip_seg_label_map_rescaled): flat soft_attn + the outputs of seg_group_table + the
     window list + the image table -> `labels` (flat uint8, or None) at every image's output size and, with `gt` (flat uint8),
     the (3, C) int64 `areas` added to in place."""
-    table, tmax, bcls, bsc = tables
-    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images)
-    nW, G, N = table.shape
-    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
-            or images.dtype != torch.int64 or bcls.dtype != torch.int32:
-        raise TypeError("seg_label_map_rescaled: fp32 soft_attn / tables, int32 window list, int64 image table")
-    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
-            or bcls.numel() != nW * G or bsc.numel() != nW * G:
-        raise ValueError("seg_label_map_rescaled: shapes do not agree")
+    keep, (nW, G, N) = _seg_fused_args("seg_label_map_rescaled", soft_attn, tables, windows, images)
     _seg_check_outputs("seg_label_map_rescaled", labels, gt, areas, N + int(bool(with_bg)))
-    keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, images))
     L.check(L.load().segclip_seg_label_map_rescaled(
         L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
         G, N, int(bool(with_bg)), float(bg_thresh), L.ptr(labels), labels.numel() if labels is not None else 0, L.ptr(gt),
@@ -2481,28 +2494,11 @@ def seg_label_map_sweep(soft_attn, tables, windows, images, n_blocks, max_image_
     uint8: plane t is the single call's output at thresholds[t], or None) and, with `gt`, the (T, 3, N + 1) int64 `areas` added
     to in place, slice t as the single call adds it.  The library checks the thresholds: a bad list is a RuntimeError, more than
     16 an L.Unsupported."""
-    table, tmax, bcls, bsc = tables
-    L.require_cuda(soft_attn, table, tmax, bcls, bsc, windows, images, labels, gt, areas)
-    nW, G, N = table.shape
-    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
-            or images.dtype != torch.int64 or bcls.dtype != torch.int32:
-        raise TypeError("seg_label_map_sweep: fp32 soft_attn / tables, int32 window list, int64 image table")
-    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
-            or bcls.numel() != nW * G or bsc.numel() != nW * G:
-        raise ValueError("seg_label_map_sweep: shapes do not agree")
+    keep, (nW, G, N) = _seg_fused_args("seg_label_map_sweep", soft_attn, tables, windows, images)
     thr = [float(v) for v in thresholds]
     T = len(thr)
-    for name, t in (("labels", labels), ("gt", gt)):
-        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
-            raise ValueError(f"seg_label_map_sweep: {name} is a contiguous uint8 tensor")
-    if labels is not None and (labels.dim() != 2 or labels.shape[0] != T):
-        raise ValueError("seg_label_map_sweep: labels is a (T, labels_bytes) uint8 tensor, one plane per threshold")
-    if (gt is None) != (areas is None):
-        raise ValueError("seg_label_map_sweep: gt and areas go together")
-    if areas is not None and (areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (T, 3, N + 1)):
-        raise ValueError("seg_label_map_sweep: areas is a contiguous (T, 3, N + 1) int64 tensor")
+    _seg_check_outputs("seg_label_map_sweep", labels, gt, areas, N + 1, T)
     host = (L.C.c_float * max(T, 1))(*thr)
-    keep = tuple(t.contiguous() for t in (soft_attn, table, tmax, bcls, bsc, windows, images))
     L.check(L.load().segclip_seg_label_map_rescaled_sweep(
         L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
         G, N, L.C.cast(host, L.C.c_void_p), T, L.ptr(labels), labels.shape[1] if labels is not None else 0, L.ptr(gt),
@@ -2552,25 +2548,12 @@ def seg_view_tables(rows, view_counts, device):
             torch.tensor(vtab, dtype=torch.int64, device=device).view(-1, 2), offs, lab, blk, most_img, most_view, max(view_counts))
 
 
-def _seg_views_args(what, soft_attn, tables, windows, images, views):
-    table, tmax, _, bsc = tables
-    L.require_cuda(soft_attn, table, tmax, bsc, windows, images, views)
-    nW, G, N = table.shape
-    if soft_attn.dtype != torch.float32 or table.dtype != torch.float32 or windows.dtype != torch.int32 \
-            or images.dtype != torch.int64 or views.dtype != torch.int64:
-        raise TypeError(f"{what}: fp32 soft_attn / tables, int32 window list, int64 image and view tables")
-    if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or views.dim() != 2 \
-            or views.shape[1] != 2 or tmax.numel() != nW or bsc.numel() != nW * G:
-        raise ValueError(f"{what}: shapes do not agree")
-    return tuple(t.contiguous() for t in (soft_attn, table, tmax, bsc, windows, images, views)), (nW, G, N)
-
-
 def seg_label_map_views(soft_attn, tables, windows, images, views, n_blocks, max_image_windows, max_view_windows, max_views, with_bg,
                         bg_thresh, labels=None, gt=None, areas=None, ignore_index=255, reduce_zero_label=False):
     """The fused multi-view kernel (segclip_seg_label_map_views): as seg_label_map_rescaled with the tables of
     seg_view_tables - per view the rescaled class logits at the mirrored position, their soft-max, the mean over an image's
     views, its first maximum -> `labels` (flat uint8, or None) and, with `gt`, the (3, C) int64 `areas` added to in place."""
-    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_views_args("seg_label_map_views", soft_attn, tables, windows, images, views)
+    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_fused_args("seg_label_map_views", soft_attn, tables, windows, images, views)
     _seg_check_outputs("seg_label_map_views", labels, gt, areas, N + int(bool(with_bg)))
     L.check(L.load().segclip_seg_label_map_views(
         L.ptr(soft), soft.numel(), L.ptr(table), L.ptr(tmax), L.ptr(bsc), L.ptr(win), L.ptr(img), img.shape[0], L.ptr(vws), nW,
@@ -2584,7 +2567,7 @@ def seg_view_probs(soft_attn, tables, windows, images, views, n_blocks, max_imag
                    bg_thresh, out_size, out=None):
     """The dense twin (segclip_seg_view_probs) for ONE image: (N + with_bg, oh, ow) fp32, the mean over its views of the
     soft-max of the rescaled class logits, by the device functions of seg_label_map_views (whose label is its first maximum)."""
-    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_views_args("seg_view_probs", soft_attn, tables, windows, images, views)
+    (soft, table, tmax, bsc, win, img, vws), (nW, G, N) = _seg_fused_args("seg_view_probs", soft_attn, tables, windows, images, views)
     if vws.shape[0] != 1:
         raise ValueError(f"seg_view_probs: one image per call, got a view table of {vws.shape[0]}")
     shape = (N + int(bool(with_bg)), int(out_size[0]), int(out_size[1]))
@@ -2620,29 +2603,61 @@ SEG_SOURCE_COLS = 6         # int64 columns of one row of the source table of se
 SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 
 
-def _seg_source_table(raws, net_sizes, flags=None):
-    """The source table of both front-end kernels: a row per source image, with a seventh column of flag words for the view
-    kernel."""
+def _seg_pictures(what, raws, noun="a source image"):
+    """The decoded pictures of a table builder, checked one by one: (h, w, 3) uint8 on one device, sides of 1 ..
+    SEG_SOURCE_LIMIT - 1, channels interleaved and pixels contiguous, rows possibly strided.  `what:` opens the messages, `noun`
+    names a picture in them.  Yields (address, h, w, row stride in bytes) per picture."""
+    L.require_cuda(*raws)
+    for t in raws:
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"{what}: {noun} is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if t.device != raws[0].device:
+            raise ValueError(f"{what}: the {noun.split(' ', 1)[1]}s are on different devices")
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"{what}: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
+            raise ValueError(f"{what}: {noun} has interleaved channels and contiguous pixels (strides (>= 3 w, 3, 1)), got "
+                             f"{tuple(t.stride())}")
+        yield t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w)
+
+
+def _check_image_table(what, table, cols, builder, rows=None):
+    """`table` of a kernel that takes one int64 row of `cols` columns per image, as `builder` makes it."""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != cols or not table.is_contiguous() \
+            or (rows is not None and table.shape[0] != rows):
+        raise ValueError(f"{what}: table is the (B, {cols}) int64 tensor of {builder}")
+
+
+def _workspace(what, ws_bytes, device, floor=0):
+    """The workspace a *_ws_bytes query asks for, at least `floor` bytes; a negative answer is the library's error."""
+    if ws_bytes < 0:
+        L.check(ws_bytes, what)
+    return torch.empty(max(ws_bytes, floor), dtype=torch.uint8, device=device)
+
+
+def _max_side(max_side):
+    """The largest h or w of a table, what its builder returned; without one the limit."""
+    return SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side)
+
+
+def seg_view_source_table(raws, net_sizes, flags):
+    """The source table of seg_view_windows_from_u8: seg_source_table's rows and a flag word per row (SEG_FLIP_H | SEG_FLIP_V)
+    -> (B, 7) int64.  One row per view: an image with several views appears once per view in `raws`.  flags None: the (B, 6)
+    table of the plain kernel."""
     if len(raws) == 0 or len(raws) != len(net_sizes):
         raise ValueError(f"seg_source_table: {len(raws)} images but {len(net_sizes)} network sizes")
     if flags is not None and (len(flags) != len(raws) or any(int(f) not in (0, 1, 2, 3) for f in flags)):
         raise ValueError("seg_view_windows_from_u8: one flag word of 0 .. 3 per source row")
     L.require_cuda(*raws)
-    tab = []
-    for k, (t, (H, W)) in enumerate(zip(raws, net_sizes)):
-        if t.dtype != torch.uint8:
+    for t in raws:
+        if t.dtype != torch.uint8:   # the front end's own error type for a wrong dtype
             raise TypeError(f"seg_windows_from_u8: a source image is uint8, got {t.dtype}")
-        if t.dim() != 3 or t.shape[2] != 3:
-            raise ValueError(f"seg_windows_from_u8: a source image is (h, w, 3), got {tuple(t.shape)}")
-        h, w = int(t.shape[0]), int(t.shape[1])
-        if t.device != raws[0].device:
-            raise ValueError("seg_windows_from_u8: the source images are on different devices")
-        if min(h, w, int(H), int(W)) < 1 or max(h, w, int(H), int(W)) >= SEG_SOURCE_LIMIT:
+    tab = []
+    for k, ((ptr, h, w, row), (H, W)) in enumerate(zip(_seg_pictures("seg_windows_from_u8", raws), net_sizes)):
+        if min(int(H), int(W)) < 1 or max(int(H), int(W)) >= SEG_SOURCE_LIMIT:
             raise ValueError(f"seg_windows_from_u8: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w} -> {H}x{W}")
-        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
-            raise ValueError(f"seg_windows_from_u8: a source image has interleaved channels and contiguous pixels (strides "
-                             f"(>= 3 w, 3, 1)), got {tuple(t.stride())}")
-        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(H), int(W)] + ([] if flags is None else [int(flags[k])]))
+        tab.append([ptr, h, w, row, int(H), int(W)] + ([] if flags is None else [int(flags[k])]))
     return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(len(tab), -1)
 
 
@@ -2650,13 +2665,7 @@ def seg_source_table(raws, net_sizes):
     """The device source table of seg_windows_from_u8: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows
     possibly strided], net_sizes [(H, W)] -> (B, 6) int64.  It holds the tensors' addresses: keep `raws` alive while it is
     in use."""
-    return _seg_source_table(raws, net_sizes)
-
-
-def seg_view_source_table(raws, net_sizes, flags):
-    """The source table of seg_view_windows_from_u8: seg_source_table's rows and a flag word per row (SEG_FLIP_H | SEG_FLIP_V)
-    -> (B, 7) int64.  One row per view: an image with several views appears once per view in `raws`."""
-    return _seg_source_table(raws, net_sizes, flags)
+    return seg_view_source_table(raws, net_sizes, None)
 
 
 def seg_view_windows_from_u8(raws, net_sizes, flags, windows, win_size, mean, inv_std, reverse_channels=False, out=None, table=None):
@@ -2680,9 +2689,8 @@ def _seg_windows_launch(raws, net_sizes, flags, table, windows, win_size, mean, 
     entry, cols = ("segclip_seg_windows_from_u8", SEG_SOURCE_COLS) if flags is None else \
         ("segclip_seg_view_windows_from_u8", SEG_SOURCE_COLS + 1)
     if table is None:
-        table = _seg_source_table(raws, net_sizes, flags)
-    if table.dtype != torch.int64 or tuple(table.shape) != (len(raws), cols) or not table.is_contiguous():
-        raise ValueError(f"seg_windows_from_u8: table is the (B, {cols}) int64 tensor of seg_source_table")
+        table = seg_view_source_table(raws, net_sizes, flags)
+    _check_image_table("seg_windows_from_u8", table, cols, "seg_source_table", rows=len(raws))
     if not torch.is_tensor(windows):
         windows = torch.tensor(windows, dtype=torch.int32, device=table.device).view(-1, 3)
     L.require_cuda(table, windows, out)
@@ -2733,20 +2741,9 @@ def seg_blend_table(raws, map_offsets):
     -> (table (B, 8) int64, output offsets, out_bytes, n_blocks)."""
     if len(raws) == 0 or len(raws) != len(map_offsets):
         raise ValueError(f"seg_blend: {len(raws)} images but {len(map_offsets)} index maps")
-    L.require_cuda(*raws)
     tab, offs, out, blk = [], [], 0, 0
-    for t, mo in zip(raws, map_offsets):
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"seg_blend: a source image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-        h, w = int(t.shape[0]), int(t.shape[1])
-        if t.device != raws[0].device:
-            raise ValueError("seg_blend: the source images are on different devices")
-        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
-            raise ValueError(f"seg_blend: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
-        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
-            raise ValueError(f"seg_blend: a source image has interleaved channels and contiguous pixels (strides (>= 3 w, 3, 1)), "
-                             f"got {tuple(t.stride())}")
-        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(mo), out, blk, 0])
+    for (ptr, h, w, row), mo in zip(_seg_pictures("seg_blend", raws), map_offsets):
+        tab.append([ptr, h, w, row, int(mo), out, blk, 0])
         offs.append(out)
         out += (3 * h * w + 3) // 4 * 4
         blk += (h * w + SEG_RENDER_TILE - 1) // SEG_RENDER_TILE
@@ -2757,8 +2754,7 @@ def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, rev
     """The overlay kernel (segclip_seg_blend): the table of seg_blend_table + the flat uint8 index maps + a (P, 3) uint8 RGB
     palette -> `out`, flat uint8, (h, w, 3) per image at the table's output offsets; `sums` (B, P, 3) int64 is added to."""
     L.require_cuda(table, maps, palette, out, sums)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_BLEND_COLS or not table.is_contiguous():
-        raise ValueError("seg_blend: table is the (B, 8) int64 tensor of seg_blend_table")
+    _check_image_table("seg_blend", table, SEG_BLEND_COLS, "seg_blend_table")
     if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256:
         raise ValueError(f"seg_blend: a palette is a (P <= 256, 3) uint8 tensor, got {palette.dtype} {tuple(palette.shape)}")
     opacity = float(opacity)
@@ -2792,20 +2788,9 @@ def seg_refine_table(raws, label_offsets):
     tensors' addresses: keep `raws` alive while it is in use.  -> (table (B, 8) int64, n_blocks, largest side)."""
     if len(raws) == 0 or len(raws) != len(label_offsets):
         raise ValueError(f"seg_refine: {len(raws)} images but {len(label_offsets)} label maps")
-    L.require_cuda(*raws)
     tab, gt, blk, side = [], 0, 0, 0
-    for t, lo in zip(raws, label_offsets):
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"seg_refine: a picture is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-        h, w = int(t.shape[0]), int(t.shape[1])
-        if t.device != raws[0].device:
-            raise ValueError("seg_refine: the pictures are on different devices")
-        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
-            raise ValueError(f"seg_refine: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
-        if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
-            raise ValueError(f"seg_refine: a picture has interleaved channels and contiguous pixels (strides (>= 3 w, 3, 1)), "
-                             f"got {tuple(t.stride())}")
-        tab.append([t.data_ptr(), h, w, max(int(t.stride(0)), 3 * w), int(lo), gt, blk, 0])
+    for (ptr, h, w, row), lo in zip(_seg_pictures("seg_refine", raws, "a picture"), label_offsets):
+        tab.append([ptr, h, w, row, int(lo), gt, blk, 0])
         gt += h * w
         blk += (h * w + SEG_REFINE_TILE - 1) // SEG_REFINE_TILE
         side = max(side, h, w)
@@ -2821,8 +2806,7 @@ def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv
     (C, h, w) final planes, for tests and inspection.  max_side: the largest h or w of the table (seg_refine_table's third
     result; defaults to the limit).  No host synchronisation; the workspace does not depend on num_classes."""
     L.require_cuda(table, labels, out, gt, areas, probs)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_REFINE_COLS or not table.is_contiguous():
-        raise ValueError("seg_refine: table is the (B, 8) int64 tensor of seg_refine_table")
+    _check_image_table("seg_refine", table, SEG_REFINE_COLS, "seg_refine_table")
     if out is None:
         out = torch.empty_like(labels)
     _seg_check_outputs("seg_refine", labels, gt, areas, int(num_classes))
@@ -2836,14 +2820,12 @@ def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv
     B, D = table.shape[0], len(dil)
     lib = L.load()
     ws_bytes, ws = 0, None
-    if int(iters) != 0:
+    if int(iters) != 0:   # no iteration: the labels pass through, nothing to hold
         ws_bytes = lib.segclip_seg_refine_ws_bytes(labels.numel(), B, D)
-        if ws_bytes < 0:
-            L.check(ws_bytes, "seg_refine")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=labels.device)
+        ws = _workspace("seg_refine", ws_bytes, labels.device)
     f3 = L.f32 * 3
     L.check(lib.segclip_seg_refine(
-        L.ptr(table), B, int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(labels), labels.numel(),
+        L.ptr(table), B, int(n_blocks), _max_side(max_side), L.ptr(labels), labels.numel(),
         int(num_classes), (C.c_int32 * max(D, 1))(*dil), D, int(iters), f3(*mean), f3(*inv_std), int(bool(reverse_channels)),
         L.ptr(out), out.numel(), L.ptr(gt), gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)),
         L.ptr(areas), L.ptr(probs), probs.numel() if probs is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_refine")
@@ -2882,8 +2864,7 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
     pixels belong to no component.  max_side: the largest h or w of the table (defaults to the limit).  No host
     synchronisation.  -> None."""
     L.require_cuda(table, labels, ids, area_px, records, count, cleaned)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_CC_COLS or not table.is_contiguous():
-        raise ValueError("seg_components: table is the (B, 8) int64 tensor of seg_components_table")
+    _check_image_table("seg_components", table, SEG_CC_COLS, "seg_components_table")
     if labels.dtype != torch.uint8 or not labels.is_contiguous():
         raise ValueError("seg_components: labels is a contiguous uint8 tensor")
     for name, t, dt in (("ids", ids, torch.int32), ("area_px", area_px, torch.int32), ("records", records, torch.int64),
@@ -2900,11 +2881,9 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
     B = table.shape[0]
     lib = L.load()
     ws_bytes = lib.segclip_seg_components_ws_bytes(labels.numel(), B, int(n_blocks))
-    if ws_bytes < 0:
-        L.check(ws_bytes, "seg_components")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=labels.device)
+    ws = _workspace("seg_components", ws_bytes, labels.device, 16)
     L.check(lib.segclip_seg_components(
-        L.ptr(table), B, int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(labels), labels.numel(),
+        L.ptr(table), B, int(n_blocks), _max_side(max_side), L.ptr(labels), labels.numel(),
         int(connectivity), -1 if skip_label is None else int(skip_label), L.ptr(ids), L.ptr(area_px), px[0] if px else 0,
         L.ptr(records), records.shape[0] if records is not None else 0, L.ptr(count), int(min_area), int(fill), L.ptr(cleaned),
         cleaned.numel() if cleaned is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_components")
@@ -2957,8 +2936,7 @@ def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255
     map), areas (2, 3, C) int64 that is ADDED to (slot 0 Boundary IoU, slot 1 trimap; needs gt).  max_side: the largest h or w
     of the table (defaults to the limit).  No host synchronisation.  -> None."""
     L.require_cuda(table, pred, gt, pred_band, gt_band, areas)
-    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != SEG_BOUNDARY_COLS or not table.is_contiguous():
-        raise ValueError("seg_boundary: table is the (B, 8) int64 tensor of seg_boundary_table")
+    _check_image_table("seg_boundary", table, SEG_BOUNDARY_COLS, "seg_boundary_table")
     for name, t in (("pred", pred), ("gt", gt), ("pred_band", pred_band), ("gt_band", gt_band)):
         if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
             raise ValueError(f"seg_boundary: {name} is a contiguous uint8 tensor")
@@ -2976,11 +2954,9 @@ def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255
     lib = L.load()
     gt_bytes = gt.numel() if gt is not None else 0
     ws_bytes = lib.segclip_seg_boundary_ws_bytes(pred.numel(), gt_bytes)
-    if ws_bytes < 0:
-        L.check(ws_bytes, "seg_boundary")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=pred.device)
+    ws = _workspace("seg_boundary", ws_bytes, pred.device, 16)
     L.check(lib.segclip_seg_boundary(
-        L.ptr(table), table.shape[0], int(n_blocks), SEG_SOURCE_LIMIT - 1 if max_side is None else int(max_side), L.ptr(pred),
+        L.ptr(table), table.shape[0], int(n_blocks), _max_side(max_side), L.ptr(pred),
         pred.numel(), L.ptr(gt), gt_bytes, num_classes, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(pred_band),
         L.ptr(gt_band), L.ptr(areas), L.ptr(ws), ws_bytes, L.stream()), "seg_boundary")
 

@@ -59,6 +59,12 @@ no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chun
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
 image without augmentation is one view with flags 0.  _list_forward (arg-max of the logits, group maps), _sweep_forward
 (the same for a list of thresholds) and _views_forward (soft-max mean, dense twin) are the kernel calls over the same steps.
+Behind the label kernel, _Maps owns the layout of a list of maps in one flat buffer (views used where they lie, copies at
+multiples of 4, zeroed bytes between the maps of an output, the gapless form that the ground truths have), and
+SegInference._post_process is the one chain labels -> refine -> clean -> areas -> boundary areas for predict_raw and every
+update path; its docstring states which kernel counts the mIoU areas.  _refuse words the refusals of the entry points that
+do not take a stage, and _check_pictures / _check_maps (here) and ops._seg_pictures (strides, where the addresses are taken)
+are the only checks of decoded pictures and index maps.
 
 Deviations from the reference.  mmseg takes a softmax between the resize and the arg-max; without augmentation the arg-max
 is taken of the logits here, which can differ only where fp32 exp rounds two different logits to one value (the augmented
@@ -70,6 +76,7 @@ to the picture's size.  Text is not drawn: input_pred_label returns the anchor p
 """
 import collections
 import colorsys
+import itertools
 import math
 
 import torch
@@ -254,17 +261,11 @@ class _RawImages(_Source):
     sizes: one (H, W) per image, with aug one per view of every image in the order of aug.views."""
 
     def __init__(self, raws, transform, net_sizes=None, aug=None):
-        if len(raws) == 0:
-            raise ValueError("empty image list")
+        self.pictures, self.default_out = list(raws), _check_pictures(raws)   # the output sizes: mmseg's ori_shape
         if not isinstance(transform, ImageTransform):
             raise TypeError("transform is an ImageTransform")
         if aug is not None and not isinstance(aug, TestAug):
             raise TypeError("aug is a TestAug")
-        ops.L.require_cuda(*raws)
-        for t in raws:
-            if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-                raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-        self.default_out = [(int(t.shape[0]), int(t.shape[1])) for t in raws]   # mmseg's ori_shape
         if aug is None:
             if net_sizes is not None and len(net_sizes) != len(raws):
                 raise ValueError(f"{len(raws)} images but {len(net_sizes)} network sizes")
@@ -335,6 +336,99 @@ class TestAug:
         return out
 
 
+def _check_pictures(raws, maps=None, noun="a label map"):
+    """Decoded pictures, (h, w, 3) uint8 device tensors, and with `maps` one map of every picture's size -> the sizes
+    [(h, w)].  The pictures' strides are checked where their addresses are taken, by the table builders of ops."""
+    if len(raws) == 0:
+        raise ValueError("empty image list")
+    if maps is not None and len(raws) != len(maps):
+        raise ValueError(f"{len(raws)} images but {len(maps)} {noun.split(' ', 1)[1]}s")
+    ops.L.require_cuda(*raws)
+    for t in raws:
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
+    if maps is not None:
+        _check_maps(maps, noun, sizes)
+    return sizes
+
+
+def _check_maps(maps, noun="a label map", sizes=None):
+    """A list of (h, w) uint8 device maps, `noun` each in the messages.  sizes: those of the pictures they belong to; without
+    them any non-empty size."""
+    plural = noun.split(" ", 1)[1] + "s"
+    if len(maps) == 0:
+        raise ValueError(f"empty list of {plural}")
+    ops.L.require_cuda(*maps)
+    for i, m in enumerate(maps):
+        plain = m.dtype == torch.uint8 and m.dim() == 2
+        if sizes is None and not (plain and m.numel() > 0):
+            raise ValueError(f"{noun} is a non-empty (h, w) uint8 tensor, got {m.dtype} {tuple(m.shape)}")
+        if sizes is not None and not (plain and tuple(m.shape) == sizes[i]):
+            raise ValueError(f"{noun} is an (h, w) uint8 tensor of its image's size {sizes[i]}, got {m.dtype} {tuple(m.shape)}")
+        if m.device != maps[0].device:
+            raise ValueError(f"the {plural} are on different devices")
+
+
+class _Maps:
+    """A list of (h_i, w_i) maps in one flat buffer: map i is the h_i * w_i elements of `flat` from offs[i], sizes[i] =
+    (h_i, w_i).  The kernels take `flat` and a table of the offsets; between two maps there may be bytes that belong to none
+    (the label kernels start every map at a multiple of 4), and what follows a kernel in the chain reads them as they are: an
+    output that is passed on has them zeroed (empty_like)."""
+
+    def __init__(self, flat, offs, sizes):
+        self.flat, self.offs, self.sizes = flat, list(offs), [(int(h), int(w)) for (h, w) in sizes]
+
+    @classmethod
+    def of(cls, maps):
+        """A list of uint8 maps -> their batch.  Contiguous views of one storage (what predict_raw and groups_raw return) are used where
+        they lie, without a copy; anything else is copied into a new zeroed buffer at offsets that are multiples of 4."""
+        sizes = [tuple(m.shape) for m in maps]
+        store = maps[0].untyped_storage().data_ptr()
+        if all(m.is_contiguous() and m.untyped_storage().data_ptr() == store for m in maps):
+            lo = min(m.storage_offset() for m in maps)
+            hi = max(m.storage_offset() + m.numel() for m in maps)
+            return cls(torch.as_strided(maps[0], (hi - lo,), (1,), lo), [m.storage_offset() - lo for m in maps], sizes)
+        offs, n = cls._running([(m.numel() + 3) // 4 * 4 for m in maps])
+        new = cls(torch.zeros(n, dtype=torch.uint8, device=maps[0].device), offs, sizes)
+        for v, m in zip(new.views(), maps):
+            v.copy_(m)
+        return new
+
+    @staticmethod
+    def _running(lengths):
+        """-> (the running sum before every length, the total)"""
+        sums = [0, *itertools.accumulate(lengths)]
+        return sums[:-1], sums[-1]
+
+    @classmethod
+    def gapless_of(cls, gts):
+        """Ground truths laid one after the other, as the kernels that score against them take them -> (flat tensor, offsets);
+        (None, None) without ground truths."""
+        if gts is None:
+            return None, None
+        flat = gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
+        return flat, cls._running([g.numel() for g in gts])[0]
+
+    def packed(self):
+        """The maps lie one after the other in list order and fill the buffer."""
+        offs, n = self._running([h * w for h, w in self.sizes])
+        return self.offs == offs and self.flat.numel() == n
+
+    def views(self):
+        """The per-image (h, w) views of the buffer."""
+        return [self.flat[o:o + h * w].view(h, w) for o, (h, w) in zip(self.offs, self.sizes)]
+
+    def empty_like(self):
+        """An output buffer of the same layout; the bytes between the maps, which no kernel writes, are zero."""
+        out = torch.empty_like(self.flat)
+        return _Maps(out if self.packed() else out.zero_(), self.offs, self.sizes)
+
+    def gapless(self):
+        """The maps one after the other in a flat tensor: `flat` itself where they lie so already, else a copy."""
+        return self.flat if self.packed() else torch.cat([v.reshape(-1) for v in self.views()])
+
+
 class PAMR:
     """Pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) as a post-processing step of the label maps: `iters`
     iterations of an affinity-weighted average over the 8 neighbours at each of `dilations` (csrc/segment_refine.inc; the
@@ -363,27 +457,17 @@ def _refine_maps(raws, maps, num_classes, transform, pamr, gts=None, areas=None,
         raise TypeError("refine is a PAMR")
     if not isinstance(transform, ImageTransform):
         raise TypeError("transform is an ImageTransform")
-    if len(raws) == 0:
-        raise ValueError("empty image list")
-    if len(raws) != len(maps):
-        raise ValueError(f"{len(raws)} images but {len(maps)} label maps")
-    ops.L.require_cuda(*raws, *maps)
-    for t, m in zip(raws, maps):
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-        if m.dtype != torch.uint8 or m.dim() != 2 or tuple(m.shape) != tuple(t.shape[:2]):
-            raise ValueError(f"a label map is an (h, w) uint8 tensor of its image's size {tuple(t.shape[:2])}, got {m.dtype} "
-                             f"{tuple(m.shape)}")
+    _check_pictures(raws, maps)
     if gts is not None:
         for g, m in zip(gts, maps):
             if tuple(g.shape) != tuple(m.shape):
                 raise ValueError(f"refine: a ground truth has its picture's size {tuple(m.shape)}, got {tuple(g.shape)}")
-    flat, offs = _flat_maps(list(maps))
-    table, n_blocks, side = ops.seg_refine_table(list(raws), offs)
-    out = ops.seg_refine(table, n_blocks, flat, num_classes, pamr.dilations, pamr.iters, transform.mean, transform.inv_std,
-                         reverse_channels=transform.channel_order == "bgr", gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index,
-                         reduce_zero_label=reduce_zero_label, max_side=side)
-    return _split_maps(out, offs, [tuple(m.shape) for m in maps])
+    batch = _Maps.of(maps)
+    table, n_blocks, side = ops.seg_refine_table(list(raws), batch.offs)
+    out = ops.seg_refine(table, n_blocks, batch.flat, num_classes, pamr.dilations, pamr.iters, transform.mean, transform.inv_std,
+                         reverse_channels=transform.channel_order == "bgr", gt=_Maps.gapless_of(gts)[0], areas=areas,
+                         ignore_index=ignore_index, reduce_zero_label=reduce_zero_label, max_side=side)
+    return _Maps(out, batch.offs, batch.sizes).views()
 
 
 @torch.no_grad()
@@ -393,17 +477,6 @@ def refine_labels(raws, labels, num_classes, transform, pamr):
     call and without a host synchronisation.  transform supplies the normalisation and the pictures' channel order.  The
     inputs stay as they are."""
     return _refine_maps(raws, labels, num_classes, transform, pamr)
-
-
-def _check_refine(refine, raws, out_shapes):
-    """refine= of predict_raw / update_raw: a PAMR, and label maps at the pictures' own sizes."""
-    if not isinstance(refine, PAMR):
-        raise TypeError("refine is a PAMR")
-    if out_shapes is not None:
-        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
-        if [(int(a), int(b)) for (a, b) in out_shapes] != sizes:
-            raise ValueError(f"refine: out_shapes must be the raw images' own sizes {sizes} (the refinement reads the picture under "
-                             f"every label), got {list(out_shapes)}")
 
 
 class Despeckle:
@@ -422,17 +495,6 @@ class Despeckle:
         if skip_label is not None and (isinstance(skip_label, bool) or not isinstance(skip_label, int) or not 0 <= skip_label <= 255):
             raise ValueError(f"Despeckle: skip_label is None or an integer in 0 .. 255, got {skip_label!r}")
         self.min_area, self.fill, self.connectivity, self.skip_label = min_area, fill, connectivity, skip_label
-
-
-def _check_label_maps(maps):
-    if len(maps) == 0:
-        raise ValueError("empty list of label maps")
-    ops.L.require_cuda(*maps)
-    for m in maps:
-        if m.dtype != torch.uint8 or m.dim() != 2 or m.numel() == 0:
-            raise ValueError(f"a label map is a non-empty (h, w) uint8 tensor, got {m.dtype} {tuple(m.shape)}")
-        if m.device != maps[0].device:
-            raise ValueError("the label maps are on different devices")
 
 
 class Objects:
@@ -460,24 +522,23 @@ def components(maps, connectivity=8, skip_label=None, max_objects=None):
     count is the ONE host synchronisation of this function; more components than max_objects raise a ValueError that names
     both numbers (ask again with a larger max_objects)."""
     maps = list(maps)
-    _check_label_maps(maps)
-    flat, offs = _flat_maps(maps)
-    sizes = [tuple(m.shape) for m in maps]
-    dev = flat.device
+    _check_maps(maps)
+    batch = _Maps.of(maps)
+    dev = batch.flat.device
     if max_objects is None:
-        max_objects = max(4096, sum(h * w for h, w in sizes) // 16)
+        max_objects = max(4096, sum(h * w for h, w in batch.sizes) // 16)
     if isinstance(max_objects, bool) or not isinstance(max_objects, int) or max_objects < 1:
         raise ValueError(f"components: max_objects is a positive integer, got {max_objects!r}")
-    table, n_blocks, side = ops.seg_components_table(sizes, offs, dev)
-    ids = torch.empty(flat.numel(), dtype=torch.int32, device=dev)
+    table, n_blocks, side = ops.seg_components_table(batch.sizes, batch.offs, dev)
+    ids = torch.empty(batch.flat.numel(), dtype=torch.int32, device=dev)   # only the maps' own entries are ever seen
     records = torch.empty(max_objects, ops.SEG_CC_RECORD, dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
-    ops.seg_components(table, n_blocks, flat, connectivity=connectivity, skip_label=skip_label, ids=ids, records=records,
+    ops.seg_components(table, n_blocks, batch.flat, connectivity=connectivity, skip_label=skip_label, ids=ids, records=records,
                        count=count, max_side=side)
     n = int(count.item())
     if n > max_objects:
         raise ValueError(f"components: the maps hold {n} components but max_objects is {max_objects}")
-    return Objects(_split_maps(ids, offs, sizes), records[:n], n)
+    return Objects(_Maps(ids, batch.offs, batch.sizes).views(), records[:n], n)
 
 
 def _check_clean(clean):
@@ -486,19 +547,16 @@ def _check_clean(clean):
 
 
 def _despeckle_maps(maps, clean):
-    """-> (the cleaned maps, views of one new buffer; that buffer; the maps' offsets in it)"""
+    """-> the cleaned maps, a _Maps over one new buffer"""
     _check_clean(clean)
     maps = list(maps)
-    _check_label_maps(maps)
-    flat, offs = _flat_maps(maps)
-    sizes = [tuple(m.shape) for m in maps]
-    table, n_blocks, side = ops.seg_components_table(sizes, offs, flat.device)
-    out = torch.empty_like(flat)
-    if out.numel() != sum(h * w for h, w in sizes):
-        out.zero_()  # the bytes between the maps
-    ops.seg_components(table, n_blocks, flat, connectivity=clean.connectivity, skip_label=clean.skip_label, min_area=clean.min_area,
-                       fill=clean.fill, cleaned=out, max_side=side)
-    return _split_maps(out, offs, sizes), out, offs
+    _check_maps(maps)
+    batch = _Maps.of(maps)
+    table, n_blocks, side = ops.seg_components_table(batch.sizes, batch.offs, batch.flat.device)
+    out = batch.empty_like()
+    ops.seg_components(table, n_blocks, batch.flat, connectivity=clean.connectivity, skip_label=clean.skip_label,
+                       min_area=clean.min_area, fill=clean.fill, cleaned=out.flat, max_side=side)
+    return out
 
 
 @torch.no_grad()
@@ -506,7 +564,7 @@ def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None):
     """maps [(h_i, w_i) uint8 label maps] -> [(h_i, w_i) uint8], views of one new buffer: every connected component with fewer
     than min_area pixels replaced by `fill` (see Despeckle), all maps in one call and without a host synchronisation.  The
     inputs stay as they are."""
-    return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label))[0]
+    return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label)).views()
 
 
 class Boundary:
@@ -541,22 +599,15 @@ def _check_boundary(boundary):
         raise TypeError("boundary is a Boundary")
 
 
-def _boundary_call(maps, boundary, gts=None, flat=None, **kw):
-    """ops.seg_boundary over a list of maps (flat: their (buffer, offsets) where _flat_maps has laid them out already) and
-    their ground truths, which lie gapless one after the other as _flat_gts lays them."""
-    flat, offs = _flat_maps(maps) if flat is None else flat
-    sizes = [tuple(m.shape) for m in maps]
-    radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(sizes)]
-    gt_offs = None
-    if gts is not None:
-        gt_offs, n = [], 0
-        for g, hw in zip(gts, sizes):
-            if tuple(g.shape) != hw:
-                raise ValueError(f"boundary: a ground truth has its label map's size {hw}, got {tuple(g.shape)}")
-            gt_offs.append(n)
-            n += g.numel()
-    table, n_blocks, side = ops.seg_boundary_table(sizes, offs, gt_offs, radii, flat.device)
-    ops.seg_boundary(table, n_blocks, flat, gt=_flat_gts(gts), max_side=side, **kw)
+def _boundary_call(batch, boundary, gts=None, **kw):
+    """ops.seg_boundary over a _Maps and the ground truths of its maps, laid gapless one after the other."""
+    radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(batch.sizes)]
+    for g, hw in zip(gts or (), batch.sizes):
+        if tuple(g.shape) != hw:
+            raise ValueError(f"boundary: a ground truth has its label map's size {hw}, got {tuple(g.shape)}")
+    gt, gt_offs = _Maps.gapless_of(gts)
+    table, n_blocks, side = ops.seg_boundary_table(batch.sizes, batch.offs, gt_offs, radii, batch.flat.device)
+    ops.seg_boundary(table, n_blocks, batch.flat, gt=gt, max_side=side, **kw)
 
 
 @torch.no_grad()
@@ -567,13 +618,11 @@ def boundary_bands(maps, boundary):
     All maps in one call and without a host synchronisation; the inputs stay as they are."""
     _check_boundary(boundary)
     maps = list(maps)
-    _check_label_maps(maps)
-    flat, offs = _flat_maps(maps)
-    band = torch.empty_like(flat)
-    if band.numel() != sum(m.numel() for m in maps):
-        band.zero_()  # the bytes between the maps
-    _boundary_call(maps, boundary, flat=(flat, offs), pred_band=band)
-    return _split_maps(band, offs, [tuple(m.shape) for m in maps])
+    _check_maps(maps)
+    batch = _Maps.of(maps)
+    band = batch.empty_like()
+    _boundary_call(batch, boundary, pred_band=band.flat)
+    return band.views()
 
 
 @torch.no_grad()
@@ -585,15 +634,43 @@ def boundary_areas(preds, gts, num_classes, boundary, ignore_index=255, reduce_z
     figures.  One call, no host synchronisation."""
     _check_boundary(boundary)
     preds, gts = list(preds), list(gts)
-    _check_label_maps(preds)
+    _check_maps(preds)
     if len(preds) != len(gts):
         raise ValueError(f"{len(preds)} predictions but {len(gts)} ground truths")
     SegEvaluator._check_gts(preds, gts)
     if areas is None:
         areas = torch.zeros(2, 3, int(num_classes), dtype=torch.int64, device=preds[0].device)
-    _boundary_call(preds, boundary, gts=gts, num_classes=num_classes, ignore_index=ignore_index,
+    _boundary_call(_Maps.of(preds), boundary, gts=gts, num_classes=num_classes, ignore_index=ignore_index,
                    reduce_zero_label=reduce_zero_label, areas=areas)
     return areas
+
+
+def _check_stages(refine, clean, raws, out_shapes):
+    """refine= and clean= of predict_raw / update_raw: a PAMR, with label maps at the pictures' own sizes, and a Despeckle.  It
+    runs before the source is built: what the host does between the source's table copy and the first launch is not hidden
+    behind the device's work."""
+    if clean is not None:
+        _check_clean(clean)
+    if refine is not None and not isinstance(refine, PAMR):
+        raise TypeError("refine is a PAMR")
+    if refine is not None and out_shapes is not None:
+        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
+        if [(int(a), int(b)) for (a, b) in out_shapes] != sizes:
+            raise ValueError(f"refine: out_shapes must be the raw images' own sizes {sizes} (the refinement reads the picture under "
+                             f"every label), got {list(out_shapes)}")
+
+
+def _refuse(entry, *stages):
+    """The entry points that do not take a stage of the chain: stages = (name, what the caller gave, the advice); the first
+    one given raises."""
+    for name, given, advice in stages:
+        if given is not None:
+            raise ValueError(f"{entry}: {name} {advice}")
+
+
+# What an evaluator's call hands to the chain: the ground truths, the (3, C) areas, the ground-truth rule (ignore_index and
+# reduce_zero_label, as keyword arguments of every kernel that counts), the Boundary or None and its (2, 3, C) areas.
+_Score = collections.namedtuple("_Score", "gts areas rule boundary boundary_areas")
 
 
 def _out_shapes(src, out_shapes):
@@ -604,17 +681,6 @@ def _out_shapes(src, out_shapes):
     if out_shapes is None or len(out_shapes) != n_img:
         raise ValueError(f"{n_img} images but {0 if out_shapes is None else len(out_shapes)} output shapes")
     return [(int(a), int(b)) for (a, b) in out_shapes]
-
-
-def _flat_gts(gts):
-    if gts is None:
-        return None
-    return gts[0].reshape(-1) if len(gts) == 1 else torch.cat([g.reshape(-1) for g in gts])
-
-
-def _split_maps(flat, offs, out_shapes):
-    """The per-image (oh, ow) views of a flat buffer of maps."""
-    return None if flat is None else [flat[o:o + oh * ow].view(oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
 
 
 def _require_eval(model):
@@ -779,13 +845,14 @@ class SegInference:
         if classes:
             labels = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
             ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels,
-                                       gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
-            labels = _split_maps(labels, offs, out_shapes)
+                                       gt=_Maps.gapless_of(gts)[0], areas=areas, ignore_index=ignore_index,
+                                       reduce_zero_label=reduce_zero_label)
+            labels = None if labels is None else _Maps(labels, offs, out_shapes).views()
         if groups is None:
             return labels
         # the table's label offsets and workgroup numbers serve the group maps as they are: same sizes, same tile
         gmaps = ops.seg_groups_rescaled(soft, images, n_blocks, n_groups, torch.empty(nbytes, dtype=torch.uint8, device=src.device))
-        return labels, _split_maps(gmaps, offs, out_shapes), n_groups
+        return labels, _Maps(gmaps, offs, out_shapes).views(), n_groups
 
     def _sweep_forward(self, src, out_shapes, thresholds, gts=None, areas=None, ignore_index=255, reduce_zero_label=False,
                        want_labels=True):
@@ -798,8 +865,8 @@ class SegInference:
         rows = self._image_rows(src, plan, win_off, out_shapes, gts is not None)
         images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, src.device)
         labels = torch.empty(len(thresholds), nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
-        ops.seg_label_map_sweep(soft, tables, dwin, images, n_blocks, most, thresholds, labels=labels, gt=_flat_gts(gts), areas=areas,
-                                ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+        ops.seg_label_map_sweep(soft, tables, dwin, images, n_blocks, most, thresholds, labels=labels, gt=_Maps.gapless_of(gts)[0],
+                                areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
         if labels is None:
             return None
         return [labels[:, o:o + oh * ow].view(-1, oh, ow) for o, (oh, ow) in zip(offs, out_shapes)]
@@ -820,12 +887,38 @@ class SegInference:
         if dense:
             return ops.seg_view_probs(*args, out_shapes[0])
         labels = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
-        ops.seg_label_map_views(*args, labels=labels, gt=_flat_gts(gts), areas=areas, ignore_index=ignore_index,
+        ops.seg_label_map_views(*args, labels=labels, gt=_Maps.gapless_of(gts)[0], areas=areas, ignore_index=ignore_index,
                                 reduce_zero_label=reduce_zero_label)
-        return _split_maps(labels, offs, out_shapes)
+        return None if labels is None else _Maps(labels, offs, out_shapes).views()
 
-    def _forward(self, src, out_shapes, **kw):
-        return (self._views_forward if src.augmented else self._list_forward)(src, out_shapes, **kw)
+    def _post_process(self, src, out_shapes, refine=None, clean=None, score=None, want_labels=True):
+        """The chain of every list entry point that returns or scores label maps: labels -> refine (a PAMR, against
+        src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas.  score: None, or the _Score of an
+        evaluator's call; the areas are those of the maps that leave the chain, counted once (`counts`), by
+
+            refine   clean       the mIoU areas are counted by
+            -        -           the label kernel
+            PAMR     -           the refinement's last kernel; the label kernel only writes the maps
+            any      Despeckle   ops.seg_areas on the cleaned maps, gapless; nothing earlier counts
+
+        and with score.boundary one more ops.seg_boundary call on the same maps adds to score.boundary_areas.  The labels are
+        formed whenever a later stage reads them, wanted or not.  -> the final maps, or None when they are not wanted."""
+        forward = self._views_forward if src.augmented else self._list_forward
+        counts = None if score is None else "clean" if clean is not None else "refine" if refine is not None else "labels"
+        counting = {} if score is None else dict(gts=score.gts, areas=score.areas, **score.rule)
+        first = dict(counting, want_labels=want_labels or score.boundary is not None) if counts == "labels" else {}
+        labels = forward(src, out_shapes, **first)
+        if refine is not None:
+            labels = _refine_maps(src.pictures, labels, self.num_classes, src.transform, refine, **(counting if counts == "refine" else {}))
+        if clean is not None:
+            cleaned = _despeckle_maps(labels, clean)
+            labels = cleaned.views()
+            if counts == "clean":
+                ops.seg_areas(cleaned.gapless(), _Maps.gapless_of(score.gts)[0], self.num_classes, areas=score.areas, **score.rule)
+        if score is not None and score.boundary is not None:
+            _boundary_call(_Maps.of(labels), score.boundary, gts=score.gts, num_classes=self.num_classes, areas=score.boundary_areas,
+                           **score.rule)
+        return labels if want_labels else None
 
     @torch.no_grad()
     def predict_list(self, imgs, out_shapes=None, refine=None, clean=None):
@@ -834,10 +927,8 @@ class SegInference:
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
         Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size.
         refine is refused: there is no raw picture here (predict_raw has it); clean too: despeckle the maps."""
-        if refine is not None:
-            raise ValueError("predict_list: refine needs the decoded pictures: use predict_raw(refine=) or refine_labels")
-        if clean is not None:
-            raise ValueError("predict_list: clean is not supported; apply despeckle to the maps it returns")
+        _refuse("predict_list", ("refine", refine, "needs the decoded pictures: use predict_raw(refine=) or refine_labels"),
+                ("clean", clean, "is not supported; apply despeckle to the maps it returns"))
         return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes)
 
     @torch.no_grad()
@@ -854,15 +945,8 @@ class SegInference:
         then be the raw sizes (the default).  It composes with aug: the refinement sees only labels.
         clean (a Despeckle): the maps, after the refinement if there is one, are despeckled before they are returned,
         = despeckle(predict_raw(raws, ...), ...) bit for bit."""
-        if clean is not None:
-            _check_clean(clean)
-        if refine is None:
-            labels = self._forward(_RawImages(raws, transform, net_sizes, aug), out_shapes)
-        else:
-            _check_refine(refine, raws, out_shapes)
-            labels = self._forward(_RawImages(raws, transform, net_sizes, aug), None)
-            labels = _refine_maps(raws, labels, self.num_classes, transform, refine)
-        return labels if clean is None else _despeckle_maps(labels, clean)[0]
+        _check_stages(refine, clean, raws, out_shapes)
+        return self._post_process(_RawImages(raws, transform, net_sizes, aug), out_shapes, refine, clean)
 
     @torch.no_grad()
     def predict_views(self, views, out_shapes):
@@ -912,10 +996,8 @@ class SegInference:
         default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
         call whatever the modes: labels and group maps come from the same encode_image pass.  refine is refused: draw refined
         maps with blend(raws, predict_raw(raws, transform, refine=...), palette).  clean is refused in the same way."""
-        if refine is not None:
-            raise ValueError("render_raw: refine is not supported; blend the maps of predict_raw(refine=) instead")
-        if clean is not None:
-            raise ValueError("render_raw: clean is not supported; blend the maps of despeckle(predict_raw(...)) instead")
+        _refuse("render_raw", ("refine", refine, "is not supported; blend the maps of predict_raw(refine=) instead"),
+                ("clean", clean, "is not supported; blend the maps of despeckle(predict_raw(...)) instead"))
         modes = list(vis_modes)
         for m in modes:
             if m not in VIS_MODES:
@@ -981,24 +1063,6 @@ def _check_palette(palette, device):
     return palette.to(device).contiguous()
 
 
-def _flat_maps(maps):
-    """Index maps -> (flat uint8 buffer, offset of every map).  Views of one buffer (what predict_raw and groups_raw return)
-    are used where they lie; anything else is copied into a new buffer at offsets that are multiples of 4."""
-    store = maps[0].untyped_storage().data_ptr()
-    if all(m.is_contiguous() and m.untyped_storage().data_ptr() == store for m in maps):
-        lo = min(m.storage_offset() for m in maps)
-        hi = max(m.storage_offset() + m.numel() for m in maps)
-        return torch.as_strided(maps[0], (hi - lo,), (1,), lo), [m.storage_offset() - lo for m in maps]
-    offs, n = [], 0
-    for m in maps:
-        offs.append(n)
-        n += (m.numel() + 3) // 4 * 4
-    flat = torch.zeros(n, dtype=torch.uint8, device=maps[0].device)
-    for m, o in zip(maps, offs):
-        flat[o:o + m.numel()].view(m.shape).copy_(m)
-    return flat, offs
-
-
 @torch.no_grad()
 def blend(raws, maps, palette, opacity=0.5, skip_zero=False, channel_order="rgb", anchors=False):
     """blend_result (vit_seg.py:258-284) for a list of pictures of mixed sizes in one launch: raws [(h_i, w_i, 3) uint8
@@ -1012,24 +1076,14 @@ def blend(raws, maps, palette, opacity=0.5, skip_zero=False, channel_order="rgb"
     opacity = float(opacity)
     if not 0.0 < opacity <= 1.0:
         raise ValueError(f"opacity lies in (0, 1], got {opacity}")
-    if len(raws) == 0:
-        raise ValueError("empty image list")
-    if len(raws) != len(maps):
-        raise ValueError(f"{len(raws)} images but {len(maps)} index maps")
-    ops.L.require_cuda(*raws, *maps)
-    for t, m in zip(raws, maps):
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a decoded image is an (h, w, 3) uint8 tensor, got {t.dtype} {tuple(t.shape)}")
-        if m.dtype != torch.uint8 or m.dim() != 2 or tuple(m.shape) != tuple(t.shape[:2]):
-            raise ValueError(f"an index map is an (h, w) uint8 tensor of its image's size {tuple(t.shape[:2])}, got {m.dtype} "
-                             f"{tuple(m.shape)}")
+    _check_pictures(raws, maps, "an index map")
     dev = raws[0].device
     palette = _check_palette(palette, dev)
-    flat, map_offs = _flat_maps(list(maps))
-    table, offs, nbytes, n_blocks = ops.seg_blend_table(list(raws), map_offs)
+    batch = _Maps.of(maps)
+    table, offs, nbytes, n_blocks = ops.seg_blend_table(list(raws), batch.offs)
     out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     sums = torch.zeros(len(raws), palette.shape[0], 3, dtype=torch.int64, device=dev) if anchors else None
-    ops.seg_blend(table, n_blocks, flat, palette, opacity, out, skip_zero=skip_zero, reverse_channels=channel_order == "bgr",
+    ops.seg_blend(table, n_blocks, batch.flat, palette, opacity, out, skip_zero=skip_zero, reverse_channels=channel_order == "bgr",
                   sums=sums)
     imgs = [out[o:o + 3 * t.shape[0] * t.shape[1]].view(t.shape[0], t.shape[1], 3) for o, t in zip(offs, raws)]
     return (imgs, sums) if anchors else imgs
@@ -1074,22 +1128,20 @@ class SegEvaluator:
         if self.boundary_areas is not None:
             self.boundary_areas.zero_()
 
-    def _score_boundary(self, labels, gts):
-        if self.boundary is not None:
-            _boundary_call(list(labels), self.boundary, gts=list(gts), num_classes=self.seg.num_classes,
-                           ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label, areas=self.boundary_areas)
+    def _score(self, gts):
+        """-> (what the chain, SegInference._post_process, scores a call against; the ground truths' sizes, its out_shapes)"""
+        rule = dict(ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
+        return _Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas), [tuple(g.shape) for g in gts]
 
     @torch.no_grad()
     def update(self, imgs, gts, return_labels=False, refine=None, clean=None):
         """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size.  refine is
         refused: there is no raw picture here (update_raw has it); clean is refused too (update_raw has it)."""
-        if refine is not None:
-            raise ValueError("SegEvaluator.update: refine needs the decoded pictures: use update_raw(refine=)")
-        if clean is not None:
-            raise ValueError("SegEvaluator.update: clean is not supported; use update_raw(clean=), or despeckle the maps and "
-                             "score them with ops.seg_areas")
+        _refuse("SegEvaluator.update", ("refine", refine, "needs the decoded pictures: use update_raw(refine=)"),
+                ("clean", clean, "is not supported; use update_raw(clean=), or despeckle the maps and score them with ops.seg_areas"))
         self._check_gts(imgs, gts)
-        return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
+        score, shapes = self._score(gts)
+        return self.seg._post_process(_SlicedImages([[(t, 0)] for t in imgs]), shapes, score=score, want_labels=return_labels)
 
     @torch.no_grad()
     def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
@@ -1099,36 +1151,16 @@ class SegEvaluator:
         clean (a Despeckle): the labels are formed (and refined) without counting, despeckled, and ops.seg_areas of the cleaned
         maps against the ground truths is added: the areas are those of the cleaned maps."""
         self._check_gts(raws, gts)
-        if clean is not None:
-            _check_clean(clean)
-            shapes = [tuple(g.shape) for g in gts]
-            if refine is None:
-                labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), shapes)
-            else:
-                _check_refine(refine, raws, shapes)
-                labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), None)
-                labels = _refine_maps(raws, labels, self.seg.num_classes, transform, refine)
-            cleaned, flat, offs = _despeckle_maps(labels, clean)
-            if flat.numel() != sum(g.numel() for g in gts):  # bytes between the maps: score a gapless copy
-                flat = torch.cat([c.reshape(-1) for c in cleaned])
-            ops.seg_areas(flat, _flat_gts(list(gts)), self.seg.num_classes, ignore_index=self.ignore_index,
-                          reduce_zero_label=self.reduce_zero_label, areas=self.areas)
-            self._score_boundary(cleaned, gts)
-            return cleaned if return_labels else None
-        if refine is None:
-            return self._forward(_RawImages(raws, transform, net_sizes, aug), gts, return_labels)
-        _check_refine(refine, raws, [tuple(g.shape) for g in gts])
-        labels = self.seg._forward(_RawImages(raws, transform, net_sizes, aug), None)
-        refined = _refine_maps(raws, labels, self.seg.num_classes, transform, refine, gts=list(gts), areas=self.areas,
-                               ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
-        self._score_boundary(refined, gts)
-        return refined if return_labels else None
+        score, shapes = self._score(gts)
+        _check_stages(refine, clean, raws, shapes)
+        return self.seg._post_process(_RawImages(raws, transform, net_sizes, aug), shapes, refine, clean, score, return_labels)
 
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):
         """views[i] = [((3, H, W) tensor, flags)] as SegInference.predict_views, scored at each ground truth's size."""
         self._check_gts(views, gts)
-        return self._forward(_SlicedImages(views, augmented=True), gts, return_labels)
+        score, shapes = self._score(gts)
+        return self.seg._post_process(_SlicedImages(views, augmented=True), shapes, score=score, want_labels=return_labels)
 
     @staticmethod
     def _check_gts(imgs, gts):
@@ -1138,13 +1170,6 @@ class SegEvaluator:
         for g in gts:
             if g.dtype != torch.uint8 or g.dim() != 2:
                 raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
-
-    def _forward(self, src, gts, return_labels):
-        labels = self.seg._forward(src, [tuple(g.shape) for g in gts], gts=list(gts), areas=self.areas,
-                                   ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label,
-                                   want_labels=return_labels or self.boundary is not None)
-        self._score_boundary(labels, gts)
-        return labels if return_labels else None
 
     @staticmethod
     def boundary_metrics_from_areas(areas):
@@ -1231,15 +1256,13 @@ class SegSweepEvaluator:
     @torch.no_grad()
     def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
         """As SegEvaluator.update_raw, without aug, without refine and without clean."""
-        if clean is not None:
-            raise ValueError("SegSweepEvaluator: clean is not supported (every threshold's map would need its own pass); despeckle "
-                             "the maps of one SegEvaluator per threshold (update_raw(clean=))")
-        if refine is not None:
-            raise ValueError("SegSweepEvaluator: refine is not supported (every threshold's map would need its own refinement); "
-                             "use one SegEvaluator per threshold")
-        if aug is not None:
-            raise ValueError("SegSweepEvaluator: aug is not supported (the augmented path needs accumulators per threshold); "
-                             "use one SegEvaluator per threshold")
+        _refuse("SegSweepEvaluator",
+                ("clean", clean, "is not supported (every threshold's map would need its own pass); despeckle the maps of one "
+                                 "SegEvaluator per threshold (update_raw(clean=))"),
+                ("refine", refine, "is not supported (every threshold's map would need its own refinement); use one SegEvaluator "
+                                   "per threshold"),
+                ("aug", aug, "is not supported (the augmented path needs accumulators per threshold); use one SegEvaluator per "
+                             "threshold"))
         SegEvaluator._check_gts(raws, gts)
         return self._forward(_RawImages(raws, transform, net_sizes), gts, return_labels)
 

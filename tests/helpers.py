@@ -4,6 +4,7 @@ import os
 import numpy as np
 import torch
 
+import segclip_amd
 from segclip_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -61,3 +62,30 @@ def noise_items(noise, flags):
     if flags.get("use_vision_mae_recon"):
         items += [("rand", noise["mask_noise"]), ("gumbel", noise["gumbel_mae"])]
     return items
+
+
+def tiny_seg_model(dtype=torch.float32):
+    """The tiny synthetic model in eval mode on the GPU, at the compute dtype `dtype` (the caller restores the dtype)."""
+    segclip_amd.set_compute_dtype(dtype)
+    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device="cuda:0")
+    return model.eval()
+
+
+class CountedEncodeImage:
+    """The sizes (windows) of the encode_image calls of a model inside the block."""
+
+    def __init__(self, model):
+        self.model, self.calls = model, []
+
+    def __enter__(self):
+        real = self.model.clip.encode_image
+
+        def counted(*a, **k):
+            self.calls.append(a[0].shape[0])
+            return real(*a, **k)
+
+        self.model.clip.encode_image = counted
+        return self.calls
+
+    def __exit__(self, *exc):
+        del self.model.clip.encode_image

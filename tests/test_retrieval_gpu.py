@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 import torch
 
-import segclip_amd
 from segclip_amd import _lib as L
 from segclip_amd import ops, synth
 from segclip_amd.retrieval import RetrievalEvaluator, metrics_from_hist
 from segclip_amd.train import eval_retrieval_epoch
 from tests import retrieval_reference as rr
+from tests.helpers import tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -130,18 +130,12 @@ def test_nothing_synchronises_before_compute():
     assert ev.compute() == one.compute()
 
 
-def _tiny_model():
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def test_evaluator_end_to_end_on_the_tiny_model():
     """add_images / add_texts in uneven chunks (chunk = 5 over 13 images and 29 captions, the captions in two calls) against
     one add_embeddings call on the embeddings of get_visual_output / get_sequence_output over the same chunks."""
     spec = synth.SPECS["tiny"]
     Ni, Nt, chunk = 13, 29, 5
-    model = _tiny_model()
+    model = tiny_seg_model()
     images = synth.synthetic_batch(spec, Ni, seed=3, device=DEV)["image"]
     texts = synth.synthetic_batch(spec, Nt, seed=4, device=DEV)
     ids, seg, mask = texts["input_ids"], texts["segment_ids"], texts["input_mask"]
@@ -268,7 +262,7 @@ def test_refuses_cpu_tensors():
 
 
 def test_refuses_a_model_in_training_mode():
-    model = _tiny_model()
+    model = tiny_seg_model()
     batch = synth.synthetic_batch(synth.SPECS["tiny"], 2, seed=1, device=DEV)
     try:
         model.train()

@@ -13,13 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-import segclip_amd
 from segclip_amd import _lib as L
 from segclip_amd import ops, synth
 from segclip_amd.retrieval import RetrievalEvaluator, ZeroShotClassifier, search
 from segclip_amd.train import eval_retrieval_epoch
 from tests import retrieval_reference as rr
 from tests import retrieval_topk_reference as tr
+from tests.helpers import tiny_seg_model
 from tests.kernel_frames import Frame
 
 pytestmark = pytest.mark.gpu
@@ -150,12 +150,6 @@ def test_agrees_with_the_ranks_of_the_evaluation():
     assert ev._topk is None                                    # reset with the ranks
 
 
-def _tiny_model():
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _tiny_inputs(Ni=13, Nt=29):
     spec = synth.SPECS["tiny"]
     images = synth.synthetic_batch(spec, Ni, seed=3, device=DEV)["image"]
@@ -166,7 +160,7 @@ def _tiny_inputs(Ni=13, Nt=29):
 
 def test_nothing_synchronises():
     V, T, g = _dev(*rr.realistic_case(33, 333, 67, 512))
-    model = _tiny_model()
+    model = tiny_seg_model()
     images, ids, seg, mask, g_tiny = _tiny_inputs()
     labels = torch.arange(67, device=DEV) % 29
     tiny = RetrievalEvaluator(model, chunk=5)
@@ -220,7 +214,7 @@ def test_search_end_to_end_on_the_tiny_model():
     embeddings of get_sequence_output / get_visual_output over the same chunks; the epoch driver with topk."""
     spec = synth.SPECS["tiny"]
     Ni, Nt, chunk, k = 13, 29, 5, 5
-    model = _tiny_model()
+    model = tiny_seg_model()
     images, ids, seg, mask, g = _tiny_inputs(Ni, Nt)
     g_dev = torch.from_numpy(g).to(DEV)
     ev = RetrievalEvaluator(model, chunk=chunk)
@@ -283,7 +277,7 @@ def test_zero_shot_classifier_counts_exactly(classes, n):
 
 
 def test_zero_shot_classifier_on_the_tiny_model_and_a_bad_label():
-    model = _tiny_model()
+    model = tiny_seg_model()
     images, ids, seg, mask, _ = _tiny_inputs()
     with torch.no_grad():
         text = ops.L2NormFn.apply(model.get_sequence_output(ids[:7].reshape(7, -1), seg[:7].reshape(7, -1),
@@ -323,7 +317,7 @@ def test_refusals():
     with pytest.raises(TypeError, match="fp32"):
         ops.retrieval_topk(Q.double(), X.double(), 3)
 
-    model = _tiny_model()
+    model = tiny_seg_model()
     batch = synth.synthetic_batch(synth.SPECS["tiny"], 2, seed=1, device=DEV)
     ev = RetrievalEvaluator(model)
     ev.add_images(batch["image"])

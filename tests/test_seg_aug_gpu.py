@@ -23,14 +23,14 @@ import torch
 
 import segclip_amd
 from segclip_amd import _lib as L
-from segclip_amd import config, ops, synth
+from segclip_amd import config, ops
 from segclip_amd.segmentation import ImageTransform, SegEvaluator, SegInference, TestAug, preprocess
 from segclip_amd.train import eval_epoch
 from tests import seg_aug_reference as sar
 from tests import seg_eval_reference as ser
 from tests import seg_frontend_reference as sfr
 from tests import seg_reference as sr
-from tests.helpers import load_golden
+from tests.helpers import load_golden, tiny_seg_model
 from tests.test_seg_eval_gpu import _f32_tables, _dev_tables, _features, _soft, _synthetic_gt
 
 pytestmark = pytest.mark.gpu
@@ -324,12 +324,6 @@ def test_view_front_end():
 
 
 # ------------------------------------------------------------------------------------------------ 3. end to end
-def _tiny_model(dtype=torch.float32):
-    segclip_amd.set_compute_dtype(dtype)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 SLIDE = dict(mode="slide", crop_size=(128, 128), stride=(96, 96))
 TF_SMALL = ImageTransform(img_scale=(1024, 128))
 AUG = TestAug(img_ratios=(1.0, 1.5), flip=True)
@@ -356,7 +350,7 @@ def _e2e_reference(seg, views, out):
 def test_predict_raw_aug_end_to_end():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws = _raws()
         outs = [(h + 3, w - 2) for (h, w) in RAW_SIZES]
@@ -402,7 +396,7 @@ def test_update_raw_aug_and_eval_epoch():
     pixels move a class's I, P and L by at most n each, hence its IoU = I / U by at most 2 n / (U - n)."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         cfg = dict(bg_thresh=0.03, **SLIDE)
@@ -451,7 +445,7 @@ def test_update_aug_allocates_less_than_one_fp32_plane_per_image():
     """update_raw(aug=) on one image -> 375 x 500 with 21 classes and four views: the peak beyond the towers' own stays below
     one fp32 plane of the output: no (C, oh, ow) tensor and no per-view probability array exists."""
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         gen = torch.Generator().manual_seed(8)
         emb = torch.randn(20, 64, generator=gen)
         emb = (emb / emb.norm(dim=-1, keepdim=True)).to(DEV)
@@ -492,7 +486,7 @@ def test_update_aug_allocates_less_than_one_fp32_plane_per_image():
 def test_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True, **SLIDE)
         raw = _raws()[0]

@@ -17,7 +17,7 @@ from segclip_amd.train import eval_epoch
 from tests import boundary_reference as br
 from tests import kernel_frames as kf
 from tests import pamr_reference as pr
-from tests.helpers import load_golden
+from tests.helpers import CountedEncodeImage, load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -345,13 +345,6 @@ OLD_KEYS = {"mIoU", "aAcc", "mAcc", "IoU", "Acc"}
 NEW_KEYS = {"bIoU", "mbIoU", "trimap_IoU", "trimap_mIoU", "trimap_aAcc"}
 
 
-def _tiny_model():
-    from segclip_amd import synth
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _raws(seed):
     g = torch.Generator().manual_seed(seed)
     raws = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
@@ -362,30 +355,10 @@ def _raws(seed):
     return raws, gts
 
 
-class _Counted:
-    """The sizes of the encode_image calls inside the block."""
-
-    def __init__(self, model):
-        self.model, self.calls = model, []
-
-    def __enter__(self):
-        real = self.model.clip.encode_image
-
-        def counted(*a, **k):
-            self.calls.append(a[0].shape[0])
-            return real(*a, **k)
-
-        self.model.clip.encode_image = counted
-        return self.calls
-
-    def __exit__(self, *exc):
-        del self.model.clip.encode_image
-
-
 def test_end_to_end():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws, gts = _raws(11)
         seg = SegInference(model, emb, True, bg_thresh=0.02, **SLIDE)
@@ -405,9 +378,9 @@ def test_end_to_end():
             ev0 = SegEvaluator(seg, reduce_zero_label=True)
             ev = SegEvaluator(seg, reduce_zero_label=True, boundary=Boundary(radius=2))
             assert ev0.boundary_areas is None and tuple(ev.boundary_areas.shape) == (2, 3, C) and ev.boundary_areas.is_cuda
-            with _Counted(model) as plain_calls:
+            with CountedEncodeImage(model) as plain_calls:
                 assert path(ev0) is None
-            with _Counted(model) as calls:
+            with CountedEncodeImage(model) as calls:
                 labels = path(ev, return_labels=True)
             assert calls == plain_calls and len(calls) > 0, name
             assert [tuple(t.shape) for t in labels] == RAW_SIZES, name
@@ -415,7 +388,7 @@ def test_end_to_end():
             want = torch.from_numpy(br.areas([t.cpu().numpy() for t in labels], [t.cpu().numpy() for t in gts], [2] * 3, C, 255, True))
             assert torch.equal(ev.boundary_areas.cpu(), want) and int(want[0, 0].sum()) > 0 and int(want[1, 2].sum()) > 0, name
             # inside, the labels are kept even when the caller does not want them
-            with _Counted(model) as calls:
+            with CountedEncodeImage(model) as calls:
                 assert path(ev) is None
             assert calls == plain_calls, name
             assert torch.equal(ev.areas, 2 * ev0.areas) and torch.equal(ev.boundary_areas.cpu(), 2 * want), name
@@ -435,7 +408,7 @@ def test_end_to_end():
 def test_eval_epoch():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         b = Boundary(radius=3)

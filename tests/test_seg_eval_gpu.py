@@ -20,12 +20,12 @@ import torch
 
 import segclip_amd
 from segclip_amd import _lib as L
-from segclip_amd import config, ops, synth
+from segclip_amd import config, ops
 from segclip_amd.segmentation import SegEvaluator, SegInference
 from segclip_amd.train import eval_epoch
 from tests import seg_eval_reference as ser
 from tests import seg_reference as sr
-from tests.helpers import load_golden
+from tests.helpers import load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -244,12 +244,6 @@ def test_kernel_limits():
 
 
 # ------------------------------------------------------------------------------------------------ 3. end to end
-def _tiny_model(dtype=torch.float32):
-    segclip_amd.set_compute_dtype(dtype)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 SLIDE = dict(mode="slide", crop_size=(128, 128), stride=(96, 96))
 # network sizes: square, tall, wide, wide (mmcv test sizes of 300 x 300, 500 x 375, 375 x 500 and 281 x 500 images)
 RAGGED = [((224, 224), (300, 300)), ((299, 224), (500, 375)), ((224, 299), (375, 500)), ((224, 399), (281, 500))]
@@ -269,7 +263,7 @@ def _e2e_reference(seg, img, out):
 def test_ragged_list_end_to_end():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         imgs, outs = _ragged_images()
         seg = SegInference(model, emb, True, bg_thresh=0.03, **SLIDE)
@@ -334,7 +328,7 @@ def test_ragged_list_end_to_end():
 def test_predict_list_equals_predict_on_a_batch(mode):
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         gen = torch.Generator().manual_seed(5)
         kw = dict(mode="slide", crop_size=(64, 64), stride=(48, 40)) if mode == "slide" else {}
@@ -366,7 +360,7 @@ def test_against_reference_golden():
     stay below the cap)."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         for si, (H, W) in enumerate(g["sizes"].tolist()):
             image = torch.from_numpy(g[f"image_{si}"]).to(DEV)
@@ -390,7 +384,7 @@ def test_update_allocates_less_than_one_fp32_plane_per_image():
     """SegEvaluator.update on one 224 x 299 -> 375 x 500 image with 21 classes: the peak beyond the towers' own (encode_image
     on the stacked windows, the stack included) stays below one fp32 plane of the output: no (C, oh, ow) tensor exists."""
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         gen = torch.Generator().manual_seed(8)
         emb = torch.randn(20, 64, generator=gen)
         emb = (emb / emb.norm(dim=-1, keepdim=True)).to(DEV)
@@ -428,7 +422,7 @@ def test_update_allocates_less_than_one_fp32_plane_per_image():
 def test_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True, **SLIDE)
         img = torch.zeros(3, 160, 160, device=DEV)
@@ -468,7 +462,7 @@ def test_eval_epoch():
     exist, n such pixels move a class's I, P and L by at most n each, hence its IoU = I / U by at most 2 n / (U - n)."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         cfg = dict(bg_thresh=0.03, **SLIDE)

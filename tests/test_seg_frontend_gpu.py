@@ -15,11 +15,11 @@ import torch
 
 import segclip_amd
 from segclip_amd import _lib as L
-from segclip_amd import ops, synth
+from segclip_amd import ops
 from segclip_amd.segmentation import ImageTransform, SegEvaluator, SegInference, preprocess, slide_windows
 from segclip_amd.train import eval_epoch
 from tests import seg_frontend_reference as sfr
-from tests.helpers import load_golden
+from tests.helpers import CountedEncodeImage, load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -195,12 +195,6 @@ RAW_SIZES = [(300, 300), (500, 375), (375, 500), (281, 500)]
 NET_SIZES = [(224, 224), (299, 224), (224, 299), (224, 399)]
 
 
-def _tiny_model():
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _raws(seed=4):
     g = torch.Generator().manual_seed(seed)
     return [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
@@ -210,27 +204,10 @@ def _same(a, b):
     return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
 
 
-class _Counted:
-    """Counts the windows of every encode_image call of a model."""
-
-    def __init__(self, model):
-        self.model, self.calls, self.real = model, [], model.clip.encode_image
-
-    def __enter__(self):
-        def counted(*a, **k):
-            self.calls.append(a[0].shape[0])
-            return self.real(*a, **k)
-        self.model.clip.encode_image = counted
-        return self.calls
-
-    def __exit__(self, *exc):
-        del self.model.clip.encode_image
-
-
 def test_predict_raw_equals_predict_list_on_preprocessed():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws = _raws()
         outs = [(h + 3, w - 2) for (h, w) in RAW_SIZES]
@@ -241,7 +218,7 @@ def test_predict_raw_equals_predict_list_on_preprocessed():
             assert float((pre[i].cpu().double() - want).abs().max()) <= TOL
         seg = SegInference(model, emb, True, bg_thresh=0.03, **SLIDE)
         total = sum(len(slide_windows(H, W, SLIDE["crop_size"], SLIDE["stride"])) for (H, W) in NET_SIZES)
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             want = seg.predict_list(pre, outs)
             got = seg.predict_raw(raws, TF, outs)
             assert calls == [total, total]
@@ -263,7 +240,7 @@ def test_predict_raw_equals_predict_list_on_preprocessed():
         # whole mode: one tower call per distinct network size, sizes the tower takes
         nets = [(128, 128), (64, 64), (128, 128), (64, 64)]
         whole = SegInference(model, emb, True, bg_thresh=0.03)
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             got = whole.predict_raw(raws, TF, outs, net_sizes=nets)
             assert calls == [2, 2]
         pre_w = preprocess(raws, TF, net_sizes=nets)
@@ -276,7 +253,7 @@ def test_predict_raw_equals_predict_list_on_preprocessed():
 def test_update_raw_and_eval_epoch():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         tokens = torch.from_numpy(g["prompt_ids"])
         raws = _raws(seed=6)
@@ -315,7 +292,7 @@ def test_update_raw_and_eval_epoch():
 def test_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True, **SLIDE)
         ev = SegEvaluator(seg)

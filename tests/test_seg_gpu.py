@@ -21,10 +21,10 @@ import torch
 
 import segclip_amd
 from segclip_amd import _lib as L
-from segclip_amd import ops, synth
+from segclip_amd import ops
 from segclip_amd.segmentation import SegInference, build_text_embedding
 from tests import seg_reference as sr
-from tests.helpers import load_golden
+from tests.helpers import load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -242,12 +242,6 @@ def test_slide_geometry(H, W, stride):
 
 
 # ------------------------------------------------------------------------------------------------ 3. end to end
-def _tiny_model(dtype=torch.float32):
-    segclip_amd.set_compute_dtype(dtype)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 # label agreement of the bf16 towers with the exact-f32 run, tiny model, golden images, 12 classes + background: measured
 # on an MI355X: 1.0 (128 x 128) and 0.99963 (256 x 64); floor = the smaller measurement - 10 %
 BF16_AGREEMENT_MEASURED = 0.99963
@@ -261,7 +255,7 @@ def test_end_to_end_against_reference_golden():
     the arg-max of this build's encode_decode exactly; build_text_embedding to 1e-4."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = build_text_embedding(model, torch.from_numpy(g["prompt_ids"]).to(DEV), chunk=7)
         assert float((emb.cpu() - torch.from_numpy(g["text_embedding"])).abs().max()) <= 1e-4
         for si, (H, W) in enumerate(g["sizes"].tolist()):
@@ -298,7 +292,7 @@ def test_bf16_towers_label_agreement():
             image = torch.from_numpy(g[f"image_{si}"]).to(DEV)
             labels = {}
             for dtype in (torch.float32, torch.bfloat16):
-                model = _tiny_model(dtype)
+                model = tiny_seg_model(dtype)
                 seg = SegInference(model, torch.from_numpy(g["text_embedding"]).to(DEV), True, bg_thresh=0.03)
                 labels[dtype] = seg.predict(image).cpu()
             agree.append(float((labels[torch.float32] == labels[torch.bfloat16]).float().mean()))
@@ -314,7 +308,7 @@ def test_batching_and_chunking_invariance(mode):
     """predict of B images in one call == B calls of one image == any max_windows chunking, bit for bit (exact-f32 mode)."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         gen = torch.Generator().manual_seed(5)
         kw = dict(mode="slide", crop_size=(64, 64), stride=(48, 40)) if mode == "slide" else {}
@@ -340,7 +334,7 @@ def test_remembered_plan_serves_only_its_own_call_shape(mode):
     predict_list of a's images straight after (the same sizes: the remembered plan serves it) equals a fresh object's."""
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         gen = torch.Generator().manual_seed(11)
         kw = dict(mode="slide", crop_size=(64, 64), stride=(48, 40)) if mode == "slide" else {}
@@ -369,7 +363,7 @@ def test_remembered_plan_serves_only_its_own_call_shape(mode):
 def test_interface_errors_and_wide_class_lists():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True)
         with pytest.raises(RuntimeError, match="no CPU fallback"):
@@ -397,7 +391,7 @@ def test_predict_allocates_less_than_one_fp32_plane_per_image():
     from segclip_amd import config
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         gen = torch.Generator().manual_seed(8)
         image = torch.randn(4, 3, 128, 128, generator=gen).to(DEV)

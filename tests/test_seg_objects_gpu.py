@@ -17,7 +17,7 @@ from segclip_amd.segmentation import (PAMR, Despeckle, ImageTransform, Objects, 
 from segclip_amd.train import eval_epoch
 from tests import cc_reference as cc
 from tests import kernel_frames as kf
-from tests.helpers import load_golden
+from tests.helpers import load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -371,13 +371,6 @@ SLIDE = dict(mode="slide", crop_size=(128, 128), stride=(96, 96))
 RAW_SIZES = [(90, 120), (130, 101), (75, 75)]
 
 
-def _tiny_model():
-    from segclip_amd import synth
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _raws(seed):
     g = torch.Generator().manual_seed(seed)
     raws = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
@@ -401,7 +394,7 @@ def _eq(a, b):
 def test_end_to_end():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws, gts = _raws(11)
         seg = SegInference(model, emb, True, bg_thresh=0.02, **SLIDE)
@@ -446,7 +439,7 @@ def test_end_to_end():
 def test_eval_epoch_and_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         d = Despeckle(6, fill=0)

@@ -23,7 +23,7 @@ from segclip_amd.segmentation import PAMR, ImageTransform, SegEvaluator, SegInfe
 from segclip_amd.train import eval_epoch
 from tests import kernel_frames as kf
 from tests import pamr_reference as pr
-from tests.helpers import load_golden
+from tests.helpers import CountedEncodeImage, load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -396,13 +396,6 @@ RAW_SIZES = [(90, 120), (130, 101), (75, 75)]
 NETS = [(128, 128), (64, 64), (128, 128)]
 
 
-def _tiny_model():
-    from segclip_amd import synth
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _raws(seed):
     g = torch.Generator().manual_seed(seed)
     raws = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
@@ -412,31 +405,11 @@ def _raws(seed):
     return raws, gts
 
 
-class _Counted:
-    """The sizes of the encode_image calls inside the block."""
-
-    def __init__(self, model):
-        self.model, self.calls = model, []
-
-    def __enter__(self):
-        real = self.model.clip.encode_image
-
-        def counted(*a, **k):
-            self.calls.append(a[0].shape[0])
-            return real(*a, **k)
-
-        self.model.clip.encode_image = counted
-        return self.calls
-
-    def __exit__(self, *exc):
-        del self.model.clip.encode_image
-
-
 @pytest.mark.parametrize("mode", ["slide", "whole", "slide_aug"])
 def test_end_to_end(mode):
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws, gts = _raws(11)
         kw = {} if mode == "whole" else dict(SLIDE)
@@ -444,13 +417,13 @@ def test_end_to_end(mode):
         aug = TestAug(flip=True) if mode == "slide_aug" else None
         pamr = PAMR(iters=3, dilations=(1, 2))
         seg = SegInference(model, emb, True, bg_thresh=0.02, **kw)
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             plain = seg.predict_raw(raws, TF, net_sizes=nets, aug=aug)
             plain_calls = list(calls)
         keep = [p.clone() for p in plain]
         want = refine_labels(raws, plain, seg.num_classes, TF, pamr)
         assert all(torch.equal(a, b) for a, b in zip(plain, keep)), "refine_labels changed its input"
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             got = seg.predict_raw(raws, TF, net_sizes=nets, aug=aug, refine=pamr, out_shapes=RAW_SIZES)
             assert list(calls) == plain_calls, "the refinement changes the tower calls"
         assert [tuple(t.shape) for t in got] == RAW_SIZES and all(t.dtype == torch.uint8 for t in got)
@@ -462,7 +435,7 @@ def test_end_to_end(mode):
             assert torch.equal(w.cpu()[firm], l64[firm])
         # the evaluator: the areas of the refined maps, once
         ev = SegEvaluator(seg, reduce_zero_label=True)
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             maps = ev.update_raw(raws, gts, TF, return_labels=True, net_sizes=nets, aug=aug, refine=pamr)
             assert list(calls) == plain_calls
         assert all(torch.equal(a, b) for a, b in zip(maps, want))
@@ -479,7 +452,7 @@ def test_end_to_end(mode):
 def test_eval_epoch_and_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         pamr = PAMR(iters=2, dilations=(1, 2))

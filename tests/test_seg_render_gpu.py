@@ -16,10 +16,10 @@ import torch
 
 import segclip_amd
 from segclip_amd import _lib as L
-from segclip_amd import ops, synth
+from segclip_amd import ops
 from segclip_amd.segmentation import (ImageTransform, SegInference, anchors_from_sums, blend, default_group_palette)
 from tests import seg_render_reference as rr
-from tests.helpers import load_golden
+from tests.helpers import CountedEncodeImage, load_golden, tiny_seg_model
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -284,12 +284,6 @@ RAW_SIZES = [(150, 200), (97, 61), (200, 150)]
 NETS = [(128, 128), (64, 64), (128, 128)]
 
 
-def _tiny_model():
-    segclip_amd.set_compute_dtype(torch.float32)
-    model, _ = synth.build_model(synth.SPECS["tiny"], {}, device=DEV)
-    return model.eval()
-
-
 def _raws(seed=4):
     g = torch.Generator().manual_seed(seed)
     return [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8).to(DEV) for (h, w) in RAW_SIZES]
@@ -299,27 +293,10 @@ def _same(a, b):
     return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
 
 
-class _Counted:
-    """Counts the windows of every encode_image call of a model."""
-
-    def __init__(self, model):
-        self.model, self.calls, self.real = model, [], model.clip.encode_image
-
-    def __enter__(self):
-        def counted(*a, **k):
-            self.calls.append(a[0].shape[0])
-            return self.real(*a, **k)
-        self.model.clip.encode_image = counted
-        return self.calls
-
-    def __exit__(self, *exc):
-        del self.model.clip.encode_image
-
-
 def test_groups_list_identity():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True, bg_thresh=0.03)
         img = torch.randn(3, 3, 128, 128, generator=torch.Generator().manual_seed(8)).to(DEV)
@@ -347,13 +324,13 @@ def test_groups_list_identity():
 def test_render_raw_end_to_end():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws = _raws()
         seg = SegInference(model, emb, True, bg_thresh=0.03)
         pal = torch.randint(0, 256, (seg.num_classes, 3), generator=torch.Generator().manual_seed(5), dtype=torch.uint8)
         modes = ["input", "pred", "input_pred", "input_pred_label", "all_groups", "first_group", "final_group"]
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             labels = seg.predict_raw(raws, TF, net_sizes=NETS)
             alone = list(calls)
             del calls[:]
@@ -392,7 +369,7 @@ def test_render_raw_end_to_end():
             assert np.array_equal(res["final_group"][i].cpu().numpy(),
                                   rr.blend(raw.cpu().numpy(), gmaps[i].cpu().numpy(), own[:8].numpy(), 0.6, reverse_channels=True))
         # only the input: no tower call at all
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             assert _same(seg.render_raw(raws, TF, ["input"], pal, net_sizes=NETS)["input"], raws) and calls == []
         with pytest.raises(ValueError, match="unknown vis mode"):
             seg.render_raw(raws, TF, ["input", "groups"], pal, net_sizes=NETS)

@@ -17,9 +17,9 @@ from segclip_amd import ops
 from segclip_amd.segmentation import ImageTransform, SegEvaluator, SegInference, SegSweepEvaluator, TestAug
 from segclip_amd.train import sweep_bg_thresh
 from tests import kernel_frames as kf
-from tests.helpers import load_golden
+from tests.helpers import CountedEncodeImage, load_golden, tiny_seg_model
 from tests.test_seg_eval_gpu import (CAP, G, NEAR_TIE_COUNTS, SLIDE, TIE, _case, _dev_tables, _f32_tables, _image_rows,
-                                     _reference, _synthetic_gt, _tiny_model)
+                                     _reference, _synthetic_gt)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -279,26 +279,6 @@ def _raws(seed):
     return raws, gts
 
 
-class _Counted:
-    """The sizes of the encode_image calls inside the block."""
-
-    def __init__(self, model):
-        self.model, self.calls = model, []
-
-    def __enter__(self):
-        real = self.model.clip.encode_image
-
-        def counted(*a, **k):
-            self.calls.append(a[0].shape[0])
-            return real(*a, **k)
-
-        self.model.clip.encode_image = counted
-        return self.calls
-
-    def __exit__(self, *exc):
-        del self.model.clip.encode_image
-
-
 def _peak(fn):
     fn()
     torch.cuda.synchronize()
@@ -315,7 +295,7 @@ def _peak(fn):
 def test_evaluator_end_to_end(mode):
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         raws, gts = _raws(6)
         kw = dict(SLIDE) if mode == "slide" else {}
@@ -324,7 +304,7 @@ def test_evaluator_end_to_end(mode):
         # seg.bg_thresh is ignored by the sweep: any value
         sweep = SegSweepEvaluator(SegInference(model, emb, True, bg_thresh=0.77, **kw), E2E_THR)
         assert tuple(sweep.areas.shape) == (T, 3, sweep.seg.num_classes) and sweep.areas.is_cuda
-        with _Counted(model) as calls:
+        with CountedEncodeImage(model) as calls:
             planes = sweep.update_raw(raws, gts, TF, return_labels=True, net_sizes=nets)
             sweep_calls = list(calls)
         assert [tuple(p.shape) for p in planes] == [(T, h, w) for (h, w) in RAW_SIZES] and all(p.dtype == torch.uint8 for p in planes)
@@ -332,7 +312,7 @@ def test_evaluator_end_to_end(mode):
         for t, thr in enumerate(E2E_THR):
             seg = SegInference(model, emb, True, bg_thresh=thr, **kw)
             ev = SegEvaluator(seg)
-            with _Counted(model) as calls:
+            with CountedEncodeImage(model) as calls:
                 ev.update_raw(raws, gts, TF, net_sizes=nets)
                 assert list(calls) == sweep_calls, "the sweep does not call the tower as one single evaluation does"
             assert torch.equal(sweep.areas[t], ev.areas), f"{mode}: areas slice {t} (bg_thresh {thr}) differs"
@@ -371,7 +351,7 @@ def test_evaluator_end_to_end(mode):
 def test_train_sweep_bg_thresh():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         tokens = torch.from_numpy(g["prompt_ids"])
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         thr = E2E_THR + [3.0]   # 2.0 and 3.0 lie above every table_max: equal slices
@@ -409,7 +389,7 @@ def test_train_sweep_bg_thresh():
 def test_interface_errors():
     g = load_golden("seg_tiny.npz")
     try:
-        model = _tiny_model()
+        model = tiny_seg_model()
         emb = torch.from_numpy(g["text_embedding"]).to(DEV)
         seg = SegInference(model, emb, True, **SLIDE)
         for bad, match in (([0.5, 0.4], "thresholds.*sorted"), ([0.4, 0.4], "thresholds.*duplicate"),

@@ -706,10 +706,10 @@ class _AllOutputs:
     """segclip_seg_components with every output on a list of label maps: buffers and table made once, call() enqueues only."""
 
     def __init__(self, maps, connectivity=8, min_area=16):
-        from segclip_amd.segmentation import _flat_maps
-        self.flat, offs = _flat_maps(list(maps))
-        n = self.flat.numel()
-        self.table, self.n_blocks, self.side = ops.seg_components_table([tuple(m.shape) for m in maps], offs, "cuda")
+        from segclip_amd.segmentation import _Maps
+        batch = _Maps.of(maps)
+        self.flat, n = batch.flat, batch.flat.numel()
+        self.table, self.n_blocks, self.side = ops.seg_components_table(batch.sizes, batch.offs, "cuda")
         self.ids, self.area = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
         self.records = torch.empty(n, ops.SEG_CC_RECORD, dtype=torch.int64, device="cuda")   # room for one component per pixel
         self.count = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -832,16 +832,12 @@ class _BoundaryCall:
     """segclip_seg_boundary on a list of label maps and ground truths, the outputs allocated once."""
 
     def __init__(self, maps, gts, C, boundary, bands):
-        from segclip_amd.segmentation import _flat_gts, _flat_maps
-        self.flat, offs = _flat_maps(list(maps))
-        self.gt = _flat_gts(list(gts))
-        sizes = [tuple(m.shape) for m in maps]
-        gt_offs, n = [], 0
-        for g in gts:
-            gt_offs.append(n)
-            n += g.numel()
-        self.radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(sizes)]
-        self.table, self.n_blocks, self.side = ops.seg_boundary_table(sizes, offs, gt_offs, self.radii, "cuda")
+        from segclip_amd.segmentation import _Maps
+        batch = _Maps.of(maps)
+        self.flat = batch.flat
+        self.gt, gt_offs = _Maps.gapless_of(list(gts))
+        self.radii = [boundary.radius_of(h, w, i) for i, (h, w) in enumerate(batch.sizes)]
+        self.table, self.n_blocks, self.side = ops.seg_boundary_table(batch.sizes, batch.offs, gt_offs, self.radii, "cuda")
         self.areas = torch.zeros(2, 3, C, dtype=torch.int64, device="cuda")
         self.pred_band = torch.zeros_like(self.flat) if bands else None
         self.gt_band = torch.zeros_like(self.gt) if bands else None
