@@ -494,6 +494,44 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
                       int64_t* areas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 16-bit label maps (segment_wide.inc): the two entries above for vocabularies of up to 1024 classes, such as
+ * Pascal-Context-459 (460 classes with the background) and ADE20K-847 (848), without the dense (C, H, W) logits.
+ *
+ * segclip_seg_label_map_rescaled_wide: the arguments, the (B, 16) image table, the tile of 1024 output pixels, the definition
+ * of a label and the ground-truth rule of segclip_seg_label_map_rescaled.  Below 257 classes its labels and areas equal that
+ * entry's, value for value: the per-class value is formed by the same fp32 operations in the same order.
+ *   labels    : flat uint16 of labels_elems ELEMENTS, or NULL.  Columns 6 (label offset) and 7 (ground-truth offset) of
+ *               `images` count elements.  A lane's four labels are one 8-byte store where the address is a multiple of 8 (a
+ *               label offset that is a multiple of 4 on a base aligned to 8), 2-byte stores otherwise.
+ *   gt, areas : flat uint16 of gt_elems ELEMENTS and (3, N + with_bg) int64, or both NULL.  A ground-truth element is read as an
+ *               UNSIGNED 16-bit value g, and ignore_index is compared with that value: an ignore_index outside 0 .. 65535
+ *               ignores nothing.  reduce_zero_label and g >= the class count as above.  Integer counters, 3 x 1024 per
+ *               workgroup in LDS, one global add per touched counter: the sums do not depend on order.
+ *   How.  A pixel whose four taps have one covering window and one group takes the label staged per (window, group), per lane.
+ *   Every other pixel - taps that disagree, or several covering windows - is resolved by its wave: the owner's tap weights and
+ *   cover lists are broadcast, lane l evaluates the classes l, l + 64, ... (a table row is read as consecutive floats by
+ *   consecutive lanes) and a shuffle reduction takes the maximum, among equal values the lowest class = the first maximum.
+ *   Up to 32 classes every lane scans the classes of its own pixel instead, as the uint8 entry does (measured faster there).
+ *   Every entry of `images` is range-checked on the device against soft_floats, labels_elems and gt_elems; an image whose row
+ *   is inconsistent is skipped.  What exceeds the device-side lists is SILENTLY IGNORED as above: at most 64 windows per
+ *   image, at most 16 windows covering one pixel.  G <= 8.  H, W, oh, ow < 2^30 and oh * ow < 2^31.
+ *   LDS: 14.5 KiB static + at most 48 KiB dynamic (no table copy where G * N > 4096: the global table is read).
+ *   Bound: the class scan of the undecided pixels, (covering windows x taps) x (N + with_bg) table reads each, from L2;
+ *   2 bytes of HBM writes per pixel.  Measured: profiles/seg_wide.txt.
+ * SEGCLIP_ERR_UNSUPPORTED (no launch): N + with_bg > 1024, max_image_windows > 64.
+ *
+ * segclip_seg_areas_wide: segclip_seg_areas for n uint16 elements.  SEGCLIP_ERR_UNSUPPORTED: C > 1024.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_label_map_rescaled_wide(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                        const int32_t* best_class, const float* best_score, const int32_t* windows,
+                                        const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
+                                        int64_t max_image_windows, int64_t G, int64_t N, int with_bg, float bg_thresh,
+                                        uint16_t* labels, int64_t labels_elems, const uint16_t* gt, int64_t gt_elems,
+                                        int ignore_index, int reduce_zero_label, int64_t* areas, void* stream);
+int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, int64_t C, int ignore_index,
+                           int reduce_zero_label, int64_t* areas, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Background-threshold sweep (segment_sweep.inc): segclip_seg_label_map_rescaled for T values of bg_thresh in ONE launch, for
  * tuning the one hyperparameter of the zero-shot evaluation (the reference's configurations use 0.80, 0.25 and 0.65:
  * the dataset files of seg_segmentation/configs/_base_/datasets, test_cfg) without repeating towers, front end and group tables per value.

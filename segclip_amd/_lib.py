@@ -174,6 +174,9 @@ SIGNATURES = {
     "segclip_seg_view_probs": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
                                          vp, i64, vp]),
     "segclip_seg_areas": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_label_map_rescaled_wide": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
+                                                      vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_areas_wide": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
     "segclip_seg_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
     "segclip_seg_view_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
     "segclip_seg_groups_rescaled": (C.c_int, [vp, i64, vp, i64, i64, i64, vp, i64, vp]),

@@ -9,7 +9,8 @@
 // The .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
-// (segment_refine.inc), their connected components (segment_objects.inc) and the training front end (train_frontend.inc).
+// (segment_refine.inc), their connected components (segment_objects.inc), the training front end (train_frontend.inc) and the
+// 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc).
 #include "common.h"
 
 #include <atomic>
@@ -298,6 +299,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 }
 
 #include "segment_eval.inc"
+#include "segment_wide.inc"
 #include "segment_sweep.inc"
 #include "segment_aug.inc"
 #include "segment_frontend.inc"
@@ -635,6 +637,70 @@ extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t
   hipLaunchKernelGGL(seg_areas_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
                      reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(areas));
   SEGCLIP_CHECK_LAUNCH("seg_areas");
+  return 0;
+}
+
+extern "C" int segclip_seg_label_map_rescaled_wide(const float* soft_attn, int64_t soft_floats, const float* table,
+                                                   const float* table_max, const int32_t* best_class, const float* best_score,
+                                                   const int32_t* windows, const int64_t* images, int64_t n_windows, int64_t B,
+                                                   int64_t n_blocks, int64_t max_image_windows, int64_t G, int64_t N, int with_bg,
+                                                   float bg_thresh, uint16_t* labels, int64_t labels_elems, const uint16_t* gt,
+                                                   int64_t gt_elems, int ignore_index, int reduce_zero_label, int64_t* areas,
+                                                   void* stream) {
+  const char* what = "seg_label_map_rescaled_wide";
+  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_elems >= 0 && gt_elems >= 0,
+                  "%s: sizes must not be negative, N >= 1", what);
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
+  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
+  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
+  const int64_t C = N + (with_bg ? 1 : 0);
+  if (C > SEG_WIDE_MAX_CLASSES) {
+    segclip_set_error("%s: %lld classes, at most %d (uint16 labels, per-class counters in LDS)", what, (long long)C,
+                      SEG_WIDE_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (max_image_windows > SEG_MAX_IMG_WIN) {
+    segclip_set_error("%s: %lld windows per image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (B == 0 || n_blocks == 0) return 0;
+  SegWideArgs s;
+  SegEvalArgs& a = s.e;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
+  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_elems; a.gt_bytes = gt_elems;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
+  a.labels = nullptr; a.gt = nullptr; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  s.labels = labels; s.gt = gt;
+  // LDS as in segclip_seg_label_map_rescaled, except that a table copy no single window fits (G * N > the copy) is not asked
+  // for: the kernel reads the global table then, and the workgroup stays at three per CU beside its 14.5 KiB of static LDS
+  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
+  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
+  int64_t want = per_image * G * N;
+  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
+  if (G * N > SEG_EVAL_TAB_FLOATS) want = 0;
+  a.tab_floats = (int)((want + 1) & ~1ll);
+  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
+  SEGCLIP_REQUIRE(lds <= 48 * 1024, "%s: internal LDS plan of %lld bytes", what, (long long)lds);  // + 14.5 KiB static <= 64 KiB
+  hipLaunchKernelGGL(seg_rescaled_wide_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, s);
+  SEGCLIP_CHECK_LAUNCH(what);
+  return 0;
+}
+
+extern "C" int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, int64_t C, int ignore_index,
+                                      int reduce_zero_label, int64_t* areas, void* stream) {
+  SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "seg_areas_wide: need 0 <= n <= 2^40 and C >= 1");
+  SEGCLIP_REQUIRE(n == 0 || (pred && gt && areas), "seg_areas_wide: pred, gt and areas are required");
+  if (C > SEG_WIDE_MAX_CLASSES) {
+    segclip_set_error("seg_areas_wide: %lld classes, at most %d", (long long)C, SEG_WIDE_MAX_CLASSES);
+    return SEGCLIP_ERR_UNSUPPORTED;
+  }
+  if (n == 0) return 0;
+  const int64_t blocks = cdiv(n, SEG_EVAL_TILE) < 1024 ? cdiv(n, SEG_EVAL_TILE) : 1024;
+  hipLaunchKernelGGL(seg_areas_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
+                     reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(areas));
+  SEGCLIP_CHECK_LAUNCH("seg_areas_wide");
   return 0;
 }
 

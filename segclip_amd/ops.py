@@ -2411,6 +2411,16 @@ SEG_IMAGE_COLS = 16   # int64 columns of one row of the image table of segclip_s
 SEG_EVAL_TILE = 1024  # output pixels of one of its workgroups
 
 
+def _upload_table(rows, dtype, device):
+    """A host-built descriptor table -> the device, through pinned memory: the copy is enqueued on the current stream and the
+    host does not wait for the device (a copy from pageable memory waits for the stream, and with it for everything enqueued
+    before).  torch's host allocator keeps the pinned block until the copy has run."""
+    table = torch.tensor(rows, dtype=dtype)
+    if torch.device(device).type != "cuda":   # the table builders also run without a device (their layout is tested there)
+        return table.to(device)
+    return table.pin_memory().to(device, non_blocking=True)
+
+
 def _seg_image_row(what, r, out, label_off, gt_off, first_block, flags=0):
     """One row of the 16-column image table: of an image (seg_image_table) or of one of its views (seg_view_tables), which
     carries its image's output size, label offset, ground-truth offset and first workgroup."""
@@ -2432,7 +2442,7 @@ def seg_image_table(rows, device):
         lab += (oh * ow + 3) // 4 * 4
         blk += (oh * ow + SEG_EVAL_TILE - 1) // SEG_EVAL_TILE
         most = max(most, r["count"])
-    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_IMAGE_COLS), offs, lab, blk, most
+    return _upload_table(tab, torch.int64, device).view(-1, SEG_IMAGE_COLS), offs, lab, blk, most
 
 
 def _seg_fused_args(what, soft_attn, tables, windows, images, views=None):
@@ -2453,13 +2463,13 @@ def _seg_fused_args(what, soft_attn, tables, windows, images, views=None):
     return tuple(t.contiguous() for t in (soft_attn, table, tmax, *ints, bsc, windows, *tabs)), (nW, G, N)
 
 
-def _seg_check_outputs(what, labels, gt, areas, n_classes, T=None):
+def _seg_check_outputs(what, labels, gt, areas, n_classes, T=None, dtype=torch.uint8):
     """`labels` / `gt` / `areas` of the fused label-map kernels and of seg_refine; T: the sweep's leading dimension of
-    `labels` and `areas`, one plane per threshold."""
+    `labels` and `areas`, one plane per threshold; dtype: of the label maps (torch.int16 for the wide entries)."""
     L.require_cuda(labels, gt, areas)
     for name, t in (("labels", labels), ("gt", gt)):
-        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
-            raise ValueError(f"{what}: {name} is a contiguous uint8 tensor")
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} is a contiguous {str(dtype).split('.')[-1]} tensor")
     if T is not None and labels is not None and (labels.dim() != 2 or labels.shape[0] != T):
         raise ValueError(f"{what}: labels is a (T, labels_bytes) uint8 tensor, one plane per threshold")
     if (gt is None) != (areas is None):
@@ -2481,6 +2491,25 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
         G, N, int(bool(with_bg)), float(bg_thresh), L.ptr(labels), labels.numel() if labels is not None else 0, L.ptr(gt),
         gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(areas), L.stream()),
         "seg_label_map_rescaled")
+    return labels
+
+
+SEG_WIDE_MAX_CLASSES = 1024   # classes (background included) of the 16-bit label maps: segclip_seg_label_map_rescaled_wide
+
+
+def seg_label_map_rescaled_wide(soft_attn, tables, windows, images, n_blocks, max_image_windows, with_bg, bg_thresh, labels=None,
+                                gt=None, areas=None, ignore_index=255, reduce_zero_label=False):
+    """seg_label_map_rescaled for up to SEG_WIDE_MAX_CLASSES classes (segclip_seg_label_map_rescaled_wide): `labels` and `gt`
+    are flat contiguous torch.int16 tensors whose elements the kernel reads and writes as unsigned 16-bit values (a uint16
+    array goes in as .view(torch.int16)), the offsets of the image table count elements, `areas` is (3, C) int64 and
+    ignore_index an integer compared with the unsigned value."""
+    keep, (nW, G, N) = _seg_fused_args("seg_label_map_rescaled_wide", soft_attn, tables, windows, images)
+    _seg_check_outputs("seg_label_map_rescaled_wide", labels, gt, areas, N + int(bool(with_bg)), dtype=torch.int16)
+    L.check(L.load().segclip_seg_label_map_rescaled_wide(
+        L.ptr(keep[0]), keep[0].numel(), *(L.ptr(t) for t in keep[1:]), nW, images.shape[0], int(n_blocks), int(max_image_windows),
+        G, N, int(bool(with_bg)), float(bg_thresh), L.ptr(labels), labels.numel() if labels is not None else 0, L.ptr(gt),
+        gt.numel() if gt is not None else 0, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(areas), L.stream()),
+        "seg_label_map_rescaled_wide")
     return labels
 
 
@@ -2599,6 +2628,22 @@ def seg_areas(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, 
     return areas
 
 
+def seg_areas_wide(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, areas=None):
+    """seg_areas for 16-bit label maps (segclip_seg_areas_wide): pred and gt are torch.int16 tensors read as unsigned 16-bit
+    values, at most SEG_WIDE_MAX_CLASSES classes -> (3, C) int64; added to `areas` when given."""
+    L.require_cuda(pred, gt, areas)
+    if pred.dtype != torch.int16 or gt.dtype != torch.int16 or pred.numel() != gt.numel():
+        raise ValueError("seg_areas_wide: pred and gt are int16 tensors of the same size")
+    if areas is None:
+        areas = torch.zeros(3, num_classes, dtype=torch.int64, device=pred.device)
+    elif areas.dtype != torch.int64 or not areas.is_contiguous() or tuple(areas.shape) != (3, num_classes):
+        raise ValueError("seg_areas_wide: areas is a contiguous (3, C) int64 tensor")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    L.check(L.load().segclip_seg_areas_wide(L.ptr(pred), L.ptr(gt), pred.numel(), int(num_classes), int(ignore_index),
+                                            int(bool(reduce_zero_label)), L.ptr(areas), L.stream()), "seg_areas_wide")
+    return areas
+
+
 SEG_SOURCE_COLS = 6         # int64 columns of one row of the source table of segclip_seg_windows_from_u8
 SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 
@@ -2658,7 +2703,7 @@ def seg_view_source_table(raws, net_sizes, flags):
         if min(int(H), int(W)) < 1 or max(int(H), int(W)) >= SEG_SOURCE_LIMIT:
             raise ValueError(f"seg_windows_from_u8: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w} -> {H}x{W}")
         tab.append([ptr, h, w, row, int(H), int(W)] + ([] if flags is None else [int(flags[k])]))
-    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(len(tab), -1)
+    return _upload_table(tab, torch.int64, raws[0].device).view(len(tab), -1)
 
 
 def seg_source_table(raws, net_sizes):

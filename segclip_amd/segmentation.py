@@ -54,6 +54,12 @@ and SegEvaluator(boundary=) scores the labels of every update path against the g
 (csrc/segment_boundary.inc), without a host synchronisation; compute() adds bIoU, mbIoU, trimap_IoU, trimap_mIoU and
 trimap_aAcc.  Not covered: SegSweepEvaluator and render_raw.
 
+Wide vocabularies (the reference evaluates VOC, Context-59 and COCO-80; open-vocabulary work also reports Pascal-Context-459
+and ADE20K-847): SegInference(label_dtype=torch.int16) writes 16-bit label maps for up to 1024 classes and SegEvaluator over it
+scores int16 ground truths (csrc/segment_wide.inc: 3 x 1024 counters per workgroup, and the pixels that need a scan over the
+classes are resolved by their wave, 64 classes at a time).  The uint8 path is unchanged and stays the default.  Not covered for
+16-bit maps: test-time augmentation, the threshold sweep, refinement, components, boundary metrics and render_raw.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -371,8 +377,9 @@ def _check_maps(maps, noun="a label map", sizes=None):
 
 
 class _Maps:
-    """A list of (h_i, w_i) maps in one flat buffer: map i is the h_i * w_i elements of `flat` from offs[i], sizes[i] =
-    (h_i, w_i).  The kernels take `flat` and a table of the offsets; between two maps there may be bytes that belong to none
+    """A list of (h_i, w_i) maps of one element type (uint8 labels, groups and bands; int16 labels of the wide path) in one flat
+    buffer: map i is the h_i * w_i elements of `flat` from offs[i], sizes[i] = (h_i, w_i); offsets count elements.  The kernels
+    take `flat` and a table of the offsets; between two maps there may be elements that belong to none
     (the label kernels start every map at a multiple of 4), and what follows a kernel in the chain reads them as they are: an
     output that is passed on has them zeroed (empty_like)."""
 
@@ -381,7 +388,7 @@ class _Maps:
 
     @classmethod
     def of(cls, maps):
-        """A list of uint8 maps -> their batch.  Contiguous views of one storage (what predict_raw and groups_raw return) are used where
+        """A list of maps of one dtype -> their batch.  Contiguous views of one storage (what predict_raw and groups_raw return) are used where
         they lie, without a copy; anything else is copied into a new zeroed buffer at offsets that are multiples of 4."""
         sizes = [tuple(m.shape) for m in maps]
         store = maps[0].untyped_storage().data_ptr()
@@ -390,7 +397,7 @@ class _Maps:
             hi = max(m.storage_offset() + m.numel() for m in maps)
             return cls(torch.as_strided(maps[0], (hi - lo,), (1,), lo), [m.storage_offset() - lo for m in maps], sizes)
         offs, n = cls._running([(m.numel() + 3) // 4 * 4 for m in maps])
-        new = cls(torch.zeros(n, dtype=torch.uint8, device=maps[0].device), offs, sizes)
+        new = cls(torch.zeros(n, dtype=maps[0].dtype, device=maps[0].device), offs, sizes)
         for v, m in zip(new.views(), maps):
             v.copy_(m)
         return new
@@ -706,12 +713,24 @@ class SegInference:
 
     mode="whole": H and W multiples of the patch size, one window per image.  mode="slide": any H, W >= crop, mmseg's
     window grid; overlapping windows average their logits.  All windows of all images of a call go through one
-    encode_image call (at most `max_windows` at a time)."""
+    encode_image call (at most `max_windows` at a time).
+
+    label_dtype=torch.int16: vocabularies of up to 1024 classes (Pascal-Context-459, ADE20K-847) without the dense logits.
+    predict, predict_list and predict_raw then return int16 maps (csrc/segment_wide.inc; below 257 classes they hold the values
+    of the uint8 maps), and a SegEvaluator over it takes int16 ground truths.  group_map, groups_list, groups_raw and
+    encode_decode do not depend on it.  Not built for 16-bit maps, each refused by name before anything is launched: aug= /
+    predict_views / update_views, refine=, clean=, SegEvaluator(boundary=), SegSweepEvaluator and render_raw."""
+
+    label_dtype, wide = torch.uint8, False   # the default path; __init__ sets both
 
     def __init__(self, model, text_embedding, with_bg, bg_thresh=0.95, mode="whole", crop_size=(224, 224), stride=(224, 224),
-                 max_windows=256):
+                 max_windows=256, label_dtype=torch.uint8):
         if mode not in ("whole", "slide"):
             raise ValueError(f"mode must be 'whole' or 'slide', got {mode!r}")
+        if label_dtype not in (torch.uint8, torch.int16):
+            raise ValueError(f"label_dtype is torch.uint8 (at most 256 classes) or torch.int16 (at most {ops.SEG_WIDE_MAX_CLASSES}), "
+                             f"got {label_dtype!r}")
+        self.label_dtype, self.wide = label_dtype, label_dtype == torch.int16
         ops.L.require_cuda(text_embedding)
         self.model = model
         self.text_embedding = text_embedding.detach().float().contiguous()
@@ -778,8 +797,19 @@ class SegInference:
         return soft, tables, win_off, n_groups
 
     def _check_classes(self):
-        if self.num_classes > 256:
-            raise ops.L.Unsupported(f"{self.num_classes} classes: the label-map kernels hold at most 256; use encode_decode")
+        if self.wide:
+            if self.num_classes > ops.SEG_WIDE_MAX_CLASSES:
+                raise ops.L.Unsupported(f"{self.num_classes} classes: the 16-bit label-map kernels hold at most "
+                                        f"{ops.SEG_WIDE_MAX_CLASSES}; use encode_decode")
+        elif self.num_classes > 256:
+            raise ops.L.Unsupported(f"{self.num_classes} classes: the label-map kernels hold at most 256; use encode_decode or "
+                                    "label_dtype=torch.int16")
+
+    def _refuse_wide(self, entry, **stages):
+        """The stages that are not built for 16-bit label maps: the first one given raises, by its name."""
+        if self.wide:
+            _refuse(entry, *((name, given, "is not built for 16-bit label maps (label_dtype=torch.int16)")
+                             for name, given in stages.items()))
 
     def _batch_forward(self, img, classes=True):
         """Vision tower + group tables of every window of a (B, 3, H, W) batch -> the pixel kernels' arguments.
@@ -795,8 +825,12 @@ class SegInference:
 
     @torch.no_grad()
     def predict(self, img):
-        """(B, 3, H, W) -> (B, H, W) uint8 labels (class 0 = background when with_bg)."""
+        """(B, 3, H, W) -> (B, H, W) uint8 labels (class 0 = background when with_bg); int16 with label_dtype=torch.int16: the
+        rescaled entry at the identity size, which is by definition the network-size label map."""
         self._check_classes()
+        if self.wide:
+            src = _BatchImages(img, self.mode == "whole")
+            return torch.stack(self._list_forward(src, src.sizes))
         return ops.seg_label_map(*self._batch_forward(img), self.with_bg, self.bg_thresh)[0]
 
     @torch.no_grad()
@@ -843,10 +877,11 @@ class SegInference:
         images, offs, nbytes, n_blocks, most = ops.seg_image_table(rows, src.device)
         labels = None
         if classes:
-            labels = torch.empty(nbytes, dtype=torch.uint8, device=src.device) if want_labels else None
-            ops.seg_label_map_rescaled(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels,
-                                       gt=_Maps.gapless_of(gts)[0], areas=areas, ignore_index=ignore_index,
-                                       reduce_zero_label=reduce_zero_label)
+            # the table's offsets count elements: it serves the 16-bit maps as it is
+            labels = torch.empty(nbytes, dtype=self.label_dtype, device=src.device) if want_labels else None
+            kernel = ops.seg_label_map_rescaled_wide if self.wide else ops.seg_label_map_rescaled
+            kernel(soft, tables, dwin, images, n_blocks, most, self.with_bg, self.bg_thresh, labels=labels,
+                   gt=_Maps.gapless_of(gts)[0], areas=areas, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
             labels = None if labels is None else _Maps(labels, offs, out_shapes).views()
         if groups is None:
             return labels
@@ -944,7 +979,9 @@ class SegInference:
         returned, = refine_labels(raws, predict_raw(raws, ...), num_classes, transform, refine) bit for bit.  out_shapes must
         then be the raw sizes (the default).  It composes with aug: the refinement sees only labels.
         clean (a Despeckle): the maps, after the refinement if there is one, are despeckled before they are returned,
-        = despeckle(predict_raw(raws, ...), ...) bit for bit."""
+        = despeckle(predict_raw(raws, ...), ...) bit for bit.
+        With label_dtype=torch.int16 the maps are int16, and aug, refine and clean are refused."""
+        self._refuse_wide("predict_raw", aug=aug, refine=refine, clean=clean)
         _check_stages(refine, clean, raws, out_shapes)
         return self._post_process(_RawImages(raws, transform, net_sizes, aug), out_shapes, refine, clean)
 
@@ -953,6 +990,7 @@ class SegInference:
         """views[i] = [((3, H, W) tensor, flags)]: the views of image i, pre-processed and ALREADY FLIPPED as mmseg hands imgs
         and img_metas to aug_test (flags: ops.SEG_FLIP_H | ops.SEG_FLIP_V, what img_metas' flip / flip_direction say)
         -> [(oh_i, ow_i) uint8 labels] of the mean probabilities, as predict_raw(aug=)."""
+        self._refuse_wide("predict_views", predict_views=views)
         return self._views_forward(_SlicedImages(views, augmented=True), out_shapes)
 
     @torch.no_grad()
@@ -996,6 +1034,7 @@ class SegInference:
         default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
         call whatever the modes: labels and group maps come from the same encode_image pass.  refine is refused: draw refined
         maps with blend(raws, predict_raw(raws, transform, refine=...), palette).  clean is refused in the same way."""
+        self._refuse_wide("SegInference", render_raw=vis_modes)
         _refuse("render_raw", ("refine", refine, "is not supported; blend the maps of predict_raw(refine=) instead"),
                 ("clean", clean, "is not supported; blend the maps of despeckle(predict_raw(...)) instead"))
         modes = list(vis_modes)
@@ -1112,9 +1151,17 @@ class SegEvaluator:
     against the ground truths with one more call (segclip_seg_boundary) that adds to `boundary_areas`, a (2, 3, C) int64
     device tensor (slot 0 Boundary IoU, slot 1 trimap); the labels are then formed even when return_labels is False, and
     compute() adds bIoU, mbIoU, trimap_IoU, trimap_mIoU and trimap_aAcc from the same host copy.  Several ranks: all_reduce
-    `boundary_areas` like `areas`.  Without it nothing changes."""
+    `boundary_areas` like `areas`.  Without it nothing changes.
+    Over a SegInference with label_dtype=torch.int16 the ground truths are (oh, ow) torch.int16 tensors whose elements are read
+    as unsigned 16-bit values (a loader's uint16 array goes in as .view(torch.int16)), ignore_index is an integer in
+    0 .. 65535 compared with that value, and boundary= is refused."""
 
     def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None):
+        self.gt_dtype = getattr(seg, "label_dtype", torch.uint8)
+        if self.gt_dtype == torch.int16:
+            _refuse("SegEvaluator", ("boundary", boundary, "is not built for 16-bit label maps (label_dtype=torch.int16)"))
+            if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index <= 65535:
+                raise ValueError(f"SegEvaluator: with 16-bit label maps ignore_index is an integer in 0 .. 65535, got {ignore_index!r}")
         if boundary is not None:
             _check_boundary(boundary)
         self.seg, self.ignore_index, self.reduce_zero_label = seg, int(ignore_index), bool(reduce_zero_label)
@@ -1139,7 +1186,7 @@ class SegEvaluator:
         refused: there is no raw picture here (update_raw has it); clean is refused too (update_raw has it)."""
         _refuse("SegEvaluator.update", ("refine", refine, "needs the decoded pictures: use update_raw(refine=)"),
                 ("clean", clean, "is not supported; use update_raw(clean=), or despeckle the maps and score them with ops.seg_areas"))
-        self._check_gts(imgs, gts)
+        self._check_gts(imgs, gts, self.gt_dtype)
         score, shapes = self._score(gts)
         return self.seg._post_process(_SlicedImages([[(t, 0)] for t in imgs]), shapes, score=score, want_labels=return_labels)
 
@@ -1150,7 +1197,8 @@ class SegEvaluator:
         kernel then only writes the maps and counts nothing.  The ground truths must have the pictures' sizes.
         clean (a Despeckle): the labels are formed (and refined) without counting, despeckled, and ops.seg_areas of the cleaned
         maps against the ground truths is added: the areas are those of the cleaned maps."""
-        self._check_gts(raws, gts)
+        self.seg._refuse_wide("SegEvaluator.update_raw", aug=aug, refine=refine, clean=clean)
+        self._check_gts(raws, gts, self.gt_dtype)
         score, shapes = self._score(gts)
         _check_stages(refine, clean, raws, shapes)
         return self.seg._post_process(_RawImages(raws, transform, net_sizes, aug), shapes, refine, clean, score, return_labels)
@@ -1158,18 +1206,22 @@ class SegEvaluator:
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):
         """views[i] = [((3, H, W) tensor, flags)] as SegInference.predict_views, scored at each ground truth's size."""
+        self.seg._refuse_wide("SegEvaluator", update_views=views)
         self._check_gts(views, gts)
         score, shapes = self._score(gts)
         return self.seg._post_process(_SlicedImages(views, augmented=True), shapes, score=score, want_labels=return_labels)
 
     @staticmethod
-    def _check_gts(imgs, gts):
+    def _check_gts(imgs, gts, dtype=torch.uint8):
+        """dtype: torch.uint8, or torch.int16 for an evaluator over 16-bit label maps"""
         if len(imgs) != len(gts):
             raise ValueError(f"{len(imgs)} images but {len(gts)} ground truths")
         ops.L.require_cuda(*gts)
+        want = "int16 tensor (label_dtype=torch.int16; a uint16 array goes in as .view(torch.int16))" if dtype == torch.int16 \
+            else "uint8 tensor"
         for g in gts:
-            if g.dtype != torch.uint8 or g.dim() != 2:
-                raise ValueError(f"a ground truth is an (oh, ow) uint8 tensor, got {g.dtype} {tuple(g.shape)}")
+            if g.dtype != dtype or g.dim() != 2:
+                raise ValueError(f"a ground truth is an (oh, ow) {want}, got {g.dtype} {tuple(g.shape)}")
 
     @staticmethod
     def boundary_metrics_from_areas(areas):
@@ -1238,6 +1290,9 @@ class SegSweepEvaluator:
     sweep (split the list over two evaluators) and a sweep of the top-5 mask."""
 
     def __init__(self, seg, thresholds, ignore_index=255, reduce_zero_label=False):
+        if getattr(seg, "wide", False):
+            raise ValueError("SegSweepEvaluator is not built for 16-bit label maps (label_dtype=torch.int16); use one SegEvaluator "
+                             "per threshold")
         if not seg.with_bg:
             raise ValueError("SegSweepEvaluator: seg must have with_bg=True (the threshold decides the background class)")
         self.thresholds = check_thresholds(thresholds)

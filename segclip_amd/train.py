@@ -295,7 +295,9 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     SegEvaluator.update_raw(clean=).  test_cfg["boundary"] (a segmentation.Boundary): the labels are also scored on their
     boundary bands, SegEvaluator(boundary=), and the function returns a dict instead of the number: mIoU, mbIoU, trimap_mIoU
     and trimap_aAcc in percent and the per-class bIoU and trimap_IoU tensors in percent; boundary_areas stays this rank's like
-    areas."""
+    areas.  test_cfg["label_dtype"] = torch.int16 (a SegInference argument): vocabularies of up to 1024 classes; gts are then
+    (oh, ow) torch.int16 tensors read as unsigned 16-bit values (a uint16 array goes in as .view(torch.int16)) and
+    test_cfg["ignore_index"] is an integer in 0 .. 65535, e.g. 65535; aug, refine, clean and boundary are refused."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)

@@ -60,9 +60,19 @@ ONE command and alternating within every repeat:
         ground truth, then counting (without scipy: unmeasured); peak allocation, the clock held, the run-to-run spread, and the
         kernels' own times from a separate `rocprofv3 --kernel-trace --stats` child (--boundary-child: five calls with every
         output on the 64 maps and nothing else).
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary] [reps=7]
+With --wide instead: the 16-bit label-map kernel (segclip_seg_label_map_rescaled_wide, csrc/segment_wide.inc) on the inputs of
+--eval (64 images of mixed VOC-like sizes, slide 224 / 224, 12.0 M output pixels) with random int16 ground truths, the arguments
+of one SegEvaluator.update captured, in ONE command and alternating within every repeat:
+  (xi)  at 21 and 151 classes the wide kernel against the uint8 kernel on the same inputs (what the 16-bit path costs where both
+        apply), labels and areas compared; at 460 and 848 classes the wide kernel against the composition a user had before it -
+        ops.seg_logits per image, F.interpolate to the output size, argmax, three bincounts - with the peak allocation of both,
+        and at every class count against two more builds of csrc/segment.hip (made on the spot with hipcc when they are missing):
+        -DSEG_WIDE_LANE_SCAN=1, in which every lane scans the classes of its own undecided pixels as the uint8 kernel does, and
+        -DSEG_WIDE_LANE_SCAN_CLASSES=0, the wave-cooperative scan at every class count (the kernel switches from the first to
+        the second above 32 classes); labels and areas compared.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide] [reps=7]
                                  [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt]"""
+                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt]"""
 import os
 import statistics
 import sys
@@ -83,12 +93,13 @@ SWEEP, SWEEP_CHILD = ("--sweep" in sys.argv[1:]), ("--sweep-child" in sys.argv[1
 REFINE, REFINE_CHILD = ("--refine" in sys.argv[1:]), ("--refine-child" in sys.argv[1:])
 OBJECTS, OBJECTS_CHILD = ("--objects" in sys.argv[1:]), ("--objects-child" in sys.argv[1:])
 BOUNDARY, BOUNDARY_CHILD = ("--boundary" in sys.argv[1:]), ("--boundary-child" in sys.argv[1:])
+WIDE = "--wide" in sys.argv[1:]
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
-                                             "--boundary-child")]
+                                             "--boundary-child", "--wide")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -947,6 +958,158 @@ def boundary_child(model, text):
     torch.cuda.synchronize()
 
 
+class _WideVariantLib:
+    """The library with ONE entry replaced: segclip_seg_label_map_rescaled_wide from a second build of csrc/segment.hip with one
+    build-time switch of csrc/segment_wide.inc set: -DSEG_WIDE_LANE_SCAN=1 (every lane scans the classes of its own undecided
+    pixels at every class count, the uint8 kernel's scheme) or -DSEG_WIDE_LANE_SCAN_CLASSES=0 (the wave-cooperative scan at every
+    class count).  The second build links against the first for everything else; it is made here when it is missing (hipcc,
+    gfx950), as csrc/build/variants/libsegclip_seg_<tag>.so."""
+
+    ENTRY = "segclip_seg_label_map_rescaled_wide"
+
+    def __init__(self, define, tag):
+        import ctypes
+        import subprocess
+        from segclip_amd import _lib as L
+        self.main = L.load()
+        csrc = os.path.join(os.path.dirname(L.lib_path()), "csrc")
+        path = os.path.join(csrc, "build", "variants", f"libsegclip_seg_{tag}.so")   # not beside the objects build.sh links
+        if not os.path.exists(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            hipcc, obj = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), path[:-3] + ".o"
+            subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", define, "-c",
+                            os.path.join(csrc, "segment.hip"), "-o", obj], check=True)
+            subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", obj, "-L" + os.path.dirname(L.lib_path()),
+                            "-l:" + os.path.basename(L.lib_path()), "-Wl,-rpath,$ORIGIN/../../..", "-o", path], check=True)
+        self.entry = getattr(ctypes.CDLL(path), self.ENTRY)
+        self.entry.restype, self.entry.argtypes = L.SIGNATURES[self.ENTRY]
+
+    def __getattr__(self, name):
+        return self.entry if name == self.ENTRY else getattr(self.main, name)
+
+
+def wide_case(model, n_images=64):
+    """(xi) the 16-bit label-map kernel at 21, 151, 460 and 848 classes on the inputs of --eval."""
+    from segclip_amd import _lib as L
+    from segclip_amd.segmentation import SegEvaluator, test_size
+    outs = [EVAL_SIZES[i % len(EVAL_SIZES)] for i in range(n_images)]
+    g = torch.Generator().manual_seed(1)
+    imgs = [torch.randn(3, *test_size(*o), generator=g).cuda() for o in outs]
+    pixels = sum(o[0] * o[1] for o in outs)
+    try:
+        lane_lib = _WideVariantLib("-DSEG_WIDE_LANE_SCAN=1", "lane_scan")
+        coop_lib = _WideVariantLib("-DSEG_WIDE_LANE_SCAN_CLASSES=0", "coop_always")
+    except Exception as e:   # no hipcc on the box
+        lane_lib = coop_lib = None
+        say(f"(xi) wide: the builds with the scan fixed are missing and cannot be made here ({e!r}): unmeasured")
+    for C in (21, 151, 460, 848):
+        name = f"(xi) wide   C={C:4d}"
+        text = torch.randn(C - 1, 512, generator=g)
+        text = (text / text.norm(dim=-1, keepdim=True)).cuda()
+        seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224),
+                           label_dtype=torch.int16)
+        gts = [torch.randint(0, C, o, generator=g).to(torch.int16).cuda() for o in outs]
+        ev = SegEvaluator(seg, ignore_index=65535)
+        captured = {}
+        real = ops.seg_label_map_rescaled_wide
+
+        def capture(*a, **k):
+            captured["call"] = (a, k)
+            return real(*a, **k)
+
+        ops.seg_label_map_rescaled_wide = capture
+        try:
+            with torch.no_grad():
+                ev.update(imgs, gts, return_labels=True)
+        finally:
+            ops.seg_label_map_rescaled_wide = real
+        a, k = captured["call"]
+        soft, tables, dwin, images = a[:4]
+        n_elems = k["labels"].numel()
+
+        def fresh(dtype):
+            return dict(k, labels=torch.zeros(n_elems, dtype=dtype, device="cuda"), gt=k["gt"].to(dtype),
+                        areas=torch.zeros(3, C, dtype=torch.int64, device="cuda"))
+
+        kw = fresh(torch.int16)
+        ways = [(f"wide kernel ({'per-lane' if C <= 32 else 'wave-cooperative'} class scan at this class count)", lambda: real(*a, **kw), 5)]
+        checks = []
+
+        def variant(lib, what):
+            kv = fresh(torch.int16)
+
+            def call():
+                main, L._lib = L._lib, lib
+                try:
+                    real(*a, **kv)
+                finally:
+                    L._lib = main
+
+            ways.append((f"wide kernel built with {what}", call, 5))
+            checks.append((f"build with {what}", kv))
+
+        if C <= 256:
+            k8 = fresh(torch.uint8)
+            k8["ignore_index"] = 255   # C <= 255: no ground truth reaches it, as none reaches 65535
+            ways.append(("uint8 kernel, segclip_seg_label_map_rescaled", lambda: ops.seg_label_map_rescaled(*a, **k8), 5))
+            checks.append(("uint8 kernel", k8))
+        else:
+            gt_long = [t.long() for t in gts]
+            first = images[:, 0].tolist()
+            count = images[:, 1].tolist()
+            dfirst = [torch.tensor([0, c], dtype=torch.int32, device="cuda") for c in count]
+            soft3 = soft.view(dwin.shape[0], -1, 14 * 14)
+            comp_areas = torch.zeros(3, C, dtype=torch.int64, device="cuda")
+
+            def composition():
+                for i, (img, gt) in enumerate(zip(imgs, gt_long)):
+                    sl = slice(first[i], first[i] + count[i])
+                    logits = ops.seg_logits(soft3[sl], tuple(t[sl] for t in tables), dwin[sl], dfirst[i], (1, img.shape[1], img.shape[2]),
+                                            (224, 224), (14, 14), True, 0.80)
+                    pred = F.interpolate(logits, size=tuple(gt.shape), mode="bilinear", align_corners=False).argmax(dim=1)[0]
+                    keep = gt != 65535
+                    p, t = pred[keep], gt[keep]
+                    comp_areas[0] += torch.bincount(p[p == t], minlength=C)
+                    comp_areas[1] += torch.bincount(p, minlength=C)
+                    comp_areas[2] += torch.bincount(t, minlength=C)
+
+            ways.append(("ops.seg_logits per image -> F.interpolate -> argmax -> 3 bincount", composition, 1))
+        if lane_lib is not None:   # both scans at every class count: where the kernel's switch between them belongs
+            variant(lane_lib, "-DSEG_WIDE_LANE_SCAN=1 (per-lane class scan)")
+            variant(coop_lib, "-DSEG_WIDE_LANE_SCAN_CLASSES=0 (wave-cooperative class scan)")
+        with torch.no_grad():
+            for _, fn, _ in ways:
+                fn()
+            torch.cuda.synchronize()
+            for what, other in checks:
+                say(f"{name}: labels equal those of the {what}: {bool(torch.equal(kw['labels'].long(), other['labels'].long()))}; areas "
+                    f"equal: {bool(torch.equal(kw['areas'], other['areas']))}")
+            if C > 256:
+                say(f"{name}: the composition's areas differ from the kernel's by "
+                    f"{float((comp_areas - kw['areas']).abs().sum()) / float(kw['areas'].sum()):.2e} of their sum")
+            for _, fn, _ in ways:
+                fn()
+            torch.cuda.synchronize()
+            ts = [[] for _ in ways]
+            sampler = ClockSampler().start()
+            for _ in range(REPS):   # alternating: every repeat times the ways one after the other
+                for i, (_, fn, inner) in enumerate(ways):
+                    t0 = time.perf_counter()
+                    for _ in range(inner):
+                        fn()
+                    torch.cuda.synchronize()
+                    ts[i].append((time.perf_counter() - t0) / inner)
+            clk = sampler.stop()
+        meds = [statistics.median(t) for t in ts]
+        say(f"{name}: {n_images} images, {dwin.shape[0]} windows, {pixels} output pixels; clock {clk}")
+        for (what, _, inner), t, med in zip(ways, ts, meds):
+            say(f"{name}: {what:78s} {med * 1e6:11.1f} us (min {min(t) * 1e6:.1f}, max {max(t) * 1e6:.1f}; {REPS} x {inner} calls)  "
+                f"{pixels / med / 1e9:7.2f} Gpixel/s   {med / meds[0]:7.2f}x the wide kernel")
+        if C > 256:
+            say(f"{name}: peak allocation of one call: wide kernel {peak_of(ways[0][1]) / 2**20:8.1f} MiB, the composition "
+                f"{peak_of(ways[1][1]) / 2**20:8.1f} MiB")
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -973,7 +1136,9 @@ if __name__ == "__main__":
     if BOUNDARY_CHILD:
         boundary_child(model, text)
         sys.exit(0)
-    if BOUNDARY:
+    if WIDE:
+        wide_case(model)
+    elif BOUNDARY:
         boundary_case(model, text)
     elif OBJECTS:
         objects_case(model, text)
