@@ -6,7 +6,9 @@
 // one-hot, (H, W, N) product and (N + 1, H, W) logit volume never have to exist: segclip_seg_group_table builds the tables
 // (latency-bound: G * N dot products of 512 per window), segclip_seg_label_map interpolates G numbers per pixel, takes the
 // first maximum and looks one row up (bound: 1-2 bytes of HBM writes per pixel).
-// The .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
+// segment_tile.inc holds what the rescaled kernels share: the image table's row check (seg_tile_load), the block's window list,
+// table copies and labels, the four taps and their blend, the area counters and the packed label store.
+// The other .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
 // (segment_refine.inc), their connected components (segment_objects.inc), the training front end (train_frontend.inc) and the
@@ -23,6 +25,7 @@
 namespace {
 
 #include "segment_pixel.inc"
+#include "segment_tile.inc"
 
 __device__ __forceinline__ float seg_clip_scale(const float* ls) { return fminf(expf(*ls), 100.f); }
 
@@ -175,6 +178,7 @@ struct SegPixelArgs {
 template <int PPL, bool LOGITS>
 __global__ __launch_bounds__(256) void seg_pixel_kernel(SegPixelArgs A) {
   __shared__ int s_wy[SEG_MAX_IMG_WIN], s_wx[SEG_MAX_IMG_WIN], s_wi[SEG_MAX_IMG_WIN], s_row[SEG_MAX_IMG_WIN];
+  const SegWinLists L = {s_wy, s_wx, s_wi, s_row};
   __shared__ int s_n;
   __shared__ uint8_t s_bg[SEG_MAX_IMG_WIN * SEG_MAX_G];
   __shared__ uint8_t s_lab[SEG_MAX_IMG_WIN * SEG_MAX_G];
@@ -194,46 +198,20 @@ __global__ __launch_bounds__(256) void seg_pixel_kernel(SegPixelArgs A) {
   const int y_hi = (int)(u_last / upr);
   const int off = A.with_bg ? 1 : 0;
 
-  // the image's windows that touch this block's rows, in window order (at most 64 = one wave: ordered compaction by ballot)
+  // the image's windows that touch this block's rows
   if (tid < 64) {
     int first = A.image_first[b], last = A.image_first[b + 1];
     first = first < 0 ? 0 : (first > A.n_windows ? A.n_windows : first);
     last = last < first ? first : (last > A.n_windows ? A.n_windows : last);
     const int cnt = last - first < SEG_MAX_IMG_WIN ? last - first : SEG_MAX_IMG_WIN;
-    bool p = false;
-    int wy = 0, wx = 0;
-    if (tid < cnt) {
-      wy = A.windows[3 * (first + tid) + 1];
-      wx = A.windows[3 * (first + tid) + 2];
-      p = wy <= y_hi && wy + A.win_h > y_lo;
-    }
-    const unsigned long long m = __ballot(p);
-    if (p) {
-      const int pos = __popcll(m & ((1ull << tid) - 1ull));
-      s_wy[pos] = wy; s_wx[pos] = wx; s_wi[pos] = first + tid;
-    }
-    if (tid == 0) s_n = __popcll(m);
+    const int n = seg_window_compact(A.windows, first, cnt, A.win_h, y_lo, y_hi, L, 0, tid);
+    if (tid == 0) s_n = n;
   }
   __syncthreads();
   const int nwin = s_n;
-  // per (window, group): background indicator and the single-window label
-  for (int i = tid; i < nwin * A.G; i += 256) {
-    const int k = i / A.G, g = i % A.G;
-    const int64_t wg = (int64_t)s_wi[k] * A.G + g;
-    const float score = A.best_score[wg];
-    const bool bg = A.with_bg && score < fminf(A.bg_thresh, A.table_max[s_wi[k]]);
-    s_bg[k * SEG_MAX_G + g] = bg ? 1 : 0;
-    // = the first maximum of [bg, row]: bg = 1 beats every table entry (score < table_max <= 1); an all-zero row gives 0
-    s_lab[k * SEG_MAX_G + g] = (uint8_t)(A.with_bg ? ((bg || !(score > 0.f)) ? 0 : A.best_class[wg] + 1) : A.best_class[wg]);
-  }
-  // the tables of these windows in LDS when they fit (overlaps and the dense logits read N entries per pixel from them)
-  const bool want_tab = LOGITS || nwin > 1;
-  const bool staged = want_tab && (int64_t)nwin * A.G * A.N <= A.tab_floats;
-  if (staged) {
-    const int per = A.G * A.N;
-    for (int i = tid; i < nwin * per; i += 256) s_tab[i] = A.table[(int64_t)s_wi[i / per] * per + i % per];
-  }
-  for (int k = tid; k < nwin; k += 256) s_row[k] = staged ? k : s_wi[k];
+  seg_window_labels(A.best_score, A.table_max, A.best_class, A.with_bg, A.bg_thresh, A.G, L, nwin, s_bg, s_lab, tid);
+  // one window and labels only: no table row is read, and no copy is made
+  const bool staged = seg_stage_tables(A.table, A.G, A.N, L, nwin, s_tab, (LOGITS || nwin > 1) ? A.tab_floats : -1, tid);
   __syncthreads();
 
   SegBlockWindows bw = {s_wy, s_wx, s_wi, nwin};
@@ -313,6 +291,27 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 
 #define ST ((hipStream_t)stream)
 
+// a size or count the kernels do not support (SEGCLIP_REQUIRE: an argument that is invalid)
+#define SEG_REFUSE(cond, ...)          \
+  do {                                 \
+    if (cond) {                        \
+      segclip_set_error(__VA_ARGS__);  \
+      return SEGCLIP_ERR_UNSUPPORTED;  \
+    }                                  \
+  } while (0)
+
+// More dynamic LDS than the 64 KiB a kernel gets without asking: the limit of `fn` is raised once per device (raised[64]).
+static int seg_raise_lds(const char* what, const void* fn, int bytes, std::atomic<bool>* raised) {
+  int dev = 0;
+  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: cannot query the current device", what);
+  if (!raised[dev]) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    SEGCLIP_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
+    raised[dev] = true;
+  }
+  return 0;
+}
+
 extern "C" int segclip_seg_group_table(const float* group_tokens, int64_t group_stride, const float* pooled, int64_t pooled_stride,
                                        const float* text, const float* logit_scale, float* table, float* table_max,
                                        int32_t* best_class, float* best_score, uint8_t* topk_mask, int64_t n_windows, int64_t G,
@@ -320,11 +319,8 @@ extern "C" int segclip_seg_group_table(const float* group_tokens, int64_t group_
   SEGCLIP_REQUIRE(n_windows >= 0 && N >= 1 && C >= 1 && topk >= 1 && topk <= N, "seg_group_table: need N, C >= 1 and 1 <= topk <= N");
   SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "seg_group_table: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
   const int64_t lds = ((G + 1) * C + (G + 1) * N + 2 * N + SEG_MAX_G) * 4;
-  if (lds > 64 * 1024) {
-    segclip_set_error("seg_group_table: N=%lld classes x C=%lld need %lld bytes of LDS (64 KiB available)", (long long)N, (long long)C,
-                      (long long)lds);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(lds > 64 * 1024, "seg_group_table: N=%lld classes x C=%lld need %lld bytes of LDS (64 KiB available)", (long long)N,
+             (long long)C, (long long)lds);
   if (n_windows == 0) return 0;
   hipLaunchKernelGGL(seg_group_table_kernel, dim3((unsigned)n_windows), dim3(256), (size_t)lds, ST, group_tokens, group_stride, pooled,
                      pooled_stride, text, logit_scale, table, table_max, best_class, best_score, topk_mask, (int)G, (int)N, (int)C,
@@ -368,11 +364,8 @@ extern "C" int segclip_seg_label_map(const float* soft_attn, const float* table,
                                      void* stream) {
   if (int rc = seg_pixel_check("seg_label_map", n_windows, B, H, W, win_h, win_w, grid_h, grid_w, G, N)) return rc;
   SEGCLIP_REQUIRE(labels || groups, "seg_label_map: one of labels, groups is required");
-  if (labels && N + (with_bg ? 1 : 0) > 256) {
-    segclip_set_error("seg_label_map: %lld classes do not fit the uint8 label map (use segclip_seg_logits)",
-                      (long long)(N + (with_bg ? 1 : 0)));
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(labels && N + (with_bg ? 1 : 0) > 256, "seg_label_map: %lld classes do not fit the uint8 label map (use segclip_seg_logits)",
+             (long long)(N + (with_bg ? 1 : 0)));
   if (B == 0) return 0;
   SegPixelArgs a = seg_args(soft_attn, table, table_max, best_class, best_score, windows, image_first, n_windows, B, H, W, win_h, win_w,
                             grid_h, grid_w, G, N, with_bg, bg_thresh);
@@ -400,46 +393,68 @@ extern "C" int segclip_seg_logits(const float* soft_attn, const float* table, co
   return 0;
 }
 
+// What the rescaled entries require of their arguments (labels_n, gt_n: elements) ...
+static int seg_eval_check(const char* what, int64_t soft_floats, int64_t labels_n, int64_t gt_n, int64_t n_windows, int64_t B,
+                          int64_t n_blocks, int64_t G, int64_t N, bool labels, bool gt, bool areas) {
+  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_n >= 0 && gt_n >= 0,
+                  "%s: sizes must not be negative, N >= 1", what);
+  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
+  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
+  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
+  return 0;
+}
+
+// ... and what they refuse: more classes C than the label element `elem` and the counters hold, too many windows in an image.
+static int seg_eval_limits(const char* what, int64_t C, int max_classes, const char* elem, int64_t max_image_windows) {
+  SEG_REFUSE(C > max_classes, "%s: %lld classes, at most %d (%s labels, per-class counters in LDS)", what, (long long)C, max_classes, elem);
+  SEG_REFUSE(max_image_windows > SEG_MAX_IMG_WIN, "%s: %lld windows per image, at most %d", what, (long long)max_image_windows,
+             SEG_MAX_IMG_WIN);
+  return 0;
+}
+
+// The arguments every tile kernel takes; labels and gt stay null: their element type is the entry's.
+static SegEvalArgs seg_eval_args(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
+                                 const int32_t* best_class, const float* best_score, const int32_t* windows, const int64_t* images,
+                                 int64_t n_windows, int64_t B, int64_t G, int64_t N, int with_bg, float bg_thresh, int64_t labels_n,
+                                 int64_t gt_n, int ignore_index, int reduce_zero_label, int64_t* areas) {
+  SegEvalArgs a;
+  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
+  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_n; a.gt_bytes = gt_n;
+  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
+  a.labels = nullptr; a.gt = nullptr; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  return a;
+}
+
+// LDS of a tile kernel: the tables of the windows that touch a tile's source rows (a tile of 1024 output pixels spans few rows,
+// so these are one or two rows of the window grid; more than the budget: the kernel reads the global table), and the
+// covering-window lists of the four taps (one slot when no image has more than one window).  -> the bytes of both
+static size_t seg_eval_lds(SegEvalArgs& a, int64_t max_image_windows, int64_t G, int64_t N) {
+  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
+  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
+  int64_t want = per_image * G * N;
+  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
+  a.tab_floats = (int)((want + 1) & ~1ll);
+  return (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
+}
+
 extern "C" int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
                                               const int32_t* best_class, const float* best_score, const int32_t* windows,
                                               const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
                                               int64_t max_image_windows, int64_t G, int64_t N, int with_bg, float bg_thresh,
                                               uint8_t* labels, int64_t labels_bytes, const uint8_t* gt, int64_t gt_bytes,
                                               int ignore_index, int reduce_zero_label, int64_t* areas, void* stream) {
-  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_bytes >= 0 && gt_bytes >= 0,
-                  "seg_label_map_rescaled: sizes must not be negative, N >= 1");
-  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "seg_label_map_rescaled: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
-  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "seg_label_map_rescaled: size out of range");
-  SEGCLIP_REQUIRE(labels || gt, "seg_label_map_rescaled: one of labels, gt is required");
-  SEGCLIP_REQUIRE(!gt || areas, "seg_label_map_rescaled: a ground truth needs the areas to add to");
-  const int64_t C = N + (with_bg ? 1 : 0);
-  if (C > SEG_MAX_CLASSES) {
-    segclip_set_error("seg_label_map_rescaled: %lld classes, at most %d (uint8 labels, per-class counters in LDS)", (long long)C,
-                      SEG_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_image_windows > SEG_MAX_IMG_WIN) {
-    segclip_set_error("seg_label_map_rescaled: %lld windows per image, at most %d", (long long)max_image_windows, SEG_MAX_IMG_WIN);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  const char* what = "seg_label_map_rescaled";
+  if (int rc = seg_eval_check(what, soft_floats, labels_bytes, gt_bytes, n_windows, B, n_blocks, G, N, labels, gt, areas)) return rc;
+  if (int rc = seg_eval_limits(what, N + (with_bg ? 1 : 0), SEG_MAX_CLASSES, "uint8", max_image_windows)) return rc;
   if (B == 0 || n_blocks == 0) return 0;
-  SegEvalArgs a;
-  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
-  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_bytes; a.gt_bytes = gt_bytes;
-  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
-  a.labels = labels; a.gt = gt; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
-  a.areas = reinterpret_cast<unsigned long long*>(areas);
-  // LDS: the tables of the windows that touch a tile's source rows (a tile of 1024 output pixels spans few rows, so these are
-  // one or two rows of the window grid; more than the budget: the kernel reads the global table), and the covering-window
-  // lists of the four taps (one slot when no image has more than one window)
-  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
-  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
-  int64_t want = per_image * G * N;
-  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
-  a.tab_floats = (int)((want + 1) & ~1ll);
-  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
+  SegEvalArgs a = seg_eval_args(soft_attn, soft_floats, table, table_max, best_class, best_score, windows, images, n_windows, B, G, N,
+                                with_bg, bg_thresh, labels_bytes, gt_bytes, ignore_index, reduce_zero_label, areas);
+  a.labels = labels; a.gt = gt;
+  const size_t lds = seg_eval_lds(a, max_image_windows, G, N);
   hipLaunchKernelGGL(seg_rescaled_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, a);
-  SEGCLIP_CHECK_LAUNCH("seg_label_map_rescaled");
+  SEGCLIP_CHECK_LAUNCH(what);
   return 0;
 }
 
@@ -451,58 +466,28 @@ extern "C" int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int6
                                                     const uint8_t* gt, int64_t gt_bytes, int ignore_index, int reduce_zero_label,
                                                     int64_t* areas, void* stream) {
   const char* what = "seg_label_map_rescaled_sweep";
-  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_bytes >= 0 && gt_bytes >= 0,
-                  "%s: sizes must not be negative, N >= 1", what);
-  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
-  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
-  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
-  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
+  if (int rc = seg_eval_check(what, soft_floats, labels_bytes, gt_bytes, n_windows, B, n_blocks, G, N, labels, gt, areas)) return rc;
   SEGCLIP_REQUIRE(thresholds && T >= 1, "%s: thresholds is a host array of T >= 1 floats", what);
-  if (T > SEG_SWEEP_MAX_T) {
-    segclip_set_error("%s: %lld thresholds, at most %d (they travel in the kernel arguments)", what, (long long)T, SEG_SWEEP_MAX_T);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(T > SEG_SWEEP_MAX_T, "%s: %lld thresholds, at most %d (they travel in the kernel arguments)", what, (long long)T,
+             SEG_SWEEP_MAX_T);
   for (int64_t t = 0; t < T; ++t)
     SEGCLIP_REQUIRE(std::isfinite(thresholds[t]) && (t == 0 || thresholds[t] > thresholds[t - 1]),
                     "%s: thresholds must be finite and strictly increasing (entry %lld)", what, (long long)t);
   const int64_t C = N + 1;
-  if (C > SEG_MAX_CLASSES) {
-    segclip_set_error("%s: %lld classes, at most %d (uint8 labels, per-class counters in LDS)", what, (long long)C, SEG_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_image_windows > SEG_MAX_IMG_WIN) {
-    segclip_set_error("%s: %lld windows per image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  if (int rc = seg_eval_limits(what, C, SEG_MAX_CLASSES, "uint8", max_image_windows)) return rc;
   if (B == 0 || n_blocks == 0) return 0;
   SegSweepArgs s;
-  SegEvalArgs& a = s.e;
-  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
-  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_bytes; a.gt_bytes = gt_bytes;
-  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = 1; a.bg_thresh = 0.f;
-  a.labels = labels; a.gt = gt; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
-  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  s.e = seg_eval_args(soft_attn, soft_floats, table, table_max, best_class, best_score, windows, images, n_windows, B, G, N, 1, 0.f,
+                      labels_bytes, gt_bytes, ignore_index, reduce_zero_label, areas);
+  s.e.labels = labels; s.e.gt = gt;
   s.T = (int)T;
   for (int t = 0; t < SEG_SWEEP_MAX_T; ++t) s.thr[t] = t < T ? thresholds[t] : 0.f;
-  // LDS: tables and cover lists as in segclip_seg_label_map_rescaled, then the (T + 1, C) prediction and intersection buckets
-  // and the C label counters
-  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
-  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
-  int64_t want = per_image * G * N;
-  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
-  a.tab_floats = (int)((want + 1) & ~1ll);
-  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2 + (size_t)(2 * (T + 1) + 1) * C * 4;
+  // then the (T + 1, C) prediction and intersection buckets and the C label counters
+  const size_t lds = seg_eval_lds(s.e, max_image_windows, G, N) + (size_t)(2 * (T + 1) + 1) * C * 4;
   SEGCLIP_REQUIRE(lds <= SEG_SWEEP_LDS_BYTES, "%s: internal LDS plan of %lld bytes", what, (long long)lds);
   if (lds > 56 * 1024) {  // beside 3 KiB of static LDS: past the 64 KiB a kernel gets without asking
     static std::atomic<bool> raised[64];
-    int dev = 0;
-    SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: cannot query the current device", what);
-    if (!raised[dev]) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(seg_sweep_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, SEG_SWEEP_LDS_BYTES);
-      SEGCLIP_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
-      raised[dev] = true;
-    }
+    if (int rc = seg_raise_lds(what, reinterpret_cast<const void*>(seg_sweep_kernel), SEG_SWEEP_LDS_BYTES, raised)) return rc;
   }
   hipLaunchKernelGGL(seg_sweep_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, s);
   SEGCLIP_CHECK_LAUNCH(what);
@@ -516,12 +501,12 @@ static int seg_views_launch(const char* what, bool dense, SegViewsArgs& v, int64
                             int64_t max_views, int64_t n_blocks, void* stream) {
   SegEvalArgs& a = v.e;
   const int64_t C = a.N + a.with_bg;
-  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
-  a.cover_slots = max_view_windows > 1 ? SEG_MAX_COVER : 1;  // no view has two windows: no pixel has two covering windows
+  // a.tab_floats as every tile kernel plans it; the byte count it returns and its cover_slots are for one view per image:
+  // here a pixel's covering windows are those of ONE view (no view has two windows: no pixel has two covering windows)
+  seg_eval_lds(a, max_image_windows, a.G, a.N);
+  a.cover_slots = max_view_windows > 1 ? SEG_MAX_COVER : 1;
   const int64_t cov_bytes = (int64_t)4 * a.cover_slots * 256 * 2;
-  int64_t want = per_image * a.G * a.N;
-  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
-  want = (want + 1) & ~1ll;
+  const int64_t want = a.tab_floats;
   int64_t left = SEG_AUG_LDS_BYTES - cov_bytes;
   v.acc_classes = (int)C; v.ms_views = 0; v.max_views = (int)max_views;
   if (C * 1024 + want * 4 > left) {
@@ -530,18 +515,11 @@ static int seg_views_launch(const char* what, bool dense, SegViewsArgs& v, int64
     const int64_t ch = (left - want * 4) / 1024;  // >= 16: 96 KiB less 32 of lists, 32 of (maximum, sum), 16 of tables
     v.acc_classes = (int)(ch < C ? ch : C);
   }
-  a.tab_floats = (int)want;
   const size_t lds = (size_t)a.tab_floats * 4 + (size_t)v.acc_classes * 1024 + (size_t)v.ms_views * 2048 + (size_t)cov_bytes;
   SEGCLIP_REQUIRE(v.acc_classes >= 1 && lds <= SEG_AUG_LDS_BYTES, "%s: internal LDS plan of %lld bytes", what, (long long)lds);
   static std::atomic<bool> raised[2][64];
-  int dev = 0;
-  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "%s: cannot query the current device", what);
   const void* fn = dense ? reinterpret_cast<const void*>(seg_views_kernel<true>) : reinterpret_cast<const void*>(seg_views_kernel<false>);
-  if (!raised[dense][dev]) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, SEG_AUG_LDS_BYTES);
-    SEGCLIP_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit: %s", what, hipGetErrorString(e));
-    raised[dense][dev] = true;
-  }
+  if (int rc = seg_raise_lds(what, fn, SEG_AUG_LDS_BYTES, raised[dense])) return rc;
   if (dense) hipLaunchKernelGGL(seg_views_kernel<true>, dim3((unsigned)n_blocks), dim3(256), lds, ST, v);
   else hipLaunchKernelGGL(seg_views_kernel<false>, dim3((unsigned)n_blocks), dim3(256), lds, ST, v);
   SEGCLIP_CHECK_LAUNCH(what);
@@ -554,18 +532,12 @@ static int seg_views_check(const char* what, int64_t soft_floats, int64_t n_rows
                   "%s: sizes must not be negative, N >= 1", what);
   SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
   SEGCLIP_REQUIRE(B <= (1 << 24) && n_rows <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
-  if (N + (with_bg ? 1 : 0) > SEG_MAX_CLASSES) {
-    segclip_set_error("%s: %lld classes, at most %d", what, (long long)(N + (with_bg ? 1 : 0)), SEG_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_views < 1 || max_views > SEG_MAX_VIEWS) {
-    segclip_set_error("%s: %lld views of an image, 1..%d supported", what, (long long)max_views, SEG_MAX_VIEWS);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_image_windows > SEG_MAX_IMG_WIN) {
-    segclip_set_error("%s: %lld windows over all views of an image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(N + (with_bg ? 1 : 0) > SEG_MAX_CLASSES, "%s: %lld classes, at most %d", what, (long long)(N + (with_bg ? 1 : 0)),
+             SEG_MAX_CLASSES);
+  SEG_REFUSE(max_views < 1 || max_views > SEG_MAX_VIEWS, "%s: %lld views of an image, 1..%d supported", what, (long long)max_views,
+             SEG_MAX_VIEWS);
+  SEG_REFUSE(max_image_windows > SEG_MAX_IMG_WIN, "%s: %lld windows over all views of an image, at most %d", what,
+             (long long)max_image_windows, SEG_MAX_IMG_WIN);
   SEGCLIP_REQUIRE(max_view_windows <= max_image_windows, "%s: %lld windows in one view but %lld over all views of an image", what,
                   (long long)max_view_windows, (long long)max_image_windows);
   return 0;
@@ -575,11 +547,8 @@ static SegViewsArgs seg_views_args(const float* soft_attn, int64_t soft_floats, 
                                    const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
                                    const int64_t* views, int64_t n_windows, int64_t B, int64_t G, int64_t N, int with_bg, float bg_thresh) {
   SegViewsArgs v;
-  SegEvalArgs& a = v.e;
-  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = nullptr; a.best_score = best_score;
-  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = 0; a.gt_bytes = 0;
-  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
-  a.labels = nullptr; a.gt = nullptr; a.ignore_index = 255; a.reduce_zero = 0; a.areas = nullptr;
+  v.e = seg_eval_args(soft_attn, soft_floats, table, table_max, nullptr, best_score, windows, images, n_windows, B, G, N, with_bg,
+                      bg_thresh, 0, 0, 255, 0, nullptr);
   v.views = views; v.n_rows = (int)n_rows; v.probs = nullptr; v.probs_floats = 0;
   return v;
 }
@@ -628,10 +597,7 @@ extern "C" int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t
                                  int64_t* areas, void* stream) {
   SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "seg_areas: need 0 <= n <= 2^40 and C >= 1");
   SEGCLIP_REQUIRE(n == 0 || (pred && gt && areas), "seg_areas: pred, gt and areas are required");
-  if (C > SEG_MAX_CLASSES) {
-    segclip_set_error("seg_areas: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(C > SEG_MAX_CLASSES, "seg_areas: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
   if (n == 0) return 0;
   const int64_t blocks = cdiv(n, SEG_EVAL_TILE) < 1024 ? cdiv(n, SEG_EVAL_TILE) : 1024;
   hipLaunchKernelGGL(seg_areas_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
@@ -648,40 +614,20 @@ extern "C" int segclip_seg_label_map_rescaled_wide(const float* soft_attn, int64
                                                    int64_t gt_elems, int ignore_index, int reduce_zero_label, int64_t* areas,
                                                    void* stream) {
   const char* what = "seg_label_map_rescaled_wide";
-  SEGCLIP_REQUIRE(B >= 0 && n_windows >= 0 && n_blocks >= 0 && N >= 1 && soft_floats >= 0 && labels_elems >= 0 && gt_elems >= 0,
-                  "%s: sizes must not be negative, N >= 1", what);
-  SEGCLIP_REQUIRE(G >= 1 && G <= SEG_MAX_G, "%s: G=%lld groups, 1..%d supported", what, (long long)G, SEG_MAX_G);
-  SEGCLIP_REQUIRE(B <= (1 << 24) && n_windows <= (1 << 24) && n_blocks < (1ll << 31), "%s: size out of range", what);
-  SEGCLIP_REQUIRE(labels || gt, "%s: one of labels, gt is required", what);
-  SEGCLIP_REQUIRE(!gt || areas, "%s: a ground truth needs the areas to add to", what);
-  const int64_t C = N + (with_bg ? 1 : 0);
-  if (C > SEG_WIDE_MAX_CLASSES) {
-    segclip_set_error("%s: %lld classes, at most %d (uint16 labels, per-class counters in LDS)", what, (long long)C,
-                      SEG_WIDE_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_image_windows > SEG_MAX_IMG_WIN) {
-    segclip_set_error("%s: %lld windows per image, at most %d", what, (long long)max_image_windows, SEG_MAX_IMG_WIN);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  if (int rc = seg_eval_check(what, soft_floats, labels_elems, gt_elems, n_windows, B, n_blocks, G, N, labels, gt, areas)) return rc;
+  if (int rc = seg_eval_limits(what, N + (with_bg ? 1 : 0), SEG_WIDE_MAX_CLASSES, "uint16", max_image_windows)) return rc;
   if (B == 0 || n_blocks == 0) return 0;
   SegWideArgs s;
-  SegEvalArgs& a = s.e;
-  a.soft = soft_attn; a.table = table; a.table_max = table_max; a.best_class = best_class; a.best_score = best_score;
-  a.windows = windows; a.images = images; a.soft_floats = soft_floats; a.labels_bytes = labels_elems; a.gt_bytes = gt_elems;
-  a.n_windows = (int)n_windows; a.B = (int)B; a.G = (int)G; a.N = (int)N; a.with_bg = with_bg ? 1 : 0; a.bg_thresh = bg_thresh;
-  a.labels = nullptr; a.gt = nullptr; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
-  a.areas = reinterpret_cast<unsigned long long*>(areas);
+  s.e = seg_eval_args(soft_attn, soft_floats, table, table_max, best_class, best_score, windows, images, n_windows, B, G, N, with_bg,
+                      bg_thresh, labels_elems, gt_elems, ignore_index, reduce_zero_label, areas);
   s.labels = labels; s.gt = gt;
-  // LDS as in segclip_seg_label_map_rescaled, except that a table copy no single window fits (G * N > the copy) is not asked
-  // for: the kernel reads the global table then, and the workgroup stays at three per CU beside its 14.5 KiB of static LDS
-  const int64_t per_image = max_image_windows < 1 ? 1 : max_image_windows;
-  a.cover_slots = per_image > 1 ? SEG_MAX_COVER : 1;
-  int64_t want = per_image * G * N;
-  if (want > SEG_EVAL_TAB_FLOATS) want = SEG_EVAL_TAB_FLOATS;
-  if (G * N > SEG_EVAL_TAB_FLOATS) want = 0;
-  a.tab_floats = (int)((want + 1) & ~1ll);
-  const size_t lds = (size_t)a.tab_floats * 4 + (size_t)4 * a.cover_slots * 256 * 2;
+  size_t lds = seg_eval_lds(s.e, max_image_windows, G, N);
+  // a table copy no single window fits (G * N > the copy) is not asked for: the kernel reads the global table then, and the
+  // workgroup stays at three per CU beside its 14.5 KiB of static LDS
+  if (G * N > SEG_EVAL_TAB_FLOATS) {
+    lds -= (size_t)s.e.tab_floats * 4;
+    s.e.tab_floats = 0;
+  }
   SEGCLIP_REQUIRE(lds <= 48 * 1024, "%s: internal LDS plan of %lld bytes", what, (long long)lds);  // + 14.5 KiB static <= 64 KiB
   hipLaunchKernelGGL(seg_rescaled_wide_kernel, dim3((unsigned)n_blocks), dim3(256), lds, ST, s);
   SEGCLIP_CHECK_LAUNCH(what);
@@ -692,10 +638,7 @@ extern "C" int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, 
                                       int reduce_zero_label, int64_t* areas, void* stream) {
   SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "seg_areas_wide: need 0 <= n <= 2^40 and C >= 1");
   SEGCLIP_REQUIRE(n == 0 || (pred && gt && areas), "seg_areas_wide: pred, gt and areas are required");
-  if (C > SEG_WIDE_MAX_CLASSES) {
-    segclip_set_error("seg_areas_wide: %lld classes, at most %d", (long long)C, SEG_WIDE_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(C > SEG_WIDE_MAX_CLASSES, "seg_areas_wide: %lld classes, at most %d", (long long)C, SEG_WIDE_MAX_CLASSES);
   if (n == 0) return 0;
   const int64_t blocks = cdiv(n, SEG_EVAL_TILE) < 1024 ? cdiv(n, SEG_EVAL_TILE) : 1024;
   hipLaunchKernelGGL(seg_areas_wide_kernel, dim3((unsigned)blocks), dim3(256), 0, ST, pred, gt, n, (int)C, ignore_index,
@@ -710,10 +653,8 @@ static int seg_front_launch(const char* what, bool views, const int64_t* images,
   const int64_t lim = 1ll << 31;
   SEGCLIP_REQUIRE(n_windows >= 0 && n_windows <= (1 << 24) && B >= 0 && B <= (1 << 24) && win_h >= 1 && win_w >= 1, "%s: sizes out of range", what);
   SEGCLIP_REQUIRE(mean && inv_std, "%s: mean and inv_std are required", what);
-  if (win_h >= lim || win_w >= lim || win_h * win_w >= lim) {
-    segclip_set_error("%s: a window of %lld x %lld pixels, fewer than 2^31 supported", what, (long long)win_h, (long long)win_w);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(win_h >= lim || win_w >= lim || win_h * win_w >= lim, "%s: a window of %lld x %lld pixels, fewer than 2^31 supported", what,
+             (long long)win_h, (long long)win_w);
   if (n_windows == 0) return 0;
   SEGCLIP_REQUIRE(windows && out && (images || B == 0), "%s: images, windows and out are required", what);
   SegFrontArgs a;
@@ -748,10 +689,7 @@ extern "C" int segclip_seg_groups_rescaled(const float* soft_attn, int64_t soft_
                                            int64_t n_blocks, int64_t G, uint8_t* groups, int64_t groups_bytes, void* stream) {
   SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && soft_floats >= 0 && groups_bytes >= 0, "seg_groups_rescaled: sizes must not be negative");
   SEGCLIP_REQUIRE(G >= 1, "seg_groups_rescaled: G >= 1");
-  if (G > SEG_MAX_G) {
-    segclip_set_error("seg_groups_rescaled: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(G > SEG_MAX_G, "seg_groups_rescaled: G=%lld groups, 1..%d supported", (long long)G, SEG_MAX_G);
   SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31), "seg_groups_rescaled: size out of range");
   if (B == 0 || n_blocks == 0) return 0;
   SEGCLIP_REQUIRE(soft_attn && images && groups, "seg_groups_rescaled: soft_attn, images and groups are required");
@@ -797,10 +735,8 @@ static SegRefineWs seg_refine_ws(int64_t n, int64_t B, int64_t D) {
 }
 
 extern "C" int64_t segclip_seg_refine_ws_bytes(int64_t labels_bytes, int64_t B, int64_t D) {
-  if (labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || D < 1 || D > SEG_REFINE_MAX_D) {
-    segclip_set_error("seg_refine_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 1 <= D <= %d", SEG_REFINE_MAX_D);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || D < 1 || D > SEG_REFINE_MAX_D,
+             "seg_refine_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 1 <= D <= %d", SEG_REFINE_MAX_D);
   return seg_refine_ws(labels_bytes, B, D).total;
 }
 
@@ -822,26 +758,18 @@ extern "C" int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_bl
   SEGCLIP_REQUIRE(!probs || B == 1, "seg_refine: probs holds the planes of one image, got %lld images", (long long)B);
   for (int c = 0; c < 3; ++c)
     SEGCLIP_REQUIRE(inv_std[c] > 0.f && inv_std[c] < INFINITY && mean[c] == mean[c], "seg_refine: inv_std is positive and finite");
-#define SEG_REFINE_REFUSE(cond, ...)     \
-  do {                                   \
-    if (cond) {                          \
-      segclip_set_error(__VA_ARGS__);    \
-      return SEGCLIP_ERR_UNSUPPORTED;    \
-    }                                    \
-  } while (0)
-  SEG_REFINE_REFUSE(D < 1 || D > SEG_REFINE_MAX_D, "seg_refine: %lld dilations, 1..%d supported", (long long)D, SEG_REFINE_MAX_D);
+  SEG_REFUSE(D < 1 || D > SEG_REFINE_MAX_D, "seg_refine: %lld dilations, 1..%d supported", (long long)D, SEG_REFINE_MAX_D);
   for (int64_t i = 0; i < D; ++i)
-    SEG_REFINE_REFUSE(dilations[i] < 1 || dilations[i] > SEG_REFINE_MAX_DIL || (i > 0 && dilations[i] <= dilations[i - 1]),
-                      "seg_refine: dilations are increasing values in 1..%d, got %d at position %lld", SEG_REFINE_MAX_DIL, dilations[i],
-                      (long long)i);
-  SEG_REFINE_REFUSE(T < 0 || T > SEG_REFINE_MAX_T, "seg_refine: %lld iterations, 0..%d supported", (long long)T, SEG_REFINE_MAX_T);
-  SEG_REFINE_REFUSE(C < 1 || C > SEG_MAX_CLASSES, "seg_refine: %lld classes, 1..%d supported (uint8 labels)", (long long)C, SEG_MAX_CLASSES);
-  SEG_REFINE_REFUSE(max_side < 1 || max_side >= SEG_REFINE_LIMIT, "seg_refine: sides of 1..%d pixels supported, got a bound of %lld",
-                    SEG_REFINE_LIMIT - 1, (long long)max_side);
+    SEG_REFUSE(dilations[i] < 1 || dilations[i] > SEG_REFINE_MAX_DIL || (i > 0 && dilations[i] <= dilations[i - 1]),
+               "seg_refine: dilations are increasing values in 1..%d, got %d at position %lld", SEG_REFINE_MAX_DIL, dilations[i],
+               (long long)i);
+  SEG_REFUSE(T < 0 || T > SEG_REFINE_MAX_T, "seg_refine: %lld iterations, 0..%d supported", (long long)T, SEG_REFINE_MAX_T);
+  SEG_REFUSE(C < 1 || C > SEG_MAX_CLASSES, "seg_refine: %lld classes, 1..%d supported (uint8 labels)", (long long)C, SEG_MAX_CLASSES);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_REFINE_LIMIT, "seg_refine: sides of 1..%d pixels supported, got a bound of %lld",
+             SEG_REFINE_LIMIT - 1, (long long)max_side);
   const SegRefineWs w = seg_refine_ws(labels_bytes, B, D);
-  SEG_REFINE_REFUSE(T > 0 && ws_bytes < w.total, "seg_refine: the workspace has %lld bytes, segclip_seg_refine_ws_bytes asks for %lld",
-                    (long long)ws_bytes, (long long)w.total);
-#undef SEG_REFINE_REFUSE
+  SEG_REFUSE(T > 0 && ws_bytes < w.total, "seg_refine: the workspace has %lld bytes, segclip_seg_refine_ws_bytes asks for %lld",
+             (long long)ws_bytes, (long long)w.total);
   if (B == 0 || n_blocks == 0) return 0;
   SEGCLIP_REQUIRE(images && labels && out, "seg_refine: images, labels and out are required");
   SEGCLIP_REQUIRE(out_bytes == labels_bytes, "seg_refine: out has the layout of labels: %lld bytes, got %lld", (long long)labels_bytes,
@@ -920,10 +848,8 @@ static SegCCWs seg_cc_ws(int64_t n, int64_t n_blocks) {
 }
 
 extern "C" int64_t segclip_seg_components_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks) {
-  if (labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31)) {
-    segclip_set_error("seg_components_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31),
+             "seg_components_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
   return seg_cc_ws(labels_bytes, n_blocks).total;
 }
 
@@ -942,23 +868,15 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
                   (long long)labels_bytes, (long long)cleaned_bytes);
   SEGCLIP_REQUIRE(!cleaned || !labels || cleaned + cleaned_bytes <= labels || labels + labels_bytes <= cleaned,
                   "seg_components: cleaned overlaps labels (the despeckling is out of place)");
-#define SEG_CC_REFUSE(cond, ...)         \
-  do {                                   \
-    if (cond) {                          \
-      segclip_set_error(__VA_ARGS__);    \
-      return SEGCLIP_ERR_UNSUPPORTED;    \
-    }                                    \
-  } while (0)
-  SEG_CC_REFUSE(connectivity != 4 && connectivity != 8, "seg_components: connectivity is 4 or 8, got %d", connectivity);
-  SEG_CC_REFUSE(skip_label < -1 || skip_label > 255, "seg_components: skip_label is a byte or -1, got %d", skip_label);
-  SEG_CC_REFUSE(fill < 0 || fill > 255, "seg_components: fill is a byte, got %d", fill);
-  SEG_CC_REFUSE(min_area < 0, "seg_components: min_area must not be negative, got %lld", (long long)min_area);
-  SEG_CC_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_components: sides of 1..%d pixels supported, got a bound of %lld",
-                SEG_CC_LIMIT - 1, (long long)max_side);
+  SEG_REFUSE(connectivity != 4 && connectivity != 8, "seg_components: connectivity is 4 or 8, got %d", connectivity);
+  SEG_REFUSE(skip_label < -1 || skip_label > 255, "seg_components: skip_label is a byte or -1, got %d", skip_label);
+  SEG_REFUSE(fill < 0 || fill > 255, "seg_components: fill is a byte, got %d", fill);
+  SEG_REFUSE(min_area < 0, "seg_components: min_area must not be negative, got %lld", (long long)min_area);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_components: sides of 1..%d pixels supported, got a bound of %lld",
+             SEG_CC_LIMIT - 1, (long long)max_side);
   const SegCCWs w = seg_cc_ws(labels_bytes, n_blocks);
-  SEG_CC_REFUSE(ws_bytes < w.total, "seg_components: the workspace has %lld bytes, segclip_seg_components_ws_bytes asks for %lld",
-                (long long)ws_bytes, (long long)w.total);
-#undef SEG_CC_REFUSE
+  SEG_REFUSE(ws_bytes < w.total, "seg_components: the workspace has %lld bytes, segclip_seg_components_ws_bytes asks for %lld",
+             (long long)ws_bytes, (long long)w.total);
   if (B == 0 || n_blocks == 0) {
     if (count) {
       const hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), ST);
@@ -1027,10 +945,8 @@ static SegBdWs seg_bd_ws(int64_t pred_bytes, int64_t gt_bytes) {
 }
 
 extern "C" int64_t segclip_seg_boundary_ws_bytes(int64_t pred_bytes, int64_t gt_bytes) {
-  if (pred_bytes < 0 || pred_bytes > (1ll << 40) || gt_bytes < 0 || gt_bytes > (1ll << 40)) {
-    segclip_set_error("seg_boundary_ws_bytes: need 0 <= pred_bytes, gt_bytes <= 2^40");
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(pred_bytes < 0 || pred_bytes > (1ll << 40) || gt_bytes < 0 || gt_bytes > (1ll << 40),
+             "seg_boundary_ws_bytes: need 0 <= pred_bytes, gt_bytes <= 2^40");
   return seg_bd_ws(pred_bytes, gt_bytes).total;
 }
 
@@ -1052,20 +968,12 @@ extern "C" int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_
                       !seg_bd_overlap(gt_band, gt_bytes, pred, pred_bytes) && !seg_bd_overlap(gt_band, gt_bytes, gt, gt_bytes) &&
                       !seg_bd_overlap(pred_band, pred_bytes, gt_band, gt_bytes),
                   "seg_boundary: a band output overlaps an input or the other band");
-  if (C > SEG_MAX_CLASSES) {
-    segclip_set_error("seg_boundary: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (max_side < 1 || max_side >= SEG_BD_LIMIT) {
-    segclip_set_error("seg_boundary: sides of 1..%d pixels supported, got a bound of %lld", SEG_BD_LIMIT - 1, (long long)max_side);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(C > SEG_MAX_CLASSES, "seg_boundary: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_BD_LIMIT, "seg_boundary: sides of 1..%d pixels supported, got a bound of %lld",
+             SEG_BD_LIMIT - 1, (long long)max_side);
   const SegBdWs w = seg_bd_ws(pred_bytes, gt_bytes);
-  if (ws_bytes < w.total) {
-    segclip_set_error("seg_boundary: the workspace has %lld bytes, segclip_seg_boundary_ws_bytes asks for %lld", (long long)ws_bytes,
-                      (long long)w.total);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(ws_bytes < w.total, "seg_boundary: the workspace has %lld bytes, segclip_seg_boundary_ws_bytes asks for %lld",
+             (long long)ws_bytes, (long long)w.total);
   if (B == 0 || n_blocks == 0) return 0;
   SEGCLIP_REQUIRE(images && pred, "seg_boundary: images and pred are required");
   SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_boundary: the workspace is required, 16-byte aligned");
@@ -1089,24 +997,14 @@ extern "C" int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_
 extern "C" int segclip_train_images_from_u8(const int64_t* images, int64_t B, int64_t out_h, int64_t out_w, const float* lut, float* out,
                                             void* stream) {
   SEGCLIP_REQUIRE(B >= 0 && B <= (1 << 24) && out_h >= 1 && out_w >= 1 && out_h < TF_LIMIT, "train_images_from_u8: sizes out of range");
-  if (out_w > TF_MAX_OUT_W) {
-    segclip_set_error("train_images_from_u8: an output of %lld columns, at most %d (coefficients and 33 rows of bytes in LDS)",
-                      (long long)out_w, TF_MAX_OUT_W);
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
+  SEG_REFUSE(out_w > TF_MAX_OUT_W, "train_images_from_u8: an output of %lld columns, at most %d (coefficients and 33 rows of bytes in LDS)",
+             (long long)out_w, TF_MAX_OUT_W);
   if (B == 0) return 0;
   SEGCLIP_REQUIRE(images && lut && out, "train_images_from_u8: images, lut and out are required");
   const int64_t bands = cdiv(out_h, TF_BAND);
   SEGCLIP_REQUIRE(B * bands < (1ll << 31), "train_images_from_u8: %lld images of %lld rows exceed one launch", (long long)B, (long long)out_h);
   static std::atomic<bool> raised[64];
-  int dev = 0;
-  SEGCLIP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64, "train_images_from_u8: cannot query the current device");
-  if (!raised[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(train_front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             TF_LDS_BYTES);
-    SEGCLIP_REQUIRE(e == hipSuccess, "train_images_from_u8: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    raised[dev] = true;
-  }
+  if (int rc = seg_raise_lds("train_images_from_u8", reinterpret_cast<const void*>(train_front_kernel), TF_LDS_BYTES, raised)) return rc;
   TrainFrontArgs a;
   a.images = images; a.lut = lut; a.out = out; a.out_h = (int)out_h; a.out_w = (int)out_w; a.bands = (int)bands;
   a.vec = (out_w % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;

@@ -1,6 +1,6 @@
 // Test-time augmentation of the zero-shot evaluation (segment.hip): mmseg's aug_test for flip and multi-scale views without a
 // (C, oh, ow), (C, H, W) or per-view probability array.  Every view of an image is one row of the image table of
-// segment_eval.inc (its own network size, windows, window size, grid and soft_attn offset) plus a flag word; an output pixel
+// segment_tile.inc (its own network size, windows, window size, grid and soft_attn offset) plus a flag word; an output pixel
 // mirrors its position per view, forms the view's class logits at the four source taps by the device functions of
 // segment_pixel.inc (the four-tap blend of segclip_seg_label_map_rescaled), takes their soft-max, and the mean over the views
 // decides the label.  segclip_seg_view_probs is the same kernel writing the mean instead of its first maximum.
@@ -32,7 +32,10 @@ struct SegViewsArgs {
 // the one place a soft-max numerator is formed: p = seg_exp_shift(v, max) / sum of seg_exp_shift over the classes
 __device__ __forceinline__ float seg_exp_shift(float v, float m) { return expf(v - m); }
 
-// the four taps of one output pixel in one view: covering-window lists and weights
+// The four taps of one output pixel in one view: covering-window lists and weights.  This kernel keeps its own statement of
+// seg_pixel_taps / seg_blend_taps (segment_tile.inc) and its own pixel loop: segclip_seg_view_probs writes the floats
+// themselves, and built from the shared pair the kernel rounded a few of them differently in the last bits and ran slower
+// (profiles/seg_tile_refactor.txt).  The row check, the window compaction and the table staging are the shared ones.
 struct SegViewTaps {
   const uint16_t *c0, *c1, *c2, *c3;
   int n0, n1, n2, n3;
@@ -50,11 +53,13 @@ __device__ __forceinline__ float seg_view_logit(const SegTables& tb, int c, cons
 
 // A workgroup owns SEG_EVAL_TILE consecutive pixels of one image's flat (oh, ow) output.  Labels: a lane owns four consecutive
 // pixels (one dword store); probabilities: pixel q * 256 + lane of the tile, so that a wave stores 256 consecutive bytes per
-// class.  Every entry of both tables is range-checked here; an image with one inconsistent view is skipped.
+// class.  Every entry of both tables is range-checked here (the view rows by seg_tile_row); an image with one inconsistent
+// view is skipped.
 template <bool DENSE>
 __global__ __launch_bounds__(256) void seg_views_kernel(SegViewsArgs VA) {
   const SegEvalArgs& A = VA.e;
   __shared__ int s_wy[SEG_MAX_IMG_WIN], s_wx[SEG_MAX_IMG_WIN], s_wi[SEG_MAX_IMG_WIN], s_row[SEG_MAX_IMG_WIN];
+  const SegWinLists L = {s_wy, s_wx, s_wi, s_row};
   __shared__ uint8_t s_bg[SEG_MAX_IMG_WIN * SEG_MAX_G];
   __shared__ int s_cnt[3 * SEG_MAX_CLASSES];
   __shared__ int s_img;
@@ -101,24 +106,17 @@ __global__ __launch_bounds__(256) void seg_views_kernel(SegViewsArgs VA) {
   const bool score = !DENSE && A.gt && A.areas && gt_off >= 0 && gt_off + total <= A.gt_bytes;
   if (!(write || score)) return;
 
-  // every view's row, checked as the rescaled kernel checks its image's
+  // every view's row, checked as the single-view kernels check their image's
   bool okv = true;
   if (tid < nv) {
     const int64_t* D = D0 + (int64_t)tid * SEG_IMG_COLS;
-    const int64_t H = D[SI_H], W = D[SI_W], win_h = D[SI_WIN_H], win_w = D[SI_WIN_W], gh = D[SI_GH], gw = D[SI_GW];
-    const int64_t soft_off = D[SI_SOFT];
-    int64_t first = D[SI_FIRST], count = D[SI_COUNT];
-    first = first < 0 ? 0 : (first > A.n_windows ? A.n_windows : first);
-    count = count < 0 ? 0 : (count > A.n_windows - first ? A.n_windows - first : count);
-    okv = H >= 1 && W >= 1 && win_h >= 1 && win_w >= 1 && gh >= 1 && gw >= 1 && H < lim && W < lim && win_h < lim && win_w < lim &&
-          gh * gw * A.G < lim && D[SI_OH] == oh && D[SI_OW] == ow;
-    okv = okv && soft_off >= 0 && soft_off + count * A.G * gh * gw <= A.soft_floats;
+    SegTileRow r;
+    okv = seg_tile_row(D, A.n_windows, A.G, A.soft_floats, r) && D[SI_OH] == oh && D[SI_OW] == ow;
     if (okv) {
       int* g = s_vgeo[tid];
-      g[VG_H] = (int)H; g[VG_W] = (int)W; g[VG_WIN_H] = (int)win_h; g[VG_WIN_W] = (int)win_w; g[VG_GH] = (int)gh; g[VG_GW] = (int)gw;
-      g[VG_FLAGS] = (int)(D[SI_FLAGS] & 3); g[VG_FIRST] = (int)first;
-      g[VG_COUNT] = (int)(count < SEG_MAX_IMG_WIN ? count : SEG_MAX_IMG_WIN);
-      s_vsoft[tid] = soft_off - first * A.G * gh * gw;
+      g[VG_H] = r.H; g[VG_W] = r.W; g[VG_WIN_H] = r.win_h; g[VG_WIN_W] = r.win_w; g[VG_GH] = r.gh; g[VG_GW] = r.gw;
+      g[VG_FLAGS] = (int)(D[SI_FLAGS] & 3); g[VG_FIRST] = r.first; g[VG_COUNT] = r.n_img;
+      s_vsoft[tid] = r.soft;
     }
   }
   if (!__syncthreads_and(okv ? 1 : 0)) return;
@@ -137,18 +135,7 @@ __global__ __launch_bounds__(256) void seg_views_kernel(SegViewsArgs VA) {
       float l;
       seg_axis_taps(vflip ? (int)oh - 1 - yb : ya, ry, g[VG_H], sy_lo, t, l);
       seg_axis_taps(vflip ? (int)oh - 1 - ya : yb, ry, g[VG_H], t, sy_hi, l);
-      bool p = false;
-      int wy = 0, wx = 0;
-      if (tid < g[VG_COUNT]) {
-        wy = A.windows[3 * (g[VG_FIRST] + tid) + 1];
-        wx = A.windows[3 * (g[VG_FIRST] + tid) + 2];
-        p = wy <= sy_hi && (int64_t)wy + g[VG_WIN_H] > sy_lo;
-      }
-      const unsigned long long m = __ballot(p);
-      const int pos = n + __popcll(m & ((1ull << tid) - 1ull));
-      if (p && pos < SEG_MAX_IMG_WIN) { s_wy[pos] = wy; s_wx[pos] = wx; s_wi[pos] = g[VG_FIRST] + tid; }
-      n += __popcll(m);
-      n = n < SEG_MAX_IMG_WIN ? n : SEG_MAX_IMG_WIN;
+      n = seg_window_compact(A.windows, g[VG_FIRST], g[VG_COUNT], g[VG_WIN_H], sy_lo, sy_hi, L, n, tid);
     }
     if (tid == 0) s_vfirst[nv] = n;
   }
@@ -159,12 +146,7 @@ __global__ __launch_bounds__(256) void seg_views_kernel(SegViewsArgs VA) {
     const float sc = A.best_score[(int64_t)s_wi[k] * A.G + g];
     s_bg[k * SEG_MAX_G + g] = (A.with_bg && sc < fminf(A.bg_thresh, A.table_max[s_wi[k]])) ? 1 : 0;
   }
-  const bool staged = (int64_t)nwin * A.G * A.N <= A.tab_floats;
-  if (staged) {
-    const int per = A.G * A.N;
-    for (int i = tid; i < nwin * per; i += 256) s_tab[i] = A.table[(int64_t)s_wi[i / per] * per + i % per];
-  }
-  for (int k = tid; k < nwin; k += 256) s_row[k] = staged ? k : s_wi[k];
+  const bool staged = seg_stage_tables(A.table, A.G, A.N, L, nwin, s_tab, A.tab_floats, tid);
   __syncthreads();
 
   const int slots = A.cover_slots;

@@ -4,7 +4,7 @@
 //                       :359-362), without the (G, H, W) and (G, oh, ow) intermediates
 //   seg_blend_kernel  : the overlay of blend_result (:258-284) in numpy's fp64 arithmetic, and optionally the per-index pixel
 //                       count, sum of y and sum of x that seg2coord (:100-115) averages
-// Both are bandwidth-bound and reuse the descriptor-table scheme of segment_eval.inc: the workgroups of all images are numbered
+// Both are bandwidth-bound and reuse the descriptor-table scheme of segment_tile.inc: the workgroups of all images are numbered
 // through, a table row names an image's first workgroup, and every row is range-checked on the device.
 
 #define SEG_RENDER_TILE 1024         // pixels of a workgroup (a lane owns 4 consecutive ones)
@@ -14,16 +14,6 @@
 #define SEG_BLEND_LIMIT (1 << 15)
 #define SEG_MAX_PALETTE 256
 enum { BL_SRC, BL_H, BL_W, BL_STRIDE, BL_MAP, BL_OUT, BL_BLK };
-
-// the last image whose first workgroup is not after this one (column `col` of a table of `cols` columns)
-__device__ __forceinline__ int seg_block_image(const int64_t* images, int B, int cols, int col, int64_t block) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (images[(int64_t)mid * cols + col] <= block) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
