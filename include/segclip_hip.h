@@ -807,6 +807,50 @@ int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, i
                            uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Despeckling by merging (segment_sieve.inc): every small connected component of a label map takes the label of its largest
+ * neighbour, in 1..8 rounds, for images of mixed sizes in one call: what a sieve filter does in the raster toolkits.  It is for
+ * vocabularies without a background class, where segclip_seg_components' constant `fill` paints the specks with a real class.
+ * THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated by tests/cc_merge_reference.py.
+ *
+ * A ROUND, per image: label map L (h, w) uint8, connectivity 4 or 8, skip_label in 0..255 or -1 for none, min_area >= 0.
+ *   Components and areas are exactly those of segclip_seg_components.  Skipped pixels belong to no component: they are never
+ *   changed and never voted for.  A component is SMALL when its area < min_area, otherwise it is KEPT.
+ *   The CANDIDATES of a small component S are the kept components that own at least one pixel 4-adjacent (left, right, up,
+ *   down, inside the image) to a pixel of S.  Contacts are 4-adjacent whatever the connectivity of the components (a
+ *   4-neighbour in another component therefore always carries another byte); a diagonal touch is no contact.
+ *   The WINNER is the candidate with the largest area, among equal areas the one with the smallest label (two candidates
+ *   that tie in both give the same byte): in integers the maximum of (area << 8) | (255 - label) over all contacts, so the
+ *   result depends on no scheduling and two calls give the same bits.
+ *   Every pixel of a small component with a winner takes the winner's label.  A small component without a candidate is an
+ *   ORPHAN and keeps its label.  All other pixels keep theirs.
+ * ROUNDS: round r + 1 runs on the output of round r with the components formed anew (a speck nested in a speck needs two).
+ *   After the LAST round only, the orphans become orphan_fill if it is 0..255; with -1 they stay.  A round that changes nothing
+ *   is a fixed point.  min_area 0 and 1 return the input.
+ *
+ *   images, n_blocks, max_side, labels, labels_bytes, connectivity, skip_label: as for segclip_seg_components (the same table)
+ *   cleaned  : flat uint8 of cleaned_bytes = labels_bytes with the labels' offsets, must not overlap labels; only the pixels of
+ *              the table's images are written
+ *   ws       : segclip_seg_sieve_ws_bytes(labels_bytes, B, n_blocks) bytes = 21 per pixel (8 slot, 4 parent, 4 root, 4 area, 1
+ *              for the map between two rounds), each part rounded up to 256; 16-byte aligned
+ *   Every round enqueues, without a host synchronisation: the clearing of the slots, the component kernels of
+ *   segclip_seg_components up to the areas (no root count, scan or ranks), the vote (keys reduced with 64-bit atomicMax in LDS
+ *   per tile-local group, then ONE global 64-bit atomicMax per (tile, group) on the slot at the component's root, which is
+ *   how a component that spans tiles sees a neighbour that touches it in another tile) and the pass that writes the winners.
+ *   The rounds alternate between `cleaned` and the workspace so that the last one lands in `cleaned`.
+ *   Traffic per pixel and round beyond the component kernels (13 B read + 12 written): 8 B of slot cleared; vote: 4 B of
+ *   root + the gathered area; a pixel of a small component also reads its 4 neighbours' roots, areas and labels; 8 B per
+ *   (tile, voting group); final: 4 B of root + the gathered area + 1 B read, 1 B written, 8 B of slot per small pixel.
+ *   A bad table row is SKIPPED on the device as in segclip_seg_components (nothing of that image read or written).
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: rounds outside 1..8, orphan_fill outside -1..255,
+ *   connectivity other than 4 or 8, skip_label outside -1..255, min_area < 0, max_side outside [1, 2^15), a workspace smaller
+ *   than ws_bytes.  SEGCLIP_ERR_INVALID: cleaned overlapping labels, cleaned_bytes != labels_bytes, missing pointers.
+ * ------------------------------------------------------------------------------------------ */
+int64_t segclip_seg_sieve_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks);
+int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                      int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill, int rounds,
+                      uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Boundary metrics of label maps (segment_boundary.inc): the boundary bands of a prediction and a ground truth, and the
  * per-class areas of Boundary IoU (Cheng et al., CVPR 2021) and of the trimap mIoU of the DeepLab papers, for maps of mixed
  * sizes in one call.  THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated with the

@@ -187,6 +187,8 @@ SIGNATURES = {
     "segclip_seg_components_ws_bytes": (i64, [i64, i64, i64]),
     "segclip_seg_components": (C.c_int, [vp, i64, i64, i64, vp, i64, C.c_int, C.c_int, vp, vp, i64, vp, i64, vp, i64, C.c_int, vp,
                                          i64, vp, i64, vp]),
+    "segclip_seg_sieve_ws_bytes": (i64, [i64, i64, i64]),
+    "segclip_seg_sieve": (C.c_int, [vp, i64, i64, i64, vp, i64, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp]),
     "segclip_seg_boundary_ws_bytes": (i64, [i64, i64]),
     "segclip_seg_boundary": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp]),
     "segclip_retrieval_thresholds": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),

@@ -11,7 +11,7 @@
 // The other .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
-// (segment_refine.inc), their connected components (segment_objects.inc), the training front end (train_frontend.inc) and the
+// (segment_refine.inc), their connected components (segment_objects.inc), despeckling by merging (segment_sieve.inc), the training front end (train_frontend.inc) and the
 // 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc).
 #include "common.h"
 
@@ -284,6 +284,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_render.inc"
 #include "segment_refine.inc"
 #include "segment_objects.inc"
+#include "segment_sieve.inc"
 #include "segment_boundary.inc"
 #include "train_frontend.inc"
 
@@ -929,6 +930,88 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
   if (area_px || cleaned) {
     hipLaunchKernelGGL(seg_cc_final_kernel, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_components (final)");
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- despeckling by merging (segment_sieve.inc)
+struct SegSieveWs { int64_t slot, parent, root, area, tmp, total; };
+static SegSieveWs seg_sieve_ws(int64_t n) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegSieveWs w;
+  w.slot = 0;
+  w.parent = up(n * 8);
+  w.root = w.parent + up(n * 4);
+  w.area = w.root + up(n * 4);
+  w.tmp = w.area + up(n * 4);
+  w.total = w.tmp + up(n);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_sieve_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks) {
+  SEG_REFUSE(labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31),
+             "seg_sieve_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
+  return seg_sieve_ws(labels_bytes).total;
+}
+
+extern "C" int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                                 int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill,
+                                 int rounds, uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_bytes >= 0 && cleaned_bytes >= 0 && ws_bytes >= 0,
+                  "seg_sieve: sizes must not be negative");
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "seg_sieve: size out of range");
+  SEGCLIP_REQUIRE(cleaned_bytes == labels_bytes, "seg_sieve: cleaned has the layout of labels: %lld bytes, got %lld",
+                  (long long)labels_bytes, (long long)cleaned_bytes);
+  SEGCLIP_REQUIRE(!cleaned || !labels || cleaned + cleaned_bytes <= labels || labels + labels_bytes <= cleaned,
+                  "seg_sieve: cleaned overlaps labels (the despeckling is out of place)");
+  SEG_REFUSE(connectivity != 4 && connectivity != 8, "seg_sieve: connectivity is 4 or 8, got %d", connectivity);
+  SEG_REFUSE(skip_label < -1 || skip_label > 255, "seg_sieve: skip_label is a byte or -1, got %d", skip_label);
+  SEG_REFUSE(orphan_fill < -1 || orphan_fill > 255, "seg_sieve: orphan_fill is a byte or -1, got %d", orphan_fill);
+  SEG_REFUSE(rounds < 1 || rounds > SEG_SIEVE_MAX_ROUNDS, "seg_sieve: 1..%d rounds supported, got %d", SEG_SIEVE_MAX_ROUNDS, rounds);
+  SEG_REFUSE(min_area < 0, "seg_sieve: min_area must not be negative, got %lld", (long long)min_area);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_sieve: sides of 1..%d pixels supported, got a bound of %lld",
+             SEG_CC_LIMIT - 1, (long long)max_side);
+  const SegSieveWs w = seg_sieve_ws(labels_bytes);
+  SEG_REFUSE(ws_bytes < w.total, "seg_sieve: the workspace has %lld bytes, segclip_seg_sieve_ws_bytes asks for %lld",
+             (long long)ws_bytes, (long long)w.total);
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(images && labels && cleaned, "seg_sieve: images, labels and cleaned are required");
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_sieve: the workspace is required, 16-byte aligned");
+
+  SegSieveArgs s;
+  SegCCArgs& a = s.cc;
+  a.images = images; a.labels_bytes = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
+  a.B = (int)B; a.max_side = (int)max_side; a.conn8 = connectivity == 8; a.skip = skip_label;
+  char* base = static_cast<char*>(ws);
+  a.seg = nullptr; a.rank = nullptr; a.area_px = nullptr; a.records = nullptr; a.K = 0; a.fill = 0; a.cleaned = nullptr;
+  a.parent = reinterpret_cast<int32_t*>(base + w.parent);
+  a.root = reinterpret_cast<int32_t*>(base + w.root);
+  a.area = reinterpret_cast<int32_t*>(base + w.area);
+  a.min_area = min_area;
+  s.slot = reinterpret_cast<unsigned long long*>(base + w.slot);
+  uint8_t* tmp = reinterpret_cast<uint8_t*>(base + w.tmp);
+
+  // round r reads what round r - 1 wrote; the outputs alternate so that the last round's is `cleaned`.  A kernel touches the
+  // pixels of the table's images only, so the bytes between the maps are read and written by none.
+  const dim3 grid((unsigned)n_blocks), block(256);
+  const uint8_t* in = labels;
+  for (int r = 1; r <= rounds; ++r) {
+    a.labels = in;
+    s.out = (rounds - r) % 2 == 0 ? cleaned : tmp;
+    s.orphan = r == rounds ? orphan_fill : -1;
+    const hipError_t e = hipMemsetAsync(s.slot, 0, (size_t)labels_bytes * sizeof(unsigned long long), ST);
+    SEGCLIP_REQUIRE(e == hipSuccess, "seg_sieve: clearing the slots failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(seg_cc_local_kernel, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_sieve (local)");
+    hipLaunchKernelGGL(seg_cc_merge_kernel, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_sieve (merge)");
+    hipLaunchKernelGGL(seg_cc_stats_kernel<false>, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_sieve (stats)");
+    hipLaunchKernelGGL(seg_sieve_vote_kernel, grid, block, 0, ST, s);
+    SEGCLIP_CHECK_LAUNCH("seg_sieve (vote)");
+    hipLaunchKernelGGL(seg_sieve_final_kernel, grid, block, 0, ST, s);
+    SEGCLIP_CHECK_LAUNCH("seg_sieve (final)");
+    in = s.out;
   }
   return 0;
 }

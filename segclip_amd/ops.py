@@ -2934,6 +2934,38 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
         cleaned.numel() if cleaned is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_components")
 
 
+SEG_SIEVE_MAX_ROUNDS = 8
+
+
+def seg_sieve(table, n_blocks, labels, connectivity=8, skip_label=None, min_area=0, orphan_fill=None, rounds=1, cleaned=None,
+              max_side=None):
+    """Despeckling by merging (segclip_seg_sieve; the definition stands in include/segclip_hip.h): under the table of
+    seg_components_table, every component of the flat uint8 `labels` with fewer than min_area pixels takes the label of its
+    largest kept 4-neighbour (among equal areas the smallest label), `rounds` (1 .. 8) times with the components formed anew.
+    A small component without a kept neighbour keeps its label, or becomes orphan_fill (a byte) after the last round.
+    cleaned: flat uint8 of the labels' size (a new tensor unless given; it may not overlap `labels`); only the pixels of the
+    table's images are written.  max_side: the largest h or w of the table (defaults to the limit).  No host
+    synchronisation.  -> cleaned."""
+    L.require_cuda(table, labels, cleaned)
+    _check_image_table("seg_sieve", table, SEG_CC_COLS, "seg_components_table")
+    if labels.dtype != torch.uint8 or not labels.is_contiguous():
+        raise ValueError("seg_sieve: labels is a contiguous uint8 tensor")
+    if cleaned is None:
+        cleaned = torch.zeros_like(labels)
+    if cleaned.dtype != torch.uint8 or not cleaned.is_contiguous():
+        raise ValueError("seg_sieve: cleaned is a contiguous uint8 tensor")
+    B = table.shape[0]
+    lib = L.load()
+    ws_bytes = lib.segclip_seg_sieve_ws_bytes(labels.numel(), B, int(n_blocks))
+    ws = _workspace("seg_sieve", ws_bytes, labels.device, 16)
+    L.check(lib.segclip_seg_sieve(
+        L.ptr(table), B, int(n_blocks), _max_side(max_side), L.ptr(labels), labels.numel(),
+        int(connectivity), -1 if skip_label is None else int(skip_label), int(min_area),
+        -1 if orphan_fill is None else int(orphan_fill), int(rounds), L.ptr(cleaned), cleaned.numel(), L.ptr(ws), ws_bytes,
+        L.stream()), "seg_sieve")
+    return cleaned
+
+
 # ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
 SEG_BOUNDARY_TILE = (32, 64)     # (rows, columns) of one wave's strip of segclip_seg_boundary; 64 is also its rows pass's chunk
 SEG_BOUNDARY_WAVES = 4           # consecutive strips of a map that share a workgroup

@@ -44,8 +44,11 @@ kernel adds the mIoU areas.  Not covered: the threshold sweep, render_raw, and t
 Objects (not in the reference): components labels the connected components of label maps on the device
 (csrc/segment_objects.inc) - ids whose value is the component's first pixel in raster order, so they depend on no scheduling -
 and returns them with a compact list of boxes, areas and coordinate sums; despeckle / Despeckle replace components below a
-minimum area by a fill label, and predict_raw / update_raw / eval_epoch take clean=, applied after refine=.  Not covered: the
-threshold sweep, render_raw, predict_list and update (apply despeckle to their maps).
+minimum area by a fill label, or with merge=True (csrc/segment_sieve.inc) by the label of their largest neighbour, in up to 8
+rounds - the mode for Context-59, COCO-Stuff, ADE and every with_bg=False configuration, where no class is the background and
+fill=0 would paint the specks with the first real class.  predict_raw / update_raw / eval_epoch take clean=, applied after
+refine=.  Not covered: the threshold sweep, render_raw, predict_list and update (apply despeckle to their maps); merging by
+the length of the shared border or by the picture's colours; more than 8 rounds in one call (call again).
 
 Boundary metrics (not in the reference): mIoU counts every pixel alike and hardly sees the borders that refine= and clean=
 exist to improve.  Boundary states the band radius of Boundary IoU (Cheng et al., CVPR 2021), boundary_bands returns the
@@ -487,21 +490,36 @@ def refine_labels(raws, labels, num_classes, transform, pamr):
 
 
 class Despeckle:
-    """Despeckling as a post-processing step of the label maps: every connected component (`connectivity` 4 or 8) with fewer
-    than `min_area` pixels becomes `fill`; the pixels of `skip_label` belong to no component and stay.  One pass: what became
-    `fill` is not merged again (csrc/segment_objects.inc; the definition stands in include/segclip_hip.h).  The reference has
-    no such step."""
+    """Despeckling as a post-processing step of the label maps: the connected components (`connectivity` 4 or 8) with fewer
+    than `min_area` pixels are removed; the pixels of `skip_label` belong to no component and stay.
+    merge=False: every such component becomes `fill`.  One pass: what became `fill` is not merged again
+    (csrc/segment_objects.inc, segclip_seg_components).  It suits vocabularies whose class 0 is the background.
+    merge=True: every such component takes the label of its largest neighbour among the components of at least min_area pixels
+    that touch it left, right, up or down (among equal areas the smallest label), `rounds` (1 .. 8) times with the components
+    formed anew: a speck nested in a speck needs two.  A small component that touches no such neighbour keeps its label, or
+    becomes `fill` after the last round; fill=None keeps it (csrc/segment_sieve.inc, segclip_seg_sieve).  It is for the
+    vocabularies without a background class, where a constant fill would paint the specks with a real class.
+    The definitions stand in include/segclip_hip.h.  The reference has no such step."""
 
-    def __init__(self, min_area, fill=0, connectivity=8, skip_label=None):
+    def __init__(self, min_area, fill=0, connectivity=8, skip_label=None, merge=False, rounds=1):
         if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 0:
             raise ValueError(f"Despeckle: min_area is a non-negative integer, got {min_area!r}")
-        if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
-            raise ValueError(f"Despeckle: fill is an integer in 0 .. 255, got {fill!r}")
+        if not isinstance(merge, bool):
+            raise ValueError(f"Despeckle: merge is True or False, got {merge!r}")
+        if fill is None and not merge:
+            raise ValueError("Despeckle: fill=None (orphans keep their label) needs merge=True")
+        if fill is not None and (isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255):
+            raise ValueError(f"Despeckle: fill is an integer in 0 .. 255{' or None' if merge else ''}, got {fill!r}")
         if isinstance(connectivity, bool) or connectivity not in (4, 8):
             raise ValueError(f"Despeckle: connectivity is 4 or 8, got {connectivity!r}")
         if skip_label is not None and (isinstance(skip_label, bool) or not isinstance(skip_label, int) or not 0 <= skip_label <= 255):
             raise ValueError(f"Despeckle: skip_label is None or an integer in 0 .. 255, got {skip_label!r}")
+        if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= ops.SEG_SIEVE_MAX_ROUNDS:
+            raise ValueError(f"Despeckle: rounds is an integer in 1 .. {ops.SEG_SIEVE_MAX_ROUNDS}, got {rounds!r}")
+        if rounds != 1 and not merge:
+            raise ValueError(f"Despeckle: rounds={rounds} needs merge=True (the fill mode is one pass)")
         self.min_area, self.fill, self.connectivity, self.skip_label = min_area, fill, connectivity, skip_label
+        self.merge, self.rounds = merge, rounds
 
 
 class Objects:
@@ -561,17 +579,21 @@ def _despeckle_maps(maps, clean):
     batch = _Maps.of(maps)
     table, n_blocks, side = ops.seg_components_table(batch.sizes, batch.offs, batch.flat.device)
     out = batch.empty_like()
-    ops.seg_components(table, n_blocks, batch.flat, connectivity=clean.connectivity, skip_label=clean.skip_label,
-                       min_area=clean.min_area, fill=clean.fill, cleaned=out.flat, max_side=side)
+    if clean.merge:
+        ops.seg_sieve(table, n_blocks, batch.flat, connectivity=clean.connectivity, skip_label=clean.skip_label,
+                      min_area=clean.min_area, orphan_fill=clean.fill, rounds=clean.rounds, cleaned=out.flat, max_side=side)
+    else:
+        ops.seg_components(table, n_blocks, batch.flat, connectivity=clean.connectivity, skip_label=clean.skip_label,
+                           min_area=clean.min_area, fill=clean.fill, cleaned=out.flat, max_side=side)
     return out
 
 
 @torch.no_grad()
-def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None):
+def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None, merge=False, rounds=1):
     """maps [(h_i, w_i) uint8 label maps] -> [(h_i, w_i) uint8], views of one new buffer: every connected component with fewer
-    than min_area pixels replaced by `fill` (see Despeckle), all maps in one call and without a host synchronisation.  The
-    inputs stay as they are."""
-    return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label)).views()
+    than min_area pixels replaced by `fill`, or with merge=True merged into its largest neighbour in `rounds` rounds (see
+    Despeckle), all maps in one call and without a host synchronisation.  The inputs stay as they are."""
+    return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label, merge, rounds)).views()
 
 
 class Boundary:

@@ -70,9 +70,19 @@ of one SegEvaluator.update captured, in ONE command and alternating within every
         -DSEG_WIDE_LANE_SCAN=1, in which every lane scans the classes of its own undecided pixels as the uint8 kernel does, and
         -DSEG_WIDE_LANE_SCAN_CLASSES=0, the wave-cooperative scan at every class count (the kernel switches from the first to
         the second above 32 classes); labels and areas compared.
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide] [reps=7]
+With --merge instead: despeckling by merging (despeckle(merge=True), csrc/segment_sieve.inc) on the label maps of --objects, in
+ONE command and alternating within every repeat:
+  (xii) despeckle(min_area=16) as shipped (the yardstick: the fill mode, the same kernels as before the feature), despeckle(...,
+        merge=True) at rounds 1 and 2, one SegEvaluator.update_raw and one update_raw(clean=Despeckle(16, merge=True)), and the
+        host route on the same maps: .cpu(), scipy.ndimage.label per class and a dilation per small component (without scipy:
+        unmeasured); the share of labels each mode changes, the clock held, the run-to-run spread; then one 500 x 500 map that is
+        one component, one 4-connected checkerboard (orphans only) and 3-label noise under both connectivities (most pixels
+        vote), fill mode against one and two rounds each; and the kernels' own times from a
+        separate `rocprofv3 --kernel-trace --stats` child (--merge-child: five one-round calls on the 64 maps and nothing else)
+        with the vote and final kernels' bytes per second against their design traffic.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge] [reps=7]
                                  [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt]"""
+                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt]"""
 import os
 import statistics
 import sys
@@ -94,12 +104,13 @@ REFINE, REFINE_CHILD = ("--refine" in sys.argv[1:]), ("--refine-child" in sys.ar
 OBJECTS, OBJECTS_CHILD = ("--objects" in sys.argv[1:]), ("--objects-child" in sys.argv[1:])
 BOUNDARY, BOUNDARY_CHILD = ("--boundary" in sys.argv[1:]), ("--boundary-child" in sys.argv[1:])
 WIDE = "--wide" in sys.argv[1:]
+MERGE, MERGE_CHILD = ("--merge" in sys.argv[1:]), ("--merge-child" in sys.argv[1:])
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
-                                             "--boundary-child", "--wide")]
+                                             "--boundary-child", "--wide", "--merge", "--merge-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -839,6 +850,133 @@ def objects_child(model, text):
     torch.cuda.synchronize()
 
 
+def host_merge(a, min_area, ndimage):
+    """One round of the merge on the host: scipy.ndimage.label per class, a cross dilation per small component."""
+    cross, ones = ndimage.generate_binary_structure(2, 1), [[1, 1, 1]] * 3
+    comp, areas, labels = a.astype("int64") * 0, [0], [-1]
+    for v in set(a.reshape(-1).tolist()):
+        lab, n = ndimage.label(a == v, structure=ones)
+        comp[lab > 0] = lab[lab > 0] + len(areas) - 1
+        areas += [int(x) for x in ndimage.sum_labels(lab > 0, lab, range(1, n + 1))]
+        labels += [v] * n
+    out = a.copy()
+    for k, sl in enumerate(ndimage.find_objects(comp), start=1):
+        if areas[k] >= min_area:
+            continue
+        box = tuple(slice(max(s.start - 1, 0), s.stop + 1) for s in sl)   # the component's box, one pixel wider
+        mask = comp[box] == k
+        ring = ndimage.binary_dilation(mask, structure=cross) & ~mask
+        cand = [c for c in set(comp[box][ring].tolist()) if areas[c] >= min_area]
+        if cand:
+            out[box][mask] = labels[min(cand, key=lambda c: (-areas[c], labels[c]))]
+    return out
+
+
+def merge_case(model, text, n_images=64):
+    """(xii) despeckling by merging (csrc/segment_sieve.inc) on the label maps of --objects, alternating within every repeat"""
+    from segclip_amd.segmentation import Despeckle, SegEvaluator, despeckle
+    from tools import rocprof_roofline as rr
+    name = f"(xii) merge {n_images} mixed sizes"
+    seg, tf, raws, gts, maps = objects_maps(model, text, n_images)
+    pixels = sum(int(m.numel()) for m in maps)
+    m = 16
+    d = Despeckle(m, merge=True)
+    plain, cleaned_ev = SegEvaluator(seg), SegEvaluator(seg)
+    # the host route comes last and update_raw first: the short calls do not follow the quarter second in which the device idles
+    ways = [("update_raw", lambda: plain.update_raw(raws, gts, tf), 2),
+            (f"update_raw(clean=Despeckle({m}, merge=True))", lambda: cleaned_ev.update_raw(raws, gts, tf, clean=d), 2),
+            (f"despeckle(min_area={m}) as shipped: the yardstick", lambda: despeckle(maps, m), 4),
+            (f"despeckle(min_area={m}, merge=True)", lambda: despeckle(maps, m, merge=True), 4),
+            (f"despeckle(min_area={m}, merge=True, rounds=2)", lambda: despeckle(maps, m, merge=True, rounds=2), 4)]
+    try:
+        from scipy import ndimage
+        ways.append((".cpu() + scipy.ndimage.label per class + a dilation per small component, one round",
+                     lambda: [host_merge(a.cpu().numpy(), m, ndimage) for a in maps], 1))
+    except ImportError:
+        ndimage = None
+    with torch.no_grad():
+        one, two = despeckle(maps, m, merge=True), despeckle(maps, m, merge=True, rounds=2)
+        changed = [sum(int((a != b).sum()) for a, b in zip(x, maps)) / pixels for x in (despeckle(maps, m), one, two)]
+        if ndimage is not None:
+            assert all(bool((torch.from_numpy(host_merge(a.cpu().numpy(), m, ndimage)).cuda() == b).all())
+                       for a, b in zip(maps[:8], one)), "the host route merges otherwise"
+        for _, fn, _ in ways[:5]:
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for rep in range(REPS):
+            for k, (_, fn, inner) in enumerate(ways):
+                if k == 5 and rep >= 3:
+                    continue   # the host route: three repeats
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    say(f"{name}: {pixels} pixels in the label maps of update_raw; below {m} pixels the fill changes {changed[0]:.4%} of the labels, "
+        f"one round of merging {changed[1]:.4%}, two rounds {changed[2]:.4%}")
+    meds = [statistics.median(t) for t in ts]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:84s} {med * 1e3:9.3f} ms (min {min(t) * 1e3:.3f}, max {max(t) * 1e3:.3f}; {len(t)} x {inner} calls)")
+    spread = max((max(t) - min(t)) / statistics.median(t) for t in ts[:5])
+    say(f"{name}: merging / the fill mode {meds[3] / meds[2]:.3f} (one round), {meds[4] / meds[2]:.3f} (two); clean= adds "
+        f"{(meds[1] - meds[0]) * 1e3:.3f} ms to update_raw ({meds[1] / meds[0]:.4f} x)"
+        + (f"; host route / one round {meds[5] / meds[3]:.1f}" if len(meds) > 5 else "; host route: unmeasured (no scipy here)")
+        + f"; largest run-to-run spread {spread:.4f} of the median; clock {clk}")
+    # how much the vote costs where most pixels vote: one kept component, orphans only, and noise whose components are mostly small
+    side = 500
+    g = torch.Generator().manual_seed(2)
+    yy, xx = torch.meshgrid(torch.arange(side), torch.arange(side), indexing="ij")
+    for what, a, conn in (("one component", torch.ones(side, side, dtype=torch.uint8), 8),
+                          ("checkerboard, 4-connectivity", ((yy + xx) % 2).to(torch.uint8), 4),
+                          ("3-label noise, 4-connectivity", torch.randint(0, 3, (side, side), generator=g).to(torch.uint8), 4),
+                          ("3-label noise", torch.randint(0, 3, (side, side), generator=g).to(torch.uint8), 8)):
+        flat = a.cuda().reshape(-1)
+        table, n_blocks, max_side = ops.seg_components_table([(side, side)], [0], "cuda")
+        out, filled = torch.zeros_like(flat), torch.zeros_like(flat)
+        kw = dict(connectivity=conn, min_area=m, max_side=max_side)
+        t_fill = timed(lambda: ops.seg_components(table, n_blocks, flat, cleaned=filled, **kw), 20)
+        t_one = timed(lambda: ops.seg_sieve(table, n_blocks, flat, cleaned=out, **kw), 20)
+        share = float((out != flat).float().mean())
+        t_two = timed(lambda: ops.seg_sieve(table, n_blocks, flat, cleaned=out, rounds=2, **kw), 20)
+        say(f"{name}: {side} x {side} {what:30s} one round changes {share:8.4%} of the labels: fill mode {t_fill[0] * 1e6:7.1f} us, "
+            f"one round {t_one[0] * 1e6:7.1f} us (min {t_one[1] * 1e6:.1f}, max {t_one[2] * 1e6:.1f}), two rounds {t_two[0] * 1e6:7.1f} us "
+            f"({REPS} x 20 calls)")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--merge-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    rows = [r for r in table if "seg_cc_" in r[0] or "seg_sieve_" in r[0]]
+    if not rows:
+        say(f"{name}: the kernels alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+    for r in rows:
+        tag = "seg_sieve_" if "seg_sieve_" in r[0] else "seg_cc_"
+        per = r[2] / 5
+        note = ""
+        if "seg_sieve_vote" in r[0]:   # design traffic: 4 B of root + 4 B of gathered area per pixel; the small pixels' extra reads are few
+            note = f"   {8 * pixels / (per * 1e-6) / 1e12:.2f} TB/s of its 8 B per pixel ({8 * pixels / (per * 1e-6) / HBM_PEAK:.1%} of the HBM peak)"
+        if "seg_sieve_final" in r[0]:  # 4 B of root + 4 B of area + 1 B read, 1 B written
+            note = f"   {10 * pixels / (per * 1e-6) / 1e12:.2f} TB/s of its 10 B per pixel ({10 * pixels / (per * 1e-6) / HBM_PEAK:.1%} of the HBM peak)"
+        say(f"{name}: {r[0][r[0].find(tag):][:36]:36s} alone (rocprofv3 --kernel-trace --stats, {r[1]} launches in 5 calls) {per:9.1f} us per call{note}")
+    if rows:
+        say(f"{name}: all kernels of one round {sum(r[2] for r in rows) / 5:9.1f} us per call (the clearing of the slots is a fill, not in this list)")
+
+
+def merge_child(model, text):
+    """Five one-round calls of despeckle(merge=True) on the 64 label maps: what the rocprofv3 child of merge_case traces."""
+    from segclip_amd.segmentation import despeckle
+    maps = objects_maps(model, text)[4]
+    for _ in range(5):
+        despeckle(maps, 16, merge=True)
+    torch.cuda.synchronize()
+
+
 class _BoundaryCall:
     """segclip_seg_boundary on a list of label maps and ground truths, the outputs allocated once."""
 
@@ -1136,7 +1274,12 @@ if __name__ == "__main__":
     if BOUNDARY_CHILD:
         boundary_child(model, text)
         sys.exit(0)
-    if WIDE:
+    if MERGE_CHILD:
+        merge_child(model, text)
+        sys.exit(0)
+    if MERGE:
+        merge_case(model, text)
+    elif WIDE:
         wide_case(model)
     elif BOUNDARY:
         boundary_case(model, text)
