@@ -1224,6 +1224,12 @@ typedef struct segclip_gemm_route {
   int32_t variant;
 } segclip_gemm_route;
 int segclip_gemm_last_route(segclip_gemm_route* out);
+/* Test hook: the plan of segclip_gemm(d) without the launch - a pure function of the descriptor (its pointers, ws and colsum_ws
+ * are read for presence and alignment, never dereferenced) and the tuning switches; runs on a machine without a GPU.  *out (nullable)
+ * is the route segclip_gemm(d) would note, family NONE where it would launch nothing; *ws_bytes (nullable) is
+ * segclip_gemm_ws_bytes(d) (0 for an empty problem, M or N = 0, and for a null descriptor or negative sizes).  Returns what segclip_gemm(d) would return before launching (0, SEGCLIP_ERR_INVALID,
+ * SEGCLIP_ERR_UNSUPPORTED) and sets the same message. */
+int segclip_gemm_plan(const segclip_gemm_desc* d, segclip_gemm_route* out, size_t* ws_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Test hook: which attention kernel instance the last segclip_attn_fwd / segclip_attn_bwd call on the calling thread launched

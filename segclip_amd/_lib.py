@@ -110,6 +110,7 @@ SIGNATURES = {
     "segclip_wgrad_group_model_us": (C.c_double, [i64, i64, C.c_int]),
     "segclip_gemm_pq_half_tail": (C.c_int, [i64]),
     "segclip_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
+    "segclip_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmRoute), C.POINTER(C.c_size_t)]),
     "segclip_wgrad_group_ws_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "segclip_wgrad_group": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, C.c_size_t, vp]),
     "segclip_layernorm_fwd_multi": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, vp]),

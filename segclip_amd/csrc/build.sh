@@ -14,7 +14,7 @@ pids=()
 J=${BUILD_JOBS:-$(nproc)}
 throttle() { while [ "$(jobs -rp | wc -l)" -ge "$J" ]; do wait -n || true; done; }
 # the 8-phase GEMM (and likewise gemm_bf16_dma.hip, DMA_PART) is compiled once per operand layout (P8_PART 0..3) and its
-# dispatcher as part 4: the slow parts build in parallel
+# family launcher as part 4: the slow parts build in parallel.  Which kernel runs is decided in gemm_plan.cpp (host code only)
 rm -f build/gemm_bf16.o
 for part in 0 1 2 3 4; do   # the register-staged kernel first: its parts are the longest single jobs
   f=gemm_bf16.hip; o=build/gemm_bf16_part$part.o
@@ -31,7 +31,7 @@ for part in 0 1 2 3 4; do
     pids+=($!)
   fi
 done
-for part in 0 1 2 3; do   # AGPR-accumulator 256x256 kernel (gemm_bf16_pq.hip): forward layout, data-gradient layout, dispatcher, weight-gradient layout
+for part in 0 1 2 3; do   # AGPR-accumulator 256x256 kernel (gemm_bf16_pq.hip): forward layout, data-gradient layout, family launcher, weight-gradient layout
   f=gemm_bf16_pq.hip; o=build/gemm_bf16_pq_part$part.o
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$newest_hdr" -nt "$o" ]; then
     throttle; $HIPCC $FLAGS -DPQ_PART=$part -c $f -o $o &
@@ -46,7 +46,7 @@ for part in 0 1 2 3 4; do
     pids+=($!)
   fi
 done
-for f in gemm_f32.hip layernorm.hip attention.hip misc.hip group_linear.hip head.hip center.hip segment.hip retrieval.hip optim.hip capi.cpp exec.cpp; do
+for f in gemm_f32.hip layernorm.hip attention.hip misc.hip group_linear.hip head.hip center.hip segment.hip retrieval.hip optim.hip capi.cpp gemm_plan.cpp exec.cpp; do
   [ -f "$f" ] || continue
   o=build/${f%.*}.o
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$newest_hdr" -nt "$o" ]; then

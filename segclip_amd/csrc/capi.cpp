@@ -2,12 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "common.h"
-
-int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream);
-int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream);
-size_t segclip_gemm_bf16_ws_bytes(const segclip_gemm_desc* d);
-int segclip_gemm_bf16_splits(const segclip_gemm_desc* d);
+#include "gemm_plan.h"
 
 static thread_local char g_err[512] = "";
 
@@ -21,25 +16,27 @@ void segclip_set_error(const char* fmt, ...) {
 extern "C" int segclip_version(void) { return SEGCLIP_ABI_VERSION; }
 extern "C" const char* segclip_last_error_string(void) { return g_err; }
 
-extern "C" size_t segclip_gemm_ws_bytes(const segclip_gemm_desc* d) {
-  if (d->b_dtype == SEGCLIP_BF16) return segclip_gemm_bf16_ws_bytes(d);
-  return 0;
-}
+// reads of the planner (gemm_plan.cpp), which segclip_gemm consults through gemm_plan()
+extern "C" size_t segclip_gemm_ws_bytes(const segclip_gemm_desc* d) { return gemm_splitk_ws_bytes(d); }
+extern "C" int segclip_gemm_splits(const segclip_gemm_desc* d) { return gemm_splits(d); }
+// the number of tail tiles a launch over `ntiles` 256 x 256 tiles runs as half-tiles (0 = none); its grid is ntiles + that
+extern "C" int segclip_gemm_pq_half_tail(int64_t ntiles) { return gemm_pq_half_tail(ntiles); }
 
-extern "C" int segclip_gemm_splits(const segclip_gemm_desc* d) {
-  if (d->b_dtype == SEGCLIP_BF16 && !(d->a_dtype == SEGCLIP_F32 && d->b_dtype == SEGCLIP_F32)) return segclip_gemm_bf16_splits(d);
-  return 1;
-}
+static const segclip_gemm_route NO_ROUTE = {SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
+static thread_local segclip_gemm_route g_route = NO_ROUTE;
 
-static thread_local segclip_gemm_route g_route = {SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
-
-void segclip_gemm_route_note(int family, bool a_ks, bool b_ks, int tile_m, int tile_n, int splits, int variant) {
-  g_route = segclip_gemm_route{family, a_ks, b_ks, tile_m, tile_n, splits, variant};
-}
+void segclip_gemm_route_note(const segclip_gemm_route& route) { g_route = route; }
 
 extern "C" int segclip_gemm_last_route(segclip_gemm_route* out) {
   if (out) *out = g_route;
   return g_route.family == SEGCLIP_GEMM_ROUTE_NONE ? SEGCLIP_ERR_UNSUPPORTED : 0;
+}
+
+extern "C" int segclip_gemm_plan(const segclip_gemm_desc* d, segclip_gemm_route* out, size_t* ws_bytes) {
+  const GemmPlan p = gemm_plan(d);
+  if (out) *out = p.route;
+  if (ws_bytes) *ws_bytes = p.ws_bytes;
+  return p.rc;
 }
 
 static thread_local segclip_attn_route g_attn_route = {SEGCLIP_ATTN_ROUTE_NONE, SEGCLIP_ATTN_ROUTE_NONE, 0, 0};
@@ -53,28 +50,20 @@ extern "C" int segclip_attn_last_route(segclip_attn_route* out) {
   return g_attn_route.fwd_kernel == SEGCLIP_ATTN_ROUTE_NONE && g_attn_route.bwd_kernel == SEGCLIP_ATTN_ROUTE_NONE ? SEGCLIP_ERR_UNSUPPORTED : 0;
 }
 
-extern "C" int segclip_gemm(const segclip_gemm_desc* d, void* stream) {
-  g_route = segclip_gemm_route{SEGCLIP_GEMM_ROUTE_NONE, 0, 0, 0, 0, 0, 0};
-  SEGCLIP_REQUIRE(d != nullptr, "gemm: null descriptor");
-  SEGCLIP_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "gemm: negative size");
-  if (d->M == 0 || d->N == 0) return 0;
-  SEGCLIP_REQUIRE(d->A && d->B && d->C, "gemm: null operand");
-  SEGCLIP_REQUIRE(!d->mul_dact || d->aux, "gemm: mul_dact needs aux");
-  SEGCLIP_REQUIRE(d->aux_kind == 0 || ((d->aux_kind == 1 || d->aux_kind == 2) && d->act == SEGCLIP_ACT_QUICK_GELU) ||
-                      (d->aux_kind == 2 && d->act == SEGCLIP_ACT_GELU_ERF),
-                  "gemm: aux_kind 1 (aux = act'(pre-activation) in the output type) is implemented for QuickGELU only, aux_kind 2 for QuickGELU and erf-GELU");
-  SEGCLIP_REQUIRE(d->aux_kind != 2 || (d->a_dtype == SEGCLIP_BF16 && d->b_dtype == SEGCLIP_BF16 && d->c_dtype == SEGCLIP_BF16),
-                  "gemm: aux_kind 2 (one byte per element) needs bf16 operands and output");
-  if (d->res_row_mod > 0 && !(d->a_dtype == SEGCLIP_BF16 && d->b_dtype == SEGCLIP_BF16)) {
-    segclip_set_error("gemm: res_row_mod is a bf16-operand feature");
-    return SEGCLIP_ERR_UNSUPPORTED;
+// plan (gemm_plan.cpp: every decision), note the route, one launcher per family, the trailing reductions
+extern "C" int segclip_gemm(const segclip_gemm_desc* d, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  g_route = NO_ROUTE;
+  const GemmPlan p = gemm_plan(d);
+  if (p.rc != 0 || p.route.family == SEGCLIP_GEMM_ROUTE_NONE) return p.rc;
+  g_route = p.route;
+  switch (p.route.family) {
+    case SEGCLIP_GEMM_ROUTE_GENERIC: segclip_gemm_launch_generic(d, p, stream); break;
+    case SEGCLIP_GEMM_ROUTE_DMA: segclip_gemm_launch_dma(d, p, stream); break;
+    case SEGCLIP_GEMM_ROUTE_P8: segclip_gemm_launch_p8(d, p, stream); break;
+    case SEGCLIP_GEMM_ROUTE_PQ: segclip_gemm_launch_pq(d, p, stream); break;
+    default: segclip_gemm_launch_f32(d, p, stream);
   }
-  if (d->a_dtype == SEGCLIP_F32 && d->b_dtype == SEGCLIP_F32) {
-    SEGCLIP_REQUIRE(d->c_dtype == SEGCLIP_F32 && (!d->residual || d->r_dtype == SEGCLIP_F32),
-                    "gemm f32: output / residual must be f32");
-    return segclip_gemm_f32_launch(d, (hipStream_t)stream);
-  }
-  if (d->b_dtype == SEGCLIP_BF16) return segclip_gemm_bf16_launch(d, (hipStream_t)stream);
-  segclip_set_error("gemm: unsupported dtype combination a=%d b=%d", d->a_dtype, d->b_dtype);
-  return SEGCLIP_ERR_UNSUPPORTED;
+  SEGCLIP_CHECK_LAUNCH(p.route.family == SEGCLIP_GEMM_ROUTE_F32 ? "gemm_f32" : "gemm_bf16");
+  return segclip_gemm_launch_reductions(d, p, stream);
 }

@@ -19,8 +19,8 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 #define SEGCLIP_WAVE 64
 
 void segclip_set_error(const char* fmt, ...);
-// host: records the kernel instance a GEMM launch site is about to launch (segclip_gemm_last_route; capi.cpp)
-void segclip_gemm_route_note(int family, bool a_ks, bool b_ks, int tile_m, int tile_n, int splits, int variant);
+// host: records the planned kernel instance of the GEMM that is about to be launched (segclip_gemm_last_route; capi.cpp)
+void segclip_gemm_route_note(const segclip_gemm_route& route);
 // host: the same for the attention entries (segclip_attn_last_route; capi.cpp).  Clears the other direction's field.
 void segclip_attn_route_note(bool bwd, int kernel, int tiles, int variant);
 // host: the current device (below 64) and its CU count, read once per device (attention.hip); false where there is none

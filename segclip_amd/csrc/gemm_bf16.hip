@@ -17,6 +17,8 @@
 // barrier per K-step).  All loads are unconditional from clamped addresses (no divergent branch around a
 // load).  Workgroup ids are remapped so each XCD walks a contiguous run of tiles (A panel reuse in its L2).
 // Split-K (grid.y) for the wgrad shapes, combined by a deterministic slab reduction.
+// This kernel takes what the planner (gemm_plan.cpp) gives to no LDS-DMA kernel; its launcher at the end of this file fills
+// Args from the plan and decides nothing.  The trailing reductions of every bf16 family (segclip_gemm, capi.cpp) are here too.
 #include <stdlib.h>
 
 #include "gemm_bf16_common.h"
@@ -24,7 +26,7 @@
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64, NT = 256;
+constexpr int BM = GEMM_TILE, BN = GEMM_TILE, BK = GEMM_BK, NT = 256;
 constexpr int KS_PITCH = 160;                 // elements per k-row of a k-strided image (320 B)
 constexpr int SZ_DIRECT = BM * BK * 2;        // 16384 B
 constexpr int SZ_KS = BK * KS_PITCH * 2;      // 20480 B
@@ -331,21 +333,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_vec_kernel(const float* __r
 
 // Compiled once per GB_PART (build.sh), like gemm_bf16_p8.hip: parts 0..3 hold the four kernel instances (fp32 / bf16
 // left operand x aligned / ragged) of one operand layout <A_KS = part>>1, B_KS = part&1> behind a launcher; part 4 is
-// the split-K reduction kernels and the host-side dispatcher.
+// the split-K reduction kernels, the family's launcher and the trailing reductions of segclip_gemm.
 #ifndef GB_PART
 #error "compile with -DGB_PART=0..4 (see build.sh)"
 #endif
-#define GB_LAUNCHER(NAME, AK, BKS)                                                                              \
-  void NAME(bool a_f32, bool fast, dim3 grid, hipStream_t stream, const void* args) {                           \
-    const Args g = *reinterpret_cast<const Args*>(args);                                                        \
-    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_GENERIC, AK, BKS, BM, BN, g.splits, (a_f32 ? 1 : 0) | (fast ? 2 : 0)); \
-    if (a_f32) {                                                                                                \
-      if (fast) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, true, true>), grid, dim3(NT), 0, stream, g);      \
-      else hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, true, false>), grid, dim3(NT), 0, stream, g);          \
-    } else {                                                                                                    \
-      if (fast) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, false, true>), grid, dim3(NT), 0, stream, g);     \
-      else hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKS, false, false>), grid, dim3(NT), 0, stream, g);         \
-    }                                                                                                           \
+// route variant (gemm_plan.cpp): bit 0 = fp32 A operand, bit 1 = 16-byte aligned (unguarded) operand loads
+#define GB_LAUNCHER(NAME, AK, BKS)                                                                    \
+  void NAME(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {                      \
+    typedef void (*kernel_t)(Args);                                                                   \
+    static const kernel_t kernels[2][2] = {{gemm_bf16_kernel<AK, BKS, true, true>, gemm_bf16_kernel<AK, BKS, true, false>},   \
+                                           {gemm_bf16_kernel<AK, BKS, false, true>, gemm_bf16_kernel<AK, BKS, false, false>}}; \
+    const int v = p.route.variant;   /* [bf16 A][ragged]: the order in which the code object holds the instances */  \
+    hipLaunchKernelGGL(kernels[!(v & 1)][!(v & 2)], gemm_grid(p), dim3(NT), 0, stream, gemm_args(d, p));               \
   }
 #if GB_PART == 0
 GB_LAUNCHER(segclip_gb_launch_ff, false, false)
@@ -358,160 +357,33 @@ GB_LAUNCHER(segclip_gb_launch_kk, true, true)
 #endif
 
 #if GB_PART == 4
-void segclip_gb_launch_ff(bool, bool, dim3, hipStream_t, const void*);
-void segclip_gb_launch_fk(bool, bool, dim3, hipStream_t, const void*);
-void segclip_gb_launch_kf(bool, bool, dim3, hipStream_t, const void*);
-void segclip_gb_launch_kk(bool, bool, dim3, hipStream_t, const void*);
+void segclip_gb_launch_ff(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_gb_launch_fk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_gb_launch_kf(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_gb_launch_kk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
 
-bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args, int splits, int64_t kper, int64_t nb,
-                               hipStream_t stream);
-bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args, int splits, int64_t kper, int64_t nb,
-                              hipStream_t stream);
-bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args, int splits, int64_t nb, hipStream_t stream);
-int segclip_gemm_bf16_dma_pick_bn(const segclip_gemm_desc* d, int64_t nbatch_splits);
-
-static bool aligned16(const segclip_gemm_desc* d) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
-  const int64_t lda = a_ks ? d->sak : d->sam, ldb = b_ks ? d->sbk : d->sbn;
-  const int64_t aes = d->a_dtype == SEGCLIP_F32 ? 4 : 2;
-  bool fast = al(d->A) && al(d->B) && lda % 8 == 0 && ldb % 8 == 0 && (d->bsA1 * aes) % 16 == 0 &&
-              (d->bsA2 * aes) % 16 == 0 && (d->bsB1 * 2) % 16 == 0 && (d->bsB2 * 2) % 16 == 0;
-  fast = fast && (a_ks ? (d->M % 8 == 0 && d->M >= 8) : (d->K % 8 == 0 && d->K >= 8));
-  fast = fast && (b_ks ? (d->N % 8 == 0 && d->N >= 8) : (d->K % 8 == 0 && d->K >= 8));
-  return fast;
-}
-// the LDS-DMA kernel (256x128 tiles) takes the large aligned bf16 x bf16 problems
-static bool want_dma(const segclip_gemm_desc* d) {
-  return d->a_dtype == SEGCLIP_BF16 && d->b_dtype == SEGCLIP_BF16 && aligned16(d) && d->K % 64 == 0 && d->K >= 64 &&
-         d->M >= 64 && d->N >= 16;
-}
-static int choose_splits(const segclip_gemm_desc* d) {
-  if (d->bias || d->residual || d->aux || d->act != SEGCLIP_ACT_NONE || d->mul_dact) return 1;
-  const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * (d->nb2 > 0 ? d->nb2 : 1);
-  const int64_t ksteps = cdiv(d->K, BK);
-  if (want_dma(d)) {
-    // 256-row tiles, long K loops: aim at one full round of the 256 CUs
-    const int64_t bn = d->N > 128 ? 256 : 128;
-    const int64_t tiles = cdiv(d->M, 256) * cdiv(d->N, bn) * nb;
-    if (tiles >= 160 || ksteps < 32) return 1;
-    int64_t s = 256 / tiles;
-    if (s > ksteps / 8) s = ksteps / 8;
-    if (s > 32) s = 32;
-    return s < 1 ? 1 : (int)s;
-  }
-  const int64_t tiles = cdiv(d->M, BM) * cdiv(d->N, BN) * nb;
-  if (tiles >= 384 || ksteps < 16) return 1;
-  int64_t s = cdiv(768, tiles);
-  if (s > ksteps / 4) s = ksteps / 4;
-  if (s > 32) s = 32;
-  return s < 1 ? 1 : (int)s;
+void segclip_gemm_launch_generic(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
+  static const gemm_layout_launcher layouts[4] = {segclip_gb_launch_ff, segclip_gb_launch_fk, segclip_gb_launch_kf, segclip_gb_launch_kk};
+  layouts[gemm_layout_index(p)](d, p, stream);
 }
 
-size_t segclip_gemm_bf16_ws_bytes(const segclip_gemm_desc* d) {
-  const int s = choose_splits(d);
-  if (s <= 1) return 0;
-  const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * (d->nb2 > 0 ? d->nb2 : 1);
-  return (size_t)s * nb * d->M * d->N * sizeof(float);
-}
-
-// number of K splits segclip_gemm_bf16_launch() will use for this descriptor (1 = no split-K, nothing in ws)
-int segclip_gemm_bf16_splits(const segclip_gemm_desc* d) {
-  int splits = choose_splits(d);
-  if (splits > 1 && (d->ws == nullptr || (size_t)d->ws_bytes < segclip_gemm_bf16_ws_bytes(d))) splits = 1;
-  if (splits <= 1) return 1;
-  const int64_t kper = cdiv(cdiv(d->K, BK), splits) * BK;
-  return (int)cdiv(d->K, kper);
-}
-
-int segclip_gemm_bf16_launch(const segclip_gemm_desc* d, hipStream_t stream) {
-  const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
-  SEGCLIP_REQUIRE(!a_ks || d->sam == 1, "gemm_bf16: A needs unit stride along k or m (sam=%lld sak=%lld)",
-                  (long long)d->sam, (long long)d->sak);
-  SEGCLIP_REQUIRE(!b_ks || d->sbn == 1, "gemm_bf16: B needs unit stride along k or n (sbn=%lld sbk=%lld)",
-                  (long long)d->sbn, (long long)d->sbk);
-  SEGCLIP_REQUIRE(d->b_dtype == SEGCLIP_BF16, "gemm_bf16: B must be bf16");
-  const bool a_f32 = d->a_dtype == SEGCLIP_F32;
-  Args g;
-  g.A = d->A; g.B = (const bf16_t*)d->B; g.C = d->C; g.bias = d->bias; g.residual = d->residual; g.aux = d->aux;
-  g.M = d->M; g.N = d->N; g.K = d->K;
-  g.lda = a_ks ? d->sak : d->sam; g.ldb = b_ks ? d->sbk : d->sbn;
-  g.ldc = d->ldc; g.ldr = d->ldr; g.ldaux = d->ldaux;
-  g.nb2 = d->nb2 > 0 ? d->nb2 : 1;
-  g.bsA1 = d->bsA1; g.bsA2 = d->bsA2; g.bsB1 = d->bsB1; g.bsB2 = d->bsB2; g.bsC1 = d->bsC1; g.bsC2 = d->bsC2;
-  g.bsR1 = d->bsR1; g.bsR2 = d->bsR2;
-  g.c_dtype = d->c_dtype; g.r_dtype = d->r_dtype; g.act = d->act; g.mul_dact = d->mul_dact; g.aux_kind = d->aux_kind; g.alpha = d->alpha;
-  g.nbx = (int)cdiv(d->N, BN); g.nby = (int)cdiv(d->M, BM);
-  const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * g.nb2;
-  SEGCLIP_REQUIRE(nb <= 65535, "gemm_bf16: batch too large (%lld)", (long long)nb);
-  g.splits = choose_splits(d);
-  if (g.splits > 1 && (d->ws == nullptr || (size_t)d->ws_bytes < segclip_gemm_bf16_ws_bytes(d))) g.splits = 1;
-  g.kper = g.splits > 1 ? cdiv(cdiv(d->K, BK), g.splits) * BK : d->K;
-  if (g.splits > 1) g.splits = (int)cdiv(d->K, g.kper);
-  g.slab = (float*)d->ws;
-  g.vec_epi = 0;
-  g.stagger = 0;
-  static const int xw_epi = segclip_tuning_int("SEGCLIP_EPI_XW", 2);
-  g.xw_epi = xw_epi;
-  static const int slab_staged = segclip_tuning_int("SEGCLIP_P8_SLAB_STAGED", 1);
-  g.slab_staged = slab_staged;
-  g.colsum_part = nullptr;
-  dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)g.splits, (unsigned)nb);
-  const bool fast = aligned16(d);
-  bool launched = false;
-  if (d->colsum) {
-    SEGCLIP_REQUIRE(d->colsum_ws != nullptr, "gemm: colsum needs colsum_ws");
-    if (!(want_dma(d) && d->M % 128 == 0 && d->N % 256 == 0 && g.splits == 1 && nb == 1)) {
-      segclip_set_error("gemm: fused colsum unsupported for this shape");
-      return SEGCLIP_ERR_UNSUPPORTED;
-    }
-    g.colsum_part = d->colsum_ws;
-  }
-  if (d->res_row_mod > 0) {   // only gemm_bf16_pq.hip's fp32-residual epilogue addresses the residual modulo a row count
-    launched = want_dma(d) && nb == 1 && g.splits == 1 && segclip_gemm_bf16_pq_try(d, &g, 1, nb, stream);
-    if (!launched) {
-      segclip_set_error("gemm: res_row_mod needs the fp32-residual epilogue on full 256 x 256 bf16 tiles");
-      return SEGCLIP_ERR_UNSUPPORTED;
-    }
-  } else if (want_dma(d)) {
-    // 256x256 tiles: the accumulator-register kernel (gemm_bf16_pq.hip) where it takes the problem, else the
-    // phase-pipelined kernel (gemm_bf16_p8.hip); 256x128 / 128x128 tiles: the one-barrier-per-K-tile kernel (gemm_bf16_dma.hip)
-    if (segclip_gemm_bf16_dma_pick_bn(d, nb * g.splits) == 256) {
-      launched = segclip_gemm_bf16_pq_try(d, &g, g.splits, nb, stream);
-      if (!launched) launched = segclip_gemm_bf16_p8_try(d, &g, g.splits, g.kper, nb, stream);
-    }
-    if (!launched) launched = segclip_gemm_bf16_dma_try(d, &g, g.splits, g.kper, nb, stream);
-  }
-  if (d->colsum && (!launched || !g.colsum_part)) {
-    segclip_set_error("gemm: fused colsum unsupported for this shape");
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (!launched && d->aux_kind == 2 && d->aux) {
-    segclip_set_error("gemm: aux_kind 2 needs full 256 x 256 tiles, 16-byte aligned operands and no split-K");
-    return SEGCLIP_ERR_UNSUPPORTED;
-  }
-  if (!launched) {
-    if (!a_ks && !b_ks) segclip_gb_launch_ff(a_f32, fast, grid, stream, &g);
-    else if (!a_ks && b_ks) segclip_gb_launch_fk(a_f32, fast, grid, stream, &g);
-    else if (a_ks && b_ks) segclip_gb_launch_kk(a_f32, fast, grid, stream, &g);
-    else segclip_gb_launch_kf(a_f32, fast, grid, stream, &g);
-  }
-  SEGCLIP_CHECK_LAUNCH("gemm_bf16");
-  if (d->colsum && !(d->flags & SEGCLIP_GEMM_DEFER_COLSUM)) {
+// after the GEMM kernel of any bf16 family: the column-sum reduction and the split-K combine, unless the caller deferred them
+int segclip_gemm_launch_reductions(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
+  if (p.colsum && !(d->flags & SEGCLIP_GEMM_DEFER_COLSUM)) {
     launch_reduce_rows((const float*)d->colsum_ws, d->M / 64, d->N, d->N, d->colsum, nullptr, nullptr, d->N, stream);
     SEGCLIP_CHECK_LAUNCH("gemm_colsum_reduce");
   }
-  if (g.splits > 1 && !(d->flags & SEGCLIP_GEMM_DEFER_SPLITK)) {
-    const int64_t total = nb * d->M * d->N;
+  if (p.route.splits > 1 && !(d->flags & SEGCLIP_GEMM_DEFER_SPLITK)) {
+    const int64_t total = p.nb * d->M * d->N;
     const int blocks = (int)(cdiv(total, 256) < 2048 ? cdiv(total, 256) : 2048);
     const int64_t cal = d->c_dtype == SEGCLIP_BF16 ? 7 : 15;
-    if (nb == 1 && d->ldc == d->N && total % 4 == 0 && (reinterpret_cast<uintptr_t>(d->C) & cal) == 0 &&
+    if (p.nb == 1 && d->ldc == d->N && total % 4 == 0 && (reinterpret_cast<uintptr_t>(d->C) & cal) == 0 &&
         (reinterpret_cast<uintptr_t>(d->ws) & 15) == 0)
       hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)cdiv(total / 4, 256)), dim3(256), 0, stream,
-                         (const float*)d->ws, d->C, total / 4, g.splits, d->alpha, d->c_dtype);
+                         (const float*)d->ws, d->C, total / 4, p.route.splits, d->alpha, d->c_dtype);
     else
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)d->ws, d->C, d->M,
-                       d->N, d->ldc, g.nb2, d->bsC1, d->bsC2, g.splits, nb, d->alpha, d->c_dtype);
+                       d->N, d->ldc, d->nb2 > 0 ? d->nb2 : 1, d->bsC1, d->bsC2, p.route.splits, p.nb, d->alpha, d->c_dtype);
     SEGCLIP_CHECK_LAUNCH("splitk_reduce");
   }
   return 0;

@@ -1,7 +1,7 @@
 // Shared by the two bf16 GEMM kernels (register-staged gemm_bf16.hip, LDS-DMA gemm_bf16_dma.hip):
 // argument block and the fused epilogue of one wave's 64x64 sub-tile (2x2 MFMA 32x32 accumulators).
 #pragma once
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -21,6 +21,28 @@ struct Args {
   int slab_staged; // 8-phase kernel: split-K partial tiles through the staged epilogue (SEGCLIP_P8_SLAB_STAGED)
   int xw_epi;   // 8-phase kernel, bf16 outputs: cross-wave row pass (whole 128-byte lines per store; SEGCLIP_EPI_XW)
 };
+
+// host: the arguments of a planned launch (gemm_plan.h) - the descriptor's operands, the plan's decisions
+inline Args gemm_args(const segclip_gemm_desc* d, const GemmPlan& p) {
+  const GemmTuning& t = gemm_tuning();
+  Args g;
+  g.A = d->A; g.B = (const bf16_t*)d->B; g.C = d->C; g.bias = d->bias; g.residual = d->residual; g.aux = d->aux;
+  g.M = d->M; g.N = d->N; g.K = d->K;
+  g.lda = p.route.a_ks ? d->sak : d->sam; g.ldb = p.route.b_ks ? d->sbk : d->sbn;
+  g.ldc = d->ldc; g.ldr = d->ldr; g.ldaux = d->ldaux;
+  g.nb2 = d->nb2 > 0 ? d->nb2 : 1;
+  g.bsA1 = d->bsA1; g.bsA2 = d->bsA2; g.bsB1 = d->bsB1; g.bsB2 = d->bsB2; g.bsC1 = d->bsC1; g.bsC2 = d->bsC2;
+  g.bsR1 = d->bsR1; g.bsR2 = d->bsR2;
+  g.c_dtype = d->c_dtype; g.r_dtype = d->r_dtype; g.act = d->act; g.mul_dact = d->mul_dact; g.aux_kind = d->aux_kind; g.alpha = d->alpha;
+  g.nbx = p.nbx; g.nby = p.nby;
+  g.splits = p.route.splits; g.kper = p.kper; g.slab = (float*)d->ws;
+  g.colsum_part = p.colsum ? d->colsum_ws : nullptr;
+  g.vec_epi = p.vec_epi;
+  g.stagger = p.route.family == SEGCLIP_GEMM_ROUTE_P8 ? t.p8_stagger : 0;
+  g.xw_epi = t.epi_xw; g.slab_staged = t.p8_slab_staged;
+  return g;
+}
+inline dim3 gemm_grid(const GemmPlan& p) { return dim3((unsigned)(p.nbx * p.nby), (unsigned)p.route.splits, (unsigned)p.nb); }
 
 
 // ---- epilogue -------------------------------------------------------------------------------

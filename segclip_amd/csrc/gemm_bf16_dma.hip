@@ -18,14 +18,15 @@
 // MFMA operand fragments are register double-buffered (chunk kc+1 is requested before the MFMAs of kc).
 // Full tiles leave through the LDS-staged coalesced epilogue (gemm_bf16_common.h).
 // Rows beyond M / N are clamped to valid addresses (their products are never stored); K must be a
-// multiple of 64 (the host falls back to the register-staged kernel otherwise).
+// multiple of 64.  Which problems come here, and on which of the three tiles, is decided by gemm_plan.cpp (want_dma,
+// pick_bn, dma_small_tiles, dma_covers); the launcher at the end of this file fills Args from the plan and decides nothing.
 #include <stdlib.h>
 
 #include "gemm_bf16_common.h"
 
 namespace {
 
-constexpr int BK = 64;
+constexpr int BK = GEMM_BK;
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
@@ -238,18 +239,19 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
 }  // namespace
 
 // Compiled once per DMA_PART (build.sh), like gemm_bf16_p8.hip: parts 0..3 hold the kernel instances of one operand
-// layout <A_KS = part>>1, B_KS = part&1> behind a launcher, part 4 the host-side dispatcher.
+// layout <A_KS = part>>1, B_KS = part&1> behind a launcher, part 4 the family's launcher (no device code).
 #ifndef DMA_PART
 #error "compile with -DDMA_PART=0..4 (see build.sh)"
 #endif
-// variant: 0 = 256x128 tile, 1 = 256x256 tile, 2 = 128x128 tile / 4 waves (problems too small to fill the chip with
-// 256-row tiles)
+// indexed by the route variant (gemm_plan.h) from the back - DMA_128x128 (4 waves), DMA_256x256, DMA_256x128 - which is the
+// order in which the code object holds the instances
 #define DMA_LAUNCHER(NAME, AK, BKS)                                                                             \
-  void NAME(int variant, dim3 grid, hipStream_t stream, const void* args) {                                     \
-    const Args g = *reinterpret_cast<const Args*>(args);                                                        \
-    if (variant == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>), grid, dim3(256), 0, stream, g); \
-    else if (variant == 1) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 256, 8>), grid, dim3(512), 0, stream, g); \
-    else hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8>), grid, dim3(512), 0, stream, g);       \
+  void NAME(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {                                \
+    typedef void (*kernel_t)(Args);                                                                             \
+    static const kernel_t kernels[3] = {gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>, gemm_bf16_dma_kernel<AK, BKS, 256, 256, 8>, \
+                                        gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8>};                            \
+    const int v = p.route.variant;                                                                              \
+    hipLaunchKernelGGL(kernels[DMA_128x128 - v], gemm_grid(p), dim3(v == DMA_128x128 ? 256 : 512), 0, stream, gemm_args(d, p)); \
   }
 #if DMA_PART == 0
 DMA_LAUNCHER(segclip_dma_launch_ff, false, false)
@@ -262,85 +264,13 @@ DMA_LAUNCHER(segclip_dma_launch_kk, true, true)
 #endif
 
 #if DMA_PART == 4
-void segclip_dma_launch_ff(int, dim3, hipStream_t, const void*);
-void segclip_dma_launch_fk(int, dim3, hipStream_t, const void*);
-void segclip_dma_launch_kf(int, dim3, hipStream_t, const void*);
-void segclip_dma_launch_kk(int, dim3, hipStream_t, const void*);
+void segclip_dma_launch_ff(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_dma_launch_fk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_dma_launch_kf(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_dma_launch_kk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
 
-// tile-count heuristic: the 256x256 tile unless it leaves the 256 CUs badly quantised and 256x128 does not
-static int pick_bn(const segclip_gemm_desc* d, int64_t nbatch_splits) {
-  constexpr int BM = 256;
-  if (d->N <= 128) return 128;
-  auto eff = [&](int bn) {
-    const double tiles = (double)cdiv(d->M, BM) * cdiv(d->N, bn) * nbatch_splits;
-    const double rounds = tiles / 256.0;
-    const double q = rounds / (double)(int64_t)(rounds + 0.999999);  // quantisation efficiency
-    const double pad = (double)d->N / (cdiv(d->N, bn) * bn);
-    return q * pad * (bn == 256 ? 1.0 : 0.72);                       // 256x128 runs at ~0.72 of the 256x256 rate
-  };
-  return eff(256) >= eff(128) ? 256 : 128;
-}
-
-// tile width the dispatcher would use (the phase-pipelined 256x256 kernel of gemm_bf16_p8.hip takes the 256-wide cases)
-int segclip_gemm_bf16_dma_pick_bn(const segclip_gemm_desc* d, int64_t nbatch_splits) { return pick_bn(d, nbatch_splits); }
-
-// Launch the LDS-DMA kernel.  `args_` is prepared by the caller (gemm_bf16.hip); returns false when the shape
-// does not meet this kernel's preconditions (the caller then uses the register-staged kernel).
-bool segclip_gemm_bf16_dma_try(const segclip_gemm_desc* d, const void* args_, int splits, int64_t kper, int64_t nb,
-                               hipStream_t stream) {
-  Args g = *reinterpret_cast<const Args*>(args_);
-  const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
-  if (d->a_dtype != SEGCLIP_BF16 || d->b_dtype != SEGCLIP_BF16) return false;
-  if (d->K % BK != 0 || kper % BK != 0 || d->K < BK) return false;
-  if (a_ks && (d->M % 8 != 0 || d->M < 8)) return false;
-  if (b_ks && (d->N % 8 != 0 || d->N < 8)) return false;
-  if (d->M < 64 || d->N < 16) return false;  // tiny problems: the 128x128 kernel wastes less
-  // 128x128 tiles, 4 waves, 68 KiB of LDS -> two workgroups per CU: the per-tile prologue / output phase of one
-  // overlaps the MFMA phase of the other.  In isolation (tools/bench_gemm.py, MI355X) this wins 10-25 % on the
-  // forward GEMMs with fewer than 4 rounds of 256x256 tiles (N=768 of the vision tower, the whole text tower) and
-  // loses 5-15 % on long-K dgrads and every split-K wgrad; inside the training step (text tower concurrent on a
-  // second stream) a shape-based choice measured 58.4 vs 58.2 ms, i.e. no gain, so the 256-wide tiles stay the default.
-  // Round 4: problems whose 256-row tiles cannot fill the 256 CUs (the center stage's q-side linears: M = 8 B = 2048 rows,
-  // 48-192 tiles) take the 128x128 tile: four times the workgroups, two per CU, half the K-loop time per tile
-  // (SEGCLIP_GEMM_SMALL_TILES=0 switches the rule off; a forward + backward pass of the center stage: see DESIGN 4.4).
-  static const int small_rule = segclip_tuning_int("SEGCLIP_GEMM_SMALL_TILES", 1);
-  const int bn_big = pick_bn(d, nb * splits);
-  // fused column sums come from the staged epilogue of FULL tiles only (a partial tile takes the per-element epilogue, which
-  // writes no partial sums): M = 256 q + 128 runs them on the 128-row tiles, where every tile is full (M % 128 == 0 and
-  // N % 256 == 0 are checked by the caller)
-  const bool colsum_rows128 = g.colsum_part && d->M % 256 != 0;
-  const bool small = colsum_rows128 ||
-                     (small_rule && d->M >= 128 && d->N >= 128 && !(d->aux_kind == 2 && d->aux) && !g.colsum_part &&
-                      cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256);
-  const int bn = small ? 128 : bn_big;
-  const int bm = small ? 128 : 256;
-  g.nbx = (int)cdiv(d->N, bn);
-  g.nby = (int)cdiv(d->M, bm);
-  g.splits = splits;
-  g.kper = kper;
-  if (g.colsum_part && bn != 256 && d->N % 128 != 0) return false;
-  {
-    auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const int64_t ce = d->c_dtype == SEGCLIP_BF16 ? 8 : 4, re = d->r_dtype == SEGCLIP_BF16 ? 8 : 4;
-    g.vec_epi = al(d->C) && al(d->aux) && al(d->residual) && al(d->bias) && d->ldc % ce == 0 &&
-                (!d->aux || d->ldaux % ce == 0) && (!d->residual || d->ldr % re == 0) && d->bsC1 % ce == 0 &&
-                d->bsC2 % ce == 0 && (!d->residual || (d->bsR1 % re == 0 && d->bsR2 % re == 0));
-    if (d->residual && d->r_dtype != d->c_dtype) g.vec_epi = 0;   // the LDS epilogue holds side operands in the output type
-    if (g.colsum_part && !g.vec_epi) return false;
-    // the one-byte derivative of the erf-GELU is produced by gemm_bf16_pq.hip only (this epilogue: QuickGELU); decoding is generic
-    if (d->aux_kind == 2 && d->aux && !d->mul_dact && d->act != SEGCLIP_ACT_QUICK_GELU) return false;
-    // aux_kind 2 (one byte per saved derivative) exists in the staged epilogue of FULL tiles only (8-byte aligned rows)
-    if (d->aux_kind == 2 && d->aux &&
-        !(g.vec_epi && d->M % 256 == 0 && d->N % 256 == 0 && d->ldaux % 8 == 0 && d->c_dtype == SEGCLIP_BF16 && splits == 1))
-      return false;
-  }
-  dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
-  const int variant = small ? 2 : bn == 256 ? 1 : 0;
-  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_DMA, a_ks, b_ks, bm, bn, splits, variant);
-  if (!a_ks && !b_ks) segclip_dma_launch_ff(variant, grid, stream, &g);
-  else if (!a_ks && b_ks) segclip_dma_launch_fk(variant, grid, stream, &g);
-  else if (a_ks && b_ks) segclip_dma_launch_kk(variant, grid, stream, &g);
-  else segclip_dma_launch_kf(variant, grid, stream, &g);
-  return true;
+void segclip_gemm_launch_dma(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
+  static const gemm_layout_launcher layouts[4] = {segclip_dma_launch_ff, segclip_dma_launch_fk, segclip_dma_launch_kf, segclip_dma_launch_kk};
+  layouts[gemm_layout_index(p)](d, p, stream);
 }
 #endif  // DMA_PART == 4

@@ -26,6 +26,8 @@
 // Ordering rules (MI355X guide, LDS-DMA): data is read one phase after the vmcnt that retires it (wait in R(q), every
 // wave passes a barrier, read in R(q+1)); a slot is refilled >= 2 phases after its last read (the reads' lgkmcnt(0) sits
 // after the barrier that follows them).
+// Which problems come here is decided by gemm_plan.cpp (pick_bn == 256, after pq_covers refused, p8_covers); the launcher at
+// the end of this file fills Args from the plan and decides nothing.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -34,7 +36,7 @@
 
 namespace {
 
-constexpr int BK = 64, BT = 256, NWV = 8;
+constexpr int BK = GEMM_BK, BT = GEMM_BIG_TILE, NWV = 8;
 constexpr int UNIT = 128 * BK * 2;            // one half-tile: 16 KiB
 constexpr int BUF = 4 * UNIT;                 // A0 A1 B0 B1
 constexpr int RING = 2 * BUF;                 // 128 KiB
@@ -401,14 +403,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
 // The file is compiled once per P8_PART (segclip_amd/csrc/build.sh) so that the four operand-layout instances - each
 // carries every epilogue variant and takes over a minute of hipcc time - build in parallel:
 //   P8_PART 0..3 : kernel instance <A_KS = part>>1, B_KS = part&1> and its launcher
-//   P8_PART 4    : the host-side dispatcher below (no device code)
+//   P8_PART 4    : the family's launcher below (no device code)
 #ifndef P8_PART
 #error "compile with -DP8_PART=0..4 (see build.sh)"
 #endif
 #define P8_LAUNCHER(NAME, A_KS, B_KS)                                               \
-  void NAME(dim3 grid, hipStream_t stream, const void* args) {                      \
-    const Args g = *reinterpret_cast<const Args*>(args);                            \
-    hipLaunchKernelGGL((gemm_bf16_p8_kernel<A_KS, B_KS>), grid, dim3(512), 0, stream, g); \
+  void NAME(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {    \
+    hipLaunchKernelGGL((gemm_bf16_p8_kernel<A_KS, B_KS>), gemm_grid(p), dim3(512), 0, stream, gemm_args(d, p)); \
   }
 #if P8_PART == 0
 P8_LAUNCHER(segclip_p8_launch_ff, false, false)
@@ -421,57 +422,13 @@ P8_LAUNCHER(segclip_p8_launch_kk, true, true)
 #endif
 
 #if P8_PART == 4
-void segclip_p8_launch_ff(dim3, hipStream_t, const void*);
-void segclip_p8_launch_fk(dim3, hipStream_t, const void*);
-void segclip_p8_launch_kf(dim3, hipStream_t, const void*);
-void segclip_p8_launch_kk(dim3, hipStream_t, const void*);
+void segclip_p8_launch_ff(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_p8_launch_fk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_p8_launch_kf(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_p8_launch_kk(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
 
-// Launch the phase-pipelined kernel for problems tiled 256x256.  `args_` is prepared by the caller (gemm_bf16.hip);
-// returns false when the shape does not meet this kernel's preconditions.
-bool segclip_gemm_bf16_p8_try(const segclip_gemm_desc* d, const void* args_, int splits, int64_t kper, int64_t nb,
-                              hipStream_t stream) {
-  static const bool disabled = segclip_tuning_int("SEGCLIP_GEMM_P8", 1) == 0;
-  if (disabled) return false;
-  Args g = *reinterpret_cast<const Args*>(args_);
-  const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
-  if (d->a_dtype != SEGCLIP_BF16 || d->b_dtype != SEGCLIP_BF16) return false;
-  if (d->K % BK != 0 || kper % BK != 0 || d->K < BK) return false;
-  if (a_ks && (d->M % 8 != 0 || d->M < 8)) return false;
-  if (b_ks && (d->N % 8 != 0 || d->N < 8)) return false;
-  if (d->M < 64 || d->N <= 128) return false;
-  // 32-bit DMA offsets: 256 rows (or 64 k-rows) of the leading dimension must stay below 4 GiB
-  if ((a_ks ? 64 : 256) * (a_ks ? d->sak : d->sam) * 2 >= (int64_t)1 << 31) return false;
-  if ((b_ks ? 64 : 256) * (b_ks ? d->sbk : d->sbn) * 2 >= (int64_t)1 << 31) return false;
-  static const int stagger = segclip_tuning_int("SEGCLIP_P8_STAGGER", 2000);   // unit cap in cycles; 0 = off.  In the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
-  g.stagger = stagger;
-  g.nbx = (int)cdiv(d->N, BT);
-  g.nby = (int)cdiv(d->M, BT);
-  g.splits = splits;
-  g.kper = kper;
-  {
-    auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const int64_t ce = d->c_dtype == SEGCLIP_BF16 ? 8 : 4, re = d->r_dtype == SEGCLIP_BF16 ? 8 : 4;
-    g.vec_epi = al(d->C) && al(d->aux) && al(d->residual) && al(d->bias) && d->ldc % ce == 0 &&
-                (!d->aux || d->ldaux % ce == 0) && (!d->residual || d->ldr % re == 0) && d->bsC1 % ce == 0 &&
-                d->bsC2 % ce == 0 && (!d->residual || (d->bsR1 % re == 0 && d->bsR2 % re == 0));
-    if (d->residual && d->r_dtype != d->c_dtype) g.vec_epi = 0;   // the LDS epilogue holds side operands in the output type
-    if (g.colsum_part && !g.vec_epi) return false;
-    // so do the fused column sums (a partial tile's per-element epilogue writes none): M = 256 q + 128 goes to the 128-row
-    // tiles of gemm_bf16_dma.hip
-    if (g.colsum_part && (d->M % BT != 0 || d->N % BT != 0)) return false;
-    // the one-byte derivative of the erf-GELU is produced by gemm_bf16_pq.hip only (this epilogue: QuickGELU); decoding is generic
-    if (d->aux_kind == 2 && d->aux && !d->mul_dact && d->act != SEGCLIP_ACT_QUICK_GELU) return false;
-    // aux_kind 2 (one byte per saved derivative) exists in the staged epilogue of FULL tiles only (8-byte aligned rows)
-    if (d->aux_kind == 2 && d->aux &&
-        !(g.vec_epi && d->M % 256 == 0 && d->N % 256 == 0 && d->ldaux % 8 == 0 && d->c_dtype == SEGCLIP_BF16 && splits == 1))
-      return false;
-  }
-  dim3 grid((unsigned)(g.nbx * g.nby), (unsigned)splits, (unsigned)nb);
-  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_P8, a_ks, b_ks, BT, BT, splits, 0);
-  if (!a_ks && !b_ks) segclip_p8_launch_ff(grid, stream, &g);
-  else if (!a_ks && b_ks) segclip_p8_launch_fk(grid, stream, &g);
-  else if (a_ks && b_ks) segclip_p8_launch_kk(grid, stream, &g);
-  else segclip_p8_launch_kf(grid, stream, &g);
-  return true;
+void segclip_gemm_launch_p8(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
+  static const gemm_layout_launcher layouts[4] = {segclip_p8_launch_ff, segclip_p8_launch_fk, segclip_p8_launch_kf, segclip_p8_launch_kk};
+  layouts[gemm_layout_index(p)](d, p, stream);
 }
 #endif  // P8_PART == 4

@@ -30,6 +30,9 @@
 // workgroup turnaround was never exposed, and the output stores cost their 2 us per tile as memory-system throughput
 // wherever they are issued (the same time with and without counted waits past them).  The one-tile form keeps the
 // hardware's dynamic workgroup scheduling, which the two concurrent towers rely on, and frees the whole ring for the output.
+//
+// Which problems come here, in which epilogue mode and with which half-tile tail, is decided by gemm_plan.cpp (pq_covers and
+// the predicates it names, plan_pq); the launchers at the end of this file fill PQArgs from the plan and decide nothing.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -38,7 +41,7 @@
 
 namespace {
 
-constexpr int BK = 64, BT = 256, NWV = 8;
+constexpr int BK = GEMM_BK, BT = GEMM_BIG_TILE, NWV = 8;
 constexpr int UNIT = 128 * BK * 2;            // one half-tile: 16 KiB
 constexpr int BUF = 4 * UNIT;                 // A0 A1 B0 B1
 constexpr int RING = 2 * BUF;                 // 128 KiB
@@ -54,8 +57,7 @@ constexpr int BIAS_OFF = EXTRA;               // bias: wave * 256 B (modes with 
 constexpr int HSLOT = 3 * UNIT;
 constexpr int BIAS_OFF_H = 3 * HSLOT;         // 144 KiB
 
-enum { PQ_PLAIN = 0, PQ_RES = 1, PQ_ACT8 = 2, PQ_DACT8 = 3, PQ_SLAB = 4, PQ_RES32 = 5, PQ_ACT8E = 6 };
-// PQ_ACT8E: PQ_ACT8 with the erf-GELU of the MAE decoders (modules/module_mae.py:110-134: timm Block, nn.GELU) instead of QuickGELU
+// epilogue modes PQ_PLAIN .. PQ_ACT8E: gemm_plan.h
 template <int MODE> constexpr bool pq_is_act8() { return MODE == PQ_ACT8 || MODE == PQ_ACT8E; }
 
 struct PQArgs {
@@ -962,31 +964,54 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_pq_group_kernel(PQArgs g, 
 
 }  // namespace
 
-// The file is compiled once per PQ_PART (build.sh): 0 = forward layout, 1 = data-gradient layout, 2 = host dispatcher,
-// 3 = weight-gradient layout
+// The file is compiled once per PQ_PART (build.sh): 0 = forward layout, 1 = data-gradient layout, 2 = the family's launcher
+// and the grouped weight gradients' host side, 3 = weight-gradient layout
 #ifndef PQ_PART
 #error "compile with -DPQ_PART=0..3 (see build.sh)"
 #endif
-#define PQ_LAUNCH(AKS, BKS, MODE) hipLaunchKernelGGL((gemm_bf16_pq_kernel<AKS, BKS, MODE>), grid, dim3(NWV * 64), 0, stream, g)
+// host: the arguments of a planned launch (gemm_plan.cpp: plan_pq) - the descriptor's operands in the roles of the plan's
+// epilogue mode, the plan's half-tile tail
+static PQArgs pq_args(const segclip_gemm_desc* d, const GemmPlan& p) {
+  const int mode = p.pq_mode, splits = p.route.splits;
+  PQArgs g = {};
+  g.A = reinterpret_cast<const bf16_t*>(d->A); g.B = reinterpret_cast<const bf16_t*>(d->B);
+  g.lda = p.route.a_ks ? d->sak : d->sam; g.ldb = p.route.b_ks ? d->sbk : d->sbn;
+  g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
+  g.nfull = p.nfull; g.half_r = p.half_r; g.half_x = p.half_x;
+  if (mode == PQ_SLAB) {          // weight gradient: fp32 out, split-K as raw partial tiles into the slabs
+    if (splits > 1) { g.Cf = reinterpret_cast<float*>(d->ws); g.ldc = d->N; g.kper = p.kper; g.slab_stride = d->M * d->N; }
+    else { g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc; g.kper = d->K; g.slab_stride = 0; }
+  } else if (mode == PQ_RES32) {  // forward + fp32 residual -> fp32
+    g.bias = d->bias; g.side = d->residual; g.lds = d->ldr; g.rmod = d->res_row_mod > 0 ? d->res_row_mod : 0;
+    g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc;
+  } else {                        // bf16 out
+    g.C = reinterpret_cast<bf16_t*>(d->C); g.bias = d->bias;
+    g.side = mode == PQ_DACT8 ? d->aux : (mode == PQ_RES ? d->residual : nullptr);
+    g.aux = (mode == PQ_ACT8 || mode == PQ_ACT8E) ? reinterpret_cast<uint8_t*>(d->aux) : nullptr;
+    g.colsum_part = p.colsum ? d->colsum_ws : nullptr;
+    g.ldc = d->ldc; g.lds = mode == PQ_RES ? d->ldr : d->ldaux; g.ldaux = d->ldaux;
+  }
+  return g;
+}
+#define PQ_LAUNCH(AKS, BKS, MODE) \
+  hipLaunchKernelGGL((gemm_bf16_pq_kernel<AKS, BKS, MODE>), dim3(p.nwg), dim3(NWV * 64), 0, stream, pq_args(d, p))
 #if PQ_PART == 0
-void segclip_pq_launch_f(int mode, dim3 grid, hipStream_t stream, const void* args) {   // forward: plain / QuickGELU + saved derivative / + residual
-  const PQArgs g = *reinterpret_cast<const PQArgs*>(args);
-  if (mode == PQ_ACT8) PQ_LAUNCH(false, false, PQ_ACT8);
-  else if (mode == PQ_ACT8E) PQ_LAUNCH(false, false, PQ_ACT8E);
-  else if (mode == PQ_RES) PQ_LAUNCH(false, false, PQ_RES);
-  else if (mode == PQ_RES32) PQ_LAUNCH(false, false, PQ_RES32);
-  else PQ_LAUNCH(false, false, PQ_PLAIN);
+void segclip_pq_launch_f(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {   // forward: plain / GELU + saved derivative / + residual
+  switch (p.pq_mode) {
+    case PQ_ACT8: PQ_LAUNCH(false, false, PQ_ACT8); break;
+    case PQ_ACT8E: PQ_LAUNCH(false, false, PQ_ACT8E); break;
+    case PQ_RES: PQ_LAUNCH(false, false, PQ_RES); break;
+    case PQ_RES32: PQ_LAUNCH(false, false, PQ_RES32); break;
+    default: PQ_LAUNCH(false, false, PQ_PLAIN);
+  }
 }
 #elif PQ_PART == 1
-void segclip_pq_launch_k(int mode, dim3 grid, hipStream_t stream, const void* args) {   // data gradient: plain / x saved derivative
-  const PQArgs g = *reinterpret_cast<const PQArgs*>(args);
-  if (mode == PQ_DACT8) PQ_LAUNCH(false, true, PQ_DACT8);
+void segclip_pq_launch_k(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {   // data gradient: plain / x saved derivative
+  if (p.pq_mode == PQ_DACT8) PQ_LAUNCH(false, true, PQ_DACT8);
   else PQ_LAUNCH(false, true, PQ_PLAIN);
 }
 #elif PQ_PART == 3
-void segclip_pq_launch_w(int mode, dim3 grid, hipStream_t stream, const void* args) {   // weight gradient: both operands k-strided, fp32 slabs
-  const PQArgs g = *reinterpret_cast<const PQArgs*>(args);
-  (void)mode;
+void segclip_pq_launch_w(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {   // weight gradient: both operands k-strided, fp32 slabs
   PQ_LAUNCH(true, true, PQ_SLAB);
 }
 void segclip_pq_launch_group(dim3 grid, hipStream_t stream, const void* args, const void* group) {
@@ -997,132 +1022,15 @@ void segclip_pq_launch_group(dim3 grid, hipStream_t stream, const void* args, co
 #endif
 
 #if PQ_PART == 2
-// Half-tile tail plan: the r = ntiles % 256 tiles of the last, partial round run as 2 r workgroups of 128 x 256 when those fit
-// one round (r <= 128): 591 tiles (N = 768 at M = 50432) are 2.3 rounds of 256 CUs and take the time of 3; the third round
-// then costs a half-tile's time (about 0.6 of a tile's: 3 of 4 operand units per K-tile, half the MFMAs, half the output).
-// No exchange between workgroups, results bit-identical to the full tiles'.  SEGCLIP_PQ_HALF=0 switches it off (A/B).
-static bool pq_half_on() {
-  static const int env = segclip_tuning_int("SEGCLIP_PQ_HALF", 1);
-  return (env == 2 ? segclip_tuning_int("SEGCLIP_PQ_HALF_NOW", 1) : env) != 0;
-}
-static int pq_half_plan(int64_t ntiles) {
-  if (!pq_half_on() || ntiles <= 256) return 0;
-  const int r = (int)(ntiles % 256);
-  return r > 0 && r <= 128 ? r : 0;
-}
-// the number of tail tiles a launch over `ntiles` 256 x 256 tiles runs as half-tiles (0 = none); its grid is ntiles + that
-extern "C" int segclip_gemm_pq_half_tail(int64_t ntiles) { return ntiles > 0 ? pq_half_plan(ntiles) : 0; }
-// fills the half-tile fields of g (pq_half_plan, and the remainder row of M = 256 q + 128); false = not taken
-static bool pq_tail_setup(PQArgs& g, const segclip_gemm_desc* d, unsigned* nwg) {
-  *nwg = (unsigned)g.ntiles;
-  const int hx = d->M % BT != 0 ? g.nbx : 0;      // M = 256 q + 128 (checked by the caller): one more row of half-tiles
-  if (hx && !pq_half_on()) return false;
-  const int hr = pq_half_plan(g.ntiles);
-  if (hr > 0 || hx > 0) { g.half_r = hr; g.half_x = hx; g.nfull = g.ntiles - hr; *nwg = (unsigned)(g.nfull + 2 * hr + hx); }
-  return true;
+void segclip_pq_launch_f(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_pq_launch_k(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+void segclip_pq_launch_w(const segclip_gemm_desc*, const GemmPlan&, hipStream_t);
+
+// the three layouts this kernel has: weight gradient (kk), data gradient (fk), forward (ff)
+void segclip_gemm_launch_pq(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
+  (p.route.a_ks ? segclip_pq_launch_w : p.route.b_ks ? segclip_pq_launch_k : segclip_pq_launch_f)(d, p, stream);
 }
 
-// segclip_gemm_last_route's variant of this kernel: epilogue mode | tail tiles run as half-tiles << 4 | half-tiles of a last
-// row of 128 rows << 16
-static int pq_route_variant(int mode, const PQArgs& g) { return mode | (g.half_r << 4) | (g.half_x << 16); }
-
-void segclip_pq_launch_f(int, dim3, hipStream_t, const void*);
-void segclip_pq_launch_k(int, dim3, hipStream_t, const void*);
-void segclip_pq_launch_w(int, dim3, hipStream_t, const void*);
-
-// Launch this kernel when the problem meets its preconditions (see the top of the file); false = not taken.
-bool segclip_gemm_bf16_pq_try(const segclip_gemm_desc* d, const void* args_, int splits, int64_t nb, hipStream_t stream) {
-  // SEGCLIP_GEMM_PQ: 1 (default) on, 0 off, 2 = consult SEGCLIP_GEMM_PQ_NOW (0/1) at every call (A/B tests in one process)
-  static const int mode_env = segclip_tuning_int("SEGCLIP_GEMM_PQ", 1);
-  if (mode_env == 0) return false;
-  if (mode_env == 2 && segclip_tuning_int("SEGCLIP_GEMM_PQ_NOW", 1) == 0) return false;
-  const Args& a = *reinterpret_cast<const Args*>(args_);
-  const bool a_ks = d->sak != 1, b_ks = d->sbk != 1;
-  if (nb != 1 || d->a_dtype != SEGCLIP_BF16 || d->b_dtype != SEGCLIP_BF16) return false;
-  // M = 256 q + 128 (the token rows of an odd multiple of 128 samples x 197 / 577 / 77 tokens): the last 128 rows run as a
-  // row of half-tiles (forward / data-gradient layouts; the weight gradient's M is a weight dimension)
-  if (d->M % (a_ks ? BT : 128) != 0 || d->M < 128 || d->N % BT != 0 || d->K % BK != 0 || d->K < BK) return false;
-  if (a_ks) {   // weight gradient: C(m,n) = sum_k A[k][m] B[k][n], fp32 out (split-K: raw partial tiles into the slabs)
-    static const int wg_env = segclip_tuning_int("SEGCLIP_GEMM_PQ_WGRAD", 1);
-    if (!wg_env || !b_ks || d->c_dtype != SEGCLIP_F32) return false;
-    if (d->bias || d->residual || d->aux || d->act != SEGCLIP_ACT_NONE || d->mul_dact || a.colsum_part) return false;
-    if (splits == 1 && (d->alpha != 1.0f || d->ldc % 4 != 0 || (reinterpret_cast<uintptr_t>(d->C) & 15) != 0)) return false;
-    if (splits > 1 && (a.slab == nullptr || a.kper % BK != 0 || d->N % 4 != 0 || (reinterpret_cast<uintptr_t>(a.slab) & 15) != 0)) return false;
-    if ((reinterpret_cast<uintptr_t>(d->A) & 15) != 0 || (reinterpret_cast<uintptr_t>(d->B) & 15) != 0) return false;
-    if (d->sak % 8 != 0 || d->sbk % 8 != 0) return false;
-    if (64 * d->sak * 2 >= (int64_t)1 << 31 || 64 * d->sbk * 2 >= (int64_t)1 << 31) return false;
-    PQArgs g = {};
-    g.A = reinterpret_cast<const bf16_t*>(d->A); g.B = reinterpret_cast<const bf16_t*>(d->B);
-    g.lda = d->sak; g.ldb = d->sbk;
-    g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
-    if (splits > 1) { g.Cf = a.slab; g.ldc = d->N; g.kper = a.kper; g.slab_stride = d->M * d->N; }
-    else { g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc; g.kper = d->K; g.slab_stride = 0; }
-    if (256 * g.ldc * 4 >= (int64_t)1 << 31) return false;
-    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, true, true, BT, BT, splits, PQ_SLAB);
-    segclip_pq_launch_w(PQ_SLAB, dim3((unsigned)(g.ntiles * splits)), stream, &g);
-    return true;
-  }
-  if (splits != 1) return false;
-  if (d->res_row_mod > 0 && !(d->c_dtype == SEGCLIP_F32 && d->residual != nullptr && d->r_dtype == SEGCLIP_F32)) return false;
-  if (d->c_dtype == SEGCLIP_F32) {   // forward + fp32 residual -> fp32 (the fp32 residual stream): fp32 patches, fp32 row pass
-    static const int r32_env = segclip_tuning_int("SEGCLIP_GEMM_PQ_RES32", 1);
-    if (!r32_env || b_ks || d->residual == nullptr || d->r_dtype != SEGCLIP_F32 || d->alpha != 1.0f) return false;
-    if (d->aux || d->act != SEGCLIP_ACT_NONE || d->mul_dact || a.colsum_part) return false;
-    auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (!al16(d->A) || !al16(d->B) || !al16(d->C) || !al16(d->bias) || !al16(d->residual)) return false;
-    if (d->sam % 8 != 0 || d->sbn % 8 != 0 || d->ldc % 4 != 0 || d->ldr % 4 != 0) return false;
-    if (256 * d->sam * 2 >= (int64_t)1 << 31 || 256 * d->sbn * 2 >= (int64_t)1 << 31 || 256 * d->ldc * 4 >= (int64_t)1 << 31) return false;
-    PQArgs g = {};
-    g.A = reinterpret_cast<const bf16_t*>(d->A); g.B = reinterpret_cast<const bf16_t*>(d->B);
-    g.bias = d->bias; g.side = d->residual; g.lds = d->ldr; g.rmod = d->res_row_mod > 0 ? d->res_row_mod : 0;
-    g.lda = d->sam; g.ldb = d->sbn; g.Cf = reinterpret_cast<float*>(d->C); g.ldc = d->ldc;
-    g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
-    unsigned nwg = 0;
-    if (!pq_tail_setup(g, d, &nwg)) return false;
-    segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, false, BT, BT, 1, pq_route_variant(PQ_RES32, g));
-    segclip_pq_launch_f(PQ_RES32, dim3(nwg), stream, &g);
-    return true;
-  }
-  if (d->c_dtype != SEGCLIP_BF16) return false;
-  if (d->alpha != 1.0f) return false;
-  int mode = PQ_PLAIN;
-  if (d->residual != nullptr) {   // + bf16 residual -> bf16 (the bf16 residual stream of the towers): forward layout only
-    if (d->r_dtype != SEGCLIP_BF16 || b_ks || d->mul_dact || d->act != SEGCLIP_ACT_NONE || d->aux || d->ldr % 8 != 0) return false;
-    mode = PQ_RES;
-  } else
-  if (d->mul_dact) {            // x act'(u), saved as one byte; optional fused column sums
-    const bool gelu = d->act == SEGCLIP_ACT_QUICK_GELU || d->act == SEGCLIP_ACT_GELU_ERF;   // (the byte is decoded the same way)
-    if (!(d->aux && d->aux_kind == 2 && gelu && !d->bias && b_ks && d->ldaux % 16 == 0)) return false;
-    mode = PQ_DACT8;
-  } else if (d->act != SEGCLIP_ACT_NONE) {   // QuickGELU / erf-GELU + saved derivative as one byte
-    const bool gelu = d->act == SEGCLIP_ACT_QUICK_GELU || d->act == SEGCLIP_ACT_GELU_ERF;
-    if (!(d->aux && d->aux_kind == 2 && gelu && !b_ks && d->ldaux % 16 == 0)) return false;
-    mode = d->act == SEGCLIP_ACT_QUICK_GELU ? PQ_ACT8 : PQ_ACT8E;
-  } else if (d->aux) {
-    return false;
-  }
-  if (a.colsum_part != nullptr && mode != PQ_DACT8) return false;
-  auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!al(d->A) || !al(d->B) || !al(d->C) || !al(d->bias) || !al(d->aux) || !al(d->residual) || d->ldc % 8 != 0) return false;
-  const int64_t lda = d->sam, ldb = b_ks ? d->sbk : d->sbn;
-  if (lda % 8 != 0 || ldb % 8 != 0) return false;
-  // 32-bit per-lane offsets: 256 rows (64 k-rows) of an operand and 256 rows of an output stay below 2 GiB
-  if (256 * lda * 2 >= (int64_t)1 << 31 || (b_ks ? 64 : 256) * ldb * 2 >= (int64_t)1 << 31) return false;
-  if (256 * d->ldc * 2 >= (int64_t)1 << 31 || 256 * d->ldaux >= (int64_t)1 << 31) return false;
-  PQArgs g = {};
-  g.A = reinterpret_cast<const bf16_t*>(d->A); g.B = reinterpret_cast<const bf16_t*>(d->B);
-  g.C = reinterpret_cast<bf16_t*>(d->C); g.bias = d->bias;
-  g.side = mode == PQ_DACT8 ? d->aux : (mode == PQ_RES ? d->residual : nullptr);
-  g.aux = (mode == PQ_ACT8 || mode == PQ_ACT8E) ? reinterpret_cast<uint8_t*>(d->aux) : nullptr;
-  g.colsum_part = a.colsum_part;
-  g.lda = lda; g.ldb = ldb; g.ldc = d->ldc; g.lds = mode == PQ_RES ? d->ldr : d->ldaux; g.ldaux = d->ldaux;
-  g.N = (int)d->N; g.K = (int)d->K; g.nbx = (int)(d->N / BT); g.ntiles = (int)((d->M / BT) * (d->N / BT));
-  unsigned nwg = 0;
-  if (!pq_tail_setup(g, d, &nwg)) return false;
-  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_PQ, false, b_ks, BT, BT, 1, pq_route_variant(mode, g));
-  (b_ks ? segclip_pq_launch_k : segclip_pq_launch_f)(mode, dim3(nwg), stream, &g);
-  return true;
-}
 void segclip_pq_launch_group(dim3, hipStream_t, const void*, const void*);
 
 // K ranges for a group of `tiles` 256x256 output tiles over `ksteps` 64-row K steps: the count that minimises the modelled time

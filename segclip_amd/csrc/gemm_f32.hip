@@ -6,7 +6,7 @@
 // tiles; the next K-step's operands are loaded into registers while the current one is multiplied.
 // LDS image is k-major ([k][m], pitch rows+1 floats) so that the one-float-per-lane MFMA operand
 // (lane l: row l&31, k = l>>5) is a conflict-free ds_read_b32 of 32 consecutive floats.
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -169,7 +169,8 @@ __global__ __launch_bounds__(NT) void gemm_f32_kernel(GemmArgs g) {
 
 }  // namespace
 
-int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream) {
+// which tile (gemm_plan.cpp: gemm_plan_f32) is the route variant; the launcher fills GemmArgs and decides nothing
+void segclip_gemm_launch_f32(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {
   GemmArgs g;
   g.A = (const float*)d->A; g.B = (const float*)d->B; g.C = (float*)d->C;
   g.bias = d->bias; g.residual = (const float*)d->residual; g.aux = (float*)d->aux;
@@ -178,23 +179,21 @@ int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream) {
   g.nb2 = d->nb2 > 0 ? d->nb2 : 1;
   g.bsA1 = d->bsA1; g.bsA2 = d->bsA2; g.bsB1 = d->bsB1; g.bsB2 = d->bsB2; g.bsC1 = d->bsC1; g.bsC2 = d->bsC2; g.bsR1 = d->bsR1; g.bsR2 = d->bsR2;
   g.act = d->act; g.mul_dact = d->mul_dact; g.aux_kind = d->aux_kind; g.alpha = d->alpha;
-  const int64_t nb = (d->nb1 > 0 ? d->nb1 : 1) * g.nb2;
-  // M <= 32: 32 x 128 tiles.  Otherwise, with fewer than half a chip of 128 x 128 tiles: 64 x 64 tiles (4x the workgroups),
-  // K-step 64.  256 x 256 x 512: 94 -> 39 us (K-step 128: 47 us - the time is the LDS staging and the one-accumulator MFMA
-  // chain of a wave, not the round trips)
-  static const int force_small = segclip_tuning_int("SEGCLIP_GEMM_F32_SMALL", -1);
-  const bool skinny = force_small != 0 && d->M <= 32;
-  const bool small = !skinny && (force_small >= 0 ? force_small != 0 : cdiv(d->N, 128) * cdiv(d->M, 128) * nb < 128);
-  const int64_t bm = skinny ? 32 : (small ? 64 : 128), bn = skinny ? 128 : (small ? 64 : 128);
-  dim3 grid((unsigned)cdiv(d->N, bn), (unsigned)cdiv(d->M, bm), (unsigned)nb);
-  SEGCLIP_REQUIRE(grid.y <= 65535 && nb <= 65535, "gemm_f32: grid too large (M=%lld batch=%lld)",
-                  (long long)d->M, (long long)nb);
-  constexpr size_t lds_small = 2 * 64 * 65 * sizeof(float), lds_big = 2 * 32 * 129 * sizeof(float),
-                   lds_skinny = 32 * (33 + 129) * sizeof(float);
-  segclip_gemm_route_note(SEGCLIP_GEMM_ROUTE_F32, d->sak != 1, d->sbk != 1, (int)bm, (int)bn, 1, skinny ? 0 : small ? 1 : 2);
-  if (skinny) hipLaunchKernelGGL((gemm_f32_kernel<1, 32, 1>), grid, dim3(NT), lds_skinny, stream, g);
-  else if (small) hipLaunchKernelGGL((gemm_f32_kernel<1, 64, 2>), grid, dim3(NT), lds_small, stream, g);
-  else hipLaunchKernelGGL((gemm_f32_kernel<2, 32, 2>), grid, dim3(NT), lds_big, stream, g);
+  typedef void (*kernel_t)(GemmArgs);
+  static const struct { kernel_t kernel; size_t lds; } tiles[3] = {   // F32_32x128, F32_64x64, F32_128x128
+      {gemm_f32_kernel<1, 32, 1>, 32 * (33 + 129) * sizeof(float)},
+      {gemm_f32_kernel<1, 64, 2>, 2 * 64 * 65 * sizeof(float)},
+      {gemm_f32_kernel<2, 32, 2>, 2 * 32 * 129 * sizeof(float)}};
+  const auto& t = tiles[p.route.variant];
+  hipLaunchKernelGGL(t.kernel, dim3((unsigned)p.nbx, (unsigned)p.nby, (unsigned)p.nb), dim3(NT), t.lds, stream, g);
+}
+
+// attention.hip's fp32 path: one valid fp32 descriptor, planned, noted (segclip_gemm_last_route) and launched as segclip_gemm would
+int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream) {
+  const GemmPlan p = gemm_plan_f32(d);
+  if (p.rc != 0) return p.rc;
+  segclip_gemm_route_note(p.route);
+  segclip_gemm_launch_f32(d, p, stream);
   SEGCLIP_CHECK_LAUNCH("gemm_f32");
   return 0;
 }

@@ -226,11 +226,54 @@ def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=No
         if _cfg.f32_split and _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux,
                                               ldaux, act, mul_dact, alpha, aux_kind, defer):
             return Cc
+    d, _keep = _gemm_desc(lib, True, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act,
+                          mul_dact, alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, defer, r_mod)
+    if _OpCount.enabled:
+        _OpCount.add("gemm_bf16" if B.dtype == torch.bfloat16 else "gemm_f32", 2.0 * M * N * K * nb1 * nb2,
+                     _gemm_algo_bytes(A, B, Cc, M, N, K, nb1 * nb2, residual, aux))
+    if _GemmProfile.enabled:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
+        e1.record()
+        _GemmProfile.records.append((e0, e1, 2.0 * M * N * K * nb1 * nb2, B.dtype == torch.bfloat16,
+                                     _gemm_algo_bytes(A, B, Cc, M, N, K, nb1 * nb2, residual, aux)))
+        return Cc
+    L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
+    return Cc
+
+
+def _addr(t, off=0):
+    """_off for a tensor on any device: the planner reads addresses only"""
+    return None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())
+
+
+class _NoQueue:
+    """gemm_plan's stand-in for a ReduceQueue: the deferral flags are set, nothing is queued"""
+
+    def add_slabs(self, *args):
+        pass
+
+    add_rows = add_slabs
+
+
+def _gemm_algo_bytes(A, B, Cc, M, N, K, nz, residual, aux):
+    """algorithmic bytes of a GEMM: operands read once + outputs written once"""
+    return nz * (M * K * A.element_size() + N * K * B.element_size() + M * N * Cc.element_size()
+                 + (M * N * residual.element_size() if residual is not None else 0)
+                 + (M * N * aux.element_size() if aux is not None else 0))
+
+
+def _gemm_desc(lib, cuda, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act, mul_dact,
+               alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, defer, r_mod):
+    """The descriptor of p_gemm's launch and the buffers it points into (column-sum partials, split-K workspace), which the
+    caller keeps alive; queues the deferred reductions on `defer`.  cuda = False (gemm_plan): tensors on any device."""
+    off, ptr = (_off, L.ptr) if cuda else (_addr, _addr)
     d = L.GemmDesc()
-    d.A, d.B, d.C = _off(A, a_off), _off(B, b_off), _off(Cc, c_off)
-    d.bias = L.ptr(bias)
-    d.residual = _off(residual, r_off)
-    d.aux = _off(aux, c_off) if aux is not None else None
+    d.A, d.B, d.C = off(A, a_off), off(B, b_off), off(Cc, c_off)
+    d.bias = ptr(bias)
+    d.residual = off(residual, r_off)
+    d.aux = off(aux, c_off) if aux is not None else None
     d.M, d.N, d.K = M, N, K
     d.sam, d.sak = sa
     d.sbn, d.sbk = sb
@@ -246,20 +289,20 @@ def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=No
         raise TypeError("gemm: aux dtype must equal output dtype (uint8 for aux_kind 2)")
     d.act, d.mul_dact, d.alpha, d.aux_kind = act, int(mul_dact), float(alpha), int(aux_kind)
     flags = 0
+    csws = ws = None
     if colsum is not None:
         csws = torch.empty((max(M // 64, 1), N), dtype=torch.float32, device=A.device)
-        d.colsum, d.colsum_ws = L.ptr(colsum), L.ptr(csws)
+        d.colsum, d.colsum_ws = ptr(colsum), ptr(csws)
         if defer is not None:
             flags |= L.GEMM_DEFER_COLSUM
             defer.add_rows(csws, M // 64, N, N, (colsum,), N)
-    ws = None
     # a workspace exists only for split-K (no epilogue operands): skip the query call on the ~60 % of launches that can never
     # have one (host time: the step is ~800 launches)
     nbytes = (lib.segclip_gemm_ws_bytes(C.byref(d))
               if (bias is None and residual is None and aux is None and act == ACT_NONE and not mul_dact) else 0)
     if nbytes:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
-        d.ws, d.ws_bytes = L.ptr(ws), nbytes
+        d.ws, d.ws_bytes = ptr(ws), nbytes
         # split-K: the combine can be deferred when C is one contiguous (M, N) array
         if (defer is not None and nb1 * nb2 == 1 and ldc == N and c_off == 0 and Cc.is_contiguous()
                 and (M * N) % 4 == 0 and Cc.data_ptr() % 16 == 0):
@@ -269,25 +312,21 @@ def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=No
                 defer.add_slabs(ws, Cc, ns, M * N, alpha)
     d.flags = flags
     d.res_row_mod = int(r_mod)
-    if _OpCount.enabled:
-        nz = nb1 * nb2
-        _OpCount.add("gemm_bf16" if B.dtype == torch.bfloat16 else "gemm_f32", 2.0 * M * N * K * nz,
-                     nz * (M * K * A.element_size() + N * K * B.element_size() + M * N * Cc.element_size()
-                           + (M * N * residual.element_size() if residual is not None else 0)
-                           + (M * N * aux.element_size() if aux is not None else 0)))
-    if _GemmProfile.enabled:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
-        e1.record()
-        nz = nb1 * nb2
-        nbytes = nz * (M * K * A.element_size() + N * K * B.element_size() + M * N * Cc.element_size()
-                       + (M * N * residual.element_size() if residual is not None else 0)
-                       + (M * N * aux.element_size() if aux is not None else 0))   # operands read once + outputs written once
-        _GemmProfile.records.append((e0, e1, 2.0 * M * N * K * nz, B.dtype == torch.bfloat16, nbytes))
-        return Cc
-    L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
-    return Cc
+    return d, (csws, ws)
+
+
+def gemm_plan(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=None, residual=None, ldr=0,
+              r_off=0, aux=None, ldaux=0, act=ACT_NONE, mul_dact=False, alpha=1.0, nb1=1, nb2=1, bsA=(0, 0),
+              bsB=(0, 0), bsC=(0, 0), bsR=None, colsum=None, aux_kind=0, defer=None, r_mod=0):
+    """The route p_gemm would take with the same arguments (include/segclip_hip.h: segclip_gemm_plan), as gemm_last_route reports it
+    afterwards; raises what p_gemm would raise before launching.  Nothing is launched and nothing queued on `defer`; the tensors
+    may live on any device (only their addresses are read).  The config.f32_split rewrite is not applied: plan its bf16 problem."""
+    lib = L.load()
+    d, _keep = _gemm_desc(lib, False, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act,
+                          mul_dact, alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, None if defer is None else _NoQueue(), r_mod)
+    r = L.GemmRoute()
+    L.check(lib.segclip_gemm_plan(C.byref(d), C.byref(r), None), "gemm")
+    return GemmRoute(L.GEMM_ROUTE_FAMILIES[r.family], bool(r.a_ks), bool(r.b_ks), r.tile_m, r.tile_n, r.splits, r.variant)
 
 
 GemmRoute = collections.namedtuple("GemmRoute", "family a_ks b_ks tile_m tile_n splits variant")
