@@ -905,6 +905,46 @@ int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Confusion matrix of label maps (segment_confusion.inc): which class the pixels of a class went to.  THE REFERENCE HAS NO
+ * SUCH OP (mmseg's eval_metrics stops at the per-class areas); the definition is this project's, restated by
+ * tests/confusion_reference.py.
+ *
+ * segclip_seg_confusion: n pixels of uint8 label maps, prediction p and raw ground truth g.
+ *   conf : a contiguous (C + 1, C + 1) int64 matrix that is ADDED to: row = ground-truth class, column = predicted class,
+ *          index C on either axis the "out of range" bin.  The ground-truth rule is segclip_seg_areas', pixel for pixel: a
+ *          pixel with g == ignore_index contributes nothing; with reduce_zero_label a pixel with g == 0 contributes nothing
+ *          either and every other g counts as g - 1; after that g >= C goes to row C, and p >= C goes to column C.
+ *   The areas are a projection of the matrix, for c < C:  areas[0][c] = conf[c][c];  areas[1][c] = the sum of column c over
+ *   ALL rows, row C included;  areas[2][c] = the sum of row c over ALL columns, column C included.
+ *   How.  A lane reads 16 bytes of pred and of gt per step, two steps in flight; the vector body starts where pred is 16-byte
+ *   aligned, gt is read aligned where it is aligned there too and as 16 bytes of element alignment otherwise, and the fewer
+ *   than two vectors of elements before and after the body are counted one by one: pred and gt may start at any element,
+ *   independently.  Equal consecutive (g, p) pairs of a lane are counted once.  Counters are 32-bit and per workgroup in LDS,
+ *   one 64-bit integer atomic per touched cell at the flush: the sums depend on no schedule.  Two routes:
+ *     dense  (C <= 180): the whole matrix in LDS, (C + 1)^2 * 4 bytes (90 KiB at 151 classes; past 64 KiB the kernel's limit
+ *            is raised, and where the runtime refuses that the sparse route is taken);
+ *     sparse (above): an open-addressing table of 4096 (cell, count) slots, 32 KiB, 8 probes; a pair that finds no slot is
+ *            added to `conf` directly, so independent random labels are counted exactly as well, only slower.
+ *   Grid: grid-stride, 512 threads, at least max(16384, 2 x LDS cells) pixels per workgroup and at most
+ *   CUs x min(4, 160 KiB / LDS bytes) workgroups.  One launch counts at most 2^30 pixels - a longer input is split by the
+ *   entry - so that no 32-bit counter overflows.  Bound: HBM reads, 2 bytes per pixel (4 for the wide entry).
+ *   Measured: profiles/seg_confusion.txt.
+ *   0 <= n <= 2^40, C >= 1; n == 0 launches nothing.  SEGCLIP_ERR_UNSUPPORTED (no launch): C > 256.
+ *
+ * segclip_seg_confusion_wide: the same for n uint16 elements; g is compared with ignore_index as an UNSIGNED 16-bit value.
+ *   SEGCLIP_ERR_UNSUPPORTED: C > 1024.
+ *
+ * segclip_seg_confusion_route: the route the entry takes for C classes on the current device (wide != 0: the uint16 entry):
+ *   0 dense, 1 sparse; negative where the entry would refuse (SEGCLIP_ERR_INVALID: C < 1 or no device;
+ *   SEGCLIP_ERR_UNSUPPORTED: too many classes).  Launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+int segclip_seg_confusion(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index, int reduce_zero_label,
+                          int64_t* conf, void* stream);
+int segclip_seg_confusion_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, int64_t C, int ignore_index,
+                               int reduce_zero_label, int64_t* conf, void* stream);
+int segclip_seg_confusion_route(int64_t C, int wide);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
  * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
  * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the

@@ -192,7 +192,10 @@ SIGNATURES = {
     "segclip_seg_sieve": (C.c_int, [vp, i64, i64, i64, vp, i64, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp]),
     "segclip_seg_boundary_ws_bytes": (i64, [i64, i64]),
     "segclip_seg_boundary": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp]),
-    "segclip_retrieval_thresholds": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "segclip_seg_confusion": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_confusion_wide": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
+    "segclip_seg_confusion_route": (C.c_int, [i64, C.c_int]),
+    "segclip_retrieval_thresholds":(C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
     "segclip_retrieval_count": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
     "segclip_retrieval_hist": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp]),
     "segclip_retrieval_topk_ws_bytes": (i64, [i64, i64, i64, i64]),

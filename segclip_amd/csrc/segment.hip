@@ -11,8 +11,9 @@
 // The other .inc files hold the kernels built on these: evaluation at the ground truth's size with the mIoU areas (segment_eval.inc),
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
-// (segment_refine.inc), their connected components (segment_objects.inc), despeckling by merging (segment_sieve.inc), the training front end (train_frontend.inc) and the
-// 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc).
+// (segment_refine.inc), their connected components (segment_objects.inc), despeckling by merging (segment_sieve.inc), the training front end (train_frontend.inc),
+// the 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc) and the confusion matrix of label maps
+// (segment_confusion.inc).
 #include "common.h"
 
 #include <atomic>
@@ -286,6 +287,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_objects.inc"
 #include "segment_sieve.inc"
 #include "segment_boundary.inc"
+#include "segment_confusion.inc"
 #include "train_frontend.inc"
 
 }  // namespace
@@ -646,6 +648,87 @@ extern "C" int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, 
                      reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(areas));
   SEGCLIP_CHECK_LAUNCH("seg_areas_wide");
   return 0;
+}
+
+// The route of a confusion count and its launch shape: dense where the (C + 1)^2 counters fit the LDS a workgroup obtains on the
+// current device (past 64 KiB the limit of both dense kernels is raised, once per device; a failure is remembered and gives the
+// sparse route), the grid as segment_confusion.inc states it.
+struct SegConfPlan {
+  bool dense;
+  size_t lds;
+  int64_t max_blocks, wg_pixels;
+};
+static int seg_conf_plan(const char* what, int64_t C, SegConfPlan& p) {
+  int dev = 0, ncu = 0;
+  SEGCLIP_REQUIRE(segclip_current_device(&dev, &ncu) && ncu >= 1, "%s: cannot query the current device", what);
+  const size_t dense_lds = (size_t)(((C + 1) * (C + 1) * 4 + 15) & ~15ll);
+  p.dense = C <= SEG_CONF_DENSE_MAX_CLASSES;
+  if (p.dense && dense_lds > 64 * 1024) {
+    static std::atomic<int> raised[64];   // 0 not tried, 1 raised, 2 refused
+    if (!raised[dev]) {
+      const int most = (((SEG_CONF_DENSE_MAX_CLASSES + 1) * (SEG_CONF_DENSE_MAX_CLASSES + 1) * 4 + 15) & ~15);
+      const hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(seg_confusion_kernel<uint8_t, true>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      const hipError_t e16 = hipFuncSetAttribute(reinterpret_cast<const void*>(seg_confusion_kernel<uint16_t, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      if (e8 != hipSuccess || e16 != hipSuccess) (void)hipGetLastError();   // not this call's error: the sparse route runs
+      raised[dev] = (e8 == hipSuccess && e16 == hipSuccess) ? 1 : 2;
+    }
+    p.dense = raised[dev] == 1;
+  }
+  p.lds = p.dense ? dense_lds : (size_t)SEG_CONF_SLOTS * 8;
+  const int64_t cells = (int64_t)p.lds / 4, per_cu = (160 * 1024) / (int64_t)p.lds;
+  p.max_blocks = (int64_t)ncu * (per_cu < 4 ? per_cu : 4);
+  p.wg_pixels = 2 * cells > SEG_CONF_MIN_WG_PIXELS ? 2 * cells : SEG_CONF_MIN_WG_PIXELS;
+  return 0;
+}
+
+template <typename T>
+static int seg_confusion_launch(const char* what, const T* pred, const T* gt, int64_t n, int64_t C, int max_classes, int ignore_index,
+                                int reduce_zero_label, int64_t* conf, void* stream) {
+  SEGCLIP_REQUIRE(n >= 0 && n <= (1ll << 40) && C >= 1, "%s: need 0 <= n <= 2^40 and C >= 1", what);
+  SEGCLIP_REQUIRE(n == 0 || (pred && gt && conf), "%s: pred, gt and conf are required", what);
+  SEGCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gt)) & (sizeof(T) - 1)) == 0 &&
+                      (reinterpret_cast<uintptr_t>(conf) & 7) == 0,
+                  "%s: pred and gt are aligned to their element, conf to 8 bytes", what);
+  SEG_REFUSE(C > max_classes, "%s: %lld classes, at most %d", what, (long long)C, max_classes);
+  if (n == 0) return 0;
+  SegConfPlan p;
+  if (int rc = seg_conf_plan(what, C, p)) return rc;
+  // at most 2^30 pixels per launch: no 32-bit counter of a workgroup can overflow
+  for (int64_t at = 0; at < n; at += SEG_CONF_LAUNCH_PIXELS) {
+    const int64_t m = n - at < SEG_CONF_LAUNCH_PIXELS ? n - at : SEG_CONF_LAUNCH_PIXELS;
+    const int64_t want = cdiv(m, p.wg_pixels);
+    const dim3 grid((unsigned)(want < p.max_blocks ? want : p.max_blocks));
+    if (p.dense)
+      hipLaunchKernelGGL((seg_confusion_kernel<T, true>), grid, dim3(SEG_CONF_THREADS), p.lds, ST, pred + at, gt + at, m, (int)C,
+                         ignore_index, reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(conf));
+    else
+      hipLaunchKernelGGL((seg_confusion_kernel<T, false>), grid, dim3(SEG_CONF_THREADS), p.lds, ST, pred + at, gt + at, m, (int)C,
+                         ignore_index, reduce_zero_label ? 1 : 0, reinterpret_cast<unsigned long long*>(conf));
+    SEGCLIP_CHECK_LAUNCH(what);
+  }
+  return 0;
+}
+
+extern "C" int segclip_seg_confusion(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t C, int ignore_index,
+                                     int reduce_zero_label, int64_t* conf, void* stream) {
+  return seg_confusion_launch("seg_confusion", pred, gt, n, C, SEG_MAX_CLASSES, ignore_index, reduce_zero_label, conf, stream);
+}
+
+extern "C" int segclip_seg_confusion_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, int64_t C, int ignore_index,
+                                          int reduce_zero_label, int64_t* conf, void* stream) {
+  return seg_confusion_launch("seg_confusion_wide", pred, gt, n, C, SEG_WIDE_MAX_CLASSES, ignore_index, reduce_zero_label, conf, stream);
+}
+
+extern "C" int segclip_seg_confusion_route(int64_t C, int wide) {
+  const char* what = "seg_confusion_route";
+  const int max_classes = wide ? SEG_WIDE_MAX_CLASSES : SEG_MAX_CLASSES;
+  SEGCLIP_REQUIRE(C >= 1, "%s: need C >= 1", what);
+  SEG_REFUSE(C > max_classes, "%s: %lld classes, at most %d", what, (long long)C, max_classes);
+  SegConfPlan p;
+  if (int rc = seg_conf_plan(what, C, p)) return rc;
+  return p.dense ? 0 : 1;
 }
 
 // views: the (B, 7) table with a flag word per row and the kernel that mirrors (segment_frontend.inc)

@@ -2683,7 +2683,38 @@ def seg_areas_wide(pred, gt, num_classes, ignore_index=255, reduce_zero_label=Fa
     return areas
 
 
-SEG_SOURCE_COLS = 6         # int64 columns of one row of the source table of segclip_seg_windows_from_u8
+def seg_confusion(pred, gt, num_classes, ignore_index=255, reduce_zero_label=False, conf=None):
+    """The confusion matrix of label maps (segclip_seg_confusion / segclip_seg_confusion_wide, picked by the dtype: uint8, or
+    torch.int16 read as unsigned 16-bit values): -> (C + 1, C + 1) int64, row = ground-truth class, column = predicted class,
+    index C on either axis the out-of-range bin; the ground-truth rule is seg_areas'.  Added to `conf` when given."""
+    L.require_cuda(pred, gt, conf)
+    if pred.dtype not in (torch.uint8, torch.int16) or gt.dtype != pred.dtype or pred.numel() != gt.numel():
+        raise ValueError("seg_confusion: pred and gt are both uint8 or both int16 tensors of the same size")
+    side = int(num_classes) + 1
+    if conf is None:
+        conf = torch.zeros(side, side, dtype=torch.int64, device=pred.device)
+    elif conf.dtype != torch.int64 or not conf.is_contiguous() or tuple(conf.shape) != (side, side):
+        raise ValueError("seg_confusion: conf is a contiguous (C + 1, C + 1) int64 tensor")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    wide = pred.dtype == torch.int16
+    fn = L.load().segclip_seg_confusion_wide if wide else L.load().segclip_seg_confusion
+    L.check(fn(L.ptr(pred), L.ptr(gt), pred.numel(), int(num_classes), int(ignore_index), int(bool(reduce_zero_label)), L.ptr(conf),
+               L.stream()), "seg_confusion_wide" if wide else "seg_confusion")
+    return conf
+
+
+def seg_confusion_route(num_classes, dtype=torch.uint8):
+    """The route seg_confusion takes for this class count and label dtype on the current device: "dense" (the whole matrix in
+    LDS) or "sparse" (a table of pairs in LDS).  Raises as seg_confusion does for a class count it refuses."""
+    if dtype not in (torch.uint8, torch.int16):
+        raise ValueError("seg_confusion_route: the label dtype is torch.uint8 or torch.int16")
+    rc = L.load().segclip_seg_confusion_route(int(num_classes), int(dtype == torch.int16))
+    if rc < 0:
+        L.check(rc, "seg_confusion_route")
+    return ("dense", "sparse")[rc]
+
+
+SEG_SOURCE_COLS = 6        # int64 columns of one row of the source table of segclip_seg_windows_from_u8
 SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 
 

@@ -63,6 +63,13 @@ scores int16 ground truths (csrc/segment_wide.inc: 3 x 1024 counters per workgro
 classes are resolved by their wave, 64 classes at a time).  The uint8 path is unchanged and stays the default.  Not covered for
 16-bit maps: test-time augmentation, the threshold sweep, refinement, components, boundary metrics and render_raw.
 
+Confusion matrix (not in the reference): the (3, C) areas say how bad a class is, not where its pixels went.
+SegEvaluator(confusion=True) counts the labels of every update path, 8- or 16-bit, against the ground truths into a
+(C + 1, C + 1) int64 device matrix with one more call (csrc/segment_confusion.inc: wide loads, run-length counting, the matrix
+or a table of pairs per workgroup in LDS), without a host synchronisation; compute() adds Dice, Precision, Recall, Fscore,
+fwIoU and kappa, and areas_from_confusion, confusion_metrics, confused_pairs and merge_classes work on a host copy without an
+evaluator.  Not covered: SegSweepEvaluator.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -699,7 +706,7 @@ def _refuse(entry, *stages):
 
 # What an evaluator's call hands to the chain: the ground truths, the (3, C) areas, the ground-truth rule (ignore_index and
 # reduce_zero_label, as keyword arguments of every kernel that counts), the Boundary or None and its (2, 3, C) areas.
-_Score = collections.namedtuple("_Score", "gts areas rule boundary boundary_areas")
+_Score = collections.namedtuple("_Score", "gts areas rule boundary boundary_areas confusion", defaults=(None,))
 
 
 def _out_shapes(src, out_shapes):
@@ -950,7 +957,7 @@ class SegInference:
 
     def _post_process(self, src, out_shapes, refine=None, clean=None, score=None, want_labels=True):
         """The chain of every list entry point that returns or scores label maps: labels -> refine (a PAMR, against
-        src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas.  score: None, or the _Score of an
+        src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas -> the confusion matrix.  score: None, or the _Score of an
         evaluator's call; the areas are those of the maps that leave the chain, counted once (`counts`), by
 
             refine   clean       the mIoU areas are counted by
@@ -958,12 +965,14 @@ class SegInference:
             PAMR     -           the refinement's last kernel; the label kernel only writes the maps
             any      Despeckle   ops.seg_areas on the cleaned maps, gapless; nothing earlier counts
 
-        and with score.boundary one more ops.seg_boundary call on the same maps adds to score.boundary_areas.  The labels are
+        and with score.boundary one more ops.seg_boundary call on the same maps adds to score.boundary_areas, with
+        score.confusion one ops.seg_confusion call on them, laid gapless, to that matrix.  The labels are
         formed whenever a later stage reads them, wanted or not.  -> the final maps, or None when they are not wanted."""
         forward = self._views_forward if src.augmented else self._list_forward
         counts = None if score is None else "clean" if clean is not None else "refine" if refine is not None else "labels"
         counting = {} if score is None else dict(gts=score.gts, areas=score.areas, **score.rule)
-        first = dict(counting, want_labels=want_labels or score.boundary is not None) if counts == "labels" else {}
+        reads_labels = score is not None and (score.boundary is not None or score.confusion is not None)
+        first = dict(counting, want_labels=want_labels or reads_labels) if counts == "labels" else {}
         labels = forward(src, out_shapes, **first)
         if refine is not None:
             labels = _refine_maps(src.pictures, labels, self.num_classes, src.transform, refine, **(counting if counts == "refine" else {}))
@@ -975,6 +984,9 @@ class SegInference:
         if score is not None and score.boundary is not None:
             _boundary_call(_Maps.of(labels), score.boundary, gts=score.gts, num_classes=self.num_classes, areas=score.boundary_areas,
                            **score.rule)
+        if score is not None and score.confusion is not None:
+            ops.seg_confusion(_Maps.of(labels).gapless(), _Maps.gapless_of(score.gts)[0], self.num_classes, conf=score.confusion,
+                              **score.rule)
         return labels if want_labels else None
 
     @torch.no_grad()
@@ -1174,11 +1186,17 @@ class SegEvaluator:
     device tensor (slot 0 Boundary IoU, slot 1 trimap); the labels are then formed even when return_labels is False, and
     compute() adds bIoU, mbIoU, trimap_IoU, trimap_mIoU and trimap_aAcc from the same host copy.  Several ranks: all_reduce
     `boundary_areas` like `areas`.  Without it nothing changes.
+    confusion (True): every update path also counts the labels whose areas it counts against the ground truths with one more
+    call (segclip_seg_confusion, or its 16-bit entry) that adds to `confusion`, a (C + 1, C + 1) int64 device tensor: row =
+    ground-truth class, column = predicted class, index C the out-of-range bin, the ground-truth rule that of `areas`, which
+    is a projection of it (areas_from_confusion).  The labels are then formed even when return_labels is False, and
+    compute() adds confusion, Dice, Precision, Recall, Fscore, mDice, mFscore, fwIoU and kappa from the same host copy.
+    Several ranks: all_reduce `confusion` (sum) like `areas`.  Without it nothing changes.
     Over a SegInference with label_dtype=torch.int16 the ground truths are (oh, ow) torch.int16 tensors whose elements are read
     as unsigned 16-bit values (a loader's uint16 array goes in as .view(torch.int16)), ignore_index is an integer in
-    0 .. 65535 compared with that value, and boundary= is refused."""
+    0 .. 65535 compared with that value, and boundary= is refused; confusion= works there too."""
 
-    def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None):
+    def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None, confusion=False):
         self.gt_dtype = getattr(seg, "label_dtype", torch.uint8)
         if self.gt_dtype == torch.int16:
             _refuse("SegEvaluator", ("boundary", boundary, "is not built for 16-bit label maps (label_dtype=torch.int16)"))
@@ -1191,16 +1209,21 @@ class SegEvaluator:
         self.boundary, self.boundary_areas = boundary, None
         if boundary is not None:
             self.boundary_areas = torch.zeros(2, 3, seg.num_classes, dtype=torch.int64, device=self.areas.device)
+        self.confusion = None
+        if confusion:
+            self.confusion = torch.zeros(seg.num_classes + 1, seg.num_classes + 1, dtype=torch.int64, device=self.areas.device)
 
     def reset(self):
         self.areas.zero_()
         if self.boundary_areas is not None:
             self.boundary_areas.zero_()
+        if self.confusion is not None:
+            self.confusion.zero_()
 
     def _score(self, gts):
         """-> (what the chain, SegInference._post_process, scores a call against; the ground truths' sizes, its out_shapes)"""
         rule = dict(ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
-        return _Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas), [tuple(g.shape) for g in gts]
+        return _Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas, self.confusion), [tuple(g.shape) for g in gts]
 
     @torch.no_grad()
     def update(self, imgs, gts, return_labels=False, refine=None, clean=None):
@@ -1268,12 +1291,93 @@ class SegEvaluator:
         return dict(mIoU=float(torch.nanmean(iou)), aAcc=float(inter.sum() / label.sum()), mAcc=float(torch.nanmean(acc)),
                     IoU=iou, Acc=acc)
 
+    @staticmethod
+    def _check_confusion(conf):
+        if conf.dim() != 2 or conf.shape[0] != conf.shape[1] or conf.shape[0] < 2 or conf.is_floating_point():
+            raise ValueError(f"conf is a (C + 1, C + 1) integer tensor, got {conf.dtype} {tuple(conf.shape)}")
+        return conf.to(torch.int64)
+
+    @staticmethod
+    def areas_from_confusion(conf):
+        """(C + 1, C + 1) integer CPU tensor (`confusion`) -> the (3, C) int64 `areas` of the same pixels: the diagonal, the
+        column sums over all rows and the row sums over all columns, the out-of-range bins included in the sums."""
+        conf = SegEvaluator._check_confusion(conf)
+        C = conf.shape[0] - 1
+        return torch.stack([conf.diagonal()[:C], conf.sum(0)[:C], conf.sum(1)[:C]])
+
+    @staticmethod
+    def confusion_metrics(conf):
+        """(C + 1, C + 1) integer CPU tensor -> dict, with I, P, L = areas_from_confusion(conf) in fp64:
+        Dice = 2 I / (P + L), Precision = I / P, Recall = I / L, Fscore = 2 Precision Recall / (Precision + Recall) (mmseg's
+        f_score with beta = 1) per class, NaN for a class absent from prediction and label; mDice and mFscore their means
+        over the other classes (as mmseg's nanmean; a class with I = 0 on one side only has an undefined Fscore and is left
+        out of mFscore too); fwIoU = sum(L IoU) / sum(L) over the classes with L > 0; kappa = (po - pe) / (1 - pe) over the
+        WHOLE matrix, the out-of-range bins being one more class on either axis: po = trace / total,
+        pe = sum(row sums x column sums) / total^2; and confusion, the int64 matrix itself."""
+        conf = SegEvaluator._check_confusion(conf)
+        a = SegEvaluator.areas_from_confusion(conf).to(torch.float64)
+        inter, pred, label = a[0], a[1], a[2]
+        dice = 2.0 * inter / (pred + label)
+        precision, recall = inter / pred, inter / label
+        fscore = 2.0 * precision * recall / (precision + recall)
+        iou = inter / (pred + label - inter)
+        seen = label > 0
+        fw = float((label[seen] * iou[seen]).sum() / label.sum())
+        m = conf.to(torch.float64)
+        total = m.sum()
+        po, pe = m.diagonal().sum() / total, (m.sum(1) * m.sum(0)).sum() / (total * total)
+        return dict(confusion=conf, Dice=dice, Precision=precision, Recall=recall, Fscore=fscore, mDice=float(torch.nanmean(dice)),
+                    mFscore=float(torch.nanmean(fscore)), fwIoU=fw, kappa=float((po - pe) / (1.0 - pe)))
+
+    @staticmethod
+    def confused_pairs(conf, k, names=None):
+        """The k largest off-diagonal cells among the first C rows and columns of a (C + 1, C + 1) integer CPU tensor, empty
+        cells left out -> [(gt, pred, count, share)], share = count / the ground-truth class's pixels (its row sum, the
+        out-of-range column included), ordered by falling count and then by rising (gt, pred); with `names` (C strings) the
+        two classes are given by name."""
+        conf = SegEvaluator._check_confusion(conf)
+        C = conf.shape[0] - 1
+        if names is not None and len(names) != C:
+            raise ValueError(f"names holds {len(names)} entries for {C} classes")
+        inner = conf[:C, :C].clone()
+        inner.fill_diagonal_(0)
+        rows = conf.sum(1).tolist()
+        cells = [(-v, i // C, i % C) for i, v in enumerate(inner.reshape(-1).tolist()) if v > 0]
+        out = []
+        for neg, g, p in sorted(cells)[:max(int(k), 0)]:
+            out.append((g if names is None else names[g], p if names is None else names[p], -neg, -neg / rows[g]))
+        return out
+
+    @staticmethod
+    def merge_classes(conf, mapping):
+        """The matrix "if these names were one class": mapping[c] in 0 .. M - 1 is the new class of class c (C entries, every new
+        class used at least once) -> the (M + 1, M + 1) int64 matrix whose cell (a, b) sums the cells of the classes mapped
+        to a and b; the out-of-range bins are carried over as bin M."""
+        conf = SegEvaluator._check_confusion(conf)
+        C = conf.shape[0] - 1
+        mapping = [int(v) for v in mapping]
+        if len(mapping) != C or min(mapping) < 0 or sorted(set(mapping)) != list(range(max(mapping) + 1)):
+            raise ValueError(f"mapping holds one new class id per class ({C}), the ids 0 .. M - 1 all used")
+        M = max(mapping) + 1
+        idx = torch.tensor(mapping + [M], dtype=torch.int64)
+        rows = torch.zeros(M + 1, C + 1, dtype=torch.int64).index_add_(0, idx, conf)
+        return torch.zeros(M + 1, M + 1, dtype=torch.int64).index_add_(1, idx, rows)
+
     def compute(self):
-        if self.boundary is None:
+        parts = [self.areas.reshape(-1)]
+        if self.boundary is not None:
+            parts.append(self.boundary_areas.reshape(-1))
+        if self.confusion is not None:
+            parts.append(self.confusion.reshape(-1))
+        if len(parts) == 1:
             return self.metrics_from_areas(self.areas.cpu())
-        both = torch.cat([self.areas.unsqueeze(0), self.boundary_areas]).cpu()  # the one host copy
-        out = self.metrics_from_areas(both[0])
-        out.update(self.boundary_metrics_from_areas(both[1:]))
+        C = self.areas.shape[1]
+        host = torch.cat(parts).cpu()  # the one host copy
+        out = self.metrics_from_areas(host[:3 * C].view(3, C))
+        if self.boundary is not None:
+            out.update(self.boundary_metrics_from_areas(host[3 * C:9 * C].view(2, 3, C)))
+        if self.confusion is not None:
+            out.update(self.confusion_metrics(host[-(C + 1) * (C + 1):].view(C + 1, C + 1)))
         return out
 
 

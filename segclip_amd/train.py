@@ -297,7 +297,11 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     and trimap_aAcc in percent and the per-class bIoU and trimap_IoU tensors in percent; boundary_areas stays this rank's like
     areas.  test_cfg["label_dtype"] = torch.int16 (a SegInference argument): vocabularies of up to 1024 classes; gts are then
     (oh, ow) torch.int16 tensors read as unsigned 16-bit values (a uint16 array goes in as .view(torch.int16)) and
-    test_cfg["ignore_index"] is an integer in 0 .. 65535, e.g. 65535; aug, refine, clean and boundary are refused."""
+    test_cfg["ignore_index"] is an integer in 0 .. 65535, e.g. 65535; aug, refine, clean and boundary are refused.
+    test_cfg["confusion"] = True: the labels are also counted into the confusion matrix, SegEvaluator(confusion=True), 8- or
+    16-bit maps alike, and the function returns a dict: mIoU, mDice, mFscore and fwIoU in percent, kappa, and `confusion`, the
+    (C + 1, C + 1) int64 CPU tensor of this rank (rows the ground truth, index C the out-of-range bin), beside the boundary
+    keys when both are asked for."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
@@ -311,10 +315,12 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     if clean is not None and transform is None:
         raise ValueError("eval_epoch: test_cfg['clean'] is applied by SegEvaluator.update_raw: pass a transform")
     boundary = cfg.pop("boundary", None)
+    confusion = bool(cfg.pop("confusion", False))
     model = _unwrap(model)
     model.eval()
     emb = build_text_embedding(model, text_tokens.to(device))
-    evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label, boundary=boundary)
+    evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label, boundary=boundary,
+                             confusion=confusion)
     for imgs, gts in batches:
         imgs, gts = [t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts]
         if transform is None:
@@ -325,13 +331,20 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     miou = metrics["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)
-    if boundary is None:
+    if boundary is None and not confusion:
         return miou
     out = {"mIoU": miou}
-    for key in ("bIoU", "mbIoU", "trimap_IoU", "trimap_mIoU", "trimap_aAcc"):
-        out[key] = metrics[key] * 100.0
-    if getattr(args, "local_rank", 0) == 0:
-        logger.info("Boundary IoU: %.2f, trimap mIoU: %.2f, trimap aAcc: %.2f", out["mbIoU"], out["trimap_mIoU"], out["trimap_aAcc"])
+    if boundary is not None:
+        for key in ("bIoU", "mbIoU", "trimap_IoU", "trimap_mIoU", "trimap_aAcc"):
+            out[key] = metrics[key] * 100.0
+        if getattr(args, "local_rank", 0) == 0:
+            logger.info("Boundary IoU: %.2f, trimap mIoU: %.2f, trimap aAcc: %.2f", out["mbIoU"], out["trimap_mIoU"], out["trimap_aAcc"])
+    if confusion:
+        for key in ("mDice", "mFscore", "fwIoU"):
+            out[key] = metrics[key] * 100.0
+        out["kappa"], out["confusion"] = metrics["kappa"], metrics["confusion"]
+        if getattr(args, "local_rank", 0) == 0:
+            logger.info("mDice: %.2f, mFscore: %.2f, fwIoU: %.2f, kappa: %.4f", out["mDice"], out["mFscore"], out["fwIoU"], out["kappa"])
     return out
 
 

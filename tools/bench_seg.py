@@ -80,9 +80,19 @@ ONE command and alternating within every repeat:
         vote), fill mode against one and two rounds each; and the kernels' own times from a
         separate `rocprofv3 --kernel-trace --stats` child (--merge-child: five one-round calls on the 64 maps and nothing else)
         with the vote and final kernels' bytes per second against their design traffic.
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge] [reps=7]
-                                 [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt]"""
+With --confusion instead: the confusion matrix of label maps (ops.seg_confusion, csrc/segment_confusion.inc) on the label maps
+that SegEvaluator.update forms for the inputs of --eval (64 images of mixed VOC-like sizes, 12.0 M pixels) at 21 and 151 classes
+(uint8 maps) and 460 and 848 classes (int16 maps), in ONE command and alternating within every repeat:
+  (xiii) ops.seg_confusion against two yardsticks: the route a user had before it - the ground-truth rule in torch, g * (C + 1) + p
+        as int64, torch.bincount - with its peak allocation, and ops.seg_areas / seg_areas_wide, which reads the same bytes and is
+        the floor the kernel should sit near; the matrices of the first two compared, the identity with the areas checked.  Three
+        inputs per class count: the label maps against themselves shifted by (3, 2) pixels with 40 rectangles per image
+        relabelled (piecewise constant, as annotations are), the label maps against independent random labels, and random labels
+        on both sides (at 460 and 848 classes more distinct pairs than the sparse table has slots: its overflow path).  Medians,
+        spread, the clock held, the route, bytes per second against the HBM peak.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge | --confusion]
+                                 [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
+                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt | seg_confusion.txt]"""
 import os
 import statistics
 import sys
@@ -105,12 +115,13 @@ OBJECTS, OBJECTS_CHILD = ("--objects" in sys.argv[1:]), ("--objects-child" in sy
 BOUNDARY, BOUNDARY_CHILD = ("--boundary" in sys.argv[1:]), ("--boundary-child" in sys.argv[1:])
 WIDE = "--wide" in sys.argv[1:]
 MERGE, MERGE_CHILD = ("--merge" in sys.argv[1:]), ("--merge-child" in sys.argv[1:])
+CONFUSION = "--confusion" in sys.argv[1:]
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
-                                             "--boundary-child", "--wide", "--merge", "--merge-child")]
+                                             "--boundary-child", "--wide", "--merge", "--merge-child", "--confusion")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -1248,6 +1259,89 @@ def wide_case(model, n_images=64):
                 f"{peak_of(ways[1][1]) / 2**20:8.1f} MiB")
 
 
+def confusion_case(model, n_images=64):
+    """(xiii) ops.seg_confusion at 21, 151, 460 and 848 classes against torch.bincount and against ops.seg_areas."""
+    from segclip_amd.segmentation import SegEvaluator, test_size
+    outs = [EVAL_SIZES[i % len(EVAL_SIZES)] for i in range(n_images)]
+    g = torch.Generator().manual_seed(1)
+    imgs = [torch.randn(3, *test_size(*o), generator=g).cuda() for o in outs]
+    pixels = sum(o[0] * o[1] for o in outs)
+    for C in (21, 151, 460, 848):
+        wide = C > 256
+        dtype, ignore = (torch.int16, 65535) if wide else (torch.uint8, 255)
+        text = torch.randn(C - 1, 512, generator=g)
+        text = (text / text.norm(dim=-1, keepdim=True)).cuda()
+        seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224), label_dtype=dtype)
+        dummy = [torch.zeros(o, dtype=dtype, device="cuda") for o in outs]
+        with torch.no_grad():
+            labels = SegEvaluator(seg, ignore_index=ignore).update(imgs, dummy, return_labels=True)
+        shifted = []
+        for m in labels:   # the annotation of a prediction: the map moved by (3, 2), 40 rectangles relabelled, a band ignored
+            t = torch.roll(m, (3, 2), (0, 1)).clone()
+            h, w = t.shape
+            for _ in range(40):
+                y, x = int(torch.randint(0, h - 40, (1,), generator=g)), int(torch.randint(0, w - 40, (1,), generator=g))
+                t[y:y + int(torch.randint(8, 40, (1,), generator=g)), x:x + int(torch.randint(8, 40, (1,), generator=g))] = \
+                    int(torch.randint(0, C, (1,), generator=g))
+            t[:4] = -1 if wide else 255
+            shifted.append(t.reshape(-1))
+        maps = torch.cat([m.reshape(-1) for m in labels])
+        noise = [torch.randint(0, C, (pixels,), generator=g).to(dtype).cuda() for _ in range(2)]
+        truths = {"shifted maps": (maps, torch.cat(shifted)), "random truth": (maps, noise[0]), "both random": (noise[1], noise[0])}
+        areas_fn = ops.seg_areas_wide if wide else ops.seg_areas
+        route = ops.seg_confusion_route(C, dtype)
+        for gt_name, (pred, gt) in truths.items():
+            name = f"(xiii) confusion C={C:4d} {gt_name:13s}"
+            distinct = int(torch.unique(pred.long() & 0xFFFF).numel())
+            conf = torch.zeros(C + 1, C + 1, dtype=torch.int64, device="cuda")
+            areas = torch.zeros(3, C, dtype=torch.int64, device="cuda")
+            kept = {}
+
+            def by_bincount():
+                p, t = pred.long(), gt.long()
+                if wide:
+                    p, t = p & 0xFFFF, t & 0xFFFF
+                keep = t != ignore
+                p, t = p[keep].clamp_(max=C), t[keep].clamp_(max=C)
+                kept["m"] = torch.bincount(t * (C + 1) + p, minlength=(C + 1) * (C + 1)).view(C + 1, C + 1)
+
+            ways = [(f"ops.seg_confusion ({route} route)", lambda: ops.seg_confusion(pred, gt, C, ignore, conf=conf), 10),
+                    ("masking in torch -> g * (C + 1) + p as int64 -> torch.bincount", by_bincount, 3),
+                    ("ops.seg_areas_wide" if wide else "ops.seg_areas", lambda: areas_fn(pred, gt, C, ignore, areas=areas), 10)]
+            with torch.no_grad():
+                conf.zero_()
+                areas.zero_()
+                for _, fn, _ in ways:
+                    fn()
+                torch.cuda.synchronize()
+                cells = int((conf > 0).sum())
+                say(f"{name}: matrix equal to bincount's: {bool(torch.equal(conf, kept['m']))}; its projection equal to the areas: "
+                    f"{bool(torch.equal(torch.stack([conf.diagonal()[:C], conf.sum(0)[:C], conf.sum(1)[:C]]), areas))}; "
+                    f"{distinct} distinct predicted labels, {cells} non-empty cells")
+                for _ in range(2):
+                    for _, fn, _ in ways:
+                        fn()
+                torch.cuda.synchronize()
+                ts = [[] for _ in ways]
+                sampler = ClockSampler().start()
+                for _ in range(REPS):   # alternating: every repeat times the ways one after the other
+                    for i, (_, fn, inner) in enumerate(ways):
+                        t0 = time.perf_counter()
+                        for _ in range(inner):
+                            fn()
+                        torch.cuda.synchronize()
+                        ts[i].append((time.perf_counter() - t0) / inner)
+                clk = sampler.stop()
+            meds = [statistics.median(t) for t in ts]
+            nbytes = 2 * pixels * pred.element_size()
+            say(f"{name}: {pixels} pixels of {'int16' if wide else 'uint8'} maps, {nbytes / 2**20:.1f} MiB read per call; clock {clk}")
+            for (what, _, inner), t, med in zip(ways, ts, meds):
+                say(f"{name}: {what:68s} {med * 1e6:10.1f} us (min {min(t) * 1e6:.1f}, max {max(t) * 1e6:.1f}; {REPS} x {inner} calls)  "
+                    f"{nbytes / med / 1e9:8.1f} GB/s = {nbytes / med / HBM_PEAK:6.4f} of the HBM peak   {med / meds[0]:7.2f}x seg_confusion")
+            say(f"{name}: ratios: bincount / seg_confusion {meds[1] / meds[0]:.2f}, seg_confusion / seg_areas {meds[0] / meds[2]:.2f}; "
+                f"peak allocation of one call: seg_confusion {peak_of(ways[0][1]) / 2**20:.1f} MiB, bincount {peak_of(by_bincount) / 2**20:.1f} MiB")
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -1277,7 +1371,9 @@ if __name__ == "__main__":
     if MERGE_CHILD:
         merge_child(model, text)
         sys.exit(0)
-    if MERGE:
+    if CONFUSION:
+        confusion_case(model)
+    elif MERGE:
         merge_case(model, text)
     elif WIDE:
         wide_case(model)
