@@ -5,10 +5,9 @@
 //   forward  Y = X W^T      : A k-contiguous, B k-contiguous          <A_KS=0, B_KS=0>
 //   dgrad    dX = dY W      : A k-contiguous, B k-strided (W[n][k])   <A_KS=0, B_KS=1>
 //   wgrad    dW = dY^T X    : A k-strided,   B k-strided             <A_KS=1, B_KS=1>
-// k-contiguous operands are staged as a [128 rows][64 k] LDS image (16-B chunk index XOR
-// ((row>>1)&7): conflict-free ds_read_b128 for the 32x32x16 fragment).  k-strided operands are
-// staged as [64 k][128 rows] (pitch 160) and the fragment is built with the gfx950 LDS
-// transpose read ds_read_b64_tr_b16, so neither W nor the activations are ever transposed in HBM.
+// k-contiguous operands are staged as the direct LDS image, k-strided ones as the ks image at pitch 320 B without XOR
+// (gemm_operand_image.h) and read with the gfx950 LDS transpose read ds_read_b64_tr_b16, so neither W nor the
+// activations are ever transposed in HBM.
 // The A operand may be fp32 in HBM (residual-stream gradients): it is rounded to bf16 while staging.
 //
 // Tile 128x128x64, 256 threads = 4 waves (2x2), each wave 64x64 = 2x2 MFMA tiles (64 acc VGPRs).
@@ -22,6 +21,7 @@
 #include <stdlib.h>
 
 #include "gemm_bf16_common.h"
+#include "gemm_bf16_lds.h"
 #include "reduce_rows.h"
 
 namespace {
@@ -132,47 +132,60 @@ __device__ __forceinline__ void gload_ks_slow(Stage<T>& s, const T* __restrict__
 }
 
 // ---- registers -> LDS -----------------------------------------------------------------------
+// The two stores spell the image addresses of gemm_operand_image.h out: called through the header, hipcc forms the address
+// in another order and the kernels' code changes.  The arithmetic sits in constexpr helpers that keep the two
+// terms of an address apart as the kernels add them, and gb_maps_follow_image() below holds the helpers to the header.
+struct LdsOff { int row, in_row; };   // byte offset of the (k-)row, byte offset inside it
+constexpr __device__ __forceinline__ LdsOff sstore_direct_off(int tid, int i) {
+  const int c = tid & 7;
+  const int r = (tid >> 3) + 32 * i;
+  return LdsOff{r * 128, (c ^ ((r >> 1) & 7)) << 4};
+}
+constexpr __device__ __forceinline__ LdsOff sstore_ks_off(int tid, int i) {
+  const int c = tid & 15;
+  const int k = (tid >> 4) + 16 * i;
+  return LdsOff{k * (KS_PITCH * 2), c * 16};
+}
 template <typename T>
 __device__ __forceinline__ void sstore_direct(const Stage<T>& s, char* lds, int tid) {
-  const int c = tid & 7;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int r = (tid >> 3) + 32 * i;
-    *reinterpret_cast<u32x4*>(lds + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = chunk(s, i);
+    const u32x4 v = chunk(s, i);
+    const LdsOff o = sstore_direct_off(tid, i);
+    *reinterpret_cast<u32x4*>(lds + o.row + o.in_row) = v;
   }
 }
 template <typename T>
 __device__ __forceinline__ void sstore_ks(const Stage<T>& s, char* lds, int tid) {
-  const int c = tid & 15;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int k = (tid >> 4) + 16 * i;
-    *reinterpret_cast<u32x4*>(lds + k * (KS_PITCH * 2) + c * 16) = chunk(s, i);
+    const u32x4 v = chunk(s, i);
+    const LdsOff o = sstore_ks_off(tid, i);
+    *reinterpret_cast<u32x4*>(lds + o.row + o.in_row) = v;
   }
 }
 
-// ---- LDS -> MFMA fragments ------------------------------------------------------------------
-// fragment of the 32-row sub-tile starting at `rbase`, k16-chunk kc: lane l -> row l&31, k = 8*(l>>5)+0..7
+// ---- LDS -> MFMA fragments (32x32x16) of the 32-row sub-tile starting at `rbase`, k16-chunk kc --------
 __device__ __forceinline__ bf16x8_t frag_direct(const char* lds, int rbase, int kc, int lane) {
-  const int r = rbase + (lane & 31);
-  const int c = kc * 2 + (lane >> 5);
-  return *reinterpret_cast<const bf16x8_t*>(lds + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+  return *reinterpret_cast<const bf16x8_t*>(lds + opimg::frag_direct<false>(rbase, kc, lane));
 }
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 __device__ __forceinline__ bf16x8_t frag_ks(const char* lds, int rbase, int kc, int lane) {
-  // ds_read_b64_tr_b16: within each 16-lane group, lane q supplies the address of 4 contiguous
-  // b16 of k-row (q>>2); lane q receives column q of the 4x16 block -> 4 consecutive k for its row.
-  const int g4 = lane >> 4, q = lane & 15;
-  const int krow = kc * 16 + 8 * (g4 >> 1) + (q >> 2);
-  const int col = rbase + 16 * (g4 & 1) + 4 * (q & 3);
-  const char* p = lds + krow * (KS_PITCH * 2) + col * 2;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * (KS_PITCH * 2)));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
+  const char* p = lds + opimg::frag_ks<KS_PITCH * 2, false, false>(rbase, kc, lane);
+  return tr16_frag(p, 4 * (KS_PITCH * 2));
 }
+
+// a thread stores the chunks it loaded (gload_*: chunk tid & 7 of rows (tid >> 3) + 32 i / rows 8 (tid & 15) .. of k-rows
+// (tid >> 4) + 16 i) at their image addresses
+constexpr bool gb_maps_follow_image() {
+  for (int tid = 0; tid < NT; ++tid)
+    for (int i = 0; i < 4; ++i) {
+      const LdsOff d = sstore_direct_off(tid, i), k = sstore_ks_off(tid, i);
+      if (d.row + d.in_row != opimg::direct_chunk((tid >> 3) + 32 * i, tid & 7)) return false;
+      if (k.row + k.in_row != opimg::ks_at<KS_PITCH * 2, false>((tid >> 4) + 16 * i, (tid & 15) * 8)) return false;
+    }
+  return true;
+}
+static_assert(gb_maps_follow_image(), "gemm_bf16.hip: sstore_*_off must be the image addresses of gemm_operand_image.h");
 
 template <bool A_KS, bool B_KS, bool A_F32, bool FAST>
 __global__ __launch_bounds__(NT) void gemm_bf16_kernel(Args g) {
@@ -183,10 +196,8 @@ __global__ __launch_bounds__(NT) void gemm_bf16_kernel(Args g) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware bijective remap of the workgroup id (block b runs on XCD b%8)
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = opimg::xcd_chunked(bid, nwg);   // each XCD walks a contiguous run of tiles
   const int64_t n0 = (int64_t)(wg % g.nbx) * BN, m0 = (int64_t)(wg / g.nbx) * BM;
   const int64_t z = blockIdx.z, z1 = z / g.nb2, z2 = z % g.nb2;
   const TA* A = reinterpret_cast<const TA*>(g.A) + z1 * g.bsA1 + z2 * g.bsA2;

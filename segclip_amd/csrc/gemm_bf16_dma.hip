@@ -10,11 +10,7 @@
 // LDS-DMA stream of >=128-byte row pieces sustains ~84 GB/s per CU (21 TB/s chip) from L2, the same
 // stream in 64-byte pieces only 40 GB/s - hence BK = 64 (128-byte rows of a k-contiguous operand) and the
 // 256x256 tile (64 KiB per 2048 MFMA-cycles keeps the DMA engine at ~75 % while the matrix pipe is full).
-// An LDS-DMA write is lane-linear (wave base + lane*16), so the bank-conflict swizzle is applied to the
-// per-lane SOURCE address and again on the fragment read:
-//   k-contiguous operand: [rows][64 k] 128-B rows, 16-B chunk ^ ((row>>1)&7)  -> conflict-free ds_read_b128
-//   k-strided operand   : [64 k][rows] rows*2-B k-rows, 16-B chunk ^ ((k&3)<<2) -> conflict-free
-//                         ds_read_b64_tr_b16 (the 4 k-rows of a transpose read land in 4 bank quadrants)
+// The LDS images (direct / ks with XOR, swizzled on the per-lane SOURCE address): gemm_operand_image.h.
 // MFMA operand fragments are register double-buffered (chunk kc+1 is requested before the MFMAs of kc).
 // Full tiles leave through the LDS-staged coalesced epilogue (gemm_bf16_common.h).
 // Rows beyond M / N are clamped to valid addresses (their products are never stored); K must be a
@@ -23,19 +19,27 @@
 #include <stdlib.h>
 
 #include "gemm_bf16_common.h"
+#include "gemm_bf16_lds.h"
 
 namespace {
 
 constexpr int BK = GEMM_BK;
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 __device__ __forceinline__ void dma16(const bf16_t* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)lds_wave_base, 16, 0, 0);
 }
 
+// issue_direct takes its piece map from gemm_operand_image.h.  issue_ks and the fragment maps spell theirs out: called through
+// the header, hipcc forms the addresses in another order and these kernels' code changes.  The arithmetic sits in constexpr
+// helpers that keep the terms of each address apart as the kernels add them, and dma_maps_follow_image() below holds the
+// helpers to the header.
+struct PieceSrc { int row, chunk; };   // what a lane of a 1-KiB ks piece fetches: k-row and 16-byte chunk (8 rows) of it
+template <int ROWS> constexpr __device__ __forceinline__ PieceSrc piece_ks_src(int idx, int lane) {
+  constexpr int CHUNKS = ROWS / 8;              // 16-B chunks per k-row
+  const int krow = idx * (512 / ROWS) + lane / CHUNKS;
+  const int chunk = (lane % CHUNKS) ^ ((krow & 3) << 2);
+  return PieceSrc{krow, chunk};
+}
 // k-contiguous operand with ROWS rows: X(row,k) = X[row*ld + k]; [ROWS][128 B]; ROWS/64 pieces per wave.
 template <int ROWS, int NWV>
 __device__ __forceinline__ void issue_direct(const bf16_t* __restrict__ X, int64_t ld, int64_t row0, int64_t nrows,
@@ -44,11 +48,11 @@ __device__ __forceinline__ void issue_direct(const bf16_t* __restrict__ X, int64
 #pragma unroll
   for (int i = 0; i < PER_WAVE; ++i) {
     const int idx = wave * PER_WAVE + i;        // 1-KiB piece = 8 rows of 128 B
-    const int row = idx * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    const int row = opimg::piece_direct_row(idx, lane);
+    const int k = opimg::piece_direct_k(row, lane);
     int64_t r = row0 + row;
     r = r < nrows ? r : nrows - 1;
-    dma16(X + r * ld + k0 + chunk * 8, lds + idx * 1024);
+    dma16(X + r * ld + k0 + k, lds + idx * 1024);
   }
 }
 // k-strided operand with ROWS rows: X(row,k) = X[k*ld + row]; LDS image [64 k][ROWS], k-row = ROWS*2 bytes.
@@ -56,36 +60,55 @@ template <int ROWS, int NWV>
 __device__ __forceinline__ void issue_ks(const bf16_t* __restrict__ X, int64_t ld, int64_t row0, int64_t nrows,
                                          int64_t k0, char* lds, int wave, int lane) {
   constexpr int PER_WAVE = ROWS / (8 * NWV);    // 64 k-rows * ROWS*2 B / 1 KiB / NWV waves
-  constexpr int CHUNKS = ROWS / 8;              // 16-B chunks per k-row
 #pragma unroll
   for (int i = 0; i < PER_WAVE; ++i) {
     const int idx = wave * PER_WAVE + i;
-    const int krow = idx * (512 / ROWS) + lane / CHUNKS;
-    const int chunk = (lane % CHUNKS) ^ ((krow & 3) << 2);
-    int64_t r = row0 + chunk * 8;
+    const PieceSrc s = piece_ks_src<ROWS>(idx, lane);
+    int64_t r = row0 + s.chunk * 8;
     r = r + 8 <= nrows ? r : nrows - 8;
-    dma16(X + (k0 + krow) * ld + r, lds + idx * 1024);
+    dma16(X + (k0 + s.row) * ld + r, lds + idx * 1024);
   }
 }
 
-// lane l -> row rbase + (l&31), k = kc*16 + 8*(l>>5) .. +7
-__device__ __forceinline__ bf16x8_t frag_direct(const char* lds, int rbase, int kc, int lane) {
+// 32x32x16 fragments: lane l -> row rbase + (l&31), k = kc*16 + 8*(l>>5) .. +7
+struct LdsOff { int row, chunk, in_chunk; };   // byte offsets: of the (k-)row, of the 16-byte slot in it, inside the slot
+constexpr __device__ __forceinline__ LdsOff frag_direct_off(int rbase, int kc, int lane) {
   const int r = rbase + (lane & 31);
   const int c = kc * 2 + (lane >> 5);
-  return *reinterpret_cast<const bf16x8_t*>(lds + r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+  return LdsOff{r * 128, (c ^ ((r >> 1) & 7)) << 4, 0};
 }
-template <int ROWS>
-__device__ __forceinline__ bf16x8_t frag_ks(const char* lds, int rbase, int kc, int lane) {
+template <int ROWS> constexpr __device__ __forceinline__ LdsOff frag_ks_off(int rbase, int kc, int lane) {
   const int g4 = lane >> 4, q = lane & 15;
   const int krow = kc * 16 + 8 * (g4 >> 1) + (q >> 2);
   const int col = rbase + 16 * (g4 & 1) + 4 * (q & 3);
-  const char* p = lds + krow * (ROWS * 2) + ((((col >> 3) ^ ((krow & 3) << 2))) << 4) + ((col & 7) << 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * (ROWS * 2)));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
+  return LdsOff{krow * (ROWS * 2), (((col >> 3) ^ ((krow & 3) << 2))) << 4, (col & 7) << 1};
+}
+template <int ROWS> constexpr bool dma_maps_follow_image() {
+  for (int l = 0; l < 64; ++l) {
+    for (int idx = 0; idx < ROWS / 8; ++idx) {
+      const PieceSrc k = piece_ks_src<ROWS>(idx, l);
+      if (k.row != opimg::piece_ks_krow<ROWS>(idx, l) || k.chunk * 8 != opimg::piece_ks_row<ROWS>(k.row, l)) return false;
+    }
+    for (int rbase = 0; rbase < ROWS; rbase += 32)
+      for (int kc = 0; kc < 4; ++kc) {
+        const LdsOff d = frag_direct_off(rbase, kc, l), k = frag_ks_off<ROWS>(rbase, kc, l);
+        if (d.row + d.chunk + d.in_chunk != opimg::frag_direct<false>(rbase, kc, l)) return false;
+        if (k.row + k.chunk + k.in_chunk != opimg::frag_ks<ROWS * 2, true, false>(rbase, kc, l)) return false;
+      }
+  }
+  return true;
+}
+static_assert(dma_maps_follow_image<128>() && dma_maps_follow_image<256>(),
+              "gemm_bf16_dma.hip: piece_ks_src / frag_*_off must be the piece and fragment maps of gemm_operand_image.h");
+__device__ __forceinline__ bf16x8_t frag_direct(const char* lds, int rbase, int kc, int lane) {
+  const LdsOff o = frag_direct_off(rbase, kc, lane);
+  return *reinterpret_cast<const bf16x8_t*>(lds + o.row + o.chunk);
+}
+template <int ROWS>
+__device__ __forceinline__ bf16x8_t frag_ks(const char* lds, int rbase, int kc, int lane) {
+  const LdsOff o = frag_ks_off<ROWS>(rbase, kc, lane);
+  const char* p = lds + o.row + o.chunk + o.in_chunk;
+  return tr16_frag(p, 4 * (ROWS * 2));
 }
 
 // <BM, BN, NWV>: <256,256,8> and <256,128,8> own a CU (139 KiB of LDS: operand ring / epilogue patches);
@@ -108,8 +131,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
   const int wm = wave / WN;
   const int wn = wave % WN;
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = opimg::xcd_chunked(bid, nwg);
   const int64_t n0 = (int64_t)(wg % g.nbx) * BN, m0 = (int64_t)(wg / g.nbx) * BM;
   const int64_t z = blockIdx.z, z1 = z / g.nb2, z2 = z % g.nb2;
   const bf16_t* A = reinterpret_cast<const bf16_t*>(g.A) + z1 * g.bsA1 + z2 * g.bsA2;

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "gemm_bf16_common.h"
+#include "gemm_bf16_lds.h"
 
 namespace {
 
@@ -41,46 +42,31 @@ constexpr int UNIT = 128 * BK * 2;            // one half-tile: 16 KiB
 constexpr int BUF = 4 * UNIT;                 // A0 A1 B0 B1
 constexpr int RING = 2 * BUF;                 // 128 KiB
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-// Two LDS-DMA pieces (1 KiB each: lane l writes 16 B at lds + l*16) of one half-tile, issued from INLINE ASM on purpose:
-// hipcc (ROCm 7.2) tracks an outstanding __builtin_amdgcn_global_load_lds as a pending LDS write and puts
-// `s_waitcnt vmcnt(0)` in front of the next ds_read_b64_tr_b16 (the transpose-read builtin carries no alias
-// information), which drains the whole ring every phase - the k-strided variants of gemm_bf16_dma.hip have exactly that
-// wait in every K-step.  Hidden from the compiler, the DMA is ordered only by the counted vmcnt waits and barriers below.
-//   s_nop 4: SGPR base written by SALU -> read by VMEM; s_nop 0: M0 written by SALU -> read by the LDS-DMA.
-// M0 is not used by anything else in this kernel (no other LDS-DMA / movrel / GWS), so it is not preserved.
-__device__ __forceinline__ void dma16x2(const char* base_uniform, uint32_t off0, uint32_t off1, uint32_t lds0) {
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %2\n\t"
-      "s_add_u32 m0, %3, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2"
-      :
-      : "v"(off0), "v"(off1), "s"(base_uniform), "s"(lds0)
-      : "memory", "scc");
-}
-
-// Per-lane byte offset (relative to the tile's first element of the operand) of DMA piece `idx` (1 KiB) of half-tile h.
-// k-contiguous operand X(row,k) = X[row*ld + k]: image [128 rows][128 B], piece = 8 rows, 16-B chunk ^ ((row>>1)&7).
-__device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld, int64_t row0, int64_t nrows) {
+// Per-lane byte offset (relative to the tile's first element of the operand) of DMA piece `idx` (1 KiB) of half-tile h
+// (128 rows: direct image / ks image at pitch 256 B, gemm_operand_image.h); rows beyond nrows are clamped.
+// (off_direct spells the direct piece map out: through the header's functions hipcc emits the same instructions in another
+// order; the static_assert below holds it to the header)
+constexpr __device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld, int64_t row0, int64_t nrows) {
   const int u = idx * 8 + (lane >> 3);
   const int chunk = (lane & 7) ^ ((u >> 1) & 7);
   int64_t r = row0 + h * 128 + u;
   r = r < nrows ? r : nrows - 1;
   return (uint32_t)(((r - row0) * ld + chunk * 8) * 2);
 }
-// k-strided operand X(row,k) = X[k*ld + row]: image [64 k][128 rows] (256-B k-rows), piece = 4 k-rows,
-// 16-B chunk (8 rows) ^ ((k&3)<<2).
+constexpr bool p8_off_direct_follows_image() {   // full tile (no row clamped), two pitches, as in gemm_bf16_pq.hip
+  for (int h = 0; h < 2; ++h)
+    for (int idx = 0; idx < 16; ++idx)
+      for (int l = 0; l < 64; ++l)
+        for (int ld = 64; ld <= 72; ld += 8) {
+          const int row = opimg::piece_direct_row(idx, l);
+          if (off_direct(h, idx, l, ld, 256, 1024) != (uint32_t)(((h * 128 + row) * ld + opimg::piece_direct_k(row, l)) * 2)) return false;
+        }
+  return true;
+}
+static_assert(p8_off_direct_follows_image(), "gemm_bf16_p8.hip: off_direct must be the direct piece map of gemm_operand_image.h");
 __device__ __forceinline__ uint32_t off_ks(int h, int idx, int lane, int64_t ld, int64_t row0, int64_t nrows) {
-  const int krow = idx * 4 + (lane >> 4);
-  const int chunk = (lane & 15) ^ ((krow & 3) << 2);
-  int64_t r = row0 + h * 128 + chunk * 8;
+  const int krow = opimg::piece_ks_krow<128>(idx, lane);
+  int64_t r = row0 + h * 128 + opimg::piece_ks_row<128>(krow, lane);
   r = r + 8 <= nrows ? r : nrows - 8;
   return (uint32_t)((krow * ld + (r - row0)) * 2);
 }
@@ -89,54 +75,16 @@ __device__ __forceinline__ uint32_t off_ks(int h, int idx, int lane, int64_t ld,
 // (row * pitch + swizzle) it spent ~94 VALU instructions per K-tile on addresses - in the R segments, which must stay
 // shorter than the partner group's 8 MFMAs.  Every fragment address is   lane base (VGPR, computed ONCE per kernel)
 // + compile-time constant (ring buffer, half-tile unit, 32-row block, k chunk), i.e. `ds_read ... offset:imm`:
-//   k-contiguous image [128 rows][128 B], 16-B chunk c stored at c ^ ((row>>1)&7): the chunk index c = 2 kc + (l>>5) enters
-//     through the XOR, so there is one base per kc (4 VGPRs per operand and ring buffer; the 16-bit DS offset cannot
-//     reach the second 64-KiB buffer from the first one's base);
-//   k-strided image [64 k][256 B], chunk (row>>3) stored at ^ ((k&3)<<2): kc is a pure row offset (kc * 16 * 256), the
-//     32-row block index flips a swizzled bit: one base per 32-row block.
-typedef __attribute__((address_space(3))) const char lds_cchar;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_bf16x8;
-
-// lane l -> row rbase + (l&31), k = kc*16 + 8*(l>>5) .. +7;  rbase must be a multiple of 16 (it does not enter the swizzle)
+//   direct image: the chunk index c = 2 kc + (l>>5) enters through the XOR, so there is one base per kc (4 VGPRs per
+//     operand and ring buffer; the 16-bit DS offset cannot reach the second 64-KiB buffer from the first one's base);
+//     a 32-row block is an immediate (4096 B: rbase does not enter the XOR);
+//   ks image: kc is a pure row offset (kc * 16 * 256), the 32-row block index flips a swizzled bit: one base per block.
 __device__ __forceinline__ uint32_t fragbase_direct(int rbase, int kc, int lane) {
-  const int r = rbase + (lane & 31);
-  const int c = kc * 2 + (lane >> 5);
-  return (uint32_t)(r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+  return (uint32_t)opimg::frag_direct<false>(rbase, kc, lane);
 }
 __device__ __forceinline__ uint32_t fragbase_ks(int rbase, int lane) {   // kc = 0; + kc * 4096 for the others
-  const int g4 = lane >> 4, q = lane & 15;
-  const int krow = 8 * (g4 >> 1) + (q >> 2);
-  const int col = rbase + 16 * (g4 & 1) + 4 * (q & 3);
-  return (uint32_t)(krow * 256 + ((((col >> 3) ^ ((krow & 3) << 2))) << 4) + ((col & 7) << 1));
+  return (uint32_t)opimg::frag_ks<256, true, false>(rbase, 0, lane);
 }
-template <int OFF> __device__ __forceinline__ bf16x8_t frag_direct_at(lds_cchar* base) {
-  return *reinterpret_cast<lds_bf16x8*>(base + OFF);
-}
-template <int OFF> __device__ __forceinline__ bf16x8_t frag_ks_at(lds_cchar* base) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + OFF));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + OFF + 4 * 256));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
-#define P8_BAR()                         \
-  do {                                   \
-    __builtin_amdgcn_sched_barrier(0);   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 
 template <bool A_KS, bool B_KS>
 __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
@@ -150,8 +98,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   // slab - and, with split-K, the SAME K range - sit behind one L2.
   const int nt = gridDim.x;
   const int nwg = nt * gridDim.y, bid = blockIdx.x + nt * blockIdx.y;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int unit_id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int unit_id = opimg::xcd_chunked(bid, nwg);
   const int wg = unit_id % nt, ksplit = unit_id / nt;
   // Tile order inside the sequence that is cut into the 8 XCD chunks: row-major over all nbx column tiles.
   const int tcol = wg % g.nbx, trow = wg / g.nbx;
@@ -223,7 +170,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   } else {
     wait_vm<4>();
   }
-  P8_BAR();
+  GEMM_RING_BAR();
 
   bf16x8_t fa[2][4], fbx[4], fby[4];
   // lane bases of the fragment reads (see the fragment helpers): [ring buffer][kc] for a k-contiguous operand,
@@ -288,7 +235,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   typedef integral_constant<int, 0> I0;
   typedef integral_constant<int, 1> I1;
   read_b(I0{}, integral_constant<int, 2 * UNIT>{}, fbx);   // B0 of K-tile 0 (in the loop this read sits in R4 of the previous tile)
-  if (wr == 1) P8_BAR();     // group 1 runs one barrier interval behind group 0
+  if (wr == 1) GEMM_RING_BAR();     // group 1 runs one barrier interval behind group 0
 
   // one K-tile: fbp holds B0(t) on entry and fbq is free; on exit fbq holds B0(t+1)
   // (bc = t & 1 as a type: the ring-buffer offset of every fragment read is a compile-time constant)
@@ -299,27 +246,27 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     // ---- phase 1: quadrant (A0, B0)
     read_a(CB{}, integral_constant<int, 0>{});
     if (n1) { stage(1, t + 1); wait_vm<10>(); } else { wait_vm<2>(); }          // retires B1(t), read in R2
-    P8_BAR();
+    GEMM_RING_BAR();
     quadrant(acc[0], 0, fbp);
-    P8_BAR();
+    GEMM_RING_BAR();
     // ---- phase 2: quadrant (A0, B1)
     read_b(CB{}, integral_constant<int, 3 * UNIT>{}, fbq);
     if (n2) { stage(2, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<8>(); } else { wait_vm<0>(); }   // retires A1(t)
-    P8_BAR();
+    GEMM_RING_BAR();
     quadrant(acc[0], 1, fbq);
-    P8_BAR();
+    GEMM_RING_BAR();
     // ---- phase 3: quadrant (A1, B1)
     read_a(CB{}, integral_constant<int, UNIT>{});
     if (n2) { stage(0, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<6>(); }   // retires B0(t+1), read in R4
-    P8_BAR();
+    GEMM_RING_BAR();
     quadrant(acc[1], 1, fbq);
-    P8_BAR();
+    GEMM_RING_BAR();
     // ---- phase 4: quadrant (A1, B0); B1's registers are free: B0(t+1) goes there
     if (n1) read_b(NB{}, integral_constant<int, 2 * UNIT>{}, fbq);
     if (n2) { stage(3, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<4>(); }   // retires A0(t+1), read in R1
-    P8_BAR();
+    GEMM_RING_BAR();
     quadrant(acc[1], 0, fbp);
-    P8_BAR();
+    GEMM_RING_BAR();
   };
   int t = 0;
   for (; t + 1 < nk; t += 2) {
@@ -327,7 +274,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     ktile(I1{}, t + 1, fby, fbx);
   }
   if (t < nk) ktile(I0{}, t, fbx, fby);
-  if (wr == 0) P8_BAR();  // group 0 catches up: both groups have executed the same number of barriers
+  if (wr == 0) GEMM_RING_BAR();  // group 0 catches up: both groups have executed the same number of barriers
 
   const int64_t nw = n0 + wc * 32;  // this wave's first column (second strip at +128)
   if (g.splits > 1) {

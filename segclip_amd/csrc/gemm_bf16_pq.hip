@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "gemm_bf16_common.h"
+#include "gemm_bf16_lds.h"
 
 namespace {
 
@@ -90,11 +91,7 @@ constexpr int PQ_GROUP_MAX = 48;
 struct PQGroup { int nprob; int pad; PQProb prob[PQ_GROUP_MAX]; };
 
 typedef float v2f __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) const char lds_cchar;
 typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) const bf16x8_t lds_bf16x8;
 typedef __attribute__((address_space(3))) u32x2 lds_u32x2;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32;
@@ -155,22 +152,7 @@ template <int B> __device__ __forceinline__ void acc_write8(const float* v) {
       : PQ_AGPRS);
 }
 
-// LDS-DMA pieces, issued from INLINE ASM (hidden from hipcc's waitcnt pass, see gemm_bf16_p8.hip).  Nothing here has a
-// VGPR destination: an asm load into registers lets hipcc copy those registers before the data has landed.
-//   s_nop 4: SGPR base written by SALU -> read by VMEM; s_nop 0: M0 written by SALU -> read by the LDS-DMA.
-__device__ __forceinline__ void dma16x2(const char* base_uniform, uint32_t off0, uint32_t off1, uint32_t lds0) {
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %2\n\t"
-      "s_add_u32 m0, %3, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2"
-      :
-      : "v"(off0), "v"(off1), "s"(base_uniform), "s"(lds0)
-      : "memory", "scc");
-}
+// single LDS-DMA pieces of the side operands, from inline asm like the operands' dma16x2 (gemm_bf16_lds.h)
 __device__ __forceinline__ void dma16(const void* base_uniform, uint32_t off, uint32_t lds0) {
   asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds0) : "memory");
 }
@@ -180,68 +162,40 @@ __device__ __forceinline__ void dma4(const void* base_uniform, uint32_t off, uin
 
 // per-lane DMA source offsets (bytes from the tile's first element), as in gemm_bf16_p8.hip; full tiles only
 __device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld) {
-  const int u = idx * 8 + (lane >> 3);
-  const int chunk = (lane & 7) ^ ((u >> 1) & 7);
-  return (uint32_t)(((int64_t)(h * 128 + u) * ld + chunk * 8) * 2);
+  const int u = opimg::piece_direct_row(idx, lane);
+  const int k = opimg::piece_direct_k(u, lane);
+  return (uint32_t)(((int64_t)(h * 128 + u) * ld + k) * 2);
 }
 __device__ __forceinline__ uint32_t off_ks(int h, int idx, int lane, int64_t ld) {
-  const int krow = idx * 4 + (lane >> 4);
-  const int chunk = (lane & 15) ^ ((krow & 3) << 2);
-  return (uint32_t)((krow * ld + h * 128 + chunk * 8) * 2);
+  const int krow = opimg::piece_ks_krow<128>(idx, lane);
+  return (uint32_t)((krow * ld + h * 128 + opimg::piece_ks_row<128>(krow, lane)) * 2);
 }
-// Operand fragments (lane l, element j = 0..7 of its 16 bytes).  32x32x16: row rbase + (l&31), k = 16 kc + 8 (l>>5) + j.
-// 16x16x32: row rbase + (l&15), k = 32 kc + 8 (l>>4) + j; the XOR (r>>1)&7 repeats every 16 rows, so the 16-row blocks
-// of a base are an immediate 2048 B apart.  ds_read_b128 of either map: conflict-free (each 16-lane group of the
-// instruction covers 8 row pairs x 8 distinct chunks).
+// lane bases of the operand fragments of the MFMA shape in use (gemm_operand_image.h); the immediates the kernel adds to them
+// (16-row blocks of the direct image 2048 B apart; ks: the next 16 rows 32 B on, the next 32 k-rows 8 KiB on) are asserted in
+// gemm_image_check.cpp.  fragbase_ks spells its map out - as a call it changes the forward and weight-gradient kernels - and
+// the static_assert below holds it to the header.
 __device__ __forceinline__ uint32_t fragbase_direct(int rbase, int kc, int lane) {
-  const int r = rbase + (M16 ? (lane & 15) : (lane & 31));
-  const int c = M16 ? kc * 4 + (lane >> 4) : kc * 2 + (lane >> 5);
-  return (uint32_t)(r * 128 + ((c ^ ((r >> 1) & 7)) << 4));
+  return (uint32_t)opimg::frag_direct<M16>(rbase, kc, lane);
 }
-// k-strided operand (LDS image [64 k-rows][256 B], 16-byte chunk c of k-row kr at c ^ ((kr&3)<<2)), read by two
-// ds_read_b64_tr_b16 (k-rows +0..3, +4..7): lane 4q+p of 16-lane group g4 addresses k-row q, columns 4p .. 4p+3 of its
-// group's block.  32x32x16: group g4 = k half g4>>1, 16-column half g4&1; 16x16x32: group g4 = k-rows 8 g4 .., the 16
-// columns rbase ..; the next 16 columns are 32 B on, the next 32 k-rows 8 KiB on.  The 16x16x32 read is 2-way: a 32-lane
-// half takes k-rows kr and kr+8 of the same columns, which the 4-periodic XOR puts on the same banks.
-__device__ __forceinline__ uint32_t fragbase_ks(int rbase, int lane) {
+constexpr __device__ __forceinline__ uint32_t fragbase_ks(int rbase, int lane) {
   const int g4 = lane >> 4, q = lane & 15;
   const int krow = M16 ? 8 * g4 + (q >> 2) : 8 * (g4 >> 1) + (q >> 2);
   const int col = M16 ? rbase + 4 * (q & 3) : rbase + 16 * (g4 & 1) + 4 * (q & 3);
   return (uint32_t)(krow * 256 + ((((col >> 3) ^ ((krow & 3) << 2))) << 4) + ((col & 7) << 1));
 }
-template <int OFF> __device__ __forceinline__ bf16x8_t frag_direct_at(lds_cchar* base) {
-  return *reinterpret_cast<lds_bf16x8*>(base + OFF);
+constexpr bool pq_fragbase_ks_follows_image() {
+  for (int l = 0; l < 64; ++l)
+    for (int rbase = 0; rbase < 128; rbase += 16)
+      if (fragbase_ks(rbase, l) != (uint32_t)opimg::frag_ks<256, true, M16>(rbase, 0, l)) return false;
+  return true;
 }
-template <int OFF> __device__ __forceinline__ bf16x8_t frag_ks_at(lds_cchar* base) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + OFF));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + OFF + 4 * 256));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
-}
+static_assert(pq_fragbase_ks_follows_image(), "gemm_bf16_pq.hip: fragbase_ks must be the ks fragment map of gemm_operand_image.h");
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else static_assert(N < 0, "unsupported vmcnt");
-}
-
-#define PQ_BAR()                         \
-  do {                                   \
-    __builtin_amdgcn_sched_barrier(0);   \
-    __builtin_amdgcn_s_barrier();        \
-    __builtin_amdgcn_sched_barrier(0);   \
-  } while (0)
 // barrier of the epilogue: this wave's LDS operations have completed before it arrives
 #define PQ_BAR_LDS()                                         \
   do {                                                       \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-    PQ_BAR();                                                \
+    GEMM_RING_BAR();                                         \
   } while (0)
 
 // 16-byte store of whole lines, issued from inline asm (not on hipcc's vmcnt scoreboard: the waits between the halves are
@@ -542,6 +496,8 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   // PQ_SLAB (split-K): the (K range, tile) units are ordered K-range-major, so that the tiles of ONE K range - which share
   // its operand rows - sit behind one L2
+  // (this and the full-tile expression below spell opimg::xcd_chunked(bid, nwg) / (bid, g.nfull) out: as calls they change the
+  // code of the forward and data-gradient kernels)
   int unit = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   if (MODE == PQ_SLAB && unit_given >= 0) unit = unit_given;
   // half-tile tail: workgroups nfull .. are the 128-row halves of the tail tiles; the half sequence (tile-major) is cut into
@@ -551,8 +507,8 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   int hsel = 0;
   if (HALF_OK && !A_KS && (g.half_r > 0 || g.half_x > 0)) {
     if (bid >= g.nfull) {
-      const int j = bid - g.nfull, n2 = 2 * g.half_r + g.half_x, q8h = n2 >> 3, r8h = n2 & 7, xh = j & 7;
-      const int hu = (xh < r8h ? xh * (q8h + 1) : r8h * (q8h + 1) + (xh - r8h) * q8h) + (j >> 3);
+      const int j = bid - g.nfull, n2 = 2 * g.half_r + g.half_x;
+      const int hu = opimg::xcd_chunked(j, n2);
       if (hu < 2 * g.half_r) {
         unit = g.nfull + (hu >> 1);
         hsel = hu & 1;
@@ -705,8 +661,8 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
       } else {
         wait_vm<2>();
       }
-      PQ_BAR();
-      if (wr == 1) PQ_BAR();
+      GEMM_RING_BAR();
+      if (wr == 1) GEMM_RING_BAR();
       auto ktile_h = [&](auto sc, auto zc, int t) {
         typedef decltype(sc) SL;
         typedef integral_constant<int, (SL::value + 2) % 3> NS;
@@ -716,15 +672,15 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
         read_a_h(SL{});
         read_b_h(SL{}, integral_constant<int, 0>{}, fbx);
         if (n2) { stage_h(0, t + 2, NS::value); wait_vm<8>(); } else if (n1) { wait_vm<6>(); } else { wait_vm<0>(); }   // retires B1(t)
-        PQ_BAR();
+        GEMM_RING_BAR();
         quadrant(I0{}, I0{}, Z{}, fbx);
-        PQ_BAR();
+        GEMM_RING_BAR();
         // ---- phase 2: quadrant (A0, B1)
         read_b_h(SL{}, integral_constant<int, UNIT>{}, fby);
         if (n2) { stage_h(1, t + 2, NS::value); stage_h(2, t + 2, NS::value); wait_vm<8>(); } else if (n1) { wait_vm<2>(); }   // retires A0(t+1), B0(t+1)
-        PQ_BAR();
+        GEMM_RING_BAR();
         quadrant(I0{}, I1{}, Z{}, fby);
-        PQ_BAR();
+        GEMM_RING_BAR();
       };
       ktile_h(I0{}, I1{}, 0);
       int t = 1;
@@ -814,9 +770,9 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   } else {
     wait_vm<4>();
   }
-  PQ_BAR();
+  GEMM_RING_BAR();
   read_b(I0{}, integral_constant<int, 2 * UNIT>{}, fbx);
-  if (wr == 1) PQ_BAR();     // group 1 runs one barrier interval behind group 0
+  if (wr == 1) GEMM_RING_BAR();     // group 1 runs one barrier interval behind group 0
 
   // one K-tile: fbp holds B0(t) on entry and fbq is free; on exit fbq holds B0(t+1)
   auto ktile = [&](auto bc, auto zc, int t, bf16x8_t (&fbp)[4], bf16x8_t (&fbq)[4]) {
@@ -827,27 +783,27 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
     // ---- phase 1: quadrant (A0, B0)
     read_a(CB{}, integral_constant<int, 0>{});
     if (n1) { stage(1, t + 1); wait_vm<10>(); } else { wait_vm<2>(); }          // retires B1(t), read in R2
-    PQ_BAR();
+    GEMM_RING_BAR();
     quadrant(I0{}, I0{}, Z{}, fbp);
-    PQ_BAR();
+    GEMM_RING_BAR();
     // ---- phase 2: quadrant (A0, B1)
     read_b(CB{}, integral_constant<int, 3 * UNIT>{}, fbq);
     if (n2) { stage(2, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<8>(); } else { wait_vm<0>(); }   // retires A1(t)
-    PQ_BAR();
+    GEMM_RING_BAR();
     quadrant(I0{}, I1{}, Z{}, fbq);
-    PQ_BAR();
+    GEMM_RING_BAR();
     // ---- phase 3: quadrant (A1, B1)
     read_a(CB{}, integral_constant<int, UNIT>{});
     if (n2) { stage(0, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<6>(); }   // retires B0(t+1), read in R4
-    PQ_BAR();
+    GEMM_RING_BAR();
     quadrant(I1{}, I1{}, Z{}, fbq);
-    PQ_BAR();
+    GEMM_RING_BAR();
     // ---- phase 4: quadrant (A1, B0); B1's registers are free: B0(t+1) goes there
     if (n1) read_b(NB{}, integral_constant<int, 2 * UNIT>{}, fbq);
     if (n2) { stage(3, t + 2); wait_vm<10>(); } else if (n1) { wait_vm<4>(); }   // retires A0(t+1), read in R1
-    PQ_BAR();
+    GEMM_RING_BAR();
     quadrant(I1{}, I0{}, Z{}, fbp);
-    PQ_BAR();
+    GEMM_RING_BAR();
   };
   ktile(I0{}, I1{}, 0, fbx, fby);     // first K-tile: the MFMAs overwrite the accumulators (C = 0)
   int t = 1;
@@ -857,7 +813,7 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
   }
   if (t < nk) ktile(I1{}, I0{}, t, fby, fbx);
   }
-  if (wr == 0) PQ_BAR();     // group 0 catches up: every wave is done with the operand ring, the VM queue is empty
+  if (wr == 0) GEMM_RING_BAR();     // group 0 catches up: every wave is done with the operand ring, the VM queue is empty
 
   // ---- output
   asm volatile("" : "+v"(lane));   // lane-dependent epilogue addresses are derived here, not kept live across the K loop
@@ -896,7 +852,7 @@ __device__ __forceinline__ void pq_main(const PQArgs& g, const int unit_given) {
     return;
   }
   if constexpr (MODE == PQ_DACT8) {
-    if (half) { side_half(0, SI1_OFF); wait_vm<0>(); PQ_BAR(); }   // half-tile: its only side-in, into ring space (exposed once per tail workgroup)
+    if (half) { side_half(0, SI1_OFF); wait_vm<0>(); GEMM_RING_BAR(); }   // half-tile: its only side-in, into ring space (exposed once per tail workgroup)
     else side_half(1, SI1_OFF);                                     // lands under the first half's arithmetic
   }
   f32x4 bias[2][4];
@@ -950,8 +906,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_pq_kernel(PQArgs g) {
 // grouped weight gradients: the XCD-chunked unit sequence runs over ALL problems (a chunk = a few K ranges of a few problems)
 __global__ __launch_bounds__(NWV * 64) void gemm_bf16_pq_group_kernel(PQArgs g, PQGroup grp) {
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int unit = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int unit = opimg::xcd_chunked(bid, nwg);
   int p = 0;
   while (p + 1 < grp.nprob && unit >= grp.prob[p].unit_end) ++p;
   const int u0 = p ? grp.prob[p - 1].unit_end : 0;
