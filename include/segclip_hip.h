@@ -415,7 +415,7 @@ int segclip_interp_bicubic(const float* src, float* dst, int64_t n_in, int64_t h
  *   table (W, G, N);  table_max (W) = its maximum (the device-side operand of min(bg_thresh, .), :253 without the .item()
  *   synchronisation);  best_class (W, G) = first maximum over N of each row, best_score (W, G) its value;
  *   topk_mask (W, N) uint8 or NULL.
- *   SEGCLIP_ERR_UNSUPPORTED: ((G + 1) * (C + N) + 2 N + 8) * 4 bytes exceed 64 KiB of LDS.  G <= 8.
+ *   SEGCLIP_ERR_UNSUPPORTED: ((G + 1) * (C + N) + 2 N + 8) * 4 bytes exceed 64 KiB of LDS.  G <= SEGCLIP_SEG_MAX_GROUPS.
  *
  * segclip_seg_label_map: the fused pixel kernel.  For every output pixel and every window covering it: the G channels of
  * soft_attn (W, G, grid_h * grid_w) interpolated with F.interpolate(mode="bilinear", align_corners=False) semantics in
@@ -430,7 +430,8 @@ int segclip_interp_bicubic(const float* src, float* dst, int64_t n_in, int64_t h
  *                 for the caller's bookkeeping and is IGNORED.
  *   image_first : (B + 1) int32, windows image_first[b] .. image_first[b + 1] - 1 belong to image b
  *   Limits of the device-side lists, which the host entry cannot inspect - what exceeds them is SILENTLY IGNORED, the caller
- *   checks them (segclip_amd/segmentation.py does): at most 64 windows per image (later ones are dropped); at most 16
+ *   checks them (segclip_amd/segmentation.py does): at most SEGCLIP_SEG_MAX_IMAGE_WINDOWS windows per image (later ones are
+ *   dropped); at most 16
  *   windows covering one pixel (later ones are dropped); with n_windows <= B every image is taken to have at most one
  *   window covering a pixel (the block then keeps one slot and no table copy in LDS).  Out-of-range entries cannot make
  *   the kernels read or write out of bounds.  Bound: HBM writes, 1-2 bytes per pixel.
@@ -438,6 +439,8 @@ int segclip_interp_bicubic(const float* src, float* dst, int64_t n_in, int64_t h
  * segclip_seg_logits: the dense output, logits (B, N + with_bg, H, W) fp32 exactly as encode_decode (:249-256) and
  * slide_inference define them; same device functions as the label map, which is its first maximum over the classes.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_MAX_GROUPS 8         /* groups per window (the center stage has 8) */
+#define SEGCLIP_SEG_MAX_IMAGE_WINDOWS 64 /* windows of one image (over all its views, where it has views) */
 int segclip_seg_group_table(const float* group_tokens, int64_t group_stride, const float* pooled, int64_t pooled_stride,
                             const float* text, const float* logit_scale, float* table, float* table_max,
                             int32_t* best_class, float* best_score, uint8_t* topk_mask, int64_t n_windows, int64_t G,
@@ -464,14 +467,14 @@ int segclip_seg_logits(const float* soft_attn, const float* table, const float* 
  * is monotone in v; two classes can change places only where it rounds two different logits to one value).  No
  * (C, oh, ow) or (C, H, W) array exists.
  *   soft_attn : flat fp32 of soft_floats elements; the windows of one image are consecutive (G, grid_h * grid_w) planes
- *   images    : (B, 16) int64 rows on the device:
+ *   images    : (B, SEGCLIP_SEG_IMAGE_COLS) int64 rows on the device (columns by name: enum segclip_seg_image_col):
  *               0 first window  1 window count  2 H  3 W  4 oh  5 ow  6 offset of the image's oh * ow labels in `labels`
- *               7 offset of its ground truth in `gt`, or -1  8 its first workgroup = the sum of ceil(oh * ow / 1024) over the
+ *               7 offset of its ground truth in `gt`, or -1  8 its first workgroup = the sum of ceil(oh * ow / SEGCLIP_SEG_EVAL_TILE) over the
  *               images before it  9 win_h  10 win_w  11 grid_h  12 grid_w  13 offset of its first window in soft_attn  14 flag word
  *               of a view (read by segclip_seg_label_map_views alone; 0 here)  15 0
  *               Windows, tables and the window list (image, y0, x0) are as above, but the window size and grid are per image.
- *   n_blocks  : the sum of ceil(oh * ow / 1024) over all images;  max_image_windows: the largest window count of an image
- *               (sizes the LDS; 1 = no image has overlapping windows)
+ *   n_blocks  : the sum of ceil(oh * ow / SEGCLIP_SEG_EVAL_TILE) over all images;  max_image_windows: the largest window count of
+ *               an image (sizes the LDS; 1 = no image has overlapping windows)
  *   labels    : flat uint8 of labels_bytes, or NULL; a label offset that is a multiple of 4 gives dword stores
  *   gt, areas : flat uint8 of gt_bytes and (3, N + with_bg) int64, or both NULL.  areas is ADDED to: [0] intersection,
  *               [1] prediction area, [2] label area per class.  Ground-truth rule of both entries: the value ignore_index
@@ -484,6 +487,12 @@ int segclip_seg_logits(const float* soft_attn, const float* table, const float* 
  *
  * The areas alone: the same accumulation for n pixels of label maps the caller already has.  SEGCLIP_ERR_UNSUPPORTED: C > 256.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_IMAGE_COLS 16  /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_EVAL_TILE 1024 /* output pixels of one workgroup */
+enum segclip_seg_image_col {
+  SEGCLIP_SI_FIRST, SEGCLIP_SI_COUNT, SEGCLIP_SI_H, SEGCLIP_SI_W, SEGCLIP_SI_OH, SEGCLIP_SI_OW, SEGCLIP_SI_LAB, SEGCLIP_SI_GT,
+  SEGCLIP_SI_BLK, SEGCLIP_SI_WIN_H, SEGCLIP_SI_WIN_W, SEGCLIP_SI_GH, SEGCLIP_SI_GW, SEGCLIP_SI_SOFT, SEGCLIP_SI_FLAGS
+};
 int segclip_seg_label_map_rescaled(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
                                    const int32_t* best_class, const float* best_score, const int32_t* windows,
                                    const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
@@ -494,7 +503,7 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
                       int64_t* areas, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * 16-bit label maps (segment_wide.inc): the two entries above for vocabularies of up to 1024 classes, such as
+ * 16-bit label maps (segment_wide.inc): the two entries above for vocabularies of up to SEGCLIP_SEG_WIDE_MAX_CLASSES classes, such as
  * Pascal-Context-459 (460 classes with the background) and ADE20K-847 (848), without the dense (C, H, W) logits.
  *
  * segclip_seg_label_map_rescaled_wide: the arguments, the (B, 16) image table, the tile of 1024 output pixels, the definition
@@ -518,10 +527,11 @@ int segclip_seg_areas(const uint8_t* pred, const uint8_t* gt, int64_t n, int64_t
  *   LDS: 14.5 KiB static + at most 48 KiB dynamic (no table copy where G * N > 4096: the global table is read).
  *   Bound: the class scan of the undecided pixels, (covering windows x taps) x (N + with_bg) table reads each, from L2;
  *   2 bytes of HBM writes per pixel.  Measured: profiles/seg_wide.txt.
- * SEGCLIP_ERR_UNSUPPORTED (no launch): N + with_bg > 1024, max_image_windows > 64.
+ * SEGCLIP_ERR_UNSUPPORTED (no launch): N + with_bg > SEGCLIP_SEG_WIDE_MAX_CLASSES, max_image_windows > 64.
  *
- * segclip_seg_areas_wide: segclip_seg_areas for n uint16 elements.  SEGCLIP_ERR_UNSUPPORTED: C > 1024.
+ * segclip_seg_areas_wide: segclip_seg_areas for n uint16 elements.  SEGCLIP_ERR_UNSUPPORTED: C > SEGCLIP_SEG_WIDE_MAX_CLASSES.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_WIDE_MAX_CLASSES 1024 /* classes of a 16-bit label map, the background included */
 int segclip_seg_label_map_rescaled_wide(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
                                         const int32_t* best_class, const float* best_score, const int32_t* windows,
                                         const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
@@ -537,7 +547,8 @@ int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, 
  * the dataset files of seg_segmentation/configs/_base_/datasets, test_cfg) without repeating towers, front end and group tables per value.
  * The arguments, descriptor tables, tile, range checks and limits are those of segclip_seg_label_map_rescaled; the background
  * class is implied (no with_bg argument, N + 1 classes).
- *   thresholds : HOST pointer to T finite, strictly increasing floats, 1 <= T <= 16; they travel in the kernel arguments
+ *   thresholds : HOST pointer to T finite, strictly increasing floats, 1 <= T <= SEGCLIP_SEG_MAX_THRESHOLDS; they travel in the
+ *                kernel arguments
  *   labels     : NULL, or T planes of labels_bytes each; plane t is, byte for byte, what segclip_seg_label_map_rescaled writes
  *                with bg_thresh = thresholds[t] (the label offsets of `images` are offsets in a plane; dword stores where
  *                plane base + offset is a multiple of 4, byte stores otherwise)
@@ -554,8 +565,9 @@ int segclip_seg_areas_wide(const uint16_t* pred, const uint16_t* gt, int64_t n, 
  *   (the limit is raised once per device when a launch needs more than 56 KiB).
  *   Bound: as the single-threshold entry (covers and class scan) plus T bytes of label stores per pixel; design figure.
  * SEGCLIP_ERR_INVALID (no launch): T < 1, thresholds NULL, a non-finite or non-increasing threshold.
- * SEGCLIP_ERR_UNSUPPORTED (no launch): T > 16, N + 1 > 256, max_image_windows > 64.
+ * SEGCLIP_ERR_UNSUPPORTED (no launch): T > SEGCLIP_SEG_MAX_THRESHOLDS, N + 1 > 256, max_image_windows > 64.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_MAX_THRESHOLDS 16 /* background thresholds of one launch */
 int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
                                          const int32_t* best_class, const float* best_score, const int32_t* windows,
                                          const int64_t* images, int64_t n_windows, int64_t B, int64_t n_blocks,
@@ -571,9 +583,9 @@ int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_fl
  * images of mixed sizes; no (C, oh, ow), (C, H, W) or per-view probability array exists.
  *
  * segclip_seg_label_map_views: the arguments of segclip_seg_label_map_rescaled, except that `images` holds one row PER VIEW
- * (the view's own network size, windows, window size, grid and soft_attn offset; column 14 = flag word, bit 0 horizontal flip,
- * bit 1 vertical flip) and `views` groups them:
- *   views   : (B, 2) int64 rows on the device: 0 the image's first row of `images` (its views are consecutive rows)  1 V
+ * (the view's own network size, windows, window size, grid and soft_attn offset; column 14 = flag word, SEGCLIP_SEG_FLIP_H =
+ * bit 0 horizontal flip, SEGCLIP_SEG_FLIP_V = bit 1 vertical flip) and `views` groups them:
+ *   views   : (B, SEGCLIP_SEG_VIEW_COLS) int64 rows on the device: 0 the image's first row of `images` (its views are consecutive rows)  1 V
  *   images  : (n_rows, 16); columns 4-8 (oh, ow, label offset, ground-truth offset, first workgroup) are the IMAGE's and are
  *             read from its first view's row; every view row must state the same (oh, ow)
  *   Output pixel (y, x) of an image with output size (oh, ow):
@@ -585,7 +597,8 @@ int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_fl
  *   4. the sum over the views in view order divided by (float)V; its first maximum is the label, one byte.
  *   labels / gt / areas / ignore_index / reduce_zero_label: as in segclip_seg_label_map_rescaled (dword stores at label offsets
  *   that are multiples of 4; per-workgroup counters in LDS).  best_class is not needed: the entry takes best_score only.
- *   Limits.  SEGCLIP_ERR_UNSUPPORTED: N + with_bg > 256; max_views > 16; max_image_windows > 64, where
+ *   Limits.  SEGCLIP_ERR_UNSUPPORTED: N + with_bg > 256; max_views > SEGCLIP_SEG_MAX_VIEWS; max_image_windows >
+ *   SEGCLIP_SEG_MAX_IMAGE_WINDOWS, where
  *   max_image_windows = the largest number of windows of one image over ALL its views, max_view_windows = the largest of one
  *   view (1 = no view has overlapping windows: one list slot per tap), max_views = the largest V.  The device-side lists are
  *   not inspected by the host entry: a view's windows beyond 64, an image's windows beyond 64 over its views and covering windows
@@ -600,6 +613,10 @@ int segclip_seg_label_map_rescaled_sweep(const float* soft_attn, int64_t soft_fl
  * 4, by the same kernel body, so the label above is its first maximum over the classes by construction.  An inconsistent
  * table or probs_floats < C * oh * ow: nothing is written.  Bound: HBM writes, 4 C bytes per pixel, beside the same ALU work.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_MAX_VIEWS 16 /* views of one image */
+#define SEGCLIP_SEG_VIEW_COLS 2  /* int64 columns of one row of the view table */
+#define SEGCLIP_SEG_FLIP_H 1     /* flag word of a view: horizontal flip */
+#define SEGCLIP_SEG_FLIP_V 2     /* vertical flip */
 int segclip_seg_label_map_views(const float* soft_attn, int64_t soft_floats, const float* table, const float* table_max,
                                 const float* best_score, const int32_t* windows, const int64_t* images, int64_t n_rows,
                                 const int64_t* views, int64_t n_windows, int64_t B, int64_t n_blocks, int64_t max_image_windows,
@@ -617,8 +634,8 @@ int segclip_seg_view_probs(const float* soft_attn, int64_t soft_floats, const fl
  * launch.  Replaces the test pipeline's Resize(keep_ratio=True) + Normalize(mean, std, to_rgb=True)
  * (seg_segmentation/configs/_base_/datasets/pascal_voc12.py:19-34, mmcv / cv2 there) and the window slicing of mmseg's
  * slide_inference; the resized image is never materialised.
- *   images  : (B, 6) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
- *             3 row stride in bytes (>= 3 w)  4 H  5 W, the network size the image is resized to
+ *   images  : (B, SEGCLIP_SEG_SOURCE_COLS) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved
+ *             channels)  1 h  2 w  3 row stride in bytes (>= 3 w)  4 H  5 W, the network size the image is resized to
  *   windows : (n_windows, 3) int32 rows (image, y0, x0) as above; here the image column IS read
  *   mean, inv_std : 3 host floats each, copied into the launch
  *   out     : (n_windows, 3, win_h, win_w) fp32, the layout segclip_im2col reads
@@ -631,19 +648,22 @@ int segclip_seg_view_probs(const float* soft_attn, int64_t soft_floats, const fl
  * NOT rounded back to uint8 as cv2's 8-bit fixed-point resize does (about one grey level, 0.015 normalised; unmeasured).
  *   Every table row is range-checked on the device.  A window is ZERO-FILLED when its image index is outside [0, B), when it
  *   does not lie inside (H, W), or when its image row has a null address, a stride below 3 w, or one of h, w, H, W outside
- *   [1, 2^15).  Nothing is read outside the (h, w, stride) a row states and nothing written outside `out`.
+ *   [1, SEGCLIP_SEG_SOURCE_LIMIT).  Nothing is read outside the (h, w, stride) a row states and nothing written outside `out`.
  *   16-byte stores when win_w % 4 == 0 and out is 16-byte aligned, scalar stores otherwise (any win_w).  Bound: HBM writes,
  *   12 bytes per window pixel.  SEGCLIP_ERR_UNSUPPORTED: win_h * win_w >= 2^31.  n_windows, B <= 2^24.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_SOURCE_COLS 6      /* int64 columns of one row of the source table */
+#define SEGCLIP_SEG_SOURCE_LIMIT 32768 /* 2^15: the sides of every picture, map and resized image of the table-driven entries stay below it */
 int segclip_seg_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
                                 int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
                                 void* stream);
 
-/* The front end for flipped views (MultiScaleFlipAug's RandomFlip after its Resize): segclip_seg_windows_from_u8 with (B, 7)
- * rows - the six columns above and 6 = flag word.  With bit 0 window pixel (Y, X) reads the resized image at (Y, W - 1 - X),
+/* The front end for flipped views (MultiScaleFlipAug's RandomFlip after its Resize): segclip_seg_windows_from_u8 with
+ * (B, SEGCLIP_SEG_SOURCE_VIEW_COLS) rows - the six columns above and 6 = flag word.  With bit 0 window pixel (Y, X) reads the resized image at (Y, W - 1 - X),
  * with bit 1 at (H - 1 - Y, X); the resize geometry is the unflipped image's.  A multi-scale view needs nothing here: it is the
  * same source address with another (H, W).  Same kernel body (the coordinates are exact integers however they are reached):
  * flags 0 give the entry above bit for bit.  One row per view: an image with V views has V rows.  Same checks, limits and bound. */
+#define SEGCLIP_SEG_SOURCE_VIEW_COLS 7 /* int64 columns of one row of the view entry's source table */
 int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windows, int64_t n_windows, int64_t B, int64_t win_h,
                                      int64_t win_w, const float* mean, const float* inv_std, int reverse_channels, float* out,
                                      void* stream);
@@ -665,7 +685,7 @@ int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windo
  *   images    : the (B, 16) int64 table of segclip_seg_label_map_rescaled, with column 6 = offset of the image's oh * ow
  *               group bytes in `groups` (a multiple of 4 gives dword stores), column 8 = its first workgroup = the sum of
  *               ceil(oh * ow / 1024) over the images before it, column 13 = offset of its window in soft_attn; 0 and 7 unused
- *   n_blocks  : the sum of ceil(oh * ow / 1024) over all images;  groups: flat uint8 of groups_bytes
+ *   n_blocks  : the sum of ceil(oh * ow / SEGCLIP_SEG_RENDER_TILE) over all images;  groups: flat uint8 of groups_bytes
  *   Group maps are defined for exactly ONE window per image, the image itself.  Every row is range-checked on the device: an
  *   image whose window count (column 1) is not 1, whose window size (9, 10) is not (H, W), whose sizes are outside
  *   [1, 2^30) or oh * ow >= 2^31, or whose offsets are inconsistent with soft_floats or groups_bytes is SKIPPED (its bytes
@@ -675,10 +695,10 @@ int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windo
  *
  * segclip_seg_blend: the overlay of blend_result (vit_seg.py:258-284) on the decoded images and, with `sums`, the sums that
  * seg2coord (:100-115) averages into the label anchors of vis_mode="input_pred_label" (:299-320), in the same pass.
- *   images  : (B, 8) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
- *             3 row stride in bytes (>= 3 w)  4 offset of the image's h * w indices in `maps`  5 offset of its 3 * h * w
+ *   images  : (B, SEGCLIP_SEG_BLEND_COLS) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved
+ *             channels)  1 h  2 w  3 row stride in bytes (>= 3 w)  4 offset of the image's h * w indices in `maps`  5 offset of its 3 * h * w
  *             output bytes in `out`  6 its first workgroup = the sum of ceil(h * w / 1024) over the images before it  7 0
- *   n_blocks: the sum of ceil(h * w / 1024) over all images
+ *   n_blocks: the sum of ceil(h * w / SEGCLIP_SEG_RENDER_TILE) over all images
  *   maps    : flat uint8 of maps_bytes: per pixel the palette index (a label or a group)
  *   palette : (P, 3) uint8, RGB, 1 <= P <= 256 (checked on the host).  reverse_channels: the source is BGR, palette channel c
  *             meets image channel 2 - c (:272)
@@ -698,6 +718,8 @@ int segclip_seg_view_windows_from_u8(const int64_t* images, const int32_t* windo
  *   that at every unit; with a padded row stride the source decides per unit), byte accesses otherwise - any w, any stride.
  *   Bound: HBM traffic, 3 + 1 bytes read and 3 written per pixel.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_RENDER_TILE 1024 /* pixels of one workgroup of both entries */
+#define SEGCLIP_SEG_BLEND_COLS 8     /* int64 columns of one row of the blend table */
 int segclip_seg_groups_rescaled(const float* soft_attn, int64_t soft_floats, const int64_t* images, int64_t B, int64_t n_blocks,
                                 int64_t G, uint8_t* groups, int64_t groups_bytes, void* stream);
 int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const uint8_t* maps, int64_t maps_bytes,
@@ -725,11 +747,11 @@ int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const 
  * with D zeros for the centre copies - never E[x^2] - E[x]^2 of the normalised values.  All other math is fp32; a pixel's sum
  * over n runs in the order of n with fused multiply-adds and there are no float atomics: two calls give the same bits.
  *
- *   images   : (B, 8) int64 rows on the device: 0 address of the picture (uint8, HWC, 3 interleaved channels)  1 h  2 w
- *              3 row stride in bytes (>= 3 w)  4 offset of the image's h * w bytes in `labels` AND `out` (and its pixel index
+ *   images   : (B, SEGCLIP_SEG_REFINE_COLS) int64 rows on the device: 0 address of the picture (uint8, HWC, 3 interleaved
+ *              channels)  1 h  2 w  3 row stride in bytes (>= 3 w)  4 offset of the image's h * w bytes in `labels` AND `out` (and its pixel index
  *              in the workspace)  5 offset of its h * w bytes in `gt`, or -1  6 its first workgroup = the sum of
- *              ceil(h * w / 256) over the images before it  7 0
- *   n_blocks : the sum of ceil(h * w / 256) over all images;  max_side: the caller's bound on every h and w
+ *              ceil(h * w / SEGCLIP_SEG_REFINE_TILE) over the images before it  7 0
+ *   n_blocks : the sum of ceil(h * w / SEGCLIP_SEG_REFINE_TILE) over all images;  max_side: the caller's bound on every h and w
  *   labels   : flat uint8 of labels_bytes, read only;  out: flat uint8 of out_bytes = labels_bytes, must not overlap labels
  *   gt/areas : optional flat uint8 ground truth and the (3, C) int64 areas of segclip_seg_areas, ADDED to for the refined
  *              labels by the last kernel (integer adds: no order dependence)
@@ -746,12 +768,17 @@ int segclip_seg_blend(const int64_t* images, int64_t B, int64_t n_blocks, const 
  *   Every table row is range-checked on the device: an image with a null address, h or w outside [1, min(max_side, 2^15 - 1)],
  *   a stride below 3 w or offsets inconsistent with labels_bytes is SKIPPED (nothing of it read, written or counted); with gt
  *   offsets inconsistent with gt_bytes it is refined but not counted.
- *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: D outside 1..6, a dilation outside 1..32 or not increasing,
- *   T outside 0..32, C outside 1..256, max_side outside [1, 2^15), a workspace smaller than ws_bytes.  SEGCLIP_ERR_INVALID:
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: D outside 1..SEGCLIP_SEG_REFINE_MAX_DILATIONS, a dilation
+ *   outside 1..SEGCLIP_SEG_REFINE_MAX_DILATION or not increasing, T outside 0..SEGCLIP_SEG_REFINE_MAX_ITERS, C outside 1..256, max_side outside [1, 2^15), a workspace smaller than ws_bytes.  SEGCLIP_ERR_INVALID:
  *   out overlapping labels, out_bytes != labels_bytes, probs with B != 1, gt without areas, missing pointers.
  *   Traffic per pixel, iteration and chunk of 8 planes: 32 D bytes of weights + 32 bytes of planes written from / to memory,
  *   and 8 D taps of 32 bytes served by the caches (dilations up to 32: an LDS halo tile does not pay).
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_REFINE_TILE 256        /* pixels of one workgroup */
+#define SEGCLIP_SEG_REFINE_COLS 8          /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_REFINE_MAX_DILATIONS 6 /* D */
+#define SEGCLIP_SEG_REFINE_MAX_DILATION 32 /* the largest d */
+#define SEGCLIP_SEG_REFINE_MAX_ITERS 32    /* T */
 int64_t segclip_seg_refine_ws_bytes(int64_t labels_bytes, int64_t B, int64_t D);
 int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
                        int64_t labels_bytes, int64_t C, const int32_t* dilations, int64_t D, int64_t T, const float* mean,
@@ -771,7 +798,7 @@ int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64
  *   Ids, areas, boxes and sums are integers and the ids depend on no scheduling: two calls give the same bits.
  *   ids[p]     = the id of p's component, or -1 for a skipped pixel
  *   area_px[p] = the pixel count of p's component, or 0 for a skipped pixel
- *   records    : one row of 10 int64 per component, rows in ascending (image, id) order:
+ *   records    : one row of SEGCLIP_SEG_CC_RECORD int64 per component, rows in ascending (image, id) order:
  *                image, id, label, area, y0, x0, y1, x1, sum of y, sum of x over its pixels; y1 and x1 are EXCLUSIVE (the box
  *                is rows y0..y1-1, columns x0..x1-1, as scipy.ndimage.find_objects gives slices)
  *   count[0]   = the number of components of all images, also when it exceeds K; then exactly the first K rows in that order
@@ -779,9 +806,10 @@ int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64
  *   cleaned[p] = fill where p is not skipped and area_px[p] < min_area, otherwise L[p].  ONE PASS: pixels that become `fill`
  *                are not merged again with neighbours that carry `fill` already, and nothing is labelled twice.
  *
- *   images   : (B, 8) int64 rows on the device: 0 h  1 w  2 offset of the image's h * w entries in `labels`, `ids`, `area_px`
- *              AND `cleaned`  3 its first workgroup = the sum of ceil(h / 16) * ceil(w / 64) over the images before it  4-7 0
- *   n_blocks : that sum over all images (the tile is 16 rows x 64 columns);  max_side: the caller's bound on every h and w
+ *   images   : (B, SEGCLIP_SEG_CC_COLS) int64 rows on the device: 0 h  1 w  2 offset of the image's h * w entries in `labels`,
+ *              `ids`, `area_px` AND `cleaned`  3 its first workgroup = the sum of ceil(h / SEGCLIP_SEG_CC_TILE_H) *
+ *              ceil(w / SEGCLIP_SEG_CC_TILE_W) over the images before it  4-7 0
+ *   n_blocks : that sum over all images (the tile is SEGCLIP_SEG_CC_TILE_H rows x SEGCLIP_SEG_CC_TILE_W columns);  max_side: the caller's bound on every h and w
  *   labels   : flat uint8 of labels_bytes, read only
  *   ids, area_px : optional flat int32 of px_count = labels_bytes entries
  *   records  : optional (K, 10) int64; needs count.  count: optional, one int64
@@ -800,6 +828,10 @@ int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_blocks, int64
  *   SEGCLIP_ERR_INVALID: records without count, cleaned overlapping labels, cleaned_bytes != labels_bytes,
  *   px_count != labels_bytes with ids or area_px, missing pointers.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_CC_TILE_H 16 /* rows and */
+#define SEGCLIP_SEG_CC_TILE_W 64 /* columns of one workgroup's tile */
+#define SEGCLIP_SEG_CC_COLS 8    /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_CC_RECORD 10 /* int64 columns of a record */
 int64_t segclip_seg_components_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks);
 int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
                            int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
@@ -808,7 +840,7 @@ int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, i
 
 /* ------------------------------------------------------------------------------------------
  * Despeckling by merging (segment_sieve.inc): every small connected component of a label map takes the label of its largest
- * neighbour, in 1..8 rounds, for images of mixed sizes in one call: what a sieve filter does in the raster toolkits.  It is for
+ * neighbour, in 1..SEGCLIP_SEG_SIEVE_MAX_ROUNDS rounds, for images of mixed sizes in one call: what a sieve filter does in the raster toolkits.  It is for
  * vocabularies without a background class, where segclip_seg_components' constant `fill` paints the specks with a real class.
  * THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated by tests/cc_merge_reference.py.
  *
@@ -841,10 +873,11 @@ int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, i
  *   root + the gathered area; a pixel of a small component also reads its 4 neighbours' roots, areas and labels; 8 B per
  *   (tile, voting group); final: 4 B of root + the gathered area + 1 B read, 1 B written, 8 B of slot per small pixel.
  *   A bad table row is SKIPPED on the device as in segclip_seg_components (nothing of that image read or written).
- *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: rounds outside 1..8, orphan_fill outside -1..255,
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: rounds outside 1..SEGCLIP_SEG_SIEVE_MAX_ROUNDS, orphan_fill outside -1..255,
  *   connectivity other than 4 or 8, skip_label outside -1..255, min_area < 0, max_side outside [1, 2^15), a workspace smaller
  *   than ws_bytes.  SEGCLIP_ERR_INVALID: cleaned overlapping labels, cleaned_bytes != labels_bytes, missing pointers.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_SIEVE_MAX_ROUNDS 8
 int64_t segclip_seg_sieve_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks);
 int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
                       int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill, int rounds,
@@ -873,12 +906,13 @@ int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_
  *   With d >= max(h, w) every band byte is non-zero and areas[0] is segclip_seg_areas'; a ground truth of one single byte
  *   leaves areas[1] as it was.
  *
- *   images   : (B, 8) int64 rows on the device: 0 h  1 w  2 offset of the map's h * w bytes in `pred` AND `pred_band`
+ *   images   : (B, SEGCLIP_SEG_BOUNDARY_COLS) int64 rows on the device: 0 h  1 w  2 offset of the map's h * w bytes in `pred` AND
+ *              `pred_band`
  *              3 its offset in `gt` AND `gt_band`, or -1 for a map without a ground truth (not looked at when gt is null)
  *              4 its radius d  5 its first workgroup = the sum of ceil(ceil(h / 32) * ceil(w / 64) / 4) over the maps
  *              before it  6-7 0
- *   n_blocks : that sum over all maps (a wave owns a strip of 32 rows x 64 columns, a workgroup four consecutive strips of
- *              a map);  max_side: the caller's bound on every h and w
+ *   n_blocks : that sum over all maps (a wave owns a strip of SEGCLIP_SEG_BOUNDARY_TILE_H rows x SEGCLIP_SEG_BOUNDARY_TILE_W
+ *              columns, a workgroup SEGCLIP_SEG_BOUNDARY_WAVES consecutive strips of a map);  max_side: the caller's bound on every h and w
  *   pred, gt : flat uint8 of pred_bytes / gt_bytes, read only; gt optional.  They have offsets of their own because an
  *              evaluator's label buffer has gaps between its maps and its ground truths lie gapless.
  *   pred_band, gt_band : optional flat uint8 with the layout of pred / gt; gt_band needs gt
@@ -891,13 +925,18 @@ int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_
  *   of the pixel it emits.  Work per pixel is (32 + 2 d) / 32 row visits, never d^2.  The areas are counted in LDS and added
  *   with one integer atomic per touched counter and workgroup: the sums depend on no schedule.
  *   Every table row is range-checked on the device: a map with h or w outside [1, min(max_side, 2^15 - 1)], a radius outside
- *   [1, 128], offsets inconsistent with pred_bytes / gt_bytes or workgroups beyond n_blocks is SKIPPED (nothing of it read,
+ *   [1, SEGCLIP_SEG_BOUNDARY_MAX_RADIUS], offsets inconsistent with pred_bytes / gt_bytes or workgroups beyond n_blocks is SKIPPED (nothing of it read,
  *   written or counted).
  *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: C > 256, max_side outside [1, 2^15), a workspace smaller
  *   than ws_bytes.
  *   SEGCLIP_ERR_INVALID: areas or gt_band without gt, a band output overlapping an input or the other band, C < 1, missing
  *   pointers.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_BOUNDARY_TILE_H 32      /* rows and */
+#define SEGCLIP_SEG_BOUNDARY_TILE_W 64      /* columns of one wave's strip */
+#define SEGCLIP_SEG_BOUNDARY_WAVES 4        /* consecutive strips of a map that share a workgroup */
+#define SEGCLIP_SEG_BOUNDARY_COLS 8         /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_BOUNDARY_MAX_RADIUS 128
 int64_t segclip_seg_boundary_ws_bytes(int64_t pred_bytes, int64_t gt_bytes);
 int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* pred,
                          int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
@@ -958,7 +997,7 @@ int segclip_seg_confusion_route(int64_t C, int wide);
  * segclip_retrieval_thresholds (modules/modeling.py:338-372 restricted to the ground-truth pairs): thr_t[t] = sim[t, g[t]] as
  *   the k-ordered fp32 fused-multiply-add chain the matrix cores form; n_cap[j] = the captions of image j; best[j] = the
  *   maximum of thr_t over them, an integer atomic maximum on an order-preserving key (no float atomics), +inf where
- *   n_cap[j] = 0.  A g[t] outside [0, Ni) is found on the device: bit 0 of *status is set (status is OR-ed into, never
+ *   n_cap[j] = 0.  A g[t] outside [0, Ni) is found on the device: SEGCLIP_RETRIEVAL_BAD_INDEX of *status is set (status is OR-ed into, never
  *   cleared here), thr_t[t] = +inf, and the caption counts for no image.  thr_t (Nt), best (Ni) fp32, n_cap (Ni) int32 are
  *   written whole.
  * segclip_retrieval_count (modules/modeling.py:356-357, the logits product, and the ranking a consumer of
@@ -973,6 +1012,7 @@ int segclip_seg_confusion_route(int64_t C, int wide);
  * SEGCLIP_ERR_UNSUPPORTED, naming the argument: E not a multiple of 32 or above 1024; Ni or Nt >= 2^24.
  * Bound of the count pass: 2 Nt Ni E flop at the f32-MFMA rate (256 flop / clock / CU).
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_RETRIEVAL_BAD_INDEX 1 /* status bit: an image index outside [0, Ni) */
 int segclip_retrieval_thresholds(const float* V, const float* T, const int32_t* g, int64_t Ni, int64_t Nt, int64_t E, float* thr_t,
                                  float* best, int32_t* n_cap, int32_t* status, void* stream);
 int segclip_retrieval_count(const float* V, const float* T, const int32_t* g, const float* thr_t, const float* best, int64_t Ni,
@@ -1022,7 +1062,7 @@ int segclip_retrieval_topk(const float* Q, const float* X, int64_t Nq, int64_t N
  * segclip_train_images_from_u8: RawImageExtractor's transforms (dataloaders/rawimage_util.py:40-52: RandomResizedCropCoord
  * with Image.BICUBIC :45, :347-361, or Resize + CenterCrop :47; ToTensor and Normalize :49) = Pillow's 8-bit BICUBIC resize of
  * a crop, a window of the result, a value table.
- *   images : (B, 13) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
+ *   images : (B, SEGCLIP_TRAIN_SOURCE_COLS) int64 rows on the device: 0 address of the source (uint8, HWC, 3 interleaved channels)  1 h  2 w
  *            3 row stride in bytes (>= 3 w)  4 x0  5 y0  6 bw  7 bh, the crop box inside the source - the filter sees the box
  *            as the whole image (crop() then resize(), NOT resize(box=...))  8 RW  9 RH, the size the box is resized to
  *            10 ox  11 oy, the offset of the (out_h, out_w) output window inside (RH, RW)  12 flags: bit 0 = horizontal,
@@ -1035,14 +1075,14 @@ int segclip_retrieval_topk(const float* Q, const float* X, int64_t Nq, int64_t N
  * index order, each divided by the sum, each rounded to (int)(w * 2^22 +- 0.5) with the sign of w.  A pass is
  * clamp((2^21 + sum byte * k) >> 22, 0, 255) in int32; the horizontal pass runs first and is rounded to bytes.
  *   Every row is range-checked on the device.  An image is ZERO-FILLED when its row has a null address, a stride below 3 w,
- *   one of h, w, RW, RH outside [1, 2^15), a box not inside (h, w), a window not inside (RH, RW), bw > 8 RW or bh > 8 RH
- *   (at most 33 taps), or flags outside 0..3; the other images are unaffected.  Nothing is read outside the box.
+ *   one of h, w, RW, RH outside [1, 2^15), a box not inside (h, w), a window not inside (RH, RW), bw or bh above
+ *   SEGCLIP_TRAIN_MAX_SCALE times RW or RH (at most 33 taps), or flags outside 0..3; the other images are unaffected.  Nothing is read outside the box.
  *   16-byte stores when out_w % 4 == 0 and out is 16-byte aligned, scalar stores otherwise.  Design bound: the crop bytes
- *   read once + 12 bytes written per output pixel.  SEGCLIP_ERR_UNSUPPORTED: out_w > 256.  out_h < 2^15, B <= 2^24.
+ *   read once + 12 bytes written per output pixel.  SEGCLIP_ERR_UNSUPPORTED: out_w > SEGCLIP_TRAIN_MAX_OUT_W.  out_h < 2^15, B <= 2^24.
  *
  * segclip_train_patch_labels: get_felzenszwalb_from_cache (dataloaders/rawimage_util.py:100-144) given the integer box of
  * :119-120, which the host computes.
- *   maps   : (B, 9) int64 rows on the device: 0 address of the map (int32, (h, w), 4-byte aligned)  1 h  2 w  3 row stride in
+ *   maps   : (B, SEGCLIP_TRAIN_MAP_COLS) int64 rows on the device: 0 address of the map (int32, (h, w), 4-byte aligned)  1 h  2 w  3 row stride in
  *            bytes (>= 4 w, a multiple of 4)  4 x0  5 y0  6 x1  7 y1, the box; x1 - x0 < 2 or y1 - y0 < 2 takes the whole
  *            map (:122)  8 flags: bit 0 = horizontal, bit 1 = vertical flip of the cropped map (:127-128)
  *   out    : (B, 1, size / patch, size / patch) int64
@@ -1052,6 +1092,10 @@ int segclip_retrieval_topk(const float* Q, const float* X, int64_t Nq, int64_t N
  *   A row with a null or unaligned address, a stride below 4 w, h or w outside [1, 2^15), a box outside the map, flags outside
  *   0..3, or a NEGATIVE label among the pixels read gives -1 in all its entries; the other rows are unaffected.
  * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_TRAIN_SOURCE_COLS 13 /* int64 columns of one row of the source table */
+#define SEGCLIP_TRAIN_MAP_COLS 9     /* int64 columns of one row of the map table */
+#define SEGCLIP_TRAIN_MAX_SCALE 8    /* crop side / resized side, per axis */
+#define SEGCLIP_TRAIN_MAX_OUT_W 256  /* columns of the output window */
 int segclip_train_images_from_u8(const int64_t* images, int64_t B, int64_t out_h, int64_t out_w, const float* lut, float* out,
                                  void* stream);
 int segclip_train_patch_labels(const int64_t* maps, int64_t B, int64_t size, int64_t patch, int64_t* out, void* stream);

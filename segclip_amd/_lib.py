@@ -6,220 +6,154 @@ and streams only); nothing of torch crosses the C ABI.
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
-F32, BF16 = 0, 1
-ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2
-GEMM_DEFER_SPLITK, GEMM_DEFER_COLSUM = 1, 2
-REDUCE_SLABS, REDUCE_ROWS, REDUCE_MAX = 0, 1, 16
-ATTN_FP8 = 1
-
-_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsegclip_hip.so")
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_LIB_PATH = os.path.join(_HERE, "libsegclip_hip.so")
+_BUILT_HEADER_PATH = os.path.join(_HERE, "libsegclip_hip.h")   # the header as csrc/build.sh compiled it
+_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "segclip_hip.h")
 _lib = None
 
 i64, i32, f32, vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
 
-
-class GemmDesc(C.Structure):
-    _fields_ = [("A", vp), ("B", vp), ("C", vp), ("bias", vp), ("residual", vp), ("aux", vp),
-                ("M", i64), ("N", i64), ("K", i64), ("sam", i64), ("sak", i64), ("sbn", i64), ("sbk", i64),
-                ("ldc", i64), ("ldr", i64), ("ldaux", i64), ("nb1", i64), ("nb2", i64),
-                ("bsA1", i64), ("bsA2", i64), ("bsB1", i64), ("bsB2", i64), ("bsC1", i64), ("bsC2", i64),
-                ("bsR1", i64), ("bsR2", i64),
-                ("a_dtype", i32), ("b_dtype", i32), ("c_dtype", i32), ("r_dtype", i32),
-                ("act", i32), ("mul_dact", i32), ("alpha", f32), ("aux_kind", i32),
-                ("ws", vp), ("ws_bytes", i64), ("colsum", vp), ("colsum_ws", vp), ("flags", i32), ("res_row_mod", i32)]
-
-
-class GemmRoute(C.Structure):
-    _fields_ = [("family", i32), ("a_ks", i32), ("b_ks", i32), ("tile_m", i32), ("tile_n", i32), ("splits", i32),
-                ("variant", i32)]
-
-
-# segclip_gemm_route.family
-GEMM_ROUTE_FAMILIES = {0: None, 1: "generic", 2: "dma", 3: "p8", 4: "pq", 5: "f32"}
+# ---------------------------------------------------------------- the ABI, read from the header
+# The types that cross the ABI by value; the names of _POINTEES may stand only behind a `*`.  Any other name is an error.
+_SCALARS = {"int": C.c_int, "int32_t": i32, "int64_t": i64, "float": f32, "double": C.c_double, "size_t": C.c_size_t}
+_POINTEES = {"void", "char", "uint8_t", "uint16_t"}
+STRUCT_NAMES = {"segclip_gemm_desc": "GemmDesc", "segclip_gemm_route": "GemmRoute", "segclip_attn_route": "AttnRoute",
+                "segclip_reduce_entry": "ReduceEntry", "segclip_wgrad_item": "WgradItem", "segclip_train_ctrl": "TrainCtrl",
+                "segclip_adamw_group": "AdamWGroup", "segclip_adamw_tensor": "AdamWTensor", "segclip_attn_desc": "AttnDesc",
+                "segclip_resblock_fwd_desc": "ResBlockFwdDesc"}
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_DEFINE = re.compile(r"\s*#\s*define\s+(SEGCLIP_\w+)\s+\(?(-?\d+)\)?\s*$")
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_ENUM = re.compile(r"enum\s*\w*\s*\{([^{}]*)\}\s*;")
+_PROTOTYPE = re.compile(r"([\w\s*]+?)\b(segclip_\w+)\s*\(([^(){};]*)\)\s*;")
+_DECLARATOR = re.compile(r"\s*((?:\*\s*(?:const\s*)?)*)(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*$")
 
 
-class AttnRoute(C.Structure):
-    _fields_ = [("fwd_kernel", i32), ("bwd_kernel", i32), ("tiles", i32), ("variant", i32)]
+def _blank(m):
+    return " " + "\n" * m.group(0).count("\n")   # keeps every line number
 
 
-# segclip_attn_route.fwd_kernel / bwd_kernel
-ATTN_ROUTE_KERNELS = {0: None, 1: "smallq", 2: "pf", 3: "generic", 4: "f32", 5: "dqw", 6: "stream", 7: "spl", 8: "sp",
-                      9: "twopass"}
+def _parse_header(path):
+    """include/segclip_hip.h -> (name -> (restype, argtypes), typedef name -> Structure class, constant name -> int).
+    Strict: beside comments and preprocessor lines, everything at file scope is a `typedef struct`, an `enum`, a prototype or the
+    extern "C" wrapper, and every type name stands in the tables above.  Anything else raises and names the line; no type is
+    ever guessed."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"segclip_amd: {path} not found - the binding is read from the C header of the source tree "
+                           "(include/segclip_hip.h beside the segclip_amd package). There is no built-in copy of the ABI.")
+    text = re.sub(_COMMENT, _blank, open(path).read())
+    signatures, structs, constants = {}, {}, {}
+
+    def fail(pos, msg):
+        raise RuntimeError(f"segclip_amd: {path}:{text.count(chr(10), 0, pos) + 1}: {msg}")
+
+    def directive(m):   # `#define SEGCLIP_X <integer>` is a constant; a guard, #include, #if... say nothing about the ABI
+        d = _DEFINE.match(m.group(0))
+        if d:
+            constants[d.group(1)] = int(d.group(2))
+        elif re.match(r"\s*#\s*define\s+\w+\s+\S", m.group(0)):
+            fail(m.start(), f"a macro that is no `SEGCLIP_X <integer>`: {m.group(0).strip()!r}")
+        return _blank(m)
+    text = re.sub(r"^[ \t]*#[^\n]*", directive, text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}\s*\Z', _blank, text)
+
+    def declare(decl, pos, result=False):
+        """'const float* const* gamma' or 'int64_t M, N, K' or 'int32_t reserved[2]' -> [(name, ctype), ...]"""
+        m = re.match(r"\s*(?:const\s+)?(\w+)\b(.*)$", decl, flags=re.S)
+        base, out = (m.group(1), []) if m else fail(pos, f"cannot read the declaration {decl.strip()!r}")
+        for part in m.group(2).split(","):
+            d = _DECLARATOR.match(part) or fail(pos, f"cannot read the declaration {decl.strip()!r}")
+            stars, name, length = d.group(1).count("*"), d.group(2), d.group(3)
+            if not (base in _SCALARS or stars and (base in _POINTEES or base in structs)):
+                fail(pos, f"unknown type {base + '*' * stars!r} of {name!r}")
+            t = (_SCALARS[base] if not stars else C.POINTER(structs[base]) if stars == 1 and base in structs else
+                 C.c_char_p if result and stars == 1 and base == "char" else vp)
+            out.append((name, t * int(length) if length else t))
+        return out
+
+    def declare_each(body, start, sep):   # the declarations of a struct body or a parameter list, each with its own line
+        for m in re.finditer(r"[^%s]+" % sep, body):
+            if m.group(0).strip():
+                yield from declare(m.group(0), start + m.start() + len(m.group(0)) - len(m.group(0).lstrip()))
+
+    pos = re.compile(r"\s*").match(text).end()
+    while pos < len(text):
+        if (m := _STRUCT.match(text, pos)):
+            if m.group(1) != m.group(3) or m.group(1) not in STRUCT_NAMES:
+                fail(pos, f"struct {m.group(1)} has no class name in STRUCT_NAMES")
+            if not re.search(r";\s*$", m.group(2)):
+                fail(m.end(2), "the last member of the struct has no ';'")
+            structs[m.group(1)] = type(STRUCT_NAMES[m.group(1)], (C.Structure,),
+                                       {"_fields_": list(declare_each(m.group(2), m.start(2), ";")), "__doc__": m.group(1)})
+        elif (m := _ENUM.match(text, pos)):
+            value = -1
+            for item in filter(None, (e.strip() for e in m.group(1).split(","))):
+                e = re.match(r"(SEGCLIP_\w+)(?:\s*=\s*(-?\d+))?$", item) or fail(pos, f"cannot read the enumerator {item!r}")
+                value = int(e.group(2)) if e.group(2) else value + 1
+                constants[e.group(1)] = value
+        elif (m := _PROTOTYPE.match(text, pos)):
+            if m.group(2) in signatures:
+                fail(pos, f"{m.group(2)} is declared twice")
+            (_, restype), = declare(m.group(1) + " " + m.group(2), pos, result=True)
+            params = [] if m.group(3).strip() == "void" else list(declare_each(m.group(3), m.start(3), ","))
+            if any(issubclass(t, C.Array) for _, t in params):
+                fail(pos, f"{m.group(2)} has an array parameter")
+            signatures[m.group(2)] = (restype, [t for _, t in params])
+        else:
+            fail(pos, f"neither a struct, an enum nor a prototype: {text[pos:].split(chr(10), 1)[0][:80]!r}")
+        pos = re.compile(r"\s*").match(text, m.end()).end()
+    missing = sorted(set(STRUCT_NAMES) - set(structs))
+    if missing:
+        raise RuntimeError(f"segclip_amd: {path} does not define {missing}")
+    return signatures, structs, constants
 
 
-class ReduceEntry(C.Structure):
-    _fields_ = [("src", vp), ("out0", vp), ("out1", vp), ("out2", vp), ("rows", i64), ("width", i64), ("ld", i64), ("seg", i64),
-                ("scale", f32), ("out_dtype", i32)]
+# name -> (restype, argtypes) of every entry; the Structure classes; every `#define SEGCLIP_X <integer>` and enumerator
+SIGNATURES, _structs, CONSTANTS = _parse_header(_HEADER_PATH)
+globals().update({cls.__name__: cls for cls in _structs.values()})   # GemmDesc, GemmRoute, ...: the values of STRUCT_NAMES
 
 
-class WgradItem(C.Structure):
-    _fields_ = [("dy", vp), ("x", vp), ("dw", vp), ("M", i64), ("N", i64), ("ld_dy", i64), ("ld_x", i64), ("ld_dw", i64)]
+def const(name):
+    """The header's SEGCLIP_<name>."""
+    return CONSTANTS["SEGCLIP_" + name]
 
 
-class TrainCtrl(C.Structure):
-    _fields_ = [("grad_sqnorm", f32), ("clip_coef", f32), ("nan_skips", i32), ("steps", i32),
-                ("loss_sum", f32), ("last_loss", f32), ("reserved", i32 * 2)]
+def _routes(prefix):
+    return {v: None if k == prefix + "NONE" else k[len(prefix):].lower() for k, v in CONSTANTS.items() if k.startswith(prefix)}
 
 
-class AdamWGroup(C.Structure):
-    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_double), ("b1", C.c_double), ("b2", C.c_double),
-                ("eps", C.c_double), ("warmup", C.c_double), ("lr_start", C.c_double), ("lr_end", C.c_double),
-                ("t_total", i64), ("schedule", i32), ("reserved", i32)]
+F32, BF16 = const("F32"), const("BF16")
+ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = const("ACT_NONE"), const("ACT_QUICK_GELU"), const("ACT_GELU_ERF")
+GEMM_DEFER_SPLITK, GEMM_DEFER_COLSUM = const("GEMM_DEFER_SPLITK"), const("GEMM_DEFER_COLSUM")
+REDUCE_SLABS, REDUCE_ROWS, REDUCE_MAX = const("REDUCE_SLABS"), const("REDUCE_ROWS"), const("REDUCE_MAX")
+ATTN_FP8 = const("ATTN_FP8")
+GEMM_ROUTE_FAMILIES = _routes("SEGCLIP_GEMM_ROUTE_")   # segclip_gemm_route.family
+ATTN_ROUTE_KERNELS = _routes("SEGCLIP_ATTN_ROUTE_")    # segclip_attn_route.fwd_kernel / bwd_kernel
 
 
-class AdamWTensor(C.Structure):
-    _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("shadow_bf16", vp),
-                ("n", i64), ("step", i32), ("group", i32)]
+def _code_lines(path):
+    """(line number, text) of every line of a header that holds code, comments dropped and white space normalised"""
+    text = re.sub(_COMMENT, _blank, open(path).read())
+    return [(n, " ".join(line.split())) for n, line in enumerate(text.split("\n"), 1) if line.strip()]
 
 
-class AttnDesc(C.Structure):
-    _fields_ = [("Q", vp), ("K", vp), ("V", vp), ("O", vp), ("stats", vp), ("dO", vp), ("dQ", vp), ("dK", vp),
-                ("dV", vp), ("ws", vp),
-                ("B", i64), ("H", i64), ("Tq", i64), ("Tk", i64), ("hd", i64),
-                ("q_sb", i64), ("q_st", i64), ("k_sb", i64), ("k_st", i64), ("v_sb", i64), ("v_st", i64),
-                ("o_sb", i64), ("o_st", i64),
-                ("dq_sb", i64), ("dq_st", i64), ("dk_sb", i64), ("dk_st", i64), ("dv_sb", i64), ("dv_st", i64),
-                ("do_sb", i64), ("do_st", i64),
-                ("scale", f32), ("causal", i32), ("dtype", i32), ("flags", i32), ("colsum_part", vp), ("klen", vp)]
-
-
-class ResBlockFwdDesc(C.Structure):
-    _fields_ = [("x", vp), ("ln1w", vp), ("ln1b", vp), ("wqkv", vp), ("bqkv", vp), ("wo", vp), ("bo", vp),
-                ("ln2w", vp), ("ln2b", vp), ("wfc", vp), ("bfc", vp), ("wpr", vp), ("bpr", vp),
-                ("y1", vp), ("mean1", vp), ("rstd1", vp), ("qkv", vp), ("o", vp), ("stats", vp), ("x1", vp),
-                ("y2", vp), ("mean2", vp), ("rstd2", vp), ("h", vp), ("ld_h", i64), ("u", vp), ("ld_u", i64), ("xo", vp),
-                ("klen", vp), ("M", i64), ("B", i64), ("T", i64), ("D", i64), ("F", i64), ("H", i64),
-                ("eps", f32), ("attn_scale", f32), ("causal", i32), ("act", i32), ("aux_kind", i32), ("x_dtype", i32)]
-
-
-# name -> (restype, argtypes); every symbol declared in include/segclip_hip.h
-SIGNATURES = {
-    "segclip_version": (C.c_int, []),
-    "segclip_last_error_string": (C.c_char_p, []),
-    "segclip_gemm_ws_bytes": (C.c_size_t, [C.POINTER(GemmDesc)]),
-    "segclip_gemm_splits": (C.c_int, [C.POINTER(GemmDesc)]),
-    "segclip_gemm": (C.c_int, [C.POINTER(GemmDesc), vp]),
-    "segclip_reduce_multi": (C.c_int, [C.POINTER(ReduceEntry), C.c_int, C.c_int, vp]),
-    "segclip_layernorm_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, vp]),
-    "segclip_layernorm_bwd_ws_bytes": (C.c_size_t, [i64, i64]),
-    "segclip_layernorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
-    "segclip_wgrad_group_splits": (C.c_int, [i64, i64]),
-    "segclip_wgrad_group_model_us": (C.c_double, [i64, i64, C.c_int]),
-    "segclip_gemm_pq_half_tail": (C.c_int, [i64]),
-    "segclip_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
-    "segclip_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmRoute), C.POINTER(C.c_size_t)]),
-    "segclip_wgrad_group_ws_bytes": (C.c_size_t, [vp, C.c_int, C.c_int]),
-    "segclip_wgrad_group": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, C.c_size_t, vp]),
-    "segclip_layernorm_fwd_multi": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, vp]),
-    "segclip_layernorm_bwd_multi_ws_bytes": (C.c_size_t, [i64, i64, C.c_int]),
-    "segclip_layernorm_bwd_multi": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, vp]),
-    "segclip_layernorm_fwd_seg": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, i64, i64, i64, vp]),
-    "segclip_layernorm_bwd_seg": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int,
-                                            i64, i64, i64, vp]),
-    "segclip_attn_stats_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
-    "segclip_attn_bwd_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
-    "segclip_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
-    "segclip_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
-    "segclip_attn_last_route": (C.c_int, [C.POINTER(AttnRoute)]),
-    "segclip_resblock_fwd": (C.c_int, [C.POINTER(ResBlockFwdDesc), vp]),
-    "segclip_cast": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp]),
-    "segclip_split3_bf16": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp]),
-    "segclip_colsum_ws_bytes": (C.c_size_t, [i64, i64]),
-    "segclip_colsum": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int, vp]),
-    "segclip_act_fwd": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp]),
-    "segclip_act_bwd": (C.c_int, [vp, vp, vp, i64, C.c_int, C.c_int, vp]),
-    "segclip_add": (C.c_int, [vp, vp, vp, i64, C.c_int, vp]),
-    "segclip_scale": (C.c_int, [vp, vp, vp, i64, vp]),
-    "segclip_gumbel_from_uniform": (C.c_int, [vp, vp, i64, vp]),
-    "segclip_reduce_sum": (C.c_int, [vp, vp, i64, f32, vp]),
-    "segclip_ce_labels_fwd": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, i64, vp]),
-    "segclip_ce_labels_bwd": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, i64, vp]),
-    "segclip_im2col": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, C.c_int, C.c_int, vp]),
-    "segclip_im2col_ld": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, C.c_int, C.c_int, i64, vp]),
-    "segclip_vis_assemble": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
-    "segclip_embed_fwd": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_embed_bwd": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_recon_mix_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_recon_mix_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_mean_cat_fwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),
-    "segclip_mean_cat_bwd": (C.c_int, [vp, vp, i64, i64, i64, vp]),
-    "segclip_mae_unshuffle_fwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_mae_unshuffle_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_gather_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, C.c_int, vp]),
-    "segclip_scatter_rows": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, C.c_int, vp]),
-    "segclip_assign_fwd": (C.c_int, [vp, vp, f32, vp, vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_assign_bwd": (C.c_int, [vp, vp, f32, vp, i64, i64, i64, vp]),
-    "segclip_l2norm_fwd": (C.c_int, [vp, vp, vp, i64, i64, vp]),
-    "segclip_l2norm_bwd": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
-    "segclip_ce_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_ce_bwd": (C.c_int, [vp, vp, vp, f32, vp, i64, i64, i64, vp]),
-    "segclip_superpixel_kl": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_masked_mse_fwd": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
-    "segclip_masked_mse_bwd": (C.c_int, [vp, vp, vp, vp, vp, f32, vp, i64, i64, i64, C.c_int, vp]),
-    "segclip_mask_sort": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_interp_bicubic": (C.c_int, [vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_seg_group_table": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
-    "segclip_seg_label_map": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                        vp, vp, vp]),
-    "segclip_seg_logits": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                     vp, vp]),
-    "segclip_seg_label_map_rescaled": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                                 vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_label_map_rescaled_sweep": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, i64,
-                                                       vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_label_map_views": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                              vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_view_probs": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                         vp, i64, vp]),
-    "segclip_seg_areas": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_label_map_rescaled_wide": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_int, f32,
-                                                      vp, i64, vp, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_areas_wide": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
-    "segclip_seg_view_windows_from_u8": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, C.c_int, vp, vp]),
-    "segclip_seg_groups_rescaled": (C.c_int, [vp, i64, vp, i64, i64, i64, vp, i64, vp]),
-    "segclip_seg_blend": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, C.c_int, C.c_double, C.c_double, C.c_int, vp, i64, vp, vp]),
-    "segclip_seg_refine_ws_bytes": (i64, [i64, i64, i64]),
-    "segclip_seg_refine": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, vp, i64, i64, vp, vp, C.c_int, vp, i64, vp, i64, C.c_int,
-                                     C.c_int, vp, vp, i64, vp, i64, vp]),
-    "segclip_seg_components_ws_bytes": (i64, [i64, i64, i64]),
-    "segclip_seg_components": (C.c_int, [vp, i64, i64, i64, vp, i64, C.c_int, C.c_int, vp, vp, i64, vp, i64, vp, i64, C.c_int, vp,
-                                         i64, vp, i64, vp]),
-    "segclip_seg_sieve_ws_bytes": (i64, [i64, i64, i64]),
-    "segclip_seg_sieve": (C.c_int, [vp, i64, i64, i64, vp, i64, C.c_int, C.c_int, i64, C.c_int, C.c_int, vp, i64, vp, i64, vp]),
-    "segclip_seg_boundary_ws_bytes": (i64, [i64, i64]),
-    "segclip_seg_boundary": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, i64, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp]),
-    "segclip_seg_confusion": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_confusion_wide": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp, vp]),
-    "segclip_seg_confusion_route": (C.c_int, [i64, C.c_int]),
-    "segclip_retrieval_thresholds":(C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
-    "segclip_retrieval_count": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
-    "segclip_retrieval_hist": (C.c_int, [vp, vp, vp, i64, i64, vp, vp, vp]),
-    "segclip_retrieval_topk_ws_bytes": (i64, [i64, i64, i64, i64]),
-    "segclip_retrieval_topk": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
-    "segclip_train_images_from_u8":(C.c_int, [vp, i64, i64, i64, vp, vp, vp]),
-    "segclip_train_patch_labels": (C.c_int, [vp, i64, i64, i64, vp, vp]),
-    "segclip_multi_cast_bf16": (C.c_int, [vp, vp, vp, i64, vp]),
-    "segclip_multi_add_f32": (C.c_int, [vp, vp, vp, i64, vp]),
-    "segclip_max_tokens_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_max_tokens_bwd": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_l2norm_pair_fwd": (C.c_int, [vp, vp, vp, vp, i64, i64, vp]),
-    "segclip_l2norm_pair_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, vp]),
-    "segclip_clip_ce_fwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_clip_ce_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp]),
-    "segclip_segmean_fwd": (C.c_int, [vp, vp, C.c_int, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_segmean_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_center_logits_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_center_logits_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp]),
-    "segclip_group_linear64": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, vp, i64, C.c_int, vp]),
-    "segclip_grad_sqnorm_ws_bytes": (C.c_size_t, [vp, i64]),
-    "segclip_grad_sqnorm": (C.c_int, [vp, vp, i64, vp, vp, f32, vp]),
-    "segclip_adamw_step": (C.c_int, [vp, i64, vp, i64, vp, vp, C.c_int, vp]),
-    "segclip_train_step_finish": (C.c_int, [vp, vp, vp, f32, vp]),
-}
+def _check_built_header():
+    """The library must have been compiled from the header that this binding was read from (csrc/build.sh keeps a copy of what
+    it compiled beside the library): a prototype, struct or table width that differs would hand the kernels wrong arguments."""
+    if not os.path.exists(_BUILT_HEADER_PATH):
+        raise RuntimeError(f"segclip_amd: {_BUILT_HEADER_PATH} not found - rebuild the library with segclip_amd/csrc/build.sh")
+    if open(_HEADER_PATH).read() == open(_BUILT_HEADER_PATH).read():
+        return
+    now, built = _code_lines(_HEADER_PATH), _code_lines(_BUILT_HEADER_PATH)
+    if [t for _, t in now] != [t for _, t in built]:
+        (n, line), (_, was) = next((a, b) for a, b in zip(now + [(0, "")], built + [(0, "")]) if a[1] != b[1])
+        raise RuntimeError(f"segclip_amd: {_LIB_PATH} was built from another {_HEADER_PATH} - rebuild it (segclip_amd/csrc/build.sh). "
+                           f"First difference, line {n}: {line!r}; the library was built with {was!r}")
 
 
 def lib_path():
@@ -235,13 +169,15 @@ def load():
         raise RuntimeError(
             f"segclip_amd: {_LIB_PATH} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or segclip_amd/csrc/build.sh (hipcc, gfx950). There is no CPU / PyTorch fallback.")
+    _check_built_header()
     lib = C.CDLL(_LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale w.r.t. the header
         fn.restype = res
         fn.argtypes = args
-    if lib.segclip_version() != 1:
-        raise RuntimeError("segclip_amd: ABI version mismatch")
+    if lib.segclip_version() != const("ABI_VERSION"):
+        raise RuntimeError(f"segclip_amd: ABI version mismatch: {_LIB_PATH} is version {lib.segclip_version()}, "
+                           f"{_HEADER_PATH} is version {const('ABI_VERSION')}")
     _lib = lib
     return lib
 
@@ -253,7 +189,7 @@ class Unsupported(RuntimeError):
 def check(rc, what):
     if rc != 0:
         msg = load().segclip_last_error_string().decode(errors="replace")
-        raise (Unsupported if rc == -2 else RuntimeError)(f"segclip_hip {what} failed (rc={rc}): {msg}")
+        raise (Unsupported if rc == const("ERR_UNSUPPORTED") else RuntimeError)(f"segclip_hip {what} failed (rc={rc}): {msg}")
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -283,6 +219,11 @@ def ptr(t):
         raise RuntimeError("segclip_amd: HIP kernels need device tensors (there is no CPU fallback); got a "
                            f"{t.device} tensor")
     return C.c_void_p(t.data_ptr())
+
+
+def struct_ptr(t, cls):
+    """ptr(t) for an argument that the header declares as a pointer to the struct `cls`."""
+    return None if t is None else C.cast(ptr(t), C.POINTER(cls))
 
 
 def require_cuda(*tensors):

@@ -59,4 +59,6 @@ rc=0
 for p in "${pids[@]}"; do wait $p || rc=1; done
 [ $rc -eq 0 ] || { echo "build failed" >&2; exit 1; }
 $HIPCC --offload-arch=gfx950 -shared -fPIC build/*.o -o $OUT
+# the header these objects were compiled from: _lib.load() refuses a library whose header differs from the one it binds
+cp ../../include/segclip_hip.h ${OUT%.so}.h
 echo "built $(realpath $OUT)"

@@ -17,7 +17,7 @@ constexpr int PITCH = BT + 1;     // k-major LDS image [k][row]: the one-float-p
 constexpr int NCH = BT * BK / (4 * NT);  // 16-byte chunks of a slice per thread
 constexpr int HIST_LDS = 2048;    // ranks below it are counted in LDS first (a trained model's ranks are small)
 
-#define RETRIEVAL_BAD_INDEX 1     // status bit: a g[t] outside [0, Ni)
+#define RETRIEVAL_BAD_INDEX SEGCLIP_RETRIEVAL_BAD_INDEX     // status bit: a g[t] outside [0, Ni)
 
 // order-preserving map of a float onto unsigned integers: the segment maximum is an integer atomicMax
 __device__ __forceinline__ uint32_t ord_key(float f) {

@@ -18,9 +18,9 @@
 
 #include <atomic>
 
-#define SEG_MAX_G 8          // groups per window (the center stage has 8)
+#define SEG_MAX_G SEGCLIP_SEG_MAX_GROUPS          // groups per window (the center stage has 8)
 #define SEG_MAX_COVER 16     // windows covering one pixel
-#define SEG_MAX_IMG_WIN 64   // windows per image
+#define SEG_MAX_IMG_WIN SEGCLIP_SEG_MAX_IMAGE_WINDOWS   // windows per image
 #define SEG_TAB_FLOATS 8192  // LDS budget of the block's table copies
 
 namespace {

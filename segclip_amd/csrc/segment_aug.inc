@@ -12,9 +12,8 @@
 // per chunk and every view's (maximum, sum) is kept in LDS from the first walk.  Bound: ALU, about 3 * V * C logit
 // evaluations and V * C expf per output pixel; one byte of HBM written.
 
-#define SEG_MAX_VIEWS 16
-#define SI_FLAGS 14                       // image-table column: bit 0 horizontal flip, bit 1 vertical flip
-#define SEG_VIEW_COLS 2                   // int64 columns of one row of the view table: first image-table row, view count
+#define SEG_MAX_VIEWS SEGCLIP_SEG_MAX_VIEWS
+#define SEG_VIEW_COLS SEGCLIP_SEG_VIEW_COLS                   // int64 columns of one row of the view table: first image-table row, view count
 #define SEG_AUG_LDS_BYTES (96 * 1024)     // dynamic LDS the launch may ask for (beside about 7 KiB of static LDS)
 enum { VG_H, VG_W, VG_WIN_H, VG_WIN_W, VG_GH, VG_GW, VG_FLAGS, VG_FIRST, VG_COUNT, VG_N };
 

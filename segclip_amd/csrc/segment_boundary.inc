@@ -13,12 +13,12 @@
 // Work per pixel: the rows pass O(1), the band pass (SEG_BD_SH + 2 d) / SEG_BD_SH row visits of one byte and two uint16, all
 // coalesced across the lanes.  Integer sums: the result depends on no schedule.
 
-#define SEG_BD_COLS 8            // int64 columns of one image row of the table (segclip_hip.h)
-#define SEG_BD_SH 32             // rows of a wave's strip
-#define SEG_BD_TW 64             // its columns: the wave
-#define SEG_BD_WAVES 4           // strips of a workgroup, consecutive in the image's raster order of strips
-#define SEG_BD_LIMIT (1 << 15)
-#define SEG_BD_MAX_RADIUS 128
+#define SEG_BD_COLS SEGCLIP_SEG_BOUNDARY_COLS            // int64 columns of one image row of the table (segclip_hip.h)
+#define SEG_BD_SH SEGCLIP_SEG_BOUNDARY_TILE_H             // rows of a wave's strip
+#define SEG_BD_TW SEGCLIP_SEG_BOUNDARY_TILE_W             // its columns: the wave
+#define SEG_BD_WAVES SEGCLIP_SEG_BOUNDARY_WAVES           // strips of a workgroup, consecutive in the image's raster order of strips
+#define SEG_BD_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
+#define SEG_BD_MAX_RADIUS SEGCLIP_SEG_BOUNDARY_MAX_RADIUS
 enum { BD_H, BD_W, BD_PRED, BD_GT, BD_RADIUS, BD_BLK };
 static_assert(SEG_BD_TW == SEGCLIP_WAVE && SEG_BD_LIMIT <= 65536, "seg_bd: a row's change count fits uint16");
 

@@ -11,10 +11,10 @@
 // (profiles/seg_frontend.txt): 1.28 TB/s written, 0.16 of the peak - the byte loads, not the writes, set the time; it is 0.6 %
 // of an evaluation call, so the simple form stays (DESIGN.md section 8 names the next step).
 
-#define SEG_FE_COLS 6    // int64 columns of one image row of the source table (segclip_hip.h)
-#define SEG_FE_VIEW_COLS 7  // ... of the view entry's table: the same row and a flag word (bit 0 horizontal, bit 1 vertical flip)
+#define SEG_FE_COLS SEGCLIP_SEG_SOURCE_COLS    // int64 columns of one image row of the source table (segclip_hip.h)
+#define SEG_FE_VIEW_COLS SEGCLIP_SEG_SOURCE_VIEW_COLS  // ... of the view entry's table: the same row and a flag word (bit 0 horizontal, bit 1 vertical flip)
 #define SEG_FE_PPL 4     // consecutive window pixels of a lane: one 16-byte store per channel
-#define SEG_FE_LIMIT (1 << 15)
+#define SEG_FE_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
 enum { FE_SRC, FE_H, FE_W, FE_STRIDE, FE_NET_H, FE_NET_W, FE_FLAGS };
 
 struct SegFrontArgs {

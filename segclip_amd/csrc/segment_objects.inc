@@ -21,11 +21,11 @@
 // Traffic per pixel with every output: local 1 B read + 8 written, roots 2 x 4 read, stats 4 read + 4 written, final 8-9 read +
 // 5 written; the merge touches the rims only.
 
-#define SEG_CC_COLS 8            // int64 columns of one image row of the table (segclip_hip.h)
-#define SEG_CC_TH 16
-#define SEG_CC_TW 64             // the wave: a tile row is one wave's lanes
+#define SEG_CC_COLS SEGCLIP_SEG_CC_COLS   // int64 columns of one image row of the table (segclip_hip.h)
+#define SEG_CC_TH SEGCLIP_SEG_CC_TILE_H
+#define SEG_CC_TW SEGCLIP_SEG_CC_TILE_W             // the wave: a tile row is one wave's lanes
 #define SEG_CC_PIX (SEG_CC_TH * SEG_CC_TW)
-#define SEG_CC_LIMIT (1 << 15)
+#define SEG_CC_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
 #define SEG_CC_SCAN_ITEMS 8
 #define SEG_CC_SCAN_CHUNK (256 * SEG_CC_SCAN_ITEMS)   // entries of the segment counts that one workgroup scans
 enum { CC_H, CC_W, CC_OFF, CC_BLK };

@@ -17,12 +17,12 @@
 // wave's load of one tap is one run of memory); with dilations up to 32 a halo tile in LDS would not pay, and the taps of a
 // picture's working set are served by L2 / the infinity cache.
 
-#define SEG_REFINE_COLS 8        // int64 columns of one image row of the refine table (segclip_hip.h)
-#define SEG_REFINE_TILE 256      // pixels of a workgroup: one per lane
-#define SEG_REFINE_LIMIT (1 << 15)
-#define SEG_REFINE_MAX_D 6
-#define SEG_REFINE_MAX_DIL 32
-#define SEG_REFINE_MAX_T 32
+#define SEG_REFINE_COLS SEGCLIP_SEG_REFINE_COLS        // int64 columns of one image row of the refine table (segclip_hip.h)
+#define SEG_REFINE_TILE SEGCLIP_SEG_REFINE_TILE      // pixels of a workgroup: one per lane
+#define SEG_REFINE_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
+#define SEG_REFINE_MAX_D SEGCLIP_SEG_REFINE_MAX_DILATIONS
+#define SEG_REFINE_MAX_DIL SEGCLIP_SEG_REFINE_MAX_DILATION
+#define SEG_REFINE_MAX_T SEGCLIP_SEG_REFINE_MAX_ITERS
 #define SEG_REFINE_PLANES 8      // class planes of one chunk
 enum { RF_SRC, RF_H, RF_W, RF_STRIDE, RF_LAB, RF_GT, RF_BLK };
 

@@ -7,11 +7,11 @@
 // Both are bandwidth-bound and reuse the descriptor-table scheme of segment_tile.inc: the workgroups of all images are numbered
 // through, a table row names an image's first workgroup, and every row is range-checked on the device.
 
-#define SEG_RENDER_TILE 1024         // pixels of a workgroup (a lane owns 4 consecutive ones)
+#define SEG_RENDER_TILE SEGCLIP_SEG_RENDER_TILE         // pixels of a workgroup (a lane owns 4 consecutive ones)
 #define SEG_RENDER_PPL 4
 #define SEG_RENDER_SOFT_FLOATS 6400  // LDS budget of the staged soft assignment: 8 x 28 x 28 floats fit
-#define SEG_BLEND_COLS 8             // int64 columns of one image row of the blend table (segclip_hip.h)
-#define SEG_BLEND_LIMIT (1 << 15)
+#define SEG_BLEND_COLS SEGCLIP_SEG_BLEND_COLS             // int64 columns of one image row of the blend table (segclip_hip.h)
+#define SEG_BLEND_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
 #define SEG_MAX_PALETTE 256
 enum { BL_SRC, BL_H, BL_W, BL_STRIDE, BL_MAP, BL_OUT, BL_BLK };
 

@@ -14,7 +14,7 @@
 // only those with a contact their parent (4 B) for the group; one 8 B atomic per (tile, voting group).  final: 4 B of root +
 // the gathered area + 1 B of label read, 1 B written, 8 B of slot per small pixel.
 
-#define SEG_SIEVE_MAX_ROUNDS 8
+#define SEG_SIEVE_MAX_ROUNDS SEGCLIP_SEG_SIEVE_MAX_ROUNDS
 
 struct SegSieveArgs {
   SegCCArgs cc;                  // labels = the round's input; parent, root and area as the component kernels left them

@@ -6,7 +6,7 @@
 // is f for the thresholds t < s and 0 for t >= s.  Covers, taps and the foreground scan run once per pixel, by the device
 // functions of segment_pixel.inc / segment_tile.inc; only the class-0 logit is evaluated per threshold, until it wins.
 
-#define SEG_SWEEP_MAX_T 16
+#define SEG_SWEEP_MAX_T SEGCLIP_SEG_MAX_THRESHOLDS
 // dynamic LDS the launch may ask for: 16 KiB of tables + 32 KiB of cover lists + (2 * 17 + 1) * 256 counters, beside 3 KiB static
 #define SEG_SWEEP_LDS_BYTES (88 * 1024)
 

@@ -5,10 +5,14 @@
 // the dense logits): every expression a label depends on is written here once.  One text is not one rounding - the compiler
 // contracts a blend to FMAs per inlining context - so the equality tests of the entries remain what guards the promise.
 
-#define SEG_IMG_COLS 16        // int64 columns of one image row of the descriptor table (segclip_hip.h)
+#define SEG_IMG_COLS SEGCLIP_SEG_IMAGE_COLS        // int64 columns of one image row of the descriptor table (segclip_hip.h)
 #define SEG_EVAL_PPL 4         // consecutive output pixels of a lane
-#define SEG_EVAL_TILE 1024     // output pixels of a workgroup
-enum { SI_FIRST, SI_COUNT, SI_H, SI_W, SI_OH, SI_OW, SI_LAB, SI_GT, SI_BLK, SI_WIN_H, SI_WIN_W, SI_GH, SI_GW, SI_SOFT };
+#define SEG_EVAL_TILE SEGCLIP_SEG_EVAL_TILE     // output pixels of a workgroup
+// the columns of enum segclip_seg_image_col (segclip_hip.h) under the kernels' short names
+#define SI_(X) SI_##X = SEGCLIP_SI_##X
+enum { SI_(FIRST), SI_(COUNT), SI_(H), SI_(W), SI_(OH), SI_(OW), SI_(LAB), SI_(GT), SI_(BLK), SI_(WIN_H), SI_(WIN_W), SI_(GH), SI_(GW), SI_(SOFT),
+       SI_(FLAGS) };
+#undef SI_
 
 struct SegEvalArgs {
   const float* soft;           // flat; window k of image i at soft + row[SI_SOFT] + (k - row[SI_FIRST]) * G * gh * gw

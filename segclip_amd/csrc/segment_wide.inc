@@ -14,7 +14,7 @@
 // table alone exceeds the copy (G * N > 4096) nothing can ever be staged and the launch asks for no copy: 46.5 KiB, three
 // workgroups per CU as the narrow kernel.
 
-#define SEG_WIDE_MAX_CLASSES 1024
+#define SEG_WIDE_MAX_CLASSES SEGCLIP_SEG_WIDE_MAX_CLASSES
 // build-time switch of tools/bench_seg.py --wide: 1 = every lane scans the classes of its own undecided pixels (the narrow
 // kernel's scheme) instead of the wave-cooperative scan
 #ifndef SEG_WIDE_LANE_SCAN

@@ -17,14 +17,14 @@
 // the source with byte loads (each row segment again from L1 for every tap), which a dword path would cut by four.
 // Unmeasured until profiles/train_frontend.txt says otherwise.
 
-#define TF_COLS 13        // int64 columns of one image row of the table (segclip_hip.h)
+#define TF_COLS SEGCLIP_TRAIN_SOURCE_COLS        // int64 columns of one image row of the table (segclip_hip.h)
 #define TF_BAND 16        // output rows of a workgroup: one patch row of the 16-pixel patches
-#define TF_MAX_SCALE 8    // crop side / resized side, per axis
+#define TF_MAX_SCALE SEGCLIP_TRAIN_MAX_SCALE    // crop side / resized side, per axis
 #define TF_MAX_TAPS 33    // (int)ceil(2 * 8) * 2 + 1
-#define TF_MAX_OUT_W 256  // columns of the output window: the coefficient table and 33 tile rows fit the LDS
+#define TF_MAX_OUT_W SEGCLIP_TRAIN_MAX_OUT_W  // columns of the output window: the coefficient table and 33 tile rows fit the LDS
 #define TF_LDS_BYTES (80 * 1024)  // two workgroups per CU
 #define TF_PBITS 22       // Pillow's PRECISION_BITS = 32 - 8 - 2
-#define TF_LIMIT (1 << 15)
+#define TF_LIMIT SEGCLIP_SEG_SOURCE_LIMIT
 enum { TF_SRC, TF_H, TF_W, TF_STRIDE, TF_X0, TF_Y0, TF_BW, TF_BH, TF_RW, TF_RH, TF_OX, TF_OY, TF_FLAGS };
 
 struct TrainFrontArgs {
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void train_front_kernel(TrainFrontArgs A) {
 
 // (b) get_felzenszwalb_from_cache for a batch: crop (or the whole map), flips, ATen's `nearest` resample to size x size, the
 // integer mean of every patch x patch tile.  One workgroup per image, one wave per patch in turn; the kernel is tiny.
-#define TL_COLS 9  // int64 columns of one map row of the table (segclip_hip.h)
+#define TL_COLS SEGCLIP_TRAIN_MAP_COLS  // int64 columns of one map row of the table (segclip_hip.h)
 enum { TL_SRC, TL_H, TL_W, TL_STRIDE, TL_X0, TL_Y0, TL_X1, TL_Y1, TL_FLAGS };
 
 // upsample_nearest's source index: both the quotient and the product in fp32

@@ -41,7 +41,7 @@ def warmup_linear(x, warmup=0.002, lr_start=0., lr_end=0.):
 
 
 SCHEDULES = {'warmup_cosine': warmup_cosine, 'warmup_constant': warmup_constant, 'warmup_linear': warmup_linear}
-_SCHEDULE_ID = {'warmup_cosine': 0, 'warmup_constant': 1, 'warmup_linear': 2}
+_SCHEDULE_ID = {name: L.const('SCHED_' + name.upper()) for name in SCHEDULES}
 _MAX_GROUPS = 16
 
 
@@ -197,7 +197,7 @@ class AdaptAdamW(Optimizer):
         if ctrl is not None:
             L.require_cuda(ctrl)
             self._ctrl = ctrl
-        L.check(lib.segclip_adamw_step(C.cast(arr, C.c_void_p), len(tensors), C.cast(groups, C.c_void_p),
-                                       len(self.param_groups), L.ptr(ctrl), L.ptr(loss.detach()) if loss is not None else None,
-                                       1 if zero_grads else 0, L.stream()), "adamw_step")
+        L.check(lib.segclip_adamw_step(arr, len(tensors), groups, len(self.param_groups), L.struct_ptr(ctrl, L.TrainCtrl),
+                                       L.ptr(loss.detach()) if loss is not None else None, 1 if zero_grads else 0, L.stream()),
+                "adamw_step")
         return ret

@@ -2446,8 +2446,8 @@ def seg_logits(soft_attn, tables, windows, image_first, out_size, win_size, grid
     return out
 
 
-SEG_IMAGE_COLS = 16   # int64 columns of one row of the image table of segclip_seg_label_map_rescaled
-SEG_EVAL_TILE = 1024  # output pixels of one of its workgroups
+SEG_IMAGE_COLS = L.const("SEG_IMAGE_COLS")  # int64 columns of one row of the image table of segclip_seg_label_map_rescaled
+SEG_EVAL_TILE = L.const("SEG_EVAL_TILE")  # output pixels of one of its workgroups
 
 
 def _upload_table(rows, dtype, device):
@@ -2497,7 +2497,8 @@ def _seg_fused_args(what, soft_attn, tables, windows, images, views=None):
         raise TypeError(f"{what}: fp32 soft_attn / tables, int32 window list, int64 image "
                         f"{'table' if views is None else 'and view tables'}")
     if tuple(windows.shape) != (nW, 3) or images.dim() != 2 or images.shape[1] != SEG_IMAGE_COLS or tmax.numel() != nW \
-            or any(t.numel() != nW * G for t in ints + (bsc,)) or (views is not None and (views.dim() != 2 or views.shape[1] != 2)):
+            or any(t.numel() != nW * G for t in ints + (bsc,)) \
+            or (views is not None and (views.dim() != 2 or views.shape[1] != L.const("SEG_VIEW_COLS"))):
         raise ValueError(f"{what}: shapes do not agree")
     return tuple(t.contiguous() for t in (soft_attn, table, tmax, *ints, bsc, windows, *tabs)), (nW, G, N)
 
@@ -2533,7 +2534,7 @@ def seg_label_map_rescaled(soft_attn, tables, windows, images, n_blocks, max_ima
     return labels
 
 
-SEG_WIDE_MAX_CLASSES = 1024   # classes (background included) of the 16-bit label maps: segclip_seg_label_map_rescaled_wide
+SEG_WIDE_MAX_CLASSES = L.const("SEG_WIDE_MAX_CLASSES")  # classes (background included) of the 16-bit label maps: segclip_seg_label_map_rescaled_wide
 
 
 def seg_label_map_rescaled_wide(soft_attn, tables, windows, images, n_blocks, max_image_windows, with_bg, bg_thresh, labels=None,
@@ -2552,7 +2553,7 @@ def seg_label_map_rescaled_wide(soft_attn, tables, windows, images, n_blocks, ma
     return labels
 
 
-SEG_MAX_THRESHOLDS = 16    # background thresholds of one segclip_seg_label_map_rescaled_sweep launch
+SEG_MAX_THRESHOLDS = L.const("SEG_MAX_THRESHOLDS")  # background thresholds of one segclip_seg_label_map_rescaled_sweep launch
 
 
 def seg_label_map_sweep(soft_attn, tables, windows, images, n_blocks, max_image_windows, thresholds, labels=None, gt=None,
@@ -2575,9 +2576,9 @@ def seg_label_map_sweep(soft_attn, tables, windows, images, n_blocks, max_image_
     return labels
 
 
-SEG_MAX_VIEWS = 16         # views of one image in segclip_seg_label_map_views
-SEG_MAX_IMAGE_WINDOWS = 64  # windows of one image, over all its views
-SEG_FLIP_H, SEG_FLIP_V = 1, 2
+SEG_MAX_VIEWS = L.const("SEG_MAX_VIEWS")  # views of one image in segclip_seg_label_map_views
+SEG_MAX_IMAGE_WINDOWS = L.const("SEG_MAX_IMAGE_WINDOWS")  # windows of one image, over all its views
+SEG_FLIP_H, SEG_FLIP_V = L.const("SEG_FLIP_H"), L.const("SEG_FLIP_V")
 
 
 def seg_view_tables(rows, view_counts, device):
@@ -2714,8 +2715,8 @@ def seg_confusion_route(num_classes, dtype=torch.uint8):
     return ("dense", "sparse")[rc]
 
 
-SEG_SOURCE_COLS = 6        # int64 columns of one row of the source table of segclip_seg_windows_from_u8
-SEG_SOURCE_LIMIT = 1 << 15  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
+SEG_SOURCE_COLS = L.const("SEG_SOURCE_COLS")  # int64 columns of one row of the source table of segclip_seg_windows_from_u8
+SEG_SOURCE_LIMIT = L.const("SEG_SOURCE_LIMIT")  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 
 
 def _seg_pictures(what, raws, noun="a source image"):
@@ -2802,7 +2803,7 @@ def seg_windows_from_u8(raws, net_sizes, windows, win_size, mean, inv_std, rever
 def _seg_windows_launch(raws, net_sizes, flags, table, windows, win_size, mean, inv_std, reverse_channels, out):
     """flags None: the plain kernel on the (B, 6) table; a flag word per row: the view kernel on the (B, 7) one."""
     entry, cols = ("segclip_seg_windows_from_u8", SEG_SOURCE_COLS) if flags is None else \
-        ("segclip_seg_view_windows_from_u8", SEG_SOURCE_COLS + 1)
+        ("segclip_seg_view_windows_from_u8", L.const("SEG_SOURCE_VIEW_COLS"))
     if table is None:
         table = seg_view_source_table(raws, net_sizes, flags)
     _check_image_table("seg_windows_from_u8", table, cols, "seg_source_table", rows=len(raws))
@@ -2827,9 +2828,9 @@ def _seg_windows_launch(raws, net_sizes, flags, table, windows, win_size, mean, 
 
 
 # ---------------------------------------------------------------- rendering of segmentation results (segment_render.inc)
-SEG_RENDER_TILE = 1024   # pixels of one workgroup of segclip_seg_groups_rescaled and segclip_seg_blend
-SEG_BLEND_COLS = 8       # int64 columns of one row of the image table of segclip_seg_blend
-SEG_MAX_GROUPS = 8
+SEG_RENDER_TILE = L.const("SEG_RENDER_TILE")  # pixels of one workgroup of segclip_seg_groups_rescaled and segclip_seg_blend
+SEG_BLEND_COLS = L.const("SEG_BLEND_COLS")  # int64 columns of one row of the image table of segclip_seg_blend
+SEG_MAX_GROUPS = L.const("SEG_MAX_GROUPS")
 
 
 def seg_groups_rescaled(soft_attn, images, n_blocks, G, groups):
@@ -2889,11 +2890,11 @@ def seg_blend(table, n_blocks, maps, palette, opacity, out, skip_zero=False, rev
 
 
 # ---------------------------------------------------------------- pixel-adaptive refinement of label maps (segment_refine.inc)
-SEG_REFINE_TILE = 256        # pixels of one workgroup of segclip_seg_refine
-SEG_REFINE_COLS = 8          # int64 columns of one row of its image table
-SEG_REFINE_MAX_DILATIONS = 6
-SEG_REFINE_MAX_DILATION = 32
-SEG_REFINE_MAX_ITERS = 32
+SEG_REFINE_TILE = L.const("SEG_REFINE_TILE")  # pixels of one workgroup of segclip_seg_refine
+SEG_REFINE_COLS = L.const("SEG_REFINE_COLS")  # int64 columns of one row of its image table
+SEG_REFINE_MAX_DILATIONS = L.const("SEG_REFINE_MAX_DILATIONS")
+SEG_REFINE_MAX_DILATION = L.const("SEG_REFINE_MAX_DILATION")
+SEG_REFINE_MAX_ITERS = L.const("SEG_REFINE_MAX_ITERS")
 
 
 def seg_refine_table(raws, label_offsets):
@@ -2948,9 +2949,9 @@ def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv
 
 
 # ---------------------------------------------------------------- connected components of label maps (segment_objects.inc)
-SEG_CC_TILE = (16, 64)       # (TH, TW): rows x columns of one workgroup's tile of segclip_seg_components
-SEG_CC_COLS = 8              # int64 columns of one row of its image table
-SEG_CC_RECORD = 10           # int64 columns of a record: image, id, label, area, y0, x0, y1, x1, sum of y, sum of x
+SEG_CC_TILE = (L.const("SEG_CC_TILE_H"), L.const("SEG_CC_TILE_W"))  # (TH, TW): rows x columns of one workgroup's tile of segclip_seg_components
+SEG_CC_COLS = L.const("SEG_CC_COLS")  # int64 columns of one row of its image table
+SEG_CC_RECORD = L.const("SEG_CC_RECORD")  # int64 columns of a record: image, id, label, area, y0, x0, y1, x1, sum of y, sum of x
 
 
 def seg_components_table(sizes, offsets, device):
@@ -3004,7 +3005,7 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
         cleaned.numel() if cleaned is not None else 0, L.ptr(ws), ws_bytes, L.stream()), "seg_components")
 
 
-SEG_SIEVE_MAX_ROUNDS = 8
+SEG_SIEVE_MAX_ROUNDS = L.const("SEG_SIEVE_MAX_ROUNDS")
 
 
 def seg_sieve(table, n_blocks, labels, connectivity=8, skip_label=None, min_area=0, orphan_fill=None, rounds=1, cleaned=None,
@@ -3037,10 +3038,11 @@ def seg_sieve(table, n_blocks, labels, connectivity=8, skip_label=None, min_area
 
 
 # ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
-SEG_BOUNDARY_TILE = (32, 64)     # (rows, columns) of one wave's strip of segclip_seg_boundary; 64 is also its rows pass's chunk
-SEG_BOUNDARY_WAVES = 4           # consecutive strips of a map that share a workgroup
-SEG_BOUNDARY_COLS = 8            # int64 columns of one row of its image table
-SEG_BOUNDARY_MAX_RADIUS = 128
+# (rows, columns) of one wave's strip of segclip_seg_boundary; the columns are also its rows pass's chunk
+SEG_BOUNDARY_TILE = (L.const("SEG_BOUNDARY_TILE_H"), L.const("SEG_BOUNDARY_TILE_W"))
+SEG_BOUNDARY_WAVES = L.const("SEG_BOUNDARY_WAVES")  # consecutive strips of a map that share a workgroup
+SEG_BOUNDARY_COLS = L.const("SEG_BOUNDARY_COLS")  # int64 columns of one row of its image table
+SEG_BOUNDARY_MAX_RADIUS = L.const("SEG_BOUNDARY_MAX_RADIUS")
 
 
 def seg_boundary_table(sizes, pred_offsets, gt_offsets, radii, device):
@@ -3109,7 +3111,7 @@ def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255
 
 
 # ---------------------------------------------------------------- image-text retrieval evaluation (retrieval.hip)
-RETRIEVAL_BAD_INDEX = 1  # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
+RETRIEVAL_BAD_INDEX = L.const("RETRIEVAL_BAD_INDEX")  # status bit of segclip_retrieval_thresholds: an image index outside [0, Ni)
 
 
 def _retrieval_inputs(what, visual, sequence, image_index):
@@ -3197,10 +3199,10 @@ def retrieval_topk(queries, gallery, k, splits=0):
 
 
 # ---------------------------------------------------------------- front end of training (train_frontend.inc)
-TRAIN_SOURCE_COLS = 13    # int64 columns of one row of the source table of segclip_train_images_from_u8
-TRAIN_MAP_COLS = 9        # int64 columns of one row of the map table of segclip_train_patch_labels
-TRAIN_MAX_SCALE = 8       # crop side / resized side, per axis (33 filter taps)
-TRAIN_MAX_OUT_W = 256
+TRAIN_SOURCE_COLS = L.const("TRAIN_SOURCE_COLS")  # int64 columns of one row of the source table of segclip_train_images_from_u8
+TRAIN_MAP_COLS = L.const("TRAIN_MAP_COLS")  # int64 columns of one row of the map table of segclip_train_patch_labels
+TRAIN_MAX_SCALE = L.const("TRAIN_MAX_SCALE")  # crop side / resized side, per axis (33 filter taps)
+TRAIN_MAX_OUT_W = L.const("TRAIN_MAX_OUT_W")
 
 
 def train_source_table(raws, geometry, out_size):

@@ -198,12 +198,13 @@ class TrainTail:
         loss = loss.detach()
         if loss.dtype != torch.float32:
             loss = loss.float()
+        ctrl = L.struct_ptr(self.ctrl, L.TrainCtrl)
         L.check(lib.segclip_grad_sqnorm(C.cast(ptrs, C.c_void_p), C.cast(sizes, C.c_void_p), n, L.ptr(self._ws),
-                                        L.ptr(self.ctrl), self.clip_grad, L.stream()), "grad_sqnorm")
+                                        ctrl, self.clip_grad, L.stream()), "grad_sqnorm")
         self.optimizer.step(loss=loss, ctrl=self.ctrl)
         m = _unwrap(self.model)
         ls = m.clip.logit_scale if hasattr(m, "clip") else None
-        L.check(lib.segclip_train_step_finish(L.ptr(self.ctrl), L.ptr(loss), L.ptr(ls.data) if ls is not None else None,
+        L.check(lib.segclip_train_step_finish(ctrl, L.ptr(loss), L.ptr(ls.data) if ls is not None else None,
                                               LN100, L.stream()), "train_step_finish")
         self.optimizer.zero_grad(set_to_none=True)
 

@@ -1,5 +1,6 @@
 """Shared test utilities (oracle-side parameter dicts, golden loading)."""
 import os
+import re
 
 import numpy as np
 import torch
@@ -9,6 +10,15 @@ from segclip_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FULL_FLAGS = dict(use_seglabel=True, use_vision_mae_recon=True)
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "segclip_hip.h")
+
+
+def header_declaration(name):
+    """The parameters of the entry `name` as include/segclip_hip.h words them: ["const uint8_t* pred", "int64_t n", ...].  For
+    tests that pin the header's text; that the binding agrees with the header is the business of tests/test_abi.py alone."""
+    m = re.search(r"^\w[\w* ]*\b" + name + r"\s*\(([^;]*)\)\s*;", open(HEADER).read(), re.M)
+    assert m, f"{name} is not declared in include/segclip_hip.h"
+    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def _beyond(got, ref, rtol):

@@ -1,8 +1,11 @@
-"""CPU: the C-ABI library loads and exports every symbol include/segclip_hip.h declares; the module
+"""CPU: the C-ABI library loads and exports every symbol include/segclip_hip.h declares; what _lib reads from that header
+(every entry's types, every struct's layout, every constant) is what a C++ compiler reads from it; the module
 mirror exposes the reference's state-dict keys; the product path refuses to run without a GPU."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -38,7 +41,70 @@ def test_library_loads_and_reports_version():
     assert lib.segclip_last_error_string() is not None
 
 
-def test_struct_layout_matches_header():
+_PROBE_HEAD = """
+#include "segclip_hip.h"
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+// one letter per type as it crosses the ABI: pointer, 32-bit int, 64-bit int, size_t, float, double
+template <class T> constexpr char kind() {
+  using U = std::remove_all_extents_t<T>;
+  return std::is_pointer_v<U> ? 'p' : std::is_same_v<U, float> ? 'f' : std::is_same_v<U, double> ? 'd' : std::is_same_v<U, size_t> ? 'z'
+       : std::is_integral_v<U> && std::is_signed_v<U> && sizeof(U) == 4 ? 'i'
+       : std::is_integral_v<U> && std::is_signed_v<U> && sizeof(U) == 8 ? 'l' : '?';
+}
+template <class R, class... A> void entry(const char* name, R (*)(A...)) {
+  std::printf("%s %c(", name, kind<R>());
+  (std::putchar(kind<A>()), ...);
+  std::printf(")\\n");
+}
+#define ENTRY(f) entry(#f, (decltype(&f))nullptr);   /* the symbol is never referenced: nothing links against the library */
+#define STRUCT(s) std::printf("%s %zu\\n", #s, sizeof(s));
+#define FIELD(s, f) std::printf("%s.%s %zu %zu %c\\n", #s, #f, offsetof(s, f), sizeof(s::f), kind<decltype(s::f)>());
+#define CONSTANT(c) std::printf("%s %lld\\n", #c, (long long)(c));
+int main() {
+"""
+
+
+def _kind(t):
+    t = getattr(t, "_type_", t) if issubclass(t, ctypes.Array) else t
+    if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)):
+        return "p"
+    return {ctypes.c_int: "i", ctypes.c_int64: "l", ctypes.c_size_t: "z", ctypes.c_float: "f", ctypes.c_double: "d"}[t]
+
+
+def test_struct_layout_matches_header(tmp_path):
+    """Everything _lib derives from the header against what a C++ compiler makes of the same header: the result and parameter
+    types of EVERY entry, size, and offset / size / type of every field of every struct, and the value of every constant.  The
+    probe includes the header alone and references no symbol; it needs a host compiler, no hipcc and no GPU."""
+    cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "the ABI test needs a host C++ compiler (c++, g++ or clang++, or $CXX)"
+    body, want = [], []
+    for name, (res, args) in _lib.SIGNATURES.items():
+        body.append(f"ENTRY({name})")
+        want.append(f"{name} {_kind(res)}({''.join(map(_kind, args))})")
+    for typedef, pyname in _lib.STRUCT_NAMES.items():
+        cls = getattr(_lib, pyname)
+        body.append(f"STRUCT({typedef})")
+        want.append(f"{typedef} {ctypes.sizeof(cls)}")
+        for field, t in cls._fields_:
+            body.append(f"FIELD({typedef}, {field})")
+            want.append(f"{typedef}.{field} {getattr(cls, field).offset} {getattr(cls, field).size} {_kind(t)}")
+    for name, value in _lib.CONSTANTS.items():
+        body.append(f"CONSTANT({name})")
+        want.append(f"{name} {value}")
+    assert len(_lib.SIGNATURES) >= 100 and len(_lib.STRUCT_NAMES) == 10
+    src = tmp_path / "abi_probe.cpp"
+    src.write_text(_PROBE_HEAD + "\n".join(body) + "\nreturn 0;\n}\n")
+    exe = tmp_path / "abi_probe"
+    subprocess.run([cxx, "-std=c++17", "-O0", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(got) == len(want)
+    wrong = [f"ctypes: {w!r}  compiler: {g!r}" for w, g in zip(want, got) if w != g]
+    assert not wrong, "\n".join(wrong)
+
+
+def test_gemm_rejects_a_bf16_operand_without_unit_stride():
     _ensure_built()
     lib = _lib.load()
     # a descriptor with a bf16 operand that has no unit stride must be rejected host-side (no launch)

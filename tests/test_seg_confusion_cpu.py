@@ -3,7 +3,6 @@ entries of the C ABI and their binding, and the static helpers of SegEvaluator o
 tests/confusion_reference.py: integers exactly, fp64 figures within 1e-12 relative (the same integers go through the same
 formulae; only the order of operations can differ)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,33 +12,22 @@ from segclip_amd import _lib as L
 from segclip_amd import ops
 from segclip_amd.segmentation import SegEvaluator
 from tests import confusion_reference as cr
+from tests.helpers import header_declaration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL = 1e-12
 
 
-def _declaration(hdr, name):
-    m = re.search(r"\bint " + name + r"\(([^;]*)\);", hdr)
-    assert m, f"{name} is not declared in include/segclip_hip.h"
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_header_declares_the_entries_and_lib_binds_them():
-    hdr = open(os.path.join(ROOT, "include", "segclip_hip.h")).read()
-    narrow = _declaration(hdr, "segclip_seg_confusion")
+    narrow = header_declaration("segclip_seg_confusion")
     assert narrow == ["const uint8_t* pred", "const uint8_t* gt", "int64_t n", "int64_t C", "int ignore_index",
                       "int reduce_zero_label", "int64_t* conf", "void* stream"]
-    wide = _declaration(hdr, "segclip_seg_confusion_wide")
+    wide = header_declaration("segclip_seg_confusion_wide")
     assert wide == ["const uint16_t* pred", "const uint16_t* gt"] + narrow[2:]
-    assert narrow[:6] == _declaration(hdr, "segclip_seg_areas")[:6]
-    route = _declaration(hdr, "segclip_seg_confusion_route")
+    assert narrow[:6] == header_declaration("segclip_seg_areas")[:6]
+    route = header_declaration("segclip_seg_confusion_route")
     assert route == ["int64_t C", "int wide"]
-    for name, args in (("segclip_seg_confusion", narrow), ("segclip_seg_confusion_wide", wide), ("segclip_seg_confusion_route", route)):
-        res, argtypes = L.SIGNATURES[name]
-        assert res is L.C.c_int and len(argtypes) == len(args)
-        for text, ctype in zip(args, argtypes):
-            want = L.vp if "*" in text else L.i64 if text.startswith("int64_t") else L.C.c_int
-            assert ctype is want, (name, text, ctype)
+    assert {"segclip_seg_confusion", "segclip_seg_confusion_wide", "segclip_seg_confusion_route"} <= set(L.SIGNATURES)   # types: test_abi.py
     assert os.path.exists(os.path.join(ROOT, "segclip_amd", "csrc", "segment_confusion.inc"))
 
 

@@ -6,11 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-from segclip_amd import _lib, ops
+from segclip_amd import ops
 from segclip_amd.segmentation import Despeckle, despeckle
 from tests import cc_merge_reference as cm
 from tests import cc_reference as cc
-from tests.test_seg_objects_cpu import _prototype
+from tests.helpers import header_declaration
 
 TH, TW = ops.SEG_CC_TILE
 
@@ -203,14 +203,7 @@ def test_despeckle_arguments():
 
 
 def test_header_and_ctypes_prototypes_agree():
-    import ctypes as C
-    kinds = {"int64_t": C.c_int64, "int": C.c_int}
-    for name in ("segclip_seg_sieve_ws_bytes", "segclip_seg_sieve"):
-        ret, args = _prototype(name)
-        want = [C.c_void_p if "*" in a else kinds[a.rsplit(" ", 1)[0]] for a in args]
-        got_ret, got = _lib.SIGNATURES[name]
-        assert got_ret is kinds[ret] and list(got) == want, name
-    _, args = _prototype("segclip_seg_sieve")
+    args = header_declaration("segclip_seg_sieve")
     assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
         "images", "B", "n_blocks", "max_side", "labels", "labels_bytes", "connectivity", "skip_label", "min_area", "orphan_fill",
         "rounds", "cleaned", "cleaned_bytes", "ws", "ws_bytes", "stream"]

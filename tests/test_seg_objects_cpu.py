@@ -1,20 +1,17 @@
 """The restatement of the connected components (tests/cc_reference.py) checked on its own, without a GPU: against
 scipy.ndimage where it is installed, the properties of the definition that the kernel tests then lean on, the host-side
-refusals that need no device, and the agreement of the header's prototypes with the ctypes signatures."""
-import os
-import re
-
+refusals that need no device, and the parameter list of the entry in the header (tests/test_abi.py holds the binding to it)."""
 import numpy as np
 import pytest
 import torch
 
-from segclip_amd import _lib, ops
+from segclip_amd import ops
 from tests import cc_reference as cc
+from tests.helpers import header_declaration
 
 TH, TW = ops.SEG_CC_TILE
 CASES = cc.cases(TH, TW)
 RANDOM = ["noise_3_labels", "blocks_21_labels", "bytes_0_7_255", "mixed_batch", "tall_noise", "1x9", "7x1"]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_tile_and_cases():
@@ -137,23 +134,8 @@ def test_host_side_refusals():
         ops.seg_components(table, n_blocks, torch.zeros(9001, dtype=torch.uint8))
 
 
-def _prototype(name):
-    hdr = open(os.path.join(ROOT, "include", "segclip_hip.h")).read()
-    m = re.search(r"\n(\w+)\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, name
-    args = [" ".join(a.split()) for a in m.group(2).split(",")]
-    return m.group(1), args
-
-
 def test_header_and_ctypes_prototypes_agree():
-    import ctypes as C
-    kinds = {"int64_t": C.c_int64, "int": C.c_int}
-    for name in ("segclip_seg_components_ws_bytes", "segclip_seg_components"):
-        ret, args = _prototype(name)
-        want = [C.c_void_p if "*" in a else kinds[a.rsplit(" ", 1)[0]] for a in args]
-        got_ret, got = _lib.SIGNATURES[name]
-        assert got_ret is kinds[ret] and list(got) == want, name
-    _, args = _prototype("segclip_seg_components")
+    args = header_declaration("segclip_seg_components")
     assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
         "images", "B", "n_blocks", "max_side", "labels", "labels_bytes", "connectivity", "skip_label", "ids", "area_px", "px_count",
         "records", "K", "count", "min_area", "fill", "cleaned", "cleaned_bytes", "ws", "ws_bytes", "stream"]

@@ -13,6 +13,7 @@ import functools
 import pytest
 import torch
 
+from segclip_amd import _lib as L
 from segclip_amd import ops
 from tests import seg_wide_cases as swc
 
@@ -22,7 +23,7 @@ G, N, C, NET, GRID = 8, 5, 6, (32, 32), (2, 2)
 THR, SWEEP_THR = 0.5, (0.3, 0.5, 0.7)
 SENT = {torch.uint8: 0xA5, torch.int16: -23131}   # 0xA5A5 as int16
 ENTRIES = ("rescaled", "wide", "sweep")
-SI_OH, SI_LAB, SI_GT, SI_SOFT = 4, 6, 7, 13       # columns of the image table (include/segclip_hip.h)
+SI_OH, SI_LAB, SI_GT, SI_SOFT = (L.const("SI_" + c) for c in ("OH", "LAB", "GT", "SOFT"))   # columns of the image table
 
 
 @functools.lru_cache(maxsize=None)

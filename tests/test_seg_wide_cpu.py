@@ -2,7 +2,6 @@
 the reference counts of the synthetic cases of tests/seg_wide_cases.py, the two new symbols of the C ABI and their binding,
 and the argument validation of the host layer."""
 import os
-import re
 import types
 
 import pytest
@@ -12,6 +11,7 @@ from segclip_amd import _lib as L
 from segclip_amd import ops
 from segclip_amd.segmentation import Boundary, SegEvaluator, SegInference, SegSweepEvaluator, _Maps
 from tests import seg_wide_cases as swc
+from tests.helpers import HEADER, header_declaration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -54,32 +54,19 @@ def test_i16_round_trip():
     assert int(swc.to_i16(torch.tensor([65535]))) == -1
 
 
-def _declaration(hdr, name):
-    m = re.search(r"\bint " + name + r"\(([^;]*)\);", hdr)
-    assert m, f"{name} is not declared in include/segclip_hip.h"
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_header_declares_the_wide_entries_and_lib_binds_them():
-    hdr = open(os.path.join(ROOT, "include", "segclip_hip.h")).read()
-    wide = _declaration(hdr, "segclip_seg_label_map_rescaled_wide")
-    narrow = _declaration(hdr, "segclip_seg_label_map_rescaled")
+    wide = header_declaration("segclip_seg_label_map_rescaled_wide")
+    narrow = header_declaration("segclip_seg_label_map_rescaled")
     assert len(wide) == len(narrow) == 24
     changed = [(a, b) for a, b in zip(narrow, wide) if a != b]
     assert changed == [("uint8_t* labels", "uint16_t* labels"), ("int64_t labels_bytes", "int64_t labels_elems"),
                        ("const uint8_t* gt", "const uint16_t* gt"), ("int64_t gt_bytes", "int64_t gt_elems")]
-    areas = _declaration(hdr, "segclip_seg_areas_wide")
-    assert areas[:2] == ["const uint16_t* pred", "const uint16_t* gt"] and len(areas) == len(_declaration(hdr, "segclip_seg_areas")) == 8
-    for name, args in (("segclip_seg_label_map_rescaled_wide", wide), ("segclip_seg_areas_wide", areas)):
-        res, argtypes = L.SIGNATURES[name]
-        assert res is L.C.c_int and len(argtypes) == len(args)
-        for text, ctype in zip(args, argtypes):   # pointers as void*, int64_t as c_int64, int as c_int, float as c_float
-            want = L.vp if "*" in text else L.i64 if text.startswith("int64_t") else L.f32 if text.startswith("float") else L.C.c_int
-            assert ctype is want, (name, text, ctype)
+    areas = header_declaration("segclip_seg_areas_wide")
+    assert areas[:2] == ["const uint16_t* pred", "const uint16_t* gt"] and len(areas) == len(header_declaration("segclip_seg_areas")) == 8
     assert L.SIGNATURES["segclip_seg_label_map_rescaled_wide"] == L.SIGNATURES["segclip_seg_label_map_rescaled"]
     assert ops.SEG_WIDE_MAX_CLASSES == 1024
     inc = open(os.path.join(ROOT, "segclip_amd", "csrc", "segment_wide.inc")).read()
-    assert "SEG_WIDE_MAX_CLASSES 1024" in inc
+    assert "#define SEGCLIP_SEG_WIDE_MAX_CLASSES 1024 " in open(HEADER).read() and "SEG_WIDE_MAX_CLASSES SEGCLIP_SEG_WIDE_MAX_CLASSES" in inc
     assert "SEG_WIDE_LANE_SCAN_CLASSES 32" in inc   # what the cases w21_small and w61_staged are placed around
 
 

@@ -82,16 +82,13 @@ def test_optimizer_abi_host_contract():
     assert lib.segclip_grad_sqnorm_ws_bytes(ctypes.cast(sizes, ctypes.c_void_p), 4) == 4 * 4
     groups = (_lib.AdamWGroup * 17)()
     tens = (_lib.AdamWTensor * 1)()
-    rc = lib.segclip_adamw_step(ctypes.cast(tens, ctypes.c_void_p), 1, ctypes.cast(groups, ctypes.c_void_p), 17,
-                                None, None, 0, None)
+    rc = lib.segclip_adamw_step(tens, 1, groups, 17, None, None, 0, None)
     assert rc == -1 and b"16 param groups" in lib.segclip_last_error_string()
     groups[0].schedule = 7
-    rc = lib.segclip_adamw_step(ctypes.cast(tens, ctypes.c_void_p), 1, ctypes.cast(groups, ctypes.c_void_p), 1,
-                                None, None, 0, None)
+    rc = lib.segclip_adamw_step(tens, 1, groups, 1, None, None, 0, None)
     assert rc == -1 and b"schedule" in lib.segclip_last_error_string()
     groups[0].schedule, groups[0].b1, groups[0].b2, groups[0].lr = 0, 0.9, 0.98, 1e-3
     tens[0].n, tens[0].param = 8, 16  # null grad / state pointers -> rejected before any launch
-    rc = lib.segclip_adamw_step(ctypes.cast(tens, ctypes.c_void_p), 1, ctypes.cast(groups, ctypes.c_void_p), 1,
-                                None, None, 0, None)
+    rc = lib.segclip_adamw_step(tens, 1, groups, 1, None, None, 0, None)
     assert rc == -1 and b"null pointer" in lib.segclip_last_error_string()
     assert lib.segclip_train_step_finish(None, None, None, 0.0, None) == -1
