@@ -18,59 +18,63 @@
 #include <atomic>
 
 #include "common.h"
+#include "attention_tile_image.h"
+#include "lds_ops.h"
 
 int segclip_gemm_f32_launch(const segclip_gemm_desc* d, hipStream_t stream);
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+constexpr int ROWB = tileimg::ROWB;  // bytes per LDS row (64 bf16)
 
-constexpr int ROWB = 128;  // bytes per LDS row (64 bf16)
-
-// swizzled byte offset of element (row, col) in a [rows][64] bf16 LDS tile.
-// f = rotr3((row>>1)&7): ds_read_b128 of 16 rows is conflict-free, and the 4-row tr16 reads of a
-// 32-lane half land in disjoint banks.
-__device__ __forceinline__ int swz(int row, int col) {
-  const int t = (row >> 1) & 7;
-  const int f = ((t & 1) << 2) | (t >> 1);
-  return row * ROWB + ((((col >> 3) ^ f)) << 4) + ((col & 7) << 1);
-}
+using tileimg::swz;   // byte offset of element (row, col) in a [rows][64] bf16 LDS tile: the row image
 
 // MFMA operand fragment, k-contiguous rows: lane l -> row rbase + (l&31), cols kc*16 + 8*(l>>5) .. +7
 __device__ __forceinline__ bf16x8_t frag_rows(const char* t, int rbase, int kc, int lane) {
-  return *reinterpret_cast<const bf16x8_t*>(t + swz(rbase + (lane & 31), kc * 16 + 8 * (lane >> 5)));
+  return *reinterpret_cast<const bf16x8_t*>(t + tileimg::frag_rows_at(rbase, kc, lane));
 }
 // MFMA operand fragment of the TRANSPOSED tile: lane l -> "row" = column cbase + (l&31) of the tile,
 // k = tile rows  rbase + 4*(l>>5) + {0,1,2,3, 8,9,10,11}   (the key order of the 32x32 accumulator)
 __device__ __forceinline__ bf16x8_t frag_tr(const char* t, int rbase, int cbase, int lane) {
-  const int g4 = lane >> 4, q = lane & 15;
-  const int row = rbase + 4 * (g4 >> 1) + (q >> 2);
-  const int col = cbase + 16 * (g4 & 1) + 4 * (q & 3);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + swz(row, col)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + swz(row + 8, col)));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
+  const int row = tileimg::frag_tr_row(rbase, lane), col = tileimg::frag_tr_col(cbase, lane);
+  const s16x4 lo = tr16_read(t + swz(row, col));
+  const s16x4 hi = tr16_read(t + swz(tileimg::frag_tr_hi(row), col));
+  return tr16_join(lo, hi);
 }
 typedef float v2f __attribute__((ext_vector_type(2)));
-// the same fragment from precomputed lane offsets (rows r0 .. r0+3 and r0+8 .. r0+11 of a 16-row group)
-__device__ __forceinline__ bf16x8_t frag_tr_at(const char* t, int off_lo, int off_hi) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + off_lo));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + off_hi));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
+// Lane offsets of the transposed fragments of a tile's first 16 rows, kept in registers by the kernels (voff / toff):
+// tileimg::frag_tr_at(0, 32 dt, lane, j).  A call of that function changes the emitted code of every kernel, so the arithmetic
+// is spelled out here, once, and the static_assert holds it to the header.  attention_pf.inc and attention_dqw.inc need the very
+// statements of the macro in their kernel bodies (even tr_lane_off changes their code).
+#define TR_LANE_OFF(g4, q, dt, j) swz(4 * ((g4) >> 1) + ((q) >> 2) + 8 * (j), (dt) * 32 + 16 * ((g4) & 1) + 4 * ((q) & 3))
+OPIMG_FN int tr_lane_off(int lane, int dt, int j) {
+  const int g4 = lane >> 4, q = lane & 15;
+  return TR_LANE_OFF(g4, q, dt, j);
 }
+constexpr bool tr_lane_off_follows_image() {
+  for (int lane = 0; lane < 64; ++lane)
+    for (int dt = 0; dt < 2; ++dt)
+      for (int j = 0; j < 2; ++j)
+        if (tr_lane_off(lane, dt, j) != tileimg::frag_tr_at(0, dt * 32, lane, j)) return false;
+  return true;
+}
+static_assert(tr_lane_off_follows_image(), "attention: TR_LANE_OFF must be the lane offset of tileimg::frag_tr_at");
+// f(r) of the row image (tileimg::row_xor) as one expression, for the loader lambdas of attention_dma_tile.inc: with any call in
+// them hipcc emits other code for both kernels that include them
+#define ROW_XOR(r) ((((((r) >> 1) & 7) & 1) << 2) | ((((r) >> 1) & 7) >> 1))
+constexpr bool row_xor_follows_image() {
+  for (int r = 0; r < 256; ++r)
+    if (ROW_XOR(r) != tileimg::row_xor(r)) return false;
+  return true;
+}
+static_assert(row_xor_follows_image(), "attention: ROW_XOR must be tileimg::row_xor");
 __device__ __forceinline__ bf16x8_t pack8(const float* p) {
   u32x4 r;
 #pragma unroll
   for (int j = 0; j < 4; ++j) r[j] = pack2bf(p[2 * j], p[2 * j + 1]);
   return __builtin_bit_cast(bf16x8_t, r);
 }
-// accumulator row index of register r for half h (32x32 tile)
-__device__ __forceinline__ int accrow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+using tileimg::acc_row;   // accumulator row index of register r for lane half h (32x32 tile)
 
 // stage `nrows_pad` rows (zero-filled beyond nvalid / beyond hd) of X[row*st + d] into a swizzled tile.
 // Loads are unconditional from clamped addresses and issued in batches of 4 before any LDS write (a load
@@ -82,16 +86,16 @@ __device__ __forceinline__ void stage_rows(char* tile, const bf16_t* __restrict_
     u32x4 v[4];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      const int idx = base + it * nthreads + tid;
-      const int r = idx >> 3, c = idx & 7;
-      const int rc = r < nvalid ? r : nvalid - 1;
-      const int cc = c * 8 < hd ? c : 0;
+      const int idx = tileimg::stage_index(base, it, nthreads, tid);
+      const int r = tileimg::stage_row(idx), c = tileimg::stage_chunk(idx);
+      const int rc = tileimg::clamp_row(r, nvalid);
+      const int cc = c * 8 < hd ? c : 0;   // tileimg::clamp_chunk; as a call it changes the code of every kernel that stages rows
       v[it] = *reinterpret_cast<const u32x4*>(X + (int64_t)(row0 + rc) * st + cc * 8);
     }
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      const int idx = base + it * nthreads + tid;
-      const int r = idx >> 3, c = idx & 7;
+      const int idx = tileimg::stage_index(base, it, nthreads, tid);
+      const int r = tileimg::stage_row(idx), c = tileimg::stage_chunk(idx);
       if (idx < total) {
         const bool ok = r < nvalid && c * 8 < hd;
         *reinterpret_cast<u32x4*>(tile + swz(r, c * 8)) = ok ? v[it] : u32x4{0u, 0u, 0u, 0u};
@@ -147,14 +151,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // the swizzle only looks at bits 1-3 of the row)
   int koff[4], voff[2][2];
 #pragma unroll
-  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, kc * 16 + 8 * lh);
-  {
-    const int g4 = lane >> 4, q = lane & 15;
+  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, tileimg::frag_rows_col(kc, lh));
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+  for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) voff[dt][j] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * j, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
-  }
+    for (int j = 0; j < 2; ++j) voff[dt][j] = tr_lane_off(lane, dt, j);
 
   for (int c0 = 0; c0 < a.Tk; c0 += KCHUNK) {
     const int nvalid = a.Tk - c0 < KCHUNK ? a.Tk - c0 : KCHUNK;
@@ -213,8 +214,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(vb, voff[dt][0], voff[dt][1]), __builtin_bit_cast(bf16x8_t, pk[0]), o[dt], 0, 0, 0);
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(vb + 16 * ROWB, voff[dt][0], voff[dt][1]), __builtin_bit_cast(bf16x8_t, pk[1]), o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(vb, voff[dt][0], voff[dt][1]), __builtin_bit_cast(bf16x8_t, pk[0]), o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(vb + 16 * ROWB, voff[dt][0], voff[dt][1]), __builtin_bit_cast(bf16x8_t, pk[1]), o[dt], 0, 0, 0);
         }
         kt += 32;
         continue;
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       if (edge) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = c0 + kt + accrow(r, lh);
+          const int key = c0 + kt + acc_row(r, lh);
           const bool ok = key < kvalid && (!a.causal || key <= qg);
           p[r] = ok ? s[r] * sc2 : -INFINITY;
           mx = fmaxf(mx, p[r]);
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         u32x2 t;
         t[0] = pack2bf(o[dt][rg * 4 + 0] * inv, o[dt][rg * 4 + 1] * inv);
         t[1] = pack2bf(o[dt][rg * 4 + 2] * inv, o[dt][rg * 4 + 3] * inv);
-        *reinterpret_cast<u32x2*>(ot + swz(li, dt * 32 + 8 * rg + 4 * lh)) = t;
+        *reinterpret_cast<u32x2*>(ot + swz(li, tileimg::park_col(dt, rg, lh))) = t;
       }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -299,7 +300,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
-      const int d = dt * 32 + 8 * rg + 4 * lh;
+      const int d = tileimg::park_col(dt, rg, lh);
       if (d < a.hd) {
         u32x2 t;
         t[0] = pack2bf(o[dt][rg * 4 + 0] * inv, o[dt][rg * 4 + 1] * inv);
@@ -349,7 +350,7 @@ __device__ __forceinline__ void store_acc_T(bf16_t* base, int64_t st, int row, i
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
-      const int d = dt * 32 + 8 * rg + 4 * lh;
+      const int d = tileimg::park_col(dt, rg, lh);
       if (d < hd) {
         u32x2 t;
         t[0] = pack2bf(acc[dt][rg * 4 + 0], acc[dt][rg * 4 + 1]);
@@ -554,7 +555,7 @@ __global__ __launch_bounds__(512) void attn_bwd_bf16_kernel(BwdArgs a) {
       if (edge) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = k0 + accrow(r, lh);
+          const int key = k0 + acc_row(r, lh);
           const bool ok = key < kvalid && q < a.Tq && (!a.causal || key <= q);
           ds[r] = ok ? __builtin_amdgcn_exp2f(s[r] * sc2 - lq) * (dp[r] - dq_) : 0.f;
         }

@@ -40,10 +40,6 @@ template <int NT> __host__ __device__ constexpr size_t bwd_dqw_lds_bytes() {
   return (size_t)2 * NT * 32 * ROWB + (size_t)DQW_NS * DQW_SLOT + (size_t)2 * NT * SP_SCR_BYTES + 4096 + 3 * 64 * 4 + 64;
 }
 
-// one 256-byte LDS-DMA piece: lane l -> 4 bytes from base + off to LDS byte address lds_dst + 4 l (see pf_dma16)
-__device__ __forceinline__ void dqw_dma4(const void* base_uniform, uint32_t off, uint32_t lds_dst) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds_dst) : "memory");
-}
 // stores of the dQ wave, from inline asm: hipcc must not see a vector-memory instruction in that wave (it would place its
 // own s_waitcnt vmcnt in front of register reuses and drain the tiles in flight); the software count below includes them.
 // (s_nop 1: a 16-byte store reads its data registers for two more cycles, a hazard hipcc only pads for its own stores.)
@@ -53,76 +49,6 @@ __device__ __forceinline__ void dqw_store16(void* base_uniform, uint32_t off, co
 __device__ __forceinline__ void dqw_store4(void* base_uniform, uint32_t off, const float v) {
   asm volatile("global_store_dword %0, %1, %2\n\ts_nop 0" : : "v"(off), "v"(v), "s"(base_uniform) : "memory");
 }
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
-__device__ __forceinline__ void dqw_wait_vm(uint32_t n) {
-  switch (n < 63u ? n : 63u) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-    case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-    case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-    case 23: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-    case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    case 25: asm volatile("s_waitcnt vmcnt(25)" ::: "memory"); break;
-    case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-    case 27: asm volatile("s_waitcnt vmcnt(27)" ::: "memory"); break;
-    case 28: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
-    case 29: asm volatile("s_waitcnt vmcnt(29)" ::: "memory"); break;
-    case 30: asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); break;
-    case 31: asm volatile("s_waitcnt vmcnt(31)" ::: "memory"); break;
-    case 32: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-    case 33: asm volatile("s_waitcnt vmcnt(33)" ::: "memory"); break;
-    case 34: asm volatile("s_waitcnt vmcnt(34)" ::: "memory"); break;
-    case 35: asm volatile("s_waitcnt vmcnt(35)" ::: "memory"); break;
-    case 36: asm volatile("s_waitcnt vmcnt(36)" ::: "memory"); break;
-    case 37: asm volatile("s_waitcnt vmcnt(37)" ::: "memory"); break;
-    case 38: asm volatile("s_waitcnt vmcnt(38)" ::: "memory"); break;
-    case 39: asm volatile("s_waitcnt vmcnt(39)" ::: "memory"); break;
-    case 40: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-    case 41: asm volatile("s_waitcnt vmcnt(41)" ::: "memory"); break;
-    case 42: asm volatile("s_waitcnt vmcnt(42)" ::: "memory"); break;
-    case 43: asm volatile("s_waitcnt vmcnt(43)" ::: "memory"); break;
-    case 44: asm volatile("s_waitcnt vmcnt(44)" ::: "memory"); break;
-    case 45: asm volatile("s_waitcnt vmcnt(45)" ::: "memory"); break;
-    case 46: asm volatile("s_waitcnt vmcnt(46)" ::: "memory"); break;
-    case 47: asm volatile("s_waitcnt vmcnt(47)" ::: "memory"); break;
-    case 48: asm volatile("s_waitcnt vmcnt(48)" ::: "memory"); break;
-    case 49: asm volatile("s_waitcnt vmcnt(49)" ::: "memory"); break;
-    case 50: asm volatile("s_waitcnt vmcnt(50)" ::: "memory"); break;
-    case 51: asm volatile("s_waitcnt vmcnt(51)" ::: "memory"); break;
-    case 52: asm volatile("s_waitcnt vmcnt(52)" ::: "memory"); break;
-    case 53: asm volatile("s_waitcnt vmcnt(53)" ::: "memory"); break;
-    case 54: asm volatile("s_waitcnt vmcnt(54)" ::: "memory"); break;
-    case 55: asm volatile("s_waitcnt vmcnt(55)" ::: "memory"); break;
-    case 56: asm volatile("s_waitcnt vmcnt(56)" ::: "memory"); break;
-    case 57: asm volatile("s_waitcnt vmcnt(57)" ::: "memory"); break;
-    case 58: asm volatile("s_waitcnt vmcnt(58)" ::: "memory"); break;
-    case 59: asm volatile("s_waitcnt vmcnt(59)" ::: "memory"); break;
-    case 60: asm volatile("s_waitcnt vmcnt(60)" ::: "memory"); break;
-    case 61: asm volatile("s_waitcnt vmcnt(61)" ::: "memory"); break;
-    case 62: asm volatile("s_waitcnt vmcnt(62)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-  }
-}
-
 // MULTI (sequences of more than NT * 32 tokens; ViT-L/14@336: 577): the work unit is (item, CHUNK of NT * 32 keys).  The key-owners hold
 // the chunk's K / V fragments and stream ALL NQ = ceil(T / 32) query tiles past them (Q, dO, O are re-streamed once per chunk:
 // NC x the reads, still ~1/10 of a CU's load rate); dK / dV of the chunk are final at the end of the unit and leave as for an
@@ -153,7 +79,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
   char* Scr = Ring + DQW_NS * DQW_SLOT;                      // [2][NT][2 KB] dS^T tiles
   char* Pat = Scr + 2 * NT * SP_SCR_BYTES;                   // dQ tile on its way out
   float* Red = reinterpret_cast<float*>(Pat + 4096);         // [3][64]: columns T, T+1 of the last dQ^T tile; token sums of dO
-  const uint32_t lds0 = (uint32_t)(uintptr_t)((pf_lds_void*)smem_bwd);
+  const uint32_t lds0 = (uint32_t)(uintptr_t)((lds_void*)smem_bwd);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nitems = a.nitems;
   const int nloc = ((int)blockIdx.x < nitems) ? (nitems - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;   // items of this workgroup
@@ -212,9 +138,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
     // every vector-memory instruction of a key-owner costs ~600 cycles of STEP time - its issue stalls the wave in the middle of its
     // dependent chain - while this wave idles for two thirds of a step and pays ~100-150 cycles per instruction of a batch.)
     auto ring_src = [&](int r, uint32_t st) {                // source chunk of (row r, LDS chunk lane & 7): the tiles' swizzle
-      const int t = (r >> 1) & 7, f = ((t & 1) << 2) | (t >> 1);
-      const int rc = r < T ? r : T - 1;
-      return (uint32_t)(((uint32_t)rc * st + (uint32_t)((co ^ f) * 8)) * 2u);
+      return (uint32_t)(((uint32_t)tileimg::clamp_row(r, T) * st + (uint32_t)(tileimg::piece_chunk(r, co) * 8)) * 2u);
     };
     auto issue_tile = [&](int t, int unC) {                  // unC: the unit (ib, ih) belongs to
       const bool nx = t >= (unC + 1) * NQ;                   // (tile t belongs to the current or to the next unit)
@@ -226,10 +150,10 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         const bf16_t* base = (kind == 0 ? aQ + b * q_sb : (kind == 1 ? aG + b * g_sb : aO + b * o_sb)) + (int64_t)h * 64;
         const uint32_t st = (uint32_t)(kind == 0 ? q_st : (kind == 1 ? g_st : o_st));
 #pragma unroll
-        for (int u = 0; u < 4; ++u) pf_dma16(base, ring_src(j * 32 + u * 8 + lro, st), slot + (uint32_t)(kind * 4096 + u * 1024));
+        for (int u = 0; u < 4; ++u) dma16(base, ring_src(j * 32 + u * 8 + lro, st), slot + (uint32_t)(kind * 4096 + u * 1024));
       }
       const int q = j * 32 + lio;
-      dqw_dma4(aL + ((int64_t)b * aH + h) * T, (uint32_t)((q < T ? q : T - 1) * 4), slot + 12288);
+      dma4(aL + ((int64_t)b * aH + h) * T, (uint32_t)((q < T ? q : T - 1) * 4), slot + 12288);
       nvmq += 13;
     };
     auto set_next = [&](int un) {                            // (ibN, ihN) of unit un
@@ -245,7 +169,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) toff[dt][jj] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * jj, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
+        for (int jj = 0; jj < 2; ++jj) toff[dt][jj] = TR_LANE_OFF(g4, q, dt, jj);
     }
     auto load_ktr = [&](int kbase) {                         // kbase: first key of the chunk in KN
       int lhk = lane >> 5;
@@ -256,7 +180,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
-            u32x4 f = __builtin_bit_cast(u32x4, frag_tr_at(KN + (kw * 32 + hf * 16) * ROWB, toff[dt][0], toff[dt][1]));
+            u32x4 f = __builtin_bit_cast(u32x4, tr16_frag(KN + (kw * 32 + hf * 16) * ROWB, toff[dt][0], toff[dt][1]));
             if (MULTI || kw == NT - 1) {                     // keys beyond T (clamped duplicates / stale rows) count as zero rows
               const int kb = kbase + kw * 32 + hf * 16 + 4 * lhk;
 #pragma unroll
@@ -269,19 +193,8 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
           }
     };
     // lane offset of the dS^T fragments inside a 2-KB scratch tile (frag_tr64): rows r0, r0 + 8, r0 + 16, r0 + 24 are + 512 bytes each
-    int soff;
-    {
-      const int g4 = lane >> 4, q = lane & 15;
-      soff = swz64(4 * (g4 >> 1) + (q >> 2), 16 * (g4 & 1) + 4 * (q & 3));
-    }
-    auto sfrag = [&](const char* t, int r16) {
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + soff + r16 * 1024));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + soff + r16 * 1024 + 512));
-      s16x8 r;
-      r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-      r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-      return __builtin_bit_cast(bf16x8_t, r);
-    };
+    const int soff = tileimg::frag_tr64_at(0, lane, 0);
+    auto sfrag = [&](const char* t, int r16) { return tr16_frag(t + soff + r16 * 1024, 512); };
     // dQ^T of tile t: one product over all keys; the bf16 tile -> patch -> global as whole 128-byte rows
     auto product = [&](int t, int jt, int cch, int b, int h) {
       f32x16 dq[2];
@@ -326,14 +239,14 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
           u32x2 w;
           w[0] = pack2bf(dq[dt][rg * 4 + 0] * ascale, dq[dt][rg * 4 + 1] * ascale);
           w[1] = pack2bf(dq[dt][rg * 4 + 2] * ascale, dq[dt][rg * 4 + 3] * ascale);
-          *reinterpret_cast<u32x2*>(Pat + swz(li, dt * 32 + 8 * rg + 4 * lh)) = w;
+          *reinterpret_cast<u32x2*>(Pat + swz(li, tileimg::park_col(dt, rg, lh))) = w;
         }
       if (jt == NQ - 1 && (li == qp || li == qp + 1)) {      // columns T, T + 1: the two bf16 parts of sum_key K[key] cs[key]
         float* dst = Red + (li - qp) * 64;
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) dst[dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = dq[dt][r];
+          for (int r = 0; r < 16; ++r) dst[dt * 32 + acc_row(r, lh)] = dq[dt][r];
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
@@ -401,7 +314,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();                      // K
         }
-        if (RING_DQ) dqw_wait_vm(nvmq);                      // what this wave issued BEFORE this step has landed / left
+        if (RING_DQ) wait_vm(nvmq);                          // what this wave issued BEFORE this step has landed / left
       }
     }
     __builtin_amdgcn_s_barrier();                            // F: the last dS^T tiles are parked
@@ -452,9 +365,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
   if (nunits > 1) set_bh(1, bN, hN, cN);
   int ilC = 0;                                               // the local unit (bC, hC, cC) belongs to
   auto src_off = [&](int r, uint32_t st) {                   // source chunk of (row r, LDS chunk lane & 7): the tiles' swizzle
-    const int t = (r >> 1) & 7, f = ((t & 1) << 2) | (t >> 1);
-    const int rc = r < T ? r : T - 1;
-    return (uint32_t)(((uint32_t)rc * st + (uint32_t)((c ^ f) * 8)) * 2u);
+    return (uint32_t)(((uint32_t)tileimg::clamp_row(r, T) * st + (uint32_t)(tileimg::piece_chunk(r, c) * 8)) * 2u);
   };
   uint32_t nvm = 0;                                          // vector-memory instructions this wave issued in the current step
   // !RING_DQ: piece idx of tile t: 0-3 Q rows, 4-7 dO rows, 8-11 O rows (8 rows each), 12 lse
@@ -466,10 +377,10 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       const int kind = idx >> 2, u = idx & 3;
       const bf16_t* base = kind == 0 ? aQ + b * q_sb : (kind == 1 ? aG + b * g_sb : aO + b * o_sb);
       const uint32_t st = (uint32_t)(kind == 0 ? q_st : (kind == 1 ? g_st : o_st));
-      pf_dma16(base + (int64_t)h * 64, src_off(j * 32 + u * 8 + lr, st), slot + (uint32_t)(kind * 4096 + u * 1024));
+      dma16(base + (int64_t)h * 64, src_off(j * 32 + u * 8 + lr, st), slot + (uint32_t)(kind * 4096 + u * 1024));
     } else {
       const int q = j * 32 + lic;
-      dqw_dma4(aL + ((int64_t)b * aH + h) * T, (uint32_t)((q < T ? q : T - 1) * 4), slot + 12288);
+      dma4(aL + ((int64_t)b * aH + h) * T, (uint32_t)((q < T ? q : T - 1) * 4), slot + 12288);
     }
     ++nvm;
   };
@@ -484,7 +395,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
     const int kb = MULTI ? cch * TP + k0 : k0;               // first global key row of this wave
     for (int u = u0; u < u1; ++u)
       if (kb + u * 8 < R) {                                  // (wave-uniform; rows beyond R are never read unmasked)
-        pf_dma16(base, src_off(kb + u * 8 + lr, st), lds0 + (uint32_t)(which * TP * ROWB) + (uint32_t)((k0 + u * 8) * ROWB));
+        dma16(base, src_off(kb + u * 8 + lr, st), lds0 + (uint32_t)(which * TP * ROWB) + (uint32_t)((k0 + u * 8) * ROWB));
         ++nvm;
       }
   };
@@ -510,7 +421,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         u32x2 w;
         w[0] = pack2bf(acc[dt][rg * 4 + 0] * mul, acc[dt][rg * 4 + 1] * mul);
         w[1] = pack2bf(acc[dt][rg * 4 + 2] * mul, acc[dt][rg * 4 + 3] * mul);
-        *reinterpret_cast<u32x2*>(tile + swz(li, dt * 32 + 8 * rg + 4 * lh)) = w;
+        *reinterpret_cast<u32x2*>(tile + swz(li, tileimg::park_col(dt, rg, lh))) = w;
       }
   };
   // D = rowsum(dO * O) of rows 8 wave .. 8 wave + 7 of tile t (waves 0-3) / its log2-domain lse (wave 4) -> the slot's vectors
@@ -550,16 +461,16 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 
   int koff[4], toff[2][2], woff[4];
 #pragma unroll
-  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, kc * 16 + 8 * lh);
+  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, tileimg::frag_rows_col(kc, lh));
   {
     const int g4 = lane >> 4, q = lane & 15;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj) toff[dt][jj] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * jj, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
+      for (int jj = 0; jj < 2; ++jj) toff[dt][jj] = TR_LANE_OFF(g4, q, dt, jj);
   }
 #pragma unroll
-  for (int rg = 0; rg < 4; ++rg) woff[rg] = swz64(li, 8 * rg + 4 * lh);
+  for (int rg = 0; rg < 4; ++rg) woff[rg] = swz64(li, tileimg::park_col(0, rg, lh));
   bf16x8_t kf[4], vf[4];
   auto load_kv = [&](int cch) {
     const bool rok = (MULTI ? cch * TP + key : key) < T;
@@ -642,10 +553,10 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
       }
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        gtf[dt][0] = frag_tr_at(gsl, toff[dt][0], toff[dt][1]);
-        gtf[dt][1] = frag_tr_at(gsl + 16 * ROWB, toff[dt][0], toff[dt][1]);
-        qtf[dt][0] = frag_tr_at(qs, toff[dt][0], toff[dt][1]);
-        qtf[dt][1] = frag_tr_at(qs + 16 * ROWB, toff[dt][0], toff[dt][1]);
+        gtf[dt][0] = tr16_frag(gsl, toff[dt][0], toff[dt][1]);
+        gtf[dt][1] = tr16_frag(gsl + 16 * ROWB, toff[dt][0], toff[dt][1]);
+        qtf[dt][0] = tr16_frag(qs, toff[dt][0], toff[dt][1]);
+        qtf[dt][1] = tr16_frag(qs + 16 * ROWB, toff[dt][0], toff[dt][1]);
       }
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
@@ -688,7 +599,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
         float dw[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int ql = 8 * (r >> 2) + 4 * lh + (r & 3);
+          const int ql = 8 * (r >> 2) + 4 * lh + (r & 3);   // acc_row(r, lh); as a call it changes this kernel's code
           dw[r] = ql == qp ? hi : (ql == qp + 1 ? lo : ds[r]);
         }
         w0 = __builtin_bit_cast(u32x4, pack8(dw));
@@ -702,7 +613,7 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
           uint32_t one = 0x3F803F80u;
           if (j == NQ - 1) {
             const int r0 = 2 * i, r1 = 2 * i + 1;
-            const int q0 = 8 * (r0 >> 2) + 4 * lho + (r0 & 3), q1 = 8 * (r1 >> 2) + 4 * lho + (r1 & 3);   // (lho: not hoisted, not spilled)
+            const int q0 = 8 * (r0 >> 2) + 4 * lho + (r0 & 3), q1 = 8 * (r1 >> 2) + 4 * lho + (r1 & 3);   // acc_row; (lho: not hoisted, not spilled)
             one = (q0 < qp ? 0x00003F80u : 0u) | (q1 < qp ? 0x3F800000u : 0u);
           }
           if (i < 4) pb0[i] = mine ? one : pb0[i];
@@ -739,12 +650,12 @@ __global__ __launch_bounds__((NT + 1) * 64) void attn_bwd_dqw_bf16_kernel(BwdArg
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) Red[128 + dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = dv[dt][r];
+          for (int r = 0; r < 16; ++r) Red[128 + dt * 32 + acc_row(r, lh)] = dv[dt][r];
       }
     }
     if (mpos == 3) mem_issue();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    dqw_wait_vm(nvm);                                        // what this wave issued BEFORE this step has landed / left
+    wait_vm(nvm);                                            // what this wave issued BEFORE this step has landed / left
     if (j == NQ - 1) {
       // end of the unit (no barrier: this wave's own rows only)
       if (il + 1 < nunits) load_kv(cN);                       // the next item's K / V fragments, then this wave's V rows are dead

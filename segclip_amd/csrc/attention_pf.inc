@@ -27,13 +27,6 @@ static inline size_t fwd_pf_lds_bytes(int n, int T) {
   return (size_t)4 * pf_kv_rows(T) * 128 + (size_t)2 * n * PF_QO_BYTES + (size_t)2 * n * 128;
 }
 
-typedef __attribute__((address_space(3))) void pf_lds_void;
-
-// one 1-KiB LDS-DMA piece: lane l -> 16 bytes from base + off to LDS byte address lds_dst + 16 l.  Issued from inline asm:
-// hipcc neither counts it nor waits for it (s_nop 4: SGPR written by SALU -> VMEM; s_nop 0: M0 -> LDS-DMA).
-__device__ __forceinline__ void pf_dma16(const void* base_uniform, uint32_t off, uint32_t lds_dst) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds_dst) : "memory");
-}
 // exchange between the two lanes (l, l + 32) that share a query row, on the VALU.  After the swap of a value with itself
 // the two results hold {own, partner} in either order in every lane.
 __device__ __forceinline__ float pf_xmax(float x) {
@@ -53,7 +46,7 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
   const int T = a.Tq;                                      // == Tk (host-checked)
   const int R = (T + 7) & ~7;                              // rows of a K / V tile in LDS
   const int TILE = R * ROWB;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)((pf_lds_void*)smem_pf);
+  const uint32_t lds0 = (uint32_t)(uintptr_t)((lds_void*)smem_pf);
   // layout: [K0][V0][K1][V1] [QO0: NT x 4 KB][QO1] [lse0: NT x 128 B][lse1]
   const int QO_OFF = 4 * TILE, LSE_OFF = QO_OFF + 2 * NT * PF_QO_BYTES;
 
@@ -66,32 +59,9 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
 
   if (wave == NT) {
     // ================================ loader wave ================================
-    // piece q of a tile: 8 rows; lane l -> row r = 8 q + (l >> 3), LDS chunk l & 7 <- source chunk (l & 7) ^ f(r)
     const int npk = R >> 3;                                // pieces per K / V tile
     const int npq = NT * 4;                                // pieces of the Q buffer (NT x 32 rows)
-    // Source offsets: the swizzle term f(r) only depends on r & 15, i.e. on the parity of the piece: two lane constants
-    // (even / odd pieces) + a uniform step per pair of pieces; only pieces that reach beyond row T clamp their rows.
-    const int lr = lane >> 3;
-    auto src_off = [&](int r, int64_t st) {
-      const int t = (r >> 1) & 7, f = ((t & 1) << 2) | (t >> 1);
-      int c = (lane & 7) ^ f;
-      if (c * 8 >= a.hd) c = 0;
-      const int rc = r < T ? r : T - 1;
-      return (uint32_t)(((int64_t)rc * st + c * 8) * 2);
-    };
-    auto dma_tile = [&](const bf16_t* base, int64_t st, int np, uint32_t dst) {
-      uint32_t o0 = src_off(lr, st), o1 = src_off(8 + lr, st);
-      const uint32_t step = (uint32_t)(16 * st * 2);
-      const int nfull = T >> 4;                             // pairs of pieces entirely below row T
-      int q = 0;
-      for (; q < 2 * nfull && q + 2 <= np; q += 2) {
-        asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2\n\t"
-                     "s_add_u32 m0, %3, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                     : : "v"(o0), "v"(o1), "s"(base), "s"(dst + q * 1024) : "memory", "scc");
-        o0 += step; o1 += step;
-      }
-      for (; q < np; ++q) pf_dma16(base, src_off(q * 8 + lr, st), dst + q * 1024);
-    };
+#include "attention_dma_tile.inc"   // src_off, dma_tile
     auto issue_kv = [&](int item, int slot) {
       const int b = item / a.H, h = item - b * a.H;
       dma_tile(a.K + (int64_t)b * a.k_sb + (int64_t)h * a.hd, a.k_st, npk, lds0 + slot * 2 * TILE);
@@ -158,13 +128,13 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
     const int lh_i = lane_i >> 5, li_i = lane_i & 31, qg_i = q0 + li_i;
     int koff[4], voff[2][2];
 #pragma unroll
-    for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li_i, kc * 16 + 8 * lh_i);
+    for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li_i, tileimg::frag_rows_col(kc, lh_i));
     {
       const int g4 = lane_i >> 4, q = lane_i & 15;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) voff[dt][j] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * j, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
+        for (int j = 0; j < 2; ++j) voff[dt][j] = TR_LANE_OFF(g4, q, dt, j);
     }
     char* const qo = smem_pf + QO_OFF + (slot * NT + wave) * PF_QO_BYTES;
     float* const lse_w = reinterpret_cast<float*>(smem_pf + LSE_OFF) + (slot * NT + wave) * 32;
@@ -196,8 +166,8 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
       const char* vb = Vt + kt * 32 * ROWB;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        vf[dt][0] = frag_tr_at(vb, voff[dt][0], voff[dt][1]);
-        vf[dt][1] = frag_tr_at(vb + 16 * ROWB, voff[dt][0], voff[dt][1]);
+        vf[dt][0] = tr16_frag(vb, voff[dt][0], voff[dt][1]);
+        vf[dt][1] = tr16_frag(vb + 16 * ROWB, voff[dt][0], voff[dt][1]);
       }
     };
     auto qk = [&](const bf16x8_t (&kf)[4]) {
@@ -289,7 +259,7 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = kt * 32 + accrow(r, lh_i);
+          const int key = kt * 32 + acc_row(r, lh_i);
           const bool ok = key < kvalid && (!CAUSAL || key <= qg_i);
           p[r] = ok ? s0[r] * sc2 : -INFINITY;
           mx = fmaxf(mx, p[r]);
@@ -332,7 +302,7 @@ __global__ __launch_bounds__((NT + 1) * 64) __attribute__((amdgpu_waves_per_eu(2
           u32x2 t;
           t[0] = pack2bf(o[dt][rg * 4 + 0] * inv, o[dt][rg * 4 + 1] * inv);
           t[1] = pack2bf(o[dt][rg * 4 + 2] * inv, o[dt][rg * 4 + 3] * inv);
-          *reinterpret_cast<u32x2*>(qo + swz(li_i, dt * 32 + 8 * rg + 4 * lh_i)) = t;
+          *reinterpret_cast<u32x2*>(qo + swz(li_i, tileimg::park_col(dt, rg, lh_i))) = t;
         }
       if (lh_i == 0) lse_w[li_i] = (l > 0.f) ? m * 0.6931471805599453f + __logf(l) : -INFINITY;
     }

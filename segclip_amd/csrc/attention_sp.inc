@@ -20,20 +20,14 @@ static inline size_t bwd_sp_lds_bytes(int tp) {
   return (size_t)tp * 2 * ROWB + (size_t)n * (SP_ACC_BYTES + SP_SCR_BYTES) + (size_t)tp * 3 * 4 + 8 * 3 * 64 * 4 + 64;
 }
 
-// byte offset of element (row = key, col = q) in a [32][32] bf16 tile with 64-byte rows; 16-byte chunk ^ ((row>>1)&3)
-__device__ __forceinline__ int swz64(int row, int col) { return row * 64 + ((((col >> 3) ^ ((row >> 1) & 3))) << 4) + ((col & 7) << 1); }
+using tileimg::swz64;   // byte offset of element (row = key, col = q) in a [32][32] bf16 tile with 64-byte rows: the scratch image
 
 // MFMA B-operand fragment of the scratch tile: lane l -> column q = l&31, k = keys rbase + 4*(l>>5) + {0..3, 8..11}
 __device__ __forceinline__ bf16x8_t frag_tr64(const char* t, int rbase, int lane) {
-  const int g4 = lane >> 4, q = lane & 15;
-  const int row = rbase + 4 * (g4 >> 1) + (q >> 2);
-  const int col = 16 * (g4 & 1) + 4 * (q & 3);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + swz64(row, col)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(t + swz64(row + 8, col)));
-  s16x8 r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, r);
+  const int row = tileimg::frag_tr_row(rbase, lane), col = tileimg::frag_tr_col(0, lane);
+  const s16x4 lo = tr16_read(t + swz64(row, col));
+  const s16x4 hi = tr16_read(t + swz64(tileimg::frag_tr_hi(row), col));
+  return tr16_join(lo, hi);
 }
 
 // MASKED = false: non-causal, no key-padding mask (the vision tower): the loop body has no branch and no mask test -
@@ -167,7 +161,7 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
   {  // the slot becomes query tile `wave`'s dQ^T accumulator: zero it (8 x 16 bytes per lane)
     f32x4* z = reinterpret_cast<f32x4*>(myacc);
 #pragma unroll
-    for (int g8 = 0; g8 < 8; ++g8) z[g8 * 64 + lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int g8 = 0; g8 < 8; ++g8) z[tileimg::accq_index(g8, lane)] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (lane == 0) Flag[wave] = 0;
   }
   __syncthreads();
@@ -183,14 +177,11 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
   // instructions per pair were address arithmetic; swz(32 j + r, c) = 32 j ROWB + swz(r, c))
   int koff[4], toff[2][2];
 #pragma unroll
-  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, kc * 16 + 8 * lh);
-  {
-    const int g4 = lane >> 4, q = lane & 15;
+  for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, tileimg::frag_rows_col(kc, lh));
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+  for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) toff[dt][j] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * j, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
-  }
+    for (int j = 0; j < 2; ++j) toff[dt][j] = tr_lane_off(lane, dt, j);
   f32x16 dk[2], dv[2];
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
@@ -255,19 +246,19 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
       {
         const u32x4 w0 = __builtin_bit_cast(u32x4, sb0), w1 = __builtin_bit_cast(u32x4, sb1);
         const u32x2 g0 = {w0[0], w0[1]}, g1 = {w0[2], w0[3]}, g2 = {w1[0], w1[1]}, g3 = {w1[2], w1[3]};
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 0 + 4 * lh)) = g0;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 8 + 4 * lh)) = g1;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 16 + 4 * lh)) = g2;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 24 + 4 * lh)) = g3;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 0, lh))) = g0;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 1, lh))) = g1;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 2, lh))) = g2;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 3, lh))) = g3;
       }
       const char* qt_ = Qt + q0 * ROWB;
       const char* gt_ = Gt + q0 * ROWB;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(gt_, toff[dt][0], toff[dt][1]), pb0, dv[dt], 0, 0, 0);
-        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(gt_ + 16 * ROWB, toff[dt][0], toff[dt][1]), pb1, dv[dt], 0, 0, 0);
-        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(qt_, toff[dt][0], toff[dt][1]), sb0, dk[dt], 0, 0, 0);
-        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr_at(qt_ + 16 * ROWB, toff[dt][0], toff[dt][1]), sb1, dk[dt], 0, 0, 0);
+        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(gt_, toff[dt][0], toff[dt][1]), pb0, dv[dt], 0, 0, 0);
+        dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(gt_ + 16 * ROWB, toff[dt][0], toff[dt][1]), pb1, dv[dt], 0, 0, 0);
+        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(qt_, toff[dt][0], toff[dt][1]), sb0, dk[dt], 0, 0, 0);
+        dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr16_frag(qt_ + 16 * ROWB, toff[dt][0], toff[dt][1]), sb1, dk[dt], 0, 0, 0);
       }
       // the scratch writes above are this wave's own (LDS operations of one wave execute in order)
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -294,10 +285,10 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
       f32x4* acc = reinterpret_cast<f32x4*>(Acc + jt * SP_ACC_BYTES);
 #pragma unroll
       for (int g8 = 0; g8 < 8; ++g8) {
-        f32x4 v = acc[g8 * 64 + lane];
-        const int dt = g8 >> 2, rb = (g8 & 3) * 4;
+        f32x4 v = acc[tileimg::accq_index(g8, lane)];
+        const int dt = tileimg::accq_dt(g8), rb = tileimg::accq_reg(g8);
         v[0] += dq[dt][rb]; v[1] += dq[dt][rb + 1]; v[2] += dq[dt][rb + 2]; v[3] += dq[dt][rb + 3];
-        acc[g8 * 64 + lane] = v;
+        acc[tileimg::accq_index(g8, lane)] = v;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -342,8 +333,8 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
     const f32x4* acc = reinterpret_cast<const f32x4*>(myacc);
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) {
-      const f32x4 v = acc[g8 * 64 + lane];
-      const int dt = g8 >> 2, rb = (g8 & 3) * 4;
+      const f32x4 v = acc[tileimg::accq_index(g8, lane)];
+      const int dt = tileimg::accq_dt(g8), rb = tileimg::accq_reg(g8);
       dq[dt][rb] = v[0] * a.scale; dq[dt][rb + 1] = v[1] * a.scale; dq[dt][rb + 2] = v[2] * a.scale; dq[dt][rb + 3] = v[3] * a.scale;
     }
   }
@@ -357,7 +348,7 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
         u32x2 t;
         t[0] = pack2bf(acc[dt][rg * 4 + 0], acc[dt][rg * 4 + 1]);
         t[1] = pack2bf(acc[dt][rg * 4 + 2], acc[dt][rg * 4 + 3]);
-        *reinterpret_cast<u32x2*>(tile + swz(li, dt * 32 + 8 * rg + 4 * lh)) = t;
+        *reinterpret_cast<u32x2*>(tile + swz(li, tileimg::park_col(dt, rg, lh))) = t;
       }
   };
   auto flush_tile = [&](const char* tile, bf16_t* base, int64_t st, int nrows) {
@@ -409,7 +400,7 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_bf16_kernel(BwdArgs a) {
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Red[(wave * 3 + 0) * 64 + dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = cq[dt][r];
+        for (int r = 0; r < 16; ++r) Red[(wave * 3 + 0) * 64 + dt * 32 + acc_row(r, lh)] = cq[dt][r];
     }
     const int c = tid & 7, nrl = (int)blockDim.x >> 3;
     float accv[8];

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
   float* Gsb = Cs + tp;                                      // [2][64] token sums of dO
   float* Red = Gsb + 2 * 64;                                 // [n][64] token sums of dQ, per key-tile wave
   volatile int* Flag = reinterpret_cast<volatile int*>(Red + n * 64);   // [8] flag ring of the main loop; [8] = parked-tile counter
-  const uint32_t lds0 = (uint32_t)(uintptr_t)((pf_lds_void*)smem_bwd);
+  const uint32_t lds0 = (uint32_t)(uintptr_t)((lds_void*)smem_bwd);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nitems = a.nitems;
 
@@ -52,30 +52,11 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
 
   if (wave == n) {
     // ================================================ loader wave ================================================
-    const int lane = threadIdx.x & 63, lr = lane >> 3, c = lane & 7;
+    const int lane = threadIdx.x & 63, c = lane & 7;
     const int npk = R >> 3;                                  // 8-row pieces of a K tile
     const int npq = tp >> 3;                                 // 8-row pieces of the Q / dO tiles
     const bool cok = c * 8 < a.hd;
-    auto src_off = [&](int r, int64_t st) {                  // source chunk of (row r, LDS chunk lane & 7): the tiles' swizzle
-      const int t = (r >> 1) & 7, f = ((t & 1) << 2) | (t >> 1);
-      int cc = c ^ f;
-      if (cc * 8 >= a.hd) cc = 0;
-      const int rc = r < T ? r : T - 1;
-      return (uint32_t)(((int64_t)rc * st + cc * 8) * 2);
-    };
-    auto dma_tile = [&](const bf16_t* base, int64_t st, int np, uint32_t dst) {
-      uint32_t o0 = src_off(lr, st), o1 = src_off(8 + lr, st);
-      const uint32_t step = (uint32_t)(16 * st * 2);
-      const int nfull = T >> 4;
-      int q = 0;
-      for (; q < 2 * nfull && q + 2 <= np; q += 2) {
-        asm volatile("s_nop 4\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2\n\t"
-                     "s_add_u32 m0, %3, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                     : : "v"(o0), "v"(o1), "s"(base), "s"(dst + q * 1024) : "memory", "scc");
-        o0 += step; o1 += step;
-      }
-      for (; q < np; ++q) pf_dma16(base, src_off(q * 8 + lr, st), dst + q * 1024);
-    };
+#include "attention_dma_tile.inc"   // src_off, dma_tile
     u32x4 gd[28];                                            // dO tile of the NEXT item: piece q -> row 8 q + lr, chunk c (unswizzled)
     // item `item`: K -> KN, dO -> gd registers, D / lse / token sums of dO -> the vectors' buffer `nb`
     auto prefetch = [&](int item, int nb) {
@@ -290,7 +271,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
         }
       f32x4* z = reinterpret_cast<f32x4*>(myacc);            // the slot becomes query tile `wave`'s dQ^T accumulator
 #pragma unroll
-      for (int g8 = 0; g8 < 8; ++g8) z[g8 * 64 + lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int g8 = 0; g8 < 8; ++g8) z[tileimg::accq_index(g8, lane)] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (lane == 0) Flag[wave] = 0;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -298,14 +279,11 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
 
     int koff[4], toff[2][2];
 #pragma unroll
-    for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, kc * 16 + 8 * lh);
-    {
-      const int g4 = lane >> 4, q = lane & 15;
+    for (int kc = 0; kc < 4; ++kc) koff[kc] = swz(li, tileimg::frag_rows_col(kc, lh));
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) toff[dt][j] = swz(4 * (g4 >> 1) + (q >> 2) + 8 * j, dt * 32 + 16 * (g4 & 1) + 4 * (q & 3));
-    }
+      for (int j = 0; j < 2; ++j) toff[dt][j] = tr_lane_off(lane, dt, j);
     f32x16 dk[2], dv[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
@@ -356,20 +334,20 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       {
         const u32x4 w0 = __builtin_bit_cast(u32x4, sb0), w1 = __builtin_bit_cast(u32x4, sb1);
         const u32x2 g0 = {w0[0], w0[1]}, g1 = {w0[2], w0[3]}, g2 = {w1[0], w1[1]}, g3 = {w1[2], w1[3]};
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 0 + 4 * lh)) = g0;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 8 + 4 * lh)) = g1;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 16 + 4 * lh)) = g2;
-        *reinterpret_cast<u32x2*>(scr + swz64(li, 24 + 4 * lh)) = g3;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 0, lh))) = g0;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 1, lh))) = g1;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 2, lh))) = g2;
+        *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, 3, lh))) = g3;
       }
       const char* qt_ = Qt + q0 * ROWB;
       const char* gt_ = Gt + q0 * ROWB;
       bf16x8_t gtf[2][2], qtf[2][2];                        // the 16 transposed fragments of the pair in one batch
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        gtf[dt][0] = frag_tr_at(gt_, toff[dt][0], toff[dt][1]);
-        gtf[dt][1] = frag_tr_at(gt_ + 16 * ROWB, toff[dt][0], toff[dt][1]);
-        qtf[dt][0] = frag_tr_at(qt_, toff[dt][0], toff[dt][1]);
-        qtf[dt][1] = frag_tr_at(qt_ + 16 * ROWB, toff[dt][0], toff[dt][1]);
+        gtf[dt][0] = tr16_frag(gt_, toff[dt][0], toff[dt][1]);
+        gtf[dt][1] = tr16_frag(gt_ + 16 * ROWB, toff[dt][0], toff[dt][1]);
+        qtf[dt][0] = tr16_frag(qt_, toff[dt][0], toff[dt][1]);
+        qtf[dt][1] = tr16_frag(qt_ + 16 * ROWB, toff[dt][0], toff[dt][1]);
       }
       asm volatile("" ::: "memory");
 #pragma unroll
@@ -396,10 +374,10 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       f32x4* acc = reinterpret_cast<f32x4*>(Acc + jt * SP_ACC_BYTES);
 #pragma unroll
       for (int g8 = 0; g8 < 8; ++g8) {
-        f32x4 v = acc[g8 * 64 + lane];
-        const int dt = g8 >> 2, rb = (g8 & 3) * 4;
+        f32x4 v = acc[tileimg::accq_index(g8, lane)];
+        const int dt = tileimg::accq_dt(g8), rb = tileimg::accq_reg(g8);
         v[0] += dq[dt][rb]; v[1] += dq[dt][rb + 1]; v[2] += dq[dt][rb + 2]; v[3] += dq[dt][rb + 3];
-        acc[g8 * 64 + lane] = v;
+        acc[tileimg::accq_index(g8, lane)] = v;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
@@ -432,12 +410,10 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       const int lr = lane >> 3, c = lane & 7;
 #pragma unroll
       for (int p4 = 0; p4 < 4; ++p4) {
-        const int r = k0 + p4 * 8 + lr;
-        const int t = (r >> 1) & 7, f = ((t & 1) << 2) | (t >> 1);
-        int cc = c ^ f;
-        if (cc * 8 >= a.hd) cc = 0;
-        const int rc = r < T ? r : T - 1;
-        pf_dma16(Qn, (uint32_t)(((int64_t)rc * a.q_st + cc * 8) * 2), lds0 + (uint32_t)(Qt - smem_bwd) + (uint32_t)(k0 + p4 * 8) * ROWB);
+        const int r = k0 + p4 * 8 + lr;                      // k0 + tileimg::piece_row(p4, lane); as a call it changes this kernel's code
+        int cc = tileimg::piece_chunk(r, c);
+        if (cc * 8 >= a.hd) cc = 0;                          // tileimg::clamp_chunk; as a call it changes this kernel's code
+        dma16(Qn, (uint32_t)(((int64_t)tileimg::clamp_row(r, T) * a.q_st + cc * 8) * 2), lds0 + (uint32_t)(Qt - smem_bwd) + (uint32_t)(k0 + p4 * 8) * ROWB);
       }
     }
     f32x16 dq[2];
@@ -445,8 +421,8 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
       const f32x4* acc = reinterpret_cast<const f32x4*>(myacc);
 #pragma unroll
       for (int g8 = 0; g8 < 8; ++g8) {
-        const f32x4 v = acc[g8 * 64 + lane];
-        const int dt = g8 >> 2, rb = (g8 & 3) * 4;
+        const f32x4 v = acc[tileimg::accq_index(g8, lane)];
+        const int dt = tileimg::accq_dt(g8), rb = tileimg::accq_reg(g8);
         dq[dt][rb] = v[0] * a.scale; dq[dt][rb + 1] = v[1] * a.scale; dq[dt][rb + 2] = v[2] * a.scale; dq[dt][rb + 3] = v[3] * a.scale;
       }
     }
@@ -460,7 +436,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
           u32x2 t;
           t[0] = pack2bf(acc[dt][rg * 4 + 0], acc[dt][rg * 4 + 1]);
           t[1] = pack2bf(acc[dt][rg * 4 + 2], acc[dt][rg * 4 + 3]);
-          *reinterpret_cast<u32x2*>(tile + swz(li, dt * 32 + 8 * rg + 4 * lh)) = t;
+          *reinterpret_cast<u32x2*>(tile + swz(li, tileimg::park_col(dt, rg, lh))) = t;
         }
     };
     put_tile(myacc, dk);                                     // the loader stores them once all waves have parked theirs
@@ -468,8 +444,8 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) __hip_atomic_fetch_add(const_cast<int*>(Flag + 8), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // "S3"
-    // dQ tile -> global through the wave's 2-KB scratch, one 32-column half at a time ([32 rows][64 B], 16-byte chunk
-    // ^ ((row >> 1) & 3)).  (Tried: dK and dV the same way, the loader only loading - 12 stores per compute wave: 305 vs
+    // dQ tile -> global through the wave's 2-KB scratch, one 32-column half at a time (the scratch image, swz64).
+    // (Tried: dK and dV the same way, the loader only loading - 12 stores per compute wave: 305 vs
     // 292 us; the 84 stores of the compute waves and the loader's Q DMA then meet in the same phase of the item.)
     {
       bf16_t* dQp = a.dQ + b * a.dq_sb + (int64_t)h * a.hd;
@@ -480,7 +456,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
           u32x2 t;
           t[0] = pack2bf(dq[dt][rg * 4 + 0], dq[dt][rg * 4 + 1]);
           t[1] = pack2bf(dq[dt][rg * 4 + 2], dq[dt][rg * 4 + 3]);
-          *reinterpret_cast<u32x2*>(scr + swz64(li, 8 * rg + 4 * lh)) = t;
+          *reinterpret_cast<u32x2*>(scr + swz64(li, tileimg::park_col(0, rg, lh))) = t;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
@@ -520,7 +496,7 @@ __global__ __launch_bounds__(512) void attn_bwd_spl_bf16_kernel(BwdArgs a) {
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) Red[wave * 64 + dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = cq[dt][r];
+          for (int r = 0; r < 16; ++r) Red[wave * 64 + dt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3)] = cq[dt][r];   // acc_row(r, lh); as a call it changes this kernel's code
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

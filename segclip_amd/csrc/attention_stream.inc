@@ -233,7 +233,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(BwdArgs a, cons
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = c0 + kk + accrow(r, lh);
+        const int key = c0 + kk + acc_row(r, lh);
         const bool ok = key < a.Tk && q < a.Tq && (!a.causal || key <= q);
         const float pv = ok ? __expf(s[r] * a.scale - lq) : 0.f;
         ds[r] = pv * (dp[r] - dq_) * a.scale;

@@ -46,8 +46,9 @@ for part in 0 1 2 3 4; do
     pids+=($!)
   fi
 done
-# gemm_image_check.cpp emits no code: its static_asserts stop the build when the GEMM's LDS operand images disagree
-for f in gemm_f32.hip layernorm.hip attention.hip misc.hip group_linear.hip head.hip center.hip segment.hip retrieval.hip optim.hip capi.cpp gemm_plan.cpp gemm_image_check.cpp exec.cpp; do
+# gemm_image_check.cpp and attention_image_check.cpp emit no code: their static_asserts stop the build when the GEMM's LDS
+# operand images / the attention kernels' LDS tile images disagree
+for f in gemm_f32.hip layernorm.hip attention.hip misc.hip group_linear.hip head.hip center.hip segment.hip retrieval.hip optim.hip capi.cpp gemm_plan.cpp gemm_image_check.cpp attention_image_check.cpp exec.cpp; do
   [ -f "$f" ] || continue
   o=build/${f%.*}.o
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$newest_hdr" -nt "$o" ]; then

@@ -152,14 +152,7 @@ template <int B> __device__ __forceinline__ void acc_write8(const float* v) {
       : PQ_AGPRS);
 }
 
-// single LDS-DMA pieces of the side operands, from inline asm like the operands' dma16x2 (gemm_bf16_lds.h)
-__device__ __forceinline__ void dma16(const void* base_uniform, uint32_t off, uint32_t lds0) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds0) : "memory");
-}
-__device__ __forceinline__ void dma4(const void* base_uniform, uint32_t off, uint32_t lds0) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" : : "v"(off), "s"(base_uniform), "s"(lds0) : "memory");
-}
-
+// (the single LDS-DMA pieces of the side operands: dma16 / dma4 of lds_ops.h)
 // per-lane DMA source offsets (bytes from the tile's first element), as in gemm_bf16_p8.hip; full tiles only
 __device__ __forceinline__ uint32_t off_direct(int h, int idx, int lane, int64_t ld) {
   const int u = opimg::piece_direct_row(idx, lane);

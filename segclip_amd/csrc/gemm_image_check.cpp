@@ -2,16 +2,15 @@
 // emitted.  A wrong image stops the build.  One assertion = one image, one configuration, one rbase.
 //   1. writer and reader agree: what a lane of an LDS-DMA piece fetches is what the image stores where the lane lands;
 //   2. fragments hold the right elements for both MFMA shapes (ks images: through the transpose-read model);
-//   3. bank-conflict degree of every fragment read, by the documented rule: bank = (a / 4) mod 64; a lane occupies 4 banks
-//      (ds_read_b128) or 2 (ds_read_b64_tr_b16); lanes conflict only within a group - ds_read_b128: {0-3, 12-15, 20-27},
-//      {4-11, 16-19, 28-31} and the same + 32; ds_read_b64_tr_b16: the two 32-lane halves; equal dwords broadcast; degree =
-//      most distinct dwords on one bank within a group.  A MODEL, not a counter reading;
+//   3. bank-conflict degree of every fragment read, by the rule of lds_bank_model.h.  A MODEL, not a counter reading;
 //   4. the XCD chunking of workgroup ids is a bijection.
 #include "gemm_operand_image.h"
+#include "lds_bank_model.h"
 
 #ifndef __HIP_DEVICE_COMPILE__   // once, in the host pass
 namespace {
 using namespace opimg;
+using namespace ldsbank;
 
 // ---- 1. writer and reader agree ------------------------------------------------------------------------------------------
 constexpr bool pieces_direct_land(int npieces) {
@@ -88,29 +87,6 @@ template <int PITCH, bool XOR, bool M16> constexpr bool frag_ks_holds(int rbase)
 }
 
 // ---- 3. bank-conflict degree (model) -------------------------------------------------------------------------------------
-struct Wave { int a[64]; };   // the byte address every lane hands to one instruction
-constexpr int b128_group(int l) {
-  const int m = l & 31;
-  return (l >> 5) * 2 + ((m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28)) ? 0 : 1);
-}
-constexpr int degree(const Wave& w, bool b128) {
-  int worst = 0;
-  for (int g = 0; g < (b128 ? 4 : 2); ++g) {
-    int dw[128] = {}, n = 0, cnt[64] = {};
-    for (int l = 0; l < 64; ++l) {
-      if ((b128 ? b128_group(l) : l >> 5) != g) continue;
-      for (int d = 0; d < (b128 ? 4 : 2); ++d) {
-        const int x = w.a[l] / 4 + d;
-        bool dup = false;
-        for (int i = 0; i < n && !dup; ++i) dup = dw[i] == x;
-        if (dup) continue;
-        dw[n++] = x;
-        if (++cnt[x & 63] > worst) worst = cnt[x & 63];
-      }
-    }
-  }
-  return worst;
-}
 // the degree every fragment read of this rbase has (all kc, both halves of a transpose read), or -1 if they differ
 template <bool M16> constexpr int degree_direct(int rbase) {
   constexpr bool m16 = M16;
