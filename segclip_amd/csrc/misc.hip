@@ -811,6 +811,8 @@ extern "C" int segclip_embed_fwd(const int64_t* ids, const float* table, const f
 }
 extern "C" int segclip_embed_bwd(const int64_t* ids, const float* dout, float* dtable, float* dpos, int64_t B, int64_t L,
                                  int64_t D, int64_t vocab, void* stream) {
+  // checked before either launch: a refused call leaves dtable as it was
+  SEGCLIP_REQUIRE(!dpos || D % 4 == 0, "embed_bwd: D=%lld must be a multiple of 4", (long long)D);
   if (B == 0) return 0;
   if (dtable) {
     hipLaunchKernelGGL(embed_bwd_table_kernel, dim3(grid1d(B * L * D)), dim3(TPB), 0, ST, ids, dout, dtable, B * L, (int)D,
@@ -818,7 +820,6 @@ extern "C" int segclip_embed_bwd(const int64_t* ids, const float* dout, float* d
     SEGCLIP_CHECK_LAUNCH("embed_bwd_table");
   }
   if (dpos) {
-    SEGCLIP_REQUIRE(D % 4 == 0, "embed_bwd: D=%lld must be a multiple of 4", (long long)D);
     hipLaunchKernelGGL(embed_bwd_pos_kernel, dim3((unsigned)cdiv(L * D / 4, 64)), dim3(64), 0, ST, dout, dpos, B, (int)L, (int)D);
     SEGCLIP_CHECK_LAUNCH("embed_bwd_pos");
   }

@@ -1,6 +1,6 @@
 """The machinery shared by the GPU test files that call one kernel at a time through the C ABI (tests/test_center_stage_gpu.py,
-tests/test_loss_head_gpu.py): NaN-framed buffers, seeded host-side inputs, the call-twice harness, and the value check with its
-floor-measuring mode.  Importing this module needs torch only; a frame allocates on the device."""
+tests/test_loss_head_gpu.py, tests/test_frontend_glue_gpu.py): NaN-framed buffers, seeded host-side inputs, the call-twice
+harness, and the value check with its floor-measuring mode.  Importing this module needs torch only; a frame allocates on the device."""
 import math
 
 import torch
@@ -12,6 +12,7 @@ DEV = "cuda"
 BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 GUARD = 64
 IDX_FILL = 0xAB
+IDX_FILL_WIDE = -0x5454545454545455   # 0xAB in every byte of an int64: for index outputs that may hold 171 themselves
 
 
 def round_up_1(x):
@@ -56,21 +57,22 @@ class Bounds:
 
 class Frame:
     """a view of `shape` (rows of shape[-1] elements, `pitch` apart) inside a flat buffer filled with NaN (0xAB for integers):
-    GUARD words before, two guard rows and GUARD words after"""
+    GUARD words before, two guard rows and GUARD words after.  `shift` moves the view that many elements further into the
+    buffer (a view that is not 16-byte aligned); `fill` replaces the guard value of an integer frame."""
 
-    def __init__(self, shape, dtype, pitch=None):
+    def __init__(self, shape, dtype, pitch=None, shift=0, fill=None):
         shape = tuple(shape)
         W = shape[-1]
         pitch = pitch or W
         rows = math.prod(shape[:-1])
-        self.fill = float("nan") if dtype.is_floating_point else IDX_FILL
-        self.buf = torch.full((GUARD + (rows + 2) * pitch + GUARD,), self.fill, dtype=dtype, device=DEV)
+        self.fill = float("nan") if dtype.is_floating_point else (IDX_FILL if fill is None else fill)
+        self.buf = torch.full((GUARD + shift + (rows + 2) * pitch + GUARD,), self.fill, dtype=dtype, device=DEV)
         st = [1] if len(shape) == 1 else [pitch, 1]
         for d in reversed(shape[1:-1]):
             st.insert(0, st[0] * d)
-        self.v = self.buf.as_strided(shape, st, GUARD)
+        self.v = self.buf.as_strided(shape, st, GUARD + shift)
         self.inside = torch.zeros_like(self.buf, dtype=torch.bool)
-        self.inside.as_strided(shape, st, GUARD).fill_(True)
+        self.inside.as_strided(shape, st, GUARD + shift).fill_(True)
 
     def intact(self):
         out = self.buf[~self.inside]
@@ -91,9 +93,9 @@ class Frame:
         return L.ptr(self.v)
 
 
-def put(t, pitch=None):
+def put(t, pitch=None, shift=0):
     """the input t inside a frame of its own"""
-    f = Frame(t.shape, t.dtype, pitch)
+    f = Frame(t.shape, t.dtype, pitch, shift)
     f.v.copy_(t)
     return f
 
@@ -106,8 +108,9 @@ def seeded(name):
     return torch.Generator().manual_seed(sum((i + 1) * ord(c) for i, c in enumerate(name)))
 
 
-def run_twice(name, call, outs):
-    """the call, its frames checked, and the same call again: bit-identical, frames included"""
+def run_twice(name, call, outs, finite=True):
+    """the call, its frames checked, and the same call again: bit-identical, frames included.  finite=False for outputs that
+    hold inf or NaN on purpose (the caller then shows by other means that every element was written)"""
     for f in outs:
         f.buf.fill_(f.fill)
     call()
@@ -118,7 +121,7 @@ def run_twice(name, call, outs):
     assert all(torch.equal(a, f.bits()) for a, f in zip(snap, outs)), f"{name}: the second call differs"
     for i, f in enumerate(outs):
         assert f.intact(), f"{name}: output {i} written outside its view"
-        assert f.finite(), f"{name}: output {i} not written everywhere / not finite"
+        assert not finite or f.finite(), f"{name}: output {i} not written everywhere / not finite"
 
 
 def lib_call(fn_name, *args):
