@@ -239,6 +239,9 @@ int segclip_attn_bwd(const segclip_attn_desc* d, void* stream);
  * modules/module_clip_ttransformer.py:20-37; bf16 mode) as ONE call - LayerNorm, in_proj, attention, out_proj + residual,
  * LayerNorm, c_fc + activation + saved derivative, c_proj + residual: the seven launches the Python layer would issue, with the
  * same descriptors, into caller-owned buffers (bit-identical results; what it saves is ~250 us of host time per block).
+ * The four GEMMs are planned before the first launch: SEGCLIP_ERR_UNSUPPORTED means that nothing was enqueued (as from
+ * segclip_gemm) and the caller may issue the launches one by one, in another form.  Only argument errors of the LayerNorm and
+ * attention entry points (SEGCLIP_ERR_INVALID: D % 4, head_dim <= 64 and a multiple of 8) can surface after a launch.
  * x, x1, xo: the residual stream (M, D) in x_dtype (fp32, or bf16 with config.bf16_resid); everything else bf16 unless noted.
  * M may exceed B*T (row-padded stack): the attention touches the B*T token rows, the pad rows of o are zeroed.
  * Weights are the (out, in) bf16 copies of the reference's parameters; biases and LayerNorm affines fp32.

@@ -39,7 +39,8 @@ bf16_resid    : bf16 mode, inside ResStackFn: the residual STREAM itself is bf16
 aux_u8        : bf16 mode: the towers keep QuickGELU'(u) for the backward as ONE BYTE per element where the MLP GEMMs run
                 on full 256 x 256 tiles (q = rint((act' + 0.125) * 204), absolute error <= 0.0025 - about bf16's relative
                 error at the typical magnitude, unbounded RELATIVE error near act' = 0); False keeps it as bf16.  Round 6: the
-                MAE decoders' erf-GELU likewise where the 256 x 256-tile GEMM takes the shape (else: the pre-activation as bf16)
+                MAE decoders' erf-GELU likewise where the 256 x 256-tile GEMM takes the shape (else: the pre-activation as bf16);
+                its derivative spans [-0.129, 1.129], so that byte is good to about 0.0065, not 0.0025
 fused_head    : training forward: max-token pooling + ln_post + projection on the pooled row only, and the contrastive head
                 (L2-normalise, all-gather, logits, both cross entropies) as ONE autograd node (ops.ClipLossFn) - ~15 instead
                 of ~90 launches between the last forward GEMM and the first backward GEMM; False: the op-by-op path
@@ -70,7 +71,8 @@ f32_split     : exact-f32 mode only.  False (default): Linear layers on the fp32
                 attention core stay exact fp32.  Held to the same 1e-3 / index bounds as the exact mode by the parity tests.
 c_exec        : bf16 mode: the forward launches of a residual block are enqueued by one C-ABI call (segclip_resblock_fwd) instead of
                 launch by launch through Python - bit-identical results, less host time (the step is host-bound below ~100 samples
-                per GPU).  Env SEGCLIP_C_EXEC=0 (with SEGCLIP_TUNING=1) for A/B.
+                per GPU; tests/test_block_exec_gpu.py).  A block the call has no kernel for is refused before its first launch
+                and runs launch by launch.  Env SEGCLIP_C_EXEC=0 (with SEGCLIP_TUNING=1) for A/B.
 noise         : None -> draw Gumbel / uniform noise from the device generator (training runs);
                 noise_injection([...("gumbel"|"rand", tensor)...]) consumed in call order -> parity runs
                 (thread-local).

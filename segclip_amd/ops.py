@@ -19,6 +19,7 @@ import torch.distributed as dist
 from torch.autograd import Function
 
 from . import _lib as L
+from . import config as _cfg
 from .config import tuning_env as _tenv
 
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = L.ACT_NONE, L.ACT_QUICK_GELU, L.ACT_GELU_ERF
@@ -213,32 +214,30 @@ def _off(t, off):
 # ------------------------------------------------------------------------------------------------
 # raw launches
 # ------------------------------------------------------------------------------------------------
-def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=None, residual=None, ldr=0,
-           r_off=0, aux=None, ldaux=0, act=ACT_NONE, mul_dact=False, alpha=1.0, nb1=1, nb2=1, bsA=(0, 0),
-           bsB=(0, 0), bsC=(0, 0), bsR=None, colsum=None, aux_kind=0, defer=None, r_mod=0):
-    """C(m,n) = epi(alpha * sum_k A(m,k) B(n,k)); sa = (sam, sak), sb = (sbn, sbk) element strides.
+def p_gemm(A, B, Cc, M, N, K, sa, sb, ldc, **kw):
+    """C(m,n) = epi(alpha * sum_k A(m,k) B(n,k)); sa = (sam, sak), sb = (sbn, sbk) element strides.  The keywords, with their
+    defaults, are those of _gemm_desc: it fills the descriptor (an unknown one is its TypeError).
     r_mod > 0: the residual of output row m is residual row m % r_mod (L.Unsupported where the library has no such kernel)."""
     lib = L.load()
     L.require_cuda(A, B, Cc)
-    if (A.dtype == torch.float32 and B.dtype == torch.float32 and Cc.dtype == torch.float32 and nb1 * nb2 == 1 and colsum is None
-            and r_mod == 0 and M >= 256 and N >= 64 and K >= 64 and K % 8 == 0):
-        from . import config as _cfg
-        if _cfg.f32_split and _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux,
-                                              ldaux, act, mul_dact, alpha, aux_kind, defer):
-            return Cc
-    d, _keep = _gemm_desc(lib, True, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act,
-                          mul_dact, alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, defer, r_mod)
-    if _OpCount.enabled:
-        _OpCount.add("gemm_bf16" if B.dtype == torch.bfloat16 else "gemm_f32", 2.0 * M * N * K * nb1 * nb2,
-                     _gemm_algo_bytes(A, B, Cc, M, N, K, nb1 * nb2, residual, aux))
-    if _GemmProfile.enabled:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
-        e1.record()
-        _GemmProfile.records.append((e0, e1, 2.0 * M * N * K * nb1 * nb2, B.dtype == torch.bfloat16,
-                                     _gemm_algo_bytes(A, B, Cc, M, N, K, nb1 * nb2, residual, aux)))
+    if (A.dtype == torch.float32 and B.dtype == torch.float32 and Cc.dtype == torch.float32
+            and kw.get("nb1", 1) * kw.get("nb2", 1) == 1 and kw.get("colsum") is None and kw.get("r_mod", 0) == 0
+            and M >= 256 and N >= 64 and K >= 64 and K % 8 == 0 and _cfg.f32_split
+            and _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, **kw)):
         return Cc
+    d, _keep = _gemm_desc(lib, True, A, B, Cc, M, N, K, sa, sb, ldc, **kw)
+    if _OpCount.enabled or _GemmProfile.enabled:
+        nz = kw.get("nb1", 1) * kw.get("nb2", 1)
+        nbytes = _gemm_algo_bytes(A, B, Cc, M, N, K, nz, kw.get("residual"), kw.get("aux"))
+        if _OpCount.enabled:
+            _OpCount.add("gemm_bf16" if B.dtype == torch.bfloat16 else "gemm_f32", 2.0 * M * N * K * nz, nbytes)
+        if _GemmProfile.enabled:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
+            e1.record()
+            _GemmProfile.records.append((e0, e1, 2.0 * M * N * K * nz, B.dtype == torch.bfloat16, nbytes))
+            return Cc
     L.check(lib.segclip_gemm(C.byref(d), L.stream()), "gemm")
     return Cc
 
@@ -264,10 +263,12 @@ def _gemm_algo_bytes(A, B, Cc, M, N, K, nz, residual, aux):
                  + (M * N * aux.element_size() if aux is not None else 0))
 
 
-def _gemm_desc(lib, cuda, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act, mul_dact,
-               alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, defer, r_mod):
+def _gemm_desc(lib, cuda, A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=None, residual=None, ldr=0,
+               r_off=0, aux=None, ldaux=0, act=ACT_NONE, mul_dact=False, alpha=1.0, nb1=1, nb2=1, bsA=(0, 0),
+               bsB=(0, 0), bsC=(0, 0), bsR=None, colsum=None, aux_kind=0, defer=None, r_mod=0):
     """The descriptor of p_gemm's launch and the buffers it points into (column-sum partials, split-K workspace), which the
-    caller keeps alive; queues the deferred reductions on `defer`.  cuda = False (gemm_plan): tensors on any device."""
+    caller keeps alive; queues the deferred reductions on `defer`.  cuda = False (gemm_plan): tensors on any device.
+    This keyword list is THE keyword list of p_gemm and gemm_plan, which pass theirs on."""
     off, ptr = (_off, L.ptr) if cuda else (_addr, _addr)
     d = L.GemmDesc()
     d.A, d.B, d.C = off(A, a_off), off(B, b_off), off(Cc, c_off)
@@ -315,15 +316,14 @@ def _gemm_desc(lib, cuda, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, b
     return d, (csws, ws)
 
 
-def gemm_plan(A, B, Cc, M, N, K, sa, sb, ldc, *, a_off=0, b_off=0, c_off=0, bias=None, residual=None, ldr=0,
-              r_off=0, aux=None, ldaux=0, act=ACT_NONE, mul_dact=False, alpha=1.0, nb1=1, nb2=1, bsA=(0, 0),
-              bsB=(0, 0), bsC=(0, 0), bsR=None, colsum=None, aux_kind=0, defer=None, r_mod=0):
+def gemm_plan(A, B, Cc, M, N, K, sa, sb, ldc, **kw):
     """The route p_gemm would take with the same arguments (include/segclip_hip.h: segclip_gemm_plan), as gemm_last_route reports it
     afterwards; raises what p_gemm would raise before launching.  Nothing is launched and nothing queued on `defer`; the tensors
     may live on any device (only their addresses are read).  The config.f32_split rewrite is not applied: plan its bf16 problem."""
     lib = L.load()
-    d, _keep = _gemm_desc(lib, False, A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act,
-                          mul_dact, alpha, nb1, nb2, bsA, bsB, bsC, bsR, colsum, aux_kind, None if defer is None else _NoQueue(), r_mod)
+    if kw.get("defer") is not None:
+        kw["defer"] = _NoQueue()
+    d, _keep = _gemm_desc(lib, False, A, B, Cc, M, N, K, sa, sb, ldc, **kw)
     r = L.GemmRoute()
     L.check(lib.segclip_gemm_plan(C.byref(d), C.byref(r), None), "gemm")
     return GemmRoute(L.GEMM_ROUTE_FAMILIES[r.family], bool(r.a_ks), bool(r.b_ks), r.tile_m, r.tile_n, r.splits, r.variant)
@@ -348,12 +348,13 @@ def _split3(t, off, rows, cols, ld, stack, role):
     return out
 
 
-def _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, residual, ldr, r_off, aux, ldaux, act, mul_dact,
-                    alpha, aux_kind, defer):
+def _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, a_off=0, b_off=0, **kw):
     """config.f32_split: C = epi(A B^T) for fp32 operands as ONE bf16 GEMM of contraction length 3 K over the operands' bf16 parts
     (A: hi | lo | hi, B: hi | hi | lo along k: A_hi B_hi + A_lo B_hi + A_hi B_lo, fp32 accumulators and epilogue).  Returns False
-    when a layout or an epilogue has no bf16 kernel: the caller then takes the exact fp32 GEMM."""
+    when a layout or an epilogue has no bf16 kernel: the caller then takes the exact fp32 GEMM.  kw: p_gemm's; the operands
+    are new tensors, so the (single) problem's batch keywords do not pass on."""
     (sam, sak), (sbn, sbk) = sa, sb
+    epi = {k: v for k, v in kw.items() if k not in ("nb1", "nb2", "bsA", "bsB", "bsC", "bsR", "colsum", "r_mod")}
     if not ((sak == 1 or sam == 1) and (sbk == 1 or sbn == 1)):
         return False
     if (sak == 1 and (sam % 4 or K % 4)) or (sak != 1 and (sak % 4 or M % 4)) or (sbk == 1 and (sbn % 4 or K % 4)) or (sbk != 1 and (sbk % 4 or N % 4)):
@@ -369,8 +370,7 @@ def _gemm_f32_split(A, B, Cc, M, N, K, sa, sb, ldc, a_off, b_off, c_off, bias, r
     else:
         B3, sb3 = _split3(B, b_off, K, N, sbk, True, 1), (1, N)
     try:
-        p_gemm(A3, B3, Cc, M, N, 3 * K, sa3, sb3, ldc, c_off=c_off, bias=bias, residual=residual, ldr=ldr, r_off=r_off, aux=aux,
-               ldaux=ldaux, act=act, mul_dact=mul_dact, alpha=alpha, aux_kind=aux_kind, defer=defer)
+        p_gemm(A3, B3, Cc, M, N, 3 * K, sa3, sb3, ldc, **epi)
     except L.Unsupported:
         return False
     return True
@@ -392,15 +392,18 @@ def p_cast(t, dtype):
 
 
 def p_linear(x, w, bias=None, act=ACT_NONE, residual=None, want_aux=False, out_dtype=None, w_kn=False, aux_kind=0,
-             pitched=False):
+             pitched=False, out=None, aux_out=None):
     """y = act(x w^T + bias) + residual.  x (M,K) view; w (N,K) [or (K,N) when w_kn]; same dtype family.
-    want_aux: also return what the backward needs of the pre-activation u: u itself (aux_kind 0) or act'(u) (aux_kind 1)."""
+    want_aux: also return what the backward needs of the pre-activation u: u itself (aux_kind 0) or act'(u) (aux_kind 1).
+    out / aux_out: preallocated y (its dtype is the output dtype) / preallocated aux in the form aux_kind names."""
     M, K = x.shape
     N = w.shape[1] if w_kn else w.shape[0]
-    out_dtype = out_dtype or x.dtype
+    out_dtype = out.dtype if out is not None else (out_dtype or x.dtype)
     alloc = _empty_pitched if pitched else _empty
-    y = alloc((M, N), out_dtype, x)
-    aux = alloc((M, N), torch.uint8 if aux_kind == 2 else out_dtype, x) if (want_aux and act != ACT_NONE) else None
+    y = out if out is not None else alloc((M, N), out_dtype, x)
+    aux = None
+    if want_aux and act != ACT_NONE:
+        aux = aux_out if aux_out is not None else alloc((M, N), torch.uint8 if aux_kind == 2 else out_dtype, x)
     sb = (1, w.stride(0)) if w_kn else (w.stride(0), 1)
     try:
         p_gemm(x, w, y, M, N, K, (_ld(x), 1), sb, _ld(y), bias=bias, residual=residual,
@@ -500,14 +503,14 @@ def p_colsum(x, out=None):
     return out
 
 
-def p_ln_fwd(x, w, b, eps, out_dtype, out=None, seg=None):
+def p_ln_fwd(x, w, b, eps, out_dtype, out=None, seg=None, stats=None):
     """seg = (seg_in, seg_out, off) with out = a (n * seg_out, cols) buffer: row r of x is written to row
-    (r // seg_in) * seg_out + off + r % seg_in of out (LayerNorm into a token slice of every sample)."""
+    (r // seg_in) * seg_out + off + r % seg_in of out (LayerNorm into a token slice of every sample).
+    stats: preallocated fp32 (mean, rstd) of `rows` entries each."""
     x = x.contiguous()
     rows, cols = x.shape
     y = out if out is not None else _empty((rows, cols), out_dtype, x)
-    mean = _empty((rows,), torch.float32, x)
-    rstd = _empty((rows,), torch.float32, x)
+    mean, rstd = stats if stats is not None else (_empty((rows,), torch.float32, x), _empty((rows,), torch.float32, x))
     if _OpCount.enabled:
         _OpCount.add("ln_fwd", 0, rows * cols * (x.element_size() + y.element_size()))
     if seg is None:
@@ -988,120 +991,117 @@ class ActFn(Function):
         return dx, None
 
 
-def _resblock_fwd_exec(x2, P, B, T, n_head, causal, act, eps, klen):
+# The state of one residual block, in forward order: its parameters (also: their GradSync slots, their needs_input_grad flags,
+# their gradients) and what its forward saves for the backward (weights: in the compute dtype).  Plain tuples to autograd.
+BlockParams = collections.namedtuple("BlockParams", "ln1w ln1b wqkv bqkv wo bo ln2w ln2b wfc bfc wpr bpr")
+BlockSaved = collections.namedtuple("BlockSaved", "x ln1w mean1 rstd1 y1 wqkv qkv o stats wo x1 ln2w mean2 rstd2 y2 wfc u h wpr")
+
+
+def _block_records(kind, flat, start=0, count=None):
+    """The per-block records in a flat sequence (a stack's *params, saved_tensors or needs_input_grad from `start` on)."""
+    n = len(kind._fields)
+    count = (len(flat) - start) // n if count is None else count
+    return [kind._make(flat[start + b * n:start + (b + 1) * n]) for b in range(count)]
+
+
+def _resblock_fwd_exec(s, P, xo, B, T, n_head, causal, act, eps, klen, ak):
     """config.c_exec: the block's seven forward launches enqueued by ONE C-ABI call (segclip_resblock_fwd, csrc/exec.cpp) into
-    buffers allocated here - the same kernels with the same descriptors as the launch-by-launch path below, so results are
-    bit-identical; ~60 us of host time per block instead of ~300.  Returns None when the library has no kernel for a shape in
-    the fused form (the caller then takes the launch-by-launch path)."""
-    ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr = P
-    M, D = x2.shape
-    F4 = wfc.shape[0]
-    bf = torch.bfloat16
-    dev = x2.device
-    wqkv_c, wo_c, wfc_c, wpr_c = (wcast(w, bf) for w in (wqkv, wo, wfc, wpr))
-    ak = _aux_kind(bf, act, M, F4)
-    y1 = torch.empty((M, D), dtype=bf, device=dev)
-    y2 = torch.empty((M, D), dtype=bf, device=dev)
-    o = torch.empty((M, D), dtype=bf, device=dev)
-    qkv = torch.empty((M, 3 * D), dtype=bf, device=dev)
-    st4 = torch.empty((4, M), dtype=torch.float32, device=dev)     # mean1 | rstd1 | mean2 | rstd2
-    x1 = torch.empty((M, D), dtype=x2.dtype, device=dev)
-    xo = torch.empty((M, D), dtype=x2.dtype, device=dev)
-    h = _empty_pitched((M, F4), bf, x2)
-    u = (_empty_pitched((M, F4), torch.uint8 if ak == 2 else bf, x2)) if act != ACT_NONE else None
-    stats = torch.empty((B * n_head * T,), dtype=torch.float32, device=dev)
+    the buffers of s (BlockSaved) and xo - the same kernels with the same descriptors as the launch-by-launch path of
+    _resblock_fwd, so results are bit-identical (tests/test_block_exec_gpu.py); ~60 us of host time per block instead of ~300.
+    Returns False when the library has no kernel for one of the block's GEMMs in this form (the one-byte derivative off the
+    256 x 256 kernel): the call plans all four before its first launch, so nothing was launched, and the caller takes the
+    launch-by-launch path at the price of this one failed call."""
+    M, D = s.x.shape
     d = L.ResBlockFwdDesc()
-    d.x = x2.data_ptr()
-    d.ln1w, d.ln1b, d.wqkv, d.bqkv = ln1w.data_ptr(), ln1b.data_ptr(), wqkv_c.data_ptr(), bqkv.data_ptr()
-    d.wo, d.bo, d.ln2w, d.ln2b = wo_c.data_ptr(), bo.data_ptr(), ln2w.data_ptr(), ln2b.data_ptr()
-    d.wfc, d.bfc, d.wpr, d.bpr = wfc_c.data_ptr(), bfc.data_ptr(), wpr_c.data_ptr(), bpr.data_ptr()
-    d.y1, d.mean1, d.rstd1 = y1.data_ptr(), st4.data_ptr(), st4.data_ptr() + 4 * M
-    d.qkv, d.o, d.stats, d.x1 = qkv.data_ptr(), o.data_ptr(), stats.data_ptr(), x1.data_ptr()
-    d.y2, d.mean2, d.rstd2 = y2.data_ptr(), st4.data_ptr() + 8 * M, st4.data_ptr() + 12 * M
-    d.h, d.ld_h = h.data_ptr(), h.stride(0)
-    if u is not None:
-        d.u, d.ld_u = u.data_ptr(), u.stride(0)
+    d.x = s.x.data_ptr()
+    d.ln1w, d.ln1b, d.wqkv, d.bqkv = P.ln1w.data_ptr(), P.ln1b.data_ptr(), s.wqkv.data_ptr(), P.bqkv.data_ptr()
+    d.wo, d.bo, d.ln2w, d.ln2b = s.wo.data_ptr(), P.bo.data_ptr(), P.ln2w.data_ptr(), P.ln2b.data_ptr()
+    d.wfc, d.bfc, d.wpr, d.bpr = s.wfc.data_ptr(), P.bfc.data_ptr(), s.wpr.data_ptr(), P.bpr.data_ptr()
+    d.y1, d.mean1, d.rstd1 = s.y1.data_ptr(), s.mean1.data_ptr(), s.rstd1.data_ptr()
+    d.qkv, d.o, d.stats, d.x1 = s.qkv.data_ptr(), s.o.data_ptr(), s.stats.data_ptr(), s.x1.data_ptr()
+    d.y2, d.mean2, d.rstd2 = s.y2.data_ptr(), s.mean2.data_ptr(), s.rstd2.data_ptr()
+    d.h, d.ld_h = s.h.data_ptr(), s.h.stride(0)
+    if s.u is not None:
+        d.u, d.ld_u = s.u.data_ptr(), s.u.stride(0)
     d.xo = xo.data_ptr()
     if klen is not None:
-        if klen.dtype != torch.int32 or klen.numel() != B or not klen.is_contiguous():
-            raise TypeError("attention: klen must be a contiguous int32 tensor of B entries")
         d.klen = klen.data_ptr()
-    d.M, d.B, d.T, d.D, d.F, d.H = M, B, T, D, F4, n_head
+    d.M, d.B, d.T, d.D, d.F, d.H = M, B, T, D, s.wfc.shape[0], n_head
     d.eps, d.attn_scale = float(eps), 1.0 / math.sqrt(D // n_head)
-    d.causal, d.act, d.aux_kind, d.x_dtype = int(causal), int(act), int(ak), L.dt(x2)
+    d.causal, d.act, d.aux_kind, d.x_dtype = int(causal), int(act), int(ak), L.dt(s.x)
     try:
         L.check(L.load().segclip_resblock_fwd(C.byref(d), L.stream()), "resblock_fwd")
     except L.Unsupported:
-        return None
-    saved = (x2, ln1w, st4[0], st4[1], y1, wqkv_c, qkv, o, stats, wo_c, x1, ln2w, st4[2], st4[3], y2, wfc_c, u, h, wpr_c)
-    return xo, saved
+        return False
+    return True
 
 
 def _resblock_fwd(x2, P, B, T, n_head, causal, act, eps, act_dtype, klen):
     """One pre-LN residual block on the (B*T, D) residual stream x2 - fp32, or bf16 inside a ResStackFn running with
-    config.bf16_resid - : returns (x_out (B*T, D) in the stream's dtype, tensors saved for backward)."""
-    ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr = P
+    config.bf16_resid - : returns (x_out (B*T, D) in the stream's dtype, the BlockSaved for the backward).  The buffers and the
+    BlockSaved are built once, here; one segclip_resblock_fwd call (config.c_exec) or seven p_* launches fill them."""
+    P = BlockParams._make(P)
     M, D = x2.shape
-    hd = D // n_head
+    F4 = P.wfc.shape[0]
     for w in P:
         sl = _slot_of(w)
         if sl is not None:
             sl.note_forward_use()
-    from . import config as _cfg
-    if (act_dtype == torch.bfloat16 and _cfg.c_exec and not _OpCount.enabled and not _GemmProfile.enabled and not _cfg.attn_fp8
-            and x2.is_contiguous() and D % 8 == 0):
-        r = _resblock_fwd_exec(x2, P, B, T, n_head, causal, act, eps, klen)
-        if r is not None:
-            return r
-    y1, mean1, rstd1 = p_ln_fwd(x2, ln1w, ln1b, eps, act_dtype)
-    wqkv_c, wo_c, wfc_c, wpr_c = (wcast(w, act_dtype) for w in (wqkv, wo, wfc, wpr))
-    qkv, _ = p_linear(y1, wqkv_c, bqkv)
-    o = _empty((M, D), act_dtype, x2)
+    bf = act_dtype == torch.bfloat16
+    fp8 = bf and bool(_cfg.attn_fp8)
+    wqkv_c, wo_c, wfc_c, wpr_c = (wcast(w, act_dtype) for w in (P.wqkv, P.wo, P.wfc, P.wpr))
+    ak = _aux_kind(act_dtype, act, M, F4)
+    hidden = _empty_pitched if bf else _empty
+    y1, y2, o = (_empty((M, D), act_dtype, x2) for _ in range(3))
+    qkv = _empty((M, 3 * D), act_dtype, x2)
+    mean1, rstd1, mean2, rstd2 = _empty((4, M), torch.float32, x2).unbind(0)
+    x1, xo = _empty((M, D), x2.dtype, x2), _empty((M, D), x2.dtype, x2)
+    h = hidden((M, F4), act_dtype, x2)
+    # bf16 mode: the c_fc epilogue stores act'(u) (its exponential is already there), the c_proj dgrad multiplies by it
+    u = hidden((M, F4), torch.uint8 if ak == 2 else act_dtype, x2) if act != ACT_NONE else None
+    ad = attn_desc_packed(qkv, o, B, n_head, T, causal, klen=klen, fp8=fp8)      # (checks klen)
+    stats = _empty((max(L.load().segclip_attn_stats_bytes(C.byref(ad)) // 4, 1),), torch.float32, x2)
+    s = BlockSaved(x=x2, ln1w=P.ln1w, mean1=mean1, rstd1=rstd1, y1=y1, wqkv=wqkv_c, qkv=qkv, o=o, stats=stats, wo=wo_c, x1=x1,
+                   ln2w=P.ln2w, mean2=mean2, rstd2=rstd2, y2=y2, wfc=wfc_c, u=u, h=h, wpr=wpr_c)
+    if (bf and _cfg.c_exec and not _OpCount.enabled and not _GemmProfile.enabled and not fp8 and x2.is_contiguous() and D % 8 == 0
+            and _resblock_fwd_exec(s, P, xo, B, T, n_head, causal, act, eps, klen, ak)):
+        return xo, s
+    p_ln_fwd(x2, P.ln1w, P.ln1b, eps, act_dtype, out=y1, stats=(mean1, rstd1))
+    p_linear(y1, wqkv_c, P.bqkv, out=qkv)
     if M > B * T:                 # row-padded stack (ResStackFn): the attention kernel writes the B * T token rows only
         o[B * T:].zero_()
-    from . import config as _cfg
-    ad = attn_desc_packed(qkv, o, B, n_head, T, causal, klen=klen, fp8=bool(_cfg.attn_fp8) and act_dtype == torch.bfloat16)
-    stats = p_attn_fwd(ad, x2)
-    x1, _ = p_linear(o, wo_c, bo, residual=x2, out_dtype=x2.dtype)
-    y2, mean2, rstd2 = p_ln_fwd(x1, ln2w, ln2b, eps, act_dtype)
-    # bf16 mode: the c_fc epilogue stores act'(u) (its exponential is already there), the c_proj dgrad multiplies by it
-    h, u = p_linear(y2, wfc_c, bfc, act=act, want_aux=True, aux_kind=_aux_kind(act_dtype, act, y2.shape[0], wfc_c.shape[0]),
-                    pitched=act_dtype == torch.bfloat16)
-    xo, _ = p_linear(h, wpr_c, bpr, residual=x1, out_dtype=x2.dtype)
-    saved = (x2, ln1w, mean1, rstd1, y1, wqkv_c, qkv, o, stats, wo_c, x1, ln2w, mean2, rstd2, y2, wfc_c, u, h, wpr_c)
-    return xo, saved
-
-
-N_SAVED = 19
+    p_attn_fwd(ad, x2, stats=stats)
+    p_linear(o, wo_c, P.bo, residual=x2, out=x1)
+    p_ln_fwd(x1, P.ln2w, P.ln2b, eps, act_dtype, out=y2, stats=(mean2, rstd2))
+    _, u = p_linear(y2, wfc_c, P.bfc, act=act, want_aux=True, aux_kind=ak, pitched=bf, out=h, aux_out=u)
+    p_linear(h, wpr_c, P.bpr, residual=x1, out=xo)
+    return xo, s._replace(u=u)      # (p_linear keeps a refused one-byte derivative as bf16: the backward reads the form off u.dtype)
 
 
 def _aux_kind(act_dtype, act, M=0, N=0):
-    """What the residual blocks keep of the MLP pre-activation: act'(u) in bf16 mode with QuickGELU (the towers) - as one
-    byte per element (aux_kind 2, config.aux_u8: half the bytes of the block's largest side tensor; absolute error
-    <= 0.0025) when the GEMM runs on 256 x 256 tiles (rows a multiple of 128), else as bf16 -, u itself in the exact-f32 mode and for the
-    erf-GELU of the MAE decoders."""
-    if act_dtype == torch.bfloat16 and act == ACT_QUICK_GELU:
-        from . import config as _cfg
-        return 2 if (_cfg.aux_u8 and M > 0 and M % 128 == 0 and N % 256 == 0) else 1
-    if act_dtype == torch.bfloat16 and act == ACT_GELU_ERF:
+    """What the residual blocks keep of the MLP pre-activation in bf16 mode: act'(u), as one byte per element (aux_kind 2,
+    config.aux_u8: half the bytes of the block's largest side tensor; absolute error <= 0.0025 for QuickGELU, about 0.0065 for
+    the erf-GELU of the MAE decoders, whose derivative spans [-0.129, 1.129]) when the GEMM runs on 256 x 256 tiles (rows a
+    multiple of 128); else act'(u) as bf16 for QuickGELU and u itself for erf-GELU.  u itself in the exact-f32 mode."""
+    if act_dtype == torch.bfloat16 and act in (ACT_QUICK_GELU, ACT_GELU_ERF):
         # round 6: the MAE decoders' erf-GELU keeps the one-byte derivative as well where the 256 x 256-tile GEMM takes the shape
         # (c_fc forward 172 -> 9x us, the c_proj data gradient no longer re-evaluates erf per element: 247 -> 1xx us at M = 50432)
-        from . import config as _cfg
-        return 2 if (_cfg.aux_u8 and M > 0 and M % 128 == 0 and N % 256 == 0) else 0
+        if _cfg.aux_u8 and M > 0 and M % 128 == 0 and N % 256 == 0:
+            return 2
+        return 1 if act == ACT_QUICK_GELU else 0
     return 0
 
 
-def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, wgroup=None, rqueue=None):
-    """Hand-scheduled backward of one block.  g: fp32 (M, D) gradient of the block output or None; g16: its bf16 copy or
-    None.  need[i]: gradient wanted for forward input i (0 = x, 1..12 = the parameters in forward order).
+def _resblock_bwd(s, cfg, klen, slots, need, g, g16, chain, wgroup=None, rqueue=None):
+    """Hand-scheduled backward of one block.  s: its BlockSaved; slots: the BlockParams of the parameters' GradSync slots (or
+    None each); need: the BlockParams of "gradient wanted" flags.  g: fp32 (M, D) gradient of the block output or None; g16:
+    its bf16 copy or None.
     chain=False: fp32 residual gradient in and out (plus the bf16 copy the LayerNorm backward emits for free).
     chain=True (bf16 mode inside ResStackFn): the residual gradient travels between the LayerNorm backwards as ONE bf16
     tensor (read 2 + written 2 bytes per element instead of 4 + 4 + 2): g may be None, returns dx fp32 = None.
-    -> (dx fp32 or None, dx bf16 or None, the 12 parameter gradients)"""
-    (x2, ln1w, mean1, rstd1, y1, wqkv_c, qkv, o, stats, wo_c, x1, ln2w, mean2, rstd2, y2, wfc_c, u, h, wpr_c) = saved
+    -> (dx fp32 or None, dx bf16 or None, the parameter gradients as a BlockParams)"""
     B, T, D, n_head, causal, act, act_dtype = cfg
-    M = x2.shape[0]               # B * T, or that rounded up to 128 rows in a row-padded stack (pad rows: zero gradients)
-    hd = D // n_head
+    M = s.x.shape[0]              # B * T, or that rounded up to 128 rows in a row-padded stack (pad rows: zero gradients)
     bf = act_dtype == torch.bfloat16
     # bf16 mode: the residual-stream gradients feed the GEMMs as bf16 copies (all GEMMs then run on the LDS-DMA
     # kernels and read half the bytes); the copy of dx comes for free out of the LayerNorm backward.
@@ -1111,9 +1111,7 @@ def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, wgroup=
         g16 = g
     res_in = g16 if chain else g
     rdt = act_dtype if chain else torch.float32
-    sq, so, sf, sp = gslots  # weight gradients land directly in their all-reduce bucket (segclip_amd/dist.py)
-    F4 = wfc_c.shape[0]
-    s_ln1w, s_ln1b, s_bqkv, s_bo, s_ln2w, s_ln2b, s_bfc, s_bpr = vslots   # ... and so do the 8 vector gradients
+    F4 = s.wfc.shape[0]
 
     # the block's trailing reductions (split-K combines, LayerNorm / bias column sums) are queued and flushed as two
     # launches at the end of the block
@@ -1126,53 +1124,71 @@ def _resblock_bwd(saved, cfg, klen, gslots, vslots, need, g, g16, chain, wgroup=
         if wgroup is not None:
             return wgroup.add(dy_, x_, out_)
         return p_wgrad(dy_, x_, out=out_, defer=rq)
+
+    def vec_out(slot, wanted, n):   # a vector gradient lands directly in its all-reduce bucket (segclip_amd/dist.py), as the weights' do
+        return _slot_out(slot, (n,)) if wanted else None
     # ---- MLP
-    du, dbfc = p_dgrad(g16, wpr_c, act_dtype, aux=u, act=act, want_colsum=True,
-                       colsum_out=_slot_out(s_bfc, (F4,)) if need[10] else None,
-                       aux_kind=2 if u.dtype == torch.uint8 else _aux_kind(act_dtype, act),
+    du, dbfc = p_dgrad(g16, s.wpr, act_dtype, aux=s.u, act=act, want_colsum=True, colsum_out=vec_out(slots.bfc, need.bfc, F4),
+                       aux_kind=2 if s.u.dtype == torch.uint8 else _aux_kind(act_dtype, act),
                        defer=rq, pitched=bf)  # (dy c_proj)*act'(u), colsum
-    dwpr = wgrad(g16, h, _slot_out(sp, (D, F4))) if need[11] else None
-    dy2 = p_dgrad(du, wfc_c, act_dtype)
-    dwfc = wgrad(du, y2, _slot_out(sf, (F4, D))) if need[9] else None
+    dwpr = wgrad(g16, s.h, _slot_out(slots.wpr, (D, F4))) if need.wpr else None
+    dy2 = p_dgrad(du, s.wfc, act_dtype)
+    dwfc = wgrad(du, s.y2, _slot_out(slots.wfc, (F4, D))) if need.wfc else None
     two = bf and not chain   # fp32 dx + its bf16 copy
-    r = p_ln_bwd(dy2, x1, ln2w, mean2, rstd2, dres=res_in, dx_dtype=rdt, want_bf16=two, want_dres_colsum=True,
-                 outs=(_slot_out(s_ln2w, (D,)) if need[7] else None, _slot_out(s_ln2b, (D,)) if need[8] else None,
-                       _slot_out(s_bpr, (D,)) if need[12] else None), defer=rq)
+    r = p_ln_bwd(dy2, s.x1, s.ln2w, s.mean2, s.rstd2, dres=res_in, dx_dtype=rdt, want_bf16=two, want_dres_colsum=True,
+                 outs=(vec_out(slots.ln2w, need.ln2w, D), vec_out(slots.ln2b, need.ln2b, D), vec_out(slots.bpr, need.bpr, D)), defer=rq)
     dx1, dln2w, dln2b = r[0], r[1], r[2]
     dx1_16 = r[3] if two else dx1
-    dbpr = r[-1] if need[12] else None                           # colsum(g), fused into the LN2 backward
+    dbpr = r[-1] if need.bpr else None                           # colsum(g), fused into the LN2 backward
     # ---- attention
-    do = p_dgrad(dx1_16, wo_c, act_dtype)
-    dwo = wgrad(dx1_16, o, _slot_out(so, (D, D))) if need[5] else None
-    dqkv = _empty((M, 3 * D), act_dtype, x2)
+    do = p_dgrad(dx1_16, s.wo, act_dtype)
+    dwo = wgrad(dx1_16, s.o, _slot_out(slots.wo, (D, D))) if need.wo else None
+    dqkv = _empty((M, 3 * D), act_dtype, s.x)
     if M > B * T:
         dqkv[B * T:].zero_()      # the attention backward writes the token rows; a pad row must contribute exact zeros downstream
     s3 = (T * 3 * D, 3 * D)
-    ad = attn_desc_packed(qkv, o, B, n_head, T, causal, klen=klen)
-    part = _empty((B, 3 * D), torch.float32, x2) if (bf and need[4]) else None  # in_proj bias gradient per sample
-    p_attn_bwd(ad, stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D, colsum_part=part)
-    dy1 = p_dgrad(dqkv, wqkv_c, act_dtype)
-    dwqkv = wgrad(dqkv, y1, _slot_out(sq, (3 * D, D))) if need[3] else None
+    ad = attn_desc_packed(s.qkv, s.o, B, n_head, T, causal, klen=klen)
+    part = _empty((B, 3 * D), torch.float32, s.x) if (bf and need.bqkv) else None  # in_proj bias gradient per sample
+    p_attn_bwd(ad, s.stats, do, dqkv, dqkv, dqkv, s3, s3, s3, (T * D, D), 0, D, 2 * D, colsum_part=part)
+    dy1 = p_dgrad(dqkv, s.wqkv, act_dtype)
+    dwqkv = wgrad(dqkv, s.y1, _slot_out(slots.wqkv, (3 * D, D))) if need.wqkv else None
     dbqkv = None
-    if need[4]:
-        bq_out = _slot_out(s_bqkv, (3 * D,))
+    if need.bqkv:
+        bq_out = _slot_out(slots.bqkv, (3 * D,))
         if part is not None and (bq_out is None or bq_out.data_ptr() % 16 == 0):
             # in_proj bias gradient = token sums of dQ|dK|dV, left per sample by the attention backward: its B partial rows
             # join the block's ONE row-reduction launch (was: a column-sum launch + its reduction per block)
-            dbqkv = bq_out if bq_out is not None else _empty((3 * D,), torch.float32, x2)
+            dbqkv = bq_out if bq_out is not None else _empty((3 * D,), torch.float32, s.x)
             rq.add_rows(part, B, 3 * D, 3 * D, (dbqkv,), 3 * D)
         else:
             dbqkv = p_colsum(part if part is not None else dqkv, out=bq_out)
-    r = p_ln_bwd(dy1, x2, ln1w, mean1, rstd1, dres=dx1, dx_dtype=rdt, want_bf16=two, want_dres_colsum=True,
-                 outs=(_slot_out(s_ln1w, (D,)) if need[1] else None, _slot_out(s_ln1b, (D,)) if need[2] else None,
-                       _slot_out(s_bo, (D,)) if need[6] else None), defer=rq)
+    r = p_ln_bwd(dy1, s.x, s.ln1w, s.mean1, s.rstd1, dres=dx1, dx_dtype=rdt, want_bf16=two, want_dres_colsum=True,
+                 outs=(vec_out(slots.ln1w, need.ln1w, D), vec_out(slots.ln1b, need.ln1b, D), vec_out(slots.bo, need.bo, D)), defer=rq)
     if rqueue is None:
         rq.flush()
-    dln1w, dln1b = r[1], r[2]
-    dbo = r[-1] if need[6] else None                             # colsum(dx1), fused into the LN1 backward
+    dbo = r[-1] if need.bo else None                             # colsum(dx1), fused into the LN1 backward
     dx32 = None if chain else r[0]
     dx16 = r[0] if chain else (r[3] if two else None)
-    return dx32, dx16, (dln1w, dln1b, dwqkv, dbqkv, dwo, dbo, dln2w, dln2b, dwfc, dbfc, dwpr, dbpr)
+    return dx32, dx16, BlockParams(ln1w=r[1], ln1b=r[2], wqkv=dwqkv, bqkv=dbqkv, wo=dwo, bo=dbo, ln2w=dln2w, ln2b=dln2b, wfc=dwfc,
+                                   bfc=dbfc, wpr=dwpr, bpr=dbpr)
+
+
+def _bf16_side_copy(g):
+    """The bf16 copy of the gradient g that its producer's LayerNorm backward left on it (attribute _segclip_bf16 of the same
+    tensor object), or None: it must be of g's size, on g's device, and g contiguous, to be viewed like g."""
+    st = getattr(g, "_segclip_bf16", None)
+    if st is not None and (st.numel() != g.numel() or st.device != g.device or not g.is_contiguous()):
+        return None
+    return st
+
+
+def _pad_rows(t, Mp):
+    """(M, D) -> (Mp, D): the rows of t, then zero rows"""
+    M = t.shape[0]
+    padded = _empty((Mp, t.shape[1]), t.dtype, t)
+    padded[:M].copy_(t)
+    padded[M:].zero_()
+    return padded
 
 
 class ResBlockFn(Function):
@@ -1187,13 +1203,12 @@ class ResBlockFn(Function):
                 act_dtype, klen=None):
         B, T, D = x.shape
         x2 = x.contiguous().view(B * T, D)
-        P = (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr)
+        P = BlockParams(ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr)
         xo, saved = _resblock_fwd(x2, P, B, T, n_head, causal, act, eps, act_dtype, klen)
         ctx.save_for_backward(*saved)
         ctx.cfg = (B, T, D, n_head, causal, act, act_dtype)
         ctx.klen = klen
-        ctx.gslots = tuple(_slot_of(w) for w in (wqkv, wo, wfc, wpr))
-        ctx.vslots = tuple(_slot_of(w) for w in (ln1w, ln1b, bqkv, bo, ln2w, ln2b, bfc, bpr))
+        ctx.slots = BlockParams._make(_slot_of(w) for w in P)
         _GradFold.other[id(ln1w)] = weakref.ref(ln1w)        # a producer that does not fold: its block's gradients go the engine's way
         return xo.view(B, T, D)
 
@@ -1201,13 +1216,11 @@ class ResBlockFn(Function):
     def backward(ctx, g):
         B, T, D, n_head, causal, act, act_dtype = ctx.cfg
         M = B * T
-        st = getattr(g, "_segclip_bf16", None)  # bf16 copy left by the next block's LayerNorm backward (same object)
-        if st is not None and (st.numel() != g.numel() or st.device != g.device or not g.is_contiguous()):
-            st = None
+        st = _bf16_side_copy(g)   # left by the next block's LayerNorm backward
         g = g.contiguous().view(M, D)
         g16 = st.view(M, D) if (st is not None and act_dtype == torch.bfloat16) else None
-        dx, dx16, grads = _resblock_bwd(ctx.saved_tensors, ctx.cfg, ctx.klen, ctx.gslots, ctx.vslots,
-                                        ctx.needs_input_grad, g, g16, False)
+        (need,) = _block_records(BlockParams, ctx.needs_input_grad, start=1, count=1)     # (after x)
+        dx, dx16, grads = _resblock_bwd(BlockSaved._make(ctx.saved_tensors), ctx.cfg, ctx.klen, ctx.slots, need, g, g16, False)
         dx = dx.view(B, T, D)
         if dx16 is not None:
             dx._segclip_bf16 = dx16.view(B, T, D)
@@ -1280,14 +1293,13 @@ class ResStackFn(Function):
     when the whole stack returns, so the bucket all-reduces keep overlapping with the rest of the backward.
     inputs: x, n_head, causal, act, eps, act_dtype, klen, chain, keep16, then 12 parameters per block."""
 
-    NP = 12
+    NP = len(BlockParams._fields)
 
     @staticmethod
     def forward(ctx, x, n_head, causal, act, eps, act_dtype, klen, chain, keep16, *params):
         B, T, D = x.shape
-        nblk = len(params) // ResStackFn.NP
+        blocks = _block_records(BlockParams, params)
         cur = x.contiguous().view(B * T, D)
-        from . import config as _cfg
         # config.pad_rows (bf16 mode): a token-row count that is not a multiple of 128 (the text tower's B x 77 at any batch
         # that is not a multiple of 128 samples) keeps every GEMM of the stack off the 256 x 256-tile kernel, off the one-byte
         # derivative and - when it is not a multiple of 64 either - off the grouped weight gradients.  The stack then runs on
@@ -1295,7 +1307,7 @@ class ResStackFn(Function):
         # only touches the B * T token rows; its outputs' pad rows are zeroed), so pad rows stay finite, carry exactly zero
         # gradients and contribute exact zeros to every weight / bias gradient.
         M = B * T
-        Mp = -(-M // 128) * 128 if (act_dtype == torch.bfloat16 and bool(_cfg.pad_rows) and M % 128 != 0 and M >= _PAD_ROWS_MIN) else M
+        Mp = 128 * -(-M // 128) if (act_dtype == torch.bfloat16 and bool(_cfg.pad_rows) and M % 128 != 0 and M >= _PAD_ROWS_MIN) else M
         ctx.Mp = Mp
         # config.bf16_resid (bf16 mode): the residual stream is bf16 between the blocks of the stack (the out_proj / c_proj
         # epilogues read and write 2 instead of 4 bytes per element and run on gemm_bf16_pq.hip; every LayerNorm pass reads
@@ -1307,28 +1319,25 @@ class ResStackFn(Function):
         elif not resid16 and cur.dtype != torch.float32:
             cur = p_cast(cur, torch.float32)
         if Mp != M:
-            padded = _empty((Mp, D), cur.dtype, cur)
-            padded[:M].copy_(cur)
-            padded[M:].zero_()
-            cur = padded
+            cur = _pad_rows(cur, Mp)
         saved = []
-        for b in range(nblk):
-            cur, sv = _resblock_fwd(cur, params[b * 12:(b + 1) * 12], B, T, n_head, causal, act, eps, act_dtype, klen)
+        for P in blocks:
+            cur, sv = _resblock_fwd(cur, P, B, T, n_head, causal, act, eps, act_dtype, klen)
             saved.extend(sv)
         if Mp != M:
             cur = cur[:M]
         ctx.save_for_backward(*saved)
         ctx.cfg = (B, T, D, n_head, causal, act, act_dtype)
-        ctx.klen, ctx.nblk = klen, nblk
+        ctx.klen = klen
         ctx.chain = (bool(chain) or resid16) and act_dtype == torch.bfloat16
         ctx.wgrad_group, ctx.wgrad_group_dist = int(_cfg.wgrad_group_blocks), int(_cfg.wgrad_group_blocks_dist)
         ctx.fold = bool(_cfg.fold_param_grads) and len(params) > 0
         if ctx.fold:     # per block (the same blocks may be cut into different stacks by the two passes)
-            for b in range(nblk):
-                k = id(params[b * 12])
+            for P in blocks:
+                k = id(P.ln1w)       # (a block is known by its first parameter)
                 _GradFold.uses[k] = _GradFold.uses.get(k, 0) + 1
-        ctx.params = params
-        ctx.slots = tuple(_slot_of(w) for w in params)
+        ctx.blocks = blocks
+        ctx.slots = [BlockParams._make(_slot_of(w) for w in P) for P in blocks]
         if resid16 and not keep16:
             cur = p_cast(cur, torch.float32)
         return cur.view(B, T, D)
@@ -1336,36 +1345,32 @@ class ResStackFn(Function):
     @staticmethod
     def backward(ctx, g):
         B, T, D, n_head, causal, act, act_dtype = ctx.cfg
-        M, nblk = B * T, ctx.nblk
+        M, nblk = B * T, len(ctx.blocks)
         Mp = ctx.Mp
         bf = act_dtype == torch.bfloat16
-        st = getattr(g, "_segclip_bf16", None)
-        if st is not None and (st.numel() != g.numel() or st.device != g.device or not g.is_contiguous()):
-            st = None
+        st = _bf16_side_copy(g)
         g = g.contiguous().view(M, D)
         if Mp != M:               # row-padded stack: the gradient of a pad row is zero
             st = None
-            padded = _empty((Mp, D), g.dtype, g)
-            padded[:M].copy_(g)
-            padded[M:].zero_()
-            g, M = padded, Mp
+            g, M = _pad_rows(g, Mp), Mp
         cur16 = st.view(M, D) if (st is not None and bf) else None
         if bf and cur16 is None and g.dtype == torch.bfloat16:   # bf16 output of the node (keep16)
             cur16 = g
         if ctx.chain and cur16 is None:
             cur16 = p_cast(g, act_dtype)
         cur32 = None if ctx.chain else (g if g.dtype == torch.float32 else p_cast(g, torch.float32))
-        saved = ctx.saved_tensors
-        need_all = ctx.needs_input_grad
-        out = [None] * (nblk * 12)
+        saved = _block_records(BlockSaved, ctx.saved_tensors)
+        needs = _block_records(BlockParams, ctx.needs_input_grad, start=len(ctx.needs_input_grad) - nblk * ResStackFn.NP)
+        out = [None] * nblk       # per block: what autograd gets for its parameters
         # config.wgrad_group_blocks (captured at forward time): the weight gradients of up to that many consecutive blocks run
         # as one grouped launch (WgradGroup); with GradSync slots the groups stay short so that the bucket exchanges keep
         # overlapping with the backward pass.  A block's gradients are published when its group has been enqueued.
         wg, sizes = None, []
         if ctx.wgrad_group > 1 and ctx.cfg[-1] == torch.bfloat16 and nblk > 1:
-            Dm, F4 = ctx.params[2].shape[1], ctx.params[8].shape[0]
+            Dm, F4 = ctx.blocks[0].wqkv.shape[1], ctx.blocks[0].wfc.shape[0]
             if Dm % 256 == 0 and F4 % 256 == 0 and Mp % 64 == 0:
-                gmax = ctx.wgrad_group if all(s is None for s in ctx.slots) else min(ctx.wgrad_group, ctx.wgrad_group_dist)
+                no_slots = all(s is None for sl in ctx.slots for s in sl)
+                gmax = ctx.wgrad_group if no_slots else min(ctx.wgrad_group, ctx.wgrad_group_dist)
                 tiles_blk = (4 * Dm * Dm + 2 * F4 * Dm) // 65536
                 sizes = wgrad_group_plan(nblk, tiles_blk, Mp // 64, gmax)
                 wg = WgradGroup() if max(sizes) > 1 else None
@@ -1374,14 +1379,8 @@ class ResStackFn(Function):
         pending = []
         adds = []
         for b in reversed(range(nblk)):
-            P = ctx.params[b * 12:(b + 1) * 12]
-            sl = ctx.slots[b * 12:(b + 1) * 12]
-            need = (True,) + tuple(need_all[9 + b * 12 + i] for i in range(12))
-            gslots = (sl[2], sl[4], sl[8], sl[10])
-            vslots = (sl[0], sl[1], sl[3], sl[5], sl[6], sl[7], sl[9], sl[11])
-            cur32, cur16, grads = _resblock_bwd(saved[b * N_SAVED:(b + 1) * N_SAVED], ctx.cfg, ctx.klen, gslots, vslots,
-                                                need, cur32, cur16, ctx.chain, wg, grq)
-            pending.append((b, P, sl, grads))
+            cur32, cur16, grads = _resblock_bwd(saved[b], ctx.cfg, ctx.klen, ctx.slots[b], needs[b], cur32, cur16, ctx.chain, wg, grq)
+            pending.append((b, ctx.blocks[b], ctx.slots[b], grads))
             if wg is not None:
                 left -= 1
                 if left > 0 and b > 0:
@@ -1391,7 +1390,8 @@ class ResStackFn(Function):
                     grq.flush()
                 left = sizes.pop(0) if sizes else nblk
             for b_, P_, sl_, grads_ in pending:
-                fold = ctx.fold and _GradFold.uses.get(id(P_[0]), 0) > 1 and not _GradFold.used_elsewhere(P_[0])   # only blocks a second STACK node of this pass shares
+                fold = ctx.fold and _GradFold.uses.get(id(P_.ln1w), 0) > 1 and not _GradFold.used_elsewhere(P_.ln1w)   # only blocks a second STACK node of this pass shares
+                given = out[b_] = list(grads_)
                 for i, (p, gr, slot) in enumerate(zip(P_, grads_, sl_)):
                     if gr is None:
                         continue
@@ -1400,10 +1400,9 @@ class ResStackFn(Function):
                         # zero-copy gradient inside its all-reduce bucket: publish it now (autograd gets None for it)
                         p.grad = gr
                         owner._on_grad(p)
+                        given[i] = None
                     elif fold and slot is None:
-                        out[b_ * 12 + i] = _GradFold.take(p, gr, adds)
-                    else:
-                        out[b_ * 12 + i] = gr
+                        given[i] = _GradFold.take(p, gr, adds)
             pending = []
         _GradFold.flush(adds)
         if Mp != B * T:                      # row-padded stack: back to the token rows
@@ -1418,32 +1417,37 @@ class ResStackFn(Function):
         dx = dx.view(B, T, D)
         if cur16 is not None and dx.dtype != torch.bfloat16:
             dx._segclip_bf16 = cur16.view(B, T, D)
-        return (dx, None, None, None, None, None, None, None, None) + tuple(out)
+        return (dx, None, None, None, None, None, None, None, None) + tuple(gr for given in out for gr in given)
 
 
 def res_stack(x, blocks_params, n_head, causal, act, eps, act_dtype, klen=None, keep16=False):
     """Run consecutive residual blocks (each a 12-tuple of parameters in ResBlockFn order) as one ResStackFn node.
     keep16 (config.bf16_resid only): hand the bf16 residual stream to the caller as it is - for the next stack."""
-    from . import config as _cfg
     flat = [p for P in blocks_params for p in P]
     keep16 = bool(keep16) and bool(_cfg.bf16_resid) and act_dtype == torch.bfloat16
     return ResStackFn.apply(x, n_head, causal, act, eps, act_dtype, klen, bool(_cfg.bf16_resgrad), keep16, *flat)
 
 
-class CrossAttnFn(Function):
-    """Attention core of CrossAttentionBlock (modules/module_seg_vit.py:215): queries (B*G, D) against
-    the projected [centers; patches] buffer kv (B*S, 2D) = [K | V].
+def _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode):
+    """Cross attention of queries qp (B*G, D) against kv (B*S, 2D) = [K | V] into o: the descriptor, and the (sample, token)
+    strides of the q-side and the kv-side tensors, which p_attn_bwd takes for the gradients too.
     mode "t18": the torch-1.8 key reshape reinterprets the (B,S,D) buffer as (S,B,D): sample b attends to
     flat tokens {r*B + b} (SURVEY.md finding 0.4).  mode "intended": its own S tokens."""
+    D = qp.shape[1]
+    hd = D // n_head
+    qs = (G * D, D)
+    ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
+    return _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, qs, ks, ks, qs, 1.0 / math.sqrt(hd), False, 0, 0, D), qs, ks
+
+
+class CrossAttnFn(Function):
+    """Attention core of CrossAttentionBlock (modules/module_seg_vit.py:215): queries (B*G, D) against
+    the projected [centers; patches] buffer kv (B*S, 2D) = [K | V]; mode: see _cross_attn_desc."""
 
     @staticmethod
     def forward(ctx, qp, kv, B, G, S, n_head, mode):
-        D = qp.shape[1]
-        hd = D // n_head
         o = torch.empty_like(qp)
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd),
-                        False, 0, 0, D)
+        ad, _, _ = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         stats = p_attn_fwd(ad, qp)
         ctx.save_for_backward(qp, kv, o, stats)
         ctx.cfg = (B, G, S, n_head, mode)
@@ -1454,14 +1458,11 @@ class CrossAttnFn(Function):
         qp, kv, o, stats = ctx.saved_tensors
         B, G, S, n_head, mode = ctx.cfg
         D = qp.shape[1]
-        hd = D // n_head
         do = do.contiguous()
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd),
-                        False, 0, 0, D)
+        ad, qs, ks = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         dq = torch.empty_like(qp)
         dkv = torch.empty_like(kv)
-        p_attn_bwd(ad, stats, do, dq, dkv, dkv, (G * D, D), ks, ks, (G * D, D), 0, 0, D)
+        p_attn_bwd(ad, stats, do, dq, dkv, dkv, qs, ks, ks, qs, 0, 0, D)
         return dq, dkv, None, None, None, None, None
 
 
@@ -1476,7 +1477,6 @@ class CrossInProjAttnFn(Function):
     @staticmethod
     def forward(ctx, xq, xk, w, b, B, G, S, n_head, mode, act_dtype):
         D = w.shape[1]
-        hd = D // n_head
         xq, xk = xq.reshape(B * G, D), xk.reshape(B * S, D)
         if xq.dtype != act_dtype:
             xq = p_cast(xq, act_dtype)
@@ -1487,9 +1487,7 @@ class CrossInProjAttnFn(Function):
         qp = p_linear(xq, wc[:D], bd[:D])[0]
         kv = p_linear(xk, wc[D:], bd[D:])[0]
         o = torch.empty_like(qp)
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd),
-                        False, 0, 0, D)
+        ad, _, _ = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         stats = p_attn_fwd(ad, qp)
         ctx.save_for_backward(xq, xk, wc, qp, kv, o, stats)
         ctx.cfg = (B, G, S, n_head, mode)
@@ -1501,15 +1499,12 @@ class CrossInProjAttnFn(Function):
         xq, xk, wc, qp, kv, o, stats = ctx.saved_tensors
         B, G, S, n_head, mode = ctx.cfg
         D = qp.shape[1]
-        hd = D // n_head
         do = do.contiguous()
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd),
-                        False, 0, 0, D)
+        ad, qs, ks = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         dq = torch.empty_like(qp)
         dkv = torch.empty_like(kv)
         part = _empty((B, 3 * D), torch.float32, do) if qp.dtype == torch.bfloat16 else None
-        p_attn_bwd(ad, stats, do, dq, dkv, dkv, (G * D, D), ks, ks, (G * D, D), 0, 0, D, colsum_part=part)
+        p_attn_bwd(ad, stats, do, dq, dkv, dkv, qs, ks, ks, qs, 0, 0, D, colsum_part=part)
         dxq = p_dgrad(dq, wc[:D], xq.dtype)
         dxk = p_dgrad(dkv, wc[D:], xk.dtype)
         dw = _slot_out(ctx.gslot, (3 * D, D))
@@ -1544,7 +1539,7 @@ class CrossBlockFn(Function):
                 n_head, mode, eps, act_dtype):
         B, G, D = q.shape
         S = kn_buf.shape[1]
-        M, hd, F4 = B * G, D // n_head, wfc.shape[0]
+        M, F4 = B * G, wfc.shape[0]
         act = ACT_QUICK_GELU
         for w in (lnxw, lnxb, lnkw, lnkb, w_in, b_in, wo, bo, ln2w, ln2b, wfc, bfc, wpr, bpr):
             sl = _slot_of(w)
@@ -1560,8 +1555,7 @@ class CrossBlockFn(Function):
         qp = p_linear(qn, wc[:D], bd[:D])[0]
         kv = p_linear(kn2d, wc[D:], bd[D:])[0]
         o = torch.empty_like(qp)
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd), False, 0, 0, D)
+        ad, _, _ = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         stats = p_attn_fwd(ad, qp)
         q1 = p_linear(o, wo_c, bo, residual=q2d, out_dtype=torch.float32)[0]
         z, m2, r2 = p_ln_fwd(q1, ln2w, ln2b, eps[2], act_dtype)
@@ -1580,7 +1574,7 @@ class CrossBlockFn(Function):
          wpr_c) = ctx.saved_tensors
         B, G, S, D, n_head, mode, act, act_dtype = ctx.cfg
         kn2d = kn_buf.detach().view(B * S, D)
-        M, hd, F4 = B * G, D // n_head, wfc_c.shape[0]
+        M, F4 = B * G, wfc_c.shape[0]
         bf = act_dtype == torch.bfloat16
         s_in, s_o, s_fc, s_pr = ctx.gslots
         g = dq2.contiguous().view(M, D)
@@ -1609,11 +1603,10 @@ class CrossBlockFn(Function):
         # ---- attention
         do = p_dgrad(dq1_16, wo_c, act_dtype)
         dwo = small_wgrad(dq1_16, o, _slot_out(s_o, (D, D)))
-        ks = (2 * D, B * 2 * D) if mode == "t18" else (S * 2 * D, 2 * D)
-        ad = _attn_desc(qp, kv, kv, o, B, n_head, G, S, hd, (G * D, D), ks, ks, (G * D, D), 1.0 / math.sqrt(hd), False, 0, 0, D)
+        ad, qs, ks = _cross_attn_desc(qp, kv, o, B, G, S, n_head, mode)
         dqp, dkv = torch.empty_like(qp), torch.empty_like(kv)
         part = _empty((B, 3 * D), torch.float32, do) if bf else None
-        p_attn_bwd(ad, stats, do, dqp, dkv, dkv, (G * D, D), ks, ks, (G * D, D), 0, 0, D, colsum_part=part)
+        p_attn_bwd(ad, stats, do, dqp, dkv, dkv, qs, ks, ks, qs, 0, 0, D, colsum_part=part)
         dqn = p_dgrad(dqp, wc[:D], act_dtype)
         dkn = p_dgrad(dkv, wc[D:], act_dtype)
         dw_in = _slot_out(s_in, (3 * D, D))

@@ -51,16 +51,16 @@ def test_planned_routes_cover_every_instance():
     assert not sorted(set(INSTANCES) - seen)
 
 
-# ops.p_gemm's keyword defaults: ops._gemm_desc, the part of p_gemm that fills the descriptor, takes them all
-DEFAULTS = dict(a_off=0, b_off=0, c_off=0, bias=None, residual=None, ldr=0, r_off=0, aux=None, ldaux=0, act=ops.ACT_NONE,
-                mul_dact=False, alpha=1.0, nb1=1, nb2=1, bsA=(0, 0), bsB=(0, 0), bsC=(0, 0), bsR=None, colsum=None, aux_kind=0,
-                defer=None, r_mod=0)
-
-
 def desc(*args, **kw):
     """the descriptor ops.gemm_plan plans for a call, and what keeps its buffers alive"""
-    d, keep = ops._gemm_desc(L.load(), False, *args, **dict(DEFAULTS, **kw))
+    d, keep = ops._gemm_desc(L.load(), False, *args, **kw)
     return d, (keep, args, kw)
+
+
+def test_unknown_keyword_is_a_type_error():
+    x, w, y = torch.empty(64, 64, dtype=BF), torch.empty(64, 64, dtype=BF), torch.empty(64, 64, dtype=BF)
+    with pytest.raises(TypeError, match="no_such_keyword"):
+        ops.gemm_plan(x, w, y, 64, 64, 64, (64, 1), (64, 1), 64, no_such_keyword=1)
 
 
 def desc_of(case, ws="exact"):

@@ -18,8 +18,8 @@ blocks = [params() for _ in range(NB)]
 x = torch.randn(B * T, D, device=dev)
 g = torch.randn(B * T, D, device=dev).to(BF)
 cfg = lambda b: (b, T, D, H, False, ops.ACT_QUICK_GELU, BF)
-none4, none8 = (None,) * 4, (None,) * 8
-need = (True,) * 13
+no_slots = ops.BlockParams._make((None,) * len(ops.BlockParams._fields))
+need = ops.BlockParams._make((True,) * len(ops.BlockParams._fields))
 
 def pipeline(xh, gh, b):
     cur, saved = xh, []
@@ -28,7 +28,7 @@ def pipeline(xh, gh, b):
         saved.append(sv)
     g16 = gh
     for sv in reversed(saved):
-        _, g16, _ = ops._resblock_bwd(sv, cfg(b), None, none4, none8, need, None, g16, True)
+        _, g16, _ = ops._resblock_bwd(sv, cfg(b), None, no_slots, need, None, g16, True)
     return g16
 
 def full():
