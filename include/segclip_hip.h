@@ -840,6 +840,16 @@ int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, i
                            int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
                            int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
                            uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
+/* segclip_seg_components_wide: the definition above for 16-bit label maps (those of segclip_seg_label_map_rescaled_wide), with
+ * "byte" read as "16-bit value".  labels and cleaned are flat uint16 (an int16 tensor is read as unsigned); labels_n, cleaned_n,
+ * px_count and the table's offsets count ELEMENTS.  skip_label is in -1..65535 and fill in 0..65535: 65535 and every value with
+ * the top bit set are labels like any other.  Column 2 of a record carries the 16-bit label.  The same table, the same
+ * device-side range checks, the same refusals with these ranges.  The workspace holds no labels: it is
+ * segclip_seg_components_ws_bytes(labels_n, B, n_blocks). */
+int segclip_seg_components_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* labels,
+                                int64_t labels_n, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                                int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                                uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Despeckling by merging (segment_sieve.inc): every small connected component of a label map takes the label of its largest
@@ -885,6 +895,15 @@ int64_t segclip_seg_sieve_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_bl
 int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
                       int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill, int rounds,
                       uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream);
+/* segclip_seg_sieve_wide: the definition above for 16-bit label maps, with "byte" read as "16-bit value".  labels and cleaned
+ * are flat uint16 (an int16 tensor is read as unsigned); labels_n, cleaned_n and the table's offsets count ELEMENTS.  The winner
+ * is the maximum of (area << 16) | (65535 - label) over all contacts (an area is below 2^30: 46 bits; zero remains "no contact").
+ * skip_label and orphan_fill are in -1..65535.  The same table, the same device-side range checks, the same refusals with these
+ * ranges.  ws: segclip_seg_sieve_wide_ws_bytes(labels_n, B, n_blocks) bytes = 22 per pixel (2 for the map between two rounds). */
+int64_t segclip_seg_sieve_wide_ws_bytes(int64_t labels_n, int64_t B, int64_t n_blocks);
+int segclip_seg_sieve_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* labels,
+                           int64_t labels_n, int connectivity, int skip_label, int64_t min_area, int orphan_fill, int rounds,
+                           uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Boundary metrics of label maps (segment_boundary.inc): the boundary bands of a prediction and a ground truth, and the
@@ -945,6 +964,16 @@ int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int
                          int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
                          int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws, int64_t ws_bytes,
                          void* stream);
+/* segclip_seg_boundary_wide: the definition above for 16-bit label maps, with "byte" read as "16-bit value" for M, q and g.
+ * pred and gt are BOTH flat uint16 (an int16 tensor is read as unsigned) of pred_n / gt_n ELEMENTS, which the table's offsets
+ * count too; the bands stay one byte per pixel, with the layout of pred / gt.  1 <= C <= SEGCLIP_SEG_WIDE_MAX_CLASSES (the
+ * counters are 24 KB of LDS, which only this entry pays for) and ignore_index in 0..65535: SEGCLIP_ERR_UNSUPPORTED otherwise,
+ * nothing launched and nothing written.  The same table, the same device-side range checks, every other refusal as above.
+ * ws: segclip_seg_boundary_ws_bytes(pred_n, gt_n) bytes (2 per element). */
+int segclip_seg_boundary_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* pred,
+                              int64_t pred_n, const uint16_t* gt, int64_t gt_n, int64_t C, int ignore_index,
+                              int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws,
+                              int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Confusion matrix of label maps (segment_confusion.inc): which class the pixels of a class went to.  THE REFERENCE HAS NO

@@ -917,6 +917,9 @@ extern "C" int segclip_seg_refine(const int64_t* images, int64_t B, int64_t n_bl
 }
 
 // ---------------------------------------------------------------- connected components (segment_objects.inc)
+// The entries of the three post-processing stages exist for uint8_t and uint16_t labels: one body each, a template on the label
+// element L.  Sizes and offsets count elements; a workspace part that holds labels has sizeof(L) bytes per pixel.
+// What differs between the two is SegLabel<L> (segment_objects.inc); the uint8 entries keep their messages word for word.
 struct SegCCWs { int64_t parent, root, area, rank, seg, part, total; };
 static SegCCWs seg_cc_ws(int64_t n, int64_t n_blocks) {
   const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
@@ -937,43 +940,46 @@ extern "C" int64_t segclip_seg_components_ws_bytes(int64_t labels_bytes, int64_t
   return seg_cc_ws(labels_bytes, n_blocks).total;
 }
 
-extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
-                                      int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
-                                      int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
-                                      uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+// `what`: the entry's name in messages; labels_bytes, cleaned_bytes: ELEMENTS of L (the uint8 entry's argument names)
+template <class L>
+static int seg_components_run(const char* what, const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const L* labels,
+                              int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                              int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                              L* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  const char* unit = SegLabel<L>::unit;
   SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_bytes >= 0 && px_count >= 0 && K >= 0 && cleaned_bytes >= 0 && ws_bytes >= 0,
-                  "seg_components: sizes must not be negative");
-  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "seg_components: size out of range");
-  SEGCLIP_REQUIRE(!records || count, "seg_components: records need count, the number of rows that exist");
+                  "%s: sizes must not be negative", what);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "%s: size out of range", what);
+  SEGCLIP_REQUIRE(!records || count, "%s: records need count, the number of rows that exist", what);
   SEGCLIP_REQUIRE(!(ids || area_px) || px_count == labels_bytes,
-                  "seg_components: ids and area_px have one entry per label byte: %lld, got %lld", (long long)labels_bytes,
+                  "%s: ids and area_px have one entry per label%s: %lld, got %lld", what, sizeof(L) == 1 ? " byte" : "", (long long)labels_bytes,
                   (long long)px_count);
-  SEGCLIP_REQUIRE(!cleaned || cleaned_bytes == labels_bytes, "seg_components: cleaned has the layout of labels: %lld bytes, got %lld",
-                  (long long)labels_bytes, (long long)cleaned_bytes);
+  SEGCLIP_REQUIRE(!cleaned || cleaned_bytes == labels_bytes, "%s: cleaned has the layout of labels: %lld %s, got %lld", what,
+                  (long long)labels_bytes, unit, (long long)cleaned_bytes);
   SEGCLIP_REQUIRE(!cleaned || !labels || cleaned + cleaned_bytes <= labels || labels + labels_bytes <= cleaned,
-                  "seg_components: cleaned overlaps labels (the despeckling is out of place)");
-  SEG_REFUSE(connectivity != 4 && connectivity != 8, "seg_components: connectivity is 4 or 8, got %d", connectivity);
-  SEG_REFUSE(skip_label < -1 || skip_label > 255, "seg_components: skip_label is a byte or -1, got %d", skip_label);
-  SEG_REFUSE(fill < 0 || fill > 255, "seg_components: fill is a byte, got %d", fill);
-  SEG_REFUSE(min_area < 0, "seg_components: min_area must not be negative, got %lld", (long long)min_area);
-  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_components: sides of 1..%d pixels supported, got a bound of %lld",
+                  "%s: cleaned overlaps labels (the despeckling is out of place)", what);
+  SEG_REFUSE(connectivity != 4 && connectivity != 8, "%s: connectivity is 4 or 8, got %d", what, connectivity);
+  SEG_REFUSE(skip_label < -1 || skip_label > SegLabel<L>::TOP, "%s: skip_label is %s or -1, got %d", what, SegLabel<L>::word, skip_label);
+  SEG_REFUSE(fill < 0 || fill > SegLabel<L>::TOP, "%s: fill is %s, got %d", what, SegLabel<L>::word, fill);
+  SEG_REFUSE(min_area < 0, "%s: min_area must not be negative, got %lld", what, (long long)min_area);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "%s: sides of 1..%d pixels supported, got a bound of %lld", what,
              SEG_CC_LIMIT - 1, (long long)max_side);
   const SegCCWs w = seg_cc_ws(labels_bytes, n_blocks);
-  SEG_REFUSE(ws_bytes < w.total, "seg_components: the workspace has %lld bytes, segclip_seg_components_ws_bytes asks for %lld",
+  SEG_REFUSE(ws_bytes < w.total, "%s: the workspace has %lld bytes, segclip_seg_components_ws_bytes asks for %lld", what,
              (long long)ws_bytes, (long long)w.total);
   if (B == 0 || n_blocks == 0) {
     if (count) {
       const hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), ST);
-      SEGCLIP_REQUIRE(e == hipSuccess, "seg_components: clearing count failed: %s", hipGetErrorString(e));
+      SEGCLIP_REQUIRE(e == hipSuccess, "%s: clearing count failed: %s", what, hipGetErrorString(e));
     }
     return 0;
   }
-  SEGCLIP_REQUIRE(images && labels, "seg_components: images and labels are required");
-  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_components: the workspace is required, 16-byte aligned");
+  SEGCLIP_REQUIRE(images && labels, "%s: images and labels are required", what);
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace is required, 16-byte aligned", what);
   if (!ids && !area_px && !count && !cleaned) return 0;  // nothing asked for
 
   SegCCArgs a;
-  a.images = images; a.labels = labels; a.labels_bytes = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
+  a.images = images; a.labels = labels; a.labels_n = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
   a.B = (int)B; a.max_side = (int)max_side; a.conn8 = connectivity == 8; a.skip = skip_label;
   char* base = static_cast<char*>(ws);
   a.seg = reinterpret_cast<int64_t*>(base + w.seg);
@@ -984,15 +990,15 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
   a.area_px = area_px; a.records = records; a.K = records ? K : 0; a.min_area = min_area; a.fill = fill; a.cleaned = cleaned;
 
   const dim3 grid((unsigned)n_blocks), block(256);
-  hipLaunchKernelGGL(seg_cc_local_kernel, grid, block, 0, ST, a);
+  hipLaunchKernelGGL(seg_cc_local_kernel<L>, grid, block, 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_components (local)");
-  hipLaunchKernelGGL(seg_cc_merge_kernel, grid, block, 0, ST, a);
+  hipLaunchKernelGGL(seg_cc_merge_kernel<L>, grid, block, 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_components (merge)");
   if (count) {
     // the entries of a table row that the device skips, and those past an image's last row, count nothing
     const hipError_t e = hipMemsetAsync(a.seg, 0, (size_t)a.n_seg * sizeof(int64_t), ST);
-    SEGCLIP_REQUIRE(e == hipSuccess, "seg_components: clearing the segment counts failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(seg_cc_roots_kernel<false>, grid, block, 0, ST, a);
+    SEGCLIP_REQUIRE(e == hipSuccess, "%s: clearing the segment counts failed: %s", what, hipGetErrorString(e));
+    hipLaunchKernelGGL((seg_cc_roots_kernel<false, L>), grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_components (count)");
     int64_t* part = reinterpret_cast<int64_t*>(base + w.part);
     const int64_t chunks = cdiv(a.n_seg, SEG_CC_SCAN_CHUNK);
@@ -1003,7 +1009,7 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
     hipLaunchKernelGGL(seg_cc_chunk_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, ST, a.seg, a.n_seg, part);
     SEGCLIP_CHECK_LAUNCH("seg_components (chunk scans)");
     if (records && K > 0) {
-      hipLaunchKernelGGL(seg_cc_roots_kernel<true>, grid, block, 0, ST, a);
+      hipLaunchKernelGGL((seg_cc_roots_kernel<true, L>), grid, block, 0, ST, a);
       SEGCLIP_CHECK_LAUNCH("seg_components (rank)");
     }
   }
@@ -1011,15 +1017,33 @@ extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t 
   else hipLaunchKernelGGL(seg_cc_stats_kernel<false>, grid, block, 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_components (stats)");
   if (area_px || cleaned) {
-    hipLaunchKernelGGL(seg_cc_final_kernel, grid, block, 0, ST, a);
+    hipLaunchKernelGGL(seg_cc_final_kernel<L>, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_components (final)");
   }
   return 0;
 }
 
+extern "C" int segclip_seg_components(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                                      int64_t labels_bytes, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                                      int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                                      uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_components_run<uint8_t>("seg_components", images, B, n_blocks, max_side, labels, labels_bytes, connectivity, skip_label, ids,
+                                     area_px, px_count, records, K, count, min_area, fill, cleaned, cleaned_bytes, ws, ws_bytes, stream);
+}
+
+// The workspace holds no labels: the size is segclip_seg_components_ws_bytes of the element count, and there is no wide query.
+extern "C" int segclip_seg_components_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* labels,
+                                           int64_t labels_n, int connectivity, int skip_label, int32_t* ids, int32_t* area_px,
+                                           int64_t px_count, int64_t* records, int64_t K, int64_t* count, int64_t min_area, int fill,
+                                           uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_components_run<uint16_t>("seg_components_wide", images, B, n_blocks, max_side, labels, labels_n, connectivity, skip_label,
+                                      ids, area_px, px_count, records, K, count, min_area, fill, cleaned, cleaned_n, ws, ws_bytes, stream);
+}
+
 // ---------------------------------------------------------------- despeckling by merging (segment_sieve.inc)
 struct SegSieveWs { int64_t slot, parent, root, area, tmp, total; };
-static SegSieveWs seg_sieve_ws(int64_t n) {
+// n pixels; the map between two rounds has `width` bytes per pixel
+static SegSieveWs seg_sieve_ws(int64_t n, int64_t width) {
   const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
   SegSieveWs w;
   w.slot = 0;
@@ -1027,43 +1051,54 @@ static SegSieveWs seg_sieve_ws(int64_t n) {
   w.root = w.parent + up(n * 4);
   w.area = w.root + up(n * 4);
   w.tmp = w.area + up(n * 4);
-  w.total = w.tmp + up(n);
+  w.total = w.tmp + up(n * width);
   return w;
 }
 
 extern "C" int64_t segclip_seg_sieve_ws_bytes(int64_t labels_bytes, int64_t B, int64_t n_blocks) {
   SEG_REFUSE(labels_bytes < 0 || labels_bytes > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31),
              "seg_sieve_ws_bytes: need 0 <= labels_bytes <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
-  return seg_sieve_ws(labels_bytes).total;
+  return seg_sieve_ws(labels_bytes, 1).total;
 }
 
-extern "C" int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
-                                 int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill,
-                                 int rounds, uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+extern "C" int64_t segclip_seg_sieve_wide_ws_bytes(int64_t labels_n, int64_t B, int64_t n_blocks) {
+  SEG_REFUSE(labels_n < 0 || labels_n > (1ll << 40) || B < 0 || B > (1 << 24) || n_blocks < 0 || n_blocks >= (1ll << 31),
+             "seg_sieve_wide_ws_bytes: need 0 <= labels_n <= 2^40, 0 <= B <= 2^24 and 0 <= n_blocks < 2^31");
+  return seg_sieve_ws(labels_n, 2).total;
+}
+
+// `what`: the entry's name in messages; labels_bytes, cleaned_bytes: ELEMENTS of L (the uint8 entry's argument names)
+template <class L>
+static int seg_sieve_run(const char* what, const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const L* labels,
+                         int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill, int rounds,
+                         L* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  const char* unit = SegLabel<L>::unit;
   SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_bytes >= 0 && cleaned_bytes >= 0 && ws_bytes >= 0,
-                  "seg_sieve: sizes must not be negative");
-  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "seg_sieve: size out of range");
-  SEGCLIP_REQUIRE(cleaned_bytes == labels_bytes, "seg_sieve: cleaned has the layout of labels: %lld bytes, got %lld",
-                  (long long)labels_bytes, (long long)cleaned_bytes);
+                  "%s: sizes must not be negative", what);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_bytes <= (1ll << 40), "%s: size out of range", what);
+  SEGCLIP_REQUIRE(cleaned_bytes == labels_bytes, "%s: cleaned has the layout of labels: %lld %s, got %lld", what,
+                  (long long)labels_bytes, unit, (long long)cleaned_bytes);
   SEGCLIP_REQUIRE(!cleaned || !labels || cleaned + cleaned_bytes <= labels || labels + labels_bytes <= cleaned,
-                  "seg_sieve: cleaned overlaps labels (the despeckling is out of place)");
-  SEG_REFUSE(connectivity != 4 && connectivity != 8, "seg_sieve: connectivity is 4 or 8, got %d", connectivity);
-  SEG_REFUSE(skip_label < -1 || skip_label > 255, "seg_sieve: skip_label is a byte or -1, got %d", skip_label);
-  SEG_REFUSE(orphan_fill < -1 || orphan_fill > 255, "seg_sieve: orphan_fill is a byte or -1, got %d", orphan_fill);
-  SEG_REFUSE(rounds < 1 || rounds > SEG_SIEVE_MAX_ROUNDS, "seg_sieve: 1..%d rounds supported, got %d", SEG_SIEVE_MAX_ROUNDS, rounds);
-  SEG_REFUSE(min_area < 0, "seg_sieve: min_area must not be negative, got %lld", (long long)min_area);
-  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "seg_sieve: sides of 1..%d pixels supported, got a bound of %lld",
+                  "%s: cleaned overlaps labels (the despeckling is out of place)", what);
+  SEG_REFUSE(connectivity != 4 && connectivity != 8, "%s: connectivity is 4 or 8, got %d", what, connectivity);
+  SEG_REFUSE(skip_label < -1 || skip_label > SegLabel<L>::TOP, "%s: skip_label is %s or -1, got %d", what,
+             SegLabel<L>::word, skip_label);
+  SEG_REFUSE(orphan_fill < -1 || orphan_fill > SegLabel<L>::TOP, "%s: orphan_fill is %s or -1, got %d", what,
+             SegLabel<L>::word, orphan_fill);
+  SEG_REFUSE(rounds < 1 || rounds > SEG_SIEVE_MAX_ROUNDS, "%s: 1..%d rounds supported, got %d", what, SEG_SIEVE_MAX_ROUNDS, rounds);
+  SEG_REFUSE(min_area < 0, "%s: min_area must not be negative, got %lld", what, (long long)min_area);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_CC_LIMIT, "%s: sides of 1..%d pixels supported, got a bound of %lld", what,
              SEG_CC_LIMIT - 1, (long long)max_side);
-  const SegSieveWs w = seg_sieve_ws(labels_bytes);
-  SEG_REFUSE(ws_bytes < w.total, "seg_sieve: the workspace has %lld bytes, segclip_seg_sieve_ws_bytes asks for %lld",
-             (long long)ws_bytes, (long long)w.total);
+  const SegSieveWs w = seg_sieve_ws(labels_bytes, (int64_t)sizeof(L));
+  SEG_REFUSE(ws_bytes < w.total, "%s: the workspace has %lld bytes, segclip_%s_ws_bytes asks for %lld", what,
+             (long long)ws_bytes, what, (long long)w.total);
   if (B == 0 || n_blocks == 0) return 0;
-  SEGCLIP_REQUIRE(images && labels && cleaned, "seg_sieve: images, labels and cleaned are required");
-  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_sieve: the workspace is required, 16-byte aligned");
+  SEGCLIP_REQUIRE(images && labels && cleaned, "%s: images, labels and cleaned are required", what);
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace is required, 16-byte aligned", what);
 
   SegSieveArgs s;
   SegCCArgs& a = s.cc;
-  a.images = images; a.labels_bytes = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
+  a.images = images; a.labels_n = labels_bytes; a.n_blocks = n_blocks; a.n_seg = n_blocks * SEG_CC_TH;
   a.B = (int)B; a.max_side = (int)max_side; a.conn8 = connectivity == 8; a.skip = skip_label;
   char* base = static_cast<char*>(ws);
   a.seg = nullptr; a.rank = nullptr; a.area_px = nullptr; a.records = nullptr; a.K = 0; a.fill = 0; a.cleaned = nullptr;
@@ -1072,31 +1107,46 @@ extern "C" int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blo
   a.area = reinterpret_cast<int32_t*>(base + w.area);
   a.min_area = min_area;
   s.slot = reinterpret_cast<unsigned long long*>(base + w.slot);
-  uint8_t* tmp = reinterpret_cast<uint8_t*>(base + w.tmp);
+  L* tmp = reinterpret_cast<L*>(base + w.tmp);
 
   // round r reads what round r - 1 wrote; the outputs alternate so that the last round's is `cleaned`.  A kernel touches the
-  // pixels of the table's images only, so the bytes between the maps are read and written by none.
+  // pixels of the table's images only, so the labels between the maps are read and written by none.
   const dim3 grid((unsigned)n_blocks), block(256);
-  const uint8_t* in = labels;
+  const L* in = labels;
   for (int r = 1; r <= rounds; ++r) {
     a.labels = in;
-    s.out = (rounds - r) % 2 == 0 ? cleaned : tmp;
+    L* out = (rounds - r) % 2 == 0 ? cleaned : tmp;
+    s.out = out;
     s.orphan = r == rounds ? orphan_fill : -1;
     const hipError_t e = hipMemsetAsync(s.slot, 0, (size_t)labels_bytes * sizeof(unsigned long long), ST);
-    SEGCLIP_REQUIRE(e == hipSuccess, "seg_sieve: clearing the slots failed: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(seg_cc_local_kernel, grid, block, 0, ST, a);
+    SEGCLIP_REQUIRE(e == hipSuccess, "%s: clearing the slots failed: %s", what, hipGetErrorString(e));
+    hipLaunchKernelGGL(seg_cc_local_kernel<L>, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_sieve (local)");
-    hipLaunchKernelGGL(seg_cc_merge_kernel, grid, block, 0, ST, a);
+    hipLaunchKernelGGL(seg_cc_merge_kernel<L>, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_sieve (merge)");
     hipLaunchKernelGGL(seg_cc_stats_kernel<false>, grid, block, 0, ST, a);
     SEGCLIP_CHECK_LAUNCH("seg_sieve (stats)");
-    hipLaunchKernelGGL(seg_sieve_vote_kernel, grid, block, 0, ST, s);
+    hipLaunchKernelGGL(seg_sieve_vote_kernel<L>, grid, block, 0, ST, s);
     SEGCLIP_CHECK_LAUNCH("seg_sieve (vote)");
-    hipLaunchKernelGGL(seg_sieve_final_kernel, grid, block, 0, ST, s);
+    hipLaunchKernelGGL(seg_sieve_final_kernel<L>, grid, block, 0, ST, s);
     SEGCLIP_CHECK_LAUNCH("seg_sieve (final)");
-    in = s.out;
+    in = out;
   }
   return 0;
+}
+
+extern "C" int segclip_seg_sieve(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* labels,
+                                 int64_t labels_bytes, int connectivity, int skip_label, int64_t min_area, int orphan_fill,
+                                 int rounds, uint8_t* cleaned, int64_t cleaned_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_sieve_run<uint8_t>("seg_sieve", images, B, n_blocks, max_side, labels, labels_bytes, connectivity, skip_label, min_area,
+                                orphan_fill, rounds, cleaned, cleaned_bytes, ws, ws_bytes, stream);
+}
+
+extern "C" int segclip_seg_sieve_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* labels,
+                                      int64_t labels_n, int connectivity, int skip_label, int64_t min_area, int orphan_fill,
+                                      int rounds, uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_sieve_run<uint16_t>("seg_sieve_wide", images, B, n_blocks, max_side, labels, labels_n, connectivity, skip_label, min_area,
+                                 orphan_fill, rounds, cleaned, cleaned_n, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
@@ -1116,48 +1166,73 @@ extern "C" int64_t segclip_seg_boundary_ws_bytes(int64_t pred_bytes, int64_t gt_
   return seg_bd_ws(pred_bytes, gt_bytes).total;
 }
 
-static bool seg_bd_overlap(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb) {
+// byte ranges
+static bool seg_bd_overlap(const void* pa, int64_t na, const void* pb, int64_t nb) {
+  const char* a = static_cast<const char*>(pa);
+  const char* b = static_cast<const char*>(pb);
   return a && b && na > 0 && nb > 0 && a < b + nb && b < a + na;
 }
 
-extern "C" int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* pred,
-                                    int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
-                                    int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws,
-                                    int64_t ws_bytes, void* stream) {
+// `what`: the entry's name in messages; pred_bytes, gt_bytes: ELEMENTS of L (the uint8 entry's argument names).  The bands are
+// bytes, one per element.
+template <class L>
+static int seg_boundary_run(const char* what, const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const L* pred,
+                            int64_t pred_bytes, const L* gt, int64_t gt_bytes, int64_t C, int ignore_index, int reduce_zero_label,
+                            uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws, int64_t ws_bytes, void* stream) {
+  constexpr int64_t EL = (int64_t)sizeof(L);
   SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && pred_bytes >= 0 && gt_bytes >= 0 && ws_bytes >= 0 && C >= 1,
-                  "seg_boundary: sizes must not be negative, and C >= 1");
+                  "%s: sizes must not be negative, and C >= 1", what);
   SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && pred_bytes <= (1ll << 40) && gt_bytes <= (1ll << 40),
-                  "seg_boundary: size out of range");
-  SEGCLIP_REQUIRE(!areas || gt, "seg_boundary: areas need gt");
-  SEGCLIP_REQUIRE(!gt_band || gt, "seg_boundary: gt_band needs gt");
-  SEGCLIP_REQUIRE(!seg_bd_overlap(pred_band, pred_bytes, pred, pred_bytes) && !seg_bd_overlap(pred_band, pred_bytes, gt, gt_bytes) &&
-                      !seg_bd_overlap(gt_band, gt_bytes, pred, pred_bytes) && !seg_bd_overlap(gt_band, gt_bytes, gt, gt_bytes) &&
+                  "%s: size out of range", what);
+  SEGCLIP_REQUIRE(!areas || gt, "%s: areas need gt", what);
+  SEGCLIP_REQUIRE(!gt_band || gt, "%s: gt_band needs gt", what);
+  SEGCLIP_REQUIRE(!seg_bd_overlap(pred_band, pred_bytes, pred, pred_bytes * EL) && !seg_bd_overlap(pred_band, pred_bytes, gt, gt_bytes * EL) &&
+                      !seg_bd_overlap(gt_band, gt_bytes, pred, pred_bytes * EL) && !seg_bd_overlap(gt_band, gt_bytes, gt, gt_bytes * EL) &&
                       !seg_bd_overlap(pred_band, pred_bytes, gt_band, gt_bytes),
-                  "seg_boundary: a band output overlaps an input or the other band");
-  SEG_REFUSE(C > SEG_MAX_CLASSES, "seg_boundary: %lld classes, at most %d", (long long)C, SEG_MAX_CLASSES);
-  SEG_REFUSE(max_side < 1 || max_side >= SEG_BD_LIMIT, "seg_boundary: sides of 1..%d pixels supported, got a bound of %lld",
+                  "%s: a band output overlaps an input or the other band", what);
+  SEG_REFUSE(C > SegLabel<L>::MAX_CLASSES, "%s: %lld classes, at most %d", what, (long long)C, SegLabel<L>::MAX_CLASSES);
+  // the uint8 entry has always taken any ignore_index (one outside 0..255 ignores nothing)
+  SEG_REFUSE(EL == 2 && (ignore_index < 0 || ignore_index > 65535), "%s: ignore_index is a 16-bit value, got %d", what, ignore_index);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_BD_LIMIT, "%s: sides of 1..%d pixels supported, got a bound of %lld", what,
              SEG_BD_LIMIT - 1, (long long)max_side);
   const SegBdWs w = seg_bd_ws(pred_bytes, gt_bytes);
-  SEG_REFUSE(ws_bytes < w.total, "seg_boundary: the workspace has %lld bytes, segclip_seg_boundary_ws_bytes asks for %lld",
+  SEG_REFUSE(ws_bytes < w.total, "%s: the workspace has %lld bytes, segclip_seg_boundary_ws_bytes asks for %lld", what,
              (long long)ws_bytes, (long long)w.total);
   if (B == 0 || n_blocks == 0) return 0;
-  SEGCLIP_REQUIRE(images && pred, "seg_boundary: images and pred are required");
-  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_boundary: the workspace is required, 16-byte aligned");
+  SEGCLIP_REQUIRE(images && pred, "%s: images and pred are required", what);
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace is required, 16-byte aligned", what);
   if (!pred_band && !gt_band && !areas) return 0;  // nothing asked for
 
   SegBdArgs a;
-  a.images = images; a.pred = pred; a.gt = gt; a.pred_bytes = pred_bytes; a.gt_bytes = gt ? gt_bytes : 0; a.n_blocks = n_blocks;
+  a.images = images; a.pred = pred; a.gt = gt; a.pred_n = pred_bytes; a.gt_n = gt ? gt_bytes : 0; a.n_blocks = n_blocks;
   a.B = (int)B; a.max_side = (int)max_side; a.C = (int)C; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
   a.pred_band = pred_band; a.gt_band = gt_band; a.areas = reinterpret_cast<unsigned long long*>(areas);
   char* base = static_cast<char*>(ws);
   a.pred_s = reinterpret_cast<uint16_t*>(base + w.pred_s);
   a.gt_s = reinterpret_cast<uint16_t*>(base + w.gt_s);
   const dim3 grid((unsigned)n_blocks), block(256);
-  hipLaunchKernelGGL(seg_bd_rows_kernel, grid, block, 0, ST, a);
+  hipLaunchKernelGGL(seg_bd_rows_kernel<L>, grid, block, 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_boundary (rows)");
-  hipLaunchKernelGGL(seg_bd_band_kernel, grid, block, 0, ST, a);
+  hipLaunchKernelGGL(seg_bd_band_kernel<L>, grid, block, 0, ST, a);
   SEGCLIP_CHECK_LAUNCH("seg_boundary (bands)");
   return 0;
+}
+
+extern "C" int segclip_seg_boundary(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint8_t* pred,
+                                    int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, int64_t C, int ignore_index,
+                                    int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+  return seg_boundary_run<uint8_t>("seg_boundary", images, B, n_blocks, max_side, pred, pred_bytes, gt, gt_bytes, C, ignore_index,
+                                   reduce_zero_label, pred_band, gt_band, areas, ws, ws_bytes, stream);
+}
+
+// The workspace is segclip_seg_boundary_ws_bytes of the element counts (2 bytes per element of pred and of gt).
+extern "C" int segclip_seg_boundary_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, const uint16_t* pred,
+                                         int64_t pred_n, const uint16_t* gt, int64_t gt_n, int64_t C, int ignore_index,
+                                         int reduce_zero_label, uint8_t* pred_band, uint8_t* gt_band, int64_t* areas, void* ws,
+                                         int64_t ws_bytes, void* stream) {
+  return seg_boundary_run<uint16_t>("seg_boundary_wide", images, B, n_blocks, max_side, pred, pred_n, gt, gt_n, C, ignore_index,
+                                    reduce_zero_label, pred_band, gt_band, areas, ws, ws_bytes, stream);
 }
 
 extern "C" int segclip_train_images_from_u8(const int64_t* images, int64_t B, int64_t out_h, int64_t out_w, const float* lut, float* out,

@@ -12,6 +12,9 @@
 //                        consecutive pixels of a lane counted once) and added with one global atomic per touched counter.
 // Work per pixel: the rows pass O(1), the band pass (SEG_BD_SH + 2 d) / SEG_BD_SH row visits of one byte and two uint16, all
 // coalesced across the lanes.  Integer sums: the result depends on no schedule.
+// The kernels are templates on the label element L of pred AND gt: uint8_t, or uint16_t for 16-bit label maps (an int16 tensor
+// read as unsigned).  The bands stay one byte per pixel.  What follows L: the run key (32 bits hold two bytes and the flags, two
+// 16-bit values need 64), the class limit and with it the counters in LDS (6 x 256 ints, or 6 x 1024 = 24 KB for uint16_t only).
 
 #define SEG_BD_COLS SEGCLIP_SEG_BOUNDARY_COLS            // int64 columns of one image row of the table (segclip_hip.h)
 #define SEG_BD_SH SEGCLIP_SEG_BOUNDARY_TILE_H             // rows of a wave's strip
@@ -24,9 +27,9 @@ static_assert(SEG_BD_TW == SEGCLIP_WAVE && SEG_BD_LIMIT <= 65536, "seg_bd: a row
 
 struct SegBdArgs {
   const int64_t* images;       // (B, SEG_BD_COLS)
-  const uint8_t* pred;         // flat
-  const uint8_t* gt;           // flat, or null
-  int64_t pred_bytes, gt_bytes, n_blocks;
+  const void* pred;            // flat, elements of L
+  const void* gt;              // flat, or null
+  int64_t pred_n, gt_n, n_blocks;   // elements of pred and of gt
   int B, max_side, C, ignore_index, reduce_zero;
   uint8_t* pred_band;          // at pred's offsets, or null
   uint8_t* gt_band;            // at gt's offsets, or null
@@ -49,10 +52,10 @@ __device__ __forceinline__ SegBdImage seg_bd_image(const SegBdArgs& A, int img) 
   I.strips_x = (I.w + SEG_BD_TW - 1) / SEG_BD_TW;
   I.strips = I.strips_x * ((I.h + SEG_BD_SH - 1) / SEG_BD_SH);
   I.blocks = (I.strips + SEG_BD_WAVES - 1) / SEG_BD_WAVES;
-  I.ok = I.ok && I.poff >= 0 && I.poff <= A.pred_bytes - px && blk >= 0 && blk <= A.n_blocks - I.blocks;
+  I.ok = I.ok && I.poff >= 0 && I.poff <= A.pred_n - px && blk >= 0 && blk <= A.n_blocks - I.blocks;
   // without a ground truth to read the column is not looked at; -1 = this map has none
   I.has_gt = A.gt && (A.gt_band || A.areas) && I.goff != -1;
-  if (I.has_gt && !(I.goff >= 0 && I.goff <= A.gt_bytes - px)) I.ok = false;
+  if (I.has_gt && !(I.goff >= 0 && I.goff <= A.gt_n - px)) I.ok = false;
   const int64_t t = (int64_t)blockIdx.x - blk;
   if (t < 0 || t >= I.blocks) I.ok = false;
   I.t = I.ok ? (int)t : 0;
@@ -69,7 +72,8 @@ __device__ __forceinline__ SegBdImage seg_bd_image(const SegBdArgs& A, int img) 
   const int lane = tid & 63, wv = tid >> 6;
 
 // ---------------------------------------------------------------- label changes along a row, counted from its left end
-__device__ __forceinline__ void seg_bd_scan_row(const uint8_t* __restrict__ m, uint16_t* __restrict__ s, int w, int lane) {
+template <class L>
+__device__ __forceinline__ void seg_bd_scan_row(const L* __restrict__ m, uint16_t* __restrict__ s, int w, int lane) {
   int carry = 0, last = 0;
   for (int x0 = 0; x0 < w; x0 += SEG_BD_TW) {  // wave-uniform
     const int x = x0 + lane;
@@ -85,21 +89,25 @@ __device__ __forceinline__ void seg_bd_scan_row(const uint8_t* __restrict__ m, u
 }
 
 // The image's SEG_BD_WAVES * blocks waves share its rows round robin.
+template <class L>
 __global__ __launch_bounds__(256) void seg_bd_rows_kernel(SegBdArgs A) {
   SEG_BD_PROLOGUE(A)
+  const L* pred = static_cast<const L*>(A.pred);
+  const L* gt = static_cast<const L*>(A.gt);
   const int waves = SEG_BD_WAVES * I.blocks;
   for (int y = SEG_BD_WAVES * I.t + wv; y < I.h; y += waves) {
     const int64_t row = (int64_t)y * I.w;
-    seg_bd_scan_row(A.pred + I.poff + row, A.pred_s + I.poff + row, I.w, lane);
-    if (I.has_gt) seg_bd_scan_row(A.gt + I.goff + row, A.gt_s + I.goff + row, I.w, lane);
+    seg_bd_scan_row(pred + I.poff + row, A.pred_s + I.poff + row, I.w, lane);
+    if (I.has_gt) seg_bd_scan_row(gt + I.goff + row, A.gt_s + I.goff + row, I.w, lane);
   }
 }
 
 // ---------------------------------------------------------------- bands and areas
 // What a lane remembers of its column above the row it has read last: the last row whose row part is not constant, the last
-// row whose byte differs from the row above it, and the byte of the last row.
+// row whose label differs from the row above it, and the label of the last row.
 struct SegBdColumn { int bad, change, byte; };
-__device__ __forceinline__ void seg_bd_visit(const uint8_t* __restrict__ m, const uint16_t* __restrict__ s, int64_t row, int y,
+template <class L>
+__device__ __forceinline__ void seg_bd_visit(const L* __restrict__ m, const uint16_t* __restrict__ s, int64_t row, int y,
                                              int x, int xl, int xr, bool first, SegBdColumn& c) {
   const int b = m[row + x];
   if (s[row + xl] != s[row + xr]) c.bad = y;
@@ -107,22 +115,28 @@ __device__ __forceinline__ void seg_bd_visit(const uint8_t* __restrict__ m, cons
   c.byte = b;
 }
 
-// key: q | g << 8 | (bp != 0) << 16 | (bg != 0) << 17 | (bg & 1) << 18, for n pixels.  The ground-truth rule is seg_area_add's.
-__device__ __forceinline__ void seg_bd_count(int* cnt, int C, int key, int n, int ignore_index, int reduce_zero) {
-  const int q = key & 255;
-  int g = (key >> 8) & 255;
+// key: q | g << BITS | (bp != 0) << 2 BITS | (bg != 0) << (2 BITS + 1) | (bg & 1) << (2 BITS + 2), for n pixels.  The
+// ground-truth rule is seg_area_add's.
+template <class L>
+__device__ __forceinline__ void seg_bd_count(int* cnt, int C, typename SegLabel<L>::key_t key, int n, int ignore_index,
+                                             int reduce_zero) {
+  typedef typename SegLabel<L>::key_t key_t;
+  constexpr int BITS = SegLabel<L>::BITS;
+  constexpr key_t ONE = 1;
+  const int q = (int)(key & ((ONE << BITS) - 1));
+  int g = (int)((key >> BITS) & ((ONE << BITS) - 1));
   if (g == ignore_index) return;
   if (reduce_zero) {
     if (g == 0) return;
     g -= 1;
   }
-  const bool in_p = key & (1 << 16), in_g = key & (1 << 17);
+  const bool in_p = key & (ONE << (2 * BITS)), in_g = key & (ONE << (2 * BITS + 1));
   if (q < C && in_p) atomicAdd(&cnt[C + q], n);
   if (g < C && in_g) {
     atomicAdd(&cnt[2 * C + g], n);
     if (q == g && in_p) atomicAdd(&cnt[q], n);
   }
-  if (key & (1 << 18)) {
+  if (key & (ONE << (2 * BITS + 2))) {
     int* tri = cnt + 3 * C;
     if (q < C) atomicAdd(&tri[C + q], n);
     if (g < C) {
@@ -132,8 +146,11 @@ __device__ __forceinline__ void seg_bd_count(int* cnt, int C, int key, int n, in
   }
 }
 
+template <class L>
 __global__ __launch_bounds__(256) void seg_bd_band_kernel(SegBdArgs A) {
-  __shared__ int s_cnt[6 * SEG_MAX_CLASSES];
+  typedef typename SegLabel<L>::key_t key_t;
+  constexpr int BITS = SegLabel<L>::BITS;
+  __shared__ int s_cnt[6 * SegLabel<L>::MAX_CLASSES];
   SEG_BD_PROLOGUE(A)
   const int C = A.C;
   const bool count = A.areas && I.has_gt;  // block-uniform
@@ -150,14 +167,15 @@ __global__ __launch_bounds__(256) void seg_bd_band_kernel(SegBdArgs A) {
     const int x = in ? xs : w - 1;  // a lane past the row reads its last column and writes nothing
     const int xl = max(0, x - d), xr = min(w - 1, x + d);
     const bool frame_x = x < d || x >= w - d;
-    const uint8_t* pm = A.pred + I.poff;
+    const L* pm = static_cast<const L*>(A.pred) + I.poff;
     const uint16_t* ps = A.pred_s + I.poff;
-    const uint8_t* gm = I.has_gt ? A.gt + I.goff : pm;
+    const L* gm = I.has_gt ? static_cast<const L*>(A.gt) + I.goff : pm;
     const uint16_t* gs = I.has_gt ? A.gt_s + I.goff : ps;
     SegBdColumn P = {-1, -1, 0}, G = {-1, -1, 0};
     const int top = max(0, ya - d);  // the first row any window of this strip reaches: its own change lies outside all of them
     int seen = top - 1;
-    int run_key = -1, run_n = 0;
+    key_t run_key = -1;
+    int run_n = 0;
     for (int y = ya; y < yb; ++y) {
       const int ylo = max(0, y - d), yhi = min(h - 1, y + d);
       while (seen < yhi) {  // wave-uniform; 2 d + 1 rows at most before the strip's first pixel, then one per pixel
@@ -174,15 +192,16 @@ __global__ __launch_bounds__(256) void seg_bd_band_kernel(SegBdArgs A) {
       const int bg = ((G.bad >= ylo || G.change > ylo) ? 1 : 0) | frame;
       if (in && A.gt_band) A.gt_band[I.goff + at] = (uint8_t)bg;
       if (!count || !in) continue;
-      const int key = pm[at] | gm[at] << 8 | (bp != 0) << 16 | (bg != 0) << 17 | (bg & 1) << 18;
+      const key_t key = (key_t)pm[at] | (key_t)gm[at] << BITS | (key_t)(bp != 0) << (2 * BITS) | (key_t)(bg != 0) << (2 * BITS + 1) |
+                        (key_t)(bg & 1) << (2 * BITS + 2);
       if (key == run_key) {
         ++run_n;
       } else {
-        if (run_n) seg_bd_count(s_cnt, C, run_key, run_n, A.ignore_index, A.reduce_zero);
+        if (run_n) seg_bd_count<L>(s_cnt, C, run_key, run_n, A.ignore_index, A.reduce_zero);
         run_key = key; run_n = 1;
       }
     }
-    if (run_n) seg_bd_count(s_cnt, C, run_key, run_n, A.ignore_index, A.reduce_zero);
+    if (run_n) seg_bd_count<L>(s_cnt, C, run_key, run_n, A.ignore_index, A.reduce_zero);
   }
   if (count) {
     __syncthreads();

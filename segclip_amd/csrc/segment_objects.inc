@@ -20,6 +20,9 @@
 // the schedule and whatever the memory holds, and no workgroup ever waits for another.
 // Traffic per pixel with every output: local 1 B read + 8 written, roots 2 x 4 read, stats 4 read + 4 written, final 8-9 read +
 // 5 written; the merge touches the rims only.
+// The kernels that read or write labels are templates on the label element L: uint8_t, or uint16_t for the maps of
+// SegInference(label_dtype=torch.int16) (an int16 tensor read as unsigned).  A label enters only through equality, the record's
+// label column and `cleaned`; with uint16_t a label read or written is one byte more, everything else is the same code.
 
 #define SEG_CC_COLS SEGCLIP_SEG_CC_COLS   // int64 columns of one image row of the table (segclip_hip.h)
 #define SEG_CC_TH SEGCLIP_SEG_CC_TILE_H
@@ -31,10 +34,32 @@
 enum { CC_H, CC_W, CC_OFF, CC_BLK };
 static_assert(SEG_CC_TW == SEGCLIP_WAVE && SEG_CC_TH % 4 == 0 && 2 * (SEG_CC_TW + SEG_CC_TH) <= 256, "seg_cc tile");
 
+// What follows the label element, stated once for the three files and their host entries (segment.hip):
+//   tile_t      : a tile's labels in LDS (seg_cc_local_kernel): every label value and -1, which no label equals
+//   key_t       : the boundary kernel's run key, q | g << BITS | flags << 2 BITS (segment_boundary.inc)
+//   BITS, TOP   : of a label in the sieve's and the boundary's keys; TOP is the largest label
+//   MAX_CLASSES : of the boundary areas (the counters in LDS)
+//   word, unit  : how the host entries' messages call a label value and the elements of a label buffer
+template <class L> struct SegLabel;
+template <> struct SegLabel<uint8_t> {
+  typedef short tile_t;
+  typedef int key_t;
+  static constexpr int BITS = 8, TOP = 255, MAX_CLASSES = SEG_MAX_CLASSES;
+  static constexpr const char* word = "a byte";
+  static constexpr const char* unit = "bytes";
+};
+template <> struct SegLabel<uint16_t> {
+  typedef int tile_t;
+  typedef long long key_t;
+  static constexpr int BITS = 16, TOP = 65535, MAX_CLASSES = SEG_WIDE_MAX_CLASSES;
+  static constexpr const char* word = "a 16-bit value";
+  static constexpr const char* unit = "elements";
+};
+
 struct SegCCArgs {
   const int64_t* images;     // (B, SEG_CC_COLS)
-  const uint8_t* labels;     // flat input labels
-  int64_t labels_bytes, n_blocks, n_seg;
+  const void* labels;        // flat input labels, elements of L
+  int64_t labels_n, n_blocks, n_seg;   // labels_n: elements of `labels`
   int B, max_side, conn8, skip;
   // per pixel, at the labels' offsets
   int32_t* parent;           // in-image index of an ancestor, -1 for a skipped pixel
@@ -47,8 +72,10 @@ struct SegCCArgs {
   int64_t K;
   int64_t min_area;
   int fill;
-  uint8_t* cleaned;
+  void* cleaned;             // elements of L
 };
+template <class L> __device__ __forceinline__ const L* seg_cc_labels(const SegCCArgs& A) { return static_cast<const L*>(A.labels); }
+
 
 // One tile of one image, range-checked: the host entry cannot inspect device memory.
 struct SegCCTile { int img, h, w, y0, x0, th, tw, tiles_x, tx; int64_t off, seg0; bool ok; };
@@ -61,7 +88,7 @@ __device__ __forceinline__ SegCCTile seg_cc_tile(const SegCCArgs& A, int img) {
   T.h = T.ok ? (int)h : 1; T.w = T.ok ? (int)w : 1;
   T.tiles_x = (T.w + SEG_CC_TW - 1) / SEG_CC_TW;
   const int tiles = T.tiles_x * ((T.h + SEG_CC_TH - 1) / SEG_CC_TH);
-  T.ok = T.ok && T.off >= 0 && T.off <= A.labels_bytes - (int64_t)T.h * T.w && blk >= 0 && blk <= A.n_blocks - tiles;
+  T.ok = T.ok && T.off >= 0 && T.off <= A.labels_n - (int64_t)T.h * T.w && blk >= 0 && blk <= A.n_blocks - tiles;
   const int64_t t = (int64_t)blockIdx.x - blk;
   if (t < 0 || t >= tiles) T.ok = false;
   const int ty = T.ok ? (int)t / T.tiles_x : 0;
@@ -114,18 +141,20 @@ __device__ __forceinline__ void seg_cc_union(int* p, int a, int b) {
   if (!T.ok) return; /* block-uniform */
 
 // ---------------------------------------------------------------- the tile in LDS
+template <class L>
 __global__ __launch_bounds__(256) void seg_cc_local_kernel(SegCCArgs A) {
+  typedef typename SegLabel<L>::tile_t tile_t;
   __shared__ int s_par[SEG_CC_PIX];
-  __shared__ short s_lab[SEG_CC_PIX];
+  __shared__ tile_t s_lab[SEG_CC_PIX];
   SEG_CC_PROLOGUE(A)
-  const uint8_t* lab = A.labels + T.off;
+  const L* lab = seg_cc_labels<L>(A) + T.off;
 #pragma unroll
   for (int k = 0; k < SEG_CC_PIX / 256; ++k) {
     const int i = tid + 256 * k, ly = i / SEG_CC_TW, lx = i % SEG_CC_TW;
     int b = -1;
     if (ly < T.th && lx < T.tw) b = lab[(T.y0 + ly) * T.w + T.x0 + lx];
     if (b == A.skip) b = -1;
-    s_lab[i] = (short)b;
+    s_lab[i] = (tile_t)b;
     // a tile row is one wave: a pixel starts under the first pixel of its horizontal run, so no union goes sideways
     const int before = __shfl_up(b, 1, 64);
     const unsigned long long starts = __ballot(lx == 0 || before != b);
@@ -168,6 +197,7 @@ __global__ __launch_bounds__(256) void seg_cc_local_kernel(SegCCArgs A) {
 // Every adjacent pair of pixels has one forward direction, and both pixels of a pair that crosses tiles lie on a rim: the rim
 // pixels looking forward see every such pair once.  A lane whose (own root, neighbour's root) pair equals its predecessor's in
 // the same direction, or its own in an earlier direction, leaves the union to that one: a rim inside one component costs one.
+template <class L>
 __global__ __launch_bounds__(256) void seg_cc_merge_kernel(SegCCArgs A) {
   SEG_CC_PROLOGUE(A)
   int ly = -1, lx = 0;
@@ -180,7 +210,7 @@ __global__ __launch_bounds__(256) void seg_cc_merge_kernel(SegCCArgs A) {
   }
   bool act = ly >= 0 && ly < T.th && lx < T.tw;
   const int y = T.y0 + ly, x = T.x0 + lx;
-  const uint8_t* lab = A.labels + T.off;
+  const L* lab = seg_cc_labels<L>(A) + T.off;
   int* par = A.parent + T.off;
   int b = -1, ra = -1;
   if (act) {
@@ -212,7 +242,7 @@ __global__ __launch_bounds__(256) void seg_cc_merge_kernel(SegCCArgs A) {
 }
 
 // ---------------------------------------------------------------- roots per row segment: count, then rank
-template <bool RANK>
+template <bool RANK, class L>
 __global__ __launch_bounds__(256) void seg_cc_roots_kernel(SegCCArgs A) {
   SEG_CC_PROLOGUE(A)
   const int lane = tid & 63, wv = tid >> 6;
@@ -231,7 +261,7 @@ __global__ __launch_bounds__(256) void seg_cc_roots_kernel(SegCCArgs A) {
       A.rank[T.off + idx] = row ? (int)rank : -1;
       if (row) {
         int64_t* R = A.records + 10 * rank;
-        R[0] = T.img; R[1] = idx; R[2] = A.labels[T.off + idx]; R[3] = 0;
+        R[0] = T.img; R[1] = idx; R[2] = seg_cc_labels<L>(A)[T.off + idx]; R[3] = 0;
         R[4] = SEG_CC_LIMIT; R[5] = SEG_CC_LIMIT; R[6] = 0; R[7] = 0; R[8] = 0; R[9] = 0;
       }
     }
@@ -399,8 +429,11 @@ __global__ __launch_bounds__(256) void seg_cc_stats_kernel(SegCCArgs A) {
 }
 
 // ---------------------------------------------------------------- area per pixel, despeckled labels
+template <class L>
 __global__ __launch_bounds__(256) void seg_cc_final_kernel(SegCCArgs A) {
   SEG_CC_PROLOGUE(A)
+  const L* lab = seg_cc_labels<L>(A);
+  L* cleaned = static_cast<L*>(A.cleaned);
 #pragma unroll
   for (int k = 0; k < SEG_CC_PIX / 256; ++k) {
     const int i = tid + 256 * k, ly = i / SEG_CC_TW, lx = i % SEG_CC_TW;
@@ -410,6 +443,6 @@ __global__ __launch_bounds__(256) void seg_cc_final_kernel(SegCCArgs A) {
     const bool in_image = r >= 0 && r < T.h * T.w;
     const int a = in_image ? A.area[T.off + r] : 0;
     if (A.area_px) A.area_px[at] = a;
-    if (A.cleaned) A.cleaned[at] = in_image && a < A.min_area ? (uint8_t)A.fill : A.labels[at];
+    if (cleaned) cleaned[at] = in_image && a < A.min_area ? (L)A.fill : lab[at];
   }
 }

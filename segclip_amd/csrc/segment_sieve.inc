@@ -7,6 +7,8 @@
 //                            stats kernel) and reach the component's slot, at its root, with ONE global 64-bit atomicMax per
 //                            such pair.  A component that spans tiles collects the contacts of all of them there.
 //   seg_sieve_final_kernel : a small pixel takes 255 - (slot & 255), or the orphan rule where the slot is still zero
+// Both are templates on the label element L (segment_objects.inc): with uint16_t the key is (area << 16) | (65535 - label) and
+// the winner 65535 - (slot & 65535).  An area is below 2^30, so the key fits 46 bits; zero remains "no contact".
 // The maximum of integers depends on no order: two calls give the same bits.  No loop depends on memory contents and no
 // workgroup waits for another.
 // Traffic per pixel and round beyond the three component kernels: 8 B of slot cleared; vote 4 B of root + the gathered area (4 B
@@ -19,10 +21,11 @@
 struct SegSieveArgs {
   SegCCArgs cc;                  // labels = the round's input; parent, root and area as the component kernels left them
   unsigned long long* slot;      // per pixel, at the labels' offsets: at a small root the largest key of its contacts, else 0
-  uint8_t* out;                  // the round's output, laid out like the labels
-  int orphan;                    // the byte of a small component without a candidate, or -1: its own
+  void* out;                     // the round's output, laid out like the labels (elements of L)
+  int orphan;                    // the label of a small component without a candidate, or -1: its own
 };
 
+template <class L>
 __global__ __launch_bounds__(256) void seg_sieve_vote_kernel(SegSieveArgs S) {
   __shared__ unsigned long long s_vote[SEG_CC_PIX];
   __shared__ int s_root[SEG_CC_PIX];
@@ -32,7 +35,7 @@ __global__ __launch_bounds__(256) void seg_sieve_vote_kernel(SegSieveArgs S) {
   for (int k = 0; k < SEG_CC_PIX / 256; ++k) s_vote[tid + 256 * k] = 0ull;
   __syncthreads();
   const int n = T.h * T.w;
-  const uint8_t* lab = A.labels + T.off;
+  const L* lab = seg_cc_labels<L>(A) + T.off;
   const int* root = A.root + T.off;
   const int* area = A.area + T.off;
 #pragma unroll
@@ -51,7 +54,7 @@ __global__ __launch_bounds__(256) void seg_sieve_vote_kernel(SegSieveArgs S) {
       if (rq < 0 || rq >= n || rq == r) continue;
       const int aq = area[rq];
       if (aq < A.min_area) continue;
-      const unsigned long long key = ((unsigned long long)(unsigned)aq << 8) | (unsigned)(255 - lab[q]);
+      const unsigned long long key = ((unsigned long long)(unsigned)aq << SegLabel<L>::BITS) | (unsigned)(SegLabel<L>::TOP - lab[q]);
       best = key > best ? key : best;
     }
     if (best == 0ull) continue;
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(256) void seg_sieve_vote_kernel(SegSieveArgs S) {
   }
 }
 
+template <class L>
 __global__ __launch_bounds__(256) void seg_sieve_final_kernel(SegSieveArgs S) {
   const SegCCArgs& A = S.cc;
   SEG_CC_PROLOGUE(A)
@@ -84,12 +88,12 @@ __global__ __launch_bounds__(256) void seg_sieve_final_kernel(SegSieveArgs S) {
     if (ly >= T.th || lx >= T.tw) continue;
     const int64_t at = T.off + (T.y0 + ly) * T.w + T.x0 + lx;
     const int r = A.root[at];
-    int b = A.labels[at];
+    int b = seg_cc_labels<L>(A)[at];
     if (r >= 0 && r < n && A.area[T.off + r] < A.min_area) {
       const unsigned long long v = S.slot[T.off + r];
-      if (v != 0ull) b = 255 - (int)(v & 255ull);
+      if (v != 0ull) b = SegLabel<L>::TOP - (int)(v & (unsigned long long)SegLabel<L>::TOP);
       else if (S.orphan >= 0) b = S.orphan;
     }
-    S.out[at] = (uint8_t)b;
+    static_cast<L*>(S.out)[at] = (L)b;
   }
 }

@@ -2942,6 +2942,13 @@ def seg_refine(table, n_blocks, labels, num_classes, dilations, iters, mean, inv
 
 
 # ---------------------------------------------------------------- connected components of label maps (segment_objects.inc)
+def _seg_label_width(what, labels, name="labels"):
+    """Components, sieve and boundary take label maps of either width: -> True for int16 (the wide entries), False for uint8."""
+    if labels.dtype not in (torch.uint8, torch.int16) or not labels.is_contiguous():
+        raise ValueError(f"{what}: {name} is a contiguous uint8 or int16 tensor")
+    return labels.dtype == torch.int16
+
+
 SEG_CC_TILE = (L.const("SEG_CC_TILE_H"), L.const("SEG_CC_TILE_W"))  # (TH, TW): rows x columns of one workgroup's tile of segclip_seg_components
 SEG_CC_COLS = L.const("SEG_CC_COLS")  # int64 columns of one row of its image table
 SEG_CC_RECORD = L.const("SEG_CC_RECORD")  # int64 columns of a record: image, id, label, area, y0, x0, y1, x1, sum of y, sum of x
@@ -2966,18 +2973,19 @@ def seg_components_table(sizes, offsets, device):
 
 def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids=None, area_px=None, records=None, count=None,
                    min_area=0, fill=0, cleaned=None, max_side=None):
-    """Connected components of the flat uint8 `labels` under the table of seg_components_table (segclip_seg_components; the
-    definition stands in include/segclip_hip.h).  Every output is optional and written where given: ids / area_px flat int32
-    with one entry per label byte, records (K, 10) int64 with count (1,) int64 (count alone is allowed), cleaned flat uint8 of
-    the labels' size (it may not overlap them): fill where a component has fewer than min_area pixels.  skip_label: a byte whose
-    pixels belong to no component.  max_side: the largest h or w of the table (defaults to the limit).  No host
-    synchronisation.  -> None."""
+    """Connected components of the flat uint8 or int16 `labels` under the table of seg_components_table (segclip_seg_components
+    / segclip_seg_components_wide by the dtype; the definition stands in include/segclip_hip.h).  An int16 tensor holds the
+    16-bit label maps of SegInference(label_dtype=torch.int16) and is read as unsigned 16-bit values.  Every output is optional
+    and written where given: ids / area_px flat int32 with one entry per label, records (K, 10) int64 with count (1,) int64
+    (count alone is allowed), cleaned flat, of the labels' dtype and size (it may not overlap them): fill where a component has
+    fewer than min_area pixels.  skip_label: a value whose pixels belong to no component.  skip_label and fill are in 0 .. 255
+    for uint8 labels and 0 .. 65535 for int16 labels.  max_side: the largest h or w of the table (defaults to the limit).  No
+    host synchronisation.  -> None."""
     L.require_cuda(table, labels, ids, area_px, records, count, cleaned)
     _check_image_table("seg_components", table, SEG_CC_COLS, "seg_components_table")
-    if labels.dtype != torch.uint8 or not labels.is_contiguous():
-        raise ValueError("seg_components: labels is a contiguous uint8 tensor")
+    wide = _seg_label_width("seg_components", labels)
     for name, t, dt in (("ids", ids, torch.int32), ("area_px", area_px, torch.int32), ("records", records, torch.int64),
-                        ("count", count, torch.int64), ("cleaned", cleaned, torch.uint8)):
+                        ("count", count, torch.int64), ("cleaned", cleaned, labels.dtype)):
         if t is not None and (t.dtype != dt or not t.is_contiguous()):
             raise ValueError(f"seg_components: {name} is a contiguous {dt} tensor")
     if records is not None and (records.dim() != 2 or records.shape[1] != SEG_CC_RECORD):
@@ -2991,7 +2999,7 @@ def seg_components(table, n_blocks, labels, connectivity=8, skip_label=None, ids
     lib = L.load()
     ws_bytes = lib.segclip_seg_components_ws_bytes(labels.numel(), B, int(n_blocks))
     ws = _workspace("seg_components", ws_bytes, labels.device, 16)
-    L.check(lib.segclip_seg_components(
+    L.check((lib.segclip_seg_components_wide if wide else lib.segclip_seg_components)(
         L.ptr(table), B, int(n_blocks), _max_side(max_side), L.ptr(labels), labels.numel(),
         int(connectivity), -1 if skip_label is None else int(skip_label), L.ptr(ids), L.ptr(area_px), px[0] if px else 0,
         L.ptr(records), records.shape[0] if records is not None else 0, L.ptr(count), int(min_area), int(fill), L.ptr(cleaned),
@@ -3004,25 +3012,25 @@ SEG_SIEVE_MAX_ROUNDS = L.const("SEG_SIEVE_MAX_ROUNDS")
 def seg_sieve(table, n_blocks, labels, connectivity=8, skip_label=None, min_area=0, orphan_fill=None, rounds=1, cleaned=None,
               max_side=None):
     """Despeckling by merging (segclip_seg_sieve; the definition stands in include/segclip_hip.h): under the table of
-    seg_components_table, every component of the flat uint8 `labels` with fewer than min_area pixels takes the label of its
-    largest kept 4-neighbour (among equal areas the smallest label), `rounds` (1 .. 8) times with the components formed anew.
-    A small component without a kept neighbour keeps its label, or becomes orphan_fill (a byte) after the last round.
-    cleaned: flat uint8 of the labels' size (a new tensor unless given; it may not overlap `labels`); only the pixels of the
-    table's images are written.  max_side: the largest h or w of the table (defaults to the limit).  No host
-    synchronisation.  -> cleaned."""
+    seg_components_table, every component of the flat uint8 or int16 `labels` (int16: 16-bit label maps read as unsigned,
+    segclip_seg_sieve_wide) with fewer than min_area pixels takes the label of its largest kept 4-neighbour (among equal areas
+    the smallest label), `rounds` (1 .. 8) times with the components formed anew.  A small component without a kept neighbour
+    keeps its label, or becomes orphan_fill after the last round.  skip_label and orphan_fill are in 0 .. 255 for uint8 labels
+    and 0 .. 65535 for int16 labels.  cleaned: flat, of the labels' dtype and size (a new tensor unless given; it may not overlap
+    `labels`); only the pixels of the table's images are written.  max_side: the largest h or w of the table (defaults to the
+    limit).  No host synchronisation.  -> cleaned."""
     L.require_cuda(table, labels, cleaned)
     _check_image_table("seg_sieve", table, SEG_CC_COLS, "seg_components_table")
-    if labels.dtype != torch.uint8 or not labels.is_contiguous():
-        raise ValueError("seg_sieve: labels is a contiguous uint8 tensor")
+    wide = _seg_label_width("seg_sieve", labels)
     if cleaned is None:
         cleaned = torch.zeros_like(labels)
-    if cleaned.dtype != torch.uint8 or not cleaned.is_contiguous():
-        raise ValueError("seg_sieve: cleaned is a contiguous uint8 tensor")
+    if cleaned.dtype != labels.dtype or not cleaned.is_contiguous():
+        raise ValueError(f"seg_sieve: cleaned is a contiguous {labels.dtype} tensor, as labels")
     B = table.shape[0]
     lib = L.load()
-    ws_bytes = lib.segclip_seg_sieve_ws_bytes(labels.numel(), B, int(n_blocks))
+    ws_bytes = (lib.segclip_seg_sieve_wide_ws_bytes if wide else lib.segclip_seg_sieve_ws_bytes)(labels.numel(), B, int(n_blocks))
     ws = _workspace("seg_sieve", ws_bytes, labels.device, 16)
-    L.check(lib.segclip_seg_sieve(
+    L.check((lib.segclip_seg_sieve_wide if wide else lib.segclip_seg_sieve)(
         L.ptr(table), B, int(n_blocks), _max_side(max_side), L.ptr(labels), labels.numel(),
         int(connectivity), -1 if skip_label is None else int(skip_label), int(min_area),
         -1 if orphan_fill is None else int(orphan_fill), int(rounds), L.ptr(cleaned), cleaned.numel(), L.ptr(ws), ws_bytes,
@@ -3067,19 +3075,27 @@ def seg_boundary_table(sizes, pred_offsets, gt_offsets, radii, device):
         strips = ((h + sh - 1) // sh) * ((w + tw - 1) // tw)
         blk += (strips + SEG_BOUNDARY_WAVES - 1) // SEG_BOUNDARY_WAVES
         side = max(side, h, w)
-    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_BOUNDARY_COLS), blk, side
+    # through pinned memory: SegEvaluator.update_maps scores without waiting for the device
+    return _upload_table(tab, torch.int64, device).view(-1, SEG_BOUNDARY_COLS), blk, side
 
 
 def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255, reduce_zero_label=False, pred_band=None,
                  gt_band=None, areas=None, max_side=None):
-    """Boundary bands and boundary areas of the flat uint8 `pred` (and `gt`) under the table of seg_boundary_table
-    (segclip_seg_boundary; the definition stands in include/segclip_hip.h).  Every output is optional and written where given:
-    pred_band / gt_band flat uint8 of pred's / gt's size (bit 0: a label change within the radius, bit 1: the window leaves the
-    map), areas (2, 3, C) int64 that is ADDED to (slot 0 Boundary IoU, slot 1 trimap; needs gt).  max_side: the largest h or w
-    of the table (defaults to the limit).  No host synchronisation.  -> None."""
+    """Boundary bands and boundary areas of the flat `pred` (and `gt`) under the table of seg_boundary_table (the definition
+    stands in include/segclip_hip.h).  pred and gt are both uint8 (segclip_seg_boundary, at most 256 classes) or both int16
+    (segclip_seg_boundary_wide: 16-bit label maps read as unsigned, at most 1024 classes, ignore_index 0 .. 65535).  Every output
+    is optional and written where given: pred_band / gt_band flat uint8, whatever the labels' dtype, with one byte per element of
+    pred / gt (bit 0: a label change within the radius, bit 1: the window leaves the map), areas (2, 3, C) int64 that is ADDED to
+    (slot 0 Boundary IoU, slot 1 trimap; needs gt).  max_side: the largest h or w of the table (defaults to the limit).  No host
+    synchronisation.  -> None."""
     L.require_cuda(table, pred, gt, pred_band, gt_band, areas)
     _check_image_table("seg_boundary", table, SEG_BOUNDARY_COLS, "seg_boundary_table")
-    for name, t in (("pred", pred), ("gt", gt), ("pred_band", pred_band), ("gt_band", gt_band)):
+    wide = _seg_label_width("seg_boundary", pred, "pred")
+    if gt is not None and (gt.dtype not in (torch.uint8, torch.int16) or not gt.is_contiguous()):
+        raise ValueError("seg_boundary: gt is a contiguous uint8 or int16 tensor")
+    if gt is not None and gt.dtype != pred.dtype:
+        raise ValueError("seg_boundary: pred and gt are both uint8 or both int16 tensors")
+    for name, t in (("pred_band", pred_band), ("gt_band", gt_band)):
         if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
             raise ValueError(f"seg_boundary: {name} is a contiguous uint8 tensor")
     if pred_band is not None and pred_band.numel() != pred.numel():
@@ -3097,7 +3113,7 @@ def seg_boundary(table, n_blocks, pred, gt=None, num_classes=1, ignore_index=255
     gt_bytes = gt.numel() if gt is not None else 0
     ws_bytes = lib.segclip_seg_boundary_ws_bytes(pred.numel(), gt_bytes)
     ws = _workspace("seg_boundary", ws_bytes, pred.device, 16)
-    L.check(lib.segclip_seg_boundary(
+    L.check((lib.segclip_seg_boundary_wide if wide else lib.segclip_seg_boundary)(
         L.ptr(table), table.shape[0], int(n_blocks), _max_side(max_side), L.ptr(pred),
         pred.numel(), L.ptr(gt), gt_bytes, num_classes, int(ignore_index), int(bool(reduce_zero_label)), L.ptr(pred_band),
         L.ptr(gt_band), L.ptr(areas), L.ptr(ws), ws_bytes, L.stream()), "seg_boundary")

@@ -61,7 +61,10 @@ Wide vocabularies (the reference evaluates VOC, Context-59 and COCO-80; open-voc
 and ADE20K-847): SegInference(label_dtype=torch.int16) writes 16-bit label maps for up to 1024 classes and SegEvaluator over it
 scores int16 ground truths (csrc/segment_wide.inc: 3 x 1024 counters per workgroup, and the pixels that need a scan over the
 classes are resolved by their wave, 64 classes at a time).  The uint8 path is unchanged and stays the default.  Not covered for
-16-bit maps: test-time augmentation, the threshold sweep, refinement, components, boundary metrics and render_raw.
+16-bit maps: test-time augmentation, the threshold sweep, refinement (PAMR's launch plan and presence map stop at 256 classes)
+and render_raw, and inside the pipeline (clean=, SegEvaluator(boundary=)) despeckling and the boundary metrics.  The stand-alone
+functions do take int16 maps - components, despeckle, boundary_bands, boundary_areas (their kernels are templates on the label
+element) - and SegEvaluator.update_maps scores label maps that exist already: predict_raw -> despeckle -> update_maps.
 
 Confusion matrix (not in the reference): the (3, C) areas say how bad a class is, not where its pixels went.
 SegEvaluator(confusion=True) counts the labels of every update path, 8- or 16-bit, against the ground truths into a
@@ -369,19 +372,25 @@ def _check_pictures(raws, maps=None, noun="a label map"):
     return sizes
 
 
-def _check_maps(maps, noun="a label map", sizes=None):
+def _check_maps(maps, noun="a label map", sizes=None, wide=False):
     """A list of (h, w) uint8 device maps, `noun` each in the messages.  sizes: those of the pictures they belong to; without
-    them any non-empty size."""
+    them any non-empty size.  wide: the caller's kernels take 16-bit label maps too (components, despeckle, the boundary
+    functions): uint8 or int16, one dtype per list."""
     plural = noun.split(" ", 1)[1] + "s"
     if len(maps) == 0:
         raise ValueError(f"empty list of {plural}")
     ops.L.require_cuda(*maps)
+    dtypes = (torch.uint8, torch.int16) if wide else (torch.uint8,)
+    words = "uint8 or int16" if wide else "uint8"
     for i, m in enumerate(maps):
-        plain = m.dtype == torch.uint8 and m.dim() == 2
+        plain = m.dtype in dtypes and m.dim() == 2
         if sizes is None and not (plain and m.numel() > 0):
-            raise ValueError(f"{noun} is a non-empty (h, w) uint8 tensor, got {m.dtype} {tuple(m.shape)}")
+            raise ValueError(f"{noun} is a non-empty (h, w) {words} tensor, got {m.dtype} {tuple(m.shape)}")
         if sizes is not None and not (plain and tuple(m.shape) == sizes[i]):
-            raise ValueError(f"{noun} is an (h, w) uint8 tensor of its image's size {sizes[i]}, got {m.dtype} {tuple(m.shape)}")
+            raise ValueError(f"{noun} is an (h, w) {words} tensor of its image's size {sizes[i]}, got {m.dtype} {tuple(m.shape)}")
+        if m.dtype != maps[0].dtype:
+            raise ValueError(f"the {plural} are all uint8 or all int16, one dtype per list; {plural[:-1]} 0 is {maps[0].dtype} and "
+                             f"{plural[:-1]} {i} is {m.dtype}")
         if m.device != maps[0].device:
             raise ValueError(f"the {plural} are on different devices")
 
@@ -506,7 +515,9 @@ class Despeckle:
     formed anew: a speck nested in a speck needs two.  A small component that touches no such neighbour keeps its label, or
     becomes `fill` after the last round; fill=None keeps it (csrc/segment_sieve.inc, segclip_seg_sieve).  It is for the
     vocabularies without a background class, where a constant fill would paint the specks with a real class.
-    The definitions stand in include/segclip_hip.h.  The reference has no such step."""
+    The definitions stand in include/segclip_hip.h.  The reference has no such step.
+    `fill` and `skip_label` are in 0 .. 255 here whatever the maps' width: through this class a 16-bit map (despeckle on int16
+    maps) can be filled with, or skip, one of the first 256 values only; ops.seg_components and ops.seg_sieve take 0 .. 65535."""
 
     def __init__(self, min_area, fill=0, connectivity=8, skip_label=None, merge=False, rounds=1):
         if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 0:
@@ -549,12 +560,13 @@ class Objects:
 
 @torch.no_grad()
 def components(maps, connectivity=8, skip_label=None, max_objects=None):
-    """maps [(h_i, w_i) uint8 label maps of any mix of sizes] -> Objects: the connected components of every map, labelled on the
-    device in one call.  max_objects bounds the record list (default: one row per 16 pixels, at least 4096 rows).  Reading the
-    count is the ONE host synchronisation of this function; more components than max_objects raise a ValueError that names
-    both numbers (ask again with a larger max_objects)."""
+    """maps [(h_i, w_i) label maps of any mix of sizes, all uint8 or all int16 (16-bit maps read as unsigned values, those of
+    SegInference(label_dtype=torch.int16))] -> Objects: the connected components of every map, labelled on the device in one
+    call; the label column of the records carries the 16-bit label.  max_objects bounds the record list (default: one row per
+    16 pixels, at least 4096 rows).  Reading the count is the ONE host synchronisation of this function; more components
+    than max_objects raise a ValueError that names both numbers (ask again with a larger max_objects)."""
     maps = list(maps)
-    _check_maps(maps)
+    _check_maps(maps, wide=True)
     batch = _Maps.of(maps)
     dev = batch.flat.device
     if max_objects is None:
@@ -582,7 +594,7 @@ def _despeckle_maps(maps, clean):
     """-> the cleaned maps, a _Maps over one new buffer"""
     _check_clean(clean)
     maps = list(maps)
-    _check_maps(maps)
+    _check_maps(maps, wide=True)
     batch = _Maps.of(maps)
     table, n_blocks, side = ops.seg_components_table(batch.sizes, batch.offs, batch.flat.device)
     out = batch.empty_like()
@@ -597,9 +609,11 @@ def _despeckle_maps(maps, clean):
 
 @torch.no_grad()
 def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None, merge=False, rounds=1):
-    """maps [(h_i, w_i) uint8 label maps] -> [(h_i, w_i) uint8], views of one new buffer: every connected component with fewer
-    than min_area pixels replaced by `fill`, or with merge=True merged into its largest neighbour in `rounds` rounds (see
-    Despeckle), all maps in one call and without a host synchronisation.  The inputs stay as they are."""
+    """maps [(h_i, w_i) label maps, all uint8 or all int16] -> [(h_i, w_i) maps of the same dtype], views of one new buffer:
+    every connected component with fewer than min_area pixels replaced by `fill`, or with merge=True merged into its largest
+    neighbour in `rounds` rounds (see Despeckle), all maps in one call and without a host synchronisation.  int16 maps are the
+    16-bit label maps of SegInference(label_dtype=torch.int16), read as unsigned values; `fill` and `skip_label` stay in
+    0 .. 255 (Despeckle).  The inputs stay as they are."""
     return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label, merge, rounds)).views()
 
 
@@ -648,32 +662,35 @@ def _boundary_call(batch, boundary, gts=None, **kw):
 
 @torch.no_grad()
 def boundary_bands(maps, boundary):
-    """maps [(h_i, w_i) uint8 label maps of any mix of sizes] -> [(h_i, w_i) uint8 band maps], views of one new buffer: bit 0
-    where a pixel within the radius (boundary.radius_of(h_i, w_i), Chebyshev distance, inside the map) carries another byte,
-    bit 1 where the (2d+1)^2 window leaves the map.  (map == k) & (band != 0) is Boundary IoU's mask_to_boundary of class k.
+    """maps [(h_i, w_i) label maps of any mix of sizes, all uint8 or all int16 (16-bit maps read as unsigned values)] ->
+    [(h_i, w_i) uint8 band maps, whatever the labels' dtype], views of one new buffer: bit 0 where a pixel within the radius
+    (boundary.radius_of(h_i, w_i), Chebyshev distance, inside the map) carries another label, bit 1 where
+    the (2d+1)^2 window leaves the map.  (map == k) & (band != 0) is Boundary IoU's mask_to_boundary of class k.
     All maps in one call and without a host synchronisation; the inputs stay as they are."""
     _check_boundary(boundary)
     maps = list(maps)
-    _check_maps(maps)
+    _check_maps(maps, wide=True)
     batch = _Maps.of(maps)
-    band = batch.empty_like()
+    flat = torch.empty(batch.flat.numel(), dtype=torch.uint8, device=batch.flat.device)
+    band = _Maps(flat if batch.packed() else flat.zero_(), batch.offs, batch.sizes)   # as empty_like, one byte per label
     _boundary_call(batch, boundary, pred_band=band.flat)
     return band.views()
 
 
 @torch.no_grad()
 def boundary_areas(preds, gts, num_classes, boundary, ignore_index=255, reduce_zero_label=False, areas=None):
-    """preds, gts [(h_i, w_i) uint8] -> (2, 3, C) int64 on the device, added to `areas` when given: slot 0 the intersection,
+    """preds, gts [(h_i, w_i), all uint8 or all int16] -> (2, 3, C) int64 on the device, added to `areas` when given: slot 0 the intersection,
     prediction area and label area of Boundary IoU (each side restricted to its own band), slot 1 those of the trimap (the
-    pixels within the radius of a change of the ground truth's byte).  The ground-truth rule (ignore_index,
-    reduce_zero_label, values >= C) is ops.seg_areas'.  SegEvaluator.boundary_metrics_from_areas turns a host copy into
-    figures.  One call, no host synchronisation."""
+    pixels within the radius of a change of the ground truth's label).  The ground-truth rule (ignore_index,
+    reduce_zero_label, values >= C) is ops.seg_areas'.  With int16 preds the ground truths are int16 too (16-bit maps read as
+    unsigned values), num_classes is at most 1024 and ignore_index is in 0 .. 65535 (65535 is the usual choice).
+    SegEvaluator.boundary_metrics_from_areas turns a host copy into figures.  One call, no host synchronisation."""
     _check_boundary(boundary)
     preds, gts = list(preds), list(gts)
-    _check_maps(preds)
+    _check_maps(preds, wide=True)
     if len(preds) != len(gts):
         raise ValueError(f"{len(preds)} predictions but {len(gts)} ground truths")
-    SegEvaluator._check_gts(preds, gts)
+    SegEvaluator._check_gts(preds, gts, preds[0].dtype)
     if areas is None:
         areas = torch.zeros(2, 3, int(num_classes), dtype=torch.int64, device=preds[0].device)
     _boundary_call(_Maps.of(preds), boundary, gts=gts, num_classes=num_classes, ignore_index=ignore_index,
@@ -747,8 +764,12 @@ class SegInference:
     label_dtype=torch.int16: vocabularies of up to 1024 classes (Pascal-Context-459, ADE20K-847) without the dense logits.
     predict, predict_list and predict_raw then return int16 maps (csrc/segment_wide.inc; below 257 classes they hold the values
     of the uint8 maps), and a SegEvaluator over it takes int16 ground truths.  group_map, groups_list, groups_raw and
-    encode_decode do not depend on it.  Not built for 16-bit maps, each refused by name before anything is launched: aug= /
-    predict_views / update_views, refine=, clean=, SegEvaluator(boundary=), SegSweepEvaluator and render_raw."""
+    encode_decode do not depend on it.  The in-pipeline stages are not built for 16-bit maps, each refused by name before
+    anything is launched: aug= / predict_views / update_views, refine=, clean=, SegEvaluator(boundary=), SegSweepEvaluator and
+    render_raw.  The stand-alone functions take the int16 maps these methods return: components, despeckle (fill and merge),
+    boundary_bands, boundary_areas, and SegEvaluator.update_maps scores maps that exist already - predict_raw, despeckle,
+    update_maps is the chain of a wide vocabulary.  Out of scope: PAMR for more than 256 classes (its ceil(C / 8) x T launch
+    plan and its 256-bit presence map need another design) and test-time augmentation of wide maps."""
 
     label_dtype, wide = torch.uint8, False   # the default path; __init__ sets both
 
@@ -1194,7 +1215,9 @@ class SegEvaluator:
     Several ranks: all_reduce `confusion` (sum) like `areas`.  Without it nothing changes.
     Over a SegInference with label_dtype=torch.int16 the ground truths are (oh, ow) torch.int16 tensors whose elements are read
     as unsigned 16-bit values (a loader's uint16 array goes in as .view(torch.int16)), ignore_index is an integer in
-    0 .. 65535 compared with that value, and boundary= is refused; confusion= works there too."""
+    0 .. 65535 compared with that value, and boundary= is refused (boundary_areas takes the int16 maps that update_raw returns);
+    confusion= works there too.
+    update_maps(preds, gts) scores label maps that exist already, of either width, without the towers."""
 
     def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None, confusion=False):
         self.gt_dtype = getattr(seg, "label_dtype", torch.uint8)
@@ -1247,6 +1270,39 @@ class SegEvaluator:
         score, shapes = self._score(gts)
         _check_stages(refine, clean, raws, shapes)
         return self.seg._post_process(_RawImages(raws, transform, net_sizes, aug), shapes, refine, clean, score, return_labels)
+
+    @torch.no_grad()
+    def update_maps(self, preds, gts):
+        """Scores label maps that exist already - refined elsewhere, read from disk, or what despeckle returned: preds
+        [(oh_i, ow_i) maps of the evaluator's label dtype, uint8 or int16], gts [the ground truths, of the same dtype and sizes].
+        Adds to `areas` (ops.seg_areas / ops.seg_areas_wide), with confusion=True to `confusion`, and on a uint8 evaluator with
+        boundary= to `boundary_areas`: exactly what update / update_raw count for the same maps.  It is how a 16-bit evaluator
+        scores despeckled maps, whose in-pipeline stage (update_raw(clean=)) stays refused.  No towers, no host
+        synchronisation.  -> None."""
+        preds, gts = list(preds), list(gts)
+        word = "int16" if self.gt_dtype == torch.int16 else "uint8"
+        if len(preds) == 0:
+            raise ValueError("SegEvaluator.update_maps: empty list of label maps")
+        if len(preds) != len(gts):
+            raise ValueError(f"SegEvaluator.update_maps: {len(preds)} label maps but {len(gts)} ground truths")
+        ops.L.require_cuda(*preds)
+        self._check_gts(preds, gts, self.gt_dtype)
+        for i, (p, g) in enumerate(zip(preds, gts)):
+            if p.dtype != self.gt_dtype or p.dim() != 2 or p.numel() == 0:
+                raise ValueError(f"SegEvaluator.update_maps: label map {i} is a non-empty (oh, ow) {word} tensor (the evaluator's "
+                                 f"label dtype), got {p.dtype} {tuple(p.shape)}")
+            if tuple(p.shape) != tuple(g.shape):
+                raise ValueError(f"SegEvaluator.update_maps: label map {i} has its ground truth's size {tuple(g.shape)}, got "
+                                 f"{tuple(p.shape)}")
+        batch = _Maps.of(preds)
+        flat, gt = batch.gapless(), _Maps.gapless_of(gts)[0]
+        C = self.seg.num_classes
+        rule = dict(ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
+        (ops.seg_areas_wide if self.gt_dtype == torch.int16 else ops.seg_areas)(flat, gt, C, areas=self.areas, **rule)
+        if self.boundary is not None:
+            _boundary_call(batch, self.boundary, gts=gts, num_classes=C, areas=self.boundary_areas, **rule)
+        if self.confusion is not None:
+            ops.seg_confusion(flat, gt, C, conf=self.confusion, **rule)
 
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):

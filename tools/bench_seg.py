@@ -90,9 +90,21 @@ that SegEvaluator.update forms for the inputs of --eval (64 images of mixed VOC-
         relabelled (piecewise constant, as annotations are), the label maps against independent random labels, and random labels
         on both sides (at 460 and 848 classes more distinct pairs than the sparse table has slots: its overflow path).  Medians,
         spread, the clock held, the route, bytes per second against the HBM peak.
-usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge | --confusion]
+With --wide-post instead: the post-processing of 16-bit label maps (components, despeckle, boundary_areas on int16 maps: the
+uint16_t instantiations of csrc/segment_objects.inc, segment_sieve.inc and segment_boundary.inc) on the 64 label maps of
+--objects and on their int16 copies - the values are below 256, so both widths give the same result, which is checked - in ONE
+command and alternating within every repeat:
+  (xiv) components(), despeckle(min_area=16) in fill mode and with merge=True, and boundary_areas against update_raw's ground
+        truths, each on the uint8 maps (the yardstick of its int16 twin) and on the int16 copies: medians, min-max, the ratio
+        int16 / uint8 of every call, the clock held, and the kernels' own times by instantiation from a separate
+        `rocprofv3 --kernel-trace --stats` child (--wide-post-child: five calls of each on both widths and nothing else).
+        The output file keeps whatever stands above the line "# ---- tools/bench_seg.py --wide-post" (the kernels' resource
+        tables) and replaces what follows it.
+usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge | --confusion |
+                                  --wide-post]
                                  [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
-                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt | seg_confusion.txt]"""
+                                  seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt | seg_confusion.txt |
+                                  seg_wide_post.txt]"""
 import os
 import statistics
 import sys
@@ -116,12 +128,15 @@ BOUNDARY, BOUNDARY_CHILD = ("--boundary" in sys.argv[1:]), ("--boundary-child" i
 WIDE = "--wide" in sys.argv[1:]
 MERGE, MERGE_CHILD = ("--merge" in sys.argv[1:]), ("--merge-child" in sys.argv[1:])
 CONFUSION = "--confusion" in sys.argv[1:]
+WIDE_POST, WIDE_POST_CHILD = ("--wide-post" in sys.argv[1:]), ("--wide-post-child" in sys.argv[1:])
+WIDE_POST_MARK = "# ---- tools/bench_seg.py --wide-post"
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
-                                             "--boundary-child", "--wide", "--merge", "--merge-child", "--confusion")]
+                                             "--boundary-child", "--wide", "--merge", "--merge-child", "--confusion", "--wide-post",
+                                             "--wide-post-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_wide_post.txt" if WIDE_POST else "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -1342,6 +1357,88 @@ def confusion_case(model, n_images=64):
                 f"peak allocation of one call: seg_confusion {peak_of(ways[0][1]) / 2**20:.1f} MiB, bincount {peak_of(by_bincount) / 2**20:.1f} MiB")
 
 
+def wide_post_ways(model, text, n_images=64):
+    """-> (the pairs (what, call on the uint8 maps, call on their int16 copies), the pixels of the maps)"""
+    from segclip_amd.segmentation import Boundary, boundary_areas, components, despeckle
+    seg, _, _, gts, maps = objects_maps(model, text, n_images)
+    maps = [m.clone() for m in maps]
+    pixels = sum(int(m.numel()) for m in maps)
+    wide, wide_gts = [m.to(torch.int16) for m in maps], [g.to(torch.int16) for g in gts]
+    C, b = seg.num_classes, Boundary()
+    pairs = [("components()", lambda m, g: components(m, max_objects=pixels).records),
+             ("despeckle(min_area=16)", lambda m, g: torch.cat([c.reshape(-1) for c in despeckle(m, 16)])),
+             ("despeckle(min_area=16, merge=True)", lambda m, g: torch.cat([c.reshape(-1) for c in despeckle(m, 16, merge=True)])),
+             ("boundary_areas()", lambda m, g: boundary_areas(m, g, C, b))]
+    ways = [(what, (lambda fn=fn: fn(maps, gts)), (lambda fn=fn: fn(wide, wide_gts))) for what, fn in pairs]
+    return ways, pixels
+
+
+def wide_post_case(model, text, n_images=64):
+    from tools import rocprof_roofline as rr
+    name = f"(xiv) wide-post {n_images} mixed sizes"
+    ways, pixels = wide_post_ways(model, text, n_images)
+    with torch.no_grad():
+        for what, narrow, wide in ways:
+            a, b = narrow(), wide()
+            assert torch.equal(a.to(torch.int64), b.to(torch.int64)), f"{what}: the int16 maps give another result"
+        torch.cuda.synchronize()
+        ts = [([], []) for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):
+            for k, (_, narrow, wide) in enumerate(ways):
+                for side, fn in enumerate((narrow, wide)):
+                    t0 = time.perf_counter()
+                    for _ in range(4):
+                        fn()
+                    torch.cuda.synchronize()
+                    ts[k][side].append((time.perf_counter() - t0) / 4)
+        clk = sampler.stop()
+    say(f"{name}: {pixels} pixels in the label maps of update_raw and in their int16 copies (values below 256: equal results, checked); "
+        f"{REPS} repeats x 4 calls, the calls alternating within each repeat; clock {clk}")
+    for (what, _, _), (t8, t16) in zip(ways, ts):
+        m8, m16 = statistics.median(t8), statistics.median(t16)
+        say(f"{name}: {what:38s} uint8 {m8 * 1e3:8.3f} ms (min {min(t8) * 1e3:.3f}, max {max(t8) * 1e3:.3f})   int16 {m16 * 1e3:8.3f} ms "
+            f"(min {min(t16) * 1e3:.3f}, max {max(t16) * 1e3:.3f})   int16 / uint8 {m16 / m8:.3f}")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--wide-post-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    rows = [r for r in table if any(tag in r[0] for tag in ("seg_cc_", "seg_sieve_", "seg_bd_"))]
+    if not rows:
+        say(f"{name}: the kernels alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+    for r in rows:
+        start = min(r[0].find(tag) for tag in ("seg_cc_", "seg_sieve_", "seg_bd_") if tag in r[0])
+        say(f"{name}: {r[0][start:][:52]:52s} alone (rocprofv3 --kernel-trace --stats, {r[1]} launches in the child's 5 calls of each) "
+            f"{r[2] / r[1]:9.1f} us per launch")
+
+
+def wide_post_child(model, text):
+    """Five calls of each of wide_post_case's calls on both widths: what its rocprofv3 child traces."""
+    ways, _ = wide_post_ways(model, text)
+    with torch.no_grad():
+        for _, narrow, wide in ways:
+            for _ in range(5):
+                narrow()
+                wide()
+    torch.cuda.synchronize()
+
+
+def write_out():
+    """the lines of this run into OUT; --wide-post keeps what stands above its mark (the kernels' resource tables)"""
+    head = []
+    if WIDE_POST:
+        if os.path.exists(OUT):
+            old = open(OUT).read().split("\n")
+            head = old[:old.index(WIDE_POST_MARK)] if WIDE_POST_MARK in old else old
+        head.append(WIDE_POST_MARK)
+    with open(OUT, "w") as f:
+        f.write("\n".join(head + lines) + "\n")
+
+
 if __name__ == "__main__":
     segclip_amd.set_compute_dtype(torch.bfloat16)
     model, _ = synth.build_model(synth.SPECS["vitb16"], {}, device="cuda")
@@ -1371,7 +1468,12 @@ if __name__ == "__main__":
     if MERGE_CHILD:
         merge_child(model, text)
         sys.exit(0)
-    if CONFUSION:
+    if WIDE_POST_CHILD:
+        wide_post_child(model, text)
+        sys.exit(0)
+    if WIDE_POST:
+        wide_post_case(model, text)
+    elif CONFUSION:
         confusion_case(model)
     elif MERGE:
         merge_case(model, text)
@@ -1395,5 +1497,4 @@ if __name__ == "__main__":
         case("(i)  whole  B=64 224x224", model, text, 64, 224, 224, 3)
         case("(ii) slide  B=16 448x672", model, text, 16, 448, 672, 2, mode="slide", crop_size=(224, 224), stride=(224, 224))
     if OUT:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        write_out()
