@@ -906,6 +906,110 @@ int segclip_seg_sieve_wide(const int64_t* images, int64_t B, int64_t n_blocks, i
                            uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Superpixels of decoded pictures (segment_superpixel.inc): an integer SLIC (after Achanta et al., TPAMI 2012) on the RGB bytes,
+ * for pictures of mixed sizes in one call.  THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and
+ * restated in numpy by tests/superpixel_reference.py.  Everything is integer arithmetic - no float appears anywhere - so the
+ * order of the atomics cannot change a result and two calls give the same bits.
+ *
+ * Per image: picture R (h, w, 3) uint8, step S, compactness m, T rounds.
+ *   Grid     : gh = ceil(h / S), gw = ceil(w / S), K = gh gw.  Centre k = i gw + j belongs to cell (i, j) for good.
+ *   A centre is five integers (y, x, r, g, b).  Initially y = min(i S + S / 2, h - 1), x = min(j S + S / 2, w - 1) (integer
+ *   division) and (r, g, b) the picture's bytes there.
+ *   Assignment of pixel (y, x): its home cell is (y / S, x / S); its candidates are the centres of the 3 x 3 cells around the
+ *   home cell that lie inside the grid, wherever those centres have moved.  D = S^2 dc^2 + m^2 ds^2 with dc^2 the sum of the
+ *   three squared byte differences and ds^2 = dy^2 + dx^2.  The pixel takes the candidate with the smallest D, among equal D
+ *   the smallest centre index.
+ *   Update   : a centre with n > 0 members becomes the floor-divided means (sum / n) of its members' y, x, r, g, b; a centre
+ *   without members keeps its values.
+ *   T rounds of (assignment, update), then one final assignment: ids[p] = the index k of p's centre, in [0, K).  Ids may be
+ *   unused and a segment need not be connected: NO CONNECTIVITY PASS belongs to this definition (segclip_seg_components gives
+ *   the connected parts of any id map to a caller who wants them).
+ *   Limits   : SEGCLIP_SEG_SP_MIN_STEP <= S <= SEGCLIP_SEG_SP_MAX_STEP, 1 <= m <= SEGCLIP_SEG_SP_MAX_COMPACTNESS,
+ *   0 <= T <= SEGCLIP_SEG_SP_MAX_ITERS, sides below SEGCLIP_SEG_SOURCE_LIMIT = 2^15.  Under them
+ *     D < 2^31   : a centre's members come from its 3 x 3 cells, so it stays inside them and ds^2 <= 18 S^2 for a candidate;
+ *                  S^2 195075 + m^2 18 S^2 < 2^31 at S = m = 64 (195075 = 3 * 255^2)
+ *     sums < 2^32: a centre has at most 9 S^2 = 36,864 members, each coordinate below 2^15 and each byte below 2^8
+ *
+ *   images   : (B, SEGCLIP_SEG_SP_COLS) int64 rows on the device: 0 address of the picture (uint8, HWC, 3 interleaved channels)
+ *              1 h  2 w  3 row stride in bytes (>= 3 w)  4 offset of the image's h * w entries in `ids`  5 its first centre =
+ *              the sum of K over the images before it (its rows in `centres`)  6 its first workgroup = the sum of
+ *              ceil(h / SEGCLIP_SEG_SP_TILE_H) * ceil(w / SEGCLIP_SEG_SP_TILE_W) over the images before it  7 0
+ *   n_blocks : that sum over all images;  max_side: the caller's bound on every h and w
+ *   ids      : flat int32 of ids_n entries; only the pixels of the table's images are written
+ *   K_total  : the sum of K over all images (at most 2^28);  centres: optional (K_total, 5) int32, the final centres
+ *   ws       : segclip_seg_superpixels_ws_bytes(K_total) bytes (44 per centre), 16-byte aligned
+ *   The entry enqueues, without a host synchronisation and with all images in every launch: the initialisation, T x (assign and
+ *   sum, update) and the final assignment.  A workgroup owns a tile of SEGCLIP_SEG_SP_TILE_H x SEGCLIP_SEG_SP_TILE_W pixels of
+ *   one image, stages the centres of the cells its tile touches plus one ring in LDS (at step 4, which puts the most centres in
+ *   a tile, (TILE_H / 4 + 2) * (TILE_W / 4 + 2) = 180 of them in 7.9 KiB of static LDS), sums (n, y, x, r, g, b) per staged
+ *   centre with LDS integer atomics and adds the rows that are not zero with one set of global integer atomics per (tile,
+ *   centre).  Traffic per round: 3 B per pixel read + the per-tile atomics; the final assignment adds 4 B per pixel of ids.
+ *   Every table row is range-checked on the device: an image with a null address, h or w outside [1, min(max_side, 2^15 - 1)],
+ *   a stride below 3 w, offsets inconsistent with ids_n or K_total or workgroups beyond n_blocks is SKIPPED (nothing of it
+ *   read or written).
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: S, m or T outside the limits, max_side outside [1, 2^15),
+ *   K_total above 2^28, a workspace smaller than ws_bytes.  SEGCLIP_ERR_INVALID: negative sizes, missing pointers.
+ * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_SP_TILE_H 32 /* rows and */
+#define SEGCLIP_SEG_SP_TILE_W 64 /* columns of one workgroup's tile */
+#define SEGCLIP_SEG_SP_COLS 8    /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_SP_MIN_STEP 4
+#define SEGCLIP_SEG_SP_MAX_STEP 64
+#define SEGCLIP_SEG_SP_MAX_COMPACTNESS 64
+#define SEGCLIP_SEG_SP_MAX_ITERS 16
+int64_t segclip_seg_superpixels_ws_bytes(int64_t K_total);
+int segclip_seg_superpixels(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, int64_t step, int64_t compactness,
+                            int64_t iters, int32_t* ids, int64_t ids_n, int64_t K_total, int32_t* centres, void* ws, int64_t ws_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Majority voting of label maps inside segments (segment_vote.inc): every segment gives its pixels the label most of them
+ * carry.  The segments are superpixels of segclip_seg_superpixels or ids of the caller's own (Felzenszwalb maps, flattened
+ * instance masks).  THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated in numpy by
+ * tests/superpixel_reference.py.  Integer counts: no dependence on the order of the atomics.
+ *
+ * Per image: label map L (n pixels), segment map G (n int32), the image's segment count K, C classes, min_share in 0..100.
+ *   A pixel VOTES when L(p) < C and 0 <= G(p) < K.
+ *   For a segment with tot > 0 voters: top = the largest per-class count, win = the smallest class that reaches it; the segment
+ *   SNAPS when 100 top >= min_share tot.
+ *   A voting pixel of a snapping segment takes win.  Every other pixel keeps its value: a label >= C (255 as an ignore value),
+ *   an id outside [0, K), a segment that does not snap.
+ *
+ *   images   : (B, SEGCLIP_SEG_VOTE_COLS) int64 rows on the device: 0 offset of the image's n entries in `labels`, `segments`
+ *              AND `out`  1 n = h * w  2 its first segment = the sum of K over the images before it (its rows of the count
+ *              table)  3 K  4 its first workgroup = the sum of ceil(n / SEGCLIP_SEG_VOTE_TILE) over the images before it  5-7 0
+ *   n_blocks : that sum over all images;  max_k: the caller's bound on every K, at most SEGCLIP_SEG_VOTE_MAX_SEGMENTS
+ *   labels   : flat uint8 of labels_bytes, read only;  segments: flat int32 of segments_n = labels_bytes entries
+ *   K_total  : the sum of K over all images;  1 <= C <= 256
+ *   out      : flat uint8 of out_bytes = labels_bytes, must not overlap labels; only the pixels of the table's images are written
+ *   ws       : segclip_seg_vote_ws_bytes(K_total, C) bytes: the (K_total, C) int32 counts and K_total int32 winners, 16-byte
+ *              aligned; cleared inside the call
+ *   Three passes, enqueued without a host synchronisation: the count (a workgroup stages the (segment, class) pairs of its
+ *   pixels in an open-addressing table in LDS - a caller's map gives no bound on the segments of a tile - and adds each with
+ *   one global atomic; a pair that finds no slot is added at once), the winner (one wave per segment: lanes stride the
+ *   classes, a shuffle reduction to the largest count and among equal counts the lowest class; -1 for "does not snap") and
+ *   the pass that writes `out`.  Traffic: about 9 B per pixel (11 with 16-bit labels) + K_total * C * 4 B of table cleared and read.
+ *   Every table row is range-checked on the device: an image with n outside [1, 2^30), K outside [1, max_k], offsets
+ *   inconsistent with labels_bytes or K_total or workgroups beyond n_blocks is SKIPPED (nothing of it read, written or counted).
+ *   SEGCLIP_ERR_UNSUPPORTED, nothing launched and nothing written: C outside 1..256, min_share outside 0..100, max_k outside
+ *   1..SEGCLIP_SEG_VOTE_MAX_SEGMENTS, K_total * C above 2^28, a workspace smaller than ws_bytes.  SEGCLIP_ERR_INVALID: out
+ *   overlapping labels, out_bytes or segments_n != labels_bytes, missing pointers.
+ * segclip_seg_vote_wide: the same for 16-bit label maps: labels and out are flat uint16 (an int16 tensor is read as unsigned),
+ * labels_n, out_n and the table's offsets count ELEMENTS, 1 <= C <= SEGCLIP_SEG_WIDE_MAX_CLASSES.  The same table, workspace
+ * query, range checks and refusals.
+ * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_VOTE_TILE 2048            /* pixels of one workgroup */
+#define SEGCLIP_SEG_VOTE_COLS 8               /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_VOTE_MAX_SEGMENTS 1048576 /* 2^20: K of one image */
+int64_t segclip_seg_vote_ws_bytes(int64_t K_total, int64_t C);
+int segclip_seg_vote(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_k, const uint8_t* labels, int64_t labels_bytes,
+                     const int32_t* segments, int64_t segments_n, int64_t K_total, int64_t C, int min_share, uint8_t* out,
+                     int64_t out_bytes, void* ws, int64_t ws_bytes, void* stream);
+int segclip_seg_vote_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_k, const uint16_t* labels, int64_t labels_n,
+                          const int32_t* segments, int64_t segments_n, int64_t K_total, int64_t C, int min_share, uint16_t* out,
+                          int64_t out_n, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Boundary metrics of label maps (segment_boundary.inc): the boundary bands of a prediction and a ground truth, and the
  * per-class areas of Boundary IoU (Cheng et al., CVPR 2021) and of the trimap mIoU of the DeepLab papers, for maps of mixed
  * sizes in one call.  THE REFERENCE HAS NO SUCH OP: the definition is this project's, stated here and restated with the

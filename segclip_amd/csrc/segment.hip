@@ -286,6 +286,8 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_refine.inc"
 #include "segment_objects.inc"
 #include "segment_sieve.inc"
+#include "segment_superpixel.inc"
+#include "segment_vote.inc"
 #include "segment_boundary.inc"
 #include "segment_confusion.inc"
 #include "train_frontend.inc"
@@ -1147,6 +1149,140 @@ extern "C" int segclip_seg_sieve_wide(const int64_t* images, int64_t B, int64_t 
                                       int rounds, uint16_t* cleaned, int64_t cleaned_n, void* ws, int64_t ws_bytes, void* stream) {
   return seg_sieve_run<uint16_t>("seg_sieve_wide", images, B, n_blocks, max_side, labels, labels_n, connectivity, skip_label, min_area,
                                  orphan_fill, rounds, cleaned, cleaned_n, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- superpixels (segment_superpixel.inc)
+#define SEG_SP_MAX_CENTRES (1ll << 28)
+struct SegSpWs { int64_t centres, acc, total; };
+static SegSpWs seg_sp_ws(int64_t K_total) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegSpWs w;
+  w.centres = 0;
+  w.acc = up(K_total * 5 * 4);
+  w.total = w.acc + up(K_total * 6 * 4);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_superpixels_ws_bytes(int64_t K_total) {
+  SEG_REFUSE(K_total < 0 || K_total > SEG_SP_MAX_CENTRES, "seg_superpixels_ws_bytes: need 0 <= K_total <= 2^28");
+  return seg_sp_ws(K_total).total;
+}
+
+extern "C" int segclip_seg_superpixels(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_side, int64_t step,
+                                       int64_t compactness, int64_t iters, int32_t* ids, int64_t ids_n, int64_t K_total,
+                                       int32_t* centres, void* ws, int64_t ws_bytes, void* stream) {
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && ids_n >= 0 && K_total >= 0 && ws_bytes >= 0, "seg_superpixels: sizes must not be negative");
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && ids_n <= (1ll << 40), "seg_superpixels: size out of range");
+  SEG_REFUSE(step < SEG_SP_MIN_STEP || step > SEG_SP_MAX_STEP, "seg_superpixels: a step of %lld, %d..%d supported", (long long)step,
+             SEG_SP_MIN_STEP, SEG_SP_MAX_STEP);
+  SEG_REFUSE(compactness < 1 || compactness > SEG_SP_MAX_COMPACT, "seg_superpixels: a compactness of %lld, 1..%d supported",
+             (long long)compactness, SEG_SP_MAX_COMPACT);
+  SEG_REFUSE(iters < 0 || iters > SEG_SP_MAX_T, "seg_superpixels: %lld iterations, 0..%d supported", (long long)iters, SEG_SP_MAX_T);
+  SEG_REFUSE(max_side < 1 || max_side >= SEG_SP_LIMIT, "seg_superpixels: sides of 1..%d pixels supported, got a bound of %lld",
+             SEG_SP_LIMIT - 1, (long long)max_side);
+  SEG_REFUSE(K_total > SEG_SP_MAX_CENTRES, "seg_superpixels: %lld centres, at most 2^28 supported", (long long)K_total);
+  const SegSpWs w = seg_sp_ws(K_total);
+  SEG_REFUSE(ws_bytes < w.total, "seg_superpixels: the workspace has %lld bytes, segclip_seg_superpixels_ws_bytes asks for %lld",
+             (long long)ws_bytes, (long long)w.total);
+  if (B == 0 || n_blocks == 0 || K_total == 0) return 0;
+  SEGCLIP_REQUIRE(images && ids, "seg_superpixels: images and ids are required");
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "seg_superpixels: the workspace is required, 16-byte aligned");
+
+  SegSpArgs a;
+  char* base = static_cast<char*>(ws);
+  a.images = images; a.ids = ids;
+  a.centres = centres ? centres : reinterpret_cast<int32_t*>(base + w.centres);
+  a.acc = reinterpret_cast<uint32_t*>(base + w.acc);
+  a.ids_n = ids_n; a.K_total = K_total; a.n_blocks = n_blocks;
+  a.B = (int)B; a.max_side = (int)max_side; a.S = (int)step; a.m2 = (int)(compactness * compactness);
+  const dim3 grid((unsigned)n_blocks), block(SEG_SP_THREADS);
+  hipLaunchKernelGGL(seg_sp_init_kernel, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_superpixels (init)");
+  for (int t = 0; t < (int)iters; ++t) {
+    hipLaunchKernelGGL(seg_sp_assign_kernel<false>, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_superpixels (assign)");
+    hipLaunchKernelGGL(seg_sp_update_kernel, grid, block, 0, ST, a);
+    SEGCLIP_CHECK_LAUNCH("seg_superpixels (update)");
+  }
+  hipLaunchKernelGGL(seg_sp_assign_kernel<true>, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_superpixels (ids)");
+  return 0;
+}
+
+// ---------------------------------------------------------------- majority voting inside segments (segment_vote.inc)
+#define SEG_VOTE_MAX_CELLS (1ll << 28)
+struct SegVoteWs { int64_t cnt, win, total; };
+static SegVoteWs seg_vote_ws(int64_t K_total, int64_t C) {
+  const auto up = [](int64_t v) { return (v + 255) & ~255ll; };
+  SegVoteWs w;
+  w.cnt = 0;
+  w.win = up(K_total * C * 4);
+  w.total = w.win + up(K_total * 4);
+  return w;
+}
+
+extern "C" int64_t segclip_seg_vote_ws_bytes(int64_t K_total, int64_t C) {
+  SEG_REFUSE(K_total < 0 || C < 1 || C > SEG_WIDE_MAX_CLASSES || K_total > SEG_VOTE_MAX_CELLS || K_total * C > SEG_VOTE_MAX_CELLS,
+             "seg_vote_ws_bytes: need 1 <= C <= %d and 0 <= K_total * C <= 2^28", SEG_WIDE_MAX_CLASSES);
+  return seg_vote_ws(K_total, C).total;
+}
+
+// `what`: the entry's name in messages; labels_n, out_n: ELEMENTS of L
+template <class L>
+static int seg_vote_run(const char* what, const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_k, const L* labels,
+                        int64_t labels_n, const int32_t* segments, int64_t segments_n, int64_t K_total, int64_t C, int min_share, L* out,
+                        int64_t out_n, void* ws, int64_t ws_bytes, void* stream) {
+  const char* unit = SegLabel<L>::unit;
+  SEGCLIP_REQUIRE(B >= 0 && n_blocks >= 0 && labels_n >= 0 && segments_n >= 0 && K_total >= 0 && out_n >= 0 && ws_bytes >= 0,
+                  "%s: sizes must not be negative", what);
+  SEGCLIP_REQUIRE(B <= (1 << 24) && n_blocks < (1ll << 31) && labels_n <= (1ll << 40), "%s: size out of range", what);
+  SEG_REFUSE(C < 1 || C > SegLabel<L>::MAX_CLASSES, "%s: %lld classes, 1..%d supported", what, (long long)C, SegLabel<L>::MAX_CLASSES);
+  SEG_REFUSE(min_share < 0 || min_share > 100, "%s: min_share is a percentage in 0..100, got %d", what, min_share);
+  SEG_REFUSE(max_k < 1 || max_k > SEG_VOTE_MAX_K, "%s: 1..%d segments per image supported, got a bound of %lld", what, SEG_VOTE_MAX_K,
+             (long long)max_k);
+  SEG_REFUSE(K_total > SEG_VOTE_MAX_CELLS || K_total * C > SEG_VOTE_MAX_CELLS,
+             "%s: %lld segments x %lld classes, at most 2^28 counters supported", what, (long long)K_total, (long long)C);
+  const SegVoteWs w = seg_vote_ws(K_total, C);
+  SEG_REFUSE(ws_bytes < w.total, "%s: the workspace has %lld bytes, segclip_seg_vote_ws_bytes asks for %lld", what, (long long)ws_bytes,
+             (long long)w.total);
+  if (B == 0 || n_blocks == 0 || K_total == 0) return 0;   // without a segment nobody votes and nothing is written
+  SEGCLIP_REQUIRE(images && labels && segments && out, "%s: images, labels, segments and out are required", what);
+  SEGCLIP_REQUIRE(out_n == labels_n && segments_n == labels_n, "%s: segments and out have the layout of labels: %lld %s, got %lld and %lld",
+                  what, (long long)labels_n, unit, (long long)segments_n, (long long)out_n);
+  SEGCLIP_REQUIRE(out + out_n <= labels || labels + labels_n <= out, "%s: out overlaps labels (the vote is out of place)", what);
+  SEGCLIP_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace is required, 16-byte aligned", what);
+
+  SegVoteArgs a;
+  char* base = static_cast<char*>(ws);
+  a.images = images; a.labels = labels; a.seg = segments; a.out = out;
+  a.cnt = reinterpret_cast<int32_t*>(base + w.cnt);
+  a.win = reinterpret_cast<int32_t*>(base + w.win);
+  a.n = labels_n; a.K_total = K_total; a.n_blocks = n_blocks;
+  a.B = (int)B; a.C = (int)C; a.max_k = (int)max_k; a.min_share = min_share;
+  const dim3 grid((unsigned)n_blocks), block(SEG_VOTE_THREADS);
+  const hipError_t e = hipMemsetAsync(a.cnt, 0, (size_t)(K_total * C) * sizeof(int32_t), ST);
+  SEGCLIP_REQUIRE(e == hipSuccess, "%s: clearing the counts failed: %s", what, hipGetErrorString(e));
+  hipLaunchKernelGGL(seg_vote_count_kernel<L>, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_vote (count)");
+  hipLaunchKernelGGL(seg_vote_winner_kernel, dim3((unsigned)cdiv(K_total, SEG_VOTE_THREADS / 64)), block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_vote (winner)");
+  hipLaunchKernelGGL(seg_vote_apply_kernel<L>, grid, block, 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH("seg_vote (apply)");
+  return 0;
+}
+
+extern "C" int segclip_seg_vote(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_k, const uint8_t* labels,
+                                int64_t labels_bytes, const int32_t* segments, int64_t segments_n, int64_t K_total, int64_t C,
+                                int min_share, uint8_t* out, int64_t out_bytes, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_vote_run<uint8_t>("seg_vote", images, B, n_blocks, max_k, labels, labels_bytes, segments, segments_n, K_total, C, min_share,
+                               out, out_bytes, ws, ws_bytes, stream);
+}
+
+extern "C" int segclip_seg_vote_wide(const int64_t* images, int64_t B, int64_t n_blocks, int64_t max_k, const uint16_t* labels,
+                                     int64_t labels_n, const int32_t* segments, int64_t segments_n, int64_t K_total, int64_t C,
+                                     int min_share, uint16_t* out, int64_t out_n, void* ws, int64_t ws_bytes, void* stream) {
+  return seg_vote_run<uint16_t>("seg_vote_wide", images, B, n_blocks, max_k, labels, labels_n, segments, segments_n, K_total, C,
+                                min_share, out, out_n, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)

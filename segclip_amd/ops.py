@@ -3038,6 +3038,126 @@ def seg_sieve(table, n_blocks, labels, connectivity=8, skip_label=None, min_area
     return cleaned
 
 
+# ---------------------------------------------------------------- superpixels (segment_superpixel.inc)
+SEG_SP_TILE = (L.const("SEG_SP_TILE_H"), L.const("SEG_SP_TILE_W"))  # (rows, columns) of one workgroup's tile of segclip_seg_superpixels
+SEG_SP_COLS = L.const("SEG_SP_COLS")  # int64 columns of one row of its image table
+SEG_SP_MIN_STEP = L.const("SEG_SP_MIN_STEP")
+SEG_SP_MAX_STEP = L.const("SEG_SP_MAX_STEP")
+SEG_SP_MAX_COMPACTNESS = L.const("SEG_SP_MAX_COMPACTNESS")
+SEG_SP_MAX_ITERS = L.const("SEG_SP_MAX_ITERS")
+
+
+def _seg_sp_step(what, step):
+    if not SEG_SP_MIN_STEP <= int(step) <= SEG_SP_MAX_STEP:
+        raise ValueError(f"{what}: step is in {SEG_SP_MIN_STEP} .. {SEG_SP_MAX_STEP}, got {step}")
+    return int(step)
+
+
+def seg_superpixels_table(raws, step, id_offsets=None):
+    """The device image table of seg_superpixels: raws [(h, w, 3) uint8 device tensors, pixels contiguous, rows possibly
+    strided], step S of the grid, id_offsets [offset of each image's (h, w) ids in the flat id buffer; by default the maps lie
+    flat one after the other].  An image has ceil(h / S) * ceil(w / S) centres, numbered through the images.  It holds the
+    tensors' addresses: keep `raws` alive while it is in use.
+    -> (table (B, 8) int64, n_blocks, largest side, counts [K per image])."""
+    S = _seg_sp_step("seg_superpixels", step)
+    if len(raws) == 0 or (id_offsets is not None and len(raws) != len(id_offsets)):
+        raise ValueError(f"seg_superpixels: {len(raws)} images but {0 if id_offsets is None else len(id_offsets)} id offsets")
+    th, tw = SEG_SP_TILE
+    tab, counts, off, cen, blk, side = [], [], 0, 0, 0, 0
+    for i, (ptr, h, w, row) in enumerate(_seg_pictures("seg_superpixels", raws, "a picture")):
+        k = ((h + S - 1) // S) * ((w + S - 1) // S)
+        tab.append([ptr, h, w, row, off if id_offsets is None else int(id_offsets[i]), cen, blk, 0])
+        counts.append(k)
+        off += h * w
+        cen += k
+        blk += ((h + th - 1) // th) * ((w + tw - 1) // tw)
+        side = max(side, h, w)
+    return torch.tensor(tab, dtype=torch.int64, device=raws[0].device).view(-1, SEG_SP_COLS), blk, side, counts
+
+
+def seg_superpixels(table, n_blocks, ids, num_centres, step=16, compactness=10, iters=5, centres=None, max_side=None):
+    """Integer SLIC superpixels (segclip_seg_superpixels; the definition stands in include/segclip_hip.h): the table of
+    seg_superpixels_table -> the flat int32 `ids`, a pixel's id the index of its centre inside its image.  num_centres: the sum
+    of the table's counts.  step 4 .. 64, compactness 1 .. 64, iters 0 .. 16.  centres: optional (num_centres, 5) int32, the
+    final (y, x, r, g, b) of every centre.  No connectivity pass (seg_components gives the connected parts of an id map).
+    max_side: the largest h or w of the table (defaults to the limit).  No host synchronisation.  -> ids."""
+    L.require_cuda(table, ids, centres)
+    _check_image_table("seg_superpixels", table, SEG_SP_COLS, "seg_superpixels_table")
+    S = _seg_sp_step("seg_superpixels", step)
+    if not 1 <= int(compactness) <= SEG_SP_MAX_COMPACTNESS:
+        raise ValueError(f"seg_superpixels: compactness is in 1 .. {SEG_SP_MAX_COMPACTNESS}, got {compactness}")
+    if not 0 <= int(iters) <= SEG_SP_MAX_ITERS:
+        raise ValueError(f"seg_superpixels: iters is in 0 .. {SEG_SP_MAX_ITERS}, got {iters}")
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError("seg_superpixels: ids is a contiguous int32 tensor")
+    K = int(num_centres)
+    if centres is not None and (centres.dtype != torch.int32 or not centres.is_contiguous() or tuple(centres.shape) != (K, 5)):
+        raise ValueError(f"seg_superpixels: centres is a contiguous ({K}, 5) int32 tensor")
+    lib = L.load()
+    ws_bytes = lib.segclip_seg_superpixels_ws_bytes(K)
+    ws = _workspace("seg_superpixels", ws_bytes, ids.device, 16)
+    L.check(lib.segclip_seg_superpixels(L.ptr(table), table.shape[0], int(n_blocks), _max_side(max_side), S, int(compactness),
+                                        int(iters), L.ptr(ids), ids.numel(), K, L.ptr(centres), L.ptr(ws), ws_bytes, L.stream()),
+            "seg_superpixels")
+    return ids
+
+
+# ---------------------------------------------------------------- majority voting inside segments (segment_vote.inc)
+SEG_VOTE_TILE = L.const("SEG_VOTE_TILE")  # pixels of one workgroup of segclip_seg_vote
+SEG_VOTE_COLS = L.const("SEG_VOTE_COLS")  # int64 columns of one row of its image table
+SEG_VOTE_MAX_SEGMENTS = L.const("SEG_VOTE_MAX_SEGMENTS")  # segments of one image
+
+
+def seg_vote_table(sizes, offsets, counts, device):
+    """The device image table of seg_vote: sizes [(h, w)], offsets [offset of each image's h * w entries in the flat label
+    buffer; the segment ids and the output take the same offsets], counts [K per image: its segment ids are 0 .. K - 1]
+    -> (table (B, 8) int64, n_blocks, num_segments = the sum of the counts, the largest count)."""
+    if len(sizes) == 0 or len(sizes) != len(offsets) or len(sizes) != len(counts):
+        raise ValueError(f"seg_vote: {len(sizes)} sizes but {len(offsets)} offsets and {len(counts)} segment counts")
+    tab, seg, blk = [], 0, 0
+    for (h, w), off, k in zip(sizes, offsets, counts):
+        h, w, k = int(h), int(w), int(k)
+        if min(h, w) < 1 or max(h, w) >= SEG_SOURCE_LIMIT:
+            raise ValueError(f"seg_vote: sizes 1 .. {SEG_SOURCE_LIMIT - 1} supported, got {h}x{w}")
+        if not 1 <= k <= SEG_VOTE_MAX_SEGMENTS:
+            raise ValueError(f"seg_vote: 1 .. {SEG_VOTE_MAX_SEGMENTS} segments per image supported, got {k}")
+        tab.append([int(off), h * w, seg, k, blk, 0, 0, 0])
+        seg += k
+        blk += (h * w + SEG_VOTE_TILE - 1) // SEG_VOTE_TILE
+    return torch.tensor(tab, dtype=torch.int64, device=device).view(-1, SEG_VOTE_COLS), blk, seg, max(int(k) for k in counts)
+
+
+def seg_vote(table, n_blocks, labels, segments, num_segments, num_classes, min_share=0, out=None, max_count=None):
+    """Majority voting inside segments (segclip_seg_vote / segclip_seg_vote_wide by the labels' dtype; the definition stands in
+    include/segclip_hip.h): under the table of seg_vote_table, every pixel whose label is below num_classes and whose int32
+    segment id lies in its image's 0 .. K - 1 takes the most frequent label of its segment (among equal counts the smallest),
+    provided that label holds at least min_share percent of the segment's voters; every other pixel keeps its value.  labels:
+    flat uint8, or int16 read as unsigned 16-bit values (up to SEG_WIDE_MAX_CLASSES classes); segments: flat int32 of the same
+    size.  out: flat, of the labels' dtype and size (a new tensor unless given; it may not overlap `labels`); only the pixels of
+    the table's images are written.  max_count: the largest K of the table (defaults to the limit).  No host synchronisation.
+    -> out."""
+    L.require_cuda(table, labels, segments, out)
+    _check_image_table("seg_vote", table, SEG_VOTE_COLS, "seg_vote_table")
+    wide = _seg_label_width("seg_vote", labels)
+    if segments.dtype != torch.int32 or not segments.is_contiguous() or segments.numel() != labels.numel():
+        raise ValueError("seg_vote: segments is a contiguous int32 tensor with one entry per label")
+    if not 0 <= int(min_share) <= 100:
+        raise ValueError(f"seg_vote: min_share is a percentage in 0 .. 100, got {min_share}")
+    if out is None:
+        out = torch.zeros_like(labels)
+    if out.dtype != labels.dtype or not out.is_contiguous():
+        raise ValueError(f"seg_vote: out is a contiguous {labels.dtype} tensor, as labels")
+    lib = L.load()
+    K, C = int(num_segments), int(num_classes)
+    ws_bytes = lib.segclip_seg_vote_ws_bytes(K, C)
+    ws = _workspace("seg_vote", ws_bytes, labels.device, 16)
+    L.check((lib.segclip_seg_vote_wide if wide else lib.segclip_seg_vote)(
+        L.ptr(table), table.shape[0], int(n_blocks), SEG_VOTE_MAX_SEGMENTS if max_count is None else int(max_count), L.ptr(labels),
+        labels.numel(), L.ptr(segments), segments.numel(), K, C, int(min_share), L.ptr(out), out.numel(), L.ptr(ws), ws_bytes,
+        L.stream()), "seg_vote")
+    return out
+
+
 # ---------------------------------------------------------------- boundary bands and areas (segment_boundary.inc)
 # (rows, columns) of one wave's strip of segclip_seg_boundary; the columns are also its rows pass's chunk
 SEG_BOUNDARY_TILE = (L.const("SEG_BOUNDARY_TILE_H"), L.const("SEG_BOUNDARY_TILE_W"))

@@ -73,6 +73,15 @@ or a table of pairs per workgroup in LDS), without a host synchronisation; compu
 fwIoU and kappa, and areas_from_confusion, confusion_metrics, confused_pairs and merge_classes work on a host copy without an
 evaluator.  Not covered: SegSweepEvaluator.
 
+Superpixels and snapping (not in the reference): the third standard answer to borders that follow the patch grid.  Superpixels
+states an integer SLIC on the RGB bytes, superpixels cuts a list of decoded pictures into segments on the device
+(csrc/segment_superpixel.inc), snap_labels gives every segment the majority label of its pixels (csrc/segment_vote.inc) - the
+segments are a Segments, or int32 maps of the caller's own with their counts (Felzenszwalb maps, flattened instance masks), the
+labels uint8 or int16 - and Snap is the stage: predict_raw / update_raw / eval_epoch take snap=, applied after refine= and
+before clean=.  Everything is integer arithmetic, without soft masks and without a host synchronisation.  No connectivity
+pass belongs to the definition (components gives the connected parts of an id map).  Not covered: predict_list, update,
+render_raw, SegSweepEvaluator and, inside the pipeline, 16-bit label maps: predict_raw -> snap_labels -> despeckle -> update_maps.
+
 The host layer.  _plan_windows turns the sizes of a call into tower batches and per-entry windows (a pure function: no model,
 no device), a source (_BatchImages, _SlicedImages, _RawImages) says where a chunk's tower input comes from, and
 SegInference._list_towers is the one loop that runs the towers, for every entry point.  A source is always view-shaped: an
@@ -80,7 +89,7 @@ image without augmentation is one view with flags 0.  _list_forward (arg-max of 
 (the same for a list of thresholds) and _views_forward (soft-max mean, dense twin) are the kernel calls over the same steps.
 Behind the label kernel, _Maps owns the layout of a list of maps in one flat buffer (views used where they lie, copies at
 multiples of 4, zeroed bytes between the maps of an output, the gapless form that the ground truths have), and
-SegInference._post_process is the one chain labels -> refine -> clean -> areas -> boundary areas for predict_raw and every
+SegInference._post_process is the one chain labels -> refine -> snap -> clean -> areas -> boundary areas for predict_raw and every
 update path; its docstring states which kernel counts the mIoU areas.  _refuse words the refusals of the entry points that
 do not take a stage, and _check_pictures / _check_maps (here) and ops._seg_pictures (strides, where the addresses are taken)
 are the only checks of decoded pictures and index maps.
@@ -617,6 +626,166 @@ def despeckle(maps, min_area, fill=0, connectivity=8, skip_label=None, merge=Fal
     return _despeckle_maps(maps, Despeckle(min_area, fill, connectivity, skip_label, merge, rounds)).views()
 
 
+def _int_in(owner, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError(f"{owner}: {name} is an integer in {lo} .. {hi}, got {v!r}")
+    return v
+
+
+class Superpixels:
+    """Superpixels of the decoded pictures: an integer SLIC on the RGB bytes (csrc/segment_superpixel.inc; the definition
+    stands in include/segclip_hip.h).  step: the side of a grid cell, an image of (h, w) pixels has ceil(h / step) *
+    ceil(w / step) centres; compactness: the weight of the distance in the plane against the distance in colour; iters: rounds
+    of (assignment, update) before the final assignment.  No connectivity pass belongs to the definition: a segment need not be
+    connected (components gives the connected parts of any id map).  The reference has no superpixels."""
+
+    def __init__(self, step=16, compactness=10, iters=5):
+        self.step = _int_in("Superpixels", "step", step, ops.SEG_SP_MIN_STEP, ops.SEG_SP_MAX_STEP)
+        self.compactness = _int_in("Superpixels", "compactness", compactness, 1, ops.SEG_SP_MAX_COMPACTNESS)
+        self.iters = _int_in("Superpixels", "iters", iters, 0, ops.SEG_SP_MAX_ITERS)
+
+    def grid(self, h, w):
+        """(rows, columns) of the centres of an (h, w) picture"""
+        return -(-int(h) // self.step), -(-int(w) // self.step)
+
+    def count(self, h, w):
+        """K of an (h, w) picture: its segment ids are 0 .. K - 1"""
+        gh, gw = self.grid(h, w)
+        return gh * gw
+
+
+class Segments:
+    """Segment maps of a list of images: maps [(h_i, w_i) int32, views of one flat buffer; the ids of image i are
+    0 .. counts[i] - 1, and an id may be unused], counts [K per image].  centres: None, or the (sum of counts, 5) int32 final
+    (y, x, r, g, b) of every centre, image after image."""
+
+    def __init__(self, maps, counts, centres=None):
+        self.maps, self.counts, self.centres = list(maps), [int(k) for k in counts], centres
+
+
+def _check_superpixels(sp):
+    if not isinstance(sp, Superpixels):
+        raise TypeError("superpixels is a Superpixels")
+
+
+@torch.no_grad()
+def superpixels(raws, sp=None, centres=False):
+    """raws [(h_i, w_i, 3) uint8 decoded images of any mix of sizes, rows possibly strided] -> Segments: the superpixels of
+    every picture under `sp` (a Superpixels; the defaults without one), all pictures in every launch of one call and without a
+    host synchronisation.  centres=True also returns the final centres.  The pictures stay as they are."""
+    sp = Superpixels() if sp is None else sp
+    _check_superpixels(sp)
+    raws = list(raws)
+    sizes = _check_pictures(raws)
+    table, n_blocks, side, counts = ops.seg_superpixels_table(raws, sp.step)
+    dev = raws[0].device
+    offs, n = _Maps._running([h * w for h, w in sizes])
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    cen = torch.empty(sum(counts), 5, dtype=torch.int32, device=dev) if centres else None
+    ops.seg_superpixels(table, n_blocks, ids, sum(counts), sp.step, sp.compactness, sp.iters, centres=cen, max_side=side)
+    return Segments(_Maps(ids, offs, sizes).views(), counts, cen)
+
+
+def _check_min_share(owner, min_share):
+    return _int_in(owner, "min_share", min_share, 0, 100)
+
+
+def _snap_maps(labels, segments, num_classes, counts=None, min_share=0):
+    """-> the snapped maps, a _Maps over one new buffer"""
+    labels = list(labels)
+    _check_maps(labels, wide=True)
+    _check_min_share("snap_labels", min_share)
+    if isinstance(segments, Segments):
+        if counts is not None:
+            raise ValueError("snap_labels: a Segments carries its counts; counts= goes with a list of segment maps")
+        segments, counts = segments.maps, segments.counts
+    else:
+        if counts is None:
+            raise ValueError("snap_labels: a list of segment maps needs counts, the number of segments of every image (finding "
+                             "the largest id would cost a host synchronisation)")
+        segments, counts = list(segments), list(counts)
+    if len(segments) != len(labels) or len(counts) != len(labels):
+        raise ValueError(f"snap_labels: {len(labels)} label maps but {len(segments)} segment maps and {len(counts)} counts")
+    ops.L.require_cuda(*segments)
+    for m, s in zip(labels, segments):
+        if s.dtype != torch.int32 or s.dim() != 2 or tuple(s.shape) != tuple(m.shape):
+            raise ValueError(f"snap_labels: a segment map is an (h, w) int32 tensor of its label map's size {tuple(m.shape)}, got "
+                             f"{s.dtype} {tuple(s.shape)}")
+        if s.device != m.device:
+            raise ValueError("snap_labels: the segment maps and the label maps are on different devices")
+    for k in counts:
+        _int_in("snap_labels", "a segment count", k, 1, ops.SEG_VOTE_MAX_SEGMENTS)
+    limit = ops.SEG_WIDE_MAX_CLASSES if labels[0].dtype == torch.int16 else 256
+    _int_in("snap_labels", f"num_classes ({'int16' if limit > 256 else 'uint8'} labels)", num_classes, 1, limit)
+    batch = _Maps.of(labels)
+    # the segment ids at the labels' offsets: where both lists lie packed in list order (predict_raw's maps under
+    # out_shapes = the raw sizes never do: the label kernels start every map at a multiple of 4) the ids are read where they are
+    store = segments[0].untyped_storage().data_ptr()
+    lo = min(s.storage_offset() for s in segments)
+    if all(s.is_contiguous() and s.untyped_storage().data_ptr() == store for s in segments) \
+            and [s.storage_offset() - lo for s in segments] == batch.offs \
+            and max(s.storage_offset() + s.numel() for s in segments) - lo == batch.flat.numel():
+        ids = torch.as_strided(segments[0], (batch.flat.numel(),), (1,), lo)
+    else:
+        ids = torch.zeros(batch.flat.numel(), dtype=torch.int32, device=batch.flat.device)
+        for v, s in zip(_Maps(ids, batch.offs, batch.sizes).views(), segments):
+            v.copy_(s)
+    return _vote(batch, ids, counts, num_classes, min_share)
+
+
+def _vote(batch, ids, counts, num_classes, min_share):
+    """batch: the label maps, ids: flat int32 segment ids at the labels' offsets -> the snapped maps, a _Maps over a new buffer"""
+    table, n_blocks, total, top = ops.seg_vote_table(batch.sizes, batch.offs, counts, batch.flat.device)
+    out = batch.empty_like()
+    ops.seg_vote(table, n_blocks, batch.flat, ids, total, num_classes, min_share=min_share, out=out.flat, max_count=top)
+    return out
+
+
+def _snap_stage(raws, labels, num_classes, snap):
+    """The snap stage of the chain: the superpixels of the pictures written at the label maps' own offsets, then the vote
+    -> the snapped maps, a _Maps over one new buffer"""
+    _check_snap(snap)
+    raws = list(raws)
+    _check_pictures(raws, labels)
+    batch = _Maps.of(labels)
+    sp = snap.superpixels
+    table, n_blocks, side, counts = ops.seg_superpixels_table(raws, sp.step, batch.offs)
+    ids = torch.empty(batch.flat.numel(), dtype=torch.int32, device=batch.flat.device)   # only the maps' own entries are ever read
+    ops.seg_superpixels(table, n_blocks, ids, sum(counts), sp.step, sp.compactness, sp.iters, max_side=side)
+    return _vote(batch, ids, counts, num_classes, snap.min_share)
+
+
+@torch.no_grad()
+def snap_labels(labels, segments, num_classes, counts=None, min_share=0):
+    """labels [(h_i, w_i) label maps, all uint8 or all int16 (16-bit maps read as unsigned values)], segments (a Segments, what
+    superpixels returns, or a list of (h_i, w_i) int32 maps of the caller's own - Felzenszwalb maps, flattened instance masks
+    - with counts [K_i]: the ids of image i are 0 .. K_i - 1) -> [(h_i, w_i) maps of the labels' dtype], views of one new
+    buffer: every segment gives its pixels the label most of them carry (csrc/segment_vote.inc; the definition stands in
+    include/segclip_hip.h).  A pixel votes when its label is below num_classes and its id lies in 0 .. K_i - 1; among equal
+    counts the smallest class wins; a segment snaps when the winner holds at least min_share percent (an integer, 0 .. 100) of
+    its voters; every other pixel keeps its value (a label >= num_classes such as an ignore value, an id outside the range,
+    a segment that does not snap).  All maps in one call and without a host synchronisation.  The inputs stay as they are."""
+    return _snap_maps(labels, segments, num_classes, counts, min_share).views()
+
+
+class Snap:
+    """Snapping as a post-processing step of the label maps: the superpixels of the decoded picture (`superpixels`, a
+    Superpixels) vote, and every superpixel whose most frequent label holds at least `min_share` percent of it takes that label
+    (snap_labels).  The third answer, beside PAMR and Despeckle, to label maps whose borders follow the patch grid: it is cheap,
+    needs no soft masks and composes with both.  The reference has no such step."""
+
+    def __init__(self, superpixels=None, min_share=0):
+        sp = Superpixels() if superpixels is None else superpixels
+        if not isinstance(sp, Superpixels):
+            raise TypeError("Snap: superpixels is a Superpixels")
+        self.superpixels, self.min_share = sp, _check_min_share("Snap", min_share)
+
+
+def _check_snap(snap):
+    if not isinstance(snap, Snap):
+        raise TypeError("snap is a Snap")
+
+
 class Boundary:
     """The band of the boundary metrics: the pixels of a map within `radius` pixels (Chebyshev distance) of a pixel with another
     label or of the picture frame.  ratio: the radius as a share of the map's diagonal, d = max(1, round(ratio * sqrt(h^2 +
@@ -698,19 +867,25 @@ def boundary_areas(preds, gts, num_classes, boundary, ignore_index=255, reduce_z
     return areas
 
 
-def _check_stages(refine, clean, raws, out_shapes):
-    """refine= and clean= of predict_raw / update_raw: a PAMR, with label maps at the pictures' own sizes, and a Despeckle.  It
-    runs before the source is built: what the host does between the source's table copy and the first launch is not hidden
-    behind the device's work."""
+def _check_stages(refine, clean, raws, out_shapes, snap=None):
+    """refine=, snap= and clean= of predict_raw / update_raw: a PAMR and a Snap, each with label maps at the pictures' own
+    sizes, and a Despeckle.  It runs before the source is built: what the host does between the source's table copy and the
+    first launch is not hidden behind the device's work."""
     if clean is not None:
         _check_clean(clean)
     if refine is not None and not isinstance(refine, PAMR):
         raise TypeError("refine is a PAMR")
-    if refine is not None and out_shapes is not None:
-        sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
-        if [(int(a), int(b)) for (a, b) in out_shapes] != sizes:
+    if snap is not None:
+        _check_snap(snap)
+    if (refine is None and snap is None) or out_shapes is None:
+        return
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in raws]
+    if [(int(a), int(b)) for (a, b) in out_shapes] != sizes:
+        if refine is not None:
             raise ValueError(f"refine: out_shapes must be the raw images' own sizes {sizes} (the refinement reads the picture under "
                              f"every label), got {list(out_shapes)}")
+        raise ValueError(f"snap: out_shapes must be the raw images' own sizes {sizes} (a superpixel lies in the picture under "
+                         f"the labels), got {list(out_shapes)}")
 
 
 def _refuse(entry, *stages):
@@ -976,27 +1151,35 @@ class SegInference:
                                 reduce_zero_label=reduce_zero_label)
         return None if labels is None else _Maps(labels, offs, out_shapes).views()
 
-    def _post_process(self, src, out_shapes, refine=None, clean=None, score=None, want_labels=True):
+    def _post_process(self, src, out_shapes, refine=None, clean=None, score=None, want_labels=True, snap=None):
         """The chain of every list entry point that returns or scores label maps: labels -> refine (a PAMR, against
-        src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas -> the confusion matrix.  score: None, or the _Score of an
+        src.pictures) -> snap (a Snap, against src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas -> the
+        confusion matrix.  score: None, or the _Score of an
         evaluator's call; the areas are those of the maps that leave the chain, counted once (`counts`), by
 
-            refine   clean       the mIoU areas are counted by
-            -        -           the label kernel
-            PAMR     -           the refinement's last kernel; the label kernel only writes the maps
-            any      Despeckle   ops.seg_areas on the cleaned maps, gapless; nothing earlier counts
+            refine   snap   clean       the mIoU areas are counted by
+            -        -      -           the label kernel
+            PAMR     -      -           the refinement's last kernel; the label kernel only writes the maps
+            any      Snap   -           ops.seg_areas on the snapped maps, laid gapless; nothing earlier counts
+            any      any    Despeckle   ops.seg_areas on the cleaned maps, gapless; nothing earlier counts
 
         and with score.boundary one more ops.seg_boundary call on the same maps adds to score.boundary_areas, with
         score.confusion one ops.seg_confusion call on them, laid gapless, to that matrix.  The labels are
         formed whenever a later stage reads them, wanted or not.  -> the final maps, or None when they are not wanted."""
         forward = self._views_forward if src.augmented else self._list_forward
-        counts = None if score is None else "clean" if clean is not None else "refine" if refine is not None else "labels"
+        counts = (None if score is None else "clean" if clean is not None else "snap" if snap is not None else
+                  "refine" if refine is not None else "labels")
         counting = {} if score is None else dict(gts=score.gts, areas=score.areas, **score.rule)
         reads_labels = score is not None and (score.boundary is not None or score.confusion is not None)
         first = dict(counting, want_labels=want_labels or reads_labels) if counts == "labels" else {}
         labels = forward(src, out_shapes, **first)
         if refine is not None:
             labels = _refine_maps(src.pictures, labels, self.num_classes, src.transform, refine, **(counting if counts == "refine" else {}))
+        if snap is not None:
+            snapped = _snap_stage(src.pictures, labels, self.num_classes, snap)
+            labels = snapped.views()
+            if counts == "snap":
+                ops.seg_areas(snapped.gapless(), _Maps.gapless_of(score.gts)[0], self.num_classes, areas=score.areas, **score.rule)
         if clean is not None:
             cleaned = _despeckle_maps(labels, clean)
             labels = cleaned.views()
@@ -1011,18 +1194,19 @@ class SegInference:
         return labels if want_labels else None
 
     @torch.no_grad()
-    def predict_list(self, imgs, out_shapes=None, refine=None, clean=None):
+    def predict_list(self, imgs, out_shapes=None, refine=None, clean=None, snap=None):
         """[(3, H_i, W_i)] of any mix of sizes -> [(oh_i, ow_i) uint8 labels], views of one flat buffer; out_shapes defaults
         to the images' own sizes.  The logits are rescaled bilinearly (align_corners=False) to the output size and the first
         maximum taken there, as mmseg's resize(size=ori_shape) + arg-max, inside one kernel launch for the whole list.
         Slide mode: the windows of all images go through encode_image max_windows at a time; whole mode: one call per size.
-        refine is refused: there is no raw picture here (predict_raw has it); clean too: despeckle the maps."""
+        refine and snap are refused: there is no raw picture here (predict_raw has it); clean too: despeckle the maps."""
         _refuse("predict_list", ("refine", refine, "needs the decoded pictures: use predict_raw(refine=) or refine_labels"),
+                ("snap", snap, "needs the decoded pictures: use predict_raw(snap=) or snap_labels"),
                 ("clean", clean, "is not supported; apply despeckle to the maps it returns"))
         return self._list_forward(_SlicedImages([[(t, 0)] for t in imgs]), out_shapes)
 
     @torch.no_grad()
-    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None, refine=None, clean=None):
+    def predict_raw(self, raws, transform, out_shapes=None, net_sizes=None, aug=None, refine=None, clean=None, snap=None):
         """[(h_i, w_i, 3) uint8 decoded images] -> [(oh_i, ow_i) uint8 labels] as predict_list(preprocess(raws, transform,
         net_sizes), out_shapes), bit for bit, without the resized images: the windows of a tower call are written from the
         raw bytes by one launch of segclip_seg_windows_from_u8.  out_shapes defaults to the raw images' own sizes (mmseg's
@@ -1033,12 +1217,16 @@ class SegInference:
         refine (a PAMR): the label maps pass through the pixel-adaptive refinement against the raw pictures before they are
         returned, = refine_labels(raws, predict_raw(raws, ...), num_classes, transform, refine) bit for bit.  out_shapes must
         then be the raw sizes (the default).  It composes with aug: the refinement sees only labels.
-        clean (a Despeckle): the maps, after the refinement if there is one, are despeckled before they are returned,
-        = despeckle(predict_raw(raws, ...), ...) bit for bit.
-        With label_dtype=torch.int16 the maps are int16, and aug, refine and clean are refused."""
-        self._refuse_wide("predict_raw", aug=aug, refine=refine, clean=clean)
-        _check_stages(refine, clean, raws, out_shapes)
-        return self._post_process(_RawImages(raws, transform, net_sizes, aug), out_shapes, refine, clean)
+        snap (a Snap): the maps, after the refinement if there is one, are snapped to the superpixels of the raw pictures,
+        = snap_labels(predict_raw(raws, ...), superpixels(raws, snap.superpixels), num_classes, min_share=snap.min_share) bit
+        for bit.  out_shapes must then be the raw sizes (the default).
+        clean (a Despeckle): the maps, after the refinement and the snapping if there are any, are despeckled before they are
+        returned, = despeckle(predict_raw(raws, ...), ...) bit for bit.
+        With label_dtype=torch.int16 the maps are int16, and aug, refine, snap and clean are refused (snap_labels and despeckle
+        take the int16 maps this returns)."""
+        self._refuse_wide("predict_raw", aug=aug, refine=refine, snap=snap, clean=clean)
+        _check_stages(refine, clean, raws, out_shapes, snap)
+        return self._post_process(_RawImages(raws, transform, net_sizes, aug), out_shapes, refine, clean, snap=snap)
 
     @torch.no_grad()
     def predict_views(self, views, out_shapes):
@@ -1076,7 +1264,8 @@ class SegInference:
         return self._list_forward(_RawImages(raws, transform, net_sizes), out_shapes, groups="only")[1]
 
     @torch.no_grad()
-    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None, refine=None, clean=None):
+    def render_raw(self, raws, transform, vis_modes, palette, group_palette=None, net_sizes=None, refine=None, clean=None,
+                   snap=None):
         """The reference's --vis modes (show_result, vit_seg.py:286-377) for decoded images, at their own sizes -> dict
         mode -> result:
           input              the raws
@@ -1088,9 +1277,10 @@ class SegInference:
         palette: (P, 3) uint8 RGB class colours (index 0 = background when with_bg); group_palette defaults to
         default_group_palette(G).  Channel order of the pictures: transform.channel_order.  The vision tower runs once per
         call whatever the modes: labels and group maps come from the same encode_image pass.  refine is refused: draw refined
-        maps with blend(raws, predict_raw(raws, transform, refine=...), palette).  clean is refused in the same way."""
+        maps with blend(raws, predict_raw(raws, transform, refine=...), palette).  snap and clean are refused in the same way."""
         self._refuse_wide("SegInference", render_raw=vis_modes)
         _refuse("render_raw", ("refine", refine, "is not supported; blend the maps of predict_raw(refine=) instead"),
+                ("snap", snap, "is not supported; blend the maps of predict_raw(snap=) instead"),
                 ("clean", clean, "is not supported; blend the maps of despeckle(predict_raw(...)) instead"))
         modes = list(vis_modes)
         for m in modes:
@@ -1249,27 +1439,30 @@ class SegEvaluator:
         return _Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas, self.confusion), [tuple(g.shape) for g in gts]
 
     @torch.no_grad()
-    def update(self, imgs, gts, return_labels=False, refine=None, clean=None):
-        """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size.  refine is
-        refused: there is no raw picture here (update_raw has it); clean is refused too (update_raw has it)."""
+    def update(self, imgs, gts, return_labels=False, refine=None, clean=None, snap=None):
+        """imgs [(3, H_i, W_i)], gts [(oh_i, ow_i) uint8]: the labels are formed at each ground truth's size.  refine and snap
+        are refused: there is no raw picture here (update_raw has it); clean is refused too (update_raw has it)."""
         _refuse("SegEvaluator.update", ("refine", refine, "needs the decoded pictures: use update_raw(refine=)"),
+                ("snap", snap, "needs the decoded pictures: use update_raw(snap=)"),
                 ("clean", clean, "is not supported; use update_raw(clean=), or despeckle the maps and score them with ops.seg_areas"))
         self._check_gts(imgs, gts, self.gt_dtype)
         score, shapes = self._score(gts)
         return self.seg._post_process(_SlicedImages([[(t, 0)] for t in imgs]), shapes, score=score, want_labels=return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None, snap=None):
         """raws [(h_i, w_i, 3) uint8 decoded images] instead of pre-processed ones, as SegInference.predict_raw (aug included).
         refine (a PAMR): the areas are those of the refined label maps, added by the refinement's last kernel; the label
         kernel then only writes the maps and counts nothing.  The ground truths must have the pictures' sizes.
-        clean (a Despeckle): the labels are formed (and refined) without counting, despeckled, and ops.seg_areas of the cleaned
-        maps against the ground truths is added: the areas are those of the cleaned maps."""
-        self.seg._refuse_wide("SegEvaluator.update_raw", aug=aug, refine=refine, clean=clean)
+        snap (a Snap): the labels are formed (and refined) without counting, snapped to the pictures' superpixels, and
+        ops.seg_areas of the snapped maps against the ground truths is added.  The ground truths must have the pictures' sizes.
+        clean (a Despeckle): the labels are formed (and refined, and snapped) without counting, despeckled, and ops.seg_areas of
+        the cleaned maps against the ground truths is added: the areas are those of the cleaned maps."""
+        self.seg._refuse_wide("SegEvaluator.update_raw", aug=aug, refine=refine, snap=snap, clean=clean)
         self._check_gts(raws, gts, self.gt_dtype)
         score, shapes = self._score(gts)
-        _check_stages(refine, clean, raws, shapes)
-        return self.seg._post_process(_RawImages(raws, transform, net_sizes, aug), shapes, refine, clean, score, return_labels)
+        _check_stages(refine, clean, raws, shapes, snap)
+        return self.seg._post_process(_RawImages(raws, transform, net_sizes, aug), shapes, refine, clean, score, return_labels, snap=snap)
 
     @torch.no_grad()
     def update_maps(self, preds, gts):
@@ -1491,9 +1684,11 @@ class SegSweepEvaluator:
         return self._forward(_SlicedImages([[(t, 0)] for t in imgs]), gts, return_labels)
 
     @torch.no_grad()
-    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None):
-        """As SegEvaluator.update_raw, without aug, without refine and without clean."""
+    def update_raw(self, raws, gts, transform, return_labels=False, net_sizes=None, aug=None, refine=None, clean=None, snap=None):
+        """As SegEvaluator.update_raw, without aug, without refine, without snap and without clean."""
         _refuse("SegSweepEvaluator",
+                ("snap", snap, "is not supported (every threshold's map would need its own vote); use one SegEvaluator per "
+                               "threshold (update_raw(snap=))"),
                 ("clean", clean, "is not supported (every threshold's map would need its own pass); despeckle the maps of one "
                                  "SegEvaluator per threshold (update_raw(clean=))"),
                 ("refine", refine, "is not supported (every threshold's map would need its own refinement); use one SegEvaluator "

@@ -291,14 +291,16 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     figure over all ranks is wanted.  test_cfg["aug"] (a segmentation.TestAug; needs transform): mmseg's flip / multi-scale
     test-time augmentation, SegEvaluator.update_raw(aug=).  test_cfg["refine"] (a segmentation.PAMR; needs transform): the
     label maps are refined against the decoded pictures before they are scored, SegEvaluator.update_raw(refine=).
+    test_cfg["snap"] (a segmentation.Snap; needs transform): the label maps, after the refinement if both are given, are snapped
+    to the superpixels of the decoded pictures before they are scored, SegEvaluator.update_raw(snap=).
     test_cfg["clean"] (a segmentation.Despeckle; needs transform): connected components of the label maps below its minimum
-    area are replaced by its fill label before the maps are scored, after the refinement if both are given,
+    area are replaced by its fill label before the maps are scored, after the refinement and the snapping if they are given,
     SegEvaluator.update_raw(clean=).  test_cfg["boundary"] (a segmentation.Boundary): the labels are also scored on their
     boundary bands, SegEvaluator(boundary=), and the function returns a dict instead of the number: mIoU, mbIoU, trimap_mIoU
     and trimap_aAcc in percent and the per-class bIoU and trimap_IoU tensors in percent; boundary_areas stays this rank's like
     areas.  test_cfg["label_dtype"] = torch.int16 (a SegInference argument): vocabularies of up to 1024 classes; gts are then
     (oh, ow) torch.int16 tensors read as unsigned 16-bit values (a uint16 array goes in as .view(torch.int16)) and
-    test_cfg["ignore_index"] is an integer in 0 .. 65535, e.g. 65535; aug, refine, clean and boundary are refused.
+    test_cfg["ignore_index"] is an integer in 0 .. 65535, e.g. 65535; aug, refine, snap, clean and boundary are refused.
     test_cfg["confusion"] = True: the labels are also counted into the confusion matrix, SegEvaluator(confusion=True), 8- or
     16-bit maps alike, and the function returns a dict: mIoU, mDice, mFscore and fwIoU in percent, kappa, and `confusion`, the
     (C + 1, C + 1) int64 CPU tensor of this rank (rows the ground truth, index C the out-of-range bin), beside the boundary
@@ -312,6 +314,9 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     refine = cfg.pop("refine", None)
     if refine is not None and transform is None:
         raise ValueError("eval_epoch: test_cfg['refine'] refines against the decoded images: pass a transform")
+    snap = cfg.pop("snap", None)
+    if snap is not None and transform is None:
+        raise ValueError("eval_epoch: test_cfg['snap'] snaps to the superpixels of the decoded images: pass a transform")
     clean = cfg.pop("clean", None)
     if clean is not None and transform is None:
         raise ValueError("eval_epoch: test_cfg['clean'] is applied by SegEvaluator.update_raw: pass a transform")
@@ -327,7 +332,7 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
         if transform is None:
             evaluator.update(imgs, gts)
         else:
-            evaluator.update_raw(imgs, gts, transform, aug=aug, refine=refine, clean=clean)
+            evaluator.update_raw(imgs, gts, transform, aug=aug, refine=refine, clean=clean, snap=snap)
     metrics = evaluator.compute()
     miou = metrics["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:

@@ -100,11 +100,20 @@ command and alternating within every repeat:
         `rocprofv3 --kernel-trace --stats` child (--wide-post-child: five calls of each on both widths and nothing else).
         The output file keeps whatever stands above the line "# ---- tools/bench_seg.py --wide-post" (the kernels' resource
         tables) and replaces what follows it.
+With --snap instead: superpixels and majority voting (superpixels, snap_labels, update_raw(snap=); csrc/segment_superpixel.inc
+and segment_vote.inc) on the inputs of --raw (64 decoded images of mixed VOC-like sizes, 12.0 M pixels, 21 classes), in ONE
+command and alternating within every repeat:
+  (xv)  update_raw (the path without the stage: the yardstick), update_raw(snap=Snap()), superpixels alone and snap_labels alone
+        on update_raw's label maps: medians, min-max, the clock held, the peak allocation of the two stand-alone calls, the
+        share of the labels the stage moves, the host route (the numpy restatement of tests/superpixel_reference.py on .cpu()
+        copies of 8 maps, scaled to 64), and the new kernels' own times from a separate `rocprofv3 --kernel-trace --stats`
+        child (--snap-child: five calls of superpixels and snap_labels and nothing else) against their design traffic
+        (DESIGN.md section 4).
 usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge | --confusion |
-                                  --wide-post]
+                                  --wide-post | --snap]
                                  [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
                                   seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt | seg_confusion.txt |
-                                  seg_wide_post.txt]"""
+                                  seg_wide_post.txt | seg_snap.txt]"""
 import os
 import statistics
 import sys
@@ -130,13 +139,14 @@ MERGE, MERGE_CHILD = ("--merge" in sys.argv[1:]), ("--merge-child" in sys.argv[1
 CONFUSION = "--confusion" in sys.argv[1:]
 WIDE_POST, WIDE_POST_CHILD = ("--wide-post" in sys.argv[1:]), ("--wide-post-child" in sys.argv[1:])
 WIDE_POST_MARK = "# ---- tools/bench_seg.py --wide-post"
+SNAP, SNAP_CHILD = ("--snap" in sys.argv[1:]), ("--snap-child" in sys.argv[1:])
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
                                              "--boundary-child", "--wide", "--merge", "--merge-child", "--confusion", "--wide-post",
-                                             "--wide-post-child")]
+                                             "--wide-post-child", "--snap", "--snap-child")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_wide_post.txt" if WIDE_POST else "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_snap.txt" if SNAP else "seg_wide_post.txt" if WIDE_POST else "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -1427,6 +1437,110 @@ def wide_post_child(model, text):
     torch.cuda.synchronize()
 
 
+def snap_inputs(model, text, n_images=64):
+    """-> (seg, transform, raws, gts, update_raw's label maps as clones) on the inputs of --raw"""
+    from segclip_amd.segmentation import ImageTransform, SegEvaluator
+    seg = SegInference(model, text, True, bg_thresh=0.80, mode="slide", crop_size=(224, 224), stride=(224, 224))
+    tf = ImageTransform()
+    raws, gts = raw_inputs(seg, n_images)
+    with torch.no_grad():
+        maps = [m.clone() for m in SegEvaluator(seg).update_raw(raws, gts, tf, return_labels=True)]
+    return seg, tf, raws, gts, maps
+
+
+def snap_case(model, text, n_images=64):
+    import numpy as np
+    from segclip_amd.segmentation import SegEvaluator, Snap, snap_labels, superpixels
+    from tests import superpixel_reference as sr
+    from tools import rocprof_roofline as rr
+    name = f"(xv) snap   {n_images} mixed sizes"
+    seg, tf, raws, gts, maps = snap_inputs(model, text, n_images)
+    snap, C = Snap(), seg.num_classes
+    sp = snap.superpixels
+    pixels = sum(int(m.numel()) for m in maps)
+    ev = SegEvaluator(seg)
+    with torch.no_grad():
+        segments = superpixels(raws, sp)
+    k_total = sum(segments.counts)
+    ways = [("update_raw", lambda: ev.update_raw(raws, gts, tf)),
+            ("update_raw(snap=Snap())", lambda: ev.update_raw(raws, gts, tf, snap=snap)),
+            ("superpixels alone", lambda: superpixels(raws, sp)),
+            ("snap_labels alone", lambda: snap_labels(maps, segments, C, min_share=snap.min_share))]
+    with torch.no_grad():
+        for _, fn in ways:
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):   # alternating: every repeat times the four ways one after the other
+            for k, (_, fn) in enumerate(ways):
+                t0 = time.perf_counter()
+                fn()
+                fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) / 2)
+        clk = sampler.stop()
+        snapped = snap_labels(maps, segments, C, min_share=snap.min_share)
+        moved = sum(int((a != b).sum()) for a, b in zip(snapped, maps))
+    meds = [statistics.median(t) for t in ts]
+    say(f"{name}: {pixels} pixels, {C} classes, Snap(Superpixels(step={sp.step}, compactness={sp.compactness}, iters={sp.iters}), "
+        f"min_share={snap.min_share}): {k_total} superpixels; {REPS} repeats x 2 calls, the ways alternating within each repeat; clock {clk}")
+    for (what, _), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:26s} {med * 1e3:8.2f} ms (min {min(t) * 1e3:.2f}, max {max(t) * 1e3:.2f})  {n_images / med:8.1f} images/s")
+    say(f"{name}: update_raw(snap=) / update_raw {meds[1] / meds[0]:.4f}; the stage moves {moved} of {pixels} labels "
+        f"({moved / pixels:.4f}; random pictures under the label maps of synthetic weights)")
+    say(f"{name}: peak allocation beyond the inputs: superpixels {peak_of(ways[2][1]) / 2 ** 20:.1f} MiB (4 B of ids per pixel + 44 B per "
+        f"centre), snap_labels {peak_of(ways[3][1]) / 2 ** 20:.1f} MiB (the ids at the labels' offsets, the output and "
+        f"{k_total * (C + 1) * 4 / 2 ** 20:.1f} MiB of counts and winners)")
+    # the host route: the numpy restatement on .cpu() copies of 8 maps
+    n_host = min(8, n_images)
+    t0 = time.perf_counter()
+    for r, m in zip(raws[:n_host], maps[:n_host]):
+        ids, cen = sr.slic(r.cpu().numpy(), sp.step, sp.compactness, sp.iters)
+        torch.from_numpy(sr.vote(m.cpu().numpy(), ids, cen.shape[0], C, snap.min_share)).cuda()
+    torch.cuda.synchronize()
+    host = (time.perf_counter() - t0) * n_images / n_host
+    say(f"{name}: host route (numpy restatement on .cpu() copies, {n_host} maps scaled to {n_images}) {host * 1e3:10.1f} ms = "
+        f"{host / (meds[2] + meds[3]):.0f} x superpixels + snap_labels")
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            rc, _, err = rr.run_child([os.path.abspath(__file__), "--snap-child"], tmp)
+            db = rr.find_db(tmp)
+            table = rr.kernel_table(db) if rc == 0 and db else []
+        except Exception as e:   # no rocprofv3 on the box
+            rc, err, table = -1, repr(e), []
+    rows = [r for r in table if any(tag in r[0] for tag in ("seg_sp_", "seg_vote_"))]
+    if not rows:
+        say(f"{name}: the kernels alone: unmeasured (rocprofv3 child rc={rc}: {err[-200:]})")
+    raw_bytes = sum(int(r.numel()) for r in raws)
+    design = {"seg_sp_assign_kernel<false>": raw_bytes, "seg_sp_assign_kernel<true>": raw_bytes + 4 * pixels,
+              "seg_vote_count_kernel": 5 * pixels, "seg_vote_apply_kernel": 6 * pixels, "seg_vote_winner_kernel": k_total * (C + 1) * 4}
+    for r in rows:
+        start = min(r[0].find(tag) for tag in ("seg_sp_", "seg_vote_") if tag in r[0])
+        kernel = r[0][start:]
+        avg_us = r[2] / r[1]
+        note = ""
+        for key, nbytes in design.items():
+            if kernel.startswith(key):   # an instantiation of the assignment by its template argument, the others by name
+                note = f"  design traffic {nbytes} B = {nbytes / avg_us / 1e6:.3f} TB/s ({nbytes / avg_us * 1e6 / HBM_PEAK:.3f} of the HBM peak)"
+        say(f"{name}: {kernel[:48]:48s} alone (rocprofv3 --kernel-trace --stats, {r[1]} launches in the child's 5 calls of each) "
+            f"{avg_us:9.1f} us per launch{note}")
+
+
+def snap_child(model, text):
+    """Five calls of superpixels and of snap_labels and nothing else: what the rocprofv3 child of snap_case traces."""
+    from segclip_amd.segmentation import Snap, snap_labels, superpixels
+    seg, _, raws, _, maps = snap_inputs(model, text)
+    snap = Snap()
+    with torch.no_grad():
+        for _ in range(5):
+            segments = superpixels(raws, snap.superpixels)
+            snap_labels(maps, segments, seg.num_classes, min_share=snap.min_share)
+    torch.cuda.synchronize()
+
+
 def write_out():
     """the lines of this run into OUT; --wide-post keeps what stands above its mark (the kernels' resource tables)"""
     head = []
@@ -1471,7 +1585,12 @@ if __name__ == "__main__":
     if WIDE_POST_CHILD:
         wide_post_child(model, text)
         sys.exit(0)
-    if WIDE_POST:
+    if SNAP_CHILD:
+        snap_child(model, text)
+        sys.exit(0)
+    if SNAP:
+        snap_case(model, text)
+    elif WIDE_POST:
         wide_post_case(model, text)
     elif CONFUSION:
         confusion_case(model)
