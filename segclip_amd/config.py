@@ -88,8 +88,8 @@ _warned_env = set()
 
 
 def tuning_env(name, default):
-    """A/B switch read from the environment.  Honoured only with SEGCLIP_TUNING=1 (the same gate as the native library's
-    kernel-selection variables, csrc/common.h): a production process cannot have its kernels re-routed by a stray variable,
+    """Default of a config option read from the environment (the six aliases below; the native library reads no environment
+    variable).  Honoured only with SEGCLIP_TUNING=1: a production process cannot have its options changed by a stray variable,
     and one that tries is told so once per variable."""
     import os
     v = os.environ.get(name)

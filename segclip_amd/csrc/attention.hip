@@ -110,8 +110,8 @@ struct FwdArgs {
   int64_t q_sb, q_st, k_sb, k_st, v_sb, v_st, o_sb, o_st;
   float scale; int causal;
   const int* klen;  // nullable: valid keys per sample
-  int staged;       // bf16 forward: output rows through LDS (SEGCLIP_ATTN_FWD_STAGED)
-  int lean;         // bf16 forward: the lean softmax step on unmasked key tiles (SEGCLIP_ATTN_FWD_LEAN, default on)
+  int staged;       // bf16 forward: output rows through LDS (plan_fwd: more than 128 queries)
+  int lean;         // bf16 forward: the lean softmax step on unmasked key tiles (segclip_attn_fwd passes 1)
 };
 
 constexpr int KCHUNK = 256;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
   }
   // Output.  The accumulators hold transposed tiles (lane = query row, registers = 4 consecutive columns): stored from
-  // registers every instruction touches 32 rows with 8 bytes each.  With SEGCLIP_ATTN_FWD_STAGED (a.staged) the tile goes
+  // registers every instruction touches 32 rows with 8 bytes each.  With a.staged the tile goes
   // through the wave's own 4 KB of the K tile instead (free once every wave has left the key loop): 8-byte LDS writes,
   // 16-byte reads of whole 128-byte rows, 16-byte coalesced global stores.
   if (a.staged) {
@@ -665,18 +665,7 @@ bool bf16_ok(const segclip_attn_desc* d) {
   return d->hd % 8 == 0 && d->hd <= 64;
 }
 
-// the tuning switches of the dispatcher (common.h), read once; each is explained where it is asked
-struct Tuning {
-  int smallq = segclip_tuning_int("SEGCLIP_ATTN_SMALLQ", 1);
-  int fwd_staged = segclip_tuning_int("SEGCLIP_ATTN_FWD_STAGED", -1), fwd_lean = segclip_tuning_int("SEGCLIP_ATTN_FWD_LEAN", 1);
-  int fwd_pf = segclip_tuning_int("SEGCLIP_ATTN_FWD_PF", 1), fwd_grid = segclip_tuning_int("SEGCLIP_ATTN_FWD_GRID", 0);
-  int bwd_dqw_long = segclip_tuning_int("SEGCLIP_ATTN_BWD_DQW_LONG", 1), bwd_dqw = segclip_tuning_int("SEGCLIP_ATTN_BWD_DQW", 1);
-  int bwd_sp = segclip_tuning_int("SEGCLIP_ATTN_BWD_SP", 1), bwd_spl = segclip_tuning_int("SEGCLIP_ATTN_BWD_SPL", 1);
-  int bwd_grid = segclip_tuning_int("SEGCLIP_ATTN_BWD_GRID", -1), bwd_waves = segclip_tuning_int("SEGCLIP_ATTN_BWD_WAVES", 0);
-};
-const Tuning& tuning() { static const Tuning t; return t; }
-
-// ---- the planner: pure functions of the descriptor and the switches, no HIP call ----
+// ---- the planner: pure functions of the descriptor, no HIP call ----
 struct Plan {
   int route, tiles, variant;   // what segclip_attn_route_note records after the launch
   int waves;                   // per workgroup, a loader / dQ wave included (0: the streaming pair sizes its own)
@@ -687,18 +676,15 @@ int tiles_of(const segclip_attn_desc* d) { return (int)cdiv(d->Tq > d->Tk ? d->T
 bool long_seq(const segclip_attn_desc* d) { return d->Tq > TMAX || d->Tk > TMAX; }
 
 Plan plan_fwd(const segclip_attn_desc* d) {
-  const Tuning& t = tuning();
   if (d->dtype != SEGCLIP_BF16) return {SEGCLIP_ATTN_ROUTE_F32, tiles_of(d)};
   // LDS-staged output rows: 117 -> 112 us at T = 196 (B = 256, H = 12), 27.8 -> 29.3 us at T = 77: on for the long sequences
-  // (SEGCLIP_ATTN_FWD_STAGED = 0 / 1 forces them off / on)
-  const int staged = t.fwd_staged >= 0 ? t.fwd_staged : (d->Tq > 128 ? 1 : 0);
-  // at most 8 queries (the learnable-center cross-attention): one wave per (batch, head), VALU.  SEGCLIP_ATTN_SMALLQ=0: off
-  if (t.smallq && smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_FWD, smallq::lds_bytes((int)d->Tk, false), staged};
+  const int staged = d->Tq > 128 ? 1 : 0;
+  // at most 8 queries (the learnable-center cross-attention): one wave per (batch, head), VALU
+  if (smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_FWD, smallq::lds_bytes((int)d->Tk, false), staged};
   const int tiles = (int)cdiv(d->Tq, 32);
   const size_t pf_lds = fwd_pf_lds_bytes(tiles, (int)d->Tq);
-  // self-attention of 65..96 / 161..200 tokens: the persistent kernel with a loader wave (attention_pf.inc);
-  // SEGCLIP_ATTN_FWD_PF=0 falls back to one workgroup per (batch, head)
-  if (t.fwd_pf && d->Tq == d->Tk && !(d->flags & SEGCLIP_ATTN_FP8) && (tiles == 3 || tiles == 6 || tiles == 7) && pf_lds <= 160 * 1024)
+  // self-attention of 65..96 / 161..200 tokens: the persistent kernel with a loader wave (attention_pf.inc)
+  if (d->Tq == d->Tk && !(d->flags & SEGCLIP_ATTN_FP8) && (tiles == 3 || tiles == 6 || tiles == 7) && pf_lds <= 160 * 1024)
     return {SEGCLIP_ATTN_ROUTE_PF, tiles, d->causal ? 1 : 0, tiles + 1, pf_lds, staged};
   // one wave per query tile, at most 8 per workgroup, spread evenly over the workgroups of a (batch, head)
   const int nw = tiles < 8 ? tiles : (tiles <= 8 ? 8 : (int)cdiv(tiles, cdiv(tiles, 8)));
@@ -706,41 +692,35 @@ Plan plan_fwd(const segclip_attn_desc* d) {
 }
 
 Plan plan_bwd(const segclip_attn_desc* d) {
-  const Tuning& t = tuning();
   const int tiles = tiles_of(d);
   if (d->dtype != SEGCLIP_BF16) return {SEGCLIP_ATTN_ROUTE_F32, tiles};
-  if (t.smallq && smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_BWD, smallq::lds_bytes((int)d->Tk, true)};
+  if (smallq::covers(d)) return {SEGCLIP_ATTN_ROUTE_SMALLQ, 1, 0, smallq::WPB_BWD, smallq::lds_bytes((int)d->Tk, true)};
   if (long_seq(d)) {
-    // unmasked self-attention, head_dim 64: the dQ-wave kernel over chunks of 224 keys (attention_dqw.inc, MULTI).
-    // SEGCLIP_ATTN_BWD_DQW_LONG=0 (tuning) keeps the two streaming launches
+    // unmasked self-attention, head_dim 64: the dQ-wave kernel over chunks of 224 keys (attention_dqw.inc, MULTI)
     // (its token sums ride on a padded key in the last chunk and on two padded rows of the last query tile)
-    if (t.bwd_dqw_long && d->Tq == d->Tk && !d->causal && d->hd == 64 && d->Tq % 32 <= 30 && d->Tq % 224 != 0)
+    if (d->Tq == d->Tk && !d->causal && d->hd == 64 && d->Tq % 32 <= 30 && d->Tq % 224 != 0)
       return {SEGCLIP_ATTN_ROUTE_DQW, 7, 1, 8, bwd_dqw_lds_bytes<7>()};
     return {SEGCLIP_ATTN_ROUTE_STREAM, tiles, 0, 0, bwd_stream_lds_bytes()};   // two streaming launches (dK,dV | dQ)
   }
   const bool masked = d->causal || d->klen;
-  // self-attention: the single-pass kernels, one wave per key tile.  SEGCLIP_ATTN_BWD_SP=0 falls back to the two-pass kernel
-  // (benchmarking); cross-attention (Tq != Tk) always takes the two-pass kernel.
-  if (t.bwd_sp && d->Tq == d->Tk) {
+  // self-attention: the single-pass kernels, one wave per key tile; cross-attention (Tq != Tk) takes the two-pass kernel
+  if (d->Tq == d->Tk) {
     // vision tower (no mask, head_dim 64, 7 tiles, padded rows in the last tile): the query tiles as a stream with a dQ wave
-    // (attention_dqw.inc, round 6); SEGCLIP_ATTN_BWD_DQW=0 keeps the kernels below
-    if (t.bwd_dqw && !masked && d->hd == 64 && tiles == 7 && d->Tq % 32 >= 1 && d->Tq % 32 <= 30)
+    // (attention_dqw.inc, round 6)
+    if (!masked && d->hd == 64 && tiles == 7 && d->Tq % 32 >= 1 && d->Tq % 32 <= 30)
       return {SEGCLIP_ATTN_ROUTE_DQW, 7, 0, 8, bwd_dqw_lds_bytes<7>()};
     // vision tower (no mask, 5-7 tiles): the variant whose memory traffic is issued by a loader wave (attention_spl.inc);
-    // SEGCLIP_ATTN_BWD_SPL=0 keeps attention_sp.inc
     // head_dim 64 only: its loader wave copies whole 128-byte rows of Q, so with a smaller head the columns beyond it (the next
     // head, or whatever follows the last one) would enter S = K Q^T against zeroed K columns: 0 x NaN, and a read past the
     // end of a separately allocated Q.  Smaller heads take attention_sp.inc, which selects by column.
     const size_t spl_lds = bwd_spl_lds_bytes((int)d->Tq);
-    if (t.bwd_spl && !masked && d->hd == 64 && tiles >= 5 && tiles <= 7 && spl_lds <= 160 * 1024)
+    if (!masked && d->hd == 64 && tiles >= 5 && tiles <= 7 && spl_lds <= 160 * 1024)
       return {SEGCLIP_ATTN_ROUTE_SPL, tiles, 0, tiles + 1, spl_lds};
     return {SEGCLIP_ATTN_ROUTE_SP, tiles, masked ? 1 : 0, tiles, bwd_sp_lds_bytes(tiles * 32)};   // variant: instance <MASKED>
   }
   // 4 waves per workgroup (each wave walks over 1-2 tiles): two such workgroups fit the registers (2 waves per SIMD
-  // at ~215 VGPRs) and the LDS of a CU, so their load / MFMA / store phases interleave.  SEGCLIP_ATTN_BWD_WAVES
-  // overrides (benchmarking).
-  int nw = tiles < 4 ? tiles : 4;
-  if (t.bwd_waves >= 1 && t.bwd_waves <= 8) nw = tiles < t.bwd_waves ? tiles : t.bwd_waves;
+  // at ~215 VGPRs) and the LDS of a CU, so their load / MFMA / store phases interleave
+  const int nw = tiles < 4 ? tiles : 4;
   return {SEGCLIP_ATTN_ROUTE_TWOPASS, tiles, nw << 8, nw, bwd_lds_bytes(tiles * 32)};
 }
 
@@ -790,9 +770,8 @@ int launch_fwd_pf_as(const FwdArgs& a, const Plan& p, int nitems, hipStream_t st
   if (int rc = raise_lds_limit<attn_fwd_pf_kernel<NT, CAUSAL>>("attn_fwd", dv, 160 * 1024)) return rc;
   std::atomic<int>& cached = pf_per_cu[dv.index][CAUSAL][NT][pf_kv_rows(a.Tq) >> 3];
   int per_cu = cached;
-  if (per_cu == 0) {   // SEGCLIP_ATTN_FWD_GRID overrides what the occupancy query says
+  if (per_cu == 0) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_fwd_pf_kernel<NT, CAUSAL>, p.waves * 64, p.lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (tuning().fwd_grid > 0) per_cu = tuning().fwd_grid;
     cached = per_cu;
   }
   return launch<attn_fwd_pf_kernel<NT, CAUSAL>>("attn_fwd_pf", dim3(std::min(nitems, dv.ncu * per_cu)), p.waves, p, stream, a, nitems);
@@ -865,10 +844,9 @@ int launch_bwd_stream(const segclip_attn_desc* d, const BwdArgs& a, const Plan& 
 }
 
 // persistent grid of the single-pass kernels: as many workgroups as the chip holds at once (LDS / registers: 1 per CU at
-// T = 197, more for the short text sequences); SEGCLIP_ATTN_BWD_GRID overrides the number per CU (0 = one workgroup per item)
+// T = 197, more for the short text sequences)
 dim3 bwd_persistent_grid(int nitems, const Device& dv, int per_cu) {
-  const int env = tuning().bwd_grid;
-  return dim3((unsigned)(env == 0 ? nitems : std::min<int64_t>(nitems, (int64_t)dv.ncu * (env > 0 ? env : per_cu))));
+  return dim3((unsigned)std::min<int64_t>(nitems, (int64_t)dv.ncu * per_cu));
 }
 // with a loader wave (attention_spl.inc): one workgroup per CU
 int launch_bwd_spl(const BwdArgs& a, const Plan& p, const Device& dv, hipStream_t stream) {
@@ -957,7 +935,7 @@ extern "C" int segclip_attn_fwd(const segclip_attn_desc* d, void* stream_) {
     SEGCLIP_REQUIRE(!(d->klen && (d->flags & SEGCLIP_ATTN_FP8)), "attn_fwd: klen is not supported with SEGCLIP_ATTN_FP8");
     fill_common(a, d);
     a.O = (bf16_t*)d->O; a.lse = (float*)d->stats;
-    a.lean = tuning().fwd_lean;   // SEGCLIP_ATTN_FWD_LEAN=0: no lean softmax step on unmasked key tiles
+    a.lean = 1;   // 0: no lean softmax step on unmasked key tiles (the kernel argument of a settled A/B; folding it in changes device code)
   }
   const Plan p = plan_fwd(d);
   a.staged = p.staged;

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(WPB_BWD * 64) void attn_smallq_bwd_kernel(BwdArgs a
 }
 
 // the cases these kernels cover: bf16, head_dim 64, at most 8 queries, no causal / key-count mask (the planner of attention.hip
-// asks this; SEGCLIP_ATTN_SMALLQ=0, read there, routes them elsewhere)
+// asks this)
 static inline bool covers(const segclip_attn_desc* d) {
   return d->dtype == SEGCLIP_BF16 && d->hd == 64 && d->Tq >= 1 && d->Tq <= QMAX && d->Tk >= 1 && !d->causal && d->klen == nullptr &&
          !(d->flags & SEGCLIP_ATTN_FP8) && lds_bytes((int)d->Tk, true) <= 64 * 1024 && lds_bytes((int)d->Tk, false) <= 64 * 1024;

@@ -114,22 +114,3 @@ __device__ __forceinline__ float apply_act_grad(int act, float x) {
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-#include <stdlib.h>
-// Kernel-selection / tuning switches of the library (SEGCLIP_GEMM_PQ, SEGCLIP_PQ_HALF, SEGCLIP_ATTN_FWD_PF, ...: A/B tools and
-// profile scripts).  They are honoured only when SEGCLIP_TUNING=1 is set as well: a production process cannot have its kernels
-// re-routed by a stray variable, and one that tries is told so once per variable.
-static inline const char* segclip_tuning_env(const char* name) {
-  static const bool on = [] { const char* t = getenv("SEGCLIP_TUNING"); return t != nullptr && atoi(t) != 0; }();
-  const char* e = getenv(name);
-  if (e != nullptr && !on) {
-    fprintf(stderr, "segclip_hip: %s=%s ignored (tuning switches need SEGCLIP_TUNING=1)\n", name, e);
-    return nullptr;
-  }
-  return e;
-}
-// the integer value of a tuning switch, or dflt where it is unset (or not honoured).  Reads the environment at every call:
-// a launch site keeps the value in a `static const int`, so that it is read once per process.
-static inline int segclip_tuning_int(const char* name, int dflt) {
-  const char* e = segclip_tuning_env(name);
-  return e ? atoi(e) : dflt;
-}

@@ -15,16 +15,24 @@ struct Args {
   int splits; int64_t kper; float* slab;  // split-K: raw fp32 partial tiles go to slab[s][z][M][N]
   float* colsum_part;  // optional [M/64][N] fp32 partial column sums of the stored output (LDS epilogue only)
   int vec_epi;  // host-checked: every C / aux / residual / bias access of a full tile may be a 16-byte vector
-  int stagger;  // 8-phase kernel: cap in cycles of the first round's stagger unit (SEGCLIP_P8_STAGGER); 0 = off
+  int stagger;  // 8-phase kernel: cap in cycles of the first round's stagger unit (ARG_P8_STAGGER); 0 = off
   int aux_kind; // 0: aux = pre-activation u (stored by EPI_ACT, differentiated by EPI_DACT); 1: aux = act'(u);
                 // 2: aux = act'(u) as one byte per element (staged epilogue only, see EPI_ACT8)
-  int slab_staged; // 8-phase kernel: split-K partial tiles through the staged epilogue (SEGCLIP_P8_SLAB_STAGED)
-  int xw_epi;   // 8-phase kernel, bf16 outputs: cross-wave row pass (whole 128-byte lines per store; SEGCLIP_EPI_XW)
+  int slab_staged; // 8-phase kernel: split-K partial tiles through the staged epilogue (ARG_P8_SLAB_STAGED)
+  int xw_epi;   // 8-phase kernel, bf16 outputs: cross-wave row pass (whole 128-byte lines per store; ARG_EPI_XW)
 };
+
+// What every launch passes in the three kernel arguments that once carried A/B switches.  The kernels still read them; folding
+// them in changes device code and wants a measurement in the training step.
+// stagger cap, in the step (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
+constexpr int ARG_P8_STAGGER = 2000;
+// cross-wave row pass for all bf16 outputs: 45.23 -> 44.98 ms in the step (epilogue_lds2 below has the isolated numbers)
+constexpr int ARG_EPI_XW = 2;
+// split-K partial tiles as whole lines through the staged epilogue, not per-element stores (gemm_bf16_p8.hip)
+constexpr int ARG_P8_SLAB_STAGED = 1;
 
 // host: the arguments of a planned launch (gemm_plan.h) - the descriptor's operands, the plan's decisions
 inline Args gemm_args(const segclip_gemm_desc* d, const GemmPlan& p) {
-  const GemmTuning& t = gemm_tuning();
   Args g;
   g.A = d->A; g.B = (const bf16_t*)d->B; g.C = d->C; g.bias = d->bias; g.residual = d->residual; g.aux = d->aux;
   g.M = d->M; g.N = d->N; g.K = d->K;
@@ -38,8 +46,8 @@ inline Args gemm_args(const segclip_gemm_desc* d, const GemmPlan& p) {
   g.splits = p.route.splits; g.kper = p.kper; g.slab = (float*)d->ws;
   g.colsum_part = p.colsum ? d->colsum_ws : nullptr;
   g.vec_epi = p.vec_epi;
-  g.stagger = p.route.family == SEGCLIP_GEMM_ROUTE_P8 ? t.p8_stagger : 0;
-  g.xw_epi = t.epi_xw; g.slab_staged = t.p8_slab_staged;
+  g.stagger = p.route.family == SEGCLIP_GEMM_ROUTE_P8 ? ARG_P8_STAGGER : 0;
+  g.xw_epi = ARG_EPI_XW; g.slab_staged = ARG_P8_SLAB_STAGED;
   return g;
 }
 inline dim3 gemm_grid(const GemmPlan& p) { return dim3((unsigned)(p.nbx * p.nby), (unsigned)p.route.splits, (unsigned)p.nb); }
@@ -450,8 +458,8 @@ __device__ __forceinline__ void epilogue_lds2(const Args& g, const f32x16 (&acc0
   // measured (tools/bench_epi.py, M = 50176): act' data gradient 315 -> 294 us (its side loads become whole lines too),
   // c_fc forward with the saved derivative 334 -> 327; the plain bias-only epilogues do not gain in isolation (qkv forward
   // 185 = 185, out_proj data gradient 87.7 -> 92: three more workgroup barriers per tile) but do in the step, where the
-  // second stream competes for the L2's write ports: 45.23 -> 44.98 ms.  SEGCLIP_EPI_XW = 0 off / 1 not for the plain
-  // epilogues / 2 (default) all bf16 outputs
+  // second stream competes for the L2's write ports: 45.23 -> 44.98 ms.  g.xw_epi = 0 off / 1 not for the plain
+  // epilogues / 2 (what gemm_args passes) all bf16 outputs
   if (MODE == EPI_PLAIN && g.xw_epi < 2) xw = nullptr;
   const bool x = sizeof(CT) == 2 && NSPLIT > 0 && xw != nullptr;
   const EpiLane L = epi_lane<CT, NSPLIT>(t, nw, lane, xw, wr, wc, n0);
@@ -465,10 +473,7 @@ __device__ __forceinline__ void epilogue_lds2(const Args& g, const f32x16 (&acc0
     epi_rows_plain<CT, MODE, NSPLIT>(g, L, mw1, coff);
     return;
   }
-#ifndef EPI_F32_OVERLAP
-#define EPI_F32_OVERLAP 0
-#endif
-  if (sizeof(CT) == 4 && !EPI_F32_OVERLAP) {
+  if (sizeof(CT) == 4) {
     // fp32 side operands are 64 VGPRs per sub-tile: with the second sub-tile's accumulators still live there is no room
     // for both, so the sub-tiles run one after the other
     epilogue_lds<CT, MODE, NSPLIT>(g, acc0, t, mw0, nw, lane, coff, roff);

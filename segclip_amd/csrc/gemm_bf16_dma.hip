@@ -1,9 +1,9 @@
 // bf16 MFMA GEMM, LDS-DMA pipeline (the fast path for the large, aligned shapes of the training step).
 // C[z](m,n) = epi(alpha * sum_k A(m,k) * B(n,k)),  A and B bf16, each k-contiguous or k-strided.
 //
-// Tile 256 x BN x 64 (BN = 256 or 128), 512 threads = 8 waves (two per SIMD):
-//   BN=256: waves 2(m) x 4(n), each 128x64 = 4x2 MFMA 32x32x16 accumulators (128 VGPRs)
-//   BN=128: waves 4(m) x 2(n), each  64x64 = 2x2
+// Tile 256 x 128 x 64, 512 threads = 8 waves (two per SIMD): waves 4(m) x 2(n), each 64x64 = 2x2 MFMA 32x32x16 accumulators;
+// or 128 x 128 x 64 on 4 waves 2(m) x 2(n).  (256 x 256 tiles run in gemm_bf16_p8.hip / gemm_bf16_pq.hip; the template
+// still states the 128x64 wave tile that a BN = 256 instance would have, but none is built.)
 // Operand tiles go L2 -> LDS directly (global_load_lds_dwordx4: 1 KiB per wave instruction, no VGPR round
 // trip) into a double buffer (2 x 64 KiB): the DMA of K-tile t+1 is issued right after the barrier that
 // publishes tile t and lands under tile t's MFMAs.  Measured on MI355X (tools/ubench/dma_bw.hip): an
@@ -14,7 +14,7 @@
 // MFMA operand fragments are register double-buffered (chunk kc+1 is requested before the MFMAs of kc).
 // Full tiles leave through the LDS-staged coalesced epilogue (gemm_bf16_common.h).
 // Rows beyond M / N are clamped to valid addresses (their products are never stored); K must be a
-// multiple of 64.  Which problems come here, and on which of the three tiles, is decided by gemm_plan.cpp (want_dma,
+// multiple of 64.  Which problems come here, and on which of the two tiles, is decided by gemm_plan.cpp (want_dma,
 // pick_bn, dma_small_tiles, dma_covers); the launcher at the end of this file fills Args from the plan and decides nothing.
 #include <stdlib.h>
 
@@ -111,7 +111,7 @@ __device__ __forceinline__ bf16x8_t frag_ks(const char* lds, int rbase, int kc, 
   return tr16_frag(p, 4 * (ROWS * 2));
 }
 
-// <BM, BN, NWV>: <256,256,8> and <256,128,8> own a CU (139 KiB of LDS: operand ring / epilogue patches);
+// <BM, BN, NWV>: <256,128,8> owns a CU (139 KB of LDS: the eight epilogue patches, over a 96 KiB operand ring);
 // <128,128,4> (waves 2x2, 64x64 each) needs 68 KiB, so two workgroups share a CU and one's output phase overlaps
 // the other's MFMA phase.
 template <bool A_KS, bool B_KS, int BM, int BN, int NWV>
@@ -230,9 +230,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
     return;
   }
   const bool full = m0 + BM <= g.M && n0 + BN <= g.N;  // uniform over the workgroup
-#ifdef SEGCLIP_NO_EPILOGUE
-  if (acc[0][0][0] != 12345.678f) return;
-#endif
   const bool vec = full && g.vec_epi;
   if (vec) __syncthreads();  // every wave is done with the operand ring: the LDS is reused as 8 private patches
   float* t = reinterpret_cast<float*>(smem + wave * EPI_WAVE_BYTES);
@@ -265,15 +262,14 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void gemm_bf16_dma_kern
 #ifndef DMA_PART
 #error "compile with -DDMA_PART=0..4 (see build.sh)"
 #endif
-// indexed by the route variant (gemm_plan.h) from the back - DMA_128x128 (4 waves), DMA_256x256, DMA_256x128 - which is the
-// order in which the code object holds the instances
+// the two instances by route variant (gemm_plan.h): DMA_128x128 (4 waves) first, which is the order in which the code object
+// holds them
 #define DMA_LAUNCHER(NAME, AK, BKS)                                                                             \
   void NAME(const segclip_gemm_desc* d, const GemmPlan& p, hipStream_t stream) {                                \
     typedef void (*kernel_t)(Args);                                                                             \
-    static const kernel_t kernels[3] = {gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>, gemm_bf16_dma_kernel<AK, BKS, 256, 256, 8>, \
-                                        gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8>};                            \
-    const int v = p.route.variant;                                                                              \
-    hipLaunchKernelGGL(kernels[DMA_128x128 - v], gemm_grid(p), dim3(v == DMA_128x128 ? 256 : 512), 0, stream, gemm_args(d, p)); \
+    static const kernel_t kernels[2] = {gemm_bf16_dma_kernel<AK, BKS, 128, 128, 4>, gemm_bf16_dma_kernel<AK, BKS, 256, 128, 8>}; \
+    const bool small = p.route.variant == DMA_128x128;                                                          \
+    hipLaunchKernelGGL(kernels[small ? 0 : 1], gemm_grid(p), dim3(small ? 256 : 512), 0, stream, gemm_args(d, p)); \
   }
 #if DMA_PART == 0
 DMA_LAUNCHER(segclip_dma_launch_ff, false, false)

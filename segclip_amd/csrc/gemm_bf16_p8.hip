@@ -281,7 +281,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
     const int li = lane & 31, lk = lane >> 5;
     float* slab = g.slab + ((int64_t)ksplit * gridDim.z + z) * g.M * g.N;
     // full tiles: the raw fp32 partial tile goes through the staged epilogue (park, 16-byte row stores: 32 store
-    // instructions per wave instead of 128 one-dword stores); SEGCLIP_P8_SLAB_STAGED=0 keeps the per-element stores
+    // instructions per wave instead of 128 one-dword stores); g.slab_staged = 0 keeps the per-element stores
     if (g.slab_staged && m0 + BT <= g.M && n0 + BT <= g.N && g.N % 4 == 0) {
       Args g2 = g;
       g2.C = slab; g2.ldc = g.N; g2.c_dtype = SEGCLIP_F32; g2.bias = nullptr; g2.residual = nullptr; g2.aux = nullptr;
@@ -313,22 +313,12 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   float* tp = reinterpret_cast<float*>(smem + wave * EPI_WAVE_BYTES);
   const int64_t mw0 = m0 + wr * 64, mw1 = m0 + 128 + wr * 64;
   if (vec) {
-#ifdef P8_TEST_SINGLE
-    if (g.c_dtype == SEGCLIP_BF16) { epilogue_lds_mode<bf16_t, 128>(g, acc[0], tp, mw0, nw, lane, coff, roff); __builtin_amdgcn_wave_barrier(); epilogue_lds_mode<bf16_t, 128>(g, acc[1], tp, mw1, nw, lane, coff, roff); }
-    else { epilogue_lds_mode<float, 128>(g, acc[0], tp, mw0, nw, lane, coff, roff); __builtin_amdgcn_wave_barrier(); epilogue_lds_mode<float, 128>(g, acc[1], tp, mw1, nw, lane, coff, roff); }
-#else
     if (g.c_dtype == SEGCLIP_BF16)
       epilogue_lds2_mode<bf16_t, 128>(g, acc[0], acc[1], tp, mw0, mw1, nw, lane, coff, roff,
                                       g.xw_epi ? reinterpret_cast<const float*>(smem) : nullptr, wr, wc, n0);
     else epilogue_lds2_mode<float, 128>(g, acc[0], acc[1], tp, mw0, mw1, nw, lane, coff, roff);
-#endif
-#ifndef P8_TEST_NORETURN
     return;
-#endif
   }
-#ifdef P8_TEST_NORETURN
-  else {
-#endif
   // two explicit copies (a loop over the A half would index the accumulators at run time -> scratch)
 #define P8_EPI(I)                                                                                              \
   do {                                                                                                         \
@@ -340,9 +330,6 @@ __global__ __launch_bounds__(NWV * 64) void gemm_bf16_p8_kernel(Args g) {
   __builtin_amdgcn_wave_barrier();
   P8_EPI(1);
 #undef P8_EPI
-#ifdef P8_TEST_NORETURN
-  }
-#endif
 }
 
 }  // namespace

@@ -20,8 +20,8 @@
 //    first half travel by LDS-DMA into the 32 KiB the ring leaves free, the second half's follow into ring space once the
 //    K loop is over; they are re-read in the accumulator layout with ds_read.
 //
-// Measured (MI355X, M = 50176, tools/bench_pq.py, bit-identical outputs): forward N = 2304, K = 768 195 -> 158 us, data
-// gradients 4-9 % faster than gemm_bf16_p8.hip; per tile (tools/debug/pq_ksweep.py): K loop 1.43 us per K-tile, fixed cost
+// Measured (MI355X, M = 50176, both kernels in one process, bit-identical outputs): forward N = 2304, K = 768 195 -> 158 us, data
+// gradients 4-9 % faster than gemm_bf16_p8.hip; per tile (a sweep over K): K loop 1.43 us per K-tile, fixed cost
 // 1.5 us + output VALU/LDS 1.4 us + output stores 2.0-2.3 us (8-phase kernel: 5.9 us of output path).
 // A PERSISTENT form of this kernel (static tile walk per XCD, the next tile's first 7 half-tile DMAs issued before the
 // epilogue, the K loop's counted waits extended past the 16 output stores: vmcnt(26)) was built and measured first

@@ -2,8 +2,6 @@
 // stands here once; gemm_plan() below is the order in which they are asked.
 #include "gemm_plan.h"
 
-const GemmTuning& gemm_tuning() { static const GemmTuning t; return t; }
-
 namespace {
 
 constexpr int BK = GEMM_BK, BT = GEMM_BIG_TILE;
@@ -106,12 +104,12 @@ int pick_bn(const segclip_gemm_desc* d, int64_t nbatch_splits) {
 // second stream) a shape-based choice measured 58.4 vs 58.2 ms, i.e. no gain, so the 256-wide tiles stay the default.
 // Round 4: problems whose 256-row tiles cannot fill the 256 CUs (the center stage's q-side linears: M = 8 B = 2048 rows,
 // 48-192 tiles) take the 128x128 tile: four times the workgroups, two per CU, half the K-loop time per tile
-// (SEGCLIP_GEMM_SMALL_TILES=0 switches the rule off; a forward + backward pass of the center stage: see DESIGN 4.4).
-bool dma_small_tiles(const segclip_gemm_desc* d, const GemmTuning& t, int64_t nb, int splits, bool colsum, int bn_big) {
+// (a forward + backward pass of the center stage: see DESIGN 4.4).
+bool dma_small_tiles(const segclip_gemm_desc* d, int64_t nb, int splits, bool colsum, int bn_big) {
   // fused column sums come from the staged epilogue of FULL tiles only (a partial tile takes the per-element epilogue, which
   // writes no partial sums): M = 256 q + 128 runs them on the 128-row tiles, where every tile is full (colsum_shape_ok)
   if (colsum) return d->M % 256 != 0;
-  return t.small_tiles && d->M >= 128 && d->N >= 128 && !aux8(d) && cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256;
+  return d->M >= 128 && d->N >= 128 && !aux8(d) && cdiv(d->M, 256) * cdiv(d->N, bn_big) * nb * splits < 256;
 }
 
 // ---- epilogues ----------------------------------------------------------------------------------------------------------
@@ -139,10 +137,10 @@ bool staged_epilogue_covers(const segclip_gemm_desc* d, int vec, int splits, boo
 bool dma_covers(const segclip_gemm_desc* d, int vec, int splits, bool colsum) {
   return staged_epilogue_covers(d, vec, splits, colsum);
 }
-// asked only where pick_bn chose 256-wide tiles (so N > 128).  SEGCLIP_GEMM_P8=0: off - the only way to the 256 x 256 instance
-// of gemm_bf16_dma.hip, which otherwise takes nothing that this kernel refuses but operand pitches of 2 GiB per 256 rows
-bool p8_covers(const segclip_gemm_desc* d, const GemmTuning& t, int vec, int splits, bool colsum) {
-  if (!t.p8) return false;
+// asked only where pick_bn chose 256-wide tiles (so N > 128).  Of the problems dma_covers takes, this kernel refuses two kinds:
+// column sums off full 256 x 256 tiles, which dma_small_tiles sends to the 128 x 128 instance, and the operand pitches below,
+// which plan_dma runs on 256 x 128 tiles (gemm_bf16_dma.hip forms every address in 64 bits)
+bool p8_covers(const segclip_gemm_desc* d, int vec, int splits, bool colsum) {
   // 32-bit DMA offsets: 256 rows (or 64 k-rows) of the leading dimension must stay below 2 GiB
   if ((a_ks(d) ? 64 : 256) * lda(d) * 2 >= LIM31 || (b_ks(d) ? 64 : 256) * ldb(d) * 2 >= LIM31) return false;
   // a partial tile's per-element epilogue writes no column sums: M = 256 q + 128 goes to the 128-row tiles of gemm_bf16_dma.hip
@@ -151,29 +149,26 @@ bool p8_covers(const segclip_gemm_desc* d, const GemmTuning& t, int vec, int spl
 }
 
 // ---- gemm_bf16_pq.hip ---------------------------------------------------------------------------------------------------
-// SEGCLIP_GEMM_PQ: 1 (default) on, 0 off, 2 = consult SEGCLIP_GEMM_PQ_NOW
-bool pq_on(const GemmTuning& t) { return (t.pq == 2 ? segclip_tuning_int("SEGCLIP_GEMM_PQ_NOW", 1) : t.pq) != 0; }
 // Half-tile tail plan: the r = ntiles % 256 tiles of the last, partial round run as 2 r workgroups of 128 x 256 when those fit
 // one round (r <= 128): 591 tiles (N = 768 at M = 50432) are 2.3 rounds of 256 CUs and take the time of 3; the third round
 // then costs a half-tile's time (about 0.6 of a tile's: 3 of 4 operand units per K-tile, half the MFMAs, half the output).
-// No exchange between workgroups, results bit-identical to the full tiles'.  SEGCLIP_PQ_HALF=0 switches it off (A/B).
-bool pq_half_on(const GemmTuning& t) { return (t.pq_half == 2 ? segclip_tuning_int("SEGCLIP_PQ_HALF_NOW", 1) : t.pq_half) != 0; }
-int pq_half_tail(const GemmTuning& t, int64_t ntiles) {
-  if (!pq_half_on(t) || ntiles <= 256) return 0;
+// No exchange between workgroups, results bit-identical to the full tiles'.
+int pq_half_tail(int64_t ntiles) {
+  if (ntiles <= 256) return 0;
   const int r = (int)(ntiles % 256);
   return r > 0 && r <= 128 ? r : 0;
 }
 // weight gradient: C(m,n) = sum_k A[k][m] B[k][n], fp32 out (split-K: raw partial tiles into the slabs)
-bool pq_covers_wgrad(const segclip_gemm_desc* d, const GemmTuning& t, int splits, bool colsum) {
-  if (!t.pq_wgrad || !b_ks(d) || d->c_dtype != SEGCLIP_F32 || !plain_epilogue(d) || colsum) return false;
+bool pq_covers_wgrad(const segclip_gemm_desc* d, int splits, bool colsum) {
+  if (!b_ks(d) || d->c_dtype != SEGCLIP_F32 || !plain_epilogue(d) || colsum) return false;
   if (splits == 1 && (d->alpha != 1.0f || d->ldc % 4 != 0 || !al16(d->C))) return false;
   if (splits > 1 && (d->N % 4 != 0 || !al16(d->ws))) return false;
   // 32-bit per-lane offsets: 64 k-rows of an operand and 256 rows of the output (the slab's pitch is N) stay below 2 GiB
   return 64 * d->sak * 2 < LIM31 && 64 * d->sbk * 2 < LIM31 && 256 * (splits > 1 ? d->N : d->ldc) * 4 < LIM31;
 }
 // forward + fp32 residual -> fp32 (the fp32 residual stream): fp32 patches, fp32 row pass
-bool pq_covers_res32(const segclip_gemm_desc* d, const GemmTuning& t, bool colsum) {
-  if (!t.pq_res32 || b_ks(d) || d->residual == nullptr || d->r_dtype != SEGCLIP_F32 || d->alpha != 1.0f) return false;
+bool pq_covers_res32(const segclip_gemm_desc* d, bool colsum) {
+  if (b_ks(d) || d->residual == nullptr || d->r_dtype != SEGCLIP_F32 || d->alpha != 1.0f) return false;
   if (d->aux || d->act != SEGCLIP_ACT_NONE || d->mul_dact || colsum) return false;
   if (!al16(d->C) || !al16(d->bias) || !al16(d->residual) || d->ldc % 4 != 0 || d->ldr % 4 != 0) return false;
   return 256 * d->sam * 2 < LIM31 && 256 * d->sbn * 2 < LIM31 && 256 * d->ldc * 4 < LIM31;
@@ -204,16 +199,16 @@ int pq_covers_bf16(const segclip_gemm_desc* d, bool colsum) {
 }
 // the epilogue mode with which the accumulator-register kernel takes a `want_dma` problem, or -1: full 256 x 256 tiles, no
 // batch, split-K in the weight gradient only
-int pq_covers(const segclip_gemm_desc* d, const GemmTuning& t, int64_t nb, int splits, bool colsum) {
-  if (!pq_on(t) || nb != 1 || d->M < 128 || d->N % BT != 0) return -1;
+int pq_covers(const segclip_gemm_desc* d, int64_t nb, int splits, bool colsum) {
+  if (nb != 1 || d->M < 128 || d->N % BT != 0) return -1;
   // M = 256 q + 128 (the token rows of an odd multiple of 128 samples x 197 / 577 / 77 tokens): the last 128 rows run as a
   // row of half-tiles (forward / data-gradient layouts; the weight gradient's M is a weight dimension)
-  if (d->M % BT != 0 && (d->M % 128 != 0 || a_ks(d) || !pq_half_on(t))) return -1;
-  if (a_ks(d)) return pq_covers_wgrad(d, t, splits, colsum) ? PQ_SLAB : -1;
+  if (d->M % BT != 0 && (d->M % 128 != 0 || a_ks(d))) return -1;
+  if (a_ks(d)) return pq_covers_wgrad(d, splits, colsum) ? PQ_SLAB : -1;
   if (splits != 1) return -1;
   // only the fp32-residual epilogue addresses the residual modulo a row count
   if (d->res_row_mod > 0 && !(d->c_dtype == SEGCLIP_F32 && d->residual != nullptr && d->r_dtype == SEGCLIP_F32)) return -1;
-  if (d->c_dtype == SEGCLIP_F32) return pq_covers_res32(d, t, colsum) ? PQ_RES32 : -1;
+  if (d->c_dtype == SEGCLIP_F32) return pq_covers_res32(d, colsum) ? PQ_RES32 : -1;
   return pq_covers_bf16(d, colsum);
 }
 
@@ -223,8 +218,8 @@ void set_route(GemmPlan& p, const segclip_gemm_desc* d, int family, int tile_m, 
   p.nbx = (int)cdiv(d->N, tile_n);
   p.nby = (int)cdiv(d->M, tile_m);
 }
-bool plan_pq(GemmPlan& p, const segclip_gemm_desc* d, const GemmTuning& t, int splits, bool colsum) {
-  const int mode = pq_covers(d, t, p.nb, splits, colsum);
+bool plan_pq(GemmPlan& p, const segclip_gemm_desc* d, int splits, bool colsum) {
+  const int mode = pq_covers(d, p.nb, splits, colsum);
   if (mode < 0) return false;
   const int nbx = (int)(d->N / BT), ntiles = (int)(d->M / BT) * nbx;   // full tiles
   p.pq_mode = mode;
@@ -234,28 +229,29 @@ bool plan_pq(GemmPlan& p, const segclip_gemm_desc* d, const GemmTuning& t, int s
     return true;
   }
   const int hx = d->M % BT != 0 ? nbx : 0;       // M = 256 q + 128: one more row of half-tiles
-  const int hr = pq_half_tail(t, ntiles);
+  const int hr = pq_half_tail(ntiles);
   if (hr > 0 || hx > 0) { p.half_r = hr; p.half_x = hx; p.nfull = ntiles - hr; }
   p.nwg = (unsigned)(ntiles + hr + hx);
   // variant: epilogue mode | tail tiles run as half-tiles << 4 | half-tiles of a last row of 128 rows << 16
   set_route(p, d, SEGCLIP_GEMM_ROUTE_PQ, BT, BT, 1, mode | (hr << 4) | (hx << 16));
   return true;
 }
-bool plan_p8(GemmPlan& p, const segclip_gemm_desc* d, const GemmTuning& t, int splits, bool colsum) {
-  if (!p8_covers(d, t, p.vec_epi, splits, colsum)) return false;
+bool plan_p8(GemmPlan& p, const segclip_gemm_desc* d, int splits, bool colsum) {
+  if (!p8_covers(d, p.vec_epi, splits, colsum)) return false;
   set_route(p, d, SEGCLIP_GEMM_ROUTE_P8, BT, BT, splits, 0);
   return true;
 }
-bool plan_dma(GemmPlan& p, const segclip_gemm_desc* d, const GemmTuning& t, int splits, bool colsum) {
+bool plan_dma(GemmPlan& p, const segclip_gemm_desc* d, int splits, bool colsum) {
   if (!dma_covers(d, p.vec_epi, splits, colsum)) return false;
+  // bn_big = 256 here: pq and p8 refused the 256 x 256 tiles pick_bn chose - off the small-tile rule that is an operand pitch of
+  // 2 GiB per 256 rows (p8_covers), and this kernel has no 256-wide instance: 256 x 128 tiles, whose addresses are 64-bit
   const int bn_big = pick_bn(d, p.nb * splits);
-  if (dma_small_tiles(d, t, p.nb, splits, colsum, bn_big)) set_route(p, d, SEGCLIP_GEMM_ROUTE_DMA, 128, 128, splits, DMA_128x128);
-  else set_route(p, d, SEGCLIP_GEMM_ROUTE_DMA, 256, bn_big, splits, bn_big == 256 ? DMA_256x256 : DMA_256x128);
+  if (dma_small_tiles(d, p.nb, splits, colsum, bn_big)) set_route(p, d, SEGCLIP_GEMM_ROUTE_DMA, 128, 128, splits, DMA_128x128);
+  else set_route(p, d, SEGCLIP_GEMM_ROUTE_DMA, 256, 128, splits, DMA_256x128);
   return true;
 }
 
 GemmPlan plan_bf16(GemmPlan p, const segclip_gemm_desc* d) {
-  const GemmTuning& t = gemm_tuning();
   PLAN_REQUIRE(!a_ks(d) || d->sam == 1, "gemm_bf16: A needs unit stride along k or m (sam=%lld sak=%lld)",
                (long long)d->sam, (long long)d->sak);
   PLAN_REQUIRE(!b_ks(d) || d->sbn == 1, "gemm_bf16: B needs unit stride along k or n (sbn=%lld sbk=%lld)",
@@ -272,13 +268,13 @@ GemmPlan plan_bf16(GemmPlan p, const segclip_gemm_desc* d) {
   if (dma) p.vec_epi = vec_epi(d);
   bool taken = false;
   if (d->res_row_mod > 0) {   // only gemm_bf16_pq.hip's fp32-residual epilogue addresses the residual modulo a row count
-    taken = dma && p.nb == 1 && splits == 1 && plan_pq(p, d, t, 1, p.colsum);
+    taken = dma && p.nb == 1 && splits == 1 && plan_pq(p, d, 1, p.colsum);
     if (!taken) PLAN_FAIL(SEGCLIP_ERR_UNSUPPORTED, "%s", MSG_RES_ROW_MOD);
   } else if (dma) {
     // 256x256 tiles: the accumulator-register kernel (gemm_bf16_pq.hip) where it takes the problem, else the phase-pipelined
     // kernel (gemm_bf16_p8.hip); 256x128 / 128x128 tiles: the one-barrier-per-K-tile kernel (gemm_bf16_dma.hip)
-    if (pick_bn(d, p.nb * splits) == 256) taken = plan_pq(p, d, t, splits, p.colsum) || plan_p8(p, d, t, splits, p.colsum);
-    if (!taken) taken = plan_dma(p, d, t, splits, p.colsum);
+    if (pick_bn(d, p.nb * splits) == 256) taken = plan_pq(p, d, splits, p.colsum) || plan_p8(p, d, splits, p.colsum);
+    if (!taken) taken = plan_dma(p, d, splits, p.colsum);
   }
   if (p.colsum && !taken) PLAN_FAIL(SEGCLIP_ERR_UNSUPPORTED, "%s", MSG_COLSUM);
   if (!taken && aux8(d)) PLAN_FAIL(SEGCLIP_ERR_UNSUPPORTED, "%s", MSG_AUX8);
@@ -299,7 +295,7 @@ int gemm_splits(const segclip_gemm_desc* d) {
   int64_t kper;
   return d->b_dtype == SEGCLIP_BF16 ? resolve_splits(d, &kper) : 1;
 }
-int gemm_pq_half_tail(int64_t ntiles) { return pq_half_tail(gemm_tuning(), ntiles); }
+int gemm_pq_half_tail(int64_t ntiles) { return pq_half_tail(ntiles); }
 
 GemmPlan gemm_plan_f32(const segclip_gemm_desc* d) {
   GemmPlan p;
@@ -307,10 +303,9 @@ GemmPlan gemm_plan_f32(const segclip_gemm_desc* d) {
   p.kper = d->K;
   // M <= 32: 32 x 128 tiles.  Otherwise, with fewer than half a chip of 128 x 128 tiles: 64 x 64 tiles (4x the workgroups),
   // K-step 64.  256 x 256 x 512: 94 -> 39 us (K-step 128: 47 us - the time is the LDS staging and the one-accumulator MFMA
-  // chain of a wave, not the round trips).  SEGCLIP_GEMM_F32_SMALL = 0 / 1 forces the 128 x 128 / 64 x 64 tiles
-  const int force_small = gemm_tuning().f32_small;
-  const bool skinny = force_small != 0 && d->M <= 32;
-  const bool small = !skinny && (force_small >= 0 ? force_small != 0 : cdiv(d->N, 128) * cdiv(d->M, 128) * p.nb < 128);
+  // chain of a wave, not the round trips)
+  const bool skinny = d->M <= 32;
+  const bool small = !skinny && cdiv(d->N, 128) * cdiv(d->M, 128) * p.nb < 128;
   const int bm = skinny ? 32 : (small ? 64 : 128), bn = skinny ? 128 : (small ? 64 : 128);
   PLAN_REQUIRE((unsigned)cdiv(d->M, bm) <= 65535 && p.nb <= 65535, "gemm_f32: grid too large (M=%lld batch=%lld)",
                (long long)d->M, (long long)p.nb);

@@ -12,25 +12,11 @@ constexpr int GEMM_BIG_TILE = 256; // 256-row tiles of gemm_bf16_dma.hip, 256 x 
 // epilogue modes of gemm_bf16_pq.hip (bits 0-3 of its route variant)
 enum { PQ_PLAIN = 0, PQ_RES = 1, PQ_ACT8 = 2, PQ_DACT8 = 3, PQ_SLAB = 4, PQ_RES32 = 5, PQ_ACT8E = 6 };
 // PQ_ACT8E: PQ_ACT8 with the erf-GELU of the MAE decoders (modules/module_mae.py:110-134: timm Block, nn.GELU) instead of QuickGELU
-// route variants of gemm_bf16_dma.hip (DMA_128x128: 4 waves, for problems too small to fill the chip with 256-row tiles) ...
-enum { DMA_256x128 = 0, DMA_256x256 = 1, DMA_128x128 = 2 };
+// route variants of gemm_bf16_dma.hip (DMA_128x128: 4 waves, for problems too small to fill the chip with 256-row tiles; 1 was
+// the retired 256 x 256 instance, and the route tables of the tests hold the other two values) ...
+enum { DMA_256x128 = 0, DMA_128x128 = 2 };
 // ... and of gemm_f32.hip
 enum { F32_32x128 = 0, F32_64x64 = 1, F32_128x128 = 2 };
-
-// The tuning switches of the GEMM (common.h: honoured with SEGCLIP_TUNING=1 only), read once per process; each is explained
-// where the planner asks it.  pq / pq_half = 2: consult SEGCLIP_GEMM_PQ_NOW / SEGCLIP_PQ_HALF_NOW (0/1) at every call (A/B
-// tests in one process).
-struct GemmTuning {
-  int pq = segclip_tuning_int("SEGCLIP_GEMM_PQ", 1), pq_wgrad = segclip_tuning_int("SEGCLIP_GEMM_PQ_WGRAD", 1);
-  int pq_res32 = segclip_tuning_int("SEGCLIP_GEMM_PQ_RES32", 1), pq_half = segclip_tuning_int("SEGCLIP_PQ_HALF", 1);
-  int p8 = segclip_tuning_int("SEGCLIP_GEMM_P8", 1), small_tiles = segclip_tuning_int("SEGCLIP_GEMM_SMALL_TILES", 1);
-  int f32_small = segclip_tuning_int("SEGCLIP_GEMM_F32_SMALL", -1);
-  // kernel arguments of gemm_bf16_p8.hip.  p8_stagger: unit cap in cycles of the first round's stagger; 0 = off.  In the step
-  // (two runs each): 5000: 43.74 ms, 2000: 43.50, 1000: 43.47, 0: 43.47, 12000: 43.98
-  int p8_stagger = segclip_tuning_int("SEGCLIP_P8_STAGGER", 2000), epi_xw = segclip_tuning_int("SEGCLIP_EPI_XW", 2);
-  int p8_slab_staged = segclip_tuning_int("SEGCLIP_P8_SLAB_STAGED", 1);
-};
-const GemmTuning& gemm_tuning();
 
 struct GemmPlan {
   int rc = 0;                  // what segclip_gemm returns before launching: 0, SEGCLIP_ERR_INVALID or SEGCLIP_ERR_UNSUPPORTED
@@ -49,8 +35,8 @@ struct GemmPlan {
   unsigned nwg = 0;
 };
 
-// The plan of segclip_gemm(d): a pure function of the descriptor and the switches.  Of the pointers, ws and colsum_ws it reads
-// presence and alignment only.
+// The plan of segclip_gemm(d): a pure function of the descriptor - it reads no environment variable and keeps no state.  Of the
+// pointers, ws and colsum_ws it reads presence and alignment only.
 GemmPlan gemm_plan(const segclip_gemm_desc* d);
 // the same for a descriptor with fp32 operands that is known to be valid (attention.hip's fp32 path)
 GemmPlan gemm_plan_f32(const segclip_gemm_desc* d);

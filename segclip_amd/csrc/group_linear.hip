@@ -13,14 +13,12 @@
 // per (input, output) pair with SWAPPED operands (result block transposed: lane = row, registers = 4 consecutive columns),
 // bf16 packing in-lane, and the 32 x 64 output block through a wave-private 4-KiB LDS patch so that it leaves as whole
 // 128-byte lines.  The next group's row fragments are in flight while the current group is multiplied.
-#include <stdlib.h>
-#include <algorithm>
-
 #include "common.h"
 
 namespace {
 
 constexpr int GL_WAVES = 4, GL_ROWS = 32, GL_HD = 64;
+constexpr int GL_GSPLIT = 6;   // grid.y: shares of the groups (the kernel says what they buy)
 
 struct GLArgs {
   const bf16_t* in[2]; bf16_t* out[2];
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(GL_WAVES * 64) void group_linear_kernel(GLArgs a) {
   if (row0 >= a.M) return;
   const int64_t row = row0 + li < a.M ? row0 + li : a.M - 1;      // clamped: rows beyond M are computed and not stored
   // blockIdx.y: a contiguous share of the groups (more waves in flight: a wave's walk is a chain of load -> MFMA -> LDS -> store;
-  // 6 shares: 101 + 89 -> 81 + 77 us for the two launches of a step, SEGCLIP_GL64_GSPLIT)
+  // GL_GSPLIT = 6 shares: 101 + 89 -> 81 + 77 us for the two launches of a step)
   const int gper = (a.groups + (int)gridDim.y - 1) / (int)gridDim.y;
   const int gbeg = (int)blockIdx.y * gper, gend = gbeg + gper < a.groups ? gbeg + gper : a.groups;
   if (gbeg >= gend) return;
@@ -140,8 +138,7 @@ extern "C" int segclip_group_linear64(const void* const* in, const int64_t* ld_i
       a.W[i][o] = (const bf16_t*)p;
     }
   a.M = M; a.groups = groups;
-  static const int gsplit_env = std::max(1, segclip_tuning_int("SEGCLIP_GL64_GSPLIT", 6));
-  const int gsplit = gsplit_env < groups ? gsplit_env : groups;
+  const int gsplit = GL_GSPLIT < groups ? GL_GSPLIT : groups;
   const dim3 grid((unsigned)cdiv(M, GL_WAVES * GL_ROWS), (unsigned)gsplit), block(GL_WAVES * 64);
   if (n_in == 1 && n_out == 1) hipLaunchKernelGGL((group_linear_kernel<1, 1>), grid, block, 0, (hipStream_t)stream, a);
   else if (n_in == 1) hipLaunchKernelGGL((group_linear_kernel<1, 2>), grid, block, 0, (hipStream_t)stream, a);

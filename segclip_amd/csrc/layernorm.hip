@@ -2,9 +2,6 @@
 // (cols <= 2048), fp32 statistics, 16-byte (fp32) / 8-byte (bf16) vector loads, wave shuffles for the
 // two reductions.  Backward fuses the residual-gradient add (dx = LN'(dy) + dres) and produces
 // dgamma/dbeta through a deterministic two-stage reduction (per-block partials -> column sums).
-#include <stdlib.h>
-#include <algorithm>
-
 #include "common.h"
 #include "reduce_rows.h"
 
@@ -382,7 +379,7 @@ __global__ __launch_bounds__(WAVES * 64) void ln_bwd_multi_kernel(const float* _
 
 // 3 workgroups of 4 waves per CU (the pipelined kernel holds two rows per wave: ~130 VGPRs at 768 columns)
 int ln_blocks(int64_t rows) {
-  static const int cap = std::max(1, segclip_tuning_int("SEGCLIP_LN_BLOCKS", 768));
+  constexpr int cap = 768;
   int64_t b = cdiv(rows, WAVES);
   return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
 }

@@ -20,7 +20,6 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import config as _cfg
-from .config import tuning_env as _tenv
 
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = L.ACT_NONE, L.ACT_QUICK_GELU, L.ACT_GELU_ERF
 
@@ -190,16 +189,16 @@ def _empty(shape, dtype, like):
 # Row pitch of the MLP hidden tensors (h, act'(u), du: M x 4D bf16).  A pitch that is a multiple of 2 KiB (4D = 3072 bf16 =
 # 6144 B) makes the 256-row store burst of every GEMM tile camp on a few HBM channels: with 1 KiB more per row the c_fc
 # forward with its two outputs runs 385 -> 312 us, the c_proj data gradient 324 -> 290 us, and the GEMMs that read these
-# tensors as their A operand 2-5 % faster (M = 50176; tools/debug/gemm_ldc_probe2.py).  SEGCLIP_HIDDEN_PAD = extra
-# elements per row (0 = dense).
-_HIDDEN_PAD = int(_tenv("SEGCLIP_HIDDEN_PAD", "512"))
+# tensors as their A operand 2-5 % faster (M = 50176; tools/debug/gemm_ldc_probe2.py).  _HIDDEN_PAD = extra
+# elements per row.
+_HIDDEN_PAD = 512
 
 
 def _empty_pitched(shape, dtype, like):
     """(M, N) view of a buffer whose row pitch avoids multiples of 2 KiB (dense when the pitch is harmless or M is small)."""
     M, N = shape
     esz = torch.empty((), dtype=dtype).element_size()
-    if _HIDDEN_PAD <= 0 or M < 4096 or (N * esz) % 2048 != 0:
+    if M < 4096 or (N * esz) % 2048 != 0:
         return _empty(shape, dtype, like)
     return torch.empty((M, N + _HIDDEN_PAD), dtype=dtype, device=like.device)[:, :N]
 
@@ -1584,7 +1583,7 @@ class CrossBlockFn(Function):
         rq = ReduceQueue()
         # the four weight gradients over the block's 8 center rows per sample (B*G rows: 9-36 output tiles each, 42 us apiece as
         # separate split-K launches) run as ONE grouped launch at the end of the node (round 6; bf16 mode)
-        wg = WgradGroup() if (bf and _CROSS_WGRAD_GROUP) else None
+        wg = WgradGroup() if bf else None
 
         def small_wgrad(dy_, x_, out_):
             if wg is not None and WgradGroup.covers(dy_, x_, out_):
@@ -1757,14 +1756,12 @@ class ReconMixFn(Function):
 
 # config.pad_rows applies from this many token rows on: below it a step is bound by the host's launch rate (per-GPU batch 64:
 # 13.5 ms of enqueue per step), where the ~50 extra small launches of a padded tower cost more than the faster kernels return
-_CROSS_WGRAD_GROUP = _tenv("SEGCLIP_CROSS_WGRAD_GROUP", "1") != "0"   # A/B: 0 = the center blocks' weight gradients as separate launches
-_PAD_ROWS_MIN = int(_tenv("SEGCLIP_PAD_ROWS_MIN", "6144"))
-_RECON_MIX = _tenv("SEGCLIP_RECON_MIX", "1") != "0"      # A/B: 0 = the batched exact-fp32 GEMM
+_PAD_ROWS_MIN = 6144
 
 
 def recon_mix(a, x):
     """a (B,M,G) @ x (B,G,D) -> (B,M,D), fp32: the dedicated kernel for G = 8, the batched GEMM otherwise."""
-    if (_RECON_MIX and a.dtype == torch.float32 and x.dtype == torch.float32 and a.dim() == 3 and x.dim() == 3 and a.shape[2] == 8
+    if (a.dtype == torch.float32 and x.dtype == torch.float32 and a.dim() == 3 and x.dim() == 3 and a.shape[2] == 8
             and x.shape[1] == 8 and x.shape[2] % 4 == 0 and 4 <= x.shape[2] <= 4096):
         return ReconMixFn.apply(a, x)
     return bmm(a, x, transB=False, out_dtype=torch.float32)

@@ -11,11 +11,8 @@ Instances and the cases that reach them:
   dma (gemm_bf16_dma.hip) 256 x 128: dma0_ff, dma0_fk_colsum, dma0_kf_pitched, dma0_kk_batched
   dma 128 x 128: dma2_ff_res32, dma2_fk_splitk, dma2_kf_f32out, dma2_kk_batched, dma2_fk_colsum_rows128,
     dma2_ff_colsum_rows128, f32split_ff (the bf16 route of config.f32_split)
-  dma 256 x 256 (all four layouts): not reachable through segclip_gemm.  The planner (csrc/gemm_plan.cpp) asks dma_covers after
-    p8_covers wherever pick_bn chose 256-wide tiles, and p8_covers is dma_covers (their shared staged_epilogue_covers) plus
-    three conditions: the SEGCLIP_GEMM_P8 switch, operand pitches below 2 GiB per 256 rows, and column sums on full 256 x 256
-    tiles only - and with column sums off full tiles dma_small_tiles sends the problem to the 128 x 128 instance.  So only
-    SEGCLIP_GEMM_P8=0 or such a pitch reach it.
+  The dma kernel has no 256 x 256 instance: a problem on 256-wide tiles that pq and p8 refuse for an operand pitch of 2 GiB or
+    more per 256 rows (per 64 k-rows) runs on the 256 x 128 instance (planned in tests/test_gemm_plan_cpu.py; not launched).
   p8 (gemm_bf16_p8.hip): p8_ff_batched, p8_ff_colsum, p8_fk_splitk, p8_kf_f32out, p8_kk_splitk
   pq (gemm_bf16_pq.hip): forward pq_f_res_rows128, data gradient pq_k_dact8_colsum_rows128, weight gradient pq_w_splitk
   f32 (gemm_f32.hip): 32 x 128 f32_skinny, 64 x 64 f32_small_batched, 128 x 128 f32_large

@@ -20,7 +20,7 @@ Instances and the rows that reach them (the forward instance of a row is indepen
   fwd generic, one tile group, rows stored from registers (Tq <= 128): s64 s97 s128, the cross rows with Tq <= 128
   fwd generic, one tile group, rows staged through LDS (129-256 queries): s129 s160 s201 s222 s223 s224 s225 s256
   fwd generic, several tile groups (more than 256 queries, always staged): s257 .. s784, x300_40
-    (several tile groups with unstaged rows is not reachable without a tuning variable: staging is on above 128 queries)
+    (several tile groups with unstaged rows is a form the kernel has and no call reaches: plan_fwd stages above 128 queries)
   fwd f32: f32_s197 f32_s77_causal f32_s40_klen f32_x40_100
   bwd smallq: as forward;  bwd dqw single: s193 s200 s201 s222 many_pf7;  bwd dqw multi: s257 s288 s449 s576 s577 s784 many_dqwm
   bwd stream pair: s319 s448 s300_causal x8_449 x8_584 x300_40;  bwd spl: s129 s160 s161 s192 many_spl many_pf6

@@ -182,6 +182,32 @@ def test_empty_problem_plans_nothing():
     assert ops.gemm_last_route() == NO_ROUTE
 
 
+def pitched_desc(M, a_ks):
+    """bf16 M x 2304 x 64 with fake pointers and an A operand whose 256 rows (64 k-rows) span exactly 2^31 bytes - the pitch
+    at which the 32-bit DMA offsets of gemm_bf16_p8.hip / gemm_bf16_pq.hip end; B k-contiguous and dense"""
+    N, K = 2304, 64
+    d = L.GemmDesc()
+    d.A, d.B, d.C = C.c_void_p(1 << 20), C.c_void_p(2 << 20), C.c_void_p(3 << 20)   # never dereferenced
+    sam, sak = (1, 1 << 24) if a_ks else (1 << 22, 1)
+    assert (64 * sak if a_ks else 256 * sam) * 2 == 1 << 31
+    d.M, d.N, d.K, d.sam, d.sak, d.sbn, d.sbk, d.ldc, d.nb1, d.nb2, d.alpha = M, N, K, sam, sak, K, 1, N, 1, 1, 1.0
+    d.a_dtype = d.b_dtype = d.c_dtype = L.BF16
+    return d
+
+
+@pytest.mark.parametrize("a_ks", [False, True], ids=["sam_4Mi", "sak_16Mi"])
+def test_two_gib_pitch_takes_the_256x128_dma_tiles(a_ks):
+    """The one input whose route moved when the 256 x 256 instance of gemm_bf16_dma.hip left: 256-wide tiles (pick_bn) that pq
+    and p8 refuse for their 32-bit operand offsets.  They run on the 256 x 128 instance, whose addresses are 64-bit; with the
+    256 x 256 instance the same descriptor planned ("dma", .., 256, 256, 1, 1).
+    M = 8192, not the 4096 the change was specified with: 16 x 9 = 144 tiles of 256 x 256 are fewer than the 256 of
+    dma_small_tiles, so M = 4096 ran - and runs - on 128 x 128 tiles and never reached the 256 x 256 instance (second assert).
+    32 x 9 = 288 tiles is past that rule and is the problem that did."""
+    DMA_256x128, DMA_128x128 = 0, 2
+    assert plan_of(pitched_desc(8192, a_ks))[::2] == (0, ops.GemmRoute("dma", a_ks, False, 256, 128, 1, DMA_256x128))
+    assert plan_of(pitched_desc(4096, a_ks))[::2] == (0, ops.GemmRoute("dma", a_ks, False, 128, 128, 1, DMA_128x128))
+
+
 @pytest.mark.parametrize("ntiles", [197 * 3, 197 * 12, 197 * 9, 256 + 128, 256 + 129, 0, 1, 154, 256, 512])
 def test_half_tile_tail_is_the_plan_s(ntiles):
     """segclip_gemm_pq_half_tail (the rows of test_wgrad_plan_cpu.test_half_tile_tail_plan) against the variant of a planned

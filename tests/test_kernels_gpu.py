@@ -188,7 +188,7 @@ def test_gemm_half_tile_tail_is_bit_identical(K):
     from segclip_amd import _lib
     lib = _lib.load()
     M, N, cut = 100 * 256, 768, 85 * 256
-    assert lib.segclip_gemm_pq_half_tail(M // 256 * 3) == 44, "SEGCLIP_PQ_HALF is off: the path under test is not reached"
+    assert lib.segclip_gemm_pq_half_tail(M // 256 * 3) == 44, "300 tiles plan no half-tile tail: the path under test is not reached"
     assert lib.segclip_gemm_pq_half_tail(cut // 256 * 3) == 0
     x, w, b = rnd(M, K, dtype=BF, seed=81), rnd(N, K, dtype=BF, seed=82, scale=K ** -0.5), rnd(N, seed=83)
     wk = rnd(K, N, dtype=BF, seed=84, scale=K ** -0.5)

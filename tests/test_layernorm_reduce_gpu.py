@@ -123,7 +123,7 @@ RT_BF = 2.0 ** -8
 DT = {F32: L.F32, BF: L.BF16}
 TN = {F32: "f32", BF: "bf16"}
 WAVES = 4
-FWD_CAP, BWD_CAP, MULTI_CAP = 4096, 768, 512          # workgroups of 4 waves (SEGCLIP_LN_BLOCKS at its default)
+FWD_CAP, BWD_CAP, MULTI_CAP = 4096, 768, 512          # workgroups of 4 waves (BWD_CAP: the cap of ln_blocks, layernorm.hip)
 CS_MAXCHUNK = 256
 
 # floors measured by floors() (torch float32 against fp64 on this file's rows, maximum over the rows of the kernel)

@@ -69,8 +69,9 @@ def test_vitl14_336_f32_matches_oracle_and_bf16_is_bounded():
           f"max |dlogit| {dlog:.4f}, hard_idx agreement {agree:.4f}, grad-norm ratio median {np.median(rat):.4f}")
     # B = 2: the loss is a 2 x 2 contrastive problem, and each of the ~1 % of patches whose 8-way argmax flips under bf16 moves
     # it.  WHICH patches flip depends on last-bit differences of the attention output: the same build gives d loss 3e-3 /
-    # |dlogit| 0.017 or 3.2e-2 / 0.13 depending on the rounding order inside the softmax (SEGCLIP_ATTN_FWD_LEAN=0/1; the
-    # kernel outputs agree to the last bf16 digit almost everywhere, tools/debug/attn_fwd_check.py) - bounds cover both
+    # |dlogit| 0.017 or 3.2e-2 / 0.13 depending on the rounding order inside the softmax (with and without the lean softmax
+    # step of the attention forward, FwdArgs::lean; the kernel outputs agree to the last bf16 digit almost everywhere) - bounds
+    # cover both
     assert dl <= 0.06 and dlog <= 0.3 and agree >= 0.97
     assert 0.95 <= float(np.median(rat)) <= 1.05
     # BASELINE configs[4] as first read: the e4m3 QK^T / PV forward in every self-attention block.  Slower than bf16 in every

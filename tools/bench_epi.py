@@ -1,7 +1,6 @@
 """Fused-epilogue GEMM variants of one residual block at the vision-tower shape against the plain kernel, with a
 numerical check of every variant against a torch fp32 product (random data, HIP events)."""
 import os, sys
-os.environ.setdefault("SEGCLIP_TUNING", "1")   # the library honours its kernel-selection switches only with this set
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from segclip_amd import ops

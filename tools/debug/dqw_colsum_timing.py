@@ -1,4 +1,5 @@
-"""Why tools/bench_attn.py (no token-sum buffer) and tools/check_attn_dqw.py (with one) time the same kernel differently."""
+"""Why the streaming attention backward (attention_dqw.inc) takes different times without a token-sum buffer (as tools/bench_attn.py
+calls it) and with one."""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

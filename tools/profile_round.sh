@@ -26,27 +26,17 @@ b vitl14 --no-cpu-baseline --no-traffic --no-parity-leg --spec vitl14_336 --batc
 b text_trim --no-cpu-baseline --no-roofline --no-parity-leg --text-trim
 for bsz in 64 96 128 192 512; do b b$bsz --no-cpu-baseline --no-roofline --no-parity-leg --batch $bsz; done
 SEGCLIP_TUNING=1 SEGCLIP_PAD_ROWS=0 b b96_pad_off --no-cpu-baseline --no-roofline --no-parity-leg --batch 96
-# same-box A/B of the grouped weight gradients (config.wgrad_group_blocks): one launch per gradient vs the default, twice
-# (library kernel-selection switches need SEGCLIP_TUNING=1)
-# same-box A/Bs, twice each: the half-tile tail of gemm_bf16_pq.hip (SEGCLIP_PQ_HALF=0 = full tiles only), B = 256 and B = 128
-# (at B = 128 the switch also decides whether M = 256 q + 128 runs on that kernel at all); gradient folding on the full loss
+# same-box A/B, twice: gradient folding on the full loss (config options read their environment defaults with SEGCLIP_TUNING=1)
 for rep in a b; do
-  SEGCLIP_TUNING=1 SEGCLIP_PQ_HALF=0 b half_off_$rep --no-cpu-baseline --no-roofline --no-parity-leg --steps 30 --warmup 8
-  b half_on_$rep --no-cpu-baseline --no-roofline --no-parity-leg --steps 30 --warmup 8
-  SEGCLIP_TUNING=1 SEGCLIP_PQ_HALF=0 b b128_half_off_$rep --no-cpu-baseline --no-roofline --no-parity-leg --batch 128 --steps 30 --warmup 8
-  b b128_half_on_$rep --no-cpu-baseline --no-roofline --no-parity-leg --batch 128 --steps 30 --warmup 8
   SEGCLIP_TUNING=1 SEGCLIP_FOLD_GRADS=0 b full_fold_off_$rep --no-cpu-baseline --no-roofline --no-parity-leg --full-loss
   b full_fold_on_$rep --no-cpu-baseline --no-roofline --no-parity-leg --full-loss
 done
-timeout 400 python tools/bench_pq_half.py 2>&1 | grep -v "$F" | grep -v "^check\|relerr" > $OUT/gemm_half_tile.txt
 timeout 300 python tools/debug/center_stage_profile.py 2>&1 | grep -v "$F" | grep -v "Warning\|warn" > $OUT/center_stage.txt
 timeout 300 python tools/bench_hbm.py 2>&1 | grep -v "$F" > $OUT/hbm_kernels.txt
 timeout 300 python tools/bench_gemm.py 2>&1 | grep -v "$F" > $OUT/gemm_shapes.txt
 timeout 300 python tools/bench_gemm.py 19712 text 2>&1 | grep -v "$F" >> $OUT/gemm_shapes.txt
 timeout 300 python tools/bench_epi.py 2>&1 | grep -v "$F" > $OUT/gemm_epilogues.txt
 timeout 200 python tools/bench_attn.py 2>&1 | grep -v "$F" > $OUT/attn.txt
-timeout 300 python tools/bench_pq.py 2>&1 | grep -v "$F" | grep -v "^check" > $OUT/gemm_pq.txt
-timeout 300 python tools/bench_pq.py 19712 2>&1 | grep -v "$F" | grep -v "^check" >> $OUT/gemm_pq.txt
 timeout 600 python tools/bench_eager.py --classes 2>/dev/null | grep "^{" > $OUT/eager_ab.json
 for spec in "50176 768 3072 nt" "50176 3072 768 dgrad" "50176 2304 768 wgrad"; do
   set -- $spec

@@ -38,15 +38,6 @@ for n, desc in (("gb2048", "--global-batch 2048 (SURVEY 8d strong-scaling base o
                 ("b96_pad_off", "--batch 96 SEGCLIP_PAD_ROWS=0 (the text tower on the ragged-edge kernels), same box"),
                 ("b128", "--batch 128"), ("b192", "--batch 192"), ("b512", "--batch 512"),
                 ("text_trim", "--text-trim: config.text_trim in the timed region (opt-in; causal text tower up to the batch's last EOT)"),
-                ("attn_fwd_old_a", "SEGCLIP_ATTN_FWD_PF=0 (one workgroup per item attention forward), same box, --steps 30"),
-                ("attn_fwd_pf_a", "default (persistent attention forward), same box, --steps 30"),
-                ("attn_fwd_old_b", "SEGCLIP_ATTN_FWD_PF=0, second pass"), ("attn_fwd_pf_b", "default, second pass"),
-                ("half_off_a", "SEGCLIP_PQ_HALF=0 (full 256 x 256 tiles only), same box, --steps 30"),
-                ("half_on_a", "default (half-tile tail of gemm_bf16_pq.hip), same box, --steps 30"),
-                ("half_off_b", "SEGCLIP_PQ_HALF=0, second pass"), ("half_on_b", "default, second pass"),
-                ("b128_half_off_a", "--batch 128 SEGCLIP_PQ_HALF=0 (M = 256 q + 128 leaves gemm_bf16_pq.hip), same box, --steps 30"),
-                ("b128_half_on_a", "--batch 128 default (last 128 rows as a row of half-tiles), same box, --steps 30"),
-                ("b128_half_off_b", "--batch 128 SEGCLIP_PQ_HALF=0, second pass"), ("b128_half_on_b", "--batch 128 default, second pass"),
                 ("full_fold_off_a", "--full-loss SEGCLIP_FOLD_GRADS=0 (the autograd engine adds the two passes' parameter gradients), same box"),
                 ("full_fold_on_a", "--full-loss default (config.fold_param_grads), same box"),
                 ("full_fold_off_b", "--full-loss SEGCLIP_FOLD_GRADS=0, second pass"), ("full_fold_on_b", "--full-loss default, second pass"),
@@ -93,13 +84,11 @@ open(P + "attn_pmc.txt", "w").write("# rocprofv3 --pmc passes on the attention k
                                    "# attn_bwd_dqw_bf16_kernel = the streaming backward with a dQ wave (attention_dqw.inc, round 6)\n" + open(R + "pmc_attn.txt").read())
 for a, h in (("gemm_shapes.txt", "# GEMM rates per shape (tools/bench_gemm.py, HIP events, 10 launches each) next to torch.matmul (hipBLASLt) on the same MI355X.\n"),
              ("gemm_epilogues.txt", "# Fused-epilogue variants of one residual block's GEMMs against the plain kernel (tools/bench_epi.py, M = 50176, D = 768)\n"),
-             ("gemm_pq.txt", "# gemm_bf16_pq.hip against the 8-phase kernel gemm_bf16_p8.hip per shape and mode, interleaved rounds (tools/bench_pq.py), M = 50176 (vision) and 19712 (text)\n"),
              ("hbm_kernels.txt", "# HBM-bound kernels against 8 TB/s (tools/bench_hbm.py)\n"),
              ("attn.txt", "# attention kernels in isolation (tools/bench_attn.py): T=196 vision (single-pass backward), T=77 causal text\n"),
              ("center_stage.txt", "# Kernel time of the learnable-center stage alone (SemanticLearnerModule forward + backward, B = 256, bf16, t18 mode;\n# tools/debug/center_stage_profile.py, torch profiler, mean of 3 passes).  Round-3 build: 4.71 ms over 361 launches, round 5: 3.18 ms over 241 (docs/experiment_log.md 4.5)\n"),
              ("stream_gaps.txt", "# tools/stream_gaps.py on the kernel trace of the bench child (profiled run: the host is slower than in the timed run)\n"),
-             ("stream_breakdown.txt", "# tools/stream_breakdown.py on the same trace: kernel time per stream and kernel (the window holds more than the 3 passes it divides by:\n# read the rows relative to each other - stream 0 is the vision tower + everything serial, i.e. the critical path)\n"),
-             ("gemm_half_tile.txt", "# tools/bench_pq_half.py: gemm_bf16_pq.hip with full tiles only against the half-tile tail (SEGCLIP_PQ_HALF=2, per-call switch), interleaved rounds, M = 50432; outputs bit-identical\n")):
+             ("stream_breakdown.txt", "# tools/stream_breakdown.py on the same trace: kernel time per stream and kernel (the window holds more than the 3 passes it divides by:\n# read the rows relative to each other - stream 0 is the vision tower + everything serial, i.e. the critical path)\n")):
     if os.path.exists(R + a):
         open(P + a, "w").write(h + open(R + a).read())
 if os.path.exists(R + "eager_ab.json"):
