@@ -1120,6 +1120,53 @@ int segclip_seg_confusion_wide(const uint16_t* pred, const uint16_t* gt, int64_t
 int segclip_seg_confusion_route(int64_t C, int wide);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-image areas of label maps (segment_image_areas.inc): the (3, C) areas of segclip_seg_areas for every picture of a list
+ * on its own, in one launch - what mmseg's pre_eval hands back per image.  The worst pictures of an evaluation, the
+ * fine-grained mIoU figures (the mean of per-image mIoU, the per-class mean over the pictures that contain the class, their
+ * worst-case variants) and a bootstrap interval over pictures are reductions of these rows.
+ *
+ * segclip_seg_image_areas: B pictures of uint8 label maps in two flat buffers.
+ *   images   : (B, SEGCLIP_SEG_IA_COLS) int64 rows on the device: 0 the offset of the picture's prediction in `pred`, in
+ *              elements  1 the offset of its ground truth in `gt`  2 its pixel count n  3 its first workgroup = the sum of
+ *              ceil(n / SEGCLIP_SEG_IA_TILE) over the pictures before it
+ *   n_blocks : that sum over all pictures, the grid
+ *   pred, gt : flat uint8 of pred_elems / gt_elems elements, read only.  They have offsets of their own because an evaluator's
+ *              label buffer has gaps between its maps (the label kernels start every map at a multiple of 4) and its ground
+ *              truths lie gapless; a picture may start at any element of either.
+ *   out      : a contiguous (B, 3, C) int64 tensor that is ADDED to.  Row i is, value for value, what segclip_seg_areas adds
+ *              for picture i alone: the same ground-truth rule pixel for pixel (a pixel with g == ignore_index contributes
+ *              nothing; with reduce_zero_label a pixel with g == 0 contributes nothing either and every other g counts as
+ *              g - 1; a value >= C on one side counts in the other side's area only) - the kernel counts with that entry's
+ *              own device functions.  The sum of the rows is segclip_seg_areas of all the pictures.
+ *   How.  256 threads; a workgroup owns one tile of SEGCLIP_SEG_IA_TILE consecutive pixels of one picture, which lane 0 finds
+ *   by a binary search over column 3.  A lane reads 16 bytes of pred and of gt per step (element alignment suffices), two
+ *   steps in flight; the fewer than 16 elements after a tile's last whole vector are read one by one.  Equal consecutive
+ *   (g, p) pairs of a lane are counted once, a constant vector in one comparison.  3 x C 32-bit counters per workgroup in LDS
+ *   (a tile is far below 2^31 pixels: none overflows), one 64-bit integer atomic per non-zero counter into the picture's
+ *   row: the sums depend on no schedule.  Bound: HBM reads, 2 bytes per pixel (4 for the wide entry).
+ *   Measured: profiles/seg_per_image.txt.
+ *   Every table row is range-checked on the device.  A row passes when its offsets are >= 0, offset + n stays within
+ *   pred_elems / gt_elems, 1 <= n < 2^31, and its workgroups lie within [0, n_blocks) and do not begin before those of the
+ *   row before it end; a workgroup whose search ends on a row that does not pass or does not hold it looks through all rows
+ *   for the first passing row that does.  A picture whose row does not pass is SKIPPED: nothing of it is read, and its row of
+ *   `out` stays as it was.  With one row whose offsets or count are refused, or whose first workgroup lies too far back, the
+ *   other pictures are counted exactly; a first workgroup that lies too far forward also fails the row after it.
+ *   B == 0 or n_blocks == 0: success, nothing launched.  SEGCLIP_ERR_UNSUPPORTED (no launch): C < 1, C > 256.
+ *   SEGCLIP_ERR_INVALID: negative sizes, B or n_blocks of 2^31 or more, missing pointers.
+ *
+ * segclip_seg_image_areas_wide: the same for uint16 elements (an int16 tensor is read as unsigned); g is compared with
+ *   ignore_index as an UNSIGNED 16-bit value.  SEGCLIP_ERR_UNSUPPORTED: C < 1, C > SEGCLIP_SEG_WIDE_MAX_CLASSES.
+ * ------------------------------------------------------------------------------------------ */
+#define SEGCLIP_SEG_IA_COLS 4     /* int64 columns of one row of the image table */
+#define SEGCLIP_SEG_IA_TILE 8192  /* pixels of one workgroup */
+int segclip_seg_image_areas(const uint8_t* pred, int64_t pred_elems, const uint8_t* gt, int64_t gt_elems, const int64_t* images,
+                            int64_t B, int64_t n_blocks, int64_t C, int ignore_index, int reduce_zero_label, int64_t* out,
+                            void* stream);
+int segclip_seg_image_areas_wide(const uint16_t* pred, int64_t pred_elems, const uint16_t* gt, int64_t gt_elems,
+                                 const int64_t* images, int64_t B, int64_t n_blocks, int64_t C, int ignore_index,
+                                 int reduce_zero_label, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image-text retrieval evaluation (retrieval.hip): Recall@K, median and mean rank in both directions from the contrastive
  * embeddings, without the (Nt, Ni) similarity matrix.  The reference trains "SegCLIP on Retrieval Task": its model carries
  * get_similarity_logits / _loose_similarity for it (modules/modeling.py:338-372) and its COCO loader builds the

@@ -12,8 +12,8 @@
 // the same for a list of background thresholds in one launch (segment_sweep.inc), test-time augmentation (segment_aug.inc), the
 // uint8 front end (segment_frontend.inc), rendering (segment_render.inc), pixel-adaptive refinement of the label maps
 // (segment_refine.inc), their connected components (segment_objects.inc), despeckling by merging (segment_sieve.inc), the training front end (train_frontend.inc),
-// the 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc) and the confusion matrix of label maps
-// (segment_confusion.inc).
+// the 16-bit label maps of vocabularies of up to 1024 classes (segment_wide.inc), the confusion matrix of label maps
+// (segment_confusion.inc) and their per-image areas (segment_image_areas.inc).
 #include "common.h"
 
 #include <atomic>
@@ -290,6 +290,7 @@ int seg_pixel_check(const char* what, int64_t n_windows, int64_t B, int64_t H, i
 #include "segment_vote.inc"
 #include "segment_boundary.inc"
 #include "segment_confusion.inc"
+#include "segment_image_areas.inc"
 #include "train_frontend.inc"
 
 }  // namespace
@@ -731,6 +732,44 @@ extern "C" int segclip_seg_confusion_route(int64_t C, int wide) {
   SegConfPlan p;
   if (int rc = seg_conf_plan(what, C, p)) return rc;
   return p.dense ? 0 : 1;
+}
+
+// per-image areas (segment_image_areas.inc): one launch of n_blocks workgroups, every table row checked on the device
+template <typename T>
+static int seg_image_areas_launch(const char* what, const T* pred, int64_t pred_elems, const T* gt, int64_t gt_elems,
+                                  const int64_t* images, int64_t B, int64_t n_blocks, int64_t C, int max_classes, int ignore_index,
+                                  int reduce_zero_label, int64_t* out, void* stream) {
+  SEG_REFUSE(C < 1 || C > max_classes, "%s: %lld classes, 1..%d supported", what, (long long)C, max_classes);
+  const int64_t lim = 1ll << 31;
+  SEGCLIP_REQUIRE(B >= 0 && B < lim && n_blocks >= 0 && n_blocks < lim && pred_elems >= 0 && gt_elems >= 0,
+                  "%s: need 0 <= B, n_blocks < 2^31 and buffer sizes that are not negative", what);
+  if (B == 0 || n_blocks == 0) return 0;
+  SEGCLIP_REQUIRE(pred && gt && images && out, "%s: pred, gt, images and out are required", what);
+  SEGCLIP_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gt)) & (sizeof(T) - 1)) == 0 &&
+                      ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(images)) & 7) == 0,
+                  "%s: pred and gt are aligned to their element, images and out to 8 bytes", what);
+  SegIAArgs a;
+  a.pred = pred; a.gt = gt; a.images = images;
+  a.pred_n = pred_elems; a.gt_n = gt_elems; a.n_blocks = n_blocks;
+  a.B = (int)B; a.C = (int)C; a.ignore_index = ignore_index; a.reduce_zero = reduce_zero_label ? 1 : 0;
+  a.out = reinterpret_cast<unsigned long long*>(out);
+  hipLaunchKernelGGL(seg_image_areas_kernel<T>, dim3((unsigned)n_blocks), dim3(SEG_IA_THREADS), 0, ST, a);
+  SEGCLIP_CHECK_LAUNCH(what);
+  return 0;
+}
+
+extern "C" int segclip_seg_image_areas(const uint8_t* pred, int64_t pred_elems, const uint8_t* gt, int64_t gt_elems,
+                                       const int64_t* images, int64_t B, int64_t n_blocks, int64_t C, int ignore_index,
+                                       int reduce_zero_label, int64_t* out, void* stream) {
+  return seg_image_areas_launch("seg_image_areas", pred, pred_elems, gt, gt_elems, images, B, n_blocks, C, SEG_MAX_CLASSES, ignore_index,
+                                reduce_zero_label, out, stream);
+}
+
+extern "C" int segclip_seg_image_areas_wide(const uint16_t* pred, int64_t pred_elems, const uint16_t* gt, int64_t gt_elems,
+                                            const int64_t* images, int64_t B, int64_t n_blocks, int64_t C, int ignore_index,
+                                            int reduce_zero_label, int64_t* out, void* stream) {
+  return seg_image_areas_launch("seg_image_areas_wide", pred, pred_elems, gt, gt_elems, images, B, n_blocks, C, SEG_WIDE_MAX_CLASSES,
+                                ignore_index, reduce_zero_label, out, stream);
 }
 
 // views: the (B, 7) table with a flag word per row and the kernel that mirrors (segment_frontend.inc)

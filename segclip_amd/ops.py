@@ -2705,6 +2705,56 @@ def seg_confusion_route(num_classes, dtype=torch.uint8):
     return ("dense", "sparse")[rc]
 
 
+SEG_IA_COLS = L.const("SEG_IA_COLS")  # int64 columns of one row of the image table of segclip_seg_image_areas
+SEG_IA_TILE = L.const("SEG_IA_TILE")  # pixels of one of its workgroups
+
+
+def seg_image_areas_table(pred_offs, gt_offs, counts, device):
+    """The device image table of seg_image_areas: pred_offs [the element offset of each picture's prediction in the flat
+    prediction buffer], gt_offs [that of its ground truth in the flat ground-truth buffer], counts [its pixels]
+    -> (table (B, 4) int64, n_blocks).  The host lists go to the device in one small copy through pinned memory."""
+    n = len(counts)
+    if n == 0:
+        raise ValueError("seg_image_areas: counts is empty")
+    for name, v in (("pred_offs", pred_offs), ("gt_offs", gt_offs)):
+        if len(v) != n:
+            raise ValueError(f"seg_image_areas: {n} counts but {name} has {len(v)} entries")
+    tab, blk = [], 0
+    for i, (po, go, cnt) in enumerate(zip(pred_offs, gt_offs, counts)):
+        po, go, cnt = int(po), int(go), int(cnt)
+        if not 1 <= cnt < 1 << 31:
+            raise ValueError(f"seg_image_areas: a picture has 1 .. 2^31 - 1 pixels, picture {i} has {cnt}")
+        if po < 0 or go < 0:
+            raise ValueError(f"seg_image_areas: offsets are not negative, picture {i} has {po} and {go}")
+        tab.append([po, go, cnt, blk])
+        blk += (cnt + SEG_IA_TILE - 1) // SEG_IA_TILE
+    return _upload_table(tab, torch.int64, device).view(-1, SEG_IA_COLS), blk
+
+
+def seg_image_areas(pred, gt, table, n_blocks, num_classes, ignore_index=255, reduce_zero_label=False, out=None):
+    """The (3, C) areas of seg_areas for every picture of a list on its own, in one launch (segclip_seg_image_areas /
+    segclip_seg_image_areas_wide, picked by the dtype: uint8, or torch.int16 read as unsigned 16-bit values): pred and gt are
+    flat buffers, `table` and n_blocks those of seg_image_areas_table -> (B, 3, C) int64, row i = intersection, prediction area
+    and label area of picture i; added to `out` when given.  A picture whose table row the device refuses is skipped.  No host
+    synchronisation."""
+    L.require_cuda(pred, gt, table, out)
+    if pred.dtype not in (torch.uint8, torch.int16) or gt.dtype != pred.dtype:
+        raise ValueError("seg_image_areas: pred and gt are both uint8 or both int16 tensors")
+    if not pred.is_contiguous() or not gt.is_contiguous():
+        raise ValueError("seg_image_areas: pred and gt are contiguous buffers (the table's offsets count their elements)")
+    _check_image_table("seg_image_areas", table, SEG_IA_COLS, "seg_image_areas_table")
+    B, C = table.shape[0], int(num_classes)
+    if out is None:
+        out = torch.zeros(B, 3, max(C, 0), dtype=torch.int64, device=pred.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or tuple(out.shape) != (B, 3, C):
+        raise ValueError(f"seg_image_areas: out is a contiguous (B, 3, C) = ({B}, 3, {C}) int64 tensor")
+    wide = pred.dtype == torch.int16
+    fn = L.load().segclip_seg_image_areas_wide if wide else L.load().segclip_seg_image_areas
+    L.check(fn(L.ptr(pred), pred.numel(), L.ptr(gt), gt.numel(), L.ptr(table), B, int(n_blocks), C, int(ignore_index),
+               int(bool(reduce_zero_label)), L.ptr(out), L.stream()), "seg_image_areas_wide" if wide else "seg_image_areas")
+    return out
+
+
 SEG_SOURCE_COLS = L.const("SEG_SOURCE_COLS")  # int64 columns of one row of the source table of segclip_seg_windows_from_u8
 SEG_SOURCE_LIMIT = L.const("SEG_SOURCE_LIMIT")  # h, w, H, W of an image stay below it (the kernel's integer coordinates)
 

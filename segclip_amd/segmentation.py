@@ -73,6 +73,17 @@ or a table of pairs per workgroup in LDS), without a host synchronisation; compu
 fwIoU and kappa, and areas_from_confusion, confusion_metrics, confused_pairs and merge_classes work on a host copy without an
 evaluator.  Not covered: SegSweepEvaluator.
 
+Per-image areas (mmseg's pre_eval hands them back; the summed (3, C) table cannot): image_areas counts a list of label maps
+against their ground truths into a (B, 3, C) int64 device tensor, one (3, C) row per picture, in one launch
+(csrc/segment_image_areas.inc: one tile of one picture per workgroup, 16-byte loads at any element offset, run-length counting,
+the counters in LDS), and SegEvaluator(per_image=True) does so on every update path, 8- or 16-bit, with one more call on the
+maps that leave the chain and without a host synchronisation; `image_areas` is the (n, 3, C) concatenation in the order the
+pictures were given.  Three reductions of the rows, static and without an evaluator: fine_grained_from_image_areas (the mean of
+per-image mIoU, the per-class mean over the pictures that contain the class, and the means of their lowest q %),
+worst_images (the k lowest pictures) and bootstrap_miou (a confidence interval of the data-set mIoU from resampled pictures);
+compute() adds the first.  Several ranks gather the rows (all_gather), they are not summed.  Not covered: SegSweepEvaluator,
+per-image boundary areas and per-image confusion.
+
 Superpixels and snapping (not in the reference): the third standard answer to borders that follow the patch grid.  Superpixels
 states an integer SLIC on the RGB bytes, superpixels cuts a list of decoded pictures into segments on the device
 (csrc/segment_superpixel.inc), snap_labels gives every segment the majority label of its pixels (csrc/segment_vote.inc) - the
@@ -867,6 +878,33 @@ def boundary_areas(preds, gts, num_classes, boundary, ignore_index=255, reduce_z
     return areas
 
 
+def _image_areas_call(batch, gts, num_classes, **rule):
+    """ops.seg_image_areas over a _Maps, read where its maps lie (gaps included), and the ground truths of its maps, laid
+    gapless one after the other -> (B, 3, C) int64."""
+    gt, gt_offs = _Maps.gapless_of(gts)
+    table, n_blocks = ops.seg_image_areas_table(batch.offs, gt_offs, [h * w for h, w in batch.sizes], batch.flat.device)
+    return ops.seg_image_areas(batch.flat, gt, table, n_blocks, num_classes, **rule)
+
+
+@torch.no_grad()
+def image_areas(preds, gts, num_classes, ignore_index=255, reduce_zero_label=False):
+    """preds, gts [(h_i, w_i) maps of any mix of sizes, all uint8 or all int16 (16-bit maps read as unsigned values), sizes equal
+    pairwise] -> (B, 3, C) int64 on the device: row i is the intersection, prediction area and label area per class of picture
+    i alone, ops.seg_areas of that pair value for value (the same ground-truth rule: ignore_index, reduce_zero_label, values
+    >= C), so the sum of the rows is the (3, C) `areas` of the list.  Predictions that are views of one buffer (what predict_raw
+    returns) are read where they lie.  One call, no host synchronisation.  SegEvaluator.fine_grained_from_image_areas,
+    worst_images and bootstrap_miou turn the rows into figures."""
+    preds, gts = list(preds), list(gts)
+    _check_maps(preds, wide=True)
+    if len(preds) != len(gts):
+        raise ValueError(f"{len(preds)} predictions but {len(gts)} ground truths")
+    SegEvaluator._check_gts(preds, gts, preds[0].dtype)
+    for i, (p, g) in enumerate(zip(preds, gts)):
+        if tuple(p.shape) != tuple(g.shape):
+            raise ValueError(f"image_areas: a ground truth has its label map's size {tuple(p.shape)}, ground truth {i} is {tuple(g.shape)}")
+    return _image_areas_call(_Maps.of(preds), gts, num_classes, ignore_index=ignore_index, reduce_zero_label=reduce_zero_label)
+
+
 def _check_stages(refine, clean, raws, out_shapes, snap=None):
     """refine=, snap= and clean= of predict_raw / update_raw: a PAMR and a Snap, each with label maps at the pictures' own
     sizes, and a Despeckle.  It runs before the source is built: what the host does between the source's table copy and the
@@ -897,8 +935,9 @@ def _refuse(entry, *stages):
 
 
 # What an evaluator's call hands to the chain: the ground truths, the (3, C) areas, the ground-truth rule (ignore_index and
-# reduce_zero_label, as keyword arguments of every kernel that counts), the Boundary or None and its (2, 3, C) areas.
-_Score = collections.namedtuple("_Score", "gts areas rule boundary boundary_areas confusion", defaults=(None,))
+# reduce_zero_label, as keyword arguments of every kernel that counts), the Boundary or None and its (2, 3, C) areas, the
+# confusion matrix or None, and the list that takes the call's (B, 3, C) per-image areas or None.
+_Score = collections.namedtuple("_Score", "gts areas rule boundary boundary_areas confusion per_image", defaults=(None, None))
 
 
 def _out_shapes(src, out_shapes):
@@ -1154,7 +1193,7 @@ class SegInference:
     def _post_process(self, src, out_shapes, refine=None, clean=None, score=None, want_labels=True, snap=None):
         """The chain of every list entry point that returns or scores label maps: labels -> refine (a PAMR, against
         src.pictures) -> snap (a Snap, against src.pictures) -> clean (a Despeckle) -> the mIoU areas -> the boundary areas -> the
-        confusion matrix.  score: None, or the _Score of an
+        confusion matrix -> the per-image areas.  score: None, or the _Score of an
         evaluator's call; the areas are those of the maps that leave the chain, counted once (`counts`), by
 
             refine   snap   clean       the mIoU areas are counted by
@@ -1164,13 +1203,14 @@ class SegInference:
             any      any    Despeckle   ops.seg_areas on the cleaned maps, gapless; nothing earlier counts
 
         and with score.boundary one more ops.seg_boundary call on the same maps adds to score.boundary_areas, with
-        score.confusion one ops.seg_confusion call on them, laid gapless, to that matrix.  The labels are
+        score.confusion one ops.seg_confusion call on them, laid gapless, to that matrix, with score.per_image one
+        ops.seg_image_areas call on them, where they lie, whose (B, 3, C) rows are appended to that list.  The labels are
         formed whenever a later stage reads them, wanted or not.  -> the final maps, or None when they are not wanted."""
         forward = self._views_forward if src.augmented else self._list_forward
         counts = (None if score is None else "clean" if clean is not None else "snap" if snap is not None else
                   "refine" if refine is not None else "labels")
         counting = {} if score is None else dict(gts=score.gts, areas=score.areas, **score.rule)
-        reads_labels = score is not None and (score.boundary is not None or score.confusion is not None)
+        reads_labels = score is not None and (score.boundary is not None or score.confusion is not None or score.per_image is not None)
         first = dict(counting, want_labels=want_labels or reads_labels) if counts == "labels" else {}
         labels = forward(src, out_shapes, **first)
         if refine is not None:
@@ -1191,6 +1231,8 @@ class SegInference:
         if score is not None and score.confusion is not None:
             ops.seg_confusion(_Maps.of(labels).gapless(), _Maps.gapless_of(score.gts)[0], self.num_classes, conf=score.confusion,
                               **score.rule)
+        if score is not None and score.per_image is not None:
+            score.per_image.append(_image_areas_call(_Maps.of(labels), score.gts, self.num_classes, **score.rule))
         return labels if want_labels else None
 
     @torch.no_grad()
@@ -1403,13 +1445,21 @@ class SegEvaluator:
     is a projection of it (areas_from_confusion).  The labels are then formed even when return_labels is False, and
     compute() adds confusion, Dice, Precision, Recall, Fscore, mDice, mFscore, fwIoU and kappa from the same host copy.
     Several ranks: all_reduce `confusion` (sum) like `areas`.  Without it nothing changes.
+    per_image (True): every update path also counts the labels whose areas it counts - the refined, snapped or cleaned ones,
+    exactly as confusion=True sees them - picture by picture with one more call (segclip_seg_image_areas, or its 16-bit
+    entry): one (3, C) row per picture, kept as a list of per-call device tensors.  `image_areas` is their concatenation,
+    (n, 3, C) int64, in the order the pictures were given ((0, 3, C) before any update; reset() clears it), and its sum over
+    the pictures is `areas`.  The labels are then formed even when return_labels is False, no update synchronises with the
+    host, and compute() adds image_mIoU, mIoU_I, IoU_C, mIoU_C, mIoU_I_q and mIoU_C_q (fine_grained_from_image_areas, reduced
+    on the device).  Several ranks: the rows are CONCATENATED - all_gather `image_areas`, never all_reduce it - and the
+    figures taken from the gathered tensor with the static functions.  Without it nothing changes.
     Over a SegInference with label_dtype=torch.int16 the ground truths are (oh, ow) torch.int16 tensors whose elements are read
     as unsigned 16-bit values (a loader's uint16 array goes in as .view(torch.int16)), ignore_index is an integer in
     0 .. 65535 compared with that value, and boundary= is refused (boundary_areas takes the int16 maps that update_raw returns);
     confusion= works there too.
     update_maps(preds, gts) scores label maps that exist already, of either width, without the towers."""
 
-    def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None, confusion=False):
+    def __init__(self, seg, ignore_index=255, reduce_zero_label=False, boundary=None, confusion=False, per_image=False):
         self.gt_dtype = getattr(seg, "label_dtype", torch.uint8)
         if self.gt_dtype == torch.int16:
             _refuse("SegEvaluator", ("boundary", boundary, "is not built for 16-bit label maps (label_dtype=torch.int16)"))
@@ -1425,6 +1475,16 @@ class SegEvaluator:
         self.confusion = None
         if confusion:
             self.confusion = torch.zeros(seg.num_classes + 1, seg.num_classes + 1, dtype=torch.int64, device=self.areas.device)
+        self._image_rows = [] if per_image else None   # one (B, 3, C) device tensor per update call
+
+    @property
+    def image_areas(self):
+        """(n, 3, C) int64 on the device: one row per picture seen, in the order given; None without per_image=True."""
+        if self._image_rows is None:
+            return None
+        if len(self._image_rows) > 1:   # kept as one tensor from here on
+            self._image_rows = [torch.cat(self._image_rows)]
+        return self._image_rows[0] if self._image_rows else self.areas.new_zeros(0, 3, self.areas.shape[1])
 
     def reset(self):
         self.areas.zero_()
@@ -1432,11 +1492,14 @@ class SegEvaluator:
             self.boundary_areas.zero_()
         if self.confusion is not None:
             self.confusion.zero_()
+        if self._image_rows is not None:
+            self._image_rows.clear()
 
     def _score(self, gts):
         """-> (what the chain, SegInference._post_process, scores a call against; the ground truths' sizes, its out_shapes)"""
         rule = dict(ignore_index=self.ignore_index, reduce_zero_label=self.reduce_zero_label)
-        return _Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas, self.confusion), [tuple(g.shape) for g in gts]
+        return (_Score(list(gts), self.areas, rule, self.boundary, self.boundary_areas, self.confusion, self._image_rows),
+                [tuple(g.shape) for g in gts])
 
     @torch.no_grad()
     def update(self, imgs, gts, return_labels=False, refine=None, clean=None, snap=None):
@@ -1468,8 +1531,8 @@ class SegEvaluator:
     def update_maps(self, preds, gts):
         """Scores label maps that exist already - refined elsewhere, read from disk, or what despeckle returned: preds
         [(oh_i, ow_i) maps of the evaluator's label dtype, uint8 or int16], gts [the ground truths, of the same dtype and sizes].
-        Adds to `areas` (ops.seg_areas / ops.seg_areas_wide), with confusion=True to `confusion`, and on a uint8 evaluator with
-        boundary= to `boundary_areas`: exactly what update / update_raw count for the same maps.  It is how a 16-bit evaluator
+        Adds to `areas` (ops.seg_areas / ops.seg_areas_wide), with confusion=True to `confusion`, with per_image=True one row
+        per map to `image_areas`, and on a uint8 evaluator with boundary= to `boundary_areas`: exactly what update / update_raw count for the same maps.  It is how a 16-bit evaluator
         scores despeckled maps, whose in-pipeline stage (update_raw(clean=)) stays refused.  No towers, no host
         synchronisation.  -> None."""
         preds, gts = list(preds), list(gts)
@@ -1496,6 +1559,8 @@ class SegEvaluator:
             _boundary_call(batch, self.boundary, gts=gts, num_classes=C, areas=self.boundary_areas, **rule)
         if self.confusion is not None:
             ops.seg_confusion(flat, gt, C, conf=self.confusion, **rule)
+        if self._image_rows is not None:
+            self._image_rows.append(_image_areas_call(batch, gts, C, **rule))
 
     @torch.no_grad()
     def update_views(self, views, gts, return_labels=False):
@@ -1612,21 +1677,148 @@ class SegEvaluator:
         rows = torch.zeros(M + 1, C + 1, dtype=torch.int64).index_add_(0, idx, conf)
         return torch.zeros(M + 1, M + 1, dtype=torch.int64).index_add_(1, idx, rows)
 
-    def compute(self):
+    @staticmethod
+    def _check_image_areas(image_areas):
+        if not isinstance(image_areas, torch.Tensor) or image_areas.dim() != 3 or image_areas.shape[1] != 3 \
+                or image_areas.is_floating_point() or image_areas.is_complex() or image_areas.dtype == torch.bool:
+            got = f"{image_areas.dtype} {tuple(image_areas.shape)}" if isinstance(image_areas, torch.Tensor) else repr(type(image_areas))
+            raise ValueError(f"image_areas is an (n, 3, C) integer tensor, got {got}")
+        return image_areas
+
+    @staticmethod
+    def _check_quantiles(quantiles):
+        qs = [float(q) for q in quantiles]
+        for q in qs:
+            if not 0.0 < q <= 1.0:   # NaN fails too
+                raise ValueError(f"a quantile q lies in (0, 1], got {q!r}")
+        return qs
+
+    @staticmethod
+    def _lowest_means(values, qs):
+        """values (m_max, K) fp64 with NaN for "no value": per column the mean of its max(1, ceil(q * m)) lowest values, m the
+        column's count of values -> [(K,) per q], NaN for a column without a value.  Tensor arithmetic only: no host copy."""
+        n = values.shape[0]
+        have = ~torch.isnan(values)
+        m = have.sum(0)
+        if n == 0:
+            return [torch.full_like(m, float("nan"), dtype=torch.float64) for _ in qs]
+        ordered = torch.sort(values, dim=0).values   # NaN sorts last
+        sums = torch.cumsum(torch.nan_to_num(ordered, nan=0.0), dim=0)
+        out = []
+        for q in qs:
+            k = torch.ceil(q * m.to(torch.float64)).to(torch.int64).clamp_(min=1)
+            mean = sums.gather(0, (k - 1).clamp_(max=n - 1).unsqueeze(0))[0] / k.to(torch.float64)
+            out.append(torch.where(m > 0, mean, torch.full_like(mean, float("nan"))))
+        return out
+
+    @staticmethod
+    def _fine_grained(image_areas, qs):
+        """The figures of fine_grained_from_image_areas as fp64 tensors on the tensor's device:
+        -> (image_mIoU (n,), IoU_C (C,), scalars (2 + 2 len(qs),) = mIoU_I, mIoU_C, mIoU_I_q..., mIoU_C_q...)."""
+        a = image_areas.to(torch.float64)
+        inter, pred, label = a[:, 0], a[:, 1], a[:, 2]
+        union = pred + label - inter
+        nan = torch.full_like(union, float("nan"))
+        iou = torch.where(union > 0, inter / union, nan)
+        per_image = torch.nanmean(iou, dim=1)
+        in_class = torch.where(label > 0, iou, nan)   # L > 0 implies U > 0
+        # the plain means are the means of the lowest 100 %: mIoU_I_q[1.0] == mIoU_I and mIoU_C_q[1.0] == mIoU_C bit for bit
+        low_i = SegEvaluator._lowest_means(per_image.unsqueeze(1), [1.0] + qs)
+        low_c = SegEvaluator._lowest_means(in_class, [1.0] + qs)
+        per_class = low_c[0]
+        scalars = [v[0] for v in low_i[:1]] + [torch.nanmean(per_class)] + [v[0] for v in low_i[1:]] + [torch.nanmean(v) for v in low_c[1:]]
+        return per_image, per_class, torch.stack(scalars)
+
+    @staticmethod
+    def _fine_grained_dict(per_image, per_class, scalars, qs):
+        s = scalars.tolist()
+        return dict(image_mIoU=per_image, mIoU_I=s[0], IoU_C=per_class, mIoU_C=s[1],
+                    mIoU_I_q={q: s[2 + i] for i, q in enumerate(qs)}, mIoU_C_q={q: s[2 + len(qs) + i] for i, q in enumerate(qs)})
+
+    @staticmethod
+    def fine_grained_from_image_areas(image_areas, quantiles=(0.05, 0.1)):
+        """(n, 3, C) integer tensor (`image_areas`), on the CPU or on a device -> dict of the fine-grained mIoU figures, in fp64.
+        Per picture i and class c, with I, P, L the picture's areas: U = P + L - I and iou[i, c] = I / U where U > 0, else NaN.
+            image_mIoU  (n,) fp64 CPU tensor: the mean of iou[i] over the classes with a value; NaN for a picture with no class
+                        on either side (all its pixels ignored).  A class that is predicted but not labelled counts, as 0.
+            mIoU_I      the mean of image_mIoU over the pictures with a score
+            IoU_C       (C,) fp64 CPU tensor: for class c the mean of iou[i, c] over the pictures with L[i, c] > 0 - those that
+                        contain the class; NaN where there is none
+            mIoU_C      the mean of IoU_C over the classes with a value
+            mIoU_I_q    {q: the mean of the max(1, ceil(q * m)) lowest of the m picture scores}: the worst q of the pictures
+            mIoU_C_q    {q: per class the mean of the max(1, ceil(q * m_c)) lowest of its m_c values, then the mean over the
+                        classes with a value}
+        q lies in (0, 1]; q = 1 gives mIoU_I and mIoU_C.  The data-set mIoU (metrics_from_areas of the summed rows) is dominated
+        by large objects and large pictures; these figures weigh every picture, or every picture of a class, alike.  The
+        reduction runs where the tensor lies, and one small copy brings the figures to the host."""
+        image_areas = SegEvaluator._check_image_areas(image_areas)
+        qs = SegEvaluator._check_quantiles(quantiles)
+        per_image, per_class, scalars = SegEvaluator._fine_grained(image_areas, qs)
+        n, C = per_image.numel(), per_class.numel()
+        host = torch.cat([per_image, per_class, scalars]).cpu()
+        return SegEvaluator._fine_grained_dict(host[:n], host[n:n + C], host[n + C:], qs)
+
+    @staticmethod
+    def worst_images(image_areas, k):
+        """(n, 3, C) integer tensor -> [(index, image_mIoU)] of the k pictures with the lowest score, by rising score and, among
+        equal scores, rising index; pictures without a score (all pixels ignored) are left out."""
+        scores = SegEvaluator.fine_grained_from_image_areas(image_areas, ())["image_mIoU"].tolist()
+        ranked = sorted((s, i) for i, s in enumerate(scores) if not math.isnan(s))
+        return [(i, s) for s, i in ranked[:max(int(k), 0)]]
+
+    @staticmethod
+    def bootstrap_miou(image_areas, n_boot=1000, alpha=0.05, seed=0):
+        """A bootstrap over pictures of the data-set mIoU: (n, 3, C) integer tensor -> dict(lo, hi, std, replicates).  Replicate
+        r draws n pictures with replacement, idx = torch.randint(0, n, (n_boot, n), generator=torch.Generator().manual_seed(
+        seed)), sums their rows - formed for all replicates at once as the fp64 product of the (n_boot, n) matrix of draw
+        counts with the (n, 3 C) areas, exact while the sums stay below 2^53 - and takes metrics_from_areas(...)["mIoU"] of
+        the sum.  replicates: (n_boot,) fp64; lo, hi: torch.quantile of them at alpha / 2 and 1 - alpha / 2; std: their
+        standard deviation (one less than their number in the denominator; 0 for a single one).  A replicate that drew only
+        pictures whose pixels are all ignored has no mIoU: it stays NaN in `replicates` and is left out of lo, hi and std.
+        Runs on a CPU copy; the same seed gives the same interval."""
+        image_areas = SegEvaluator._check_image_areas(image_areas)
+        n, _, C = image_areas.shape
+        n_boot = int(n_boot)
+        if n < 1 or n_boot < 1:
+            raise ValueError(f"bootstrap_miou needs at least one picture and one replicate, got n = {n} and n_boot = {n_boot}")
+        if not 0.0 < float(alpha) < 1.0:
+            raise ValueError(f"alpha lies in (0, 1), got {alpha!r}")
+        rows = image_areas.cpu().to(torch.float64).reshape(n, 3 * C)
+        idx = torch.randint(0, n, (n_boot, n), generator=torch.Generator().manual_seed(int(seed)))
+        draws = torch.zeros(n_boot, n, dtype=torch.float64).scatter_add_(1, idx, torch.ones(n_boot, n, dtype=torch.float64))
+        sums = (draws @ rows).view(n_boot, 3, C)
+        replicates = torch.tensor([SegEvaluator.metrics_from_areas(s)["mIoU"] for s in sums], dtype=torch.float64)
+        scored = replicates[~torch.isnan(replicates)]   # a replicate that drew all-ignored pictures only has no mIoU
+        if scored.numel() == 0:
+            return dict(lo=float("nan"), hi=float("nan"), std=float("nan"), replicates=replicates)
+        lo, hi = torch.quantile(scored, torch.tensor([alpha / 2.0, 1.0 - alpha / 2.0], dtype=torch.float64)).tolist()
+        return dict(lo=lo, hi=hi, std=float(scored.std()) if scored.numel() > 1 else 0.0, replicates=replicates)
+
+    def compute(self, quantiles=(0.05, 0.1)):
+        """quantiles: the q of mIoU_I_q and mIoU_C_q, read with per_image=True only."""
         parts = [self.areas.reshape(-1)]
         if self.boundary is not None:
             parts.append(self.boundary_areas.reshape(-1))
         if self.confusion is not None:
             parts.append(self.confusion.reshape(-1))
+        fine = None
+        if self._image_rows is not None:   # reduced on the device; the figures go to the host beside the areas
+            qs = self._check_quantiles(quantiles)
+            fine = self._fine_grained(self.image_areas, qs)
         if len(parts) == 1:
-            return self.metrics_from_areas(self.areas.cpu())
-        C = self.areas.shape[1]
-        host = torch.cat(parts).cpu()  # the one host copy
-        out = self.metrics_from_areas(host[:3 * C].view(3, C))
-        if self.boundary is not None:
-            out.update(self.boundary_metrics_from_areas(host[3 * C:9 * C].view(2, 3, C)))
-        if self.confusion is not None:
-            out.update(self.confusion_metrics(host[-(C + 1) * (C + 1):].view(C + 1, C + 1)))
+            out = self.metrics_from_areas(self.areas.cpu())
+        else:
+            C = self.areas.shape[1]
+            host = torch.cat(parts).cpu()  # the one host copy
+            out = self.metrics_from_areas(host[:3 * C].view(3, C))
+            if self.boundary is not None:
+                out.update(self.boundary_metrics_from_areas(host[3 * C:9 * C].view(2, 3, C)))
+            if self.confusion is not None:
+                out.update(self.confusion_metrics(host[-(C + 1) * (C + 1):].view(C + 1, C + 1)))
+        if fine is not None:
+            n, C = fine[0].numel(), fine[1].numel()
+            host = torch.cat(fine).cpu()
+            out.update(self._fine_grained_dict(host[:n], host[n:n + C], host[n + C:], qs))
         return out
 
 

@@ -304,7 +304,12 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     test_cfg["confusion"] = True: the labels are also counted into the confusion matrix, SegEvaluator(confusion=True), 8- or
     16-bit maps alike, and the function returns a dict: mIoU, mDice, mFscore and fwIoU in percent, kappa, and `confusion`, the
     (C + 1, C + 1) int64 CPU tensor of this rank (rows the ground truth, index C the out-of-range bin), beside the boundary
-    keys when both are asked for."""
+    keys when both are asked for.
+    test_cfg["per_image"] = True: the labels are also counted picture by picture, SegEvaluator(per_image=True), 8- or 16-bit
+    maps alike, and the function returns a dict: mIoU, mIoU_I (the mean of per-image mIoU) and mIoU_C (the per-class mean over
+    the pictures that contain the class) in percent, the worst-case dicts mIoU_I_q and mIoU_C_q ({q: percent}, q = 0.05 and
+    0.1), and `image_mIoU`, the (n,) fp64 CPU tensor of this rank's per-picture scores (0 .. 1, NaN for a picture whose
+    pixels are all ignored), in the order of `batches`; beside the boundary and confusion keys when those are asked for."""
     from .segmentation import SegEvaluator, SegInference, build_text_embedding
     cfg = dict(test_cfg or {})
     ignore_index, reduce_zero_label = cfg.pop("ignore_index", 255), cfg.pop("reduce_zero_label", False)
@@ -322,11 +327,12 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
         raise ValueError("eval_epoch: test_cfg['clean'] is applied by SegEvaluator.update_raw: pass a transform")
     boundary = cfg.pop("boundary", None)
     confusion = bool(cfg.pop("confusion", False))
+    per_image = bool(cfg.pop("per_image", False))
     model = _unwrap(model)
     model.eval()
     emb = build_text_embedding(model, text_tokens.to(device))
     evaluator = SegEvaluator(SegInference(model, emb, with_bg, **cfg), ignore_index, reduce_zero_label, boundary=boundary,
-                             confusion=confusion)
+                             confusion=confusion, per_image=per_image)
     for imgs, gts in batches:
         imgs, gts = [t.to(device, non_blocking=True) for t in imgs], [g.to(device, non_blocking=True) for g in gts]
         if transform is None:
@@ -337,7 +343,7 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
     miou = metrics["mIoU"] * 100.0
     if getattr(args, "local_rank", 0) == 0:
         logger.info("Zero-shot segmentation mIoU: %.2f", miou)
-    if boundary is None and not confusion:
+    if boundary is None and not confusion and not per_image:
         return miou
     out = {"mIoU": miou}
     if boundary is not None:
@@ -351,6 +357,15 @@ def eval_epoch(args, model, device, n_gpu, batches, text_tokens, with_bg, test_c
         out["kappa"], out["confusion"] = metrics["kappa"], metrics["confusion"]
         if getattr(args, "local_rank", 0) == 0:
             logger.info("mDice: %.2f, mFscore: %.2f, fwIoU: %.2f, kappa: %.4f", out["mDice"], out["mFscore"], out["fwIoU"], out["kappa"])
+    if per_image:
+        out["mIoU_I"], out["mIoU_C"] = metrics["mIoU_I"] * 100.0, metrics["mIoU_C"] * 100.0
+        for key in ("mIoU_I_q", "mIoU_C_q"):
+            out[key] = {q: v * 100.0 for q, v in metrics[key].items()}
+        out["image_mIoU"] = metrics["image_mIoU"]
+        if getattr(args, "local_rank", 0) == 0:
+            logger.info("Per-image mIoU: %.2f, per-class mIoU over the pictures of a class: %.2f; worst %s of the pictures: %s",
+                        out["mIoU_I"], out["mIoU_C"], ", ".join(f"{q:g}" for q in out["mIoU_I_q"]),
+                        ", ".join(f"{v:.2f}" for v in out["mIoU_I_q"].values()))
     return out
 
 

@@ -109,11 +109,23 @@ command and alternating within every repeat:
         copies of 8 maps, scaled to 64), and the new kernels' own times from a separate `rocprofv3 --kernel-trace --stats`
         child (--snap-child: five calls of superpixels and snap_labels and nothing else) against their design traffic
         (DESIGN.md section 4).
+With --per-image instead: the per-image areas (segmentation.image_areas, SegEvaluator(per_image=True);
+csrc/segment_image_areas.inc) on the 64 label maps of --objects (12.0 M pixels, views of update_raw's label buffer, read where
+they lie) at 21 and 151 classes and on their int16 copies, in the same layout, at 21, 151, 460 and 848 classes, against
+two ground truths - update_raw's per-pixel noise, which leaves the run-length counting nothing to merge, and the maps shifted
+by (3, 2) pixels with a band ignored, piecewise constant as annotations are - in ONE command and alternating within every repeat:
+  (xvi) one image_areas call (checks, the ground truths laid gapless, the table copy, one launch), ops.seg_image_areas alone on the
+        same buffers with the table made beforehand, and the only device means there was before: one ops.seg_areas /
+        seg_areas_wide call per picture into the rows of a (B, 3, C) tensor; the three results compared; then one
+        SegEvaluator.update_raw (the path without the feature: the yardstick) and one update_raw of an evaluator with
+        per_image=True.  Medians, min-max, the clock held, bytes per second of the launch alone against the HBM peak, and
+        whether the single call is slower than the loop outside the two ways' own min-max.  The output file keeps whatever
+        stands above the line "# ---- tools/bench_seg.py --per-image" (the kernels' resources, the tile measurements).
 usage: python tools/bench_seg.py [--eval | --raw | --aug | --sweep | --refine | --objects | --boundary | --wide | --merge | --confusion |
-                                  --wide-post | --snap]
+                                  --wide-post | --snap | --per-image]
                                  [reps=7] [out=profiles/seg_infer.txt | seg_eval.txt | seg_frontend.txt | seg_aug.txt | seg_sweep.txt |
                                   seg_refine.txt | seg_objects.txt | seg_boundary.txt | seg_wide.txt | seg_merge.txt | seg_confusion.txt |
-                                  seg_wide_post.txt | seg_snap.txt]"""
+                                  seg_wide_post.txt | seg_snap.txt | seg_per_image.txt]"""
 import os
 import statistics
 import sys
@@ -140,13 +152,15 @@ CONFUSION = "--confusion" in sys.argv[1:]
 WIDE_POST, WIDE_POST_CHILD = ("--wide-post" in sys.argv[1:]), ("--wide-post-child" in sys.argv[1:])
 WIDE_POST_MARK = "# ---- tools/bench_seg.py --wide-post"
 SNAP, SNAP_CHILD = ("--snap" in sys.argv[1:]), ("--snap-child" in sys.argv[1:])
+PER_IMAGE = "--per-image" in sys.argv[1:]
+PER_IMAGE_MARK = "# ---- tools/bench_seg.py --per-image"
 ARGV = [a for a in sys.argv[1:] if a not in ("--eval", "--raw", "--raw-child", "--aug", "--aug-child", "--sweep", "--sweep-child",
                                              "--refine", "--refine-child", "--objects", "--objects-child", "--boundary",
                                              "--boundary-child", "--wide", "--merge", "--merge-child", "--confusion", "--wide-post",
-                                             "--wide-post-child", "--snap", "--snap-child")]
+                                             "--wide-post-child", "--snap", "--snap-child", "--per-image")]
 REPS = int(ARGV[0]) if len(ARGV) > 0 else 7
 OUT = ARGV[1] if len(ARGV) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "seg_snap.txt" if SNAP else "seg_wide_post.txt" if WIDE_POST else "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
+                                                 "seg_per_image.txt" if PER_IMAGE else "seg_snap.txt" if SNAP else "seg_wide_post.txt" if WIDE_POST else "seg_confusion.txt" if CONFUSION else "seg_merge.txt" if MERGE else "seg_wide.txt" if WIDE else "seg_boundary.txt" if BOUNDARY else "seg_objects.txt" if OBJECTS else "seg_refine.txt" if REFINE else "seg_sweep.txt" if SWEEP else "seg_aug.txt" if AUG else "seg_frontend.txt" if RAW else
                                                  "seg_eval.txt" if EVAL else "seg_infer.txt")
 HBM_PEAK = 8.0e12   # bytes / s, MI355X specification
 lines = []
@@ -1541,14 +1555,126 @@ def snap_child(model, text):
     torch.cuda.synchronize()
 
 
+def per_image_case(model, text, n_images=64):
+    """(xvi) image_areas against one seg_areas call per picture, and update_raw with and without per_image=True."""
+    from segclip_amd.segmentation import SegEvaluator, _Maps, image_areas
+    seg, tf, raws, gts, maps = objects_maps(model, text, n_images)
+    batch = _Maps.of(maps)   # update_raw's label buffer: views, every map at a multiple of 4
+    assert batch.flat.data_ptr() == min(m.data_ptr() for m in maps), "the maps are not read where they lie"
+    pixels = sum(h * w for h, w in batch.sizes)
+    shifted = []
+    for m in maps:   # the annotation of a prediction: the map moved by (3, 2), a band ignored
+        t = torch.roll(m, (3, 2), (0, 1)).clone()
+        t[:4] = 255
+        shifted.append(t)
+    wide_flat = batch.flat.to(torch.int16)
+    wide_maps = _Maps(wide_flat, batch.offs, batch.sizes).views()
+    verdicts = []
+    for dtype, classes in ((torch.uint8, (21, 151)), (torch.int16, (21, 151, 460, 848))):
+        wide = dtype == torch.int16
+        preds, flat = (wide_maps, wide_flat) if wide else (maps, batch.flat)
+        ignore = 65535 if wide else 255
+        areas_fn = ops.seg_areas_wide if wide else ops.seg_areas
+        for truth_name, truth in (("noise truth", gts), ("shifted maps", shifted)):
+            # 255 -> 65535: the ignored band stays ignored in the int16 copies
+            truth = [torch.where(t == 255, -1, t.to(torch.int16)).to(torch.int16) for t in truth] if wide else truth
+            gt_flat, gt_offs = _Maps.gapless_of(truth)
+            table, n_blocks = ops.seg_image_areas_table(batch.offs, gt_offs, [h * w for h, w in batch.sizes], "cuda")
+            for C in classes:
+                name = f"(xvi) per-image {'int16' if wide else 'uint8'} C={C:4d} {truth_name:12s}"
+                rows = torch.zeros(n_images, 3, C, dtype=torch.int64, device="cuda")
+                alone = torch.zeros_like(rows)
+                kept = {}
+
+                def one_call():
+                    kept["rows"] = image_areas(preds, truth, C, ignore)
+
+                def per_picture():
+                    for i, (p, t) in enumerate(zip(preds, truth)):
+                        areas_fn(p.reshape(-1), t.reshape(-1), C, ignore, areas=rows[i])
+
+                ways = [("segmentation.image_areas: one call, one launch", one_call, 10),
+                        ("ops.seg_image_areas alone, table and flat truths made beforehand",
+                         lambda: ops.seg_image_areas(flat, gt_flat, table, n_blocks, C, ignore, out=alone), 10),
+                        (f"one {'ops.seg_areas_wide' if wide else 'ops.seg_areas'} call per picture ({n_images} launches)", per_picture, 3)]
+                with torch.no_grad():
+                    for _, fn, _ in ways:
+                        fn()
+                    torch.cuda.synchronize()
+                    say(f"{name}: the rows of the one call equal those of the per-picture loop: {bool(torch.equal(kept['rows'], rows))}; "
+                        f"of the launch alone: {bool(torch.equal(alone, rows))}; {int((rows[:, 2] > 0).sum())} (picture, class) pairs labelled")
+                    for _ in range(2):
+                        for _, fn, _ in ways:
+                            fn()
+                    torch.cuda.synchronize()
+                    ts = [[] for _ in ways]
+                    sampler = ClockSampler().start()
+                    for _ in range(REPS):   # alternating: every repeat times the ways one after the other
+                        for i, (_, fn, inner) in enumerate(ways):
+                            t0 = time.perf_counter()
+                            for _ in range(inner):
+                                fn()
+                            torch.cuda.synchronize()
+                            ts[i].append((time.perf_counter() - t0) / inner)
+                    clk = sampler.stop()
+                meds = [statistics.median(t) for t in ts]
+                nbytes = 2 * pixels * flat.element_size()
+                say(f"{name}: {n_images} pictures, {pixels} pixels, {n_blocks} workgroups, {nbytes / 2**20:.1f} MiB read per call; clock {clk}")
+                for (what, _, inner), t, med in zip(ways, ts, meds):
+                    say(f"{name}: {what:70s} {med * 1e6:10.1f} us (min {min(t) * 1e6:.1f}, max {max(t) * 1e6:.1f}; {REPS} x {inner} calls)  "
+                        f"{nbytes / med / 1e9:8.1f} GB/s = {nbytes / med / HBM_PEAK:6.4f} of the HBM peak   {med / meds[2]:6.3f}x the loop")
+                slower = min(ts[0]) > max(ts[2])
+                verdicts.append(slower)
+                say(f"{name}: loop / one call {meds[2] / meds[0]:.2f}, loop / launch alone {meds[2] / meds[1]:.2f}; the one call is "
+                    f"{'SLOWER than the loop outside both min-max ranges' if slower else 'not slower than the loop outside the runs min-max'}")
+    say(f"(xvi) per-image: the one call slower than the per-picture loop outside the min-max ranges in {sum(verdicts)} of {len(verdicts)} cases")
+    # the evaluator: update_raw without the feature (the yardstick) and with it
+    name = f"(xvi) per-image update_raw {n_images} mixed sizes"
+    ev0, ev1 = SegEvaluator(seg), SegEvaluator(seg, per_image=True)
+
+    def with_rows():
+        ev1.reset()   # the rows of earlier calls are not kept: the same work every call
+        ev1.update_raw(raws, gts, tf)
+
+    ways = [("SegEvaluator.update_raw", lambda: ev0.update_raw(raws, gts, tf), 2),
+            ("SegEvaluator(per_image=True).update_raw", with_rows, 2)]
+    with torch.no_grad():
+        for _ in range(3):
+            for _, fn, _ in ways:
+                fn()
+        torch.cuda.synchronize()
+        ev0.reset()
+        ev0.update_raw(raws, gts, tf)
+        say(f"{name}: the rows sum to the areas of the evaluator without them: {bool(torch.equal(ev1.image_areas.sum(0), ev0.areas))}; "
+            f"rows {tuple(ev1.image_areas.shape)}")
+        ts = [[] for _ in ways]
+        sampler = ClockSampler().start()
+        for _ in range(REPS):
+            for i, (_, fn, inner) in enumerate(ways):
+                t0 = time.perf_counter()
+                for _ in range(inner):
+                    fn()
+                torch.cuda.synchronize()
+                ts[i].append((time.perf_counter() - t0) / inner)
+        clk = sampler.stop()
+    meds = [statistics.median(t) for t in ts]
+    for (what, _, inner), t, med in zip(ways, ts, meds):
+        say(f"{name}: {what:42s} {med * 1e3:8.3f} ms (min {min(t) * 1e3:.3f}, max {max(t) * 1e3:.3f}; {REPS} x {inner} calls)   clock {clk}")
+    say(f"{name}: per_image=True adds {(meds[1] - meds[0]) * 1e3:+.3f} ms = {(meds[1] / meds[0] - 1) * 100:+.2f} %; update_raw's own "
+        f"max - min is {(max(ts[0]) - min(ts[0])) * 1e3:.3f} ms; peak allocation of one call: without {peak_of(ways[0][1]) / 2**20:.1f} MiB, "
+        f"with {peak_of(ways[1][1]) / 2**20:.1f} MiB")
+
+
 def write_out():
-    """the lines of this run into OUT; --wide-post keeps what stands above its mark (the kernels' resource tables)"""
+    """the lines of this run into OUT; --wide-post and --per-image keep what stands above their mark (the kernels' resource
+    tables, the tile measurements)"""
     head = []
-    if WIDE_POST:
+    mark = WIDE_POST_MARK if WIDE_POST else PER_IMAGE_MARK if PER_IMAGE else None
+    if mark is not None:
         if os.path.exists(OUT):
             old = open(OUT).read().split("\n")
-            head = old[:old.index(WIDE_POST_MARK)] if WIDE_POST_MARK in old else old
-        head.append(WIDE_POST_MARK)
+            head = old[:old.index(mark)] if mark in old else old
+        head.append(mark)
     with open(OUT, "w") as f:
         f.write("\n".join(head + lines) + "\n")
 
@@ -1588,7 +1714,9 @@ if __name__ == "__main__":
     if SNAP_CHILD:
         snap_child(model, text)
         sys.exit(0)
-    if SNAP:
+    if PER_IMAGE:
+        per_image_case(model, text)
+    elif SNAP:
         snap_case(model, text)
     elif WIDE_POST:
         wide_post_case(model, text)
